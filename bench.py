@@ -7,8 +7,8 @@ One step = one video frame: upload of frame k+1 and its mask (copy stream, frame
 optical flow of the frame pair (k, k+1), then IteratedMSKalmanFilter.compute on frame k+1 with
 that flow (predict, mask projection, iterated measurement update), flow handed over in
 device memory.  Workload at every N: BASELINE.json config "1024x1024 video, ~200-vertex
-mesh" -- a textured disk advected by an analytic field, synthetic, one independent video
-per GPU (weak scaling: the EKF is a recurrence over the frames of one video, videos are
+mesh" -- a textured disk advected by an analytic field, synthetic, shown forth and back over the frames
+in which the disk's circle is inside the picture (BenchVideo), one independent video per GPU (weak scaling: the EKF is a recurrence over the frames of one video, videos are
 the shardable unit; the only collective is the final gather of the tracked states).
 
 Prints ONE JSON line (rank 0).  The frames and masks of the timed region are read from host memory and
@@ -27,6 +27,14 @@ full flow series inside the timed region.
 has nothing to hide behind; `value` includes it).  `cpu_baseline` is the oracle (C/OpenMP restatement of
 the reference's CPU path) timed on this host: whole Brox pairs and one whole KFState.update at the
 bench's size.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step as
+DIR/<name>.npy (float32 / float64, at most 64 MB in all; a larger array is cut to a fixed, seeded sample of
+its elements).  Video workload: `state_X` (the gathered tracked states, one row per video), `ekf_error` (the
+error tuple compute() returned for the last frame, one row per video of rank 0) and `flow_u` / `flow_v` (the
+flow of the last frame pair of rank 0's first video).  Flowbatch workload: `flow` (the gathered flows).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output
+(`bench_outputs/` is the directory name .gitignore keeps out of the tree).
 """
 import argparse
 import json
@@ -46,6 +54,24 @@ HBM_PEAK_GBPS = 8000.0                    # MI355X_MICROARCH.md: 8.0 TB/s spec
 SOR_PMC = os.path.join(ROOT, "profiles", "r04_sor_pmc.json")
 SOR_LIMITED_BY = ("tile load phase (seven coefficient planes per tile through the L2 -> CU path) not overlapped with the "
                   "sweeps of the same workgroup, then vector issue and barrier waits: profiles/r03_sor_sq_counters.csv")
+
+DUMP_LIMIT_BYTES = 64 << 20               # --dump-outputs: all arrays together
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: [(name, ndarray)] -> out_dir/<name>.npy, float64 kept, everything else as float32.  The budget is split
+    evenly between the arrays; an array over its share is replaced by a fixed sample of its elements (seeded by
+    nothing but its size, so two runs with the same arguments sample the same elements)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays:
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def kernel_revision():
@@ -119,6 +145,54 @@ def make_video(n, frames, seed):
     from hydra_mi import synth
     video, masks, centre, radius = synth.disk_video(n, frames, "translate_leftup", seed)
     return video, masks, centre, radius
+
+
+def whole_disk_frames(n):
+    """How many frames of make_video(n, ...) keep the disk's circle (centre (n-1)/2, radius 0.33 n) inside the picture:
+    it drifts towards the upper left (~2.56 px per frame at 1024^2; 68 frames from n = 256 up), and beyond that the
+    tracked object leaves the picture (after ~330 frames it is gone and the filter has nothing to measure)."""
+    from hydra_mi import synth
+    vx, vy = synth.scaled_field("translate_leftup", n)(0.0, 0.0)
+    c, r = (n - 1) / 2.0, 0.33 * n                          # synth.disk_video's centre and radius
+    return int(np.floor((c - r) / max(abs(vx), abs(vy)))) + 1
+
+
+def shown_frame(f, period):
+    """Frame of a `period`-frame video shown as frame f of one that runs forth, holds its last frame one step, runs
+    back, holds its first frame one step, and so on (the hold halves the change of velocity at a turn)."""
+    if period < 2:
+        return 0
+    m = f % (2 * period)
+    return m if m < period else 2 * period - 1 - m
+
+
+class BenchVideo:
+    """The bench's video of any length (a frame source of hydra_mi.pipeline.FlowEKFPipeline): the first
+    whole_disk_frames(n) frames of make_video, then the same frames backwards, forwards again and so on (shown_frame).
+    Consecutive frames are equal or consecutive frames of make_video, and a run of up to whole_disk_frames(n) frames
+    is make_video's own video.  (The filter follows the turns for about two thousand frames at 1024^2.)"""
+
+    def __init__(self, n, frames, seed):
+        from hydra_mi.pipeline import ArraySource
+        self.F = int(frames)
+        video, masks, self.centre, self.radius = make_video(n, min(self.F, whole_disk_frames(n)), seed)
+        self.base = ArraySource(video, masks)
+        self.masks = self.base.masks
+
+    def __len__(self):
+        return self.F
+
+    @property
+    def shape(self):
+        return self.base.shape
+
+    def frame_at(self, f):
+        if not 0 <= f < self.F:
+            raise IndexError("frame %d of a %d-frame video" % (f, self.F))
+        return self.base.frame_at(shown_frame(f, len(self.base)))
+
+    def __getitem__(self, f):
+        return self.frame_at(f)[0]
 
 
 def cpu_baseline(n, video, masks, dm, iters_per_frame, budget_s=30.0):
@@ -300,6 +374,8 @@ def flowbatch(args, rank, world, dev, coll_dev):
         elapsed = float(t.item())
     if rank == 0:
         assert gathered.shape[0] == total
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [("flow", gathered.cpu().numpy())])
         print(json.dumps({
             "metric": "frame pairs/sec (Brox flow) at %d^2" % n, "value": total * args.steps / elapsed,
             "unit": "pairs/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -346,7 +422,11 @@ def main():
     ap.add_argument("--stub-flow", action="store_true",
                     help="flowbatch only: a CPU stand-in for the flow, to rehearse sharding + gather without a GPU "
                          "(with --backend gloo); the line it prints is marked stub_flow and is not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -413,13 +493,15 @@ def main():
 
         def __init__(self, seed):
             frames = K + Wm + 1
-            self.video, self.masks, centre, radius = make_video(n, frames, seed=seed)
+            self.video = BenchVideo(n, frames, seed)
+            self.masks = self.video.masks
+            centre, radius = self.video.centre, self.video.radius
             self.dm = mesh.disk_mesh(centre[0], centre[1], radius - 1.0, args.h0 * n)
             self.kf = kalman.IteratedMSKalmanFilter(self.dm, self.video[0], np.zeros((n, n, 2), np.float32), True, device=dev)
             extra = {} if args.cu_reserve is None else {"cu_reserve": args.cu_reserve}
             if args.one_flow_handle or args.split_start:     # (split_start is an experiment of the one-series mode)
                 extra["concurrent_series"] = False
-            self.pipe = FlowEKFPipeline(self.kf, self.video, self.masks, flow_batch=B, device=dev, resident=args.resident, **extra)
+            self.pipe = FlowEKFPipeline(self.kf, self.video, flow_batch=B, device=dev, resident=args.resident, **extra)
             self.bf = self.pipe.bf
             if args.split_start:
                 self.pipe.split_start = True
@@ -445,7 +527,10 @@ def main():
             self.kf.predtime = self.kf.updatetime = self.kf.projecttime = 0.0
 
         def timed(self):
-            self.pipe.run(Wm, Wm + K)
+            self.pipe.run(Wm, Wm + K, on_frame=self.keep_error)
+
+        def keep_error(self, k, e):
+            self.last_error = e
 
         def flow_sync(self):
             self.pipe.flow_sync()
@@ -514,6 +599,12 @@ def run_video(args, tracks, rank, world, dev, coll_dev, info, V, K, Wm, B, n):
     elapsed = t_end - t0
     for tr in tracks:
         tr.flow_sync()
+    if args.dump_outputs and rank == 0:   # (before the series after the clock overwrite the flow planes)
+        last_flow = tracks[0].pipe.flow_host(Wm + K - 1)
+        dump_outputs(args.dump_outputs, [
+            ("state_X", gathered.cpu().numpy()),
+            ("ekf_error", np.array([tr.last_error[:4] for tr in tracks], np.float64)),
+            ("flow_u", last_flow[:, :, 0]), ("flow_v", last_flow[:, :, 1])])
     prof_pairs, prof_where = tracks[0].pipe.profiled_pairs, "of the timed region"
     if prof_pairs == 0:                 # a timed region too short for a series of B pairs: one more, after the clock
         tr = tracks[0]

@@ -288,3 +288,40 @@ def test_chained_state_path_equals_the_three_calls(hm):
     failed = _short_track(hm, tune=[("newton_fail", 1)])
     host = _short_track(hm, attrs=[("newton_on_device", False)])
     _same_track(failed, host, upto=6)
+
+
+def test_bench_dumps_the_last_step_of_the_video_workload(hm, tmp_path):
+    """`bench.py --dump-outputs DIR` on the headline workload (flow + EKF per frame) at a small size: --steps sets the
+    timed frames, the dump holds the tracked state, the last frame's error tuple and the flow of the last pair, and
+    that flow is the one BroxOpticalFlow.calc gives for the same two frames of the bench's video.  The run is longer
+    than the frames in which the disk stays in the picture: the video turns back twice (bench.BenchVideo) and the
+    filter follows it."""
+    import json
+    import subprocess
+    import bench
+    from hydra_mi import brox
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    n, K, Wm = 256, 150, 1
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(Wm), "--size", str(n),
+           "--no-cpu-baseline", "--dump-outputs", str(out_dir)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == K and out["config"]["frames_per_gpu"] == K
+    assert abs(out["ms_per_step"] - 1e3 / out["value"]) <= 1e-6 * out["ms_per_step"]
+    assert sorted(os.listdir(str(out_dir))) == ["ekf_error.npy", "flow_u.npy", "flow_v.npy", "state_X.npy"]
+    X, err = np.load(str(out_dir / "state_X.npy")), np.load(str(out_dir / "ekf_error.npy"))
+    u, v = np.load(str(out_dir / "flow_u.npy")), np.load(str(out_dir / "flow_v.npy"))
+    assert X.dtype == np.float64 and X.shape[0] == 1 and X.shape[1] % 4 == 0 and np.isfinite(X).all()
+    # the tracked vertices (x, y interleaved, then the velocities) are still on the disk of the last frame
+    N = X.shape[1] // 4
+    c = (n - 1) / 2.0 - bench.shown_frame(Wm + K, bench.whole_disk_frames(n)) * 1.5 * n / 600.0
+    dist = np.hypot(X[0, 0:2 * N:2] - c, X[0, 1:2 * N:2] - c)
+    assert dist.max() <= 0.33 * n + 4.0
+    assert err.dtype == np.float64 and err.shape == (1, 4) and np.isfinite(err).all()
+    assert u.dtype == np.float32 and u.shape == (n, n) and v.shape == (n, n)
+    video = bench.BenchVideo(n, K + Wm + 1, 0)
+    assert K + Wm + 1 > 2 * bench.whole_disk_frames(n)
+    ru, rv = brox.BroxOpticalFlow(n, n).calc(video[Wm + K - 1], video[Wm + K])
+    assert np.array_equal(u, ru) and np.array_equal(v, rv)

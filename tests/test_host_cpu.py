@@ -605,6 +605,62 @@ def test_bench_starts_its_own_ranks_or_refuses(hm):
     assert one.returncode == 0 and json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][0])["n_gpus"] == 1
 
 
+def test_bench_dump_outputs_of_the_last_step(hm, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed path computed in its last step (flowbatch: the gathered flow
+    planes) as DIR/<name>.npy, the same from run to run with the same arguments; --steps below 1 is refused."""
+    import json
+    import subprocess
+    from hydra_mi import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "1"
+    n, P = 32, 3
+    flows = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload",
+               "flowbatch", "--backend", "gloo", "--stub-flow", "--size", str(n), "--pairs-per-gpu", str(P),
+               "--dump-outputs", str(tmp_path / d)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert sorted(os.listdir(str(tmp_path / d))) == ["flow.npy"]
+        flows.append(np.load(str(tmp_path / d / "flow.npy")))
+    assert flows[0].dtype == np.float32 and flows[0].shape == (P, 2, n, n)
+    assert np.array_equal(flows[0], flows[1])
+    for i in range(P):                                 # the stand-in's flow of pair i (seed i): f1 - f0, f0 + f1
+        f0, f1 = (a.astype(np.float32) for a in synth.warp_pair(n, "translate_leftup_stretch", i)[:2])
+        assert np.array_equal(flows[0][i, 0], f1 - f0) and np.array_equal(flows[0][i, 1], f0 + f1)
+    bad = subprocess.run(cmd[:5] + ["0"] + cmd[6:], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+    assert bad.returncode != 0 and "--steps must be at least 1" in bad.stderr
+
+
+def test_bench_video_turns_back_before_the_disk_leaves(hm):
+    """bench.BenchVideo: any number of frames, made of the frames of bench.make_video in which the disk's circle is
+    inside the picture, forth and back with the end frames held one step; consecutive frames are equal or consecutive
+    frames of make_video, and a video no longer than that is make_video's own."""
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 128
+    P = bench.whole_disk_frames(n)
+    assert bench.whole_disk_frames(1024) == 68        # the default run (64 + 2 steps, 67 frames) never turns
+    v = bench.BenchVideo(n, 3 * P, 0)
+    assert len(v) == 3 * P and v.shape == (n, n) and len(v.base) == P
+    idx = [bench.shown_frame(f, P) for f in range(3 * P)]
+    assert idx[:P] == list(range(P)) and idx[P:2 * P] == list(range(P - 1, -1, -1)) and idx[2 * P:] == list(range(P))
+    assert all(abs(a - b) <= 1 for a, b in zip(idx, idx[1:]))
+    for f in (0, P - 1, P, 2 * P - 1, 3 * P - 1):
+        fr, mk, ob = v.frame_at(f)
+        assert np.array_equal(fr, v.base.video[idx[f]]) and np.array_equal(mk, v.masks[idx[f]]) and ob is None
+        assert np.array_equal(v[f], fr)
+    with pytest.raises(IndexError):
+        v.frame_at(3 * P)
+    short, masks = bench.make_video(n, 20, 0)[:2]
+    w = bench.BenchVideo(n, 20, 0)
+    assert np.array_equal(w.base.video, short) and np.array_equal(w.masks, masks)
+    # the last frame before the turn: the circle still inside the picture
+    c = (n - 1) / 2.0 - (P - 1) * 1.5 * n / 600.0
+    assert c - 0.33 * n >= 0.0
+
 def test_newton_worker_equals_synchronous_call(hm):
     """hm_ms_newton_start / _finish (the next frame's state prediction on a host thread, include/hydra_mi.h) give
     the numbers and the iteration count of hm_ms_newton; a worker takes one job at a time and can be reused."""
