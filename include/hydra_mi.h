@@ -53,6 +53,8 @@ int hm_copy_stream_sync(int device, void *stream);
 int hm_host_alloc(uint64_t bytes, void **out);
 int hm_host_free(void *ptr);
 int hm_dev_upload_async(int device, void *dst, const void *src, uint64_t bytes, void *stream);
+/* ... and back: device -> page-locked host memory on the caller's copy stream (the video of the pipeline) */
+int hm_dev_download_async(int device, void *dst, const void *src, uint64_t bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * Brox optical flow.  Replaces cv::cuda::BroxOpticalFlow as used by
@@ -366,6 +368,57 @@ int hm_chain_states(hm_ctx_t h, double *predicted, double *projected, int *newto
 int hm_ctx_tune(hm_ctx_t h, const char *key, int value);
 int hm_ctx_sync(hm_ctx_t h);
 void *hm_ctx_stream(hm_ctx_t h);
+
+/* ------------------------------------------------------------------------
+ * Views of the tracker (reference renderer.py:436-475 screenshot, :595-628 draw,
+ * :344-373 the wireframe; kalman.py:638-674 plotforces).  Every view is H x W x 3
+ * uint8, B, G, R, rows top to bottom, rendered at the state X (4N doubles) on the
+ * handle's stream with targets of its own: a view changes nothing a later
+ * measurement, update or chained prediction reads.
+ *   which  0 raw      the gray render in all three channels
+ *          1 overlay  R = the observed frame in place (hm_set_observation*), G = the render,
+ *                     B = the wireframe
+ *          2 texture  raw plus the wireframe
+ *          3 mask     R = 255 inside the mesh, G = label / 256, B = label % 256 of the palette
+ *                     (`palette`: one label per triangle, -1 or NULL: 255, 255), plus the wireframe
+ *          4 flowx, 5 flowy  the rendered flow plane, floor(255 (p - min) / (max - min)) in f64
+ *                     (0 where max == min), in all three channels
+ * The wireframe: the three edges of every triangle (interior edges twice), end points rint(vertex),
+ * pixel i = 0..n, n = max(|dx|, |dy|): x0 + floor((2 i dx + n) / (2 n)); B = min(255, B + 128 count).
+ * Segments with an end point beyond +-2^20 px are not drawn.
+ * hm_view_dev writes into device memory d_bgr and does not wait; `stream` (may be NULL) waits for
+ * the view on the device, so a copy queued there reads it whole.  The observed frame is read when
+ * the view runs: keep it in place until then.
+ * hm_view_forces: the overlay with every channel halved, then the arrows of plotforces in four layers,
+ * each over the one before: orig -> pred white, pred -> pred + 10 tv (255, 0, 0), + 10 fv (0, 255, 0),
+ * + 10 mv (0, 0, 255) (B, G, R); orig, pred, tv, fv, mv: the 2N vertex coordinates.  End points are
+ * truncated as C int() does; the head is two segments from the tip at +-45 degrees, 0.1 of the shaft:
+ * tip + rint(K (dx - dy), K (dy + dx)) and tip + rint(K (dx + dy), K (dy - dx)), (dx, dy) = start - tip,
+ * K = 0.1 sqrt(1/2).  Not the reference's: no 2x upscale, thickness 1, no legend text. */
+int hm_view(hm_ctx_t h, const double *X, int which, const int32_t *palette, uint8_t *bgr);
+int hm_view_dev(hm_ctx_t h, const double *X, int which, const int32_t *palette, void *d_bgr, void *stream);
+int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, const double *pred, const double *tv,
+                   const double *fv, const double *mv, uint8_t *bgr);
+
+/* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
+ * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
+ * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the
+ * 55-entry Middlebury colour code at flow / 15 px, interpolated in f32, saturation rad (x 0.75 past
+ * 15 px), truncated to uint8; 0 for a non-finite flow.  on_device 0: host arrays, synchronous;
+ * 1: device arrays, queued on `stream`. */
+int hm_flow_preview(int device, int n, int W, int H, int channels, const uint8_t *frames, const float *fx,
+                    const float *fy, uint8_t *out, int on_device, void *stream);
+
+/* The video container (reference src/optical_flow_ext.cpp:351-358 cv::VideoWriter at 20 frames/s;
+ * run_kalmanfilter.py:43-44 the output video): uncompressed 24-bit AVI, one 'DIB ' stream, rows
+ * bottom-up padded to 4 bytes, 'idx1' for the first RIFF; past riff_limit bytes (0: 1 GiB) the file
+ * goes on in OpenDML 'AVIX' RIFFs, every RIFF indexed by an 'ix00' chunk named in the 'indx' super
+ * index, the total frame count in 'odml'/'dmlh'.  Frames are H x W x 3 B G R, rows top to bottom.
+ * Host only; close writes the indices and frees the handle. */
+typedef struct hm_avi *hm_avi_t;
+int hm_avi_open(const char *path, int W, int H, int fps, uint64_t riff_limit, hm_avi_t *out);
+int hm_avi_write(hm_avi_t avi, const uint8_t *bgr);
+int hm_avi_close(hm_avi_t avi);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,7 @@ SIGNATURES = {
     "hm_host_alloc": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(c_vp)]),
     "hm_host_free": (ctypes.c_int, [c_vp]),
     "hm_dev_upload_async": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, ctypes.c_uint64, c_vp]),
+    "hm_dev_download_async": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, ctypes.c_uint64, c_vp]),
     "hm_brox_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(c_vp)]),
@@ -116,6 +117,15 @@ SIGNATURES = {
     "hm_ctx_tune": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_int]),
     "hm_ctx_sync": (ctypes.c_int, [c_vp]),
     "hm_ctx_stream": (c_vp, [c_vp]),
+    "hm_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "hm_view_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "hm_view_forces": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hm_flow_preview": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                       c_vp, c_vp, ctypes.c_int, c_vp]),
+    "hm_avi_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                   ctypes.POINTER(c_vp)]),
+    "hm_avi_write": (ctypes.c_int, [c_vp, c_vp]),
+    "hm_avi_close": (ctypes.c_int, [c_vp]),
 }
 
 _lib = None

@@ -132,6 +132,14 @@ extern "C" int hm_dev_upload_async(int device, void *dst, const void *src, uint6
     return HM_OK;
 }
 
+extern "C" int hm_dev_download_async(int device, void *dst, const void *src, uint64_t bytes, void *stream)
+{
+    HM_ARG(dst && src && stream, "hm_dev_download_async: NULL pointer");
+    HM_HIP(hipSetDevice(device));
+    HM_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return HM_OK;
+}
+
 // ---- geometry -----------------------------------------------------------------------
 static Geo make_geo(int w, int h)
 {

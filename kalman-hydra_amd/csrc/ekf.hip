@@ -7,6 +7,7 @@
 #include "chol_flow_kernels.h"
 #include "project_kernels.h"
 #include "predict_kernels.h"
+#include "view_kernels.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -230,7 +231,15 @@ struct hm_ctx {
     bool outline_ready = false;      // the outline of the resident mask (o_ym) has been queued on the second stream
     const uint8_t *prepared_mask = nullptr;   // hm_prepare_mask: the outline in the buffers is that of this mask (device memory)
     hipEvent_t ev_outline = nullptr; // ... recorded behind every outline queued on the second stream
-    hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)
+    hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)    // hm_view / hm_view_dev / hm_view_forces: targets of their own, allocated on first use -- a view touches nothing the
+    // filter reads (its render, triangle setups, state copy and wireframe counts are all here)
+    Targets V = {nullptr, nullptr, nullptr, nullptr};
+    TriSetup *d_vsetup = nullptr;
+    int *d_vids = nullptr, *d_vlab = nullptr;
+    unsigned *d_vwire = nullptr, *d_vmm = nullptr;
+    double *d_vX = nullptr, *d_vforce = nullptr;
+    uint8_t *d_vout = nullptr;
+    hipEvent_t ev_view = nullptr;
 };
 
 static int alloc_targets(Targets &t, size_t n)
@@ -398,6 +407,10 @@ static int ctx_free(hm_ctx *h)
     free_targets(h->ref);
     free_targets(h->P);
     free_targets(h->Q);
+    free_targets(h->V);
+    { void *q[] = {h->d_vsetup, h->d_vids, h->d_vlab, h->d_vwire, h->d_vmm, h->d_vX, h->d_vforce, h->d_vout};
+      for (void *x : q) if (x) (void)hipFree(x); }
+    if (h->ev_view) (void)hipEventDestroy(h->ev_view);
     { void *q[] = {h->d_n4nbr, h->d_n4nbb, h->d_n4bars, h->d_n4l0, h->d_n4X, h->d_pm_done}; for (void *x : q) if (x) (void)hipFree(x); }
     // (the streams were drained at the top: nothing writes into the page-locked blocks any more)
     if (h->pin) (void)hipHostFree(h->pin);
@@ -2418,4 +2431,178 @@ extern "C" int hm_chain_states(hm_ctx_t h, double *predicted, double *projected,
     if (newton_iterations) *newton_iterations = h->chain_its;
     if (moved) *moved = h->chain_moved;
     return HM_OK;
+}
+
+// ---- views of a context (reference renderer.py:436-475 screenshot, :595-628 draw; kalman.py:638-674 plotforces) ------
+static int view_buffers(hm_ctx *h)
+{
+    if (h->d_vX) return HM_OK;
+    const size_t n = (size_t)h->W * h->H;
+    const int rc = alloc_targets(h->V, n);
+    if (rc) return rc;
+    HM_HIP(hm_malloc((void **)&h->d_vsetup, (size_t)h->T * sizeof(TriSetup)));
+    HM_HIP(hm_malloc((void **)&h->d_vids, n * sizeof(int)));
+    HM_HIP(hm_malloc((void **)&h->d_vlab, (size_t)h->T * sizeof(int)));
+    HM_HIP(hm_malloc((void **)&h->d_vwire, n * sizeof(unsigned)));
+    HM_HIP(hm_malloc((void **)&h->d_vmm, 2 * sizeof(unsigned)));
+    HM_HIP(hm_malloc((void **)&h->d_vforce, (size_t)10 * h->N * sizeof(double)));
+    HM_HIP(hm_malloc((void **)&h->d_vout, 3 * n));
+    HM_HIP(hipEventCreateWithFlags(&h->ev_view, hipEventDisableTiming));
+    HM_HIP(hm_malloc((void **)&h->d_vX, (size_t)4 * h->N * sizeof(double)));
+    return HM_OK;
+}
+
+// Queue view `which` (VIEW_*) of state X (host) into d_out (device, W*H*3) on the handle's stream.  palette: the mask
+// view's label per triangle (NULL: -1, i.e. (255, 255, 255)).  forces (VIEW_FORCES_BASE): orig | pred | tv | fv | mv,
+// 2N doubles each, host.
+static int view_queue(hm_ctx *h, const double *X, int which, const int32_t *palette, const double *const forces[5],
+                      uint8_t *d_out, const char *who)
+{
+    HM_ARG(h && X && d_out, "%s: NULL argument", who);
+    HM_ARG(which >= VIEW_RAW && which <= VIEW_FORCES_BASE, "%s: view %d outside 0..%d", who, which, VIEW_FLOWY);
+    HM_JOIN_LAZY(h);
+    if (!h->have_tex) { hm_set_error("%s: hm_set_texture has not been called", who); return HM_ERR_STATE; }
+    if ((which == VIEW_OVERLAY || which == VIEW_FORCES_BASE) && !h->have_obs) {
+        hm_set_error("%s: the overlay shows the observed frame, and hm_set_observation has not been called", who);
+        return HM_ERR_STATE;
+    }
+    HM_HIP(hipSetDevice(h->device));
+    int rc = view_buffers(h);
+    if (rc) return rc;
+    const int n = h->W * h->H;
+    HM_HIP(hipMemcpyAsync(h->d_vX, X, (size_t)4 * h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    Mesh m = {h->W, h->H, h->N, h->T, h->d_tri, h->d_uv, h->d_tex};
+    hipLaunchKernelGGL(k_setup_all, dim3(hm_cdiv(h->T, 64)), dim3(64), 0, h->stream, m, (const double *)h->d_vX, h->d_vsetup);
+    const dim3 grid(hm_cdiv(h->W, EKF_TILE), hm_cdiv(h->H, EKF_TILE)), block(EKF_TILE, EKF_TILE);
+    if (which == VIEW_MASK) {
+        if (palette) HM_HIP(hipMemcpyAsync(h->d_vlab, palette, (size_t)h->T * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        else HM_HIP(hipMemsetAsync(h->d_vlab, 0xFF, (size_t)h->T * sizeof(int), h->stream));
+        hipLaunchKernelGGL((k_render<1>), grid, block, 0, h->stream, m, (const double *)h->d_vX, (const TriSetup *)h->d_vsetup,
+                           h->V, (const int *)h->d_vlab, h->d_vids);
+    } else {
+        hipLaunchKernelGGL((k_render<0>), grid, block, 0, h->stream, m, (const double *)h->d_vX, (const TriSetup *)h->d_vsetup,
+                           h->V, (const int *)nullptr, (int *)nullptr);
+    }
+    const bool wire = which == VIEW_TEXTURE || which == VIEW_OVERLAY || which == VIEW_MASK || which == VIEW_FORCES_BASE;
+    if (wire) {
+        HM_HIP(hipMemsetAsync(h->d_vwire, 0, (size_t)n * sizeof(unsigned), h->stream));
+        hipLaunchKernelGGL(k_view_wire, dim3(hm_cdiv(3 * h->T, 256 / VIEW_SEG_WAVE)), dim3(256), 0, h->stream,
+                           (const int *)h->d_tri, h->T, (const double *)h->d_vX, h->W, h->H, h->d_vwire);
+    }
+    ViewArgs a;
+    a.n = n; a.which = which;
+    a.acc = h->V.acc; a.cnt = h->V.cnt; a.ids = h->d_vids;
+    a.flow = which == VIEW_FLOWY ? h->V.fy : h->V.fx;
+    a.mm = h->d_vmm;
+    a.wire = wire ? h->d_vwire : nullptr;
+    a.obs = h->o_yim;
+    a.out = d_out;
+    if (which == VIEW_FLOWX || which == VIEW_FLOWY) {
+        HM_HIP(hipMemsetAsync(h->d_vmm, 0xFF, sizeof(unsigned), h->stream));
+        HM_HIP(hipMemsetAsync(h->d_vmm + 1, 0, sizeof(unsigned), h->stream));
+        hipLaunchKernelGGL(k_view_minmax, dim3(std::min(hm_cdiv(n, 256), 256)), dim3(256), 0, h->stream, a.flow, n, h->d_vmm);
+    }
+    hipLaunchKernelGGL(k_view_compose, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, a);
+    if (which == VIEW_FORCES_BASE) {
+        const size_t n2 = (size_t)2 * h->N;
+        for (int k = 0; k < 5; k++)
+            HM_HIP(hipMemcpyAsync(h->d_vforce + k * n2, forces[k], n2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        const double *o = h->d_vforce, *p = o + n2;
+        const dim3 ag(hm_cdiv(3 * h->N, 256 / VIEW_SEG_WAVE));
+        // reference kalman.py:654-661, in its order: prediction (white), template (blue), flow (green), mask (red) force
+        hipLaunchKernelGGL(k_view_arrows, ag, dim3(256), 0, h->stream, o, p, (const double *)nullptr, 0.0, h->N, h->W, h->H,
+                           make_uchar3(255, 255, 255), d_out);
+        hipLaunchKernelGGL(k_view_arrows, ag, dim3(256), 0, h->stream, p, (const double *)nullptr, (const double *)(p + n2), 10.0,
+                           h->N, h->W, h->H, make_uchar3(255, 0, 0), d_out);
+        hipLaunchKernelGGL(k_view_arrows, ag, dim3(256), 0, h->stream, p, (const double *)nullptr, (const double *)(p + 2 * n2),
+                           10.0, h->N, h->W, h->H, make_uchar3(0, 255, 0), d_out);
+        hipLaunchKernelGGL(k_view_arrows, ag, dim3(256), 0, h->stream, p, (const double *)nullptr, (const double *)(p + 3 * n2),
+                           10.0, h->N, h->W, h->H, make_uchar3(0, 0, 255), d_out);
+    }
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+static int view_download(hm_ctx *h, uint8_t *bgr)
+{
+    HM_HIP(hipMemcpyAsync(bgr, h->d_vout, (size_t)3 * h->W * h->H, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_view(hm_ctx_t h, const double *X, int which, const int32_t *palette, uint8_t *bgr)
+{
+    HM_ARG(h && bgr, "hm_view: NULL argument");
+    HM_ARG(which >= VIEW_RAW && which <= VIEW_FLOWY, "hm_view: view %d outside 0..%d", which, VIEW_FLOWY);
+    HM_HIP(hipSetDevice(h->device));
+    int rc = view_buffers(h);
+    if (rc) return rc;
+    rc = view_queue(h, X, which, palette, nullptr, h->d_vout, "hm_view");
+    if (rc) return rc;
+    return view_download(h, bgr);
+}
+
+extern "C" int hm_view_dev(hm_ctx_t h, const double *X, int which, const int32_t *palette, void *d_bgr, void *stream)
+{
+    HM_ARG(h && d_bgr, "hm_view_dev: NULL argument");
+    HM_ARG(which >= VIEW_RAW && which <= VIEW_FLOWY, "hm_view_dev: view %d outside 0..%d", which, VIEW_FLOWY);
+    int rc = view_queue(h, X, which, palette, nullptr, (uint8_t *)d_bgr, "hm_view_dev");
+    if (rc) return rc;
+    if (stream) {
+        HM_HIP(hipEventRecord(h->ev_view, h->stream));
+        HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_view, 0));
+    }
+    return HM_OK;
+}
+
+extern "C" int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, const double *pred, const double *tv,
+                              const double *fv, const double *mv, uint8_t *bgr)
+{
+    HM_ARG(h && bgr && orig && pred && tv && fv && mv, "hm_view_forces: NULL argument");
+    HM_HIP(hipSetDevice(h->device));
+    int rc = view_buffers(h);
+    if (rc) return rc;
+    const double *f[5] = {orig, pred, tv, fv, mv};
+    rc = view_queue(h, X, VIEW_FORCES_BASE, nullptr, f, h->d_vout, "hm_view_forces");
+    if (rc) return rc;
+    return view_download(h, bgr);
+}
+
+// ---- the flow tool's preview video (reference src/optical_flow_ext.cpp:172-281, 336-389) ---------------------------
+extern "C" int hm_flow_preview(int device, int n, int W, int H, int channels, const uint8_t *frames, const float *fx,
+                               const float *fy, uint8_t *out, int on_device, void *stream)
+{
+    HM_ARG(frames && fx && fy && out, "hm_flow_preview: NULL argument");
+    HM_ARG(n >= 1 && W >= 1 && H >= 1 && (channels == 1 || channels == 3),
+           "hm_flow_preview: bad size n=%d %dx%d channels=%d", n, W, H, channels);
+    HM_HIP(hipSetDevice(device));
+    const long long px = (long long)n * W * H;
+    const dim3 grid((unsigned)((px + 255) / 256));
+    if (on_device) {
+        hipLaunchKernelGGL(k_flow_preview, grid, dim3(256), 0, (hipStream_t)stream, frames, channels, fx, fy, px, out);
+        HM_HIP(hipGetLastError());
+        return HM_OK;
+    }
+    uint8_t *d_f = nullptr, *d_o = nullptr;
+    float *d_x = nullptr, *d_y = nullptr;
+    int rc = HM_OK;
+    auto run = [&]() -> int {
+        HM_HIP(hm_malloc((void **)&d_f, (size_t)px * channels));
+        HM_HIP(hm_malloc((void **)&d_o, (size_t)px * 3));
+        HM_HIP(hm_malloc((void **)&d_x, (size_t)px * sizeof(float)));
+        HM_HIP(hm_malloc((void **)&d_y, (size_t)px * sizeof(float)));
+        HM_HIP(hipMemcpy(d_f, frames, (size_t)px * channels, hipMemcpyHostToDevice));
+        HM_HIP(hipMemcpy(d_x, fx, (size_t)px * sizeof(float), hipMemcpyHostToDevice));
+        HM_HIP(hipMemcpy(d_y, fy, (size_t)px * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_flow_preview, grid, dim3(256), 0, 0, (const uint8_t *)d_f, channels, (const float *)d_x,
+                           (const float *)d_y, px, d_o);
+        HM_HIP(hipGetLastError());
+        HM_HIP(hipMemcpy(out, d_o, (size_t)px * 3, hipMemcpyDeviceToHost));
+        return HM_OK;
+    };
+    rc = run();
+    void *ptrs[] = {d_f, d_o, d_x, d_y};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    return rc;
 }

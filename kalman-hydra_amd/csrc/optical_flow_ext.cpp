@@ -68,6 +68,14 @@ struct NpyVideo {
     }
 
     // frame k as 8-bit gray (H*W bytes)
+    // frame k as stored (gray, or B G R)
+    bool raw(int k, uint8_t *out)
+    {
+        const size_t bytes = (size_t)H * W * chans;
+        if (fseek(f, data_start + (long)((size_t)k * bytes), SEEK_SET) != 0) return false;
+        return fread(out, 1, bytes, f) == bytes;
+    }
+
     bool gray(int k, uint8_t *out, std::vector<uint8_t> &tmp)
     {
         const size_t px = (size_t)H * W;
@@ -106,7 +114,8 @@ void help(const char *me)
               << "  int inner_iterations = number of lagged non-linearity iterations (inner loop)" << std::endl
               << "  int outer_iterations = number of warping iterations (number of pyramid levels)" << std::endl
               << "  int solver_iterations = number of linear system solver iterations" << std::endl
-              << "Output: <output filename>_%03d_x.mat and _y.mat for every consecutive frame pair" << std::endl;
+              << "Output: <output filename>_%03d_x.mat and _y.mat for every consecutive frame pair" << std::endl
+              << "  (HYDRA_MI_FLOW_PREVIEW=1: also <output filename>.avi, every frame blended with its flow)" << std::endl;
 }
 
 template <typename T>
@@ -157,6 +166,18 @@ int main(int ac, char **av)
     std::vector<uint8_t> frames((size_t)(B + 1) * px), tmp;
     std::vector<float> fx((size_t)B * px), fy((size_t)B * px);
     int rc = 0;
+    // HYDRA_MI_FLOW_PREVIEW=1: <prefix>.avi, frame n = frame n + 1 as read blended with the flow of pair n (:336-389)
+    hm_avi_t preview = nullptr;
+    std::vector<uint8_t> raw, blend;
+    if (const char *e = getenv("HYDRA_MI_FLOW_PREVIEW"); e && std::string(e) == "1" && pairs > 0) {
+        if (hm_avi_open((fn_out + ".avi").c_str(), video.W, video.H, 20, 0, &preview) != HM_OK) {
+            std::cerr << "hm_avi_open failed: " << hm_last_error() << std::endl;
+            hm_brox_destroy(h);
+            return 1;
+        }
+        raw.resize((size_t)B * px * video.chans);
+        blend.resize((size_t)B * px * 3);
+    }
     for (int s = 0; s < pairs && rc == 0; s += B) {
         const int nb = pairs - s < B ? pairs - s : B;
         // frames s .. s + nb, contiguous: frame0 of pair i is frame s + i, frame1 is the one after it
@@ -178,6 +199,23 @@ int main(int ac, char **av)
                 rc = 1;
             }
         }
+        if (preview && rc == 0) {
+            for (int k = 0; k < nb && rc == 0; k++)
+                if (!video.raw(s + k + 1, raw.data() + (size_t)k * px * video.chans)) { std::cerr << "Failed to read frame " << s + k + 1 << std::endl; rc = 1; }
+            if (rc == 0 && hm_flow_preview(0, nb, video.W, video.H, video.chans, raw.data(), fx.data(), fy.data(), blend.data(), 0, nullptr) != HM_OK) {
+                std::cerr << "hm_flow_preview failed: " << hm_last_error() << std::endl;
+                rc = 1;
+            }
+            for (int k = 0; k < nb && rc == 0; k++)
+                if (hm_avi_write(preview, blend.data() + (size_t)k * px * 3) != HM_OK) {
+                    std::cerr << "hm_avi_write failed: " << hm_last_error() << std::endl;
+                    rc = 1;
+                }
+        }
+    }
+    if (preview && hm_avi_close(preview) != HM_OK && rc == 0) {
+        std::cerr << "hm_avi_close failed: " << hm_last_error() << std::endl;
+        rc = 1;
     }
     hm_brox_destroy(h);
     if (rc == 0) std::cout << "Finished." << std::endl;

@@ -537,10 +537,23 @@ class KalmanFilter:
             self.updatetime += t3 - t2
             self._say("Prediction time: %g\nProjection time: %g\nUpdate time: %g" % (t1 - t0, t2 - t1, t3 - t2))
             if imageoutput is not None:
-                self._say("imageoutput=%r ignored: screenshots are not part of this path" % (imageoutput,))
+                self.screenshots(imageoutput)
             return self.error(y_im, y_flow, y_m, want_flow=self.return_flow)
         finally:
             r.frame_in_place = False
+
+    def screenshots(self, basename):
+        """The reference's imageoutput (renderer.py:436-475, kalman.py:638-674): <basename>_<view>.png of the six views at
+        the state the update kept, and <basename>_forces.png -> the overlay."""
+        from .videoio import write_png
+        r = self.state.renderer
+        X = self.state.X
+        overlay = r.screenshot(saveall=True, basename=basename, X=X)
+        orig, pred = getattr(self, "orig_x", None), getattr(self, "pred_x", None)
+        tv, fv, mv = getattr(self, "tv", None), getattr(self, "fv", None), getattr(self, "mv", None)
+        if not any(a is None for a in (orig, pred, tv, fv, mv)):
+            write_png("%s_forces.png" % basename, r.view_forces(X, orig, pred, tv, fv, mv))
+        return overlay
 
     _chain_predict_s = None
 

@@ -43,8 +43,8 @@ def to_gray(a):
     return a
 
 
-def load_video(fn):
-    """The whole video as gray frames (frames, H, W) uint8 -- shared by run_kalmanfilter.py and
+def load_video(fn, gray=True):
+    """The whole video as gray frames (frames, H, W) uint8 (gray=False: as read, (frames, H, W[, 3]) B G R) -- shared by run_kalmanfilter.py and
     optical_flow_ext.py, so that the tracker sees the frames its flow was computed on.  Sources (no OpenCV on this
     path; reference renderer.py:745 opens anything cv2.VideoCapture can): a NumPy ``.npy`` / ``.npz`` array of shape
     (frames, H, W[, 3]), or a multi-page TIFF stack (``.tif`` / ``.tiff``, 8-bit gray or RGB pages, read with PIL)."""
@@ -67,7 +67,7 @@ def load_video(fn):
         a = np.asarray(a)
     if a.dtype != np.uint8 or a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[-1] != 3):
         raise ValueError("%s: expected an 8-bit array of shape (frames, H, W[, 3])" % fn)
-    return np.ascontiguousarray(to_gray(a))
+    return np.ascontiguousarray(to_gray(a) if gray else a)
 
 
 def threshold_mask(gray, threshold):
@@ -291,6 +291,93 @@ class FrameRing:
             self._stage = None
         for b in {id(b): b for b in (self.d_video, self.d_masks, self.d_observed)}.values():
             b.close()
+
+
+class VideoTap:
+    """The overlay video of a pipeline run (FlowEKFPipeline.run(video=...)): after every step the overlay at the state the
+    frame ended with is queued on the device (hm_view_dev, on the filter's stream, into a ring of device slots), copied
+    into page-locked memory on a copy stream of its own, and appended to the AviWriter by a writer thread.  The filter's
+    launches and the flow series never wait for the disk; only when all `slots` are still waiting to be written does the
+    next frame wait for the oldest.  close() drains the writer."""
+
+    def __init__(self, renderer, writer, device=0, slots=4):
+        import queue
+        self.r, self.writer, self.device = renderer, writer, int(device)
+        self.slots = int(slots)
+        self.n = 3 * renderer.nx * renderer.ny
+        if (writer.width, writer.height) != (renderer.nx, renderer.ny):
+            raise ValueError("a %dx%d video for %dx%d frames" % (writer.width, writer.height, renderer.nx, renderer.ny))
+        L = _lib.lib()
+        self._stream = _lib.c_vp()
+        _lib.check(L.hm_copy_stream_create(self.device, ctypes.byref(self._stream)), "hm_copy_stream_create")
+        self._pin = _lib.c_vp()
+        _lib.check(L.hm_host_alloc(self.slots * self.n, ctypes.byref(self._pin)), "hm_host_alloc")
+        self._dev = [DeviceBuffer(self.n, device) for _ in range(self.slots)]
+        self._free = threading.Semaphore(self.slots)
+        self._q = queue.Queue()
+        self._next = 0
+        self._error = None
+        self._closed = False
+        self._thread = threading.Thread(target=self._write_loop, name="hydra_mi-video", daemon=True)
+        self._thread.start()
+        _lib.register(self, 0)
+
+    def frame(self, X):
+        """Queue the overlay of state X as the next video frame."""
+        if self._error is not None:
+            raise self._error
+        self._free.acquire()
+        s = self._next % self.slots
+        self._next += 1
+        d = self._dev[s].ptr
+        self.r.view_dev(X, "overlay", d, self._stream)
+        _lib.check(_lib.lib().hm_dev_download_async(self.device, self._pin.value + s * self.n, d, self.n, self._stream),
+                   "hm_dev_download_async")
+        self._q.put(s)
+
+    def _write_loop(self):
+        L = _lib.lib()
+        while True:
+            s = self._q.get()
+            if s is None:
+                return
+            try:
+                if self._error is None:
+                    _lib.check(L.hm_copy_stream_sync(self.device, self._stream), "hm_copy_stream_sync")
+                    self.writer.write_ptr(self._pin.value + s * self.n)
+            except Exception as e:          # noqa: BLE001 -- reported by the next frame() / close()
+                self._error = e
+            finally:
+                self._free.release()
+
+    def drain(self):
+        """Wait until every frame queued so far is in the file."""
+        for _ in range(self.slots):
+            self._free.acquire()
+        for _ in range(self.slots):
+            self._free.release()
+        if self._error is not None:
+            raise self._error
+
+    def close(self):
+        if self._closed:
+            return
+        self._closed = True
+        try:
+            self._q.put(None)
+            self._thread.join()
+        finally:
+            L = _lib.lib()
+            if self._stream:
+                L.hm_copy_stream_destroy(self.device, self._stream)
+                self._stream = None
+            for b in self._dev:
+                b.close()
+            if self._pin:
+                L.hm_host_free(self._pin)
+                self._pin = None
+        if self._error is not None:
+            raise self._error
 
 
 class _Done:
@@ -726,8 +813,12 @@ class FlowEKFPipeline:
                           [(f["lo"], f["hi"]) for f in self._flying]))
         return e
 
-    def run(self, first=0, end=None, on_frame=None):
+    def run(self, first=0, end=None, on_frame=None, video=None):
         """compute() for the frames first+1 .. end; on_frame(k, error_tuple) after each.
+
+        video: a videoio.AviWriter of the frame size: after every step the overlay at the state the frame ended with
+        (Renderer.view(X, "overlay")) is appended to it, composed on the device and written by a thread of its own
+        (VideoTap); run() returns when every frame is in the file.  None: nothing is launched or allocated for it.
 
         gc_freeze (attribute, default True; the name is round 3's): the interpreter's automatic collections are switched
         off for the phase (gc.disable) and switched back on at its end if they were on -- a full collection, which the
@@ -742,15 +833,31 @@ class FlowEKFPipeline:
             gc.disable()
         try:
             self.begin(first, end)
+            tap = None
+            if video is not None:
+                tap = self._video_tap(video)
             for k in range(first, end):
                 e = self.step(k)
+                if tap is not None:
+                    tap.frame(self.kf.state.X)
                 if on_frame is not None:
                     on_frame(k, e)
                 if quiet and (k - first) % 64 == 63:
                     gc.collect(0)
+            if tap is not None:
+                tap.drain()
         finally:
             if quiet:
                 gc.enable()
+
+    def _video_tap(self, writer):
+        """the VideoTap of this writer, made on first use and kept across run() calls (closed by close())"""
+        tap = getattr(self, "_tap", None)
+        if tap is None or tap.writer is not writer:
+            if tap is not None:
+                tap.close()
+            tap = self._tap = VideoTap(self.kf.state.renderer, writer, self.device)
+        return tap
 
     def close(self):
         """Joins the helper threads of the series in flight, drains and destroys the copy stream, frees the ring, the
@@ -759,6 +866,9 @@ class FlowEKFPipeline:
             return
         self._closed = True
         try:
+            tap, self._tap = getattr(self, "_tap", None), None
+            if tap is not None:
+                tap.close()
             self.flow_sync()
         finally:
             self.ring.close()

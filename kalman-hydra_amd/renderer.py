@@ -7,8 +7,10 @@ that the reference splits between OpenGL (renderer.py:310-325) and the CUDA
 kernels of ``CUDAGL`` / ``CUDAGL_multi`` (cuda.py, cuda_multi.py).  Here both
 live in libhydra_mi.so (csrc/ekf.hip): a software rasteriser and fused
 perturb-and-reduce kernels; nothing is rendered on a CPU and there is no
-fallback.  The on-screen views, screenshots and key bindings of the reference
-canvas are visualisation and are not part of this path.
+fallback.  The views of the reference canvas (raw, overlay, texture, mask, flowx,
+flowy; renderer.py:436-475, 595-628) and its force plot are composed on the device
+as well (``view``, ``screenshot``, ``view_forces``); the on-screen canvas and its
+key bindings are not part of this build.
 
 Same method names and argument meaning as the reference:
 ``update_vertex_buffer``, ``render``, ``initjacobian``, ``jz``, ``jz_multi``,
@@ -124,6 +126,63 @@ class Renderer:
         """reference renderer.py:666-672."""
         _, fx, fy, _ = self.render()
         return fx, fy
+
+    # -- views (reference renderer.py:436-475, 595-628) --------------------------------------------
+    def _view_palette(self):
+        """the mask view's face palette: hessfacecolors[:, :, 1] (renderer.py:624-628, 453), i.e. labels_hess[:, 1];
+        -1 (255, 255) for every triangle when there is no such column"""
+        lh = self.labels_hess
+        if lh is None or np.ndim(lh) != 2 or np.shape(lh)[1] < 2:
+            return None
+        return np.ascontiguousarray(np.asarray(lh)[:, 1], np.int32)
+
+    def view(self, X=None, which="overlay"):
+        """The view `which` (raw, overlay, texture, mask, flowx, flowy) at state X (default: the vertex buffer)
+        -> (H, W, 3) uint8, B G R (hm_view).  The overlay's red channel is the observed frame in place."""
+        from .videoio import VIEWS
+        x = self._X() if X is None else np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+        if x.shape[0] != 4 * self.n:
+            raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
+        out = np.empty((self.ny, self.nx, 3), np.uint8)
+        pal = self._view_palette() if which == "mask" else None
+        _lib.check(_lib.lib().hm_view(self._h, _lib.ptr(x), VIEWS[which], _lib.ptr(pal), _lib.ptr(out)), "hm_view")
+        return out
+
+    def view_dev(self, X, which, d_out, stream=None):
+        """hm_view_dev: queue the view into device memory d_out (W*H*3 bytes); `stream` waits for it on the device."""
+        from .videoio import VIEWS
+        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+        pal = self._view_palette() if which == "mask" else None
+        _lib.check(_lib.lib().hm_view_dev(self._h, _lib.ptr(x), VIEWS[which], _lib.ptr(pal), ctypes.c_void_p(int(d_out)),
+                                          stream), "hm_view_dev")
+
+    def view_forces(self, X, orig, pred, tv, fv, mv):
+        """The force plot of reference kalman.py:638-674 at state X (hm_view_forces): the overlay halved, then the
+        arrows orig -> pred (white), pred -> pred + 10 tv / fv / mv (blue, green, red).  Vectors: state-sized or
+        2N; the first 2N entries (the vertex coordinates) are used."""
+        n2 = 2 * self.n
+        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+        f = [np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1)[:n2]) for a in (orig, pred, tv, fv, mv)]
+        if x.shape[0] != 4 * self.n or any(a.shape[0] != n2 for a in f):
+            raise ValueError("view_forces: states of 4N and vectors of at least 2N entries (N=%d)" % self.n)
+        out = np.empty((self.ny, self.nx, 3), np.uint8)
+        _lib.check(_lib.lib().hm_view_forces(self._h, _lib.ptr(x), *[_lib.ptr(a) for a in f], _lib.ptr(out)),
+                   "hm_view_forces")
+        return out
+
+    def screenshot(self, saveall=True, basename="screenshot", X=None):
+        """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask
+        at state X (default: the vertex buffer) and returns the overlay.  Unlike the reference the names carry no
+        time stamp: a second call with the same basename overwrites.  saveall=False writes the overlay alone."""
+        from .videoio import write_png
+        views = ("flowx", "flowy", "raw", "overlay", "texture", "mask") if saveall else ("overlay",)
+        overlay = None
+        for v in views:
+            img = self.view(X, v)
+            write_png("%s_%s.png" % (basename, v), img)
+            if v == "overlay":
+                overlay = img
+        return overlay
 
     # -- observation ------------------------------------------------------------------------
     def update_frame(self, y_im, y_flow, y_m):

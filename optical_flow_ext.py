@@ -8,6 +8,9 @@ Parameters and defaults as there (:453-488): alpha 0.197, gamma 50, scale_factor
 inner 10, outer 77, solver 10.  The video is a .npy / .npz array (frames, H, W[, 3]) uint8
 (no OpenCV on this path).  All pairs of the video go to the GPU as one batch per
 `HYDRA_MI_FLOW_BATCH` (default 16) pairs -- they are independent.
+With HYDRA_MI_FLOW_PREVIEW=1 it also writes <prefix>.avi (:336-389): frame n is frame n + 1 as read blended
+0.4 / 0.6 with the flow of pair n in the Middlebury colour code, saturating at 15 px (hm_flow_preview; the AVI is
+the library's, uncompressed, 20 frames/s) -- the same bytes as the native tool writes.
 """
 import os
 import sys
@@ -15,7 +18,7 @@ import sys
 import numpy as np
 
 import hydra_mi  # noqa: F401
-from hydra_mi import brox, matio, pipeline
+from hydra_mi import brox, matio, pipeline, videoio
 
 
 def main(av):
@@ -23,7 +26,8 @@ def main(av):
         print(__doc__)
         return 1
     try:                                             # BGR -> gray as cvtColor(BGR2GRAY) (:366-368)
-        a = pipeline.load_video(av[1])
+        raw = pipeline.load_video(av[1], gray=False)
+        a = np.ascontiguousarray(pipeline.to_gray(raw))
     except (OSError, ValueError) as exc:
         sys.stderr.write("Failed to open the video: %s\n" % exc)
         return 1
@@ -38,11 +42,19 @@ def main(av):
     B = max(1, int(os.environ.get("HYDRA_MI_FLOW_BATCH", "16")))
     n = a.shape[0] - 1
     bf = brox.BroxOpticalFlow(a.shape[2], a.shape[1], alpha, gamma, scale, inner, outer, solver, max_batch=min(B, max(n, 1)))
+    preview = None
+    if os.environ.get("HYDRA_MI_FLOW_PREVIEW", "") == "1":
+        preview = videoio.AviWriter(prefix + ".avi", a.shape[2], a.shape[1])
     for s in range(0, n, B):
         e = min(n, s + B)
         fx, fy = bf.calc_batch(np.ascontiguousarray(a[s:e]), np.ascontiguousarray(a[s + 1:e + 1]))
         for k in range(s, e):
             matio.write_flow(prefix, k, fx[k - s], fy[k - s])
+        if preview is not None:
+            for img in videoio.flow_preview(raw[s + 1:e + 1], fx[:e - s], fy[:e - s]):
+                preview.write(img)
+    if preview is not None:
+        preview.close()
     print("Finished.")
     return 0
 

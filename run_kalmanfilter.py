@@ -9,13 +9,19 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      flow tool (optical_flow_ext.py); if no flow files exist the flow is
                      computed in-process with the same Brox defaults, streamed to the filter on
                      the GPU (hydra_mi.pipeline.FlowEKFPipeline)
-    fn_out           output file: the tracked states of all frames (np.savez)
-    -n/--name        name for saving run images (accepted, unused: no screenshots on this path)
+    fn_out           output file: the tracked states of all frames (np.savez; a name without .npz gets it
+                     appended).  When it ends in .avi the overlay video of the run is written there as well
+                     (reference :43-44; uncompressed 24-bit AVI at 20 frames/s, hydra_mi.videoio) and the
+                     states go to <fn_out>.npz
+    -n/--name        when given: the reference's screenshots of every frame k (:89),
+                     screenshots/<name>_frame_<k>_{raw,overlay,texture,mask,flowx,flowy,forces}.png
+                     (no time stamp in the names, unlike the reference)
     -t/--threshold   threshold intensity below which is background (default 9)
     -s/--gridsize    edge length for mesh (default 22)
     -c/--cuda        whether to do the analysis on the GPU (default True; there is no CPU path)
 """
 import argparse
+import os
 import sys
 
 import numpy as np
@@ -25,6 +31,7 @@ from hydra_mi import kalman
 from hydra_mi.distmesh_dyn import DistMesh
 from hydra_mi.pipeline import FlowEKFPipeline, VideoStream
 from hydra_mi.renderer import FlowStream
+from hydra_mi.videoio import AviWriter
 
 
 def main(argv=None):
@@ -35,8 +42,8 @@ def main(argv=None):
                         help="input optic flow path")
     parser.add_argument("fn_out", default="./video/johntest_brightcontrast_short_output.npz", nargs="?",
                         help="output file (tracked states)")
-    parser.add_argument("-n", "--name", default="johntest_brightcontrast_short", nargs="?",
-                        help="name for saving run images")
+    parser.add_argument("-n", "--name", default=None, nargs="?", const="johntest_brightcontrast_short",
+                        help="name for saving run images (screenshots/<name>_frame_<k>_*.png; none without -n)")
     parser.add_argument("-t", "--threshold", default=9, type=int,
                         help="threshold intensity below which is background")
     parser.add_argument("-s", "--gridsize", default=22, type=int,
@@ -55,10 +62,16 @@ def main(argv=None):
     flowstream = FlowStream(args.flow_in)
     ret_flow, flowframe = flowstream.peek()
     states, errors = [], []
+    H, W = frame.shape[:2]
+    video = AviWriter(args.fn_out, W, H) if args.fn_out.lower().endswith(".avi") else None
+    if args.name is not None:
+        os.makedirs("screenshots", exist_ok=True)
 
-    def keep(kf, e):
+    def keep(kf, e, count):
         states.append(kf.state.X.reshape(-1).copy())
         errors.append([float(e[0]), float(e[1]), float(e[2]), float(e[3])])
+        if args.name is not None:                              # reference :89, imageoutput of compute()
+            kf.screenshots("screenshots/%s_frame_%d" % (args.name, count))
 
     if ret_flow:
         # the reference's loop (:78-89): one flow file per frame
@@ -71,7 +84,9 @@ def main(argv=None):
             if ret is False or ret_flow is False:
                 break
             print("Frame %d" % count)
-            keep(kf, kf.compute(grayframe, flowframe, m))
+            keep(kf, kf.compute(grayframe, flowframe, m), count)
+            if video is not None:
+                video.write(kf.state.renderer.view(kf.state.X, "overlay"))
     else:
         # no flow files: flow and filter in one process, the flow of the coming frames computed on the GPU
         # beside the filter (hydra_mi.pipeline; replaces the file hand-off of reference README.md:26-31)
@@ -82,9 +97,12 @@ def main(argv=None):
 
         def on_frame(k, e):
             print("Frame %d" % (k + 1))
-            keep(kf, e)
-        pipe.run(on_frame=on_frame)
+            keep(kf, e, k + 1)
+        pipe.run(on_frame=on_frame, video=video)
         pipe.close()
+    if video is not None:
+        video.close()
+        print("Overlay video: %d frames in %s" % (video.frames, args.fn_out))
     np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri)
     print("Finished: %d frames, states in %s" % (len(states), args.fn_out))
     return 0
