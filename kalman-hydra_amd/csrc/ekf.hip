@@ -126,6 +126,9 @@ struct hm_ctx {
     // the tail block of the last hm_update_run (Hz components, gains): taken by hm_update_tail, or by hm_update_run itself
     // when its caller wants them at once
     bool tail_pending = false;
+    // the tail block belongs to the last hm_update_run, which succeeded: false from the entry of every hm_update_run until it
+    // has taken, queued or zero-filled the block (an update that fails leaves nothing for hm_update_tail to hand out)
+    bool tail_valid = false;
     long long tail_ticket = 0;
     hipStream_t tail_stream = nullptr;
     const uint8_t *armed_mask = nullptr;     // hm_update_arm_mask: the next hm_update_run queues this mask's outline when its state is final
@@ -1632,11 +1635,16 @@ extern "C" int hm_update_arm_mask(hm_ctx_t h, const uint8_t *d_y_m)
 
 // Hz components (4N x 4) and gains (3 x 4N) of the last hm_update_run that was called with Hzc = gains = NULL (such a
 // call does not wait for the kernels that form them: the caller gets on with the next frame); either may be NULL.
-// Available until the next hm_update_run on h; zeros for an update without iterations.
+// Available until the next hm_update_run on h; zeros for an update without iterations.  HM_ERR_STATE when the last
+// hm_update_run failed or there was none: its tail is not what the caller asks for.
 extern "C" int hm_update_tail(hm_ctx_t h, double *Hzc, double *gains)
 {
     HM_ARG(h != nullptr, "hm_update_tail: NULL handle");
     HM_JOIN_LAZY(h);                               // (the helper thread may still be queueing the kernels that form them)
+    if (!h->tail_valid) {
+        hm_set_error("hm_update_tail: the last hm_update_run on this handle did not succeed (or there was none)");
+        return HM_ERR_STATE;
+    }
     const size_t n4 = (size_t)4 * h->N;
     if (h->tail_pending) {
         HM_HIP(hipSetDevice(h->device));
@@ -1653,23 +1661,26 @@ extern "C" int hm_update_run(hm_ctx_t h, const double *W_prior, double *X, doubl
                              double reltol, int info[4], double *errs, double *Hzc, double *gains, double *W_out)
 {
     HM_ARG(h && X && info, "hm_update_run: NULL argument");
-    HM_JOIN_LAZY(h);                               // (the tail of the last update: waited for before the first solve below)
-    HM_ARG(deltaX > 0 && max_iter >= 0, "hm_update_run: deltaX must be positive, max_iter >= 0");
-    // hm_chain_project: the prior mean is being left in d_X0 by the kernels of the state path; X is output only
-    const bool chained = h->chain_pending;
-    h->chain_pending = false;
-    // what hm_update_arm_newton armed is for THIS call only: taken out of the handle before anything can fail, so that an
-    // error return never leaves a worker pointer behind for a later call to start a job on
-    h->last_err_valid = false;
+    // what hm_update_arm_newton / _arm_cov / _arm_mask armed is for THIS call only: taken out of the handle before anything
+    // can fail, so that an error return never leaves a worker pointer or a mask address behind for a later call to start a
+    // job on (the helper thread joined below touches none of these fields), and the tail block of the last update stops
+    // being handed out
     const bool pn_go = h->pn_armed;
     void *const pn_worker = h->pn_worker;
     h->pn_armed = false;
     h->pn_worker = nullptr;
     const bool pq_go = h->pq_armed && pn_go;
     h->pq_armed = false;
-    h->pq_valid = false;
     const uint8_t *next_mask = h->armed_mask;
     h->armed_mask = nullptr;
+    h->tail_valid = false;
+    HM_JOIN_LAZY(h);                               // (the tail of the last update: waited for before the first solve below)
+    HM_ARG(deltaX > 0 && max_iter >= 0, "hm_update_run: deltaX must be positive, max_iter >= 0");
+    // hm_chain_project: the prior mean is being left in d_X0 by the kernels of the state path; X is output only
+    const bool chained = h->chain_pending;
+    h->chain_pending = false;
+    h->last_err_valid = false;
+    h->pq_valid = false;                           // (after the join: the last update's tail may have queued a prediction)
     h->tail_pending = false;                       // (the block of the last update is about to be overwritten)
     NEED_TEX(h, "hm_update_run");
     NEED_OBS(h, "hm_update_run");
@@ -1959,6 +1970,7 @@ extern "C" int hm_update_run(hm_ctx_t h, const double *W_prior, double *X, doubl
         if (gains) memset(gains, 0, (size_t)n4 * 3 * sizeof(double));
         std::fill(h->tailv.begin(), h->tailv.end(), 0.0);
     }
+    h->tail_valid = true;                          // (taken, queued for hm_update_tail, or zeros)
     memcpy(X, Xcur.data(), (size_t)n4 * sizeof(double));
     info[0] = niter; info[1] = accepted; info[2] = reverted ? 1 : 0; info[3] = conv ? 1 : 0;
     if (niter > 0 && !reverted) {
@@ -2396,11 +2408,17 @@ extern "C" int hm_chain_project(hm_ctx_t h)
 // streaming caller has the next frame's mask in device memory a frame early): ~0.2 ms of kernels on the second stream
 // that would otherwise start when the next frame does and keep its projection waiting.  Queued behind whatever the
 // second stream still has to do with the current outline.  The mask must not change until that hm_set_observation_dev;
-// any other observation, or a projection onto a host mask, simply discards the preparation.
+// any other observation, or a projection onto a host mask, simply discards the preparation.  Only the address is
+// compared: d_y_m = NULL discards the preparation, if any, for a caller about to put another mask at that address (a
+// frame ring slot reused, a new phase).
 extern "C" int hm_prepare_mask(hm_ctx_t h, const uint8_t *d_y_m)
 {
-    HM_ARG(h && d_y_m, "hm_prepare_mask: NULL argument");
-    HM_JOIN_LAZY(h);
+    HM_ARG(h != nullptr, "hm_prepare_mask: NULL handle");
+    HM_JOIN_LAZY(h);                             // (an update's tail on the helper thread may be preparing an armed mask)
+    if (!d_y_m) {
+        h->prepared_mask = nullptr;
+        return HM_OK;
+    }
     return prepare_mask(h, d_y_m);
 }
 static int prepare_mask(hm_ctx *h, const uint8_t *d_y_m)

@@ -678,6 +678,9 @@ class IteratedKalmanFilter(KalmanFilter):
         t0 = time.time()
         # (the gains -- tv, fv, mv below -- are fetched when somebody reads them: the call does not wait for their kernels)
         lazy = bool(self.lazy_gains) and hasattr(st.renderer, "update_tail")
+        # (an update that raises leaves no gains of an earlier frame behind: tv / fv / mv then ask update_tail(), which
+        # reports that the last update failed)
+        self._gains = None
         X, info, errs, Hzc, gains, W = st.renderer.update_run(st._W, st.X, y_im, y_flow, y_m, self.nI, self.reltol, tail=not lazy)
         stats.stateupdatetc[0] += time.time() - t0
         stats.stateupdatetc[1] += info["niter"]

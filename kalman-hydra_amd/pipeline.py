@@ -705,10 +705,19 @@ class FlowEKFPipeline:
         self._ready = (first, first)
         self._cursor = first
         self._flow_late = False
+        self._discard_prepared_mask()
         if not self.resident:
             self.ring.reset(first)               # nothing of an earlier phase is assumed to be in the ring
         if self.model_ramp and self.adaptive_first and not self._calibrated:
             self.calibrate(first)                # (the frames it uploads are the first ones of this phase: they stay)
+
+    def _discard_prepared_mask(self):
+        """The filter compares a prepared outline with the next observation's mask by address only (hm_prepare_mask):
+        a new phase or random access may put another frame's mask in the slot of the one prepared, and a pipeline made
+        after this one may be given the same memory."""
+        r = getattr(getattr(self.kf, "state", None), "renderer", None)
+        if r is not None and getattr(r, "_h", None) and hasattr(r, "prepare_mask"):
+            r.prepare_mask(None)
 
     def _top_up(self):
         """Keep as many series in flight as there are handles (one unless concurrent_series) -- two at the very start of
@@ -790,7 +799,9 @@ class FlowEKFPipeline:
         n = self._px
         # the next frame's mask, when its upload has been waited for already (every flow series is launched behind a wait
         # for the uploads of its frames): the filter queues that mask's outline a frame ahead
-        nxt = self.ring.ptr(1, k + 2) if (k + 2 < self.F and self.ring.lo <= k + 2 < self.ring.synced_hi) else None
+        # for frame k + 2, not on the last step of a phase: the phase after it may put another frame in that slot
+        nxt = (self.ring.ptr(1, k + 2) if (k + 1 < self._end and k + 2 < self.F and self.ring.lo <= k + 2 < self.ring.synced_hi)
+               else None)
         obs = DeviceObservation(self.ring.ptr(2, k + 1), pu, pv, self.ring.ptr(1, k + 1),
                                 y_m_host=self.source.frame_at(k + 1)[1], next_mask=nxt)
         e = self.kf.compute(obs, None, None, maskflow=self.maskflow)
@@ -870,6 +881,7 @@ class FlowEKFPipeline:
             if tap is not None:
                 tap.close()
             self.flow_sync()
+            self._discard_prepared_mask()
         finally:
             self.ring.close()
             for b in (self.d_u, self.d_v):

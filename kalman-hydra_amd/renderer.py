@@ -453,8 +453,10 @@ class Renderer:
         _lib.check(_lib.lib().hm_update_arm_mask(self._h, ctypes.c_void_p(int(d_mask))), "hm_update_arm_mask")
 
     def prepare_mask(self, d_mask):
-        """hm_prepare_mask: pruning + outline of the NEXT observation's mask (device address) queued a frame ahead."""
-        _lib.check(_lib.lib().hm_prepare_mask(self._h, ctypes.c_void_p(int(d_mask))), "hm_prepare_mask")
+        """hm_prepare_mask: pruning + outline of the NEXT observation's mask (device address) queued a frame ahead.
+        None discards the preparation (before the memory of the prepared mask is given another mask)."""
+        p = None if d_mask is None else ctypes.c_void_p(int(d_mask))
+        _lib.check(_lib.lib().hm_prepare_mask(self._h, p), "hm_prepare_mask")
 
     def chain_states(self):
         """hm_chain_states -> (predicted state, projected state, Newton iterations, vertices moved) of the last chained
