@@ -70,8 +70,8 @@ __global__ __launch_bounds__(OUTLINE_NT) void k_outline(const uint8_t *__restric
 //   k_ccl_stats    nesting comes from the roots: the pixel ABOVE a component's first pixel belongs to the component
 //                  that encloses it (an enclosed component cannot have pixels above whatever encloses it).  Every
 //                  pixel adds 1 to each contour it lies inside or on (its own object's outer contour, the hole that
-//                  object sits in, ...); object pixels 4-adjacent to the outside / to a hole of their own object count
-//                  the contours' boundary points;
+//                  object sits in, ...), all the way out to level 0, however deep it is nested; object pixels
+//                  4-adjacent to the outside / to a hole of their own object count the contours' boundary points;
 //   k_ccl_select   the level-0 object with the largest area (ties: first in raster order);
 //   k_ccl_write    the pruned mask: inside that object's outer contour and not inside one of its holes of area >= 40.
 // All counts are whole numbers, areas are compared doubled (2 A = 2 inside -/+ boundary - 2): same decisions as the oracle.
@@ -258,7 +258,9 @@ __global__ __launch_bounds__(CCL_NT) void k_ccl_flatten(const uint8_t *__restric
 }
 
 // the component that encloses the component with root r (a pixel index): the one the pixel above r belongs to;
-// -1: the frame edge (r in row 0)
+// -1: the frame edge (r in row 0).  Its root is at most r - W: a walk outwards through the parents visits roots in
+// rows that strictly decrease, so it ends -- at an object in row 0 or at background that reaches the frame edge (an
+// enclosed background component is never in row 0) -- within H steps, however deep the nesting
 __device__ __forceinline__ int d_ccl_parent(const Ccl &c, int r) { return r < c.W ? -1 : c.L[r - c.W]; }
 
 __global__ __launch_bounds__(CCL_NT) void k_ccl_stats(const uint8_t *__restrict__ ym, Ccl c)
@@ -278,10 +280,10 @@ __global__ __launch_bounds__(CCL_NT) void k_ccl_stats(const uint8_t *__restrict_
     __syncthreads();
     const int hot = s_root;
     if (in) {
-        // 1: the contours this pixel lies inside or on
+        // 1: the contours this pixel lies inside or on, at any depth (d_ccl_parent: the walk ends within H steps)
         int cur = r;
         bool curfg = fg;
-        for (int depth = 0; depth < 64; depth++) {
+        for (int step = 0; step < H; step++) {
             if (curfg) {
                 if (cur == hot) atomicAdd(&s_n, 1); else atomicAdd(&c.cnt[cur], 1);
                 const int par = d_ccl_parent(c, cur);
@@ -352,7 +354,7 @@ __global__ __launch_bounds__(CCL_NT) void k_ccl_write(const uint8_t *__restrict_
     if (key != 0ull && a2 >= 80) {
         int cur = c.L[p];
         bool curfg = ym[p] > 0;
-        for (int depth = 0; depth < 64; depth++) {
+        for (int step = 0; step < c.H; step++) {                         // (d_ccl_parent: it ends within H steps)
             if (curfg) {
                 if (cur == best) { v = 1; break; }
                 const int par = d_ccl_parent(c, cur);
