@@ -273,6 +273,7 @@ static void sor_launch(const SorPlan &p, SorArgs a, int n, hipStream_t s, hipEve
 // ---- handle ------------------------------------------------------------------------------
 struct hm_brox {
     int device, W, H, B;
+    HmOwner own{2};              // every buffer, stream and event below (HYDRA_MI_POISON class 2)
     float alpha, gamma, scale, omega;
     int inner, outer, solver, fuse, sor_threads;
     int sor_dry;                 // development knob: SOR launches load and store but do not iterate (wrong results)
@@ -323,18 +324,9 @@ struct hm_brox {
 static int brox_free(hm_brox *h)
 {
     if (!h) return HM_OK;
-    hipSetDevice(h->device);
-    for (hipEvent_t e : h->ev) hipEventDestroy(e);
-    if (h->arena) hipFree(h->arena);
-    if (h->d_f0) hipFree(h->d_f0);
-    if (h->d_f1) hipFree(h->d_f1);
-    if (h->d_ox) hipFree(h->d_ox);
-    if (h->d_oy) hipFree(h->d_oy);
-    if (h->whole) hipStreamDestroy(h->whole);
-    if (h->masked) hipStreamDestroy(h->masked);
-    if (h->masked2) hipStreamDestroy(h->masked2);
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    if (h->ev_join) hipEventDestroy(h->ev_join);
+    (void)hipSetDevice(h->device);
+    h->own.drain();
+    h->own.release();
     delete h;
     return HM_OK;
 }
@@ -356,9 +348,6 @@ extern "C" int hm_brox_create(int device, int W, int H, int max_batch, float alp
     h->inner = inner; h->outer = outer; h->solver = solver; h->fuse = 0; h->sor_threads = 0; h->sor_dry = 0;
     h->coarse_max = 32; h->sor_deep = 1; h->cus = 0; h->coarse_stagger = 0; h->sor_wide = 0;
     if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) h->cus = 0;
-    h->arena = nullptr; h->d_f0 = h->d_f1 = nullptr; h->d_ox = h->d_oy = nullptr; h->stream = nullptr;
-    h->prof = false; h->ev_used = 0; h->prof_ms = 0; h->prof_pxit = 0; h->prof_px = 0; h->prof_launches = 0;
-    h->warp_window = false;
     make_levels(W, H, scale, outer, h->geo);
     h->taps = make_taps(scale);
 
@@ -368,7 +357,7 @@ extern "C" int hm_brox_create(int device, int W, int H, int max_batch, float alp
     for (const Geo &g : h->geo) pyr_floats += (size_t)g.plane * B;
     const int nfields = 2 + 7 + 8 + 7 + 4 + 4 + 1;
     h->arena_floats = 2 * pyr_floats + (size_t)nfields * plane0 * B;
-    hipError_t e = hm_malloc((void **)&h->arena, h->arena_floats * sizeof(float));
+    hipError_t e = h->own.alloc(&h->arena, h->arena_floats * sizeof(float));
     if (e != hipSuccess) {
         hm_set_error("hm_brox_create: hipMalloc of %zu MiB failed: %s", h->arena_floats * 4 >> 20, hipGetErrorString(e));
         brox_free(h);
@@ -380,14 +369,14 @@ extern "C" int hm_brox_create(int device, int W, int H, int max_batch, float alp
     // (Tried and taken back: this stream as a CU-masked one with every CU in its mask, which has a hardware queue of its
     // own instead of a place among the runtime's four -- the benches ran as before, the native flow tool, which has no
     // other stream in its process, hung in its first series.)
-    e = hipStreamCreateWithFlags(&h->whole, hipStreamNonBlocking);
+    e = h->own.stream(&h->whole, false);
     h->stream = h->whole;
     if (e == hipSuccess) e = hipMemsetAsync(h->arena, 0, h->arena_floats * sizeof(float), h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hm_malloc((void **)&h->d_f0, B * W * H);
-    if (e == hipSuccess) e = hm_malloc((void **)&h->d_f1, B * W * H);
-    if (e == hipSuccess) e = hm_malloc((void **)&h->d_ox, B * W * H * sizeof(float));
-    if (e == hipSuccess) e = hm_malloc((void **)&h->d_oy, B * W * H * sizeof(float));
+    if (e == hipSuccess) e = h->own.alloc(&h->d_f0, B * W * H);
+    if (e == hipSuccess) e = h->own.alloc(&h->d_f1, B * W * H);
+    if (e == hipSuccess) e = h->own.alloc(&h->d_ox, B * W * H * sizeof(float));
+    if (e == hipSuccess) e = h->own.alloc(&h->d_oy, B * W * H * sizeof(float));
     if (e != hipSuccess) {
         hm_set_error("hm_brox_create: device setup failed: %s", hipGetErrorString(e));
         brox_free(h);
@@ -446,14 +435,14 @@ extern "C" int hm_brox_tune(hm_brox_t h, const char *key, int value)
         HM_ARG(value >= 0 && value < h->cus, "hm_brox_tune: cu_reserve must be in 0..%d", h->cus - 1);
         HM_HIP(hipSetDevice(h->device));
         HM_HIP(hipStreamSynchronize(h->stream));
-        if (h->masked) { HM_HIP(hipStreamDestroy(h->masked)); h->masked = nullptr; }
-        if (h->masked2) { HM_HIP(hipStreamDestroy(h->masked2)); h->masked2 = nullptr; }
+        h->stream = h->whole;
+        HM_HIP(h->own.release(&h->masked));
+        HM_HIP(h->own.release(&h->masked2));
         if (value > 0) {
-            const int words = (h->cus + 31) / 32;
-            std::vector<uint32_t> mask(words, 0u);
+            std::vector<uint32_t> mask((h->cus + 31) / 32, 0u);
             for (int i = 0; i < h->cus - value; i++) mask[i / 32] |= 1u << (i % 32);
-            HM_HIP(hipExtStreamCreateWithCUMask(&h->masked, (uint32_t)words, mask.data()));
-            if (h->lanes >= 2) HM_HIP(hipExtStreamCreateWithCUMask(&h->masked2, (uint32_t)words, mask.data()));
+            HM_HIP(h->own.cu_stream(&h->masked, mask));
+            if (h->lanes >= 2) HM_HIP(h->own.cu_stream(&h->masked2, mask));
         }
         h->stream = h->masked ? h->masked : h->whole;
     } else if (!strcmp(key, "whole_chip")) {
@@ -476,9 +465,9 @@ extern "C" int hm_brox_tune(hm_brox_t h, const char *key, int value)
         HM_ARG(value == 1 || value == 2, "hm_brox_tune: lanes must be 1 or 2");
         HM_ARG(value == 1 || h->masked == nullptr, "hm_brox_tune: lanes must be set before cu_reserve");
         HM_HIP(hipSetDevice(h->device));
-        if (value == 2 && !h->ev_fork) {
-            HM_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            HM_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+        if (value == 2) {
+            HM_HIP(h->own.event(&h->ev_fork));
+            HM_HIP(h->own.event(&h->ev_join));
         }
         h->lanes = value;
     } else if (!strcmp(key, "sor_wide")) {           // same bits either way
@@ -702,14 +691,12 @@ static int brox_run(hm_brox *h, int z0, int n, hipStream_t s, const uint8_t *d_f
                 a.g = g;
                 a.om = h->omega; a.om1 = 1.0f - h->omega;
                 bool rec = h->prof;
-                if (rec) {
-                    if (h->ev_used + 2 > h->ev.size()) {
-                        hipEvent_t e0, e1;
-                        HM_HIP(hipEventCreate(&e0));
-                        HM_HIP(hipEventCreate(&e1));
-                        h->ev.push_back(e0);
-                        h->ev.push_back(e1);
-                    }
+                if (rec && h->ev_used + 2 > h->ev.size()) {
+                    hipEvent_t e0 = nullptr, e1 = nullptr;
+                    HM_HIP(h->own.event(&e0, hipEventDefault));
+                    HM_HIP(h->own.event(&e1, hipEventDefault));
+                    h->ev.push_back(e0);
+                    h->ev.push_back(e1);
                 }
                 SorPlan run = plan;
                 if (h->sor_dry) run.K = 0;

@@ -80,6 +80,7 @@ struct Helper {
 
 struct hm_ctx {
     int device, W, H, N, T, E, njobs;
+    HmOwner own{1};                  // every buffer, stream and event below (HYDRA_MI_POISON class 1)
     Helper helper;
     bool helper_used = false;
     int tail_async = 1;              // hm_ctx_tune "tail_async": the tail of hm_update_run queued by the helper thread (same results)
@@ -94,7 +95,7 @@ struct hm_ctx {
     // observation
     uint8_t *d_yim, *d_ym;
     float *d_yfx, *d_yfy, *d_yfxm, *d_yfym;
-    bool obs_owned;                  // false when set_observation_dev aliases caller memory
+    bool obs_owned = true;           // false when set_observation_dev aliases caller memory
     const uint8_t *o_yim, *o_ym;     // pointers in use (owned or caller's)
     const float *o_yfx, *o_yfy;
     bool have_tex, have_obs, have_ref;
@@ -112,7 +113,7 @@ struct hm_ctx {
                                      // every pattern entry is rewritten by every measurement), used for nothing else
     double *d_H, *d_Hz, *d_Hzc, *d_invW0, *d_Af[2], *d_T[2], *d_step, *d_Wtmp, *d_X0, *d_Xn, *d_Wprior, *d_gain, *d_Awork, *d_Lt[2];
     std::vector<double> upd_X0;      // prior mean given to hm_update_begin
-    int upd_last, upd_prev;          // which d_Af holds the factor of the last / previous step (-1: none)
+    int upd_last = -1, upd_prev = -1;   // which d_Af holds the factor of the last / previous step (-1: none)
     double *d_Wres;                  // the covariance resident on the device (the result of the last
                                      // hm_cov_predict / hm_update_cov / hm_update_run): d_Wtmp, d_H or
                                      // d_Wprior, or NULL when that buffer has been reused since
@@ -140,11 +141,10 @@ struct hm_ctx {
     int *d_area;
     int *d_sp_off, *d_sp_bar, *d_sp_other;
     double *d_sp_blk;
-    size_t sp_cap;                   // capacity (springs) of the d_sp_* arrays
     bool upd_open;
     bool prefactored;                // d_invW0 is the inverse of the resident covariance d_Wprior (hm_update_prefactor)
     std::vector<double> h_partial;
-    int red_blocks;
+    int red_blocks = 512;
     double *d_tpart = nullptr;       // per-tile partial sums of Renderer.error from k_render_iter (tiles x 4)
     std::vector<double> h_tpart;
     int ntiles = 0;
@@ -155,7 +155,7 @@ struct hm_ctx {
     double last_err[4] = {0, 0, 0, 0};
     std::vector<double> last_err_X;
     long long run_ticket;            // sequence number of hm_update_run's per-iteration result blocks
-    int vsplit, esplit;              // workgroups per vertex / per edge job of the measurement (hm_ctx_tune)
+    int vsplit = 5, esplit;          // workgroups per vertex / per edge job of the measurement (hm_ctx_tune)
     // hm_update_arm_newton: what the next hm_update_run starts when its state is final
     bool pn_armed = false;
     void *pn_worker = nullptr;
@@ -174,7 +174,6 @@ struct hm_ctx {
     hipStream_t stream3 = nullptr;
     int *d_n4nbr = nullptr, *d_n4nbb = nullptr, *d_n4bars = nullptr;
     double *d_n4l0 = nullptr;
-    size_t n4cap = 0;                // bars the device arrays hold
     int n4deg = 0;                   // padded degree of the table on the device (8 or 12), 0: this mesh does not fit the kernel
     std::vector<int32_t> n4_bars;    // the springs the table was built for
     std::vector<double> n4_l0;
@@ -185,18 +184,22 @@ struct hm_ctx {
     bool n4_pending = false;
     int newton_fail = 0;             // test knob: the next device predictions report a failed inner solve
     hipEvent_t ev_n4 = nullptr, ev_pm = nullptr;     // the prediction's kernel / the chained projection have run
+    bool n4_ready = false;           // hm_newton_dev_start's stream, blocks and event are there
     // hm_chain_project: projectmask of the prediction in flight queued behind it; the projected state (d_X0) is the
     // prior mean of the next hm_update_run, which also collects what the two kernels report
     bool chain_pending = false;
     std::vector<double> chain_pred, chain_proj;     // ... the predicted / the projected state of the last chained update
     int chain_its = 0, chain_moved = 0;
     double *pin_blk = nullptr;       // page-locked staging of the spring blocks of that prediction
-    size_t pin_blk_cap = 0;
     std::thread worker;              // hm_update_prefactor queues its launches from here while the caller predicts the state
     bool worker_active;
     int worker_rc;
     char worker_err[512];
-    int chol_flow, flow_wgs;         // the factorisation as one persistent launch (chol_flow_kernels.h) / its workgroups
+    // the factorisation as one persistent launch (chol_flow_kernels.h) / its workgroups.  (192 workgroups: 304.9 -> 306.9 us
+    // per iteration with the filter alone, but 260.5 -> 264.2 and 318.6 -> 324.1 frames/s in the two benches -- the
+    // workgroups that poll for blocks take issue slots from the flow's kernels on every compute unit they sit on; 160 and
+    // 128 starve the chain: profiles/r04_ab_tunes.txt)
+    int chol_flow = 1, flow_wgs = 192;
     int flow_stall = 0;              // test knob: FlowArgs.stall
     int speculate = 1;               // hm_update_run queues the next iteration's measurement before it knows that there is one
     double *d_flowP;                 // 3 x nb x 32 x 32 scratch of that launch
@@ -213,12 +216,11 @@ struct hm_ctx {
     int tail_split = 1;              // hm_ctx_tune "tail_split": 0 keeps the tail on `stream` (same results either way)
     int *d_nbars, *d_nvoff, *d_nvbar, *d_ninfo;     // its spring topology (bars, CSR of the bars of every vertex), result words
     double *d_nl0, *d_nX;
-    size_t ncap;                     // bars the buffers hold
+    bool newton_ready = false;       // hm_ms_predict's buffers are there and k_ms_newton may take its LDS
     int *d_ids[3];                   // hm_jz_multi / hm_j_multi: id images of the reference and the two perturbed renders,
     int *d_labels;                   // the label palette (T), per-label boxes and sums; allocated on first use
     int4 *d_lbox;
     double *d_lout;
-    int lcap;                        // labels the last two hold
     std::vector<double> h_lout;
     int2 *d_outline;                 // hm_project_mask: outline pixels (W*H), counters, uploaded mask; allocated on first use
     int *d_outline_cnt;
@@ -231,10 +233,12 @@ struct hm_ctx {
     std::vector<double> pmv;         // the host's copy of that block
     int *d_pm_done = nullptr;        // workgroups of k_project_mask_host that have finished
     long long pm_ticket = 0;
+    bool pm_ready = false;           // project_buffers has built all of the above
     bool outline_ready = false;      // the outline of the resident mask (o_ym) has been queued on the second stream
     const uint8_t *prepared_mask = nullptr;   // hm_prepare_mask: the outline in the buffers is that of this mask (device memory)
     hipEvent_t ev_outline = nullptr; // ... recorded behind every outline queued on the second stream
-    hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)    // hm_view / hm_view_dev / hm_view_forces: targets of their own, allocated on first use -- a view touches nothing the
+    hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)
+    // hm_view / hm_view_dev / hm_view_forces: targets of their own, allocated on first use -- a view touches nothing the
     // filter reads (its render, triangle setups, state copy and wireframe counts are all here)
     Targets V = {nullptr, nullptr, nullptr, nullptr};
     TriSetup *d_vsetup = nullptr;
@@ -245,31 +249,30 @@ struct hm_ctx {
     hipEvent_t ev_view = nullptr;
 };
 
-static int alloc_targets(Targets &t, size_t n)
+static hipError_t alloc_targets(HmOwner &own, Targets &t, size_t n)
 {
-    HM_HIP(hm_malloc((void **)&t.acc, n * sizeof(int)));
-    HM_HIP(hm_malloc((void **)&t.fx, n * sizeof(float)));
-    HM_HIP(hm_malloc((void **)&t.fy, n * sizeof(float)));
-    HM_HIP(hm_malloc((void **)&t.cnt, n * sizeof(int)));
-    return HM_OK;
-}
-static void free_targets(Targets &t)
-{
-    if (t.acc) (void)hipFree(t.acc);
-    if (t.fx) (void)hipFree(t.fx);
-    if (t.fy) (void)hipFree(t.fy);
-    if (t.cnt) (void)hipFree(t.cnt);
+    hipError_t e = own.alloc(&t.acc, n * sizeof(int));
+    if (e == hipSuccess) e = own.alloc(&t.fx, n * sizeof(float));
+    if (e == hipSuccess) e = own.alloc(&t.fy, n * sizeof(float));
+    if (e == hipSuccess) e = own.alloc(&t.cnt, n * sizeof(int));
+    return e;
 }
 
+// the launches the helper thread is still queueing (the tail of the last update), and their failure, if any
+static int helper_join(hm_ctx *h)
+{
+    if (h->helper_used) {
+        const int rc = h->helper.wait();
+        if (rc != HM_OK) { hm_set_error("%s", h->helper.err); return rc; }
+    }
+    return HM_OK;
+}
 // Every entry point waits for the launches hm_update_prefactor is still queueing (one handle = one
 // stream = one thread at a time, as far as the device can tell) and reports their failure, if any.
 static int ctx_join(hm_ctx *h, bool lazy = false)
 {
     if (!h) return HM_OK;
-    if (h->helper_used) {                        // launches the helper thread is still queueing (the tail of the last update)
-        const int rc = h->helper.wait();
-        if (rc != HM_OK) { hm_set_error("%s", h->helper.err); return rc; }
-    }
+    if (const int rc = helper_join(h)) return rc;
     if (!lazy && h->tail_on_stream4) {
         h->tail_on_stream4 = false;
         if (hipSetDevice(h->device) != hipSuccess || hipStreamWaitEvent(h->stream, h->ev_tail, 0) != hipSuccess) {
@@ -346,26 +349,17 @@ static int hb_wait(hipStream_t st, const double *blk, size_t first, size_t n, un
 }
 
 // ---- the pool of parked difference images (DPool, ekf_kernels.h) -------------------------------------------------
-static void pool_release(hm_ctx *h)
+static hipError_t pool_alloc(hm_ctx *h, long long cap)
 {
-    void *ptrs[] = {h->pool.live, h->pool.xi, h->pool.yi, h->pool.xfx, h->pool.xfy, h->pool.yfx, h->pool.yfy, h->pool.vxfx, h->pool.vyfy};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    h->pool.live = nullptr; h->pool.xi = h->pool.yi = nullptr;
-    h->pool.xfx = h->pool.xfy = h->pool.yfx = h->pool.yfy = h->pool.vxfx = h->pool.vyfy = nullptr;
-    h->pool.cap = 0;
-}
-static int pool_alloc(hm_ctx *h, long long cap)
-{
-    pool_release(h);
     const size_t pc = (size_t)cap;
-    HM_HIP(hm_malloc((void **)&h->pool.live, (pc / 64 + 1) * sizeof(int)));
-    short2 **sp[] = {&h->pool.xi, &h->pool.yi};
-    for (short2 **q : sp) HM_HIP(hm_malloc((void **)q, pc * sizeof(short2)));
-    float **fp[] = {&h->pool.xfx, &h->pool.xfy, &h->pool.yfx, &h->pool.yfy, &h->pool.vxfx, &h->pool.vyfy};
-    for (float **q : fp) HM_HIP(hm_malloc((void **)q, pc * sizeof(float)));
-    h->pool.cap = cap;
-    return HM_OK;
+    h->pool.cap = 0;
+    hipError_t e = h->own.grow(&h->pool.live, (pc / 64 + 1) * sizeof(int));
+    for (short2 **q : {&h->pool.xi, &h->pool.yi})
+        if (e == hipSuccess) e = h->own.grow(q, pc * sizeof(short2));
+    for (float **q : {&h->pool.xfx, &h->pool.xfy, &h->pool.yfx, &h->pool.yfy, &h->pool.vxfx, &h->pool.vyfy})
+        if (e == hipSuccess) e = h->own.grow(q, pc * sizeof(float));
+    if (e == hipSuccess) h->pool.cap = cap;
+    return e;
 }
 // A measurement reported that its star regions do not fit (the reference has no such limit: its renders are whole
 // frames): make room for them -- the region areas are on the device -- plus a quarter.  The stream must be idle.
@@ -383,8 +377,11 @@ static int pool_grow(hm_ctx *h, const char *who)
         return HM_ERR_STATE;
     }
     if (getenv("HYDRA_MI_TRACE")) fprintf(stderr, "[hydra_mi] %s: difference-image pool %lld -> %lld pixels\n", who, h->pool.cap, want);
-    int rc = pool_alloc(h, want);
-    if (rc) { hm_set_error("%s: cannot grow the difference-image pool to %lld pixels: %s", who, want, hm_last_error()); return rc; }
+    const hipError_t e = pool_alloc(h, want);
+    if (e != hipSuccess) {
+        hm_set_error("%s: cannot grow the difference-image pool to %lld pixels: %s", who, want, hipGetErrorString(e));
+        return HM_ERR_HIP;
+    }
     return HM_OK;
 }
 
@@ -394,49 +391,18 @@ static int ctx_free(hm_ctx *h)
     (void)ctx_join(h);
     if (h->helper_used) h->helper.stop();
     (void)hipSetDevice(h->device);
-    // every stream of the handle first: a state prediction started ahead is always pending after the last frame (it writes
-    // into pin_n4), and so may be launches of an update that ended in an error
-    { hipStream_t q[] = {h->stream, h->stream2, h->stream3, h->stream4}; for (hipStream_t x : q) if (x) (void)hipStreamSynchronize(x); }
-    void *ptrs[] = {h->d_tri, h->d_star_off, h->d_star_tri, h->d_edges, h->d_uv, h->d_tex, h->d_yim, h->d_ym, h->d_yfx,
-                    h->d_yfy, h->d_yfxm, h->d_yfym, h->d_setup, h->d_cfgs, h->d_ubox, h->d_X, h->d_out, h->d_partial, h->d_im8, h->d_m8,
-                    h->d_HTH, h->d_H, h->d_Hz, h->d_Hzc, h->d_invW0, h->d_Af[0], h->d_Af[1], h->d_T[0], h->d_T[1], h->d_step, h->d_Wprior, h->d_gain, h->d_Awork, h->d_Lt[0], h->d_Lt[1],
-                    h->d_Wtmp, h->d_X0, h->d_Xn, h->d_sp_off, h->d_sp_bar, h->d_sp_other, h->d_sp_blk,
-                    h->pool.hdr, h->pool.overflow, h->d_area,
-                    h->d_outline, h->d_outline_cnt, h->d_pm_mask, h->d_pm_flag, h->d_pm_X, h->d_pm_pruned, h->ccl.L, h->ccl.cnt, h->ccl.bnd, h->ccl.edge, h->ccl.best, h->d_ids[0], h->d_ids[1], h->d_ids[2], h->d_labels, h->d_lbox,
-                    h->d_lout, h->d_tpart, h->d_tmask, h->d_tlist, h->d_tcount, h->d_nb_off, h->d_nb_u, h->d_nb_e, h->d_flowP, h->d_flowctl, h->d_nbars, h->d_nvoff, h->d_nvbar, h->d_ninfo, h->d_nl0, h->d_nX};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    pool_release(h);
-    free_targets(h->ref);
-    free_targets(h->P);
-    free_targets(h->Q);
-    free_targets(h->V);
-    { void *q[] = {h->d_vsetup, h->d_vids, h->d_vlab, h->d_vwire, h->d_vmm, h->d_vX, h->d_vforce, h->d_vout};
-      for (void *x : q) if (x) (void)hipFree(x); }
-    if (h->ev_view) (void)hipEventDestroy(h->ev_view);
-    { void *q[] = {h->d_n4nbr, h->d_n4nbb, h->d_n4bars, h->d_n4l0, h->d_n4X, h->d_pm_done}; for (void *x : q) if (x) (void)hipFree(x); }
-    // (the streams were drained at the top: nothing writes into the page-locked blocks any more)
-    if (h->pin) (void)hipHostFree(h->pin);
-    if (h->pin_pm) (void)hipHostFree(h->pin_pm);
-    if (h->pin_blk) (void)hipHostFree(h->pin_blk);
-    if (h->pin_n4) (void)hipHostFree(h->pin_n4);
-    if (h->ev_n4) (void)hipEventDestroy(h->ev_n4);
-    if (h->ev_pm) (void)hipEventDestroy(h->ev_pm);
-    if (h->ev_outline) (void)hipEventDestroy(h->ev_outline);
-    if (h->ev_m0) (void)hipEventDestroy(h->ev_m0);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    if (h->stream4) (void)hipStreamDestroy(h->stream4);
-    if (h->stream3) (void)hipStreamDestroy(h->stream3);
-    if (h->stream2) (void)hipStreamDestroy(h->stream2);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    // every stream of the handle drained before anything is freed: a state prediction started ahead is always pending after
+    // the last frame (it writes into pin_n4), and so may be launches of an update that ended in an error
+    h->own.drain();
+    h->own.release();
     delete h;
     return HM_OK;
 }
 
 template <typename T>
-static int upload(T **dst, const T *src, size_t n)
+static int upload(HmOwner &own, T **dst, const T *src, size_t n)
 {
-    HM_HIP(hm_malloc((void **)dst, (n ? n : 1) * sizeof(T)));
+    HM_HIP(own.alloc(dst, (n ? n : 1) * sizeof(T)));
     if (n) HM_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     return HM_OK;
 }
@@ -476,33 +442,10 @@ extern "C" int hm_ctx_create(int device, int W, int H, int N, int T, const int32
     hm_ctx *h = new hm_ctx();
     h->device = device; h->W = W; h->H = H; h->N = N; h->T = T;
     h->eps_Z = eps_Z; h->eps_J = eps_J; h->eps_M = eps_M;
-    h->obs_owned = true; h->have_tex = h->have_obs = h->have_ref = false;
-    h->o_yim = h->o_ym = nullptr; h->o_yfx = h->o_yfy = nullptr;
-    h->d_yim = h->d_ym = nullptr; h->d_yfx = h->d_yfy = h->d_yfxm = h->d_yfym = nullptr;
-    h->ref = Targets{nullptr, nullptr, nullptr, nullptr}; h->P = h->ref; h->Q = h->ref;
-    h->d_setup = nullptr; h->d_cfgs = nullptr; h->d_ubox = nullptr; h->d_X = h->d_out = h->d_partial = nullptr; h->d_im8 = h->d_m8 = nullptr;
-    h->d_HTH = nullptr;
-    h->d_H = h->d_Hz = h->d_Hzc = h->d_invW0 = h->d_Af[0] = h->d_Af[1] = h->d_Wtmp = nullptr;
-    h->d_Wprior = h->d_gain = h->d_Awork = h->d_Lt[0] = h->d_Lt[1] = nullptr; h->d_Wres = nullptr; h->pin = nullptr; h->pin_n = 0;
     h->tri.assign(tri, tri + (size_t)3 * T);
-    h->d_outline = nullptr; h->d_outline_cnt = nullptr; h->d_pm_mask = nullptr;
-    // (192 workgroups of the factorisation launch: 304.9 -> 306.9 us per iteration with the filter alone, but 260.5 -> 264.2 and
-    // 318.6 -> 324.1 frames/s in the two benches -- the workgroups that poll for blocks take issue slots from the flow's
-    // kernels on every compute unit they sit on; 160 and 128 starve the chain: profiles/r04_ab_tunes.txt)
-    h->chol_flow = 1; h->flow_wgs = 192; h->d_flowP = nullptr; h->d_flowctl = nullptr;
-    h->stream2 = nullptr; h->d_nbars = h->d_nvoff = h->d_nvbar = h->d_ninfo = nullptr; h->d_nl0 = h->d_nX = nullptr; h->ncap = 0;
-    h->d_ids[0] = h->d_ids[1] = h->d_ids[2] = nullptr; h->d_labels = nullptr; h->d_lbox = nullptr; h->d_lout = nullptr; h->lcap = 0;
-    h->worker_active = false; h->worker_rc = HM_OK; h->worker_err[0] = 0;
-    h->d_T[0] = h->d_T[1] = h->d_step = nullptr; h->d_X0 = h->d_Xn = nullptr;
-    memset(&h->pool, 0, sizeof h->pool); h->d_area = nullptr;
-    h->d_sp_off = h->d_sp_bar = h->d_sp_other = nullptr; h->d_sp_blk = nullptr; h->sp_cap = 0;
-    h->upd_last = h->upd_prev = -1; h->upd_open = false; h->prefactored = false;
     for (const auto &e : eset) { h->edges.push_back(e.first); h->edges.push_back(e.second); }
     h->E = (int)eset.size();
     h->njobs = N + h->E;
-    h->red_blocks = 512;
-    h->run_ticket = 0;
-    h->vsplit = 5;
     // two workgroups per edge job as long as they are ONE round of the chip (122 VGPRs: four workgroups per CU, 1 024 slots),
     // else one: at 201 vertices 556 edges x 2 = 1 112 workgroups had 88 of them wait for a slot and the launch take a second
     // round (308.6 -> 305.1 us per iteration with one; the sums of an edge are then added in another order: rounding-level
@@ -511,11 +454,11 @@ extern "C" int hm_ctx_create(int device, int W, int H, int N, int T, const int32
     const size_t n = (size_t)W * H;
     int rc = HM_OK;
     auto step = [&](int r) { if (rc == HM_OK) rc = r; };
-    step(upload(&h->d_tri, tri, (size_t)3 * T));
-    step(upload(&h->d_uv, uv, (size_t)2 * N));
-    step(upload(&h->d_star_off, off.data(), off.size()));
-    step(upload(&h->d_star_tri, flat.data(), flat.size()));
-    step(upload(&h->d_edges, h->edges.data(), h->edges.size()));
+    step(upload(h->own, &h->d_tri, tri, (size_t)3 * T));
+    step(upload(h->own, &h->d_uv, uv, (size_t)2 * N));
+    step(upload(h->own, &h->d_star_off, off.data(), off.size()));
+    step(upload(h->own, &h->d_star_tri, flat.data(), flat.size()));
+    step(upload(h->own, &h->d_edges, h->edges.data(), h->edges.size()));
     {   // neighbours of every vertex with the edge job that holds their block of HTH
         std::vector<std::vector<std::pair<int, int>>> nb(N);
         for (int e = 0; e < h->E; e++) {
@@ -533,88 +476,85 @@ extern "C" int hm_ctx_create(int device, int W, int H, int N, int T, const int32
                 rc = HM_ERR_ARG;
             }
         }
-        step(upload(&h->d_nb_off, noff.data(), noff.size()));
-        step(upload(&h->d_nb_u, nu.data(), nu.size()));
-        step(upload(&h->d_nb_e, ne.data(), ne.size()));
+        step(upload(h->own, &h->d_nb_off, noff.data(), noff.size()));
+        step(upload(h->own, &h->d_nb_u, nu.data(), nu.size()));
+        step(upload(h->own, &h->d_nb_e, ne.data(), ne.size()));
     }
+    // the device set-up: it ends at the first failure, and ctx_free releases whatever it made
+    hipError_t e = hipSuccess;
+    auto dev = [&](auto **p, size_t bytes) { if (e == hipSuccess) e = h->own.alloc(p, bytes); };
     if (rc == HM_OK) {
         // the filter's launches are a dependent chain of short kernels beside the flow's long ones on another stream:
         // its queue gets the highest dispatch priority the device offers (HYDRA_MI_EKF_PRIORITY=0 turns that off)
-        int least = 0, greatest = 0;
         const char *pe = getenv("HYDRA_MI_EKF_PRIORITY");
-        hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (e == hipSuccess && greatest != least && !(pe && atoi(pe) == 0))
-            e = hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, greatest);
-        else if (e == hipSuccess)
-            e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_tex, n);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_yim, n);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_ym, n);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_yfx, n * sizeof(float));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_yfy, n * sizeof(float));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_yfxm, n * sizeof(float));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_yfym, n * sizeof(float));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_setup, (size_t)T * sizeof(TriSetup));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_cfgs, (size_t)N * MEAS_NCFG * (EKF_MAX_STAR + 1) * sizeof(TriSetup));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_ubox, (size_t)N * UBOX_STRIDE * sizeof(int4));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_tmask, (size_t)N * TMASK_STRIDE * sizeof(unsigned));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_tlist, (size_t)N * TMASK_STRIDE * sizeof(int));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_tcount, (size_t)N * sizeof(int));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_X, (size_t)4 * N * sizeof(double));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_out, (size_t)h->njobs * MEAS_VSPLIT_MAX * MEAS_OUT * sizeof(double));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_partial, (size_t)h->red_blocks * 4 * sizeof(double));
+        e = h->own.stream(&h->stream, !(pe && atoi(pe) == 0));
+        dev(&h->d_tex, n);
+        dev(&h->d_yim, n);
+        dev(&h->d_ym, n);
+        dev(&h->d_yfx, n * sizeof(float));
+        dev(&h->d_yfy, n * sizeof(float));
+        dev(&h->d_yfxm, n * sizeof(float));
+        dev(&h->d_yfym, n * sizeof(float));
+        dev(&h->d_setup, (size_t)T * sizeof(TriSetup));
+        dev(&h->d_cfgs, (size_t)N * MEAS_NCFG * (EKF_MAX_STAR + 1) * sizeof(TriSetup));
+        dev(&h->d_ubox, (size_t)N * UBOX_STRIDE * sizeof(int4));
+        dev(&h->d_tmask, (size_t)N * TMASK_STRIDE * sizeof(unsigned));
+        dev(&h->d_tlist, (size_t)N * TMASK_STRIDE * sizeof(int));
+        dev(&h->d_tcount, (size_t)N * sizeof(int));
+        dev(&h->d_X, (size_t)4 * N * sizeof(double));
+        dev(&h->d_out, (size_t)h->njobs * MEAS_VSPLIT_MAX * MEAS_OUT * sizeof(double));
+        dev(&h->d_partial, (size_t)h->red_blocks * 4 * sizeof(double));
         h->ntiles = hm_cdiv(W, RI_W) * hm_cdiv(H, 8);           // most strips of k_render_iter (render_rows 8)
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_tpart, (size_t)h->ntiles * RI_NV * sizeof(double));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_im8, n);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_m8, n);
+        dev(&h->d_tpart, (size_t)h->ntiles * RI_NV * sizeof(double));
+        dev(&h->d_im8, n);
+        dev(&h->d_m8, n);
         const size_t n4 = (size_t)4 * N, nn = n4 * n4 * sizeof(double);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_H, nn);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_HTH, nn);
+        dev(&h->d_H, nn);
+        dev(&h->d_HTH, nn);
         if (e == hipSuccess) e = hipMemsetAsync(h->d_HTH, 0, nn, h->stream);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_invW0, nn);
+        dev(&h->d_invW0, nn);
         const size_t nn_aug = (size_t)(hm_cdiv((int)n4, DNB) * DNB + DNB) * n4 * sizeof(double);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Af[0], nn_aug);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Af[1], nn_aug);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Awork, nn_aug);
+        dev(&h->d_Af[0], nn_aug);
+        dev(&h->d_Af[1], nn_aug);
+        dev(&h->d_Awork, nn_aug);
         const size_t ld_bytes = (size_t)hm_cdiv((int)n4, DNB) * DNB * DNB * sizeof(double);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_T[0], nn);       // L^-1 of the factor in the same slot
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_T[1], nn);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_step, n4 * sizeof(double));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Lt[0], ld_bytes);  // inverses of the factored diagonal blocks
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Lt[1], ld_bytes);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Wtmp, nn);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_flowP, 3 * ld_bytes);      // P, Q and Y blocks of k_chol_flow
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_flowctl, 4 * sizeof(unsigned));
+        dev(&h->d_T[0], nn);       // L^-1 of the factor in the same slot
+        dev(&h->d_T[1], nn);
+        dev(&h->d_step, n4 * sizeof(double));
+        dev(&h->d_Lt[0], ld_bytes);  // inverses of the factored diagonal blocks
+        dev(&h->d_Lt[1], ld_bytes);
+        dev(&h->d_Wtmp, nn);
+        dev(&h->d_flowP, 3 * ld_bytes);      // P, Q and Y blocks of k_chol_flow
+        dev(&h->d_flowctl, 4 * sizeof(unsigned));
         if (e == hipSuccess) e = hipMemsetAsync(h->d_flowctl, 0, 4 * sizeof(unsigned), h->stream);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Hz, n4 * sizeof(double));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Hzc, n4 * 4 * sizeof(double));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Wprior, nn);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_gain, n4 * 3 * sizeof(double));
+        dev(&h->d_Hz, n4 * sizeof(double));
+        dev(&h->d_Hzc, n4 * 4 * sizeof(double));
+        dev(&h->d_Wprior, nn);
+        dev(&h->d_gain, n4 * 3 * sizeof(double));
         h->pin_n = 2 * (n4 + RES_HEAD + n4 * 4 + n4 * 3) + 2;
-        if (e == hipSuccess) e = hipHostMalloc((void **)&h->pin, h->pin_n * sizeof(double), hipHostMallocCoherent);
+        if (e == hipSuccess) e = h->own.host_alloc(&h->pin, h->pin_n * sizeof(double), hipHostMallocCoherent);
         if (e == hipSuccess) memset(h->pin, 0, h->pin_n * sizeof(double));
         h->pin_scratch = (int *)(h->pin + h->pin_n - 2);
         h->resv.assign(n4 + RES_HEAD, 0.0);
         h->tailv.assign(n4 * 7, 0.0);
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_X0, n4 * sizeof(double));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->pool.hdr, (size_t)4 * N * sizeof(int));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->pool.overflow, sizeof(int));
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_area, (size_t)N * sizeof(int));
+        dev(&h->d_X0, n4 * sizeof(double));
+        dev(&h->pool.hdr, (size_t)4 * N * sizeof(int));
+        dev(&h->pool.overflow, sizeof(int));
+        dev(&h->d_area, (size_t)N * sizeof(int));
         h->pool.area = h->d_area;
         // pool of parked difference images (32 B per pixel): the star regions overlap about six times, so a mesh that
         // covers the whole frame needs about six frames' worth of pixels plus the padding of every region to whole 8x8
         // tiles (the bench's disk, a third of the frame: 1.6); it starts at 8 frames' worth = 268 MB at 1024^2 and grows
         // when a measurement reports that its regions do not fit (pool_grow)
-        if (e == hipSuccess && pool_alloc(h, (long long)8 * W * H) != HM_OK) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hm_malloc((void **)&h->d_Xn, n4 * sizeof(double));
-        if (e != hipSuccess) {
-            hm_set_error("hm_ctx_create: device allocation failed: %s", hipGetErrorString(e));
-            rc = HM_ERR_HIP;
-        }
+        if (e == hipSuccess) e = pool_alloc(h, (long long)8 * W * H);
+        dev(&h->d_Xn, n4 * sizeof(double));
+        for (Targets *t : {&h->ref, &h->P, &h->Q})
+            if (e == hipSuccess) e = alloc_targets(h->own, *t, n);
     }
-    step(alloc_targets(h->ref, n));
-    step(alloc_targets(h->P, n));
-    step(alloc_targets(h->Q, n));
+    if (e != hipSuccess) {
+        hm_set_error("hm_ctx_create: device allocation failed: %s", hipGetErrorString(e));
+        step(HM_ERR_HIP);
+    }
     if (rc != HM_OK) {
         ctx_free(h);
         return rc;
@@ -711,40 +651,37 @@ extern "C" int hm_set_texture(hm_ctx_t h, const uint8_t *tex)
 // The second stream (projectmask, hm_ms_predict): short launches beside the first stream's, same dispatch priority.
 static int ensure_stream2(hm_ctx *h)
 {
-    if (h->stream2) return HM_OK;
-    int least = 0, greatest = 0;
-    HM_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    if (greatest != least) { HM_HIP(hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, greatest)); }
-    else HM_HIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
+    HM_HIP(h->own.stream(&h->stream2));
     return HM_OK;
 }
 
 // hm_project_mask's buffers and the outline of a mask in device memory, queued on the second stream
 static int project_buffers(hm_ctx *h)
 {
-    if (h->d_outline) return HM_OK;
+    if (h->pm_ready) return HM_OK;
     const size_t n = (size_t)h->W * h->H, n4 = (size_t)4 * h->N;
-    HM_HIP(hm_malloc((void **)&h->d_outline, n * sizeof(int2)));
-    HM_HIP(hm_malloc((void **)&h->d_outline_cnt, 4 * sizeof(int)));
-    HM_HIP(hm_malloc((void **)&h->d_pm_flag, n));
-    HM_HIP(hm_malloc((void **)&h->d_pm_pruned, n));
-    HM_HIP(hm_malloc((void **)&h->ccl.L, n * sizeof(int)));
-    HM_HIP(hm_malloc((void **)&h->ccl.cnt, n * sizeof(int)));
-    HM_HIP(hm_malloc((void **)&h->ccl.bnd, n * sizeof(int)));
-    HM_HIP(hm_malloc((void **)&h->ccl.edge, n));
-    HM_HIP(hm_malloc((void **)&h->ccl.best, sizeof(unsigned long long)));
+    HM_HIP(h->own.alloc(&h->d_outline, n * sizeof(int2)));
+    HM_HIP(h->own.alloc(&h->d_outline_cnt, 4 * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->d_pm_flag, n));
+    HM_HIP(h->own.alloc(&h->d_pm_pruned, n));
+    HM_HIP(h->own.alloc(&h->ccl.L, n * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->ccl.cnt, n * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->ccl.bnd, n * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->ccl.edge, n));
+    HM_HIP(h->own.alloc(&h->ccl.best, sizeof(unsigned long long)));
     h->ccl.W = h->W; h->ccl.H = h->H;
-    HM_HIP(hm_malloc((void **)&h->d_pm_X, n4 * sizeof(double)));
-    HM_HIP(hm_malloc((void **)&h->d_pm_done, sizeof(int)));
+    HM_HIP(h->own.alloc(&h->d_pm_X, n4 * sizeof(double)));
+    HM_HIP(h->own.alloc(&h->d_pm_done, sizeof(int)));
     // zeroed on the stream the kernel that counts in it runs on: a hipMemset on the null stream is not ordered with a
     // non-blocking stream and may land in the middle of that kernel -- no workgroup is the last one then, the count of
     // moved vertices never comes and the projection of a context's first frame was silently dropped (seen once in ~10 runs)
     HM_HIP(hipMemsetAsync(h->d_pm_done, 0, sizeof(int), h->stream2));
-    HM_HIP(hipHostMalloc((void **)&h->pin_pm, (n4 + 2 * (n4 + 1)) * sizeof(double), hipHostMallocCoherent));
+    HM_HIP(h->own.host_alloc(&h->pin_pm, (n4 + 2 * (n4 + 1)) * sizeof(double), hipHostMallocCoherent));
     memset(h->pin_pm, 0, (n4 + 2 * (n4 + 1)) * sizeof(double));
     h->pmv.assign(n4 + 1, 0.0);
-    HM_HIP(hipEventCreateWithFlags(&h->ev_pm, hipEventDisableTiming));
-    HM_HIP(hipEventCreateWithFlags(&h->ev_outline, hipEventDisableTiming));
+    HM_HIP(h->own.event(&h->ev_pm));
+    HM_HIP(h->own.event(&h->ev_outline));
+    h->pm_ready = true;
     return HM_OK;
 }
 // the reference's contour pruning of the mask (imgproc.py:198-228: the largest object, its holes of area >= 40) into
@@ -995,18 +932,10 @@ extern "C" int hm_j(hm_ctx_t h, const double *X, double deltaX, int i, int j, do
 static int multi_setup(hm_ctx *h, const int32_t *labels, int n_labels, const double *const states[], int n_states)
 {
     const size_t n = (size_t)h->W * h->H;
-    if (!h->d_ids[0]) {
-        for (int k = 0; k < 3; k++) HM_HIP(hm_malloc((void **)&h->d_ids[k], n * sizeof(int)));
-        HM_HIP(hm_malloc((void **)&h->d_labels, (size_t)h->T * sizeof(int)));
-    }
-    if (n_labels > h->lcap) {
-        if (h->d_lbox) (void)hipFree(h->d_lbox);
-        if (h->d_lout) (void)hipFree(h->d_lout);
-        h->d_lbox = nullptr; h->d_lout = nullptr; h->lcap = 0;
-        HM_HIP(hm_malloc((void **)&h->d_lbox, (size_t)n_labels * sizeof(int4)));
-        HM_HIP(hm_malloc((void **)&h->d_lout, (size_t)n_labels * 5 * sizeof(double)));
-        h->lcap = n_labels;
-    }
+    for (int k = 0; k < 3; k++) HM_HIP(h->own.alloc(&h->d_ids[k], n * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->d_labels, (size_t)h->T * sizeof(int)));
+    HM_HIP(h->own.grow(&h->d_lbox, (size_t)n_labels * sizeof(int4)));
+    HM_HIP(h->own.grow(&h->d_lout, (size_t)n_labels * 5 * sizeof(double)));
     std::vector<int4> box(n_labels, make_int4(1, 0, 1, 0));
     for (int t = 0; t < h->T; t++) {
         const int lab = labels[t];
@@ -1534,7 +1463,7 @@ extern "C" int hm_project_mask(hm_ctx_t h, const uint8_t *y_m, double *X, int *m
         return HM_OK;
     }
     h->outline_ready = false;                    // the buffers are about to hold the outline of the caller's mask
-    if (!h->d_pm_mask) HM_HIP(hm_malloc((void **)&h->d_pm_mask, n));
+    HM_HIP(h->own.alloc(&h->d_pm_mask, n));
     HM_HIP(hipMemcpyAsync(h->d_pm_mask, y_m, n, hipMemcpyHostToDevice, s));
     const uint8_t *mask = h->d_pm_mask;
     rc = queue_outline(h, mask);
@@ -1565,7 +1494,7 @@ extern "C" int hm_prune_mask(hm_ctx_t h, const uint8_t *y_m, uint8_t *out)
     if (rc) return rc;
     const size_t n = (size_t)h->W * h->H;
     h->outline_ready = false;                    // the buffers are about to hold the outline of the caller's mask
-    if (!h->d_pm_mask) HM_HIP(hm_malloc((void **)&h->d_pm_mask, n));
+    HM_HIP(h->own.alloc(&h->d_pm_mask, n));
     HM_HIP(hipMemcpyAsync(h->d_pm_mask, y_m, n, hipMemcpyHostToDevice, h->stream2));
     rc = queue_outline(h, h->d_pm_mask);
     if (rc) return rc;
@@ -1744,7 +1673,7 @@ extern "C" int hm_update_run(hm_ctx_t h, const double *W_prior, double *X, doubl
             // (the event now; the launches when this iteration's own launches are queued and the host has nothing to do
             // but wait: eight launches here kept the first system of the frame waiting for the host, ~17 us per iteration
             // on average in the kernel trace)
-            if (!h->ev_m0) HM_HIP(hipEventCreateWithFlags(&h->ev_m0, hipEventDisableTiming));
+            HM_HIP(h->own.event(&h->ev_m0));
             HM_HIP(hipEventRecord(h->ev_m0, h->stream));
         }
         if (collected) h->X0 = Xcur;               // the state of the reference render (hm_jz / hm_j)
@@ -1887,13 +1816,8 @@ extern "C" int hm_update_run(hm_ctx_t h, const double *W_prior, double *X, doubl
     rc = ctx_join(h);                              // (a tail nobody has joined since: an update without iterations)
     if (rc) return rc;
     if (!W_out && h->tail_split) {
-        if (!h->stream4) {
-            int least = 0, greatest = 0;
-            HM_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            if (greatest != least) { HM_HIP(hipStreamCreateWithPriority(&h->stream4, hipStreamNonBlocking, greatest)); }
-            else HM_HIP(hipStreamCreateWithFlags(&h->stream4, hipStreamNonBlocking));
-            HM_HIP(hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));
-        }
+        HM_HIP(h->own.stream(&h->stream4));
+        HM_HIP(h->own.event(&h->ev_tail));
         ts = h->stream4;
     }
     const long long tail_ticket = niter > 0 ? ++h->run_ticket : h->run_ticket;
@@ -2035,17 +1959,10 @@ static int cov_predict_core(hm_ctx *h, const double *W_in, int n_bars, const int
                 bar[fill[q]] = i; other[fill[q]++] = p;
             }
         }
-        if (!h->d_sp_off) HM_HIP(hm_malloc((void **)&h->d_sp_off, (size_t)(N + 1) * sizeof(int)));
-        if ((size_t)n_bars > h->sp_cap) {
-            if (h->d_sp_bar) (void)hipFree(h->d_sp_bar);
-            if (h->d_sp_other) (void)hipFree(h->d_sp_other);
-            if (h->d_sp_blk) (void)hipFree(h->d_sp_blk);
-            h->d_sp_bar = h->d_sp_other = nullptr; h->d_sp_blk = nullptr;
-            HM_HIP(hm_malloc((void **)&h->d_sp_bar, 2 * (size_t)n_bars * sizeof(int)));
-            HM_HIP(hm_malloc((void **)&h->d_sp_other, 2 * (size_t)n_bars * sizeof(int)));
-            HM_HIP(hm_malloc((void **)&h->d_sp_blk, 3 * (size_t)n_bars * sizeof(double)));
-            h->sp_cap = n_bars;
-        }
+        HM_HIP(h->own.alloc(&h->d_sp_off, (size_t)(N + 1) * sizeof(int)));
+        HM_HIP(h->own.grow(&h->d_sp_bar, 2 * (size_t)n_bars * sizeof(int)));
+        HM_HIP(h->own.grow(&h->d_sp_other, 2 * (size_t)n_bars * sizeof(int)));
+        HM_HIP(h->own.grow(&h->d_sp_blk, 3 * (size_t)n_bars * sizeof(double)));
         HM_HIP(hipMemcpyAsync(h->d_sp_off, off.data(), (size_t)(N + 1) * sizeof(int), hipMemcpyHostToDevice, st));
         if (n_bars > 0) {
             HM_HIP(hipMemcpyAsync(h->d_sp_bar, bar.data(), bar.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -2121,12 +2038,7 @@ static int queue_predict_ahead(hm_ctx *h, const double *X, int n_bars, const int
 {
     for (int i = 0; i < 2 * n_bars; i++)
         if (bars[i] < 0 || bars[i] >= h->N) return HM_OK;                 // the caller's own hm_cov_predict reports it
-    if ((size_t)n_bars > h->pin_blk_cap) {
-        if (h->pin_blk) (void)hipHostFree(h->pin_blk);
-        h->pin_blk = nullptr; h->pin_blk_cap = 0;
-        HM_HIP(hipHostMalloc((void **)&h->pin_blk, 3 * (size_t)n_bars * sizeof(double), hipHostMallocDefault));
-        h->pin_blk_cap = n_bars;
-    }
+    HM_HIP(h->own.host_grow(&h->pin_blk, 3 * (size_t)n_bars * sizeof(double), hipHostMallocDefault));
     spring_blocks(n_bars, bars, l0, kappa, X, h->pin_blk);
     double *const post = h->d_Wres;
     int rc = cov_predict_core(h, nullptr, n_bars, bars, h->pin_blk, dt, dt / M, eps_F, nullptr, true, st);
@@ -2192,22 +2104,16 @@ extern "C" int hm_ms_predict(hm_ctx_t h, int n_bars, const int32_t *bars, const 
     const bool on_device = lds <= 160 * 1024;
     if (on_device) {
         { const int rc2 = ensure_stream2(h); if (rc2) return rc2; }
-        if (!h->d_nX) {
-            HM_HIP(hm_malloc((void **)&h->d_nX, (size_t)n4 * sizeof(double)));
-            HM_HIP(hm_malloc((void **)&h->d_nvoff, (size_t)(N + 1) * sizeof(int)));
-            HM_HIP(hm_malloc((void **)&h->d_ninfo, 2 * sizeof(int)));
+        if (!h->newton_ready) {
+            HM_HIP(h->own.alloc(&h->d_nX, (size_t)n4 * sizeof(double)));
+            HM_HIP(h->own.alloc(&h->d_nvoff, (size_t)(N + 1) * sizeof(int)));
+            HM_HIP(h->own.alloc(&h->d_ninfo, 2 * sizeof(int)));
             HM_HIP(hipFuncSetAttribute((const void *)k_ms_newton, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            h->newton_ready = true;
         }
-        if ((size_t)n_bars > h->ncap) {
-            if (h->d_nbars) (void)hipFree(h->d_nbars);
-            if (h->d_nvbar) (void)hipFree(h->d_nvbar);
-            if (h->d_nl0) (void)hipFree(h->d_nl0);
-            h->d_nbars = h->d_nvbar = nullptr; h->d_nl0 = nullptr; h->ncap = 0;
-            HM_HIP(hm_malloc((void **)&h->d_nbars, 2 * (size_t)n_bars * sizeof(int)));
-            HM_HIP(hm_malloc((void **)&h->d_nvbar, 2 * (size_t)n_bars * sizeof(int)));
-            HM_HIP(hm_malloc((void **)&h->d_nl0, (size_t)n_bars * sizeof(double)));
-            h->ncap = n_bars;
-        }
+        HM_HIP(h->own.grow(&h->d_nbars, 2 * (size_t)n_bars * sizeof(int)));
+        HM_HIP(h->own.grow(&h->d_nvbar, 2 * (size_t)n_bars * sizeof(int)));
+        HM_HIP(h->own.grow(&h->d_nl0, (size_t)n_bars * sizeof(double)));
         std::vector<int> off(N + 1, 0), vbar(2 * (size_t)n_bars);
         for (int i = 0; i < n_bars; i++) { off[bars[2 * i] + 1]++; off[bars[2 * i + 1] + 1]++; }
         for (int v = 0; v < N; v++) off[v + 1] += off[v];
@@ -2260,24 +2166,25 @@ extern "C" int hm_newton_dev_start(hm_ctx_t h, int N, int n_bars, const int32_t 
 {
     HM_ARG(h && bars && l0 && X && n_bars >= 1, "hm_newton_dev_start: bad argument");
     if (N != h->N || N > NEWTON4_NT) return 1;
+    // it may create the resources below, so the tail of the last update must not be queueing (hm_ms_newton_start calls
+    // it between frames); the prefactor worker, which creates nothing, goes on
+    if (const int rc = helper_join(h)) return rc;
     HM_HIP(hipSetDevice(h->device));
     if (h->n4_pending) {                          // a prediction nobody fetched: let it finish (its result block is dropped)
         HM_HIP(hipStreamSynchronize(h->stream3));
         h->n4_pending = false;
     }
-    if (!h->stream3) {
-        int least = 0, greatest = 0;
-        HM_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        if (greatest != least) { HM_HIP(hipStreamCreateWithPriority(&h->stream3, hipStreamNonBlocking, greatest)); }
-        else HM_HIP(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking));
+    if (!h->n4_ready) {
+        HM_HIP(h->own.stream(&h->stream3));
         // page-locked and coherent (hipHostMalloc without flags already is: the flag states the intent, it was not the
         // cause of round 3's wrong tracks -- host_block.h has that story): [X in (4N) | a result block of 4N + 2 values]
         const size_t words = (size_t)4 * N + 2 * ((size_t)4 * N + 2);
-        HM_HIP(hipHostMalloc((void **)&h->pin_n4, words * sizeof(double), hipHostMallocCoherent));
+        HM_HIP(h->own.host_alloc(&h->pin_n4, words * sizeof(double), hipHostMallocCoherent));
         memset(h->pin_n4, 0, words * sizeof(double));
-        HM_HIP(hm_malloc((void **)&h->d_n4X, ((size_t)4 * N + 2) * sizeof(double)));
+        HM_HIP(h->own.alloc(&h->d_n4X, ((size_t)4 * N + 2) * sizeof(double)));
         h->n4v.assign((size_t)4 * N + 2, 0.0);
-        HM_HIP(hipEventCreateWithFlags(&h->ev_n4, hipEventDisableTiming));
+        HM_HIP(h->own.event(&h->ev_n4));
+        h->n4_ready = true;
     }
     const bool same = h->n4_bars.size() == 2 * (size_t)n_bars && memcmp(h->n4_bars.data(), bars, 2 * (size_t)n_bars * sizeof(int32_t)) == 0;
     if (!same) {
@@ -2285,7 +2192,7 @@ extern "C" int hm_newton_dev_start(hm_ctx_t h, int N, int n_bars, const int32_t 
         std::vector<int> deg(N, 0);
         for (int i = 0; i < 2 * n_bars; i++) deg[bars[i]]++;
         const int maxdeg = *std::max_element(deg.begin(), deg.end());
-        h->n4_bars.assign(bars, bars + 2 * (size_t)n_bars);
+        h->n4_bars.clear();                       // (the springs of the table once it is on the device)
         h->n4_l0.clear();
         h->n4deg = maxdeg <= 8 ? 8 : maxdeg <= 12 ? 12 : 0;
         if (h->n4deg) {
@@ -2298,24 +2205,19 @@ extern "C" int hm_newton_dev_start(hm_ctx_t h, int N, int n_bars, const int32_t 
                 nbr[(size_t)a * D + fill[a]] = b; nbb[(size_t)a * D + fill[a]++] = i;
                 nbr[(size_t)b * D + fill[b]] = a; nbb[(size_t)b * D + fill[b]++] = i;
             }
-            if ((size_t)n_bars > h->n4cap || !h->d_n4nbr) {
-                void *q[] = {h->d_n4nbr, h->d_n4nbb, h->d_n4bars, h->d_n4l0};
-                for (void *x : q) if (x) (void)hipFree(x);
-                h->d_n4nbr = h->d_n4nbb = h->d_n4bars = nullptr; h->d_n4l0 = nullptr; h->n4cap = 0;
-                HM_HIP(hm_malloc((void **)&h->d_n4nbr, (size_t)N * 12 * sizeof(int)));
-                HM_HIP(hm_malloc((void **)&h->d_n4nbb, (size_t)N * 12 * sizeof(int)));
-                HM_HIP(hm_malloc((void **)&h->d_n4bars, 2 * (size_t)n_bars * sizeof(int)));
-                HM_HIP(hm_malloc((void **)&h->d_n4l0, (size_t)n_bars * sizeof(double)));
-                h->n4cap = n_bars;
-            }
+            HM_HIP(h->own.alloc(&h->d_n4nbr, (size_t)N * 12 * sizeof(int)));
+            HM_HIP(h->own.alloc(&h->d_n4nbb, (size_t)N * 12 * sizeof(int)));
+            HM_HIP(h->own.grow(&h->d_n4bars, 2 * (size_t)n_bars * sizeof(int)));
+            HM_HIP(h->own.grow(&h->d_n4l0, (size_t)n_bars * sizeof(double)));
             // on the kernel's own stream and waited for (nbr / nbb are locals): ordered before the launch by the stream
             // itself rather than by hipMemcpy's return (that was not the cause of round 3's wrong tracks either -- a track
             // uploads these tables once, the wrong predictions came at frame 13 -- but it is the form that needs no argument)
             HM_HIP(hipMemcpyAsync(h->d_n4nbr, nbr.data(), nbr.size() * sizeof(int), hipMemcpyHostToDevice, h->stream3));
             HM_HIP(hipMemcpyAsync(h->d_n4nbb, nbb.data(), nbb.size() * sizeof(int), hipMemcpyHostToDevice, h->stream3));
-            HM_HIP(hipMemcpyAsync(h->d_n4bars, h->n4_bars.data(), 2 * (size_t)n_bars * sizeof(int), hipMemcpyHostToDevice, h->stream3));
+            HM_HIP(hipMemcpyAsync(h->d_n4bars, bars, 2 * (size_t)n_bars * sizeof(int), hipMemcpyHostToDevice, h->stream3));
             HM_HIP(hipStreamSynchronize(h->stream3));            // (nbr / nbb are locals)
         }
+        h->n4_bars.assign(bars, bars + 2 * (size_t)n_bars);
     }
     if (!h->n4deg) return 1;
     if (h->n4_l0.size() != (size_t)n_bars || memcmp(h->n4_l0.data(), l0, (size_t)n_bars * sizeof(double)) != 0) {
@@ -2454,19 +2356,17 @@ extern "C" int hm_chain_states(hm_ctx_t h, double *predicted, double *projected,
 // ---- views of a context (reference renderer.py:436-475 screenshot, :595-628 draw; kalman.py:638-674 plotforces) ------
 static int view_buffers(hm_ctx *h)
 {
-    if (h->d_vX) return HM_OK;
     const size_t n = (size_t)h->W * h->H;
-    const int rc = alloc_targets(h->V, n);
-    if (rc) return rc;
-    HM_HIP(hm_malloc((void **)&h->d_vsetup, (size_t)h->T * sizeof(TriSetup)));
-    HM_HIP(hm_malloc((void **)&h->d_vids, n * sizeof(int)));
-    HM_HIP(hm_malloc((void **)&h->d_vlab, (size_t)h->T * sizeof(int)));
-    HM_HIP(hm_malloc((void **)&h->d_vwire, n * sizeof(unsigned)));
-    HM_HIP(hm_malloc((void **)&h->d_vmm, 2 * sizeof(unsigned)));
-    HM_HIP(hm_malloc((void **)&h->d_vforce, (size_t)10 * h->N * sizeof(double)));
-    HM_HIP(hm_malloc((void **)&h->d_vout, 3 * n));
-    HM_HIP(hipEventCreateWithFlags(&h->ev_view, hipEventDisableTiming));
-    HM_HIP(hm_malloc((void **)&h->d_vX, (size_t)4 * h->N * sizeof(double)));
+    HM_HIP(alloc_targets(h->own, h->V, n));
+    HM_HIP(h->own.alloc(&h->d_vsetup, (size_t)h->T * sizeof(TriSetup)));
+    HM_HIP(h->own.alloc(&h->d_vids, n * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->d_vlab, (size_t)h->T * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->d_vwire, n * sizeof(unsigned)));
+    HM_HIP(h->own.alloc(&h->d_vmm, 2 * sizeof(unsigned)));
+    HM_HIP(h->own.alloc(&h->d_vforce, (size_t)10 * h->N * sizeof(double)));
+    HM_HIP(h->own.alloc(&h->d_vout, 3 * n));
+    HM_HIP(h->own.event(&h->ev_view));
+    HM_HIP(h->own.alloc(&h->d_vX, (size_t)4 * h->N * sizeof(double)));
     return HM_OK;
 }
 
@@ -2552,6 +2452,7 @@ extern "C" int hm_view(hm_ctx_t h, const double *X, int which, const int32_t *pa
 {
     HM_ARG(h && bgr, "hm_view: NULL argument");
     HM_ARG(which >= VIEW_RAW && which <= VIEW_FLOWY, "hm_view: view %d outside 0..%d", which, VIEW_FLOWY);
+    HM_JOIN_LAZY(h);                             // (view_buffers may create resources: the helper must not be queueing)
     HM_HIP(hipSetDevice(h->device));
     int rc = view_buffers(h);
     if (rc) return rc;
@@ -2577,6 +2478,7 @@ extern "C" int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, c
                               const double *fv, const double *mv, uint8_t *bgr)
 {
     HM_ARG(h && bgr && orig && pred && tv && fv && mv, "hm_view_forces: NULL argument");
+    HM_JOIN_LAZY(h);                             // (view_buffers may create resources: the helper must not be queueing)
     HM_HIP(hipSetDevice(h->device));
     int rc = view_buffers(h);
     if (rc) return rc;

@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstdint>
 #include <cstdlib>
+#include <unordered_map>
+#include <vector>
 #include "../../include/hydra_mi.h"
 
 void hm_set_error(const char *fmt, ...);
@@ -54,3 +56,104 @@ static inline hipError_t hm_malloc(void **p, size_t bytes, int cls = HM_ALLOC_CL
     }
     return e;
 }
+
+// The GPU resources of one native handle (hm_ctx, hm_brox): every device allocation, page-locked host allocation, stream
+// and event the handle creates is recorded here, and release() frees them all.  Allocations are recorded by address, not
+// by field: the handles swap and alias their pointers (render targets, state buffers, the resident covariance, the
+// pool's area), and the kernel-argument structs hold them raw -- whichever field holds an address, it is freed once.
+// The calls that create are idempotent on the field they fill: a non-null field is left as it is (alloc, host_alloc,
+// stream, event) or kept while its allocation is large enough (grow, host_grow), so a lazily built group of resources
+// can simply be built again after a failure part-way.
+// No lock: one thread at a time uses a handle's owner.  For the filter handle that is the caller's thread, or the helper
+// thread while it queues an update's tail (which grows the spring arrays and builds the projection buffers); every entry
+// point that creates anything waits for the helper first (ctx_join), and hm_update_arm_* and the prefactor worker, which
+// do not wait, create nothing.
+namespace {
+struct HmOwner {
+    struct Mem { size_t bytes; bool host; };
+    int cls;                                   // the HYDRA_MI_POISON class of the device allocations (hm_malloc)
+    std::unordered_map<void *, Mem> mem;
+    std::vector<hipEvent_t> events;
+    std::vector<hipStream_t> streams;
+
+    explicit HmOwner(int cls) : cls(cls) {}
+    HmOwner(const HmOwner &) = delete;
+    HmOwner &operator=(const HmOwner &) = delete;
+
+    template <typename T> hipError_t alloc(T **p, size_t bytes) { return *p ? hipSuccess : grow(p, bytes); }
+    template <typename T> hipError_t grow(T **p, size_t bytes) { return take((void **)p, bytes, false, 0); }
+    template <typename T> hipError_t host_alloc(T **p, size_t bytes, unsigned flags)
+    {
+        return *p ? hipSuccess : host_grow(p, bytes, flags);
+    }
+    template <typename T> hipError_t host_grow(T **p, size_t bytes, unsigned flags) { return take((void **)p, bytes, true, flags); }
+    // a non-blocking stream, at the device's greatest priority when it offers a range of them and `greatest` is set
+    hipError_t stream(hipStream_t *s, bool greatest = true)
+    {
+        if (*s) return hipSuccess;
+        int least = 0, most = 0;
+        hipError_t e = greatest ? hipDeviceGetStreamPriorityRange(&least, &most) : hipSuccess;
+        if (e == hipSuccess)
+            e = greatest && most != least ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, most)
+                                          : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+        return keep(streams, s, e);
+    }
+    // a stream on the compute units of `mask` (hipExtStreamCreateWithCUMask)
+    hipError_t cu_stream(hipStream_t *s, const std::vector<uint32_t> &mask)
+    {
+        if (*s) return hipSuccess;
+        return keep(streams, s, hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data()));
+    }
+    hipError_t event(hipEvent_t *ev, unsigned flags = hipEventDisableTiming)
+    {
+        if (*ev) return hipSuccess;
+        return keep(events, ev, hipEventCreateWithFlags(ev, flags));
+    }
+    // destroys one stream of the handle and clears the field
+    hipError_t release(hipStream_t *s)
+    {
+        for (size_t i = 0; i < streams.size(); i++)
+            if (streams[i] == *s) {
+                streams.erase(streams.begin() + i);
+                const hipError_t e = hipStreamDestroy(*s);
+                *s = nullptr;
+                return e;
+            }
+        return hipSuccess;
+    }
+    // waits for every stream of the handle
+    void drain()
+    {
+        for (hipStream_t s : streams) (void)hipStreamSynchronize(s);
+    }
+    // everything: memory first, then events, then streams (the streams must be idle)
+    void release()
+    {
+        for (const auto &m : mem) (void)(m.second.host ? hipHostFree(m.first) : hipFree(m.first));
+        for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+        for (hipStream_t s : streams) (void)hipStreamDestroy(s);
+        mem.clear(); events.clear(); streams.clear();
+    }
+
+  private:
+    hipError_t take(void **p, size_t bytes, bool host, unsigned flags)
+    {
+        const auto it = *p ? mem.find(*p) : mem.end();
+        if (bytes <= (it != mem.end() ? it->second.bytes : 0)) return hipSuccess;
+        if (it != mem.end()) {
+            (void)(it->second.host ? hipHostFree(*p) : hipFree(*p));
+            mem.erase(it);
+        }
+        *p = nullptr;
+        const hipError_t e = host ? hipHostMalloc(p, bytes, flags) : hm_malloc(p, bytes, cls);
+        if (*p) mem[*p] = Mem{bytes, host};   // (also when hm_malloc's poison fill failed: it is freed with the rest)
+        return e;
+    }
+    template <typename H> static hipError_t keep(std::vector<H> &list, H *x, hipError_t e)
+    {
+        if (e == hipSuccess) list.push_back(*x);
+        else *x = nullptr;
+        return e;
+    }
+};
+}  // namespace
