@@ -403,6 +403,34 @@ int hm_view_dev(hm_ctx_t h, const double *X, int which, const int32_t *palette, 
 int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, const double *pred, const double *tv,
                    const double *fv, const double *mv, uint8_t *bgr);
 
+/* The body-frame readout: frames pulled back through the tracked mesh into the coordinates of its texture
+ * (the frame-0 pixel grid of the initial vertices uv), the neuron-tracking layer the reference leaves
+ * unbuilt (test_neurontracking.py:15; its synthetic neurons move with the animal, synth.py:219-266).
+ *   body map  every pixel (r, c) takes the lowest-indexed triangle that covers its centre at X = uv, by
+ *             the render's rule (snapped positions, exact edge functions, top-left ties, orientation
+ *             swap), or -1, and l1 = e1 / area, l2 = e2 / area (binary64, correctly rounded, the
+ *             swapped vertex order i0, i1, i2).  Built once per handle, on first use.
+ *   warp      x = (X[i0] + l1 (X[i1] - X[i0])) + l2 (X[i2] - X[i0]) in binary64, the same for y; the
+ *             frame sampled bilinearly at (x - 0.5, y - 0.5), texels clamped to the frame, rint half to
+ *             even; 0 outside the map and where x or y is not finite or beyond +-2^20 px.
+ *   sums      uint64 sums of the registered values per triangle (T) and per label (L) of the label
+ *             image, overwritten on every call; labels count only on pixels of the map.
+ * hm_body_map: the triangle per pixel (W*H, may be NULL) and the pixels per triangle (T, may be NULL).
+ * hm_body_set_labels: a W*H label image in body coordinates, -1 = none, labels 0..L-1 (NULL clears);
+ * counts (L, may be NULL): the map pixels per label.
+ * hm_body_warp: host arrays; frame W*H gray, out W*H (may be NULL), sums may be NULL; tri_sums holds T
+ * values, label_sums the L of the last hm_body_set_labels (the caller keeps that count: there is no length here).
+ * hm_body_warp_dev: device arrays queued on the handle's stream; out_channels 1 or 3 (B = G = R, the AVI's
+ * layout), d_out 4-byte aligned or NULL, the sums 8-byte aligned (sizes as for hm_body_warp); `stream` (may be
+ * NULL) waits for the warp on the device.
+ * hm_body_fence: `stream` waits on the device for the last warp queued (before it overwrites its frame). */
+int hm_body_map(hm_ctx_t h, int32_t *tri_of_pixel, uint32_t *tri_counts);
+int hm_body_set_labels(hm_ctx_t h, const int32_t *labels, int L, uint32_t *counts);
+int hm_body_warp(hm_ctx_t h, const double *X, const uint8_t *frame, uint8_t *out, uint64_t *tri_sums, uint64_t *label_sums);
+int hm_body_warp_dev(hm_ctx_t h, const double *X, const void *d_frame, void *d_out, int out_channels,
+                     void *d_tri_sums, void *d_label_sums, void *stream);
+int hm_body_fence(hm_ctx_t h, void *stream);
+
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
  * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the

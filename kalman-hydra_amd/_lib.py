@@ -120,6 +120,11 @@ SIGNATURES = {
     "hm_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_view_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     "hm_view_forces": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hm_body_map": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "hm_body_set_labels": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp]),
+    "hm_body_warp": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hm_body_warp_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "hm_body_fence": (ctypes.c_int, [c_vp, c_vp]),
     "hm_flow_preview": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                        c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_avi_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,

@@ -1,0 +1,351 @@
+"""Body-frame readout of a track: the frames in the animal's own coordinates, points marked in frame 0 followed through
+the mesh, and intensity traces of body regions (the neuron tracking the reference's synthetic neurons are made for,
+reference gen_synthetic_neurons.py, synth.py:219-266, and that its test_neurontracking.py:15 leaves unbuilt).
+
+Body coordinates are the frame-0 pixel grid of the texture coordinates uv (the initial vertices).  The mesh maps every
+triangle from uv to its place in frame k (the state X); pulling frame k back through that piecewise-affine map gives the
+registered frame.  The registered frames and the sums of their values per triangle and per label are computed on the
+device (hm_body_* in include/hydra_mi.h, csrc/body_kernels.h); points are located and tracked here, on the host, by the
+same coverage rule and the same position formula, so a point at a pixel centre gets exactly that pixel's position.
+
+    body = BodyReadout(kf, points=read_points_csv("neurons.csv")[1])
+    for each frame: kf.compute(...); reg, tri_means, point_means = body.frame(kf.state.X, raw_frame)
+    res = body.results()          # tri_means (F x T), points (F x P x 2), point_means (F x P), ...
+
+FlowEKFPipeline.run(body=body) queues the same readout on the device after every step (BodyTap).
+"""
+import ctypes
+import threading
+
+import numpy as np
+
+from . import _lib
+
+SUB = 256          # the render's sub-pixel grid (csrc/ekf_kernels.h EKF_SUB)
+
+
+def read_points_csv(path):
+    """reference synth.py:227-231: lines ``name,x,y`` -> (names, (P, 2) float64 in body coordinates)."""
+    names, pts = [], []
+    with open(path) as f:
+        for line in f:
+            parts = line.strip().split(",")
+            if len(parts) < 3:
+                continue
+            try:
+                x, y = float(parts[1]), float(parts[2])
+            except ValueError:               # a header line
+                continue
+            names.append(parts[0])
+            pts.append([x, y])
+    return names, np.array(pts, np.float64).reshape(-1, 2)
+
+
+def write_points_txt(path, points):
+    """reference synth.py:245-266: one line ``neurons,x0,y0,x1,y1,...`` per frame; points (F, P, 2).  Values are written
+    as repr() of the float (``nan`` for a point outside the mesh), so they read back exactly."""
+    pts = np.asarray(points, np.float64)
+    with open(path, "w") as f:
+        for row in pts.reshape(pts.shape[0], -1):
+            f.write("neurons," + ",".join(repr(float(v)) for v in row) + "\n")
+
+
+def read_points_txt(path):
+    """The inverse of write_points_txt -> (F, P, 2)."""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            parts = line.strip().split(",")
+            if parts and parts[0] == "neurons":
+                rows.append([float(v) for v in parts[1:]])
+    return np.array(rows, np.float64).reshape(len(rows), -1, 2)
+
+
+def disc_labels(tri_of_pixel, points, radius):
+    """Label image of point discs: each map pixel (tri_of_pixel >= 0) whose centre (c + 0.5, r + 0.5) lies within
+    `radius` of a point, distance^2 <= radius^2 in float64, gets that point's index; the nearest point wins, the lower
+    index on a tie.  -1 elsewhere."""
+    tri = np.asarray(tri_of_pixel)
+    H, W = tri.shape
+    pts = np.asarray(points, np.float64).reshape(-1, 2)
+    lab = np.full((H, W), -1, np.int32)
+    best = np.full((H, W), np.inf)
+    r = float(radius)
+    r2 = r * r
+    for i, (qx, qy) in enumerate(pts):
+        if not (np.isfinite(qx) and np.isfinite(qy)):
+            continue
+        c0, c1 = max(0, int(np.floor(qx - r - 1))), min(W, int(np.ceil(qx + r + 1)) + 1)
+        r0, r1 = max(0, int(np.floor(qy - r - 1))), min(H, int(np.ceil(qy + r + 1)) + 1)
+        if c0 >= c1 or r0 >= r1:
+            continue
+        cx = np.arange(c0, c1, dtype=np.float64) + 0.5
+        cy = np.arange(r0, r1, dtype=np.float64) + 0.5
+        d2 = (cx[None, :] - qx) ** 2 + (cy[:, None] - qy) ** 2
+        sl = (slice(r0, r1), slice(c0, c1))
+        take = (d2 <= r2) & (d2 < best[sl]) & (tri[sl] >= 0)      # (strictly nearer: a tie keeps the lower index)
+        best[sl] = np.where(take, d2, best[sl])
+        lab[sl] = np.where(take, i, lab[sl])
+    return lab
+
+
+def locate(uv, tri, points):
+    """Points q (P, 2) in body coordinates -> (triangle (P,) int64, -1 outside every triangle; l1, l2 (P,) float64).
+    The render's coverage rule at the snapped point rint(256 q) instead of a pixel centre (positions uv snapped to
+    1/256 px, exact integer edge functions, top-left ties, the orientation swap), the lowest triangle index first;
+    l1 = e1 / area, l2 = e2 / area, the vertex ids in the swapped order."""
+    P = np.rint(np.asarray(uv, np.float64) * SUB).astype(np.int64)
+    q = np.asarray(points, np.float64).reshape(-1, 2)
+    tri = np.asarray(tri, np.int64)
+    n = q.shape[0]
+    out_t = np.full(n, -1, np.int64)
+    out_ids = np.zeros((n, 3), np.int64)
+    l1 = np.zeros(n)
+    l2 = np.zeros(n)
+    for k in range(n):
+        if not (np.isfinite(q[k]).all() and np.abs(q[k]).max() < 2.0 ** 24):
+            continue
+        px, py = (int(v) for v in np.rint(q[k] * SUB))
+        for t, (i0, i1, i2) in enumerate(tri):
+            i0, i1, i2 = int(i0), int(i1), int(i2)
+            (x0, y0), (x1, y1), (x2, y2) = P[i0].tolist(), P[i1].tolist(), P[i2].tolist()
+            area = (x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0)
+            if area == 0:
+                continue
+            if area < 0:
+                i1, i2 = i2, i1
+                (x1, y1), (x2, y2) = (x2, y2), (x1, y1)
+                area = -area
+            e0 = (x2 - x1) * (py - y1) - (y2 - y1) * (px - x1)
+            e1 = (x0 - x2) * (py - y2) - (y0 - y2) * (px - x2)
+            e2 = (x1 - x0) * (py - y0) - (y1 - y0) * (px - x0)
+
+            def inside(e, dx, dy):
+                return e > 0 or (e == 0 and (dy > 0 or (dy == 0 and dx < 0)))
+            if inside(e0, x2 - x1, y2 - y1) and inside(e1, x0 - x2, y0 - y2) and inside(e2, x1 - x0, y1 - y0):
+                out_t[k] = t
+                out_ids[k] = (i0, i1, i2)
+                l1[k] = e1 / area                        # Python integers: one correctly rounded division
+                l2[k] = e2 / area
+                break
+    return out_t, out_ids, l1, l2
+
+
+def track(pos, ids, l1, l2, inside):
+    """Positions (P, 2) in the frame whose vertex positions are pos (2N values, x0, y0, x1, ...):
+    (X[i0] + l1 (X[i1] - X[i0])) + l2 (X[i2] - X[i0]) in binary64; NaN for the points not inside."""
+    pos = np.asarray(pos, np.float64).reshape(-1, 2)
+    n = len(l1)
+    out = np.full((n, 2), np.nan)
+    if n == 0:
+        return out
+    a, b, c = pos[ids[:, 0]], pos[ids[:, 1]], pos[ids[:, 2]]
+    p = (a + l1[:, None] * (b - a)) + l2[:, None] * (c - a)
+    out[inside] = p[inside]
+    return out
+
+
+def _means(sums, counts):
+    s = np.asarray(sums, np.float64)
+    c = np.asarray(counts, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(c > 0, s / np.where(c > 0, c, 1.0), np.nan)
+
+
+class BodyReadout:
+    """The body-frame readout of one tracker (a kalman.*KalmanFilter or a renderer.Renderer).
+
+    points: (P, 2) points in body coordinates, followed through the mesh (``track``) and read out over discs of
+    point_radius px (``disc_labels``); labels: an (H, W) int32 label image in body coordinates (-1: none) instead of
+    the discs; video: an AviWriter of the frame size that receives the registered frames (B = G = R)."""
+
+    def __init__(self, kf_or_renderer, points=None, point_radius=3.0, labels=None, video=None):
+        r = kf_or_renderer.state.renderer if hasattr(kf_or_renderer, "state") else kf_or_renderer
+        self.r = r
+        self.H, self.W, self.T = r.ny, r.nx, int(r.tri.shape[0])
+        self.video = video
+        if video is not None and (video.width, video.height) != (self.W, self.H):
+            raise ValueError("a %dx%d video for %dx%d frames" % (video.width, video.height, self.W, self.H))
+        self.tri_of_pixel, self.tri_counts = r.body_map()
+        if points is not None and labels is not None:
+            raise ValueError("BodyReadout: give points (their discs are the labels) or a label image, not both")
+        self.points = None if points is None else np.asarray(points, np.float64).reshape(-1, 2)
+        self.point_radius = float(point_radius)
+        self.outside = np.zeros(0, bool)
+        if self.points is not None:
+            self.locate(self.points)
+            labels = disc_labels(self.tri_of_pixel, self.points, self.point_radius)
+            L = self.points.shape[0]
+        elif labels is not None:
+            labels = np.ascontiguousarray(labels, np.int32)
+            L = int(labels.max()) + 1 if labels.size else 0
+        self.labels = labels
+        self.L = 0
+        # the handle holds one label image: this readout sets (or clears) it, and a later readout or body_set_labels on
+        # the same tracker replaces it -- this one then refuses to go on (_own_labels)
+        if labels is not None and L > 0:
+            self.label_counts = r.body_set_labels(labels, L)
+            self.L = L
+        else:
+            self.label_counts = r.body_set_labels(None, 0)
+        self._labels = r.body_labels
+        self._rows = []         # per state passed: [positions or None, tri sums, label sums]
+
+    # -- points -----------------------------------------------------------------------------------------
+    def locate(self, points):
+        """-> (triangle, l1, l2) of every point (triangle -1: outside the mesh); keeps them for ``track``."""
+        t, ids, l1, l2 = locate(self.r.uv, self.r.tri, points)
+        self._loc = (t, ids, l1, l2)
+        self.outside = t < 0
+        return t, l1, l2
+
+    def track(self, X):
+        """Positions (P, 2) of the located points in the frame of state X (NaN outside the mesh)."""
+        t, ids, l1, l2 = self._loc
+        x = np.asarray(X, np.float64).reshape(-1)[:2 * self.r.n]
+        return track(x, ids, l1, l2, t >= 0)
+
+    # -- frames -----------------------------------------------------------------------------------------
+    def registered(self, X, frame):
+        """Frame (H, W) uint8 pulled back through the mesh at state X -> (H, W) uint8 in body coordinates."""
+        self._own_labels()
+        return self.r.body_warp(X, frame)[0]
+
+    def frame(self, X, frame):
+        """Read out one frame: -> (registered (H, W) uint8, triangle means (T,), label means (L,)); kept for results()
+        and written to the video, if any."""
+        self._own_labels()
+        reg, ts, ls = self.r.body_warp(X, frame)
+        self._keep(X, ts, ls)
+        if self.video is not None:
+            self.video.write(np.repeat(reg[:, :, None], 3, axis=2))
+        return reg, _means(ts, self.tri_counts), _means(ls, self.label_counts) if ls is not None else np.zeros(0)
+
+    def _own_labels(self):
+        if self.r.body_labels != self._labels:
+            raise RuntimeError("BodyReadout: the tracker's label image has been replaced since this readout set it (one "
+                               "readout per tracker at a time)")
+
+    def _keep(self, X, ts, ls):
+        pos = self.track(X) if self.points is not None else None
+        self._rows.append([pos, ts, ls])
+
+    def results(self):
+        """Arrays with one row per state passed: tri_sums / tri_means (F x T), tri_counts (T); with labels label_sums /
+        label_means (F x L), label_counts; with points also points (F x P x 2), point_means (F x P), point_counts (P)."""
+        F = len(self._rows)
+        ts = np.array([r[1] for r in self._rows], np.uint64).reshape(F, self.T)
+        out = {"tri_sums": ts, "tri_means": _means(ts, self.tri_counts[None, :]), "tri_counts": self.tri_counts.copy()}
+        if self.L > 0:
+            ls = np.array([r[2] for r in self._rows], np.uint64).reshape(F, self.L)
+            out.update(label_sums=ls, label_means=_means(ls, self.label_counts[None, :]),
+                       label_counts=self.label_counts.copy())
+        if self.points is not None:
+            P = self.points.shape[0]
+            out["points"] = np.array([r[0] for r in self._rows], np.float64).reshape(F, P, 2)
+            out["point_counts"] = self.label_counts.copy() if self.L > 0 else np.zeros(P, np.uint32)
+            out["point_means"] = out["label_means"] if self.L > 0 else np.full((F, P), np.nan)
+        return out
+
+
+class BodyTap:
+    """The readout of a pipeline run (FlowEKFPipeline.run(body=...)): after every step the warp of the raw frame at the
+    state the frame ended with is queued on the filter's stream (hm_body_warp_dev) into a ring of device slots -- its
+    sums, and the registered frame as B = G = R when the readout has a video --, copied into page-locked memory on a copy
+    stream of its own that waits for the warp, and taken by a writer thread (sums into the readout's rows, frames into
+    the video).  The frame ring may reuse the slot of a frame the warp reads only after the warp: ``frame`` hands the
+    ring a fence (hm_body_fence) that its copy stream waits on before its next upload."""
+
+    def __init__(self, body, device=0, slots=4):
+        import queue
+        self.b, self.device, self.slots = body, int(device), int(slots)
+        r = body.r
+        self.npx = r.nx * r.ny
+        self.ns = 8 * (body.T + body.L)                 # a slot: the sums (8-byte aligned), then the frame, if any
+        self.nv = 3 * self.npx if body.video is not None else 0
+        self.stride = self.ns + self.nv
+        L = _lib.lib()
+        self._stream = _lib.c_vp()
+        _lib.check(L.hm_copy_stream_create(self.device, ctypes.byref(self._stream)), "hm_copy_stream_create")
+        self._pin = _lib.c_vp()
+        _lib.check(L.hm_host_alloc(self.slots * self.stride, ctypes.byref(self._pin)), "hm_host_alloc")
+        from .pipeline import DeviceBuffer
+        self._dev = [DeviceBuffer(self.stride, device) for _ in range(self.slots)]
+        self._free = threading.Semaphore(self.slots)
+        self._q = queue.Queue()
+        self._next = 0
+        self._error = None
+        self._closed = False
+        self._thread = threading.Thread(target=self._write_loop, name="hydra_mi-body", daemon=True)
+        self._thread.start()
+        _lib.register(self, 0)
+
+    def frame(self, X, d_frame, ring=None):
+        """Queue the readout of the raw frame at device address d_frame at state X (a frame of `ring`, if given)."""
+        if self._error is not None:
+            raise self._error
+        self.b._own_labels()                        # (the slot holds the sums of this readout's L labels)
+        self._free.acquire()
+        s = self._next % self.slots
+        self._next += 1
+        d = self._dev[s].ptr
+        b = self.b
+        self.b._keep(X, None, None)
+        row = len(b._rows) - 1
+        b.r.body_warp_dev(X, d_frame, d + self.ns if self.nv else None, 3, d, d + 8 * b.T if b.L else None, self._stream)
+        if ring is not None:
+            ring.fence_after(lambda st: b.r.body_fence(st))
+        _lib.check(_lib.lib().hm_dev_download_async(self.device, self._pin.value + s * self.stride, d, self.stride,
+                                                    self._stream), "hm_dev_download_async")
+        self._q.put((s, row))
+
+    def _write_loop(self):
+        L = _lib.lib()
+        while True:
+            item = self._q.get()
+            if item is None:
+                return
+            s, row = item
+            try:
+                if self._error is None:
+                    _lib.check(L.hm_copy_stream_sync(self.device, self._stream), "hm_copy_stream_sync")
+                    base = self._pin.value + s * self.stride
+                    blk = np.ctypeslib.as_array(ctypes.cast(base, ctypes.POINTER(ctypes.c_uint64)),
+                                                shape=(self.b.T + self.b.L,)).copy()
+                    self.b._rows[row][1] = blk[:self.b.T]
+                    self.b._rows[row][2] = blk[self.b.T:] if self.b.L else None
+                    if self.nv:
+                        self.b.video.write_ptr(base + self.ns)
+            except Exception as e:          # noqa: BLE001 -- reported by the next frame() / close()
+                self._error = e
+            finally:
+                self._free.release()
+
+    def drain(self):
+        """Wait until every frame queued so far has been taken."""
+        for _ in range(self.slots):
+            self._free.acquire()
+        for _ in range(self.slots):
+            self._free.release()
+        if self._error is not None:
+            raise self._error
+
+    def close(self):
+        if self._closed:
+            return
+        self._closed = True
+        try:
+            self._q.put(None)
+            self._thread.join()
+        finally:
+            L = _lib.lib()
+            if self._stream:
+                L.hm_copy_stream_destroy(self.device, self._stream)
+                self._stream = None
+            for b in self._dev:
+                b.close()
+            if self._pin:
+                L.hm_host_free(self._pin)
+                self._pin = None
+        if self._error is not None:
+            raise self._error

@@ -1,0 +1,197 @@
+// The body-frame readout: frames pulled back through the tracked mesh into the coordinates of its texture (the frame-0
+// pixel grid of the initial vertices), with sums of the registered values over triangles and over caller labels.
+//
+// The body map (k_body_map, once per handle): every pixel (r, c) takes the lowest-indexed triangle of the mesh at
+// X = uv whose coverage -- the render's rule, snapped positions, exact integer edge functions at the pixel centre,
+// top-left ties -- includes it, or -1, and its barycentrics l1 = e1 / area, l2 = e2 / area as correctly rounded binary64
+// divisions of whole numbers (the vertex order after the render's orientation swap).
+// The warp (k_body_warp, per frame): the pixel's position in frame k, x = (X[i0] + l1 (X[i1] - X[i0])) + l2 (X[i2] - X[i0])
+// in binary64 (the library builds with -ffp-contract=off), a bilinear sample of the frame at (x - 0.5, y - 0.5) with the
+// texels clamped to the frame, rint half to even; 0 outside the map or for a position that is not finite or beyond
+// +-2^20 px.  tests/body_ref.py restates all of it in NumPy.
+#pragma once
+#include "ekf_kernels.h"
+#include "view_kernels.h"
+
+// Sums of val over the lanes of a wave by key, NK keys per lane (-1: none), one integer atomic per distinct key: the
+// first lane with a key left names it, the lanes add what they hold under it, a wave reduction, the atomic.  Exact and
+// independent of the order.  Every lane of the wave must call it (a wave's sum of at most 64 NK values of <= 255 fits
+// 32 bits).
+template <int NK, typename S>
+__device__ __forceinline__ void d_peel_add(const int (&key)[NK], const unsigned (&val)[NK], S *__restrict__ sums)
+{
+    unsigned pend = 0;
+#pragma unroll
+    for (int j = 0; j < NK; j++)
+        if (key[j] >= 0) pend |= 1u << j;
+    const int lane = __lane_id();
+    for (;;) {
+        const unsigned long long act = __ballot(pend != 0);
+        if (act == 0) break;
+        const int lead = __ffsll((unsigned long long)act) - 1;
+        int mine = -1;
+#pragma unroll
+        for (int j = NK - 1; j >= 0; j--)
+            if ((pend >> j) & 1u) mine = key[j];
+        const int k = __shfl(mine, lead);
+        unsigned s = 0;
+#pragma unroll
+        for (int j = 0; j < NK; j++)
+            if (((pend >> j) & 1u) && key[j] == k) { s += val[j]; pend &= ~(1u << j); }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += (unsigned)__shfl_xor((int)s, o);
+        if (lane == lead) atomicAdd(&sums[k], (S)s);
+    }
+}
+
+// X = uv (binary32 promoted), velocities 0: the configuration the body map is taken at
+__global__ __launch_bounds__(256) void k_body_uvX(const float *__restrict__ uv, int N, double *__restrict__ X)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 4 * N) X[i] = i < 2 * N ? (double)uv[i] : 0.0;
+}
+
+// One 16 x 16 tile per workgroup, the triangles binned as in k_render and visited in ascending order: the first that
+// covers the pixel is its triangle.  Writes the triangle per pixel (-1: none), its barycentrics, the pixels per triangle
+// (cnt, zeroed by the caller), and -- workgroup (0, 0) -- the vertex ids of every triangle in the setup's order.
+__global__ __launch_bounds__(EKF_TILE *EKF_TILE) void k_body_map(int W, int H, int T, const TriSetup *__restrict__ setup,
+                                                                 int *__restrict__ tri_of, double2 *__restrict__ bary,
+                                                                 int4 *__restrict__ tidx, unsigned *__restrict__ cnt)
+{
+    __shared__ unsigned s_mask[EKF_MAX_TRI / 32];
+    const int tid = threadIdx.y * EKF_TILE + threadIdx.x;
+    const int words = (T + 31) / 32;
+    for (int i = tid; i < words; i += EKF_TILE * EKF_TILE) s_mask[i] = 0;
+    __syncthreads();
+    const int c0 = blockIdx.x * EKF_TILE, r0 = blockIdx.y * EKF_TILE;
+    for (int t = tid; t < T; t += EKF_TILE * EKF_TILE) {
+        const TriSetup &s = setup[t];
+        if (s.cmin <= s.cmax && s.cmax >= c0 && s.cmin < c0 + EKF_TILE && s.rmax >= r0 && s.rmin < r0 + EKF_TILE)
+            atomicOr(&s_mask[t >> 5], 1u << (t & 31));
+        if (blockIdx.x == 0 && blockIdx.y == 0) tidx[t] = make_int4(s.i0, s.i1, s.i2, 0);
+    }
+    __syncthreads();
+    const int c = c0 + threadIdx.x, r = r0 + threadIdx.y;
+    int found = -1;
+    if (c < W && r < H) {
+        const double dc = (double)c, dr = (double)r;
+        double2 l = make_double2(0.0, 0.0);
+        for (int wd = 0; wd < words && found < 0; wd++) {
+            unsigned bits = s_mask[wd];
+            while (bits) {
+                const int b = __ffs(bits) - 1;
+                bits &= bits - 1;
+                const TriSetup &s = setup[wd * 32 + b];
+                double e1, e2;
+                if (!d_tri_cover2(s, dc, dr, e1, e2)) continue;
+                // whole numbers below 2^53 throughout (TriSetup): the edge values without the top-left bias and their
+                // sum, which is the area of the swapped vertex order, are exact
+                e1 -= s.tl[1] ? 1.0 : 0.0;
+                e2 -= s.tl[2] ? 1.0 : 0.0;
+                const double e0 = fma(s.ea[0], dc, fma(s.eb[0], dr, s.ec[0]));
+                const double area = (e0 + e1) + e2;
+                l = make_double2(e1 / area, e2 / area);
+                found = wd * 32 + b;
+                break;
+            }
+        }
+        const int p = r * W + c;
+        tri_of[p] = found;
+        bary[p] = l;
+    }
+    const int key[1] = {found};
+    const unsigned one[1] = {1u};
+    d_peel_add(key, one, cnt);
+}
+
+// pixels per label: labels of pixels of the map (-1 and pixels outside the map count nowhere); cnt zeroed by the caller
+__global__ __launch_bounds__(256) void k_body_label_count(const int *__restrict__ tri_of, const int *__restrict__ labels, int n,
+                                                          unsigned *__restrict__ cnt)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int key[1] = {p < n && tri_of[p] >= 0 ? labels[p] : -1};
+    const unsigned one[1] = {1u};
+    d_peel_add(key, one, cnt);
+}
+
+struct BodyWarpArgs {
+    int n, W, H, ch;                   // pixels, frame size, output channels (1, or 3: B = G = R)
+    const int *tri_of;                 // the body map
+    const double2 *bary;
+    const int4 *tidx;                  // vertex ids per triangle
+    const double *X;                   // positions of frame k (2N)
+    const uint8_t *frame;              // frame k, W x H
+    const int *labels;                 // the label image (W x H, -1: none), NULL: no label sums
+    uint8_t *out;                      // n x ch, NULL: sums only
+    unsigned long long *tsum, *lsum;   // sums per triangle / per label (zeroed by the caller), NULL: none
+};
+
+__device__ __forceinline__ unsigned d_body_px(const BodyWarpArgs &a, int t, double2 l)
+{
+    if (t < 0) return 0u;
+    const int4 v = a.tidx[t];
+    const double x0 = a.X[2 * v.x], y0 = a.X[2 * v.x + 1];
+    const double x1 = a.X[2 * v.y], y1 = a.X[2 * v.y + 1];
+    const double x2 = a.X[2 * v.z], y2 = a.X[2 * v.z + 1];
+    const double x = (x0 + l.x * (x1 - x0)) + l.y * (x2 - x0);
+    const double y = (y0 + l.x * (y1 - y0)) + l.y * (y2 - y0);
+    if (!(d_coord_ok(x) && d_coord_ok(y))) return 0u;
+    const double u = x - 0.5, w = y - 0.5;
+    const double fc = floor(u), fr = floor(w);
+    const double ax = u - fc, b = w - fr;
+    const int c0 = (int)fc, r0 = (int)fr;
+    const int ca = min(max(c0, 0), a.W - 1), cb = min(max(c0 + 1, 0), a.W - 1);
+    const int ra = min(max(r0, 0), a.H - 1), rb = min(max(r0 + 1, 0), a.H - 1);
+    const double f00 = a.frame[ra * a.W + ca], f01 = a.frame[ra * a.W + cb];
+    const double f10 = a.frame[rb * a.W + ca], f11 = a.frame[rb * a.W + cb];
+    const double val = (1.0 - b) * ((1.0 - ax) * f00 + ax * f01) + b * ((1.0 - ax) * f10 + ax * f11);
+    return (unsigned)rint(val);
+}
+
+// one gather per pixel, 4 pixels per thread; the region sums in the same pass.  No thread leaves before the sums: the
+// peeling loop needs every lane of its wave.
+__global__ __launch_bounds__(256) void k_body_warp(BodyWarpArgs a)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const int p0 = 4 * q;
+    int key[4] = {-1, -1, -1, -1};
+    unsigned val[4] = {0u, 0u, 0u, 0u};
+    const bool whole = p0 + 4 <= a.n;
+    if (whole) {
+        const int4 t = *(const int4 *)(a.tri_of + p0);
+        key[0] = t.x; key[1] = t.y; key[2] = t.z; key[3] = t.w;
+    } else {
+        for (int j = 0; j < 4; j++)
+            if (p0 + j < a.n) key[j] = a.tri_of[p0 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (key[j] >= 0) val[j] = d_body_px(a, key[j], a.bary[p0 + j]);
+    if (a.out) {
+        if (whole && a.ch == 1) {
+            *(unsigned *)(a.out + p0) = val[0] | (val[1] << 8) | (val[2] << 16) | (val[3] << 24);
+        } else if (whole) {            // B = G = R: 12 bytes as three dwords
+            unsigned *o = (unsigned *)(a.out + 12 * (size_t)q);
+            o[0] = val[0] * 0x010101u | (val[1] << 24);
+            o[1] = val[1] * 0x0101u | (val[2] * 0x0101u << 16);
+            o[2] = val[2] | (val[3] * 0x010101u << 8);
+        } else {
+            for (int j = 0; j < 4 && p0 + j < a.n; j++)
+                for (int k = 0; k < a.ch; k++) a.out[(size_t)a.ch * (p0 + j) + k] = (uint8_t)val[j];
+        }
+    }
+    if (a.tsum) d_peel_add(key, val, a.tsum);
+    if (a.lsum) {
+        int lab[4];
+        if (whole) {
+            const int4 t = *(const int4 *)(a.labels + p0);
+            lab[0] = t.x; lab[1] = t.y; lab[2] = t.z; lab[3] = t.w;
+        } else {
+            for (int j = 0; j < 4; j++) lab[j] = p0 + j < a.n ? a.labels[p0 + j] : -1;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (key[j] < 0) lab[j] = -1;
+        d_peel_add(lab, val, a.lsum);
+    }
+}

@@ -8,6 +8,7 @@
 #include "project_kernels.h"
 #include "predict_kernels.h"
 #include "view_kernels.h"
+#include "body_kernels.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -247,6 +248,22 @@ struct hm_ctx {
     double *d_vX = nullptr, *d_vforce = nullptr;
     uint8_t *d_vout = nullptr;
     hipEvent_t ev_view = nullptr;
+    // hm_body_*: the body-frame readout (body_kernels.h), buffers of its own allocated on first use -- it reads the state
+    // it is given and nothing else of the filter's
+    bool body_ready = false;         // the body map and its counts are there
+    TriSetup *d_bsetup = nullptr;
+    double *d_buvX = nullptr, *d_bX = nullptr;
+    int *d_btri = nullptr;           // triangle per pixel (W*H), -1: none
+    double2 *d_bbary = nullptr;      // l1, l2 per pixel
+    int4 *d_btidx = nullptr;         // vertex ids per triangle after the orientation swap
+    unsigned *d_btcnt = nullptr;     // pixels per triangle
+    std::vector<uint32_t> h_btcnt;
+    int *d_blab = nullptr;           // the label image (W*H) of hm_body_set_labels; body_L labels, 0: none set
+    int body_L = 0;
+    unsigned *d_blcnt = nullptr;     // pixels per label
+    uint8_t *d_bframe = nullptr, *d_bout = nullptr;     // hm_body_warp's frame and output (W*H, 3 W*H)
+    unsigned long long *d_bsum = nullptr;               // hm_body_warp's sums: T per triangle, then body_L per label
+    hipEvent_t ev_body = nullptr;    // recorded behind every queued warp (hm_body_warp_dev, hm_body_fence)
 };
 
 static hipError_t alloc_targets(HmOwner &own, Targets &t, size_t n)
@@ -2486,6 +2503,152 @@ extern "C" int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, c
     rc = view_queue(h, X, VIEW_FORCES_BASE, nullptr, f, h->d_vout, "hm_view_forces");
     if (rc) return rc;
     return view_download(h, bgr);
+}
+
+// ---- the body-frame readout (body_kernels.h) --------------------------------------------------------------------
+// The body map at X = uv (k_setup_all, then k_body_map), the pixels per triangle on the host.  Once per handle.
+static int body_map_build(hm_ctx *h)
+{
+    HM_HIP(hipSetDevice(h->device));
+    if (h->body_ready) return HM_OK;
+    const size_t n = (size_t)h->W * h->H;
+    HM_HIP(h->own.alloc(&h->d_bsetup, (size_t)h->T * sizeof(TriSetup)));
+    HM_HIP(h->own.alloc(&h->d_buvX, (size_t)4 * h->N * sizeof(double)));
+    HM_HIP(h->own.alloc(&h->d_bX, (size_t)2 * h->N * sizeof(double)));
+    HM_HIP(h->own.alloc(&h->d_btri, n * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->d_bbary, n * sizeof(double2)));
+    HM_HIP(h->own.alloc(&h->d_btidx, (size_t)h->T * sizeof(int4)));
+    HM_HIP(h->own.alloc(&h->d_btcnt, (size_t)h->T * sizeof(unsigned)));
+    HM_HIP(h->own.alloc(&h->d_bsum, (size_t)(h->T + h->body_L) * sizeof(unsigned long long)));
+    HM_HIP(h->own.event(&h->ev_body));
+    Mesh m = {h->W, h->H, h->N, h->T, h->d_tri, h->d_uv, h->d_tex};
+    hipLaunchKernelGGL(k_body_uvX, dim3(hm_cdiv(4 * h->N, 256)), dim3(256), 0, h->stream, (const float *)h->d_uv, h->N, h->d_buvX);
+    hipLaunchKernelGGL(k_setup_all, dim3(hm_cdiv(h->T, 64)), dim3(64), 0, h->stream, m, (const double *)h->d_buvX, h->d_bsetup);
+    HM_HIP(hipMemsetAsync(h->d_btcnt, 0, (size_t)h->T * sizeof(unsigned), h->stream));
+    hipLaunchKernelGGL(k_body_map, dim3(hm_cdiv(h->W, EKF_TILE), hm_cdiv(h->H, EKF_TILE)), dim3(EKF_TILE, EKF_TILE), 0, h->stream,
+                       h->W, h->H, h->T, (const TriSetup *)h->d_bsetup, h->d_btri, h->d_bbary, h->d_btidx, h->d_btcnt);
+    HM_HIP(hipGetLastError());
+    h->h_btcnt.resize(h->T);
+    HM_HIP(hipMemcpyAsync(h->h_btcnt.data(), h->d_btcnt, (size_t)h->T * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    h->body_ready = true;
+    return HM_OK;
+}
+
+extern "C" int hm_body_map(hm_ctx_t h, int32_t *tri_of_pixel, uint32_t *tri_counts)
+{
+    HM_ARG(h != nullptr, "hm_body_map: NULL handle");
+    HM_JOIN_LAZY(h);                             // (body_map_build creates resources: the helper must not be queueing)
+    int rc = body_map_build(h);
+    if (rc) return rc;
+    if (tri_of_pixel) {
+        HM_HIP(hipMemcpyAsync(tri_of_pixel, h->d_btri, (size_t)h->W * h->H * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HM_HIP(hipStreamSynchronize(h->stream));
+    }
+    if (tri_counts) memcpy(tri_counts, h->h_btcnt.data(), (size_t)h->T * sizeof(uint32_t));
+    return HM_OK;
+}
+
+extern "C" int hm_body_set_labels(hm_ctx_t h, const int32_t *labels, int L, uint32_t *counts)
+{
+    HM_ARG(labels == nullptr || L >= 1, "hm_body_set_labels: %d labels (need at least 1 with a label image)", L);
+    HM_ARG(h != nullptr, "hm_body_set_labels: NULL handle");
+    const size_t n = (size_t)h->W * h->H;
+    if (labels) {
+        for (size_t p = 0; p < n; p++)
+            HM_ARG(labels[p] >= -1 && labels[p] < L, "hm_body_set_labels: label %d at pixel %zu outside -1..%d", (int)labels[p],
+                   p, L - 1);
+    }
+    HM_JOIN_LAZY(h);
+    int rc = body_map_build(h);
+    if (rc) return rc;
+    if (!labels) { h->body_L = 0; return HM_OK; }
+    HM_HIP(h->own.alloc(&h->d_blab, n * sizeof(int)));
+    HM_HIP(h->own.grow(&h->d_blcnt, (size_t)L * sizeof(unsigned)));
+    HM_HIP(h->own.grow(&h->d_bsum, (size_t)(h->T + L) * sizeof(unsigned long long)));
+    h->body_L = 0;                               // (until the label image and its counts are in place)
+    HM_HIP(hipMemcpyAsync(h->d_blab, labels, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(h->d_blcnt, 0, (size_t)L * sizeof(unsigned), h->stream));
+    hipLaunchKernelGGL(k_body_label_count, dim3(hm_cdiv((int)n, 256)), dim3(256), 0, h->stream, (const int *)h->d_btri,
+                       (const int *)h->d_blab, (int)n, h->d_blcnt);
+    HM_HIP(hipGetLastError());
+    if (counts) HM_HIP(hipMemcpyAsync(counts, h->d_blcnt, (size_t)L * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    h->body_L = L;
+    return HM_OK;
+}
+
+// Queue the warp of frame d_frame (device) at state X (host, the first 2N values are read) on the handle's stream.
+static int body_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, uint8_t *d_out, int ch, unsigned long long *d_tsum,
+                      unsigned long long *d_lsum, const char *who)
+{
+    if (d_lsum && h->body_L == 0) { hm_set_error("%s: label sums asked for, and hm_body_set_labels has set no labels", who); return HM_ERR_STATE; }
+    const int n = h->W * h->H;
+    HM_HIP(hipMemcpyAsync(h->d_bX, X, (size_t)2 * h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (d_tsum) HM_HIP(hipMemsetAsync(d_tsum, 0, (size_t)h->T * sizeof(unsigned long long), h->stream));
+    if (d_lsum) HM_HIP(hipMemsetAsync(d_lsum, 0, (size_t)h->body_L * sizeof(unsigned long long), h->stream));
+    BodyWarpArgs a;
+    a.n = n; a.W = h->W; a.H = h->H; a.ch = ch;
+    a.tri_of = h->d_btri; a.bary = h->d_bbary; a.tidx = h->d_btidx;
+    a.X = h->d_bX; a.frame = d_frame; a.labels = h->d_blab;
+    a.out = d_out; a.tsum = d_tsum; a.lsum = d_lsum;
+    hipLaunchKernelGGL(k_body_warp, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, a);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipEventRecord(h->ev_body, h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_warp(hm_ctx_t h, const double *X, const uint8_t *frame, uint8_t *out, uint64_t *tri_sums,
+                            uint64_t *label_sums)
+{
+    HM_ARG(X && frame, "hm_body_warp: NULL state or frame");
+    HM_ARG(h != nullptr, "hm_body_warp: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_map_build(h);
+    if (rc) return rc;
+    if (label_sums && h->body_L == 0) { hm_set_error("hm_body_warp: label sums asked for, and hm_body_set_labels has set no labels"); return HM_ERR_STATE; }
+    const size_t n = (size_t)h->W * h->H;
+    HM_HIP(h->own.alloc(&h->d_bframe, n));
+    HM_HIP(h->own.alloc(&h->d_bout, 3 * n));
+    HM_HIP(hipMemcpyAsync(h->d_bframe, frame, n, hipMemcpyHostToDevice, h->stream));
+    unsigned long long *ts = h->d_bsum, *ls = h->d_bsum + h->T;
+    rc = body_queue(h, X, h->d_bframe, out ? h->d_bout : nullptr, 1, tri_sums ? ts : nullptr, label_sums ? ls : nullptr,
+                    "hm_body_warp");
+    if (rc) return rc;
+    if (out) HM_HIP(hipMemcpyAsync(out, h->d_bout, n, hipMemcpyDeviceToHost, h->stream));
+    if (tri_sums) HM_HIP(hipMemcpyAsync(tri_sums, ts, (size_t)h->T * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    if (label_sums) HM_HIP(hipMemcpyAsync(label_sums, ls, (size_t)h->body_L * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_warp_dev(hm_ctx_t h, const double *X, const void *d_frame, void *d_out, int out_channels,
+                                void *d_tri_sums, void *d_label_sums, void *stream)
+{
+    HM_ARG(out_channels == 1 || out_channels == 3, "hm_body_warp_dev: out_channels %d (1 or 3)", out_channels);
+    HM_ARG(X && d_frame, "hm_body_warp_dev: NULL state or frame");
+    HM_ARG(((uintptr_t)d_out & 3) == 0, "hm_body_warp_dev: d_out is not 4-byte aligned");
+    HM_ARG(((uintptr_t)d_tri_sums & 7) == 0 && ((uintptr_t)d_label_sums & 7) == 0,
+           "hm_body_warp_dev: the sums are not 8-byte aligned");
+    HM_ARG(h != nullptr, "hm_body_warp_dev: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_map_build(h);
+    if (rc) return rc;
+    rc = body_queue(h, X, (const uint8_t *)d_frame, (uint8_t *)d_out, out_channels, (unsigned long long *)d_tri_sums,
+                    (unsigned long long *)d_label_sums, "hm_body_warp_dev");
+    if (rc) return rc;
+    if (stream) HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_body, 0));
+    return HM_OK;
+}
+
+extern "C" int hm_body_fence(hm_ctx_t h, void *stream)
+{
+    HM_ARG(h && stream, "hm_body_fence: NULL argument");
+    if (h->ev_body) {
+        HM_HIP(hipSetDevice(h->device));
+        HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_body, 0));
+    }
+    return HM_OK;
 }
 
 // ---- the flow tool's preview video (reference src/optical_flow_ext.cpp:172-281, 336-389) ---------------------------

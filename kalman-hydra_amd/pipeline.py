@@ -229,6 +229,7 @@ class FrameRing:
         _lib.register(self, 4)
         self.lo = self.hi = 0                                    # frames [lo, hi) are in the ring (queued or there)
         self.bytes_uploaded = 0
+        self._fence = None       # a reader queued on another stream: the copy stream waits for it before it overwrites a slot
 
     def reset(self, first):
         with self._lock:
@@ -239,6 +240,13 @@ class FrameRing:
         """Device address of frame f in plane 0 (raw), 1 (mask) or 2 (shown to the filter)."""
         buf = (self.d_video, self.d_masks, self.d_observed)[plane]
         return buf.ptr + (f % self.R) * self.n
+
+    def fence_after(self, fence):
+        """fence(copy stream) makes the copy stream wait on the device for a read of a frame just queued elsewhere (the
+        body readout's warp): it is called before the next upload, whichever frame and slot that is (after reset() the
+        first uploads may go into slots of frames such a read still has to see)."""
+        with self._lock:
+            self._fence = fence
 
     def run_ptr(self, f):
         """Base address of the raw frames f, f + 1, ... (contiguous for extra + 1 frames)."""
@@ -256,6 +264,9 @@ class FrameRing:
                 if self._staged == self._nstage:                  # the staging block is full: wait for its copies
                     _lib.check(L.hm_copy_stream_sync(self.device, self._stream), "hm_copy_stream_sync")
                     self._staged = 0
+                if self._fence is not None:
+                    self._fence(self._stream)
+                    self._fence = None
                 st = self._stage_np[self._staged]
                 fr, mk, ob = self.src.frame_at(f)
                 parts = [(self.d_video, fr), (self.d_masks, mk)]
@@ -824,12 +835,18 @@ class FlowEKFPipeline:
                           [(f["lo"], f["hi"]) for f in self._flying]))
         return e
 
-    def run(self, first=0, end=None, on_frame=None, video=None):
+    def run(self, first=0, end=None, on_frame=None, video=None, body=None):
         """compute() for the frames first+1 .. end; on_frame(k, error_tuple) after each.
 
         video: a videoio.AviWriter of the frame size: after every step the overlay at the state the frame ended with
         (Renderer.view(X, "overlay")) is appended to it, composed on the device and written by a thread of its own
         (VideoTap); run() returns when every frame is in the file.  None: nothing is launched or allocated for it.
+
+        body: a body.BodyReadout of the filter's renderer: after every step the raw frame k+1 is read out at the state the
+        frame ended with (the warp queued on the device from the frame ring, its sums and registered frame downloaded by
+        a thread of its own: body.BodyTap), one row of body.results() per step; run() returns when every row is in.
+        The frame ring overwrites the slot of a frame only after its warp (FrameRing.fence_after).  None: nothing is
+        launched or allocated for it.
 
         gc_freeze (attribute, default True; the name is round 3's): the interpreter's automatic collections are switched
         off for the phase (gc.disable) and switched back on at its end if they were on -- a full collection, which the
@@ -847,16 +864,21 @@ class FlowEKFPipeline:
             tap = None
             if video is not None:
                 tap = self._video_tap(video)
+            btap = self._body_tap(body) if body is not None else None
             for k in range(first, end):
                 e = self.step(k)
                 if tap is not None:
                     tap.frame(self.kf.state.X)
+                if btap is not None:
+                    btap.frame(self.kf.state.X, self.ring.ptr(0, k + 1), self.ring)
                 if on_frame is not None:
                     on_frame(k, e)
                 if quiet and (k - first) % 64 == 63:
                     gc.collect(0)
             if tap is not None:
                 tap.drain()
+            if btap is not None:
+                btap.drain()
         finally:
             if quiet:
                 gc.enable()
@@ -870,6 +892,18 @@ class FlowEKFPipeline:
             tap = self._tap = VideoTap(self.kf.state.renderer, writer, self.device)
         return tap
 
+    def _body_tap(self, body):
+        """the BodyTap of this readout, made on first use and kept across run() calls (closed by close())"""
+        from .body import BodyTap
+        tap = getattr(self, "_btap", None)
+        if tap is None or tap.b is not body:
+            if tap is not None:
+                tap.close()
+            if body.r is not self.kf.state.renderer:
+                raise ValueError("run(body=...): the readout of another filter")
+            tap = self._btap = BodyTap(body, self.device)
+        return tap
+
     def close(self):
         """Joins the helper threads of the series in flight, drains and destroys the copy stream, frees the ring, the
         flow planes and the flow handles (idempotent).  The filter is the caller's."""
@@ -877,9 +911,11 @@ class FlowEKFPipeline:
             return
         self._closed = True
         try:
-            tap, self._tap = getattr(self, "_tap", None), None
-            if tap is not None:
-                tap.close()
+            for name in ("_tap", "_btap"):
+                tap = getattr(self, name, None)
+                setattr(self, name, None)
+                if tap is not None:
+                    tap.close()
             self.flow_sync()
             self._discard_prepared_mask()
         finally:

@@ -59,6 +59,8 @@ class Renderer:
         _lib.check(L.hm_ctx_create(int(device), self.nx, self.ny, self.n, int(self.tri.shape[0]), _lib.ptr(self.tri),
                                    _lib.ptr(uv), eps_Z, eps_J, eps_M, ctypes.byref(h)), "hm_ctx_create")
         self._h = h
+        self.uv = uv                            # body coordinates of the readout (body.py)
+        self._body_L, self._body_serial = 0, 0  # the label image of the readout in place (body_set_labels)
         self._worker = None                     # a state-prediction worker attached to this handle (attach_worker)
         _lib.register(self, 2)
         _lib.check(L.hm_set_texture(self._h, _lib.ptr(np.ascontiguousarray(tex, np.uint8))), "hm_set_texture")
@@ -169,6 +171,63 @@ class Renderer:
         _lib.check(_lib.lib().hm_view_forces(self._h, _lib.ptr(x), *[_lib.ptr(a) for a in f], _lib.ptr(out)),
                    "hm_view_forces")
         return out
+
+    # -- the body-frame readout (hm_body_*; hydra_mi.body) ------------------------------------------------
+    def body_map(self):
+        """-> (triangle per pixel (H, W) int32, -1 outside the mesh; pixels per triangle (T,) uint32) at X = uv."""
+        tri = np.empty((self.ny, self.nx), np.int32)
+        cnt = np.empty(self.tri.shape[0], np.uint32)
+        _lib.check(_lib.lib().hm_body_map(self._h, _lib.ptr(tri), _lib.ptr(cnt)), "hm_body_map")
+        return tri, cnt
+
+    def body_set_labels(self, labels, L):
+        """The label image (H, W) int32 of the label sums (-1: none; None clears) -> map pixels per label (L,) uint32.
+        The handle holds one label image: this replaces the one set before (body_labels names the one in place)."""
+        self._body_L = 0                          # (a failed call leaves no label count that could outgrow a buffer)
+        self._body_serial += 1
+        if labels is None:
+            _lib.check(_lib.lib().hm_body_set_labels(self._h, None, 0, None), "hm_body_set_labels")
+            return np.zeros(0, np.uint32)
+        lab = np.ascontiguousarray(labels, np.int32)
+        if lab.shape != (self.ny, self.nx):
+            raise ValueError("label image of shape %r for %dx%d frames" % (lab.shape, self.nx, self.ny))
+        cnt = np.empty(int(L), np.uint32)
+        _lib.check(_lib.lib().hm_body_set_labels(self._h, _lib.ptr(lab), int(L), _lib.ptr(cnt)), "hm_body_set_labels")
+        self._body_L = int(L)
+        return cnt
+
+    @property
+    def body_labels(self):
+        """(labels L of the label image in place, 0: none; serial number of the body_set_labels call that set it)"""
+        return self._body_L, self._body_serial
+
+    def body_warp(self, X, frame):
+        """hm_body_warp: frame (H, W) uint8 pulled back through the mesh at state X -> (registered (H, W) uint8, sums per
+        triangle (T,) uint64, sums per label (L,) uint64 of the label image in place, or None when there is none)."""
+        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+        if x.shape[0] < 2 * self.n:
+            raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
+        f = np.ascontiguousarray(frame, np.uint8)
+        if f.shape != (self.ny, self.nx):
+            raise ValueError("frame of shape %r for %dx%d frames" % (f.shape, self.nx, self.ny))
+        out = np.empty((self.ny, self.nx), np.uint8)
+        ts = np.empty(self.tri.shape[0], np.uint64)
+        ls = np.empty(self._body_L, np.uint64) if self._body_L else None    # (the library writes L values there)
+        _lib.check(_lib.lib().hm_body_warp(self._h, _lib.ptr(x), _lib.ptr(f), _lib.ptr(out), _lib.ptr(ts), _lib.ptr(ls)),
+                   "hm_body_warp")
+        return out, ts, ls
+
+    def body_warp_dev(self, X, d_frame, d_out, channels, d_tri_sums, d_label_sums, stream=None):
+        """hm_body_warp_dev: device addresses (None: NULL); d_label_sums holds body_labels[0] values; `stream` waits for the
+        warp on the device."""
+        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+        v = lambda a: None if a is None else ctypes.c_void_p(int(a))
+        _lib.check(_lib.lib().hm_body_warp_dev(self._h, _lib.ptr(x), v(d_frame), v(d_out), int(channels), v(d_tri_sums),
+                                               v(d_label_sums), stream), "hm_body_warp_dev")
+
+    def body_fence(self, stream):
+        """hm_body_fence: `stream` waits on the device for the last warp queued."""
+        _lib.check(_lib.lib().hm_body_fence(self._h, stream), "hm_body_fence")
 
     def screenshot(self, saveall=True, basename="screenshot", X=None):
         """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask

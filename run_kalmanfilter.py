@@ -19,6 +19,13 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
     -t/--threshold   threshold intensity below which is background (default 9)
     -s/--gridsize    edge length for mesh (default 22)
     -c/--cuda        whether to do the analysis on the GPU (default True; there is no CPU path)
+    --registered OUT.avi   the registered video: every raw frame pulled back through the tracked mesh into body
+                     coordinates (the frame-0 grid of the initial mesh; hydra_mi.body)
+    --points FILE.csv      points in body coordinates, lines name,x,y (reference synth.py:227-231), followed through
+                     the mesh and read out over discs of --point-radius px (default 3)
+    With --registered or --points the states file also gets tri_means (frames x triangles) and tri_counts, and with
+    --points points (frames x P x 2), point_means (frames x P), point_counts and <fn_out>_points.txt (one line
+    neurons,x0,y0,... per frame, reference synth.py:245-266).  Rows line up with X.
 """
 import argparse
 import os
@@ -28,6 +35,7 @@ import numpy as np
 
 import hydra_mi  # noqa: F401
 from hydra_mi import kalman
+from hydra_mi.body import BodyReadout, read_points_csv, write_points_txt
 from hydra_mi.distmesh_dyn import DistMesh
 from hydra_mi.pipeline import FlowEKFPipeline, VideoStream
 from hydra_mi.renderer import FlowStream
@@ -49,6 +57,9 @@ def main(argv=None):
     parser.add_argument("-s", "--gridsize", default=22, type=int,
                         help="edge length for mesh (smaller is finer; unstable much further below 18)")
     parser.add_argument("-c", "--cuda", default=True, type=bool, help="whether or not to do analysis on the GPU")
+    parser.add_argument("--registered", default=None, help="write the registered (body-frame) video here (.avi)")
+    parser.add_argument("--points", default=None, help="points to track, CSV lines name,x,y in body coordinates")
+    parser.add_argument("--point-radius", default=3.0, type=float, help="radius of the point discs read out (px)")
     args = parser.parse_args(argv)
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
@@ -66,6 +77,17 @@ def main(argv=None):
     video = AviWriter(args.fn_out, W, H) if args.fn_out.lower().endswith(".avi") else None
     if args.name is not None:
         os.makedirs("screenshots", exist_ok=True)
+    readout = args.registered is not None or args.points is not None
+    points = read_points_csv(args.points)[1] if args.points is not None else None
+    reg_video = AviWriter(args.registered, W, H) if args.registered is not None else None
+
+    def make_body(kf):
+        if not readout:
+            return None
+        body = BodyReadout(kf, points=points, point_radius=args.point_radius, video=reg_video)
+        for i in np.flatnonzero(body.outside):
+            print("Warning: point %d (%g, %g) lies outside the mesh: NaN in every frame" % (i, points[i, 0], points[i, 1]))
+        return body
 
     def keep(kf, e, count):
         states.append(kf.state.X.reshape(-1).copy())
@@ -76,6 +98,7 @@ def main(argv=None):
     if ret_flow:
         # the reference's loop (:78-89): one flow file per frame
         kf = kalman.IteratedMSKalmanFilter(distmesh, frame, flowframe, cuda=args.cuda, sparse=True, multi=True)
+        body = make_body(kf)
         count = 0
         while capture.isOpened():
             count += 1
@@ -87,6 +110,8 @@ def main(argv=None):
             keep(kf, kf.compute(grayframe, flowframe, m), count)
             if video is not None:
                 video.write(kf.state.renderer.view(kf.state.X, "overlay"))
+            if body is not None:
+                body.frame(kf.state.X, capture.frame)            # the raw frame, as the pipeline reads it
     else:
         # no flow files: flow and filter in one process, the flow of the coming frames computed on the GPU
         # beside the filter (hydra_mi.pipeline; replaces the file hand-off of reference README.md:26-31)
@@ -94,16 +119,29 @@ def main(argv=None):
         kf = kalman.IteratedMSKalmanFilter(distmesh, frame, np.zeros(frame.shape + (2,), np.float32), cuda=args.cuda,
                                            sparse=True, multi=True)
         pipe = FlowEKFPipeline(kf, capture)          # frames, masks and background-subtracted frames read from the stream
+        body = make_body(kf)
 
         def on_frame(k, e):
             print("Frame %d" % (k + 1))
             keep(kf, e, k + 1)
-        pipe.run(on_frame=on_frame, video=video)
+        pipe.run(on_frame=on_frame, video=video, body=body)
         pipe.close()
     if video is not None:
         video.close()
         print("Overlay video: %d frames in %s" % (video.frames, args.fn_out))
-    np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri)
+    extra = {}
+    if body is not None:
+        res = body.results()
+        extra = {"tri_means": res["tri_means"], "tri_counts": res["tri_counts"]}
+        if points is not None:
+            extra.update(points=res["points"], point_means=res["point_means"], point_counts=res["point_counts"])
+            fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
+            write_points_txt(fn_pts, res["points"])
+            print("Tracked points: %s" % fn_pts)
+    if reg_video is not None:
+        reg_video.close()
+        print("Registered video: %d frames in %s" % (reg_video.frames, args.registered))
+    np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri, **extra)
     print("Finished: %d frames, states in %s" % (len(states), args.fn_out))
     return 0
 
