@@ -156,7 +156,13 @@ typedef struct hm_ctx *hm_ctx_t;
  * CUDAGL_multi constructor (cuda_multi.py:24-71): mesh topology, texture
  * coordinates (= initial vertex positions in pixels, renderer.py:579) and the
  * measurement-noise scales that the reference bakes into its kernels
- * (cuda_multi.py:420).  tri: T*3 int32 vertex ids; uv: N*2 float pixels. */
+ * (cuda_multi.py:420).  tri: T*3 int32 vertex ids; uv: N*2 float pixels.
+ * Refused (HM_ERR_ARG, the message names the limit): a frame outside
+ * 1..4096 px either way, more than 4096 triangles (EKF_MAX_TRI), a vertex in
+ * more than 24 triangles (EKF_MAX_STAR) or with more than 25 neighbours
+ * (PREP_MAX_ENTRIES = 104 terms of a row of k_solve_prep).  A star region of
+ * more than 1024 tiles of 8x8 px (TMASK_STRIDE) is measured without a tile
+ * list: same numbers, more tiles walked. */
 int hm_ctx_create(int device, int width, int height, int n_vertices, int n_triangles,
                   const int32_t *tri, const float *uv,
                   double eps_Z, double eps_J, double eps_M, hm_ctx_t *out);
