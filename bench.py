@@ -14,7 +14,7 @@ the shardable unit; the only collective is the final gather of the tracked state
 Prints ONE JSON line (rank 0).  The frames and masks of the timed region are read from host memory and
 uploaded inside it (the pipeline's frame ring: one frame + one mask per step over a copy stream), as
 SURVEY.md 8d asks.  `roofline` is the SOR kernel: kernel start/stop events of every SOR launch of one
-full flow series inside the timed region.
+full flow series inside the timed region (null when the timed region is too short to hold one).
   frac / achieved    PHYSICAL: HBM bytes per launch from the rocprofv3 PMC passes (FETCH_SIZE x 2 +
                      WRITE_SIZE, profiles/r04_sor_pmc.json, valid for the kernel sources it names) over the
                      launch time measured here, against 8 TB/s.  When the PMC file was taken for other
@@ -24,9 +24,15 @@ full flow series inside the timed region.
   limited_by         what the SQ counters show (profiles/r03_sor_sq_counters.csv).
   finest_level       the same figures for the launches of pyramid level 0 alone (the 40 % target).
 `steady_state` is the rate over the last 60 % of the timed frames (the first flow series of the region
-has nothing to hide behind; `value` includes it).  `cpu_baseline` is the oracle (C/OpenMP restatement of
-the reference's CPU path) timed on this host: whole Brox pairs and one whole KFState.update at the
-bench's size.
+has nothing to hide behind; `value` includes it).
+
+A plain run does only what its headline figure needs: set-up, warm-up, the timed steps, the dump, the line.
+`--full` adds what takes runs of its own after the clock, on the same workload:
+  roofline.alone     the same flow series once more with nothing beside it (the chip to itself); when the timed
+                     region held no full series, one after the clock stands in for `roofline` as well.
+  cpu_baseline       the oracle (C/OpenMP restatement of the reference's CPU path) timed on this host: whole Brox
+                     pairs and one whole KFState.update at the bench's size (tens of seconds; --no-cpu-baseline
+                     leaves it out).  Null in a plain run.
 
 `--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step as
 DIR/<name>.npy (float32 / float64, at most 64 MB in all; a larger array is cut to a fixed, seeded sample of
@@ -401,7 +407,10 @@ def main():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--h0", type=float, default=0.047, help="mesh edge length as a fraction of the frame size")
     ap.add_argument("--flow-batch", type=int, default=8, help="consecutive frame pairs per Brox launch series")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="video workload: after the timed steps, also the flow series alone (roofline.alone) and the "
+                         "CPU baseline (cpu_baseline); a plain run prints the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--one-flow-handle", action="store_true", help="experiment: one flow series in flight at a time (default: two, on two handles)")
     ap.add_argument("--split-start", action="store_true", help="experiment: a phase starts with two flow series side by side (pipeline.split_start)")
     ap.add_argument("--first-series", type=int, default=0, help="experiment: fixed size of the first flow series of a phase (default: sized from measurements)")
@@ -606,7 +615,7 @@ def run_video(args, tracks, rank, world, dev, coll_dev, info, V, K, Wm, B, n):
             ("ekf_error", np.array([tr.last_error[:4] for tr in tracks], np.float64)),
             ("flow_u", last_flow[:, :, 0]), ("flow_v", last_flow[:, :, 1])])
     prof_pairs, prof_where = tracks[0].pipe.profiled_pairs, "of the timed region"
-    if prof_pairs == 0:                 # a timed region too short for a series of B pairs: one more, after the clock
+    if prof_pairs == 0 and args.full:   # a timed region too short for a series of B pairs: one more, after the clock
         tr = tracks[0]
         prof_pairs, prof_where = min(B, len(tr.video) - 1), "after the timed region"
         tr.pipe.begin(0, prof_pairs)
@@ -615,22 +624,25 @@ def run_video(args, tracks, rank, world, dev, coll_dev, info, V, K, Wm, B, n):
         tr.bf.profile(True)
         tr.bf.calc_dev(prof_pairs, tr.pipe.ring.run_ptr(0), tr.pipe.ring.run_ptr(0) + n * n, tr.pipe.d_u.ptr, tr.pipe.d_v.ptr)
         tr.bf.sync()
-    prof_bf = tracks[0].pipe.profiled_handle or tracks[0].bf
-    levels = prof_bf.profile_levels()
-    sor_ms, sor_launches, sor_pxit, sor_px = prof_bf.profile_read()
-    # the same series once more with nothing beside it (after the clock): what the kernel does when it has the chip
-    tr = tracks[0]
-    alone_pairs = min(B, len(tr.video) - 1)
-    tr.pipe.begin(0, alone_pairs)
-    tr.pipe.ring.ensure(alone_pairs + 1, 0)
-    tr.pipe.ring.sync()
-    torch.cuda.synchronize()
-    tr.bf.profile(True)
-    tr.bf.calc_dev(alone_pairs, tr.pipe.ring.run_ptr(0), tr.pipe.ring.run_ptr(0) + n * n, tr.pipe.d_u.ptr, tr.pipe.d_v.ptr)
-    tr.bf.sync()
-    alone_levels = tr.bf.profile_levels()
-    alone = tr.bf.profile_read()
-    tr.bf.profile(False)
+    if prof_pairs:
+        prof_bf = tracks[0].pipe.profiled_handle or tracks[0].bf
+        levels = prof_bf.profile_levels()
+        sor_ms, sor_launches, sor_pxit, sor_px = prof_bf.profile_read()
+    alone = None
+    if args.full:
+        # the same series once more with nothing beside it (after the clock): what the kernel does when it has the chip
+        tr = tracks[0]
+        alone_pairs = min(B, len(tr.video) - 1)
+        tr.pipe.begin(0, alone_pairs)
+        tr.pipe.ring.ensure(alone_pairs + 1, 0)
+        tr.pipe.ring.sync()
+        torch.cuda.synchronize()
+        tr.bf.profile(True)
+        tr.bf.calc_dev(alone_pairs, tr.pipe.ring.run_ptr(0), tr.pipe.ring.run_ptr(0) + n * n, tr.pipe.d_u.ptr, tr.pipe.d_v.ptr)
+        tr.bf.sync()
+        alone_levels = tr.bf.profile_levels()
+        alone = tr.bf.profile_read()
+        tr.bf.profile(False)
     kf, video, masks, dm = tracks[0].kf, tracks[0].video, tracks[0].masks, tracks[0].dm
     N = kf.N
     t_flow = sum(tr.pipe.t_flow for tr in tracks) / V
@@ -674,21 +686,22 @@ def run_video(args, tracks, rank, world, dev, coll_dev, info, V, K, Wm, B, n):
             "breakdown_ms_per_step": {"brox_flow": 1e3 * t_flow / K, "ekf_compute": 1e3 * t_ekf / K,
                                       "ekf_predict": 1e3 * predtime / K, "ekf_update": 1e3 * updatetime / K,
                                       "iekf_iterations": iters / K},
-            "roofline": sor_roofline(sor_ms, sor_launches, sor_pxit, sor_px,
-                                     pmc_traffic() if n == 1024 else None,
-                                     "one flow series (%d pairs) %s, %s" % (prof_pairs, prof_where, "the filter's kernels running beside it"
-                                                                             if prof_where == "of the timed region" else "nothing beside it"),
-                                     levels, prof_pairs),
+            "roofline": None if not prof_pairs else sor_roofline(
+                sor_ms, sor_launches, sor_pxit, sor_px, pmc_traffic() if n == 1024 else None,
+                "one flow series (%d pairs) %s, %s" % (prof_pairs, prof_where, "the filter's kernels running beside it"
+                                                        if prof_where == "of the timed region" else "nothing beside it"),
+                levels, prof_pairs),
         }
-        # ... and with the chip to itself (the figure the 40 % target of north_star is about)
-        ra = sor_roofline(alone[0], alone[1], alone[2], alone[3], pmc_traffic() if n == 1024 else None,
-                          "one flow series (%d pairs) after the timed region, nothing beside it" % alone_pairs, alone_levels, alone_pairs)
-        out["roofline"]["alone"] = {k: ra[k] for k in ("achieved", "frac", "traffic", "traffic_source", "achieved_contract",
-                                                         "frac_contract", "launches", "avg_launch_us", "profiled") if k in ra}
-        if "finest_level" in ra:
-            out["roofline"]["alone"]["finest_level"] = ra["finest_level"]
-        out["cpu_baseline"] = None                           # a reported baseline, timed at N = 1 only
-        if not args.no_cpu_baseline and world == 1:
+        if alone is not None:
+            # ... and with the chip to itself (the figure the 40 % target of north_star is about)
+            ra = sor_roofline(alone[0], alone[1], alone[2], alone[3], pmc_traffic() if n == 1024 else None,
+                              "one flow series (%d pairs) after the timed region, nothing beside it" % alone_pairs, alone_levels, alone_pairs)
+            out["roofline"]["alone"] = {k: ra[k] for k in ("achieved", "frac", "traffic", "traffic_source", "achieved_contract",
+                                                             "frac_contract", "launches", "avg_launch_us", "profiled") if k in ra}
+            if "finest_level" in ra:
+                out["roofline"]["alone"]["finest_level"] = ra["finest_level"]
+        out["cpu_baseline"] = None                           # a reported baseline (--full), timed at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(n, video, masks, dm, max(1.0, iters / K))
         print(json.dumps(out), flush=True)
 

@@ -325,3 +325,29 @@ def test_bench_dumps_the_last_step_of_the_video_workload(hm, tmp_path):
     assert K + Wm + 1 > 2 * bench.whole_disk_frames(n)
     ru, rv = brox.BroxOpticalFlow(n, n).calc(video[Wm + K - 1], video[Wm + K])
     assert np.array_equal(u, ru) and np.array_equal(v, rv)
+
+
+def test_bench_full_adds_the_runs_after_the_clock(hm):
+    """A plain `bench.py` run prints the headline figure without the runs of its own after the timed steps; `--full`
+    adds the flow series alone (`roofline.alone`) and the CPU baseline, and `--no-cpu-baseline` leaves the latter out
+    again.  The headline fields are the same in both lines."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "2", "--size", "256",
+            "--h0", "0.12"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full"]), ("full_no_cpu", ["--full", "--no-cpu-baseline"])):
+        res = subprocess.run(base + extra, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines[name] = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
+    plain, full, no_cpu = lines["plain"], lines["full"], lines["full_no_cpu"]
+    for out in (plain, full, no_cpu):
+        assert out["steps"] == 12 and out["warmup"] == 2 and out["unit"] == "frames/sec" and out["higher_is_better"] is True
+        assert out["value"] > 0 and abs(out["ms_per_step"] - 1e3 / out["value"]) <= 1e-6 * out["ms_per_step"]
+        assert out["metric"] == plain["metric"] and out["dtype"] == plain["dtype"]
+    assert plain["cpu_baseline"] is None and (plain["roofline"] is None or "alone" not in plain["roofline"])
+    assert full["roofline"]["alone"]["launches"] > 0 and full["roofline"]["launches"] > 0
+    cb = full["cpu_baseline"]
+    assert cb["value"] > 0 and cb["unit"] == "frames/sec" and cb["seconds"]["brox_pair"] > 0
+    assert no_cpu["cpu_baseline"] is None and no_cpu["roofline"]["alone"]["launches"] > 0

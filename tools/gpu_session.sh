@@ -3,9 +3,9 @@
 # at the first that fails (no GPU step is started behind a failed one).  Output under gpurun_out/<tag>/.
 #   tests      pytest -m gpu
 #   bench      bench.py --steps 20 --warmup 5 (what the driver runs) and the default 64 frames
-#   prof       rocprofv3 --kernel-trace --stats around the 20-frame bench (must exit 0), iteration / frame-gap timelines
-#   b512       the same two runs at 512^2 (BASELINE config 3), the first with the CPU baseline
-#   driver     the driver's command, CPU baseline included
+#   prof       rocprofv3 --kernel-trace --stats around the 20-frame bench with --full (must exit 0), iteration / frame-gap timelines
+#   b512       the same two runs at 512^2 (BASELINE config 3), the first with --full and the CPU baseline
+#   driver     the driver's command with --full, CPU baseline included
 #   pmc        the two rocprofv3 --pmc passes of tools/brox_pmc.py and tools/sor_pmc_json.py (profiles/rNN_sor_pmc.json)
 #   series     kernel trace of a flow series of 8 pairs alone, by kernel
 #   stamps     tools/stamp_chol.py with the instrumented build (build_exp/libhydra_mi_stamp.so)
@@ -27,7 +27,7 @@ for step in "$@"; do
             cut -c1-300 "$OUT/bench64.json"
         fi ;;
     prof)
-        timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bp" -o b -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/benchprof.log" 2>&1; rc=$?
+        timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bp" -o b -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/benchprof.log" 2>&1; rc=$?
         echo "rocprofv3 bench exit code $rc" | tee "$OUT/benchprof_rc.txt"
         python tools/iter_timeline.py "$OUT/bp/b_kernel_trace.csv" > "$OUT/iter_timeline.txt" 2>&1
         python tools/frame_gap_timeline.py "$OUT/bp/b_kernel_trace.csv" > "$OUT/frame_gap.txt" 2>&1
@@ -35,14 +35,14 @@ for step in "$@"; do
         rm -f "$OUT/bp/b_kernel_trace.csv"
         cat "$OUT/iter_timeline.txt"; head -40 "$OUT/frame_gap.txt" ;;
     b512)
-        timeout -k 10 300 python bench.py --size 512 --steps 20 --warmup 5 > "$OUT/bench512_20.json" 2> "$OUT/bench512_20.err"; rc=$?
+        timeout -k 10 300 python bench.py --size 512 --steps 20 --warmup 5 --full > "$OUT/bench512_20.json" 2> "$OUT/bench512_20.err"; rc=$?
         cut -c1-300 "$OUT/bench512_20.json"
         if [ $rc -eq 0 ]; then
             timeout -k 10 300 python bench.py --size 512 --no-cpu-baseline > "$OUT/bench512_64.json" 2> "$OUT/bench512_64.err"; rc=$?
             cut -c1-300 "$OUT/bench512_64.json"
         fi ;;
     driver)
-        timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"; rc=$?
+        timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"; rc=$?
         cut -c1-300 "$OUT/bench_driver.json" ;;
     pmc)
         timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -o b -- python tools/brox_pmc.py > "$OUT/pmc_fetch.log" 2>&1; rc=$?
