@@ -379,6 +379,50 @@ int hm_ctx_sync(hm_ctx_t h);
 void *hm_ctx_stream(hm_ctx_t h);
 
 /* ------------------------------------------------------------------------
+ * Rauch-Tung-Striebel smoothing of a recorded track (offline; the reference has no smoother).
+ * P_k, x_k: the posterior covariance and mean frame k's update kept; m_k: the prior mean that update started from,
+ * after projectmask (the projection onto the mask is part of the prior the filter used, so the recursion takes m_k, not
+ * the raw prediction F x_{k-1}); F_k = [[I, a I], [s dfdy(x_k), I]] with the spring blocks at x_k (hm_cov_predict),
+ * Pp_{k+1} = F_k P_k F_k^T + Weps.  Backward, k = K-2 .. 0, from xs_{K-1} = x_{K-1}, Ps_{K-1} = P_{K-1}:
+ *     G_k  = P_k F_k^T Pp_{k+1}^-1
+ *     xs_k = x_k + G_k (xs_{k+1} - m_{k+1})
+ *     Ps_k = P_k + G_k (Ps_{k+1} - Pp_{k+1}) G_k^T        (with covariances only)
+ * A smoother belongs to one filter handle and is destroyed before it.
+ *
+ * create: a record of `capacity` (>= 2) frames -- capacity slots of 4N x 4N doubles plus 4 x 4N doubles per frame,
+ *     and seven 4N x 4N work matrices -- and the model: springs bars (n_bars x 2 vertex ids), rest lengths l0, kappa,
+ *     a, s, eps_F as hm_cov_predict takes them with the blocks of hm_ms_predict (a = dt, s = dt / M); n_bars = 0 with
+ *     a = 1, s = 0: the constant-velocity model.  HM_ERR_ARG: capacity < 2, a NULL handle, a spring outside the mesh;
+ *     HM_ERR_HIP: an allocation failed (the message names its size).
+ * record: one call per frame, after that frame's update (hm_update_run, also after hm_update_arm_cov; hm_update_begin /
+ *     _step / _cov; a chained run): queues on the filter's stream a device-to-device copy of the covariance the update
+ *     kept (ordered behind the launches that form it and ahead of everything on the handle that overwrites it) and of
+ *     the prior mean the update keeps on the device; X (4N): x_k, the state the update kept.  HM_ERR_STATE: the record
+ *     is full, or no update has run on the handle -- the record is left as it was.
+ * run: the backward pass over the K frames recorded, on the filter's stream.  Pp_{k+1} is recomputed by the kernels
+ *     and from the inputs of the forward prediction (same bits) and factored by the update's factorisation, per step;
+ *     xs (K x 4N) always; want_cov != 0: var (K x 4N) = diag(Ps_k), and Ps_k replaces P_k in slot k (after such a run
+ *     the record takes no more frames and cannot be run again).  want_cov = 0 needs matrix-vector products only and
+ *     leaves the record as it is; its xs are bit-equal to those of a run with covariances.  HM_ERR_NUMERIC: some
+ *     Pp_{k+1} is not positive definite.
+ * count: the frames recorded and the capacity (either pointer may be NULL).
+ * fetch: slot k (4N x 4N: P_k, or Ps_k after a run with covariances), x_k and m_k (4N each); any may be NULL.
+ * prior: Pp_k (k >= 1) recomputed from slot k-1 as the backward pass does; HM_ERR_STATE after a run with covariances.
+ * hm_op_smooth_gemm: the backward step's products on host n x n row-major arrays on the f64 matrix cores, for tests:
+ *     which 0: out = A^T B (G = (F P)^T inv(Pp));  1: out = A (B - C) (E = G (Ps' - Pp));  2: out = C + A B^T formed
+ *     for the lower triangle and mirrored (Ps = P + E G^T, exactly symmetric). */
+typedef struct hm_smooth *hm_smooth_t;
+int hm_smooth_create(hm_ctx_t ctx, int capacity, int n_bars, const int32_t *bars, const double *l0, double kappa,
+                     double a, double s, double eps_F, hm_smooth_t *out);
+int hm_smooth_destroy(hm_smooth_t sm);
+int hm_smooth_record(hm_smooth_t sm, const double *X);
+int hm_smooth_run(hm_smooth_t sm, int want_cov, double *xs, double *var);
+int hm_smooth_count(hm_smooth_t sm, int *frames, int *capacity);
+int hm_smooth_fetch(hm_smooth_t sm, int k, double *P_out, double *x_out, double *m_out);
+int hm_smooth_prior(hm_smooth_t sm, int k, double *Pp_out);
+int hm_op_smooth_gemm(int device, int which, int n, const double *A, const double *B, const double *C, double *out);
+
+/* ------------------------------------------------------------------------
  * Views of the tracker (reference renderer.py:436-475 screenshot, :595-628 draw,
  * :344-373 the wireframe; kalman.py:638-674 plotforces).  Every view is H x W x 3
  * uint8, B, G, R, rows top to bottom, rendered at the state X (4N doubles) on the

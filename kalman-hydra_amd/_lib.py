@@ -117,6 +117,15 @@ SIGNATURES = {
     "hm_ctx_tune": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_int]),
     "hm_ctx_sync": (ctypes.c_int, [c_vp]),
     "hm_ctx_stream": (c_vp, [c_vp]),
+    "hm_smooth_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_double, ctypes.POINTER(c_vp)]),
+    "hm_smooth_destroy": (ctypes.c_int, [c_vp]),
+    "hm_smooth_record": (ctypes.c_int, [c_vp, c_vp]),
+    "hm_smooth_run": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp]),
+    "hm_smooth_count": (ctypes.c_int, [c_vp, c_i32p, c_i32p]),
+    "hm_smooth_fetch": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "hm_smooth_prior": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
+    "hm_op_smooth_gemm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "hm_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_view_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     "hm_view_forces": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -185,6 +194,7 @@ def missing_symbols():
     return [name for name in SIGNATURES if getattr(L, name, None) is None]
 
 
+HM_ERR_STATE = -3
 HM_ERR_NUMERIC = -4
 
 

@@ -835,7 +835,7 @@ class FlowEKFPipeline:
                           [(f["lo"], f["hi"]) for f in self._flying]))
         return e
 
-    def run(self, first=0, end=None, on_frame=None, video=None, body=None):
+    def run(self, first=0, end=None, on_frame=None, video=None, body=None, smoother=None):
         """compute() for the frames first+1 .. end; on_frame(k, error_tuple) after each.
 
         video: a videoio.AviWriter of the frame size: after every step the overlay at the state the frame ended with
@@ -847,6 +847,10 @@ class FlowEKFPipeline:
         a thread of its own: body.BodyTap), one row of body.results() per step; run() returns when every row is in.
         The frame ring overwrites the slot of a frame only after its warp (FrameRing.fence_after).  None: nothing is
         launched or allocated for it.
+
+        smoother: a smooth.RTSSmoother of the filter: after every step the frame is recorded (smoother.record(), device
+        copies queued on the filter's stream); run its backward pass after run().  None: nothing is launched or
+        allocated for it.
 
         gc_freeze (attribute, default True; the name is round 3's): the interpreter's automatic collections are switched
         off for the phase (gc.disable) and switched back on at its end if they were on -- a full collection, which the
@@ -865,8 +869,12 @@ class FlowEKFPipeline:
             if video is not None:
                 tap = self._video_tap(video)
             btap = self._body_tap(body) if body is not None else None
+            if smoother is not None and smoother.kf is not self.kf:
+                raise ValueError("run(smoother=...): the smoother of another filter")
             for k in range(first, end):
                 e = self.step(k)
+                if smoother is not None:
+                    smoother.record()
                 if tap is not None:
                     tap.frame(self.kf.state.X)
                 if btap is not None:

@@ -26,6 +26,10 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
     With --registered or --points the states file also gets tri_means (frames x triangles) and tri_counts, and with
     --points points (frames x P x 2), point_means (frames x P), point_counts and <fn_out>_points.txt (one line
     neurons,x0,y0,... per frame, reference synth.py:245-266).  Rows line up with X.
+    --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
+                     (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
+                     diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
+                     memory per frame; a video beyond --smooth-max-gb fails before tracking starts.
 """
 import argparse
 import os
@@ -39,6 +43,7 @@ from hydra_mi.body import BodyReadout, read_points_csv, write_points_txt
 from hydra_mi.distmesh_dyn import DistMesh
 from hydra_mi.pipeline import FlowEKFPipeline, VideoStream
 from hydra_mi.renderer import FlowStream
+from hydra_mi.smooth import RTSSmoother, check_budget
 from hydra_mi.videoio import AviWriter
 
 
@@ -60,6 +65,8 @@ def main(argv=None):
     parser.add_argument("--registered", default=None, help="write the registered (body-frame) video here (.avi)")
     parser.add_argument("--points", default=None, help="points to track, CSV lines name,x,y in body coordinates")
     parser.add_argument("--point-radius", default=3.0, type=float, help="radius of the point discs read out (px)")
+    parser.add_argument("--smooth", action="store_true", help="smooth the track backward: Xs, Xs_std in the states file")
+    parser.add_argument("--smooth-max-gb", default=8.0, type=float, help="device memory the smoother may take (GiB)")
     args = parser.parse_args(argv)
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
@@ -69,6 +76,11 @@ def main(argv=None):
     mask, ctrs, fd = capture.backsub()
     distmesh = DistMesh(frame, h0=args.gridsize)               # reference run_kalmanfilter.py:62-63
     distmesh.createMesh(ctrs, fd, frame, plot=False)
+    smooth_budget = int(args.smooth_max_gb * (1 << 30))
+    smooth_frames = 2
+    if args.smooth:
+        smooth_frames = max(capture.frames.shape[0] - 1, 2)    # one record per compute(), frames 1 .. F-1
+        check_budget(distmesh.size(), smooth_frames, smooth_budget)             # before any tracking
 
     flowstream = FlowStream(args.flow_in)
     ret_flow, flowframe = flowstream.peek()
@@ -89,6 +101,11 @@ def main(argv=None):
             print("Warning: point %d (%g, %g) lies outside the mesh: NaN in every frame" % (i, points[i, 0], points[i, 1]))
         return body
 
+    def make_smoother(kf):
+        if not args.smooth:
+            return None
+        return RTSSmoother(kf, smooth_frames, covariances=True, max_bytes=smooth_budget)
+
     def keep(kf, e, count):
         states.append(kf.state.X.reshape(-1).copy())
         errors.append([float(e[0]), float(e[1]), float(e[2]), float(e[3])])
@@ -99,6 +116,7 @@ def main(argv=None):
         # the reference's loop (:78-89): one flow file per frame
         kf = kalman.IteratedMSKalmanFilter(distmesh, frame, flowframe, cuda=args.cuda, sparse=True, multi=True)
         body = make_body(kf)
+        sm = make_smoother(kf)
         count = 0
         while capture.isOpened():
             count += 1
@@ -108,6 +126,8 @@ def main(argv=None):
                 break
             print("Frame %d" % count)
             keep(kf, kf.compute(grayframe, flowframe, m), count)
+            if sm is not None:
+                sm.record()
             if video is not None:
                 video.write(kf.state.renderer.view(kf.state.X, "overlay"))
             if body is not None:
@@ -120,11 +140,12 @@ def main(argv=None):
                                            sparse=True, multi=True)
         pipe = FlowEKFPipeline(kf, capture)          # frames, masks and background-subtracted frames read from the stream
         body = make_body(kf)
+        sm = make_smoother(kf)
 
         def on_frame(k, e):
             print("Frame %d" % (k + 1))
             keep(kf, e, k + 1)
-        pipe.run(on_frame=on_frame, video=video, body=body)
+        pipe.run(on_frame=on_frame, video=video, body=body, smoother=sm)
         pipe.close()
     if video is not None:
         video.close()
@@ -141,6 +162,14 @@ def main(argv=None):
     if reg_video is not None:
         reg_video.close()
         print("Registered video: %d frames in %s" % (reg_video.frames, args.registered))
+    if sm is not None:
+        if len(sm) > 0:
+            xs, var = sm.run()
+            extra.update(Xs=xs, Xs_std=np.sqrt(var))
+        else:
+            extra.update(Xs=np.zeros((0, 4 * kf.N)), Xs_std=np.zeros((0, 4 * kf.N)))
+        sm.close()
+        print("Smoothed track: Xs, Xs_std (%d frames)" % len(states))
     np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri, **extra)
     print("Finished: %d frames, states in %s" % (len(states), args.fn_out))
     return 0
