@@ -64,7 +64,9 @@ typedef struct hm_brox *hm_brox_t;
 
 /* cuda::BroxOpticalFlow::create(alpha, gamma, scale_factor, inner, outer, solver)
  * (src/optical_flow_ext.cpp:310; parameter meaning :300-308; defaults :453-488).
- * max_batch = number of frame pairs one calc_batch call may carry. */
+ * max_batch = number of frame pairs one calc_batch call may carry.
+ * HM_ERR_ARG, before anything is allocated, when a pyramid level would be 1x1 px
+ * (a 1x1 frame, or a scale_factor that shrinks a level to one pixel): its flow is undefined. */
 int hm_brox_create(int device, int width, int height, int max_batch,
                    float alpha, float gamma, float scale_factor,
                    int inner_iterations, int outer_iterations, int solver_iterations,

@@ -341,6 +341,13 @@ extern "C" int hm_brox_create(int device, int W, int H, int max_batch, float alp
     HM_ARG(scale > 0.0f && scale < 1.0f, "hm_brox_create: scale_factor must be in (0,1), got %g", scale);
     HM_ARG(inner >= 1 && outer >= 1 && solver >= 1, "hm_brox_create: iteration counts must be >= 1");
     HM_ARG(alpha > 0.0f && gamma >= 0.0f, "hm_brox_create: alpha must be > 0 and gamma >= 0");
+    // A level of one pixel has no flow: no neighbours and no gradient, so its 2 x 2 system is 0 / 0 and the NaN it
+    // gives is prolonged into every finer level.  Refused before anything is allocated or launched.
+    std::vector<Geo> geo;
+    make_levels(W, H, scale, outer, geo);
+    for (size_t k = 0; k < geo.size(); k++)
+        HM_ARG(geo[k].w > 1 || geo[k].h > 1, "hm_brox_create: pyramid level %zu is 1x1 px (frame %dx%d, scale_factor %g)",
+               k, W, H, scale);
     HM_HIP(hipSetDevice(device));
     hm_brox *h = new hm_brox();
     h->device = device; h->W = W; h->H = H; h->B = max_batch;
@@ -348,7 +355,7 @@ extern "C" int hm_brox_create(int device, int W, int H, int max_batch, float alp
     h->inner = inner; h->outer = outer; h->solver = solver; h->fuse = 0; h->sor_threads = 0; h->sor_dry = 0;
     h->coarse_max = 32; h->sor_deep = 1; h->cus = 0; h->coarse_stagger = 0; h->sor_wide = 0;
     if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) h->cus = 0;
-    make_levels(W, H, scale, outer, h->geo);
+    h->geo = geo;
     h->taps = make_taps(scale);
 
     const size_t B = (size_t)max_batch;

@@ -41,7 +41,12 @@ def main(av):
           % (alpha, gamma, scale, inner, outer, solver))
     B = max(1, int(os.environ.get("HYDRA_MI_FLOW_BATCH", "16")))
     n = a.shape[0] - 1
-    bf = brox.BroxOpticalFlow(a.shape[2], a.shape[1], alpha, gamma, scale, inner, outer, solver, max_batch=min(B, max(n, 1)))
+    try:
+        bf = brox.BroxOpticalFlow(a.shape[2], a.shape[1], alpha, gamma, scale, inner, outer, solver,
+                                  max_batch=min(B, max(n, 1)))
+    except RuntimeError as exc:                      # e.g. a pyramid level of one pixel
+        sys.stderr.write("%s\n" % exc)
+        return 1
     preview = None
     if os.environ.get("HYDRA_MI_FLOW_PREVIEW", "") == "1":
         preview = videoio.AviWriter(prefix + ".avi", a.shape[2], a.shape[1])

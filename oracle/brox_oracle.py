@@ -54,6 +54,11 @@ def set_threads(n):
     lib().brox_ref_set_threads(ctypes.c_int(int(n)))
 
 
+def set_omega(omega):
+    """SOR relaxation factor of every later calc / sor (the default is 1.99, as hm_brox_create's)."""
+    lib().brox_ref_set_omega(ctypes.c_float(omega))
+
+
 def levels(W, H, scale=0.8, outer=77):
     ws = np.zeros(128, np.int32)
     hs = np.zeros(128, np.int32)

@@ -345,6 +345,10 @@ int brox_ref_calc_f32(const float *f0, const float *f1, int W, int H,
 {
     int ws[BROX_MAX_LEVELS], hs[BROX_MAX_LEVELS];
     if (W < 1 || H < 1 || !(scale > 0.0f && scale < 1.0f) || outer < 1) return -1;
+    /* a level of one pixel has no flow (its 2x2 system is 0/0): refused, as the product refuses it */
+    int nl0 = brox_ref_levels(W, H, scale, outer, ws, hs);
+    for (int k = 0; k < nl0; k++)
+        if (ws[k] == 1 && hs[k] == 1) return -2;
     int nl = brox_ref_levels(W, H, scale, outer, ws, hs);
     float g[2 * BROX_MAX_RADIUS + 1];
     int R = brox_ref_gauss(scale, g);
