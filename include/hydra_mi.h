@@ -483,6 +483,34 @@ int hm_body_warp_dev(hm_ctx_t h, const double *X, const void *d_frame, void *d_o
                      void *d_tri_sums, void *d_label_sums, void *stream);
 int hm_body_fence(hm_ctx_t h, void *stream);
 
+/* Statistics of the registered video, for finding cells in the body frame.  Between begin and end every
+ * hm_body_warp and hm_body_warp_dev adds its registered frame (also one called without an output), right
+ * behind the warp on the handle's stream.  Per pixel p of the map, v_k the registered value of frame k:
+ *   s1 = sum v_k(p), s2 = sum v_k(p)^2, vmax = max v_k(p),
+ *   cross[d] = sum v_k(p) v_k(p + d), d = 0..3 the neighbours right, down-right, down, down-left, where
+ *              p + d is on the frame and in the map, else 0;
+ * zeros outside the map.  Exact integers: at most 65536 frames per accumulation (65536 * 255^2 < 2^32);
+ * the warp that would add one more fails with HM_ERR_STATE and adds nothing.
+ * Images (binary64, F frames, every step one correctly rounded operation in this order):
+ *   var = F s2 - s1 s1;  mean = s1 / F;  std = sqrt(var) / F;  max = vmax;
+ *   rho(p, q) = (F cross(p, q) - s1(p) s1(q)) / sqrt(var(p) var(q)) over the eight neighbours q on the frame
+ *   and in the map with var(p) > 0 and var(q) > 0;  corr = their sum in the order E, SE, S, SW, W, NW, N,
+ *   NE divided by their number, 0 when there is none.  NaN (max: 0) outside the map.
+ * Peaks of a score image (which: 0 corr, 1 std, 2 max - mean): the map pixels p with score(p) >= min_score
+ * and no map pixel q != p within the (2 radius + 1)^2 window around p that has a greater score, or an equal
+ * score and a lower raster index; 1 <= radius <= 16.  Sorted by score descending, raster index (row * W +
+ * column) ascending; the first `cap` are written, *count is the number found.
+ * begin allocates and zeroes (called again: starts over); end stops and frees (harmless when not begun);
+ * fetch (cross: 4 planes of W*H), images and peaks wait for the warps queued so far and take NULL for what
+ * is not wanted; HM_ERR_STATE before begin, images and peaks also while no frame has been added. */
+int hm_body_stats_begin(hm_ctx_t h);
+int hm_body_stats_end(hm_ctx_t h);
+int hm_body_stats_count(hm_ctx_t h, int *frames);
+int hm_body_stats_fetch(hm_ctx_t h, uint32_t *s1, uint32_t *s2, uint32_t *cross, uint8_t *vmax);
+int hm_body_stats_images(hm_ctx_t h, double *mean, double *std, double *corr, uint8_t *vmax);
+int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int cap, int32_t *index,
+                        double *score, int *count);
+
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
  * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the

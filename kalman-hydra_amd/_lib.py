@@ -134,6 +134,13 @@ SIGNATURES = {
     "hm_body_warp": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "hm_body_warp_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     "hm_body_fence": (ctypes.c_int, [c_vp, c_vp]),
+    "hm_body_stats_begin": (ctypes.c_int, [c_vp]),
+    "hm_body_stats_end": (ctypes.c_int, [c_vp]),
+    "hm_body_stats_count": (ctypes.c_int, [c_vp, c_vp]),
+    "hm_body_stats_fetch": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hm_body_stats_images": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hm_body_stats_peaks": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_vp, c_vp,
+                                           c_vp]),
     "hm_flow_preview": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                        c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_avi_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,

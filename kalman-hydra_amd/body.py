@@ -13,6 +13,11 @@ same coverage rule and the same position formula, so a point at a pixel centre g
     res = body.results()          # tri_means (F x T), points (F x P x 2), point_means (F x P), ...
 
 FlowEKFPipeline.run(body=body) queues the same readout on the device after every step (BodyTap).
+
+Where the cells are: BodyReadout(kf, stats=True) accumulates per-pixel sums of the registered frames on the device while
+the video is tracked (hm_body_stats_*); summary() gives the mean, standard deviation, maximum and local correlation
+images, find_points(n) the n best local maxima of one of them in the format `points` takes, and read_out(kf, states,
+frames, points) the second pass over the recorded states that reads their traces.
 """
 import ctypes
 import threading
@@ -39,6 +44,21 @@ def read_points_csv(path):
             names.append(parts[0])
             pts.append([x, y])
     return names, np.array(pts, np.float64).reshape(-1, 2)
+
+
+def write_points_csv(path, points, names=None):
+    """The inverse of read_points_csv: lines ``name,x,y`` (names default to p0, p1, ...), the coordinates as repr() of
+    the float, so they read back exactly."""
+    pts = np.asarray(points, np.float64).reshape(-1, 2)
+    if names is None:
+        names = ["p%d" % i for i in range(pts.shape[0])]
+    if len(names) != pts.shape[0]:
+        raise ValueError("%d names for %d points" % (len(names), pts.shape[0]))
+    with open(path, "w") as f:
+        for name, (x, y) in zip(names, pts):
+            if "," in str(name):
+                raise ValueError("a comma in the point name %r" % (name,))
+            f.write("%s,%r,%r\n" % (name, float(x), float(y)))
 
 
 def write_points_txt(path, points):
@@ -157,9 +177,10 @@ class BodyReadout:
 
     points: (P, 2) points in body coordinates, followed through the mesh (``track``) and read out over discs of
     point_radius px (``disc_labels``); labels: an (H, W) int32 label image in body coordinates (-1: none) instead of
-    the discs; video: an AviWriter of the frame size that receives the registered frames (B = G = R)."""
+    the discs; video: an AviWriter of the frame size that receives the registered frames (B = G = R); stats: start the
+    tracker's statistics of the registered video (every frame read out from now on is added: summary, find_points)."""
 
-    def __init__(self, kf_or_renderer, points=None, point_radius=3.0, labels=None, video=None):
+    def __init__(self, kf_or_renderer, points=None, point_radius=3.0, labels=None, video=None, stats=False):
         r = kf_or_renderer.state.renderer if hasattr(kf_or_renderer, "state") else kf_or_renderer
         self.r = r
         self.H, self.W, self.T = r.ny, r.nx, int(r.tri.shape[0])
@@ -190,6 +211,9 @@ class BodyReadout:
             self.label_counts = r.body_set_labels(None, 0)
         self._labels = r.body_labels
         self._rows = []         # per state passed: [positions or None, tri sums, label sums]
+        self.stats = bool(stats)
+        if self.stats:
+            r.body_stats_begin()
 
     # -- points -----------------------------------------------------------------------------------------
     def locate(self, points):
@@ -230,6 +254,26 @@ class BodyReadout:
         pos = self.track(X) if self.points is not None else None
         self._rows.append([pos, ts, ls])
 
+    # -- where the cells are ----------------------------------------------------------------------------
+    def summary(self):
+        """Summary images of the frames read out since the readout was made (stats=True): {"frames": F, "mean", "std",
+        "corr": (H, W) float64, NaN outside the mesh, "max": (H, W) uint8}.  Waits for the frames queued so far."""
+        if not self.stats:
+            raise RuntimeError("BodyReadout.summary: the readout was made without stats=True")
+        frames = self.r.body_stats_count()
+        mean, std, corr, vmax = self.r.body_stats_images()
+        return {"frames": frames, "mean": mean, "std": std, "max": vmax, "corr": corr}
+
+    def find_points(self, n, radius=6, score="corr", min_score=None):
+        """The n best local maxima of a summary image ("corr", "std" or "range" = max - mean) within (2 radius + 1)^2
+        windows, at least min_score (None: no threshold) -> (points (P <= n, 2) float64 at the pixel centres
+        (c + 0.5, r + 0.5) in body coordinates, what ``points=`` and read_points_csv speak; scores (P,))."""
+        if not self.stats:
+            raise RuntimeError("BodyReadout.find_points: the readout was made without stats=True")
+        idx, sc, _ = self.r.body_stats_peaks(score, radius, -np.inf if min_score is None else float(min_score), int(n))
+        rr, cc = np.divmod(idx.astype(np.int64), self.W)
+        return np.stack((cc + 0.5, rr + 0.5), 1).astype(np.float64).reshape(-1, 2), sc
+
     def results(self):
         """Arrays with one row per state passed: tri_sums / tri_means (F x T), tri_counts (T); with labels label_sums /
         label_means (F x L), label_counts; with points also points (F x P x 2), point_means (F x P), point_counts (P)."""
@@ -246,6 +290,21 @@ class BodyReadout:
             out["point_counts"] = self.label_counts.copy() if self.L > 0 else np.zeros(P, np.uint32)
             out["point_means"] = out["label_means"] if self.L > 0 else np.full((F, P), np.nan)
         return out
+
+
+def read_out(kf_or_renderer, states, frames, points, point_radius=3.0):
+    """The second pass: a fresh BodyReadout with these points over recorded states and the raw frames they belong to
+    (any iterable of (H, W) uint8 frames, one per state), no tracking -> its results().  The traces need the cells and the
+    cells need the whole video: two passes over the frames, one tracking run."""
+    b = BodyReadout(kf_or_renderer, points=points, point_radius=point_radius)
+    it = iter(frames)
+    for X in states:
+        try:
+            f = next(it)
+        except StopIteration:
+            raise ValueError("read_out: fewer frames than states (%d)" % len(states)) from None
+        b.frame(X, f)
+    return b.results()
 
 
 class BodyTap:

@@ -123,6 +123,7 @@ struct BodyWarpArgs {
     const uint8_t *frame;              // frame k, W x H
     const int *labels;                 // the label image (W x H, -1: none), NULL: no label sums
     uint8_t *out;                      // n x ch, NULL: sums only
+    uint8_t *reg;                      // n, the plane k_body_stats_add reads; NULL: no statistics
     unsigned long long *tsum, *lsum;   // sums per triangle / per label (zeroed by the caller), NULL: none
 };
 
@@ -180,6 +181,11 @@ __global__ __launch_bounds__(256) void k_body_warp(BodyWarpArgs a)
                 for (int k = 0; k < a.ch; k++) a.out[(size_t)a.ch * (p0 + j) + k] = (uint8_t)val[j];
         }
     }
+    if (a.reg) {
+        if (whole) *(unsigned *)(a.reg + p0) = val[0] | (val[1] << 8) | (val[2] << 16) | (val[3] << 24);
+        else
+            for (int j = 0; j < 4 && p0 + j < a.n; j++) a.reg[p0 + j] = (uint8_t)val[j];
+    }
     if (a.tsum) d_peel_add(key, val, a.tsum);
     if (a.lsum) {
         int lab[4];
@@ -193,5 +199,202 @@ __global__ __launch_bounds__(256) void k_body_warp(BodyWarpArgs a)
         for (int j = 0; j < 4; j++)
             if (key[j] < 0) lab[j] = -1;
         d_peel_add(lab, val, a.lsum);
+    }
+}
+
+// ---- statistics of the registered video (hm_body_stats_*) -------------------------------------------------------------
+// Integer sums over the frames added since hm_body_stats_begin, per pixel p of the map, v the registered value:
+//   s1 = sum v(p), s2 = sum v(p)^2, cross[d] = sum v(p) v(p + d) for d = right, down-right, down, down-left (0 where
+//   p + d is off the frame or outside the map), vmax = max v(p).
+// Pixels outside the map are registered as 0 (k_body_warp), so a product with one is 0 without a look at the map, and
+// their own sums stay 0.  At most BODY_STATS_CAP frames: 65536 * 255^2 < 2^32, every sum is an exact uint32.
+#define BODY_STATS_CAP 65536
+
+struct BodyStats {
+    unsigned *s1, *s2, *cross;         // n, n, 4 planes of n values `stride` apart; every plane 16-byte aligned
+    size_t stride;
+    uint8_t *vmax;                     // n
+};
+
+// 4 pixels per thread (p0 = 4 q, linear as in k_body_warp: they may straddle a row end when W is not a multiple of 4).
+// Each pixel's sums belong to its thread alone: plain read-modify-write in 16-byte vectors.  A thread whose pixels are
+// all outside the map loads its four map entries and nothing else.  reg: the registered plane the warp has just written.
+__global__ __launch_bounds__(256) void k_body_stats_add(int n, int W, const int *__restrict__ tri_of,
+                                                        const uint8_t *__restrict__ reg, BodyStats st)
+{
+    const int p0 = 4 * (blockIdx.x * 256 + threadIdx.x);
+    if (p0 >= n) return;
+    const bool whole = p0 + 4 <= n;
+    int t[4] = {-1, -1, -1, -1};
+    if (whole) {
+        const int4 k = *(const int4 *)(tri_of + p0);
+        t[0] = k.x; t[1] = k.y; t[2] = k.z; t[3] = k.w;
+    } else {
+        for (int j = 0; j < 4 && p0 + j < n; j++) t[j] = tri_of[p0 + j];
+    }
+    if ((t[0] & t[1] & t[2] & t[3]) < 0) return;           // (all four negative)
+    // a[j] = reg[p0 + j], j = 0..4; b[j] = reg[p0 + W - 1 + j], j = 0..5; 0 beyond the plane
+    unsigned a[5], b[6];
+    if (whole) {
+        const unsigned w = *(const unsigned *)(reg + p0);
+        a[0] = w & 255u; a[1] = (w >> 8) & 255u; a[2] = (w >> 16) & 255u; a[3] = w >> 24;
+    } else {
+        for (int j = 0; j < 4; j++) a[j] = p0 + j < n ? reg[p0 + j] : 0u;
+    }
+    a[4] = p0 + 4 < n ? reg[p0 + 4] : 0u;
+    const int q0 = p0 + W;
+    if ((W & 3) == 0 && q0 + 4 <= n) {
+        const unsigned w = *(const unsigned *)(reg + q0);
+        b[1] = w & 255u; b[2] = (w >> 8) & 255u; b[3] = (w >> 16) & 255u; b[4] = w >> 24;
+    } else {
+        for (int j = 1; j < 5; j++) b[j] = q0 - 1 + j < n ? reg[q0 - 1 + j] : 0u;
+    }
+    b[0] = q0 - 1 < n ? reg[q0 - 1] : 0u;
+    b[5] = q0 + 4 < n ? reg[q0 + 4] : 0u;
+    unsigned add[6][4];
+    const int c0 = p0 % W;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        int c = c0 + j;
+        while (c >= W) c -= W;
+        const unsigned v = a[j];                           // 0 outside the map and beyond the plane
+        const bool right = c + 1 < W, left = c > 0;        // the row below exists where its index is < n: b is 0 there
+        add[0][j] = v;
+        add[1][j] = v * v;
+        add[2][j] = right ? v * a[j + 1] : 0u;
+        add[3][j] = right ? v * b[j + 2] : 0u;
+        add[4][j] = v * b[j + 1];
+        add[5][j] = left ? v * b[j] : 0u;
+    }
+    unsigned *plane[6] = {st.s1, st.s2, st.cross, st.cross + st.stride, st.cross + 2 * st.stride, st.cross + 3 * st.stride};
+    if (whole) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            uint4 s = *(uint4 *)(plane[k] + p0);
+            s.x += add[k][0]; s.y += add[k][1]; s.z += add[k][2]; s.w += add[k][3];
+            *(uint4 *)(plane[k] + p0) = s;
+        }
+        const unsigned m = *(const unsigned *)(st.vmax + p0);
+        *(unsigned *)(st.vmax + p0) = max(m & 255u, a[0]) | (max((m >> 8) & 255u, a[1]) << 8) |
+                                      (max((m >> 16) & 255u, a[2]) << 16) | (max(m >> 24, a[3]) << 24);
+    } else {
+        for (int j = 0; j < 4 && p0 + j < n; j++) {
+            for (int k = 0; k < 6; k++) plane[k][p0 + j] += add[k][j];
+            st.vmax[p0 + j] = (uint8_t)max((unsigned)st.vmax[p0 + j], a[j]);
+        }
+    }
+}
+
+struct BodyImages {
+    int n, W, H;
+    double F;                          // frames added, >= 1
+    const int *tri_of;
+    BodyStats st;
+    double *mean, *sd, *corr;          // n each; NaN outside the map
+};
+
+// The summary images, one pixel per thread, binary64, every step one correctly rounded operation in this order (the
+// integers and their products F s2, s1^2, F cross, s1(p) s1(q) are below 2^53: exact):
+//   var = F s2 - s1 s1;  mean = s1 / F;  std = sqrt(var) / F;
+//   rho(p, q) = (F cross(p, q) - s1(p) s1(q)) / sqrt(var(p) var(q)) for the neighbours q in the frame and the map with
+//   var(p) > 0 and var(q) > 0, in the order E, SE, S, SW, W, NW, N, NE (the last four from the sums stored at q);
+//   corr = their sum in that order / their number, 0 when there is none.
+__global__ __launch_bounds__(256) void k_body_stats_images(BodyImages g)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= g.n) return;
+    if (g.tri_of[p] < 0) {
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        g.mean[p] = nan; g.sd[p] = nan; g.corr[p] = nan;
+        return;
+    }
+    const int r = p / g.W, c = p - r * g.W;
+    const double s1 = (double)g.st.s1[p];
+    const double var = g.F * (double)g.st.s2[p] - s1 * s1;
+    g.mean[p] = s1 / g.F;
+    g.sd[p] = sqrt(var) / g.F;
+    double sum = 0.0;
+    int cnt = 0;
+    if (var > 0.0) {
+        const int dc[8] = {1, 1, 0, -1, -1, -1, 0, 1}, dr[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int cq = c + dc[k], rq = r + dr[k];
+            if (cq < 0 || cq >= g.W || rq < 0 || rq >= g.H) continue;
+            const int q = rq * g.W + cq;
+            if (g.tri_of[q] < 0) continue;
+            const double t1 = (double)g.st.s1[q];
+            const double vq = g.F * (double)g.st.s2[q] - t1 * t1;
+            if (!(vq > 0.0)) continue;
+            const double x = (double)(k < 4 ? g.st.cross[k * g.st.stride + p] : g.st.cross[(k - 4) * g.st.stride + q]);
+            sum += (g.F * x - s1 * t1) / sqrt(var * vq);
+            cnt++;
+        }
+    }
+    g.corr[p] = cnt ? sum / (double)cnt : 0.0;
+}
+
+struct BodyPeaks {
+    int W, H, which, radius, cap;      // which: 0 corr, 1 std, 2 max - mean; 1 <= radius <= BODY_PEAK_RMAX
+    double min_score;
+    const int *tri_of;
+    const double *mean, *sd, *corr;
+    const uint8_t *vmax;
+    int *count;                        // peaks found (zeroed by the caller)
+    int *index;                        // cap entries: raster index, in the order the waves arrive
+    double *score;
+};
+
+#define BODY_PEAK_RMAX 16
+#define BODY_PEAK_TILE 16
+
+// A map pixel p is a peak when score(p) >= min_score and no map pixel q != p of the (2 radius + 1)^2 window around it has
+// score(q) > score(p), or score(q) == score(p) and a lower raster index.  One 16 x 16 tile per workgroup, its scores with
+// a halo of `radius` staged in LDS -- NaN off the frame and outside the map, which loses every comparison --, the peaks
+// compacted with one atomic per wave as k_outline does.
+__global__ __launch_bounds__(BODY_PEAK_TILE *BODY_PEAK_TILE) void k_body_peaks(BodyPeaks g)
+{
+    constexpr int S = BODY_PEAK_TILE + 2 * BODY_PEAK_RMAX;
+    __shared__ double s_sc[S * S];
+    const int tid = threadIdx.y * BODY_PEAK_TILE + threadIdx.x;
+    const int R = g.radius, side = BODY_PEAK_TILE + 2 * R;
+    const int c0 = blockIdx.x * BODY_PEAK_TILE - R, r0 = blockIdx.y * BODY_PEAK_TILE - R;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int i = tid; i < side * side; i += BODY_PEAK_TILE * BODY_PEAK_TILE) {
+        const int lr = i / side, lc = i - lr * side;
+        const int r = r0 + lr, c = c0 + lc;
+        double s = nan;
+        if (r >= 0 && r < g.H && c >= 0 && c < g.W) {
+            const int q = r * g.W + c;
+            if (g.tri_of[q] >= 0) s = g.which == 0 ? g.corr[q] : g.which == 1 ? g.sd[q] : (double)g.vmax[q] - g.mean[q];
+        }
+        s_sc[lr * S + lc] = s;
+    }
+    __syncthreads();
+    const int c = c0 + R + threadIdx.x, r = r0 + R + threadIdx.y;
+    const int lane = tid & 63;
+    bool peak = false;
+    double mine = 0.0;
+    if (c < g.W && r < g.H && g.tri_of[r * g.W + c] >= 0) {
+        mine = s_sc[(threadIdx.y + R) * S + threadIdx.x + R];
+        peak = mine >= g.min_score;
+        for (int dy = -R; dy <= R && peak; dy++) {
+            const double *row = s_sc + (threadIdx.y + R + dy) * S + threadIdx.x + R;
+            for (int dx = -R; dx <= R; dx++) {
+                const double s = row[dx];
+                // before p in raster order: an equal score wins as well
+                if (dy < 0 || (dy == 0 && dx < 0) ? s >= mine : s > mine) peak = false;
+            }
+        }
+    }
+    const unsigned long long bo = __ballot(peak);
+    if (!bo) return;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(g.count, __popcll(bo));
+    base = __shfl(base, 0);
+    const int slot = base + __popcll(bo & ((1ull << lane) - 1ull));
+    if (peak && slot < g.cap) {
+        g.index[slot] = r * g.W + c;
+        g.score[slot] = mine;
     }
 }

@@ -265,6 +265,16 @@ struct hm_ctx {
     uint8_t *d_bframe = nullptr, *d_bout = nullptr;     // hm_body_warp's frame and output (W*H, 3 W*H)
     unsigned long long *d_bsum = nullptr;               // hm_body_warp's sums: T per triangle, then body_L per label
     hipEvent_t ev_body = nullptr;    // recorded behind every queued warp (hm_body_warp_dev, hm_body_fence)
+    // hm_body_stats_*: sums of the registered video over the warps queued between begin and end
+    bool stats_on = false;
+    int stats_frames = 0;            // frames added since hm_body_stats_begin
+    int stats_cap = BODY_STATS_CAP;  // hm_ctx_tune "body_stats_cap" (tests lower it)
+    uint8_t *d_breg = nullptr;       // the registered plane (W*H) every warp writes while the statistics are on
+    unsigned *d_stsum = nullptr;     // s1, s2, cross[4]: 6 planes of W*H, body_stats_stride values apart
+    uint8_t *d_stmax = nullptr;      // W*H
+    double *d_stimg = nullptr;       // mean, std, corr: 3 planes of W*H (hm_body_stats_images / _peaks)
+    int *d_pkidx = nullptr, *d_pkcnt = nullptr;     // hm_body_stats_peaks: raster indices (W*H), their number
+    double *d_pkscore = nullptr;
 };
 
 static hipError_t alloc_targets(HmOwner &own, Targets &t, size_t n)
@@ -634,6 +644,9 @@ extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
     } else if (!strcmp(key, "edge_split")) {
         HM_ARG(value >= 1 && value <= MEAS_VSPLIT_MAX, "hm_ctx_tune: edge_split must be in 1..%d", MEAS_VSPLIT_MAX);
         h->esplit = value;
+    } else if (!strcmp(key, "body_stats_cap")) {       // tests only: frames one hm_body_stats accumulation takes
+        HM_ARG(value >= 1 && value <= BODY_STATS_CAP, "hm_ctx_tune: body_stats_cap must be in 1..%d", BODY_STATS_CAP);
+        h->stats_cap = value;
     } else {
         hm_set_error("hm_ctx_tune: unknown key '%s'", key);
         return HM_ERR_ARG;
@@ -2587,11 +2600,24 @@ extern "C" int hm_body_set_labels(hm_ctx_t h, const int32_t *labels, int L, uint
     return HM_OK;
 }
 
+// the planes of the sums start 16 bytes aligned (k_body_stats_add moves four values at a time)
+static size_t body_stats_stride(const hm_ctx *h) { return ((size_t)h->W * h->H + 3) & ~(size_t)3; }
+static BodyStats body_stats_planes(const hm_ctx *h)
+{
+    const size_t ns = body_stats_stride(h);
+    return BodyStats{h->d_stsum, h->d_stsum + ns, h->d_stsum + 2 * ns, ns, h->d_stmax};
+}
+
 // Queue the warp of frame d_frame (device) at state X (host, the first 2N values are read) on the handle's stream.
 static int body_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, uint8_t *d_out, int ch, unsigned long long *d_tsum,
                       unsigned long long *d_lsum, const char *who)
 {
     if (d_lsum && h->body_L == 0) { hm_set_error("%s: label sums asked for, and hm_body_set_labels has set no labels", who); return HM_ERR_STATE; }
+    if (h->stats_on && h->stats_frames >= h->stats_cap) {
+        hm_set_error("%s: the statistics hold %d frames, their capacity is %d (sums of 32 bits are exact up to %d frames): "
+                     "nothing added", who, h->stats_frames, h->stats_cap, BODY_STATS_CAP);
+        return HM_ERR_STATE;
+    }
     const int n = h->W * h->H;
     HM_HIP(hipMemcpyAsync(h->d_bX, X, (size_t)2 * h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (d_tsum) HM_HIP(hipMemsetAsync(d_tsum, 0, (size_t)h->T * sizeof(unsigned long long), h->stream));
@@ -2601,9 +2627,17 @@ static int body_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, uint8_
     a.tri_of = h->d_btri; a.bary = h->d_bbary; a.tidx = h->d_btidx;
     a.X = h->d_bX; a.frame = d_frame; a.labels = h->d_blab;
     a.out = d_out; a.tsum = d_tsum; a.lsum = d_lsum;
+    a.reg = h->stats_on ? h->d_breg : nullptr;
     hipLaunchKernelGGL(k_body_warp, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, a);
     HM_HIP(hipGetLastError());
     HM_HIP(hipEventRecord(h->ev_body, h->stream));
+    if (h->stats_on) {               // (behind the event: whoever waits for the warp's output does not wait for this)
+        const BodyStats st = body_stats_planes(h);
+        hipLaunchKernelGGL(k_body_stats_add, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, n, h->W,
+                           (const int *)h->d_btri, (const uint8_t *)h->d_breg, st);
+        HM_HIP(hipGetLastError());
+        h->stats_frames++;
+    }
     return HM_OK;
 }
 
@@ -2657,6 +2691,160 @@ extern "C" int hm_body_fence(hm_ctx_t h, void *stream)
         HM_HIP(hipSetDevice(h->device));
         HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_body, 0));
     }
+    return HM_OK;
+}
+
+// ---- statistics of the registered video: sums per pixel, summary images, peaks (body_kernels.h) -------------------
+extern "C" int hm_body_stats_begin(hm_ctx_t h)
+{
+    HM_ARG(h != nullptr, "hm_body_stats_begin: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_map_build(h);
+    if (rc) return rc;
+    const size_t n = (size_t)h->W * h->H;
+    h->stats_on = false;                         // (until every buffer is there and zeroed)
+    HM_HIP(h->own.alloc(&h->d_breg, n));
+    const size_t ns = body_stats_stride(h);
+    HM_HIP(h->own.alloc(&h->d_stsum, 6 * ns * sizeof(unsigned)));
+    HM_HIP(h->own.alloc(&h->d_stmax, n));
+    HM_HIP(hipMemsetAsync(h->d_stsum, 0, 6 * ns * sizeof(unsigned), h->stream));
+    HM_HIP(hipMemsetAsync(h->d_stmax, 0, n, h->stream));
+    h->stats_frames = 0;
+    h->stats_on = true;
+    return HM_OK;
+}
+
+extern "C" int hm_body_stats_end(hm_ctx_t h)
+{
+    HM_ARG(h != nullptr, "hm_body_stats_end: NULL handle");
+    HM_JOIN_LAZY(h);
+    h->stats_on = false;
+    h->stats_frames = 0;
+    if (!h->d_stsum) return HM_OK;
+    HM_HIP(hipSetDevice(h->device));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    hipError_t e = h->own.free(&h->d_breg);
+    if (e == hipSuccess) e = h->own.free(&h->d_stsum);
+    if (e == hipSuccess) e = h->own.free(&h->d_stmax);
+    if (e == hipSuccess) e = h->own.free(&h->d_stimg);
+    if (e == hipSuccess) e = h->own.free(&h->d_pkidx);
+    if (e == hipSuccess) e = h->own.free(&h->d_pkscore);
+    if (e == hipSuccess) e = h->own.free(&h->d_pkcnt);
+    HM_HIP(e);
+    return HM_OK;
+}
+
+extern "C" int hm_body_stats_count(hm_ctx_t h, int *frames)
+{
+    HM_ARG(h && frames, "hm_body_stats_count: NULL argument");
+    HM_JOIN_LAZY(h);
+    *frames = h->stats_on ? h->stats_frames : 0;
+    return HM_OK;
+}
+
+static int body_stats_begun(hm_ctx *h, bool need_frames, const char *who)
+{
+    if (!h->stats_on) { hm_set_error("%s: no statistics (hm_body_stats_begin first)", who); return HM_ERR_STATE; }
+    if (need_frames && h->stats_frames < 1) { hm_set_error("%s: no frame added since hm_body_stats_begin", who); return HM_ERR_STATE; }
+    HM_HIP(hipSetDevice(h->device));
+    return HM_OK;
+}
+
+extern "C" int hm_body_stats_fetch(hm_ctx_t h, uint32_t *s1, uint32_t *s2, uint32_t *cross, uint8_t *vmax)
+{
+    HM_ARG(h != nullptr, "hm_body_stats_fetch: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_stats_begun(h, false, "hm_body_stats_fetch");
+    if (rc) return rc;
+    const size_t n = (size_t)h->W * h->H, b = n * sizeof(uint32_t);
+    const BodyStats st = body_stats_planes(h);
+    if (s1) HM_HIP(hipMemcpyAsync(s1, st.s1, b, hipMemcpyDeviceToHost, h->stream));
+    if (s2) HM_HIP(hipMemcpyAsync(s2, st.s2, b, hipMemcpyDeviceToHost, h->stream));
+    for (int d = 0; cross && d < 4; d++)
+        HM_HIP(hipMemcpyAsync(cross + d * n, st.cross + d * st.stride, b, hipMemcpyDeviceToHost, h->stream));
+    if (vmax) HM_HIP(hipMemcpyAsync(vmax, h->d_stmax, n, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// the three summary images of the sums so far into d_stimg, queued on the handle's stream
+static int body_stats_images_queue(hm_ctx *h)
+{
+    const size_t n = (size_t)h->W * h->H;
+    HM_HIP(h->own.alloc(&h->d_stimg, 3 * n * sizeof(double)));
+    BodyImages g;
+    g.n = (int)n; g.W = h->W; g.H = h->H; g.F = (double)h->stats_frames;
+    g.tri_of = h->d_btri;
+    g.st = body_stats_planes(h);
+    g.mean = h->d_stimg; g.sd = h->d_stimg + n; g.corr = h->d_stimg + 2 * n;
+    hipLaunchKernelGGL(k_body_stats_images, dim3(hm_cdiv((int)n, 256)), dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_body_stats_images(hm_ctx_t h, double *mean, double *std, double *corr, uint8_t *vmax)
+{
+    HM_ARG(h != nullptr, "hm_body_stats_images: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_stats_begun(h, true, "hm_body_stats_images");
+    if (rc) return rc;
+    rc = body_stats_images_queue(h);
+    if (rc) return rc;
+    const size_t n = (size_t)h->W * h->H, b = n * sizeof(double);
+    if (mean) HM_HIP(hipMemcpyAsync(mean, h->d_stimg, b, hipMemcpyDeviceToHost, h->stream));
+    if (std) HM_HIP(hipMemcpyAsync(std, h->d_stimg + n, b, hipMemcpyDeviceToHost, h->stream));
+    if (corr) HM_HIP(hipMemcpyAsync(corr, h->d_stimg + 2 * n, b, hipMemcpyDeviceToHost, h->stream));
+    if (vmax) HM_HIP(hipMemcpyAsync(vmax, h->d_stmax, n, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int cap, int32_t *index,
+                                   double *score, int *count)
+{
+    HM_ARG(which >= 0 && which <= 2, "hm_body_stats_peaks: score %d (0 corr, 1 std, 2 max - mean)", which);
+    HM_ARG(radius >= 1 && radius <= BODY_PEAK_RMAX, "hm_body_stats_peaks: radius %d outside 1..%d", radius, BODY_PEAK_RMAX);
+    HM_ARG(!(min_score != min_score), "hm_body_stats_peaks: min_score is NaN");
+    HM_ARG(cap >= 0 && (cap == 0 || (index && score)), "hm_body_stats_peaks: cap %d without arrays to fill", cap);
+    HM_ARG(h && count, "hm_body_stats_peaks: NULL argument");
+    HM_JOIN_LAZY(h);
+    int rc = body_stats_begun(h, true, "hm_body_stats_peaks");
+    if (rc) return rc;
+    rc = body_stats_images_queue(h);
+    if (rc) return rc;
+    const size_t n = (size_t)h->W * h->H;
+    HM_HIP(h->own.alloc(&h->d_pkidx, n * sizeof(int)));
+    HM_HIP(h->own.alloc(&h->d_pkscore, n * sizeof(double)));
+    HM_HIP(h->own.alloc(&h->d_pkcnt, sizeof(int)));
+    HM_HIP(hipMemsetAsync(h->d_pkcnt, 0, sizeof(int), h->stream));
+    BodyPeaks g;
+    g.W = h->W; g.H = h->H; g.which = which; g.radius = radius; g.cap = (int)n; g.min_score = min_score;
+    g.tri_of = h->d_btri;
+    g.mean = h->d_stimg; g.sd = h->d_stimg + n; g.corr = h->d_stimg + 2 * n; g.vmax = h->d_stmax;
+    g.count = h->d_pkcnt; g.index = h->d_pkidx; g.score = h->d_pkscore;
+    hipLaunchKernelGGL(k_body_peaks, dim3(hm_cdiv(h->W, BODY_PEAK_TILE), hm_cdiv(h->H, BODY_PEAK_TILE)),
+                       dim3(BODY_PEAK_TILE, BODY_PEAK_TILE), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    int found = 0;
+    HM_HIP(hipMemcpyAsync(&found, h->d_pkcnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    if (found < 0 || (size_t)found > n) { hm_set_error("hm_body_stats_peaks: %d peaks reported for %zu pixels", found, n); return HM_ERR_HIP; }
+    std::vector<int> idx(found);
+    std::vector<double> sc(found);
+    if (found) {
+        HM_HIP(hipMemcpyAsync(idx.data(), h->d_pkidx, (size_t)found * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HM_HIP(hipMemcpyAsync(sc.data(), h->d_pkscore, (size_t)found * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HM_HIP(hipStreamSynchronize(h->stream));
+    }
+    // the waves arrive in any order: score descending, raster index ascending
+    std::vector<int> order(found);
+    for (int i = 0; i < found; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return sc[a] != sc[b] ? sc[a] > sc[b] : idx[a] < idx[b]; });
+    for (int i = 0; i < found && i < cap; i++) {
+        index[i] = idx[order[i]];
+        score[i] = sc[order[i]];
+    }
+    *count = found;
     return HM_OK;
 }
 

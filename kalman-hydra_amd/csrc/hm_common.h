@@ -109,6 +109,16 @@ struct HmOwner {
         if (*ev) return hipSuccess;
         return keep(events, ev, hipEventCreateWithFlags(ev, flags));
     }
+    // frees one allocation of the handle and clears the field (the caller has waited for its last use)
+    template <typename T> hipError_t free(T **p)
+    {
+        const auto it = *p ? mem.find((void *)*p) : mem.end();
+        if (it == mem.end()) return hipSuccess;
+        const hipError_t e = it->second.host ? hipHostFree(it->first) : hipFree(it->first);
+        mem.erase(it);
+        *p = nullptr;
+        return e;
+    }
     // destroys one stream of the handle and clears the field
     hipError_t release(hipStream_t *s)
     {

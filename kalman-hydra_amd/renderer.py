@@ -229,6 +229,55 @@ class Renderer:
         """hm_body_fence: `stream` waits on the device for the last warp queued."""
         _lib.check(_lib.lib().hm_body_fence(self._h, stream), "hm_body_fence")
 
+    # -- statistics of the registered video (hm_body_stats_*; hydra_mi.body.BodyReadout(stats=True)) -------
+    SCORES = {"corr": 0, "std": 1, "range": 2}
+
+    def body_stats_begin(self):
+        """hm_body_stats_begin: every body_warp / body_warp_dev from now on adds its registered frame; again: restart."""
+        _lib.check(_lib.lib().hm_body_stats_begin(self._h), "hm_body_stats_begin")
+
+    def body_stats_end(self):
+        """hm_body_stats_end: stop accumulating and free the sums (harmless when not begun)."""
+        _lib.check(_lib.lib().hm_body_stats_end(self._h), "hm_body_stats_end")
+
+    def body_stats_count(self):
+        """-> frames added since body_stats_begin"""
+        n = ctypes.c_int(0)
+        _lib.check(_lib.lib().hm_body_stats_count(self._h, ctypes.byref(n)), "hm_body_stats_count")
+        return n.value
+
+    def body_stats_fetch(self):
+        """-> (s1 (H, W) uint32, s2 (H, W) uint32, cross (4, H, W) uint32: right, down-right, down, down-left,
+        vmax (H, W) uint8) of the frames added so far; zeros outside the map."""
+        H, W = self.ny, self.nx
+        s1, s2 = np.empty((H, W), np.uint32), np.empty((H, W), np.uint32)
+        cross, vmax = np.empty((4, H, W), np.uint32), np.empty((H, W), np.uint8)
+        _lib.check(_lib.lib().hm_body_stats_fetch(self._h, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(cross), _lib.ptr(vmax)),
+                   "hm_body_stats_fetch")
+        return s1, s2, cross, vmax
+
+    def body_stats_images(self):
+        """-> (mean, std, corr (H, W) float64, NaN outside the map; max (H, W) uint8) of the frames added so far."""
+        H, W = self.ny, self.nx
+        mean, std, corr = (np.empty((H, W), np.float64) for _ in range(3))
+        vmax = np.empty((H, W), np.uint8)
+        _lib.check(_lib.lib().hm_body_stats_images(self._h, _lib.ptr(mean), _lib.ptr(std), _lib.ptr(corr), _lib.ptr(vmax)),
+                   "hm_body_stats_images")
+        return mean, std, corr, vmax
+
+    def body_stats_peaks(self, score="corr", radius=6, min_score=-np.inf, cap=None):
+        """hm_body_stats_peaks: the local maxima of a score image ("corr", "std", "range" = max - mean, or 0, 1, 2)
+        within (2 radius + 1)^2 windows -> (raster indices (P,) int32, scores (P,) float64, number found); score
+        descending, the first `cap` of them (None: all)."""
+        which = self.SCORES[score] if isinstance(score, str) else int(score)
+        cap = self.nx * self.ny if cap is None else int(cap)
+        idx, sc = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.float64)
+        n = ctypes.c_int(0)
+        _lib.check(_lib.lib().hm_body_stats_peaks(self._h, which, int(radius), float(min_score), cap, _lib.ptr(idx),
+                                                  _lib.ptr(sc), ctypes.byref(n)), "hm_body_stats_peaks")
+        k = min(n.value, cap)
+        return idx[:k].copy(), sc[:k].copy(), n.value
+
     def screenshot(self, saveall=True, basename="screenshot", X=None):
         """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask
         at state X (default: the vertex buffer) and returns the overlay.  Unlike the reference the names carry no

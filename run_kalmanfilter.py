@@ -26,6 +26,14 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
     With --registered or --points the states file also gets tri_means (frames x triangles) and tri_counts, and with
     --points points (frames x P x 2), point_means (frames x P), point_counts and <fn_out>_points.txt (one line
     neurons,x0,y0,... per frame, reference synth.py:245-266).  Rows line up with X.
+    --find-points N  find the cells: the statistics of the registered video are accumulated on the GPU while it is
+                     tracked (hydra_mi.body, BodyReadout(stats=True)); the states file gets the summary images body_mean,
+                     body_std, body_max, body_corr (H x W; NaN, body_max 0, outside the mesh) and found_points (P <= N, 2),
+                     found_scores: the N best local maxima of --find-score (corr: mean correlation with the 8 neighbours,
+                     the default; std; range: max - mean) within windows of --find-radius px (default 6).  A second pass
+                     over the recorded states then reads them out as --points would (points, point_means, point_counts,
+                     <fn_out>_points.txt); --points-out FILE.csv writes them in the format --points reads.  Not together
+                     with --points.
     --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
                      (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
                      diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
@@ -39,7 +47,7 @@ import numpy as np
 
 import hydra_mi  # noqa: F401
 from hydra_mi import kalman
-from hydra_mi.body import BodyReadout, read_points_csv, write_points_txt
+from hydra_mi.body import BodyReadout, read_out, read_points_csv, write_points_csv, write_points_txt
 from hydra_mi.distmesh_dyn import DistMesh
 from hydra_mi.pipeline import FlowEKFPipeline, VideoStream
 from hydra_mi.renderer import FlowStream
@@ -65,9 +73,21 @@ def main(argv=None):
     parser.add_argument("--registered", default=None, help="write the registered (body-frame) video here (.avi)")
     parser.add_argument("--points", default=None, help="points to track, CSV lines name,x,y in body coordinates")
     parser.add_argument("--point-radius", default=3.0, type=float, help="radius of the point discs read out (px)")
+    parser.add_argument("--find-points", default=None, type=int, metavar="N",
+                        help="find the N best cells from the statistics of the registered video and read them out")
+    parser.add_argument("--find-radius", default=6, type=int, help="half width of the window a cell is the maximum of (1..16)")
+    parser.add_argument("--find-score", default="corr", choices=("corr", "std", "range"), help="the summary image searched")
+    parser.add_argument("--points-out", default=None, help="write the points found here (CSV lines name,x,y)")
     parser.add_argument("--smooth", action="store_true", help="smooth the track backward: Xs, Xs_std in the states file")
     parser.add_argument("--smooth-max-gb", default=8.0, type=float, help="device memory the smoother may take (GiB)")
     args = parser.parse_args(argv)
+    if args.find_points is not None:
+        if args.points is not None:
+            parser.error("--find-points finds the points itself: not together with --points")
+        if args.find_points < 1 or not 1 <= args.find_radius <= 16:
+            parser.error("--find-points needs N >= 1 and a --find-radius in 1..16")
+    elif args.points_out is not None:
+        parser.error("--points-out goes with --find-points")
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
 
@@ -89,14 +109,15 @@ def main(argv=None):
     video = AviWriter(args.fn_out, W, H) if args.fn_out.lower().endswith(".avi") else None
     if args.name is not None:
         os.makedirs("screenshots", exist_ok=True)
-    readout = args.registered is not None or args.points is not None
+    find = args.find_points is not None
+    readout = args.registered is not None or args.points is not None or find
     points = read_points_csv(args.points)[1] if args.points is not None else None
     reg_video = AviWriter(args.registered, W, H) if args.registered is not None else None
 
     def make_body(kf):
         if not readout:
             return None
-        body = BodyReadout(kf, points=points, point_radius=args.point_radius, video=reg_video)
+        body = BodyReadout(kf, points=points, point_radius=args.point_radius, video=reg_video, stats=find)
         for i in np.flatnonzero(body.outside):
             print("Warning: point %d (%g, %g) lies outside the mesh: NaN in every frame" % (i, points[i, 0], points[i, 1]))
         return body
@@ -159,6 +180,22 @@ def main(argv=None):
             fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
             write_points_txt(fn_pts, res["points"])
             print("Tracked points: %s" % fn_pts)
+    if find:
+        # the cells need the whole video and the traces need the cells: a second pass over the recorded states
+        sm_img = body.summary()
+        found, scores = body.find_points(args.find_points, radius=args.find_radius, score=args.find_score)
+        kf.state.renderer.body_stats_end()
+        extra.update(body_mean=sm_img["mean"], body_std=sm_img["std"], body_max=sm_img["max"], body_corr=sm_img["corr"],
+                     found_points=found, found_scores=scores)
+        print("Found %d points (%s, radius %d) in %d frames" % (len(found), args.find_score, args.find_radius, sm_img["frames"]))
+        res = read_out(kf, states, capture.frames[1:1 + len(states)], found, args.point_radius)    # state k: frame k + 1
+        extra.update(points=res["points"], point_means=res["point_means"], point_counts=res["point_counts"])
+        fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
+        write_points_txt(fn_pts, res["points"])
+        print("Tracked points: %s" % fn_pts)
+        if args.points_out is not None:
+            write_points_csv(args.points_out, found)
+            print("Points found: %s" % args.points_out)
     if reg_video is not None:
         reg_video.close()
         print("Registered video: %d frames in %s" % (reg_video.frames, args.registered))
