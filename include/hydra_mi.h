@@ -265,7 +265,10 @@ int hm_update_cov(hm_ctx_t h, int which, double *W_out);                     /* 
  *   X       in: the predicted state (prior mean); out: the state kept;
  *   info    iterations run, iterations accepted, reverted (a triangle flipped, :806-811), converged
  *           (|e_new - e_old| / e_new < reltol, :817-819);
- *   errs    max_iter x 4 (may be NULL): hm_error of every new iterate;
+ *   errs    max_iter x 4 (may be NULL): hm_error of every new iterate, one row per iteration run.  The row of an
+ *           iteration whose iterate flipped a triangle is written as well -- the sums of the flipped iterate's render,
+ *           which the reference never forms (it leaves the loop at :811, before error() at :813): only the first
+ *           info[1] rows are the reference's; rows from info[0] on are not written;
  *   Hzc     4N x 4 (may be NULL) of the last measurement; gains 3 x 4N (may be NULL): W Hzc[:,0],
  *           W (Hzc[:,1] + Hzc[:,2]), W Hzc[:,3] with the covariance kept (:828-830);
  *   W_out   4N x 4N, or NULL to leave the covariance on the device (hm_cov_fetch / hm_cov_predict).

@@ -427,8 +427,12 @@ def orientation(X, N, tri):
     return np.sign(a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0])
 
 
-def iekf_update(meas, X, W, J, tri, y_im, y_flow, y_m, nI=10, reltol=1e-4, deltaX=2.0):
-    """IteratedKalmanFilter.update, kalman.py:774-831.  Returns (X, W, iterations, trace)."""
+def iekf_update(meas, X, W, J, tri, y_im, y_flow, y_m, nI=10, reltol=1e-4, deltaX=2.0, history=None):
+    """IteratedKalmanFilter.update, kalman.py:774-831.  Returns (X, W, iterations, trace).
+
+    history (a list): receives one dict per round -- X_meas (the point of the measurement), Hz, Hzc, HTH, A = inv(W0) + HTH,
+    W = inv(A), X (the new iterate, also when it flips a triangle) and, for an accepted round, ratio (the convergence
+    figure |e_new - e_old| / e_new of :817)."""
     N = X.size // 4
     X = np.array(X, np.float64).reshape(-1, 1)
     X_orig, X_old = X.copy(), X.copy()
@@ -441,7 +445,11 @@ def iekf_update(meas, X, W, J, tri, y_im, y_flow, y_m, nI=10, reltol=1e-4, delta
         Hz, Hzc = jacobian(meas, X.reshape(-1), y_im, y_flow, y_m, deltaX)
         HTH = hessian_sparse(meas, X.reshape(-1), J, deltaX)
         W = np.linalg.inv(invW_orig + HTH)
+        X_meas = X
         X = X_orig + W @ Hz - W @ (HTH @ (X_orig - X))
+        if history is not None:
+            history.append(dict(X_meas=X_meas.reshape(-1).copy(), Hz=Hz.reshape(-1).copy(), Hzc=Hzc.copy(), HTH=HTH,
+                                A=invW_orig + HTH, W=W, X=X.reshape(-1).copy()))
         if np.any(orientation(X.reshape(-1), N, tri) < 0):
             X, W = X_old, W_old
             trace.append(("reverted",))
@@ -449,6 +457,8 @@ def iekf_update(meas, X, W, J, tri, y_im, y_flow, y_m, nI=10, reltol=1e-4, delta
         e_im, e_fx, e_fy, e_m, _, _ = meas.error(X.reshape(-1), y_im, y_flow, y_m)
         enew = float(np.sqrt(float(e_im) ** 2 + e_fx ** 2 + e_fy ** 2 + float(e_m) ** 2))
         trace.append((e_im, e_fx, e_fy, e_m))
+        if history is not None:
+            history[-1]["ratio"] = abs(enew - eold) / enew
         if abs(enew - eold) / enew < reltol:
             break
         eold = enew
