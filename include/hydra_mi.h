@@ -514,6 +514,43 @@ int hm_body_stats_images(hm_ctx_t h, double *mean, double *std, double *corr, ui
 int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int cap, int32_t *index,
                         double *score, int *count);
 
+/* The registered video kept on the device, and exact integer reductions over it: what footprints, ROIs and
+ * neuropil-corrected traces are built from (hydra_mi/roi.py).  Between begin and end every
+ * hm_body_warp and hm_body_warp_dev appends its registered frame (also one called without an output), right
+ * behind the warp on the handle's stream as the statistics are; statistics and record may be on together.
+ * The record holds the bounding box of the body map, one byte per pixel (rows padded to 4 bytes), in chunks
+ * allocated as it grows.  max_bytes is its budget: the warp that would pass it fails with HM_ERR_STATE, names
+ * the numbers and appends nothing (nor adds to the statistics).  begin called again starts over; end stops
+ * and frees (harmless when not begun); count gives the frames appended since begin.
+ * fetch: frames k0 .. k0 + n - 1 as full W*H planes (0 outside the box), equal to what the warps returned.
+ * The reductions run over all F recorded frames, wait for the warps queued so far and for their results, and
+ * fail with HM_ERR_STATE before begin and while no frame is recorded.  v_k(p) is the registered value of
+ * pixel p in frame k; only pixels of the map count (the others are registered as 0).
+ *   label_sums     a W*H label image given now (-1: none, labels 0..L-1) -> out[k * L + l], the sums of
+ *                  hm_body_warp's label_sums for every frame, without a second pass over the video.
+ *   seed_sums      P seeds, (column, row) pairs of map pixels.  Per seed s and frame k, d2 the whole number
+ *                  dx^2 + dy^2 from the seed, compared in binary64 with r * r:
+ *                    T_k = sum v_k over the disc d2 <= r_disc^2 (n_T map pixels),
+ *                    G_k = sum v_k over the ring r_in^2 <= d2 <= r_out^2 (n_G map pixels; 0 and G = 0 when empty),
+ *                    U_k = n_G T_k - n_T G_k (int64): the disc trace minus the ring trace, as a whole number;
+ *                  per pixel p of the (2R + 1)^2 window round the seed, R <= 16, index (dy + R)(2R + 1) + dx + R:
+ *                    w1 = sum v_k(p), w2 = sum v_k(p)^2, c = sum v_k(p) U_k (0 off the frame, outside the map);
+ *                  per seed u1 = sum U_k, u2 = sum U_k^2.  T, G, U hold F*P values (frame-major), w1, w2, c
+ *                  P (2R + 1)^2, the others P; any output may be NULL.  Discs and rings of different seeds may
+ *                  overlap; radii at most 32.  HM_ERR_ARG with the numbers when F (255 n_T n_G)^2 could pass 2^63
+ *                  (every sum is exact in 64 bits below that), and for a seed that is no pixel of the map.
+ *   weighted_sums  P windows of (2R + 1)^2 uint16 weights round the seeds, R <= 32 -> out[k * P + s] =
+ *                  sum a_s(p) v_k(p): traces of ROIs that overlap or carry weights. */
+int hm_body_rec_begin(hm_ctx_t h, uint64_t max_bytes);
+int hm_body_rec_end(hm_ctx_t h);
+int hm_body_rec_count(hm_ctx_t h, int *frames);
+int hm_body_rec_fetch(hm_ctx_t h, int k0, int n, uint8_t *out);
+int hm_body_rec_label_sums(hm_ctx_t h, const int32_t *labels, int L, uint64_t *out);
+int hm_body_rec_seed_sums(hm_ctx_t h, int P, const int32_t *seeds, double r_disc, double r_in, double r_out, int R,
+                          uint32_t *n_T, uint32_t *n_G, uint64_t *T, uint64_t *G, int64_t *U, uint64_t *w1,
+                          uint64_t *w2, int64_t *c, int64_t *u1, int64_t *u2);
+int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds, int R, const uint16_t *weights, uint64_t *out);
+
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
  * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the

@@ -141,6 +141,14 @@ SIGNATURES = {
     "hm_body_stats_images": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "hm_body_stats_peaks": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_vp, c_vp,
                                            c_vp]),
+    "hm_body_rec_begin": (ctypes.c_int, [c_vp, ctypes.c_uint64]),
+    "hm_body_rec_end": (ctypes.c_int, [c_vp]),
+    "hm_body_rec_count": (ctypes.c_int, [c_vp, c_vp]),
+    "hm_body_rec_fetch": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp]),
+    "hm_body_rec_label_sums": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp]),
+    "hm_body_rec_seed_sums": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hm_body_rec_weighted_sums": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_flow_preview": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                        c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_avi_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,

@@ -18,6 +18,9 @@ Where the cells are: BodyReadout(kf, stats=True) accumulates per-pixel sums of t
 the video is tracked (hm_body_stats_*); summary() gives the mean, standard deviation, maximum and local correlation
 images, find_points(n) the n best local maxima of one of them in the format `points` takes, and read_out(kf, states,
 frames, points) the second pass over the recorded states that reads their traces.
+
+BodyReadout(kf, keep=True) keeps the registered video itself on the device (hm_body_rec_*): hydra_mi.roi.extract builds
+footprints, ROIs and neuropil-corrected dF/F traces from it, and the traces of points found afterwards need no second pass.
 """
 import ctypes
 import threading
@@ -178,9 +181,12 @@ class BodyReadout:
     points: (P, 2) points in body coordinates, followed through the mesh (``track``) and read out over discs of
     point_radius px (``disc_labels``); labels: an (H, W) int32 label image in body coordinates (-1: none) instead of
     the discs; video: an AviWriter of the frame size that receives the registered frames (B = G = R); stats: start the
-    tracker's statistics of the registered video (every frame read out from now on is added: summary, find_points)."""
+    tracker's statistics of the registered video (every frame read out from now on is added: summary, find_points);
+    keep: keep the registered video itself in device memory (hm_body_rec_*, at most keep_bytes; the frame that would pass
+    them raises and is not read out), for hydra_mi.roi.extract and the traces of points found afterwards."""
 
-    def __init__(self, kf_or_renderer, points=None, point_radius=3.0, labels=None, video=None, stats=False):
+    def __init__(self, kf_or_renderer, points=None, point_radius=3.0, labels=None, video=None, stats=False, keep=False,
+                 keep_bytes=8 << 30):
         r = kf_or_renderer.state.renderer if hasattr(kf_or_renderer, "state") else kf_or_renderer
         self.r = r
         self.H, self.W, self.T = r.ny, r.nx, int(r.tri.shape[0])
@@ -214,6 +220,9 @@ class BodyReadout:
         self.stats = bool(stats)
         if self.stats:
             r.body_stats_begin()
+        self.keep = bool(keep)
+        if self.keep:
+            r.body_rec_begin(int(keep_bytes))
 
     # -- points -----------------------------------------------------------------------------------------
     def locate(self, points):
@@ -305,6 +314,40 @@ def read_out(kf_or_renderer, states, frames, points, point_radius=3.0):
             raise ValueError("read_out: fewer frames than states (%d)" % len(states)) from None
         b.frame(X, f)
     return b.results()
+
+
+def record_bytes(tri_of_pixel, frames):
+    """Device memory the kept registered video of `frames` frames takes (hm_body_rec_*): the bounding box of the body
+    map, one byte per pixel, rows padded to 4 bytes and frames to 16."""
+    m = np.asarray(tri_of_pixel) >= 0
+    if not m.any():
+        return 16 * int(frames)
+    rows, cols = np.flatnonzero(m.any(1)), np.flatnonzero(m.any(0))
+    bw, bh = int(cols[-1] - cols[0] + 1), int(rows[-1] - rows[0] + 1)
+    return ((((bw + 3) // 4 * 4) * bh + 15) // 16 * 16) * int(frames)
+
+
+def read_out_recorded(body, states, points, point_radius=3.0):
+    """What read_out gives for `points`, from the registered video a BodyReadout(keep=True) holds on the device instead
+    of a second pass over the frames: the discs' sums of every recorded frame in one call (hm_body_rec_label_sums), the
+    positions from the recorded states.  One state per recorded frame."""
+    r = body.r
+    pts = np.asarray(points, np.float64).reshape(-1, 2)
+    P = pts.shape[0]
+    F = r.body_rec_count()
+    if len(states) != F:
+        raise ValueError("read_out_recorded: %d states for %d recorded frames" % (len(states), F))
+    t, ids, l1, l2 = locate(r.uv, r.tri, pts)
+    x = np.asarray(states, np.float64).reshape(F, -1)[:, :2 * r.n]
+    pos = np.array([track(row, ids, l1, l2, t >= 0) for row in x], np.float64).reshape(F, P, 2)
+    labels = disc_labels(body.tri_of_pixel, pts, point_radius)
+    counts = np.bincount(labels[labels >= 0], minlength=P).astype(np.uint32) if P else np.zeros(0, np.uint32)
+    if P and F:
+        sums = r.body_rec_label_sums(labels, P)
+        means = _means(sums, counts[None, :])
+    else:
+        means = np.full((F, P), np.nan)
+    return {"points": pos, "point_means": means, "point_counts": counts}
 
 
 class BodyTap:

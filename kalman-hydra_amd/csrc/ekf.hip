@@ -9,6 +9,7 @@
 #include "predict_kernels.h"
 #include "view_kernels.h"
 #include "body_kernels.h"
+#include "roi_kernels.h"
 #include "smooth_kernels.h"
 #include <algorithm>
 #include <atomic>
@@ -275,6 +276,17 @@ struct hm_ctx {
     double *d_stimg = nullptr;       // mean, std, corr: 3 planes of W*H (hm_body_stats_images / _peaks)
     int *d_pkidx = nullptr, *d_pkcnt = nullptr;     // hm_body_stats_peaks: raster indices (W*H), their number
     double *d_pkscore = nullptr;
+    // hm_body_rec_*: the registered video of the warps queued between begin and end, kept on the device (roi_kernels.h)
+    bool rec_on = false;
+    int rec_frames = 0;              // frames appended since hm_body_rec_begin
+    int rec_cap = 0;                 // frames the budget of hm_body_rec_begin holds
+    int rec_chunk = 0;               // hm_ctx_tune "body_rec_chunk": frames per chunk (0: REC_CHUNK_BYTES worth; tests lower it)
+    unsigned long long rec_max = 0;  // the budget in bytes
+    RecBox rec_box = {0, 0, 0, 0, 0, 0, 0};
+    std::vector<uint8_t *> rec_chunks;
+    std::vector<int> h_btri;         // the body map on the host (the box, and the pixel counts of discs and rings)
+    uint8_t **d_rec_tab = nullptr;   // the chunks' addresses for the reductions
+    uint8_t *d_rec_tmp = nullptr;    // their arguments and results
 };
 
 static hipError_t alloc_targets(HmOwner &own, Targets &t, size_t n)
@@ -647,6 +659,9 @@ extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
     } else if (!strcmp(key, "body_stats_cap")) {       // tests only: frames one hm_body_stats accumulation takes
         HM_ARG(value >= 1 && value <= BODY_STATS_CAP, "hm_ctx_tune: body_stats_cap must be in 1..%d", BODY_STATS_CAP);
         h->stats_cap = value;
+    } else if (!strcmp(key, "body_rec_chunk")) {       // tests only: frames per chunk of the next hm_body_rec_begin
+        HM_ARG(value >= 0, "hm_ctx_tune: body_rec_chunk must be >= 0 (0: the default size)");
+        h->rec_chunk = value;
     } else {
         hm_set_error("hm_ctx_tune: unknown key '%s'", key);
         return HM_ERR_ARG;
@@ -2608,6 +2623,8 @@ static BodyStats body_stats_planes(const hm_ctx *h)
     return BodyStats{h->d_stsum, h->d_stsum + ns, h->d_stsum + 2 * ns, ns, h->d_stmax};
 }
 
+static int body_rec_slot(hm_ctx *h, const char *who, uint8_t **dst);
+
 // Queue the warp of frame d_frame (device) at state X (host, the first 2N values are read) on the handle's stream.
 static int body_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, uint8_t *d_out, int ch, unsigned long long *d_tsum,
                       unsigned long long *d_lsum, const char *who)
@@ -2618,6 +2635,11 @@ static int body_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, uint8_
                      "nothing added", who, h->stats_frames, h->stats_cap, BODY_STATS_CAP);
         return HM_ERR_STATE;
     }
+    uint8_t *rec_dst = nullptr;
+    if (h->rec_on) {                 // (before anything is queued: a refused warp leaves statistics and record as they were)
+        const int rc = body_rec_slot(h, who, &rec_dst);
+        if (rc) return rc;
+    }
     const int n = h->W * h->H;
     HM_HIP(hipMemcpyAsync(h->d_bX, X, (size_t)2 * h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (d_tsum) HM_HIP(hipMemsetAsync(d_tsum, 0, (size_t)h->T * sizeof(unsigned long long), h->stream));
@@ -2627,7 +2649,7 @@ static int body_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, uint8_
     a.tri_of = h->d_btri; a.bary = h->d_bbary; a.tidx = h->d_btidx;
     a.X = h->d_bX; a.frame = d_frame; a.labels = h->d_blab;
     a.out = d_out; a.tsum = d_tsum; a.lsum = d_lsum;
-    a.reg = h->stats_on ? h->d_breg : nullptr;
+    a.reg = h->stats_on || h->rec_on ? h->d_breg : nullptr;
     hipLaunchKernelGGL(k_body_warp, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, a);
     HM_HIP(hipGetLastError());
     HM_HIP(hipEventRecord(h->ev_body, h->stream));
@@ -2637,6 +2659,13 @@ static int body_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, uint8_
                            (const int *)h->d_btri, (const uint8_t *)h->d_breg, st);
         HM_HIP(hipGetLastError());
         h->stats_frames++;
+    }
+    if (h->rec_on) {                 // (behind the event as well)
+        const RecBox &b = h->rec_box;
+        hipLaunchKernelGGL(k_rec_copy, dim3(hm_cdiv((b.pitch >> 2) * b.bh, 256)), dim3(256), 0, h->stream, h->W, b,
+                           (const uint8_t *)h->d_breg, rec_dst);
+        HM_HIP(hipGetLastError());
+        h->rec_frames++;
     }
     return HM_OK;
 }
@@ -2723,7 +2752,7 @@ extern "C" int hm_body_stats_end(hm_ctx_t h)
     if (!h->d_stsum) return HM_OK;
     HM_HIP(hipSetDevice(h->device));
     HM_HIP(hipStreamSynchronize(h->stream));
-    hipError_t e = h->own.free(&h->d_breg);
+    hipError_t e = h->rec_on ? hipSuccess : h->own.free(&h->d_breg);     // (the record's copy reads the same plane)
     if (e == hipSuccess) e = h->own.free(&h->d_stsum);
     if (e == hipSuccess) e = h->own.free(&h->d_stmax);
     if (e == hipSuccess) e = h->own.free(&h->d_stimg);
@@ -2845,6 +2874,313 @@ extern "C" int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min
         score[i] = sc[order[i]];
     }
     *count = found;
+    return HM_OK;
+}
+
+// ---- the registered video kept on the device, and the reductions over it (roi_kernels.h) ---------------------------
+#define REC_CHUNK_BYTES ((size_t)64 << 20)
+#define REC_MAX_FRAMES (1 << 24)
+
+// stop recording and free the record (the caller has checked that there is one)
+static int body_rec_drop(hm_ctx *h)
+{
+    h->rec_on = false;
+    h->rec_frames = 0;
+    HM_HIP(hipSetDevice(h->device));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    hipError_t e = hipSuccess;
+    for (uint8_t *&c : h->rec_chunks) {
+        const hipError_t e1 = h->own.free(&c);
+        if (e == hipSuccess) e = e1;
+    }
+    h->rec_chunks.clear();
+    if (e == hipSuccess) e = h->own.free(&h->d_rec_tab);
+    if (e == hipSuccess) e = h->own.free(&h->d_rec_tmp);
+    if (e == hipSuccess && !h->stats_on) e = h->own.free(&h->d_breg);
+    HM_HIP(e);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_begin(hm_ctx_t h, uint64_t max_bytes)
+{
+    HM_ARG(h != nullptr, "hm_body_rec_begin: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_map_build(h);
+    if (rc) return rc;
+    if (h->rec_on) {
+        rc = body_rec_drop(h);
+        if (rc) return rc;
+    }
+    const size_t n = (size_t)h->W * h->H;
+    if (h->h_btri.empty()) {
+        h->h_btri.resize(n);
+        HM_HIP(hipMemcpyAsync(h->h_btri.data(), h->d_btri, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HM_HIP(hipStreamSynchronize(h->stream));
+    }
+    int c0 = h->W, c1 = -1, r0 = h->H, r1 = -1;
+    for (int r = 0; r < h->H; r++)
+        for (int c = 0; c < h->W; c++)
+            if (h->h_btri[(size_t)r * h->W + c] >= 0) {
+                c0 = std::min(c0, c); c1 = std::max(c1, c);
+                r0 = std::min(r0, r); r1 = std::max(r1, r);
+            }
+    if (c1 < 0) c0 = c1 = r0 = r1 = 0;          // (an empty map: one pixel, registered as 0)
+    RecBox &b = h->rec_box;
+    b.c0 = c0; b.r0 = r0; b.bw = c1 - c0 + 1; b.bh = r1 - r0 + 1;
+    b.pitch = (b.bw + 3) & ~3;
+    b.fs = ((size_t)b.pitch * b.bh + 15) & ~(size_t)15;
+    b.fpc = h->rec_chunk > 0 ? h->rec_chunk : (int)std::max<size_t>(1, REC_CHUNK_BYTES / b.fs);
+    h->rec_max = max_bytes;
+    h->rec_cap = (int)std::min<unsigned long long>(max_bytes / b.fs, REC_MAX_FRAMES);
+    HM_HIP(h->own.alloc(&h->d_breg, n));
+    h->rec_frames = 0;
+    h->rec_on = true;
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_end(hm_ctx_t h)
+{
+    HM_ARG(h != nullptr, "hm_body_rec_end: NULL handle");
+    HM_JOIN_LAZY(h);
+    if (!h->rec_on) return HM_OK;
+    return body_rec_drop(h);
+}
+
+extern "C" int hm_body_rec_count(hm_ctx_t h, int *frames)
+{
+    HM_ARG(h && frames, "hm_body_rec_count: NULL argument");
+    HM_JOIN_LAZY(h);
+    *frames = h->rec_on ? h->rec_frames : 0;
+    return HM_OK;
+}
+
+// where the next frame of the record goes; allocates the chunk it starts
+static int body_rec_slot(hm_ctx *h, const char *who, uint8_t **dst)
+{
+    const RecBox &b = h->rec_box;
+    if (h->rec_frames >= h->rec_cap) {
+        hm_set_error("%s: the record holds %d frames of %zu bytes (a box of %d x %d pixels) and its budget of %llu bytes holds "
+                     "%d: nothing appended", who, h->rec_frames, b.fs, b.bw, b.bh, h->rec_max, h->rec_cap);
+        return HM_ERR_STATE;
+    }
+    const int ch = h->rec_frames / b.fpc;
+    if (ch == (int)h->rec_chunks.size()) {
+        const int frames = std::min(b.fpc, h->rec_cap - ch * b.fpc);
+        uint8_t *p = nullptr;
+        HM_HIP(h->own.alloc(&p, (size_t)frames * b.fs));
+        h->rec_chunks.push_back(p);
+    }
+    *dst = h->rec_chunks[ch] + (size_t)(h->rec_frames - ch * b.fpc) * b.fs;
+    return HM_OK;
+}
+
+static int body_rec_begun(hm_ctx *h, const char *who)
+{
+    if (!h->rec_on) { hm_set_error("%s: no record (hm_body_rec_begin first)", who); return HM_ERR_STATE; }
+    HM_HIP(hipSetDevice(h->device));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_fetch(hm_ctx_t h, int k0, int n, uint8_t *out)
+{
+    HM_ARG(h != nullptr, "hm_body_rec_fetch: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_begun(h, "hm_body_rec_fetch");
+    if (rc) return rc;
+    HM_ARG(k0 >= 0 && n >= 0 && k0 <= h->rec_frames && n <= h->rec_frames - k0,
+           "hm_body_rec_fetch: frames %d .. %d of a record of %d", k0, k0 + n - 1, h->rec_frames);
+    HM_ARG(out || n == 0, "hm_body_rec_fetch: NULL output");
+    HM_HIP(hipStreamSynchronize(h->stream));
+    const RecBox &b = h->rec_box;
+    const size_t px = (size_t)h->W * h->H;
+    for (int k = 0; k < n; k++) {
+        uint8_t *o = out + (size_t)k * px;
+        memset(o, 0, px);
+        const int ch = (k0 + k) / b.fpc;
+        const uint8_t *src = h->rec_chunks[ch] + (size_t)(k0 + k - ch * b.fpc) * b.fs;
+        HM_HIP(hipMemcpy2D(o + (size_t)b.r0 * h->W + b.c0, (size_t)h->W, src, (size_t)b.pitch, (size_t)b.bw, (size_t)b.bh,
+                           hipMemcpyDeviceToHost));
+    }
+    return HM_OK;
+}
+
+// a reduction may start: there are frames, and the chunks' addresses are on the device
+static int body_rec_ready(hm_ctx *h, const char *who)
+{
+    const int rc = body_rec_begun(h, who);
+    if (rc) return rc;
+    if (h->rec_frames < 1) { hm_set_error("%s: no frame recorded since hm_body_rec_begin", who); return HM_ERR_STATE; }
+    const size_t bytes = h->rec_chunks.size() * sizeof(uint8_t *);
+    HM_HIP(h->own.grow(&h->d_rec_tab, bytes));       // (every reduction waits for its results: nothing in flight reads it)
+    HM_HIP(hipMemcpyAsync(h->d_rec_tab, h->rec_chunks.data(), bytes, hipMemcpyHostToDevice, h->stream));
+    return HM_OK;
+}
+
+// the reductions' buffers, carved from one allocation (16-byte aligned pieces)
+struct RecCarve {
+    uint8_t *base;
+    size_t off;
+    template <typename T> T *take(size_t count)
+    {
+        off = (off + 15) & ~(size_t)15;
+        T *p = (T *)(base + off);
+        off += count * sizeof(T);
+        return p;
+    }
+};
+
+extern "C" int hm_body_rec_label_sums(hm_ctx_t h, const int32_t *labels, int L, uint64_t *out)
+{
+    HM_ARG(labels && out && L >= 1, "hm_body_rec_label_sums: NULL argument or %d labels", L);
+    HM_ARG(h != nullptr, "hm_body_rec_label_sums: NULL handle");
+    const size_t n = (size_t)h->W * h->H;
+    for (size_t p = 0; p < n; p++)
+        HM_ARG(labels[p] >= -1 && labels[p] < L, "hm_body_rec_label_sums: label %d at pixel %zu outside -1..%d", (int)labels[p],
+               p, L - 1);
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_label_sums");
+    if (rc) return rc;
+    const RecBox &b = h->rec_box;
+    const int F = h->rec_frames, nb = b.pitch * b.bh;
+    int *d_img = nullptr, *d_lab = nullptr;
+    unsigned long long *d_sum = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+        RecCarve cv = {pass ? h->d_rec_tmp : nullptr, 0};
+        d_img = cv.take<int>(n);
+        d_lab = cv.take<int>(nb);
+        d_sum = cv.take<unsigned long long>((size_t)F * L);
+        if (!pass) HM_HIP(h->own.grow(&h->d_rec_tmp, cv.off));
+    }
+    HM_HIP(hipMemcpyAsync(d_img, labels, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(d_sum, 0, (size_t)F * L * sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(k_rec_box_labels, dim3(hm_cdiv(nb, 256)), dim3(256), 0, h->stream, h->W, b, (const int *)h->d_btri,
+                       (const int *)d_img, d_lab);
+    hipLaunchKernelGGL(k_rec_label_sums, dim3(hm_cdiv(nb >> 2, 256), std::min(F, 1024)), dim3(256), 0, h->stream, b,
+                       (const uint8_t *const *)h->d_rec_tab, F, (const int *)d_lab, L, d_sum);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, d_sum, (size_t)F * L * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// seeds are pixels of the map
+static int body_rec_seeds(hm_ctx *h, int P, const int32_t *seeds, const char *who)
+{
+    for (int s = 0; s < P; s++) {
+        const int c = seeds[2 * s], r = seeds[2 * s + 1];
+        if (!(c >= 0 && c < h->W && r >= 0 && r < h->H && h->h_btri[(size_t)r * h->W + c] >= 0)) {
+            hm_set_error("%s: seed %d (column %d, row %d) is not a pixel of the body map", who, s, c, r);
+            return HM_ERR_ARG;
+        }
+    }
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_seed_sums(hm_ctx_t h, int P, const int32_t *seeds, double r_disc, double r_in, double r_out, int R,
+                                     uint32_t *n_T, uint32_t *n_G, uint64_t *T, uint64_t *G, int64_t *U, uint64_t *w1,
+                                     uint64_t *w2, int64_t *c, int64_t *u1, int64_t *u2)
+{
+    HM_ARG(P >= 1 && seeds, "hm_body_rec_seed_sums: %d seeds", P);
+    HM_ARG(r_disc >= 0.0 && r_disc <= REC_RMAX && r_in >= 0.0 && r_in <= r_out && r_out <= REC_RMAX,
+           "hm_body_rec_seed_sums: radii %g, %g, %g (need 0 <= r_disc <= %d and 0 <= r_in <= r_out <= %d)", r_disc, r_in, r_out,
+           REC_RMAX, REC_RMAX);
+    HM_ARG(R >= 0 && R <= REC_WIN_RMAX, "hm_body_rec_seed_sums: window radius %d outside 0..%d", R, REC_WIN_RMAX);
+    HM_ARG(h != nullptr, "hm_body_rec_seed_sums: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_seed_sums");
+    if (rc) return rc;
+    rc = body_rec_seeds(h, P, seeds, "hm_body_rec_seed_sums");
+    if (rc) return rc;
+    const int F = h->rec_frames;
+    HM_ARG((long long)F * P < (1ll << 30), "hm_body_rec_seed_sums: %d frames x %d seeds", F, P);
+    // the pixels of every disc and ring, and the bound that keeps sum U^2 exact: |U| <= 255 n_T n_G
+    const double rd2 = r_disc * r_disc, ri2 = r_in * r_in, ro2 = r_out * r_out;
+    const int Rg = (int)std::max(r_disc, r_out);
+    std::vector<unsigned> cnt(2 * (size_t)P, 0);
+    for (int s = 0; s < P; s++) {
+        for (int dy = -Rg; dy <= Rg; dy++)
+            for (int dx = -Rg; dx <= Rg; dx++) {
+                const int x = seeds[2 * s] + dx, y = seeds[2 * s + 1] + dy;
+                if (x < 0 || x >= h->W || y < 0 || y >= h->H || h->h_btri[(size_t)y * h->W + x] < 0) continue;
+                const double d2 = (double)(dx * dx + dy * dy);
+                if (d2 <= rd2) cnt[s]++;
+                if (d2 >= ri2 && d2 <= ro2) cnt[P + s]++;
+            }
+        const unsigned __int128 m = (unsigned __int128)255 * cnt[s] * cnt[P + s];
+        HM_ARG(m * m * (unsigned __int128)F < ((unsigned __int128)1 << 63),
+               "hm_body_rec_seed_sums: seed %d: F (255 n_T n_G)^2 = %d (255 x %u x %u)^2 could pass 2^63", s, F, cnt[s], cnt[P + s]);
+    }
+    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
+    RecSeeds g;
+    RecWin q;
+    int2 *d_seeds = nullptr;
+    unsigned *d_cnt = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+        RecCarve cv = {pass ? h->d_rec_tmp : nullptr, 0};
+        d_seeds = cv.take<int2>(P);
+        d_cnt = cv.take<unsigned>(2 * (size_t)P);
+        g.T = cv.take<unsigned long long>(fp);
+        g.G = cv.take<unsigned long long>(fp);
+        g.U = cv.take<long long>(fp);
+        q.w1 = cv.take<unsigned long long>(P * nw);
+        q.w2 = cv.take<unsigned long long>(P * nw);
+        q.c = cv.take<long long>(P * nw);
+        q.u1 = cv.take<long long>(P);
+        q.u2 = cv.take<long long>(P);
+        if (!pass) HM_HIP(h->own.grow(&h->d_rec_tmp, cv.off));
+    }
+    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_cnt, cnt.data(), 2 * (size_t)P * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    g.b = h->rec_box; g.chunks = (const uint8_t *const *)h->d_rec_tab; g.F = F; g.P = P; g.R = Rg;
+    g.seeds = d_seeds; g.rd2 = rd2; g.ri2 = ri2; g.ro2 = ro2; g.nT = d_cnt; g.nG = d_cnt + P;
+    hipLaunchKernelGGL(k_rec_seed_traces, dim3(hm_cdiv((int)fp, 4)), dim3(256), 0, h->stream, g);
+    q.b = h->rec_box; q.chunks = g.chunks; q.F = F; q.P = P; q.R = R; q.seeds = d_seeds; q.U = g.U;
+    hipLaunchKernelGGL(k_rec_window_sums, dim3(hm_cdiv((int)nw, 256), P), dim3(256), 0, h->stream, q);
+    HM_HIP(hipGetLastError());
+    if (n_T) memcpy(n_T, cnt.data(), (size_t)P * sizeof(uint32_t));
+    if (n_G) memcpy(n_G, cnt.data() + P, (size_t)P * sizeof(uint32_t));
+    if (T) HM_HIP(hipMemcpyAsync(T, g.T, fp * 8, hipMemcpyDeviceToHost, h->stream));
+    if (G) HM_HIP(hipMemcpyAsync(G, g.G, fp * 8, hipMemcpyDeviceToHost, h->stream));
+    if (U) HM_HIP(hipMemcpyAsync(U, g.U, fp * 8, hipMemcpyDeviceToHost, h->stream));
+    if (w1) HM_HIP(hipMemcpyAsync(w1, q.w1, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
+    if (w2) HM_HIP(hipMemcpyAsync(w2, q.w2, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
+    if (c) HM_HIP(hipMemcpyAsync(c, q.c, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
+    if (u1) HM_HIP(hipMemcpyAsync(u1, q.u1, (size_t)P * 8, hipMemcpyDeviceToHost, h->stream));
+    if (u2) HM_HIP(hipMemcpyAsync(u2, q.u2, (size_t)P * 8, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds, int R, const uint16_t *weights, uint64_t *out)
+{
+    HM_ARG(P >= 1 && seeds && weights && out, "hm_body_rec_weighted_sums: NULL argument or %d seeds", P);
+    HM_ARG(R >= 0 && R <= REC_RMAX, "hm_body_rec_weighted_sums: window radius %d outside 0..%d", R, REC_RMAX);
+    HM_ARG(h != nullptr, "hm_body_rec_weighted_sums: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_weighted_sums");
+    if (rc) return rc;
+    rc = body_rec_seeds(h, P, seeds, "hm_body_rec_weighted_sums");
+    if (rc) return rc;
+    const int F = h->rec_frames;
+    HM_ARG((long long)F * P < (1ll << 30), "hm_body_rec_weighted_sums: %d frames x %d seeds", F, P);
+    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
+    int2 *d_seeds = nullptr;
+    uint16_t *d_w = nullptr;
+    unsigned long long *d_out = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+        RecCarve cv = {pass ? h->d_rec_tmp : nullptr, 0};
+        d_seeds = cv.take<int2>(P);
+        d_w = cv.take<uint16_t>(P * nw);
+        d_out = cv.take<unsigned long long>(fp);
+        if (!pass) HM_HIP(h->own.grow(&h->d_rec_tmp, cv.off));
+    }
+    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_w, weights, P * nw * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_rec_weighted_sums, dim3(hm_cdiv((int)fp, 4)), dim3(256), 0, h->stream, h->rec_box,
+                       (const uint8_t *const *)h->d_rec_tab, F, P, R, (const int2 *)d_seeds, (const uint16_t *)d_w, d_out);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, d_out, fp * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
     return HM_OK;
 }
 

@@ -278,6 +278,67 @@ class Renderer:
         k = min(n.value, cap)
         return idx[:k].copy(), sc[:k].copy(), n.value
 
+    # -- the registered video kept on the device (hm_body_rec_*; hydra_mi.body.BodyReadout(keep=True), hydra_mi.roi) --
+    def body_rec_begin(self, max_bytes=8 << 30):
+        """hm_body_rec_begin: every body_warp / body_warp_dev from now on appends its registered frame to a record in device
+        memory of at most max_bytes; again: start over."""
+        _lib.check(_lib.lib().hm_body_rec_begin(self._h, int(max_bytes)), "hm_body_rec_begin")
+
+    def body_rec_end(self):
+        """hm_body_rec_end: stop recording and free the record (harmless when not begun)."""
+        _lib.check(_lib.lib().hm_body_rec_end(self._h), "hm_body_rec_end")
+
+    def body_rec_count(self):
+        """-> frames recorded since body_rec_begin"""
+        n = ctypes.c_int(0)
+        _lib.check(_lib.lib().hm_body_rec_count(self._h, ctypes.byref(n)), "hm_body_rec_count")
+        return n.value
+
+    def body_rec_fetch(self, k0=0, n=None):
+        """-> recorded frames k0 .. k0 + n - 1 (default: all from k0) as (n, H, W) uint8"""
+        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
+        _lib.check(_lib.lib().hm_body_rec_fetch(self._h, int(k0), n, _lib.ptr(out)), "hm_body_rec_fetch")
+        return out
+
+    def body_rec_label_sums(self, labels, L):
+        """hm_body_rec_label_sums: a label image (H, W) int32 given now -> (F, L) uint64, the sums per label of every
+        recorded frame."""
+        lab = np.ascontiguousarray(labels, np.int32)
+        if lab.shape != (self.ny, self.nx):
+            raise ValueError("label image of shape %r for %dx%d frames" % (lab.shape, self.nx, self.ny))
+        out = np.empty((self.body_rec_count(), int(L)), np.uint64)
+        _lib.check(_lib.lib().hm_body_rec_label_sums(self._h, _lib.ptr(lab), int(L), _lib.ptr(out)), "hm_body_rec_label_sums")
+        return out
+
+    def body_rec_seed_sums(self, seeds, r_disc, r_in, r_out, R):
+        """hm_body_rec_seed_sums: seeds (P, 2) integer (column, row) map pixels -> dict: n_T, n_G (P,) uint32; T, G (F, P)
+        uint64 disc and ring sums; U (F, P) int64 = n_G T - n_T G; w1, w2 (P, 2R+1, 2R+1) uint64 and c (same, int64):
+        sums of v, v^2 and v U per window pixel; u1, u2 (P,) int64: sums of U and U^2."""
+        sd = np.ascontiguousarray(seeds, np.int32).reshape(-1, 2)
+        P, F, S = sd.shape[0], self.body_rec_count(), 2 * int(R) + 1
+        o = dict(n_T=np.empty(P, np.uint32), n_G=np.empty(P, np.uint32), T=np.empty((F, P), np.uint64),
+                 G=np.empty((F, P), np.uint64), U=np.empty((F, P), np.int64), w1=np.empty((P, S, S), np.uint64),
+                 w2=np.empty((P, S, S), np.uint64), c=np.empty((P, S, S), np.int64), u1=np.empty(P, np.int64),
+                 u2=np.empty(P, np.int64))
+        _lib.check(_lib.lib().hm_body_rec_seed_sums(self._h, P, _lib.ptr(sd), float(r_disc), float(r_in), float(r_out), int(R),
+                                                    *[_lib.ptr(o[k]) for k in ("n_T", "n_G", "T", "G", "U", "w1", "w2", "c",
+                                                                               "u1", "u2")]), "hm_body_rec_seed_sums")
+        return o
+
+    def body_rec_weighted_sums(self, seeds, weights, R):
+        """hm_body_rec_weighted_sums: weights (P, 2R+1, 2R+1) uint16 round the seeds -> (F, P) uint64 sums of weight x
+        value of every recorded frame."""
+        sd = np.ascontiguousarray(seeds, np.int32).reshape(-1, 2)
+        S = 2 * int(R) + 1
+        w = np.ascontiguousarray(weights, np.uint16)
+        if w.shape != (sd.shape[0], S, S):
+            raise ValueError("weights of shape %r for %d seeds and windows of %d x %d" % (w.shape, sd.shape[0], S, S))
+        out = np.empty((self.body_rec_count(), sd.shape[0]), np.uint64)
+        _lib.check(_lib.lib().hm_body_rec_weighted_sums(self._h, sd.shape[0], _lib.ptr(sd), int(R), _lib.ptr(w), _lib.ptr(out)),
+                   "hm_body_rec_weighted_sums")
+        return out
+
     def screenshot(self, saveall=True, basename="screenshot", X=None):
         """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask
         at state X (default: the vertex buffer) and returns the overlay.  Unlike the reference the names carry no

@@ -34,6 +34,13 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      over the recorded states then reads them out as --points would (points, point_means, point_counts,
                      <fn_out>_points.txt); --points-out FILE.csv writes them in the format --points reads.  Not together
                      with --points.
+    --rois           with --find-points or --points: keep the registered video on the device while tracking (hydra_mi.body,
+                     BodyReadout(keep=True), at most --rois-max-gb GiB) and build footprints, ROIs and neuropil-corrected
+                     dF/F traces of the points from it (hydra_mi.roi.extract): roi_points (indices of the points inside
+                     the mesh, the rows of the rest), roi_footprints, roi_labels (H x W), roi_counts, roi_ring_counts,
+                     roi_F, roi_Fnp, roi_dff (frames x points), roi_seed_fallback.  With --find-points the disc traces
+                     come from the record as well: no second pass over the video.  A video whose record would not fit is
+                     said to be so and read out as without --rois.
     --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
                      (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
                      diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
@@ -47,7 +54,9 @@ import numpy as np
 
 import hydra_mi  # noqa: F401
 from hydra_mi import kalman
-from hydra_mi.body import BodyReadout, read_out, read_points_csv, write_points_csv, write_points_txt
+from hydra_mi import roi
+from hydra_mi.body import (BodyReadout, read_out, read_out_recorded, read_points_csv, record_bytes, write_points_csv,
+                           write_points_txt)
 from hydra_mi.distmesh_dyn import DistMesh
 from hydra_mi.pipeline import FlowEKFPipeline, VideoStream
 from hydra_mi.renderer import FlowStream
@@ -78,6 +87,10 @@ def main(argv=None):
     parser.add_argument("--find-radius", default=6, type=int, help="half width of the window a cell is the maximum of (1..16)")
     parser.add_argument("--find-score", default="corr", choices=("corr", "std", "range"), help="the summary image searched")
     parser.add_argument("--points-out", default=None, help="write the points found here (CSV lines name,x,y)")
+    parser.add_argument("--rois", action="store_true", help="footprints, ROIs and dF/F traces of the points (roi_* arrays)")
+    parser.add_argument("--rois-max-gb", default=8.0, type=float, help="device memory the kept registered video may take (GiB)")
+    parser.add_argument("--roi-thr", default=None, type=float, help="footprint threshold of an ROI (default %g)" % roi.DEFAULT_THR)
+    parser.add_argument("--roi-alpha", default=0.7, type=float, help="share of the ring trace taken off the ROI trace")
     parser.add_argument("--smooth", action="store_true", help="smooth the track backward: Xs, Xs_std in the states file")
     parser.add_argument("--smooth-max-gb", default=8.0, type=float, help="device memory the smoother may take (GiB)")
     args = parser.parse_args(argv)
@@ -88,6 +101,8 @@ def main(argv=None):
             parser.error("--find-points needs N >= 1 and a --find-radius in 1..16")
     elif args.points_out is not None:
         parser.error("--points-out goes with --find-points")
+    if args.rois and args.find_points is None and args.points is None:
+        parser.error("--rois reads cells out: it needs --find-points or --points")
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
 
@@ -117,7 +132,16 @@ def main(argv=None):
     def make_body(kf):
         if not readout:
             return None
-        body = BodyReadout(kf, points=points, point_radius=args.point_radius, video=reg_video, stats=find)
+        keep, budget = args.rois, int(args.rois_max_gb * (1 << 30))
+        if keep:
+            probe = kf.state.renderer.body_map()[0]
+            need = record_bytes(probe, max(capture.frames.shape[0] - 1, 1))
+            if need > budget:
+                print("The registered video takes %d bytes on the device, --rois-max-gb allows %d: no ROIs, the disc "
+                      "read-out instead" % (need, budget))
+                keep = False
+        body = BodyReadout(kf, points=points, point_radius=args.point_radius, video=reg_video, stats=find, keep=keep,
+                           keep_bytes=budget)
         for i in np.flatnonzero(body.outside):
             print("Warning: point %d (%g, %g) lies outside the mesh: NaN in every frame" % (i, points[i, 0], points[i, 1]))
         return body
@@ -188,7 +212,10 @@ def main(argv=None):
         extra.update(body_mean=sm_img["mean"], body_std=sm_img["std"], body_max=sm_img["max"], body_corr=sm_img["corr"],
                      found_points=found, found_scores=scores)
         print("Found %d points (%s, radius %d) in %d frames" % (len(found), args.find_score, args.find_radius, sm_img["frames"]))
-        res = read_out(kf, states, capture.frames[1:1 + len(states)], found, args.point_radius)    # state k: frame k + 1
+        if body.keep:                # the registered video is on the device: the discs are summed there
+            res = read_out_recorded(body, states, found, args.point_radius)
+        else:
+            res = read_out(kf, states, capture.frames[1:1 + len(states)], found, args.point_radius)    # state k: frame k + 1
         extra.update(points=res["points"], point_means=res["point_means"], point_counts=res["point_counts"])
         fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
         write_points_txt(fn_pts, res["points"])
@@ -196,6 +223,17 @@ def main(argv=None):
         if args.points_out is not None:
             write_points_csv(args.points_out, found)
             print("Points found: %s" % args.points_out)
+    if body is not None and body.keep:
+        pts = found if find else points
+        inside = np.flatnonzero(body.locate(pts)[0] >= 0)
+        if len(inside) and len(states):
+            e = roi.extract(body, pts[inside], r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
+            extra.update(roi_points=inside, roi_footprints=e["footprints"], roi_labels=e["roi_labels"],
+                         roi_counts=e["roi_counts"], roi_ring_counts=e["ring_counts"], roi_F=e["F_roi"], roi_Fnp=e["F_np"],
+                         roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
+            print("ROIs: %d cells, %d..%d pixels, %d kept their disc" % (len(inside), e["roi_counts"].min(),
+                                                                          e["roi_counts"].max(), e["seed_fallback"].sum()))
+        kf.state.renderer.body_rec_end()
     if reg_video is not None:
         reg_video.close()
         print("Registered video: %d frames in %s" % (reg_video.frames, args.registered))
