@@ -540,7 +540,14 @@ int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int
  *                  overlap; radii at most 32.  HM_ERR_ARG with the numbers when F (255 n_T n_G)^2 could pass 2^63
  *                  (every sum is exact in 64 bits below that), and for a seed that is no pixel of the map.
  *   weighted_sums  P windows of (2R + 1)^2 uint16 weights round the seeds, R <= 32 -> out[k * P + s] =
- *                  sum a_s(p) v_k(p): traces of ROIs that overlap or carry weights. */
+ *                  sum a_s(p) v_k(p): traces of ROIs that overlap or carry weights.
+ *   trace_products P seeds and one int32 trace per seed, q[k * P + s] (any values, negative ones too), R <= 16 ->
+ *                  out[s (2R + 1)^2 + p] = sum_k v_k(p) q[k * P + s] (int64; 0 off the frame, outside the map): the
+ *                  product of every window pixel with a trace the host supplies, what the shape step of demixing
+ *                  repeats every iteration (hydra_mi/demix.py).  Exact while
+ *                  F x 255 x 2^31 < 2^63, HM_ERR_ARG with the numbers beyond that and for a seed that is no pixel
+ *                  of the map.  The frames are split over the grid in runs of hm_ctx_tune "rec_tp_frames" (1..1024,
+ *                  default 32) and the partial sums meet in 64-bit integer atomics: the same result in any order. */
 int hm_body_rec_begin(hm_ctx_t h, uint64_t max_bytes);
 int hm_body_rec_end(hm_ctx_t h);
 int hm_body_rec_count(hm_ctx_t h, int *frames);
@@ -550,6 +557,7 @@ int hm_body_rec_seed_sums(hm_ctx_t h, int P, const int32_t *seeds, double r_disc
                           uint32_t *n_T, uint32_t *n_G, uint64_t *T, uint64_t *G, int64_t *U, uint64_t *w1,
                           uint64_t *w2, int64_t *c, int64_t *u1, int64_t *u2);
 int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds, int R, const uint16_t *weights, uint64_t *out);
+int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seeds, int R, const int32_t *q, int64_t *out);
 
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy

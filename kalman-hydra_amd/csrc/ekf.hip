@@ -281,6 +281,7 @@ struct hm_ctx {
     int rec_frames = 0;              // frames appended since hm_body_rec_begin
     int rec_cap = 0;                 // frames the budget of hm_body_rec_begin holds
     int rec_chunk = 0;               // hm_ctx_tune "body_rec_chunk": frames per chunk (0: REC_CHUNK_BYTES worth; tests lower it)
+    int rec_tp_frames = 32;          // hm_ctx_tune "rec_tp_frames": frames per workgroup of hm_body_rec_trace_products
     unsigned long long rec_max = 0;  // the budget in bytes
     RecBox rec_box = {0, 0, 0, 0, 0, 0, 0};
     std::vector<uint8_t *> rec_chunks;
@@ -662,6 +663,9 @@ extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
     } else if (!strcmp(key, "body_rec_chunk")) {       // tests only: frames per chunk of the next hm_body_rec_begin
         HM_ARG(value >= 0, "hm_ctx_tune: body_rec_chunk must be >= 0 (0: the default size)");
         h->rec_chunk = value;
+    } else if (!strcmp(key, "rec_tp_frames")) {        // frames per workgroup of hm_body_rec_trace_products
+        HM_ARG(value >= 1 && value <= REC_TP_MAX, "hm_ctx_tune: rec_tp_frames must be in 1..%d", REC_TP_MAX);
+        h->rec_tp_frames = value;
     } else {
         hm_set_error("hm_ctx_tune: unknown key '%s'", key);
         return HM_ERR_ARG;
@@ -3180,6 +3184,47 @@ extern "C" int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds
                        (const uint8_t *const *)h->d_rec_tab, F, P, R, (const int2 *)d_seeds, (const uint16_t *)d_w, d_out);
     HM_HIP(hipGetLastError());
     HM_HIP(hipMemcpyAsync(out, d_out, fp * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seeds, int R, const int32_t *q, int64_t *out)
+{
+    HM_ARG(P >= 1 && seeds && q && out, "hm_body_rec_trace_products: NULL argument or %d seeds", P);
+    HM_ARG(R >= 0 && R <= REC_WIN_RMAX, "hm_body_rec_trace_products: window radius %d outside 0..%d", R, REC_WIN_RMAX);
+    HM_ARG(h != nullptr, "hm_body_rec_trace_products: NULL handle");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_trace_products");
+    if (rc) return rc;
+    rc = body_rec_seeds(h, P, seeds, "hm_body_rec_trace_products");
+    if (rc) return rc;
+    const int F = h->rec_frames;
+    HM_ARG((long long)F * P < (1ll << 30), "hm_body_rec_trace_products: %d frames x %d seeds", F, P);
+    // |v q| <= 255 x 2^31 per frame
+    HM_ARG((unsigned __int128)F * 255u * ((unsigned __int128)1 << 31) < ((unsigned __int128)1 << 63),
+           "hm_body_rec_trace_products: F x 255 x 2^31 = %d x 255 x 2^31 could pass 2^63", F);
+    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
+    const int tiles = hm_cdiv((int)nw, 64);
+    HM_ARG((long long)P * tiles < (1ll << 31), "hm_body_rec_trace_products: %d seeds x %d tiles of the window", P, tiles);
+    RecTP g;
+    int2 *d_seeds = nullptr;
+    int *d_q = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+        RecCarve cv = {pass ? h->d_rec_tmp : nullptr, 0};
+        d_seeds = cv.take<int2>(P);
+        d_q = cv.take<int>(fp);
+        g.out = cv.take<unsigned long long>(P * nw);
+        if (!pass) HM_HIP(h->own.grow(&h->d_rec_tmp, cv.off));
+    }
+    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_q, q, fp * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(g.out, 0, P * nw * sizeof(unsigned long long), h->stream));
+    g.b = h->rec_box; g.chunks = (const uint8_t *const *)h->d_rec_tab; g.F = F; g.P = P; g.R = R;
+    g.tpf = h->rec_tp_frames; g.seeds = d_seeds; g.q = d_q;
+    const int runs = hm_cdiv(F, g.tpf);
+    hipLaunchKernelGGL(k_rec_trace_products, dim3(P * tiles, std::min(runs, 65535)), dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, g.out, P * nw * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HM_HIP(hipStreamSynchronize(h->stream));
     return HM_OK;
 }

@@ -201,3 +201,53 @@ __global__ __launch_bounds__(256) void k_rec_weighted_sums(RecBox b, const uint8
     sum = d_wave_sum64(sum);
     if (lane == 0) out[(size_t)k * P + s] = sum;
 }
+
+#define REC_TP_MAX 1024                // the most frames of a workgroup's run (hm_ctx_tune "rec_tp_frames")
+
+struct RecTP {
+    RecBox b;
+    const uint8_t *const *chunks;
+    int F, P, R, tpf;                  // frames, seeds, half width of the window, frames per run
+    const int2 *seeds;
+    const int *q;                      // F x P, frame-major
+    unsigned long long *out;           // P x (2R + 1)^2, zeroed by the caller
+};
+
+// out[s, p] += sum over a run of frames of v_k(p) q[k, s].  A workgroup takes 64 consecutive window pixels of one seed
+// (blockIdx.x; a lane per pixel, so a wave reads a record row in runs of 2R + 1 bytes) and runs of tpf frames
+// (blockIdx.y strides over them).  The run's q sits in LDS; the four waves take every fourth frame of the run, add
+// their sums through LDS, and one wave adds the result to `out` with one 64-bit atomic per pixel: whole numbers mod
+// 2^64, so the order of the adds does not matter.  A window pixel outside the box adds nothing.
+__global__ __launch_bounds__(256) void k_rec_trace_products(RecTP g)
+{
+    __shared__ int qs[REC_TP_MAX];
+    __shared__ long long part[3][64];
+    const int S = 2 * g.R + 1, n = S * S, tiles = (n + 63) >> 6;
+    const int s = blockIdx.x / tiles, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int i = (blockIdx.x - s * tiles) * 64 + lane;
+    const int2 sd = g.seeds[s];
+    bool in = false;
+    size_t off = 0;
+    if (i < n) {
+        const int iy = i / S, dy = iy - g.R, dx = i - iy * S - g.R;
+        const int x = sd.x + dx - g.b.c0, y = sd.y + dy - g.b.r0;
+        in = x >= 0 && x < g.b.bw && y >= 0 && y < g.b.bh;
+        if (in) off = (size_t)y * g.b.pitch + x;
+    }
+    long long acc = 0;
+    const int runs = (g.F + g.tpf - 1) / g.tpf;
+    for (int run = blockIdx.y; run < runs; run += gridDim.y) {         // (the same trips for the whole workgroup)
+        const int k0 = run * g.tpf, m = min(g.tpf, g.F - k0);
+        __syncthreads();                                               // the previous run's q has been read
+        for (int j = threadIdx.x; j < m; j += 256) qs[j] = g.q[(size_t)(k0 + j) * g.P + s];
+        __syncthreads();
+        if (in)
+            for (int j = w; j < m; j += 4) acc += (long long)d_rec_frame(g.b, g.chunks, k0 + j)[off] * (long long)qs[j];
+    }
+    if (w) part[w - 1][lane] = acc;
+    __syncthreads();
+    if (w == 0 && in) {
+        acc += part[0][lane] + part[1][lane] + part[2][lane];
+        atomicAdd(g.out + (size_t)s * n + i, (unsigned long long)acc);
+    }
+}

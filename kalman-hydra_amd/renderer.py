@@ -339,6 +339,20 @@ class Renderer:
                    "hm_body_rec_weighted_sums")
         return out
 
+    def body_rec_trace_products(self, seeds, q, R):
+        """hm_body_rec_trace_products: one int32 trace per seed, q (F, P) -> (P, 2R+1, 2R+1) int64, the sum over the
+        recorded frames of every window pixel times the seed's trace (0 off the frame and outside the map)."""
+        sd = np.ascontiguousarray(seeds, np.int32).reshape(-1, 2)
+        S, F = 2 * int(R) + 1, self.body_rec_count()
+        q = np.asarray(q)
+        if q.dtype != np.int32 or q.ndim != 2 or q.shape[1] != sd.shape[0] or (F and q.shape[0] != F):   # (F 0: the call says why)
+            raise ValueError("traces %s of shape %r for %d frames and %d seeds (need int32)" % (q.dtype, q.shape, F, sd.shape[0]))
+        q = np.ascontiguousarray(q)
+        out = np.empty((sd.shape[0], S, S), np.int64)
+        _lib.check(_lib.lib().hm_body_rec_trace_products(self._h, sd.shape[0], _lib.ptr(sd), int(R), _lib.ptr(q), _lib.ptr(out)),
+                   "hm_body_rec_trace_products")
+        return out
+
     def screenshot(self, saveall=True, basename="screenshot", X=None):
         """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask
         at state X (default: the vertex buffer) and returns the overlay.  Unlike the reference the names carry no

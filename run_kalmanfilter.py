@@ -41,6 +41,9 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      roi_F, roi_Fnp, roi_dff (frames x points), roi_seed_fallback.  With --find-points the disc traces
                      come from the record as well: no second pass over the video.  A video whose record would not fit is
                      said to be so and read out as without --rois.
+    --demix          --rois, and the overlapping cells demixed (hydra_mi.demix.extract: shapes and traces fitted in turn
+                     to the kept video, --demix-iters rounds): demix_shapes (points x 17 x 17), demix_C, demix_dff
+                     (frames x points), demix_change (the relative change of demix_C per round).
     --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
                      (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
                      diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
@@ -54,6 +57,7 @@ import numpy as np
 
 import hydra_mi  # noqa: F401
 from hydra_mi import kalman
+from hydra_mi import demix
 from hydra_mi import roi
 from hydra_mi.body import (BodyReadout, read_out, read_out_recorded, read_points_csv, record_bytes, write_points_csv,
                            write_points_txt)
@@ -91,6 +95,8 @@ def main(argv=None):
     parser.add_argument("--rois-max-gb", default=8.0, type=float, help="device memory the kept registered video may take (GiB)")
     parser.add_argument("--roi-thr", default=None, type=float, help="footprint threshold of an ROI (default %g)" % roi.DEFAULT_THR)
     parser.add_argument("--roi-alpha", default=0.7, type=float, help="share of the ring trace taken off the ROI trace")
+    parser.add_argument("--demix", action="store_true", help="--rois, and overlapping cells demixed (demix_* arrays)")
+    parser.add_argument("--demix-iters", default=6, type=int, help="rounds of shapes given traces, traces given shapes")
     parser.add_argument("--smooth", action="store_true", help="smooth the track backward: Xs, Xs_std in the states file")
     parser.add_argument("--smooth-max-gb", default=8.0, type=float, help="device memory the smoother may take (GiB)")
     args = parser.parse_args(argv)
@@ -101,6 +107,10 @@ def main(argv=None):
             parser.error("--find-points needs N >= 1 and a --find-radius in 1..16")
     elif args.points_out is not None:
         parser.error("--points-out goes with --find-points")
+    if args.demix:
+        args.rois = True
+        if args.demix_iters < 1:
+            parser.error("--demix-iters needs at least one round")
     if args.rois and args.find_points is None and args.points is None:
         parser.error("--rois reads cells out: it needs --find-points or --points")
     if len(sys.argv) == 1 and argv is None:
@@ -227,7 +237,14 @@ def main(argv=None):
         pts = found if find else points
         inside = np.flatnonzero(body.locate(pts)[0] >= 0)
         if len(inside) and len(states):
-            e = roi.extract(body, pts[inside], r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
+            if args.demix:
+                e = demix.extract(body, pts[inside], iters=args.demix_iters, r_disc=args.point_radius, thr=args.roi_thr,
+                                  alpha=args.roi_alpha)
+                extra.update(demix_shapes=e["shapes"], demix_C=e["C"], demix_dff=e["dff_demixed"],
+                             demix_change=e["demix_change"])
+                print("Demixed: %d cells, %d rounds, last change %.3g" % (len(inside), args.demix_iters, e["demix_change"][-1]))
+            else:
+                e = roi.extract(body, pts[inside], r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
             extra.update(roi_points=inside, roi_footprints=e["footprints"], roi_labels=e["roi_labels"],
                          roi_counts=e["roi_counts"], roi_ring_counts=e["ring_counts"], roi_F=e["F_roi"], roi_Fnp=e["F_np"],
                          roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
