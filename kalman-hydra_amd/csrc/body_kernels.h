@@ -10,7 +10,7 @@
 // texels clamped to the frame, rint half to even; 0 outside the map or for a position that is not finite or beyond
 // +-2^20 px.  tests/body_ref.py restates all of it in NumPy.
 #pragma once
-#include "ekf_kernels.h"
+#include "hm_types.h"
 #include "view_kernels.h"
 
 // Sums of val over the lanes of a wave by key, NK keys per lane (-1: none), one integer atomic per distinct key: the
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void k_body_warp(BodyWarpArgs a)
 //   p + d is off the frame or outside the map), vmax = max v(p).
 // Pixels outside the map are registered as 0 (k_body_warp), so a product with one is 0 without a look at the map, and
 // their own sums stay 0.  At most BODY_STATS_CAP frames: 65536 * 255^2 < 2^32, every sum is an exact uint32.
-#define BODY_STATS_CAP 65536
+// (BODY_STATS_CAP: hm_types.h)
 
 struct BodyStats {
     unsigned *s1, *s2, *cross;         // n, n, 4 planes of n values `stride` apart; every plane 16-byte aligned

@@ -1,0 +1,389 @@
+// The filter handle of libhydra_mi.so (hm_ctx) and the helpers every translation unit that works on one needs.  Private to
+// the library: ekf.hip (the filter, the smoother) and readout.hip (views, body-frame readout, record) include it, both built
+// by the one compiler command of the Makefile.  Everything defined here is static or a template; the two launchers at the
+// end are defined once, in ekf.hip.
+#pragma once
+#include "hm_common.h"
+#include "hm_types.h"
+#include <chrono>
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+// A persistent helper thread of a handle: it queues launches the calling thread does not have to wait for (the tail of
+// hm_update_run: ~20 launches, ~80 us of host time at a frame boundary, where the caller's way to the NEXT frame's first
+// launches is what the device ends up waiting for).  One job at a time; every entry point joins it first (ctx_join).
+struct Helper {
+    std::thread th;
+    std::mutex m;
+    std::condition_variable cv;
+    std::function<int()> job;
+    bool posted = false, busy = false, quit = false;
+    int rc = HM_OK;
+    char err[512] = "";
+    void run()
+    {
+        std::unique_lock<std::mutex> lk(m);
+        for (;;) {
+            cv.wait(lk, [&] { return quit || posted; });
+            if (quit) return;
+            posted = false;
+            std::function<int()> f = std::move(job);
+            lk.unlock();
+            const int r = f();
+            if (r != HM_OK) snprintf(err, sizeof err, "%s", hm_last_error());
+            lk.lock();
+            rc = r;
+            busy = false;
+            cv.notify_all();
+        }
+    }
+    void post(std::function<int()> f)
+    {
+        std::unique_lock<std::mutex> lk(m);
+        if (!th.joinable()) th = std::thread([this] { run(); });
+        job = std::move(f);
+        posted = busy = true;
+        cv.notify_all();
+    }
+    // waits for the job in flight; its return code (reported once)
+    int wait()
+    {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return !busy; });
+        const int r = rc;
+        rc = HM_OK;
+        return r;
+    }
+    void stop()
+    {
+        {
+            std::unique_lock<std::mutex> lk(m);
+            cv.wait(lk, [&] { return !busy; });
+            quit = true;
+            cv.notify_all();
+        }
+        if (th.joinable()) th.join();
+    }
+};
+
+// What hm_update_arm_newton / _arm_cov / _arm_mask arm, for the next hm_update_run only: that call takes the whole value out
+// of the handle before anything can fail, so an error return never leaves a worker pointer or a mask address behind for a
+// later call to start a job on.
+struct Armed {
+    bool newton = false;             // start the state prediction on `worker` when the state is final ...
+    void *worker = nullptr;
+    bool cov = false;                // ... and queue the covariance half of the next frame's prediction (with newton only)
+    const uint8_t *mask = nullptr;   // queue this mask's outline when the state is final
+};
+
+// hm_view / hm_view_dev / hm_view_forces: targets of their own, allocated on first use -- a view touches nothing the
+// filter reads (its render, triangle setups, state copy and wireframe counts are all here)
+struct ViewState {
+    Targets targets = {nullptr, nullptr, nullptr, nullptr};
+    TriSetup *setup = nullptr;
+    int *ids = nullptr, *lab = nullptr;
+    unsigned *wire = nullptr, *mm = nullptr;
+    double *X = nullptr, *force = nullptr;
+    uint8_t *out = nullptr;
+    hipEvent_t ev = nullptr;
+};
+
+// hm_body_*: the body-frame readout (body_kernels.h), buffers of its own allocated on first use -- it reads the state
+// it is given and nothing else of the filter's
+struct BodyState {
+    bool ready = false;              // the body map and its counts are there
+    TriSetup *setup = nullptr;
+    double *uvX = nullptr, *X = nullptr;
+    int *tri = nullptr;              // triangle per pixel (W*H), -1: none
+    double2 *bary = nullptr;         // l1, l2 per pixel
+    int4 *tidx = nullptr;            // vertex ids per triangle after the orientation swap
+    unsigned *tcnt = nullptr;        // pixels per triangle
+    std::vector<uint32_t> h_tcnt;
+    std::vector<int> h_tri;          // the body map on the host (the record's box, and the pixel counts of discs and rings)
+    int *lab = nullptr;              // the label image (W*H) of hm_body_set_labels; L labels, 0: none set
+    int L = 0;
+    unsigned *lcnt = nullptr;        // pixels per label
+    uint8_t *frame = nullptr, *out = nullptr;           // hm_body_warp's frame and output (W*H, 3 W*H)
+    unsigned long long *sum = nullptr;                  // hm_body_warp's sums: T per triangle, then L per label
+    hipEvent_t ev = nullptr;         // recorded behind every queued warp (hm_body_warp_dev, hm_body_fence)
+    // hm_body_stats_*: sums of the registered video over the warps queued between begin and end
+    bool stats_on = false;
+    int stats_frames = 0;            // frames added since hm_body_stats_begin
+    int stats_cap = BODY_STATS_CAP;  // hm_ctx_tune "body_stats_cap" (tests lower it)
+    uint8_t *reg = nullptr;          // the registered plane (W*H) every warp writes while the statistics or the record are on
+    unsigned *stsum = nullptr;       // s1, s2, cross[4]: 6 planes of W*H, body_stats_stride values apart
+    uint8_t *stmax = nullptr;        // W*H
+    double *stimg = nullptr;         // mean, std, corr: 3 planes of W*H (hm_body_stats_images / _peaks)
+    int *pkidx = nullptr, *pkcnt = nullptr;             // hm_body_stats_peaks: raster indices (W*H), their number
+    double *pkscore = nullptr;
+};
+
+// hm_body_rec_*: the registered video of the warps queued between begin and end, kept on the device (roi_kernels.h)
+struct RecState {
+    bool on = false;
+    int frames = 0;                  // frames appended since hm_body_rec_begin
+    int cap = 0;                     // frames the budget of hm_body_rec_begin holds
+    int chunk = 0;                   // hm_ctx_tune "body_rec_chunk": frames per chunk (0: REC_CHUNK_BYTES worth; tests lower it)
+    int tp_frames = 32;              // hm_ctx_tune "rec_tp_frames": frames per workgroup of hm_body_rec_trace_products
+    unsigned long long max = 0;      // the budget in bytes
+    RecBox box = {0, 0, 0, 0, 0, 0, 0};
+    std::vector<uint8_t *> chunks;
+    uint8_t **tab = nullptr;         // the chunks' addresses for the reductions
+    uint8_t *tmp = nullptr;          // their arguments and results
+};
+
+struct hm_ctx {
+    int device, W, H, N, T, E, njobs;
+    HmOwner own{1};                  // every buffer, stream and event below (HYDRA_MI_POISON class 1)
+    Helper helper;
+    bool helper_used = false;
+    int tail_async = 1;              // hm_ctx_tune "tail_async": the tail of hm_update_run queued by the helper thread (same results)
+    double eps_Z, eps_J, eps_M;
+    hipStream_t stream;
+    // mesh
+    int *d_tri, *d_star_off, *d_star_tri, *d_edges;
+    int *d_nb_off = nullptr, *d_nb_u = nullptr, *d_nb_e = nullptr;   // per vertex: neighbours (ascending) and their edge jobs (k_solve_prep)
+    float *d_uv;
+    uint8_t *d_tex;
+    std::vector<int> edges;          // host copy, E*2
+    // observation
+    uint8_t *d_yim, *d_ym;
+    float *d_yfx, *d_yfy, *d_yfxm, *d_yfym;
+    bool obs_owned = true;           // false when set_observation_dev aliases caller memory
+    const uint8_t *o_yim, *o_ym;     // pointers in use (owned or caller's)
+    const float *o_yfx, *o_yfy;
+    bool have_tex, have_obs, have_ref;
+    // renders
+    Targets ref, P, Q;
+    TriSetup *d_setup, *d_cfgs;
+    int4 *d_ubox;
+    int *d_tlist = nullptr, *d_tcount = nullptr;   // ... and the list / count of the tiles with a non-zero word
+    unsigned *d_tmask = nullptr;     // per vertex and tile of its star region: the star triangles that can reach the tile (k_measure_vertex)
+    double *d_X, *d_out, *d_partial;
+    uint8_t *d_im8, *d_m8;
+    std::vector<double> X0;          // state of the reference render
+    // dense update on the device (n4 = 4N)
+    double *d_HTH;                   // dense HTH of the last measurement: zero outside the J pattern (cleared once;
+                                     // every pattern entry is rewritten by every measurement), used for nothing else
+    double *d_H, *d_Hz, *d_Hzc, *d_invW0, *d_Af[2], *d_T[2], *d_step, *d_Wtmp, *d_X0, *d_Xn, *d_Wprior, *d_gain, *d_Awork, *d_Lt[2];
+    std::vector<double> upd_X0;      // prior mean given to hm_update_begin
+    int upd_last = -1, upd_prev = -1;   // which d_Af holds the factor of the last / previous step (-1: none)
+    double *d_Wres;                  // the covariance resident on the device (the result of the last
+                                     // hm_cov_predict / hm_update_cov / hm_update_run): d_Wtmp, d_H or
+                                     // d_Wprior, or NULL when that buffer has been reused since
+    double *pin;                     // page-locked, device-mapped: hm_update_run's result blocks (host_block.h) -- per iteration
+                                     // [step (n4) | RES_HEAD values], then the tail block [Hzc (n4 x 4) | gains (3 x n4)], every value
+                                     // a pair of words -- and two words of scratch (pin_scratch)
+    size_t pin_n;
+    int *pin_scratch;                // ... where hm_measure / hm_update_step have a flag copied to
+    std::vector<double> resv, tailv; // the host's copies of the two blocks, taken when whole (hb_wait)
+    int result_delay = 0;            // test knob: the result kernels publish a block's last word first, the rest this many us later
+    // the tail block of the last hm_update_run (Hz components, gains): taken by hm_update_tail, or by hm_update_run itself
+    // when its caller wants them at once
+    bool tail_pending = false;
+    // the tail block belongs to the last hm_update_run, which succeeded: false from the entry of every hm_update_run until it
+    // has taken, queued or zero-filled the block (an update that fails leaves nothing for hm_update_tail to hand out)
+    bool tail_valid = false;
+    long long tail_ticket = 0;
+    hipStream_t tail_stream = nullptr;
+    Armed armed;                     // hm_update_arm_*: taken whole by the next hm_update_run
+    std::vector<int> sp_h_off, sp_h_bar, sp_h_other;   // host staging of the spring topology
+    std::vector<double> sp_h_blk;
+    std::vector<int32_t> sp_bars_cached;   // the springs whose topology is on the device (d_sp_off / _bar / _other)
+    std::vector<int> tri;            // host copy of the triangles (orientation test of hm_update_run)
+    DPool pool;                      // parked difference images (see ekf_kernels.h)
+    int *d_area;
+    int *d_sp_off, *d_sp_bar, *d_sp_other;
+    double *d_sp_blk;
+    bool upd_open;
+    bool prefactored;                // d_invW0 is the inverse of the resident covariance d_Wprior (hm_update_prefactor)
+    std::vector<double> h_partial;
+    int red_blocks = 512;
+    double *d_tpart = nullptr;       // per-tile partial sums of Renderer.error from k_render_iter (tiles x 4)
+    std::vector<double> h_tpart;
+    int ntiles = 0;
+    int render_rows = RI_H;          // strip height of k_render_iter (16 or 8)
+    // Renderer.error of the state hm_update_run kept, against the raw flow, from the render of its last iteration
+    // (hm_update_last_error): valid until the observation or anything else on the handle changes
+    bool last_err_valid = false;
+    double last_err[4] = {0, 0, 0, 0};
+    std::vector<double> last_err_X;
+    long long run_ticket;            // sequence number of hm_update_run's per-iteration result blocks
+    int vsplit = 5, esplit;          // workgroups per vertex / per edge job of the measurement (hm_ctx_tune)
+    // hm_update_arm_newton: the springs and parameters of the prediction the next hm_update_run starts (armed.newton);
+    // they stay: the tail on the helper thread reads them
+    std::vector<int32_t> pn_bars;
+    std::vector<double> pn_l0;
+    double pn_par[4] = {0, 0, 0, 0};
+    int pn_maxiter = 0;
+    // hm_update_arm_cov: the covariance half of the next frame's prediction queued by hm_update_run itself (pq = "pre-queued")
+    double pq_eps_F = 0.0;
+    bool pq_valid = false;           // queued and not yet taken: d_Wprior / d_invW0 hold the prediction made from ...
+    std::vector<double> pq_X, pq_l0; // ... this state, these springs and parameters (kappa, a, s, eps_F)
+    std::vector<int32_t> pq_bars;
+    double pq_par[4] = {0, 0, 0, 0};
+    // hm_newton_dev_start / _finish: the state prediction's Newton loop as a four-wave kernel on a stream of its own
+    hipStream_t stream3 = nullptr;
+    int *d_n4nbr = nullptr, *d_n4nbb = nullptr, *d_n4bars = nullptr;
+    double *d_n4l0 = nullptr;
+    int n4deg = 0;                   // padded degree of the table on the device (8 or 12), 0: this mesh does not fit the kernel
+    std::vector<int32_t> n4_bars;    // the springs the table was built for
+    std::vector<double> n4_l0;
+    double *pin_n4 = nullptr;        // page-locked: [X in (4N) | result block of 4N + 2 values (host_block.h): X out, iterations, failed]
+    double *d_n4X = nullptr;         // the same 4N + 2 values in device memory, for hm_chain_project
+    std::vector<double> n4v;         // the host's copy of that block
+    long long n4_ticket = 0;
+    bool n4_pending = false;
+    int newton_fail = 0;             // test knob: the next device predictions report a failed inner solve
+    hipEvent_t ev_n4 = nullptr, ev_pm = nullptr;     // the prediction's kernel / the chained projection have run
+    bool n4_ready = false;           // hm_newton_dev_start's stream, blocks and event are there
+    // hm_chain_project: projectmask of the prediction in flight queued behind it; the projected state (d_X0) is the
+    // prior mean of the next hm_update_run, which also collects what the two kernels report
+    bool chain_pending = false;
+    std::vector<double> chain_pred, chain_proj;     // ... the predicted / the projected state of the last chained update
+    int chain_its = 0, chain_moved = 0;
+    double *pin_blk = nullptr;       // page-locked staging of the spring blocks of that prediction
+    std::thread worker;              // hm_update_prefactor queues its launches from here while the caller predicts the state
+    bool worker_active;
+    int worker_rc;
+    char worker_err[512];
+    // the factorisation as one persistent launch (chol_flow_kernels.h) / its workgroups.  (192 workgroups: 304.9 -> 306.9 us
+    // per iteration with the filter alone, but 260.5 -> 264.2 and 318.6 -> 324.1 frames/s in the two benches -- the
+    // workgroups that poll for blocks take issue slots from the flow's kernels on every compute unit they sit on; 160 and
+    // 128 starve the chain: profiles/r04_ab_tunes.txt)
+    int chol_flow = 1, flow_wgs = 192;
+    int flow_stall = 0;              // test knob: FlowArgs.stall
+    int speculate = 1;               // hm_update_run queues the next iteration's measurement before it knows that there is one
+    double *d_flowP;                 // 3 x nb x 32 x 32 scratch of that launch
+    unsigned *d_flowctl;             // its task counter and time-out word
+    hipStream_t stream2;             // hm_ms_predict: the state prediction runs beside the covariance half of the update
+    // The tail of hm_update_run -- covariance of the kept state, gains, their result block, and the covariance half of the
+    // NEXT frame's prediction (queue_predict_ahead) -- runs on a stream of its own: beside the measurement hm_update_run
+    // queued for an iteration that did not happen, and beside the next frame's reference render and measurement, which
+    // need none of its buffers.  tail_on_stream4: it may still be running; `stream` waits for ev_tail (on the device)
+    // before anything there touches the dense buffers (ctx_join; hm_update_run itself only before its first solve).
+    hipStream_t stream4 = nullptr;
+    hipEvent_t ev_tail = nullptr;
+    bool tail_on_stream4 = false;
+    int tail_split = 1;              // hm_ctx_tune "tail_split": 0 keeps the tail on `stream` (same results either way)
+    int *d_nbars, *d_nvoff, *d_nvbar, *d_ninfo;     // its spring topology (bars, CSR of the bars of every vertex), result words
+    double *d_nl0, *d_nX;
+    bool newton_ready = false;       // hm_ms_predict's buffers are there and k_ms_newton may take its LDS
+    int *d_ids[3];                   // hm_jz_multi / hm_j_multi: id images of the reference and the two perturbed renders,
+    int *d_labels;                   // the label palette (T), per-label boxes and sums; allocated on first use
+    int4 *d_lbox;
+    double *d_lout;
+    std::vector<double> h_lout;
+    int2 *d_outline;                 // hm_project_mask: outline pixels (W*H), counters, uploaded mask; allocated on first use
+    int *d_outline_cnt;
+    uint8_t *d_pm_mask;
+    uint8_t *d_pm_flag = nullptr;    // border-pixel flags of that mask (W*H)
+    uint8_t *d_pm_pruned = nullptr;  // the mask after the reference's contour pruning (k_ccl_*): what the outline and the walk use
+    Ccl ccl = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};     // its working arrays
+    double *d_pm_X = nullptr;        // hm_project_mask's copy of the state (second stream)
+    double *pin_pm = nullptr;        // page-locked: [X in (4N) | result block of 4N + 1 values: projected X, vertices moved] (k_project_mask_host)
+    std::vector<double> pmv;         // the host's copy of that block
+    int *d_pm_done = nullptr;        // workgroups of k_project_mask_host that have finished
+    long long pm_ticket = 0;
+    bool pm_ready = false;           // project_buffers has built all of the above
+    bool outline_ready = false;      // the outline of the resident mask (o_ym) has been queued on the second stream
+    const uint8_t *prepared_mask = nullptr;   // hm_prepare_mask: the outline in the buffers is that of this mask (device memory)
+    hipEvent_t ev_outline = nullptr; // ... recorded behind every outline queued on the second stream
+    hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)
+    // The readout: views, the body-frame readout with its statistics, the kept record.  Each has buffers of its own, allocated
+    // on first use through `own`, and touches nothing the filter reads (readout.hip has the code and names no other field
+    // of the handle than W, H, N, T, device, own, stream, d_tri, d_uv, d_tex and, for the overlay, have_tex, have_obs, o_yim).
+    ViewState view;
+    BodyState body;
+    RecState rec;
+};
+
+static hipError_t alloc_targets(HmOwner &own, Targets &t, size_t n)
+{
+    hipError_t e = own.alloc(&t.acc, n * sizeof(int));
+    if (e == hipSuccess) e = own.alloc(&t.fx, n * sizeof(float));
+    if (e == hipSuccess) e = own.alloc(&t.fy, n * sizeof(float));
+    if (e == hipSuccess) e = own.alloc(&t.cnt, n * sizeof(int));
+    return e;
+}
+
+// the launches the helper thread is still queueing (the tail of the last update), and their failure, if any
+static int helper_join(hm_ctx *h)
+{
+    if (h->helper_used) {
+        const int rc = h->helper.wait();
+        if (rc != HM_OK) { hm_set_error("%s", h->helper.err); return rc; }
+    }
+    return HM_OK;
+}
+// Every entry point waits for the launches hm_update_prefactor is still queueing (one handle = one
+// stream = one thread at a time, as far as the device can tell) and reports their failure, if any.
+static int ctx_join(hm_ctx *h, bool lazy = false)
+{
+    if (!h) return HM_OK;
+    if (const int rc = helper_join(h)) return rc;
+    if (!lazy && h->tail_on_stream4) {
+        h->tail_on_stream4 = false;
+        if (hipSetDevice(h->device) != hipSuccess || hipStreamWaitEvent(h->stream, h->ev_tail, 0) != hipSuccess) {
+            hm_set_error("the handle's stream cannot wait for the tail of the last update");
+            return HM_ERR_HIP;
+        }
+    }
+    if (h->worker_active) {
+        h->worker.join();
+        h->worker_active = false;
+        if (h->worker_rc != HM_OK) {
+            const int rc = h->worker_rc;
+            h->worker_rc = HM_OK;
+            h->prefactored = false;
+            hm_set_error("%s", h->worker_err);
+            return rc;
+        }
+    }
+    return HM_OK;
+}
+#define HM_JOIN(h) do { int _j = ctx_join(h); if (_j) return _j; } while (0)
+// entry points of the frame loop that touch none of the tail's buffers (or wait for it themselves, where they do)
+#define HM_JOIN_LAZY(h) do { int _j = ctx_join(h, true); if (_j) return _j; } while (0)
+
+// Wait for the stream: poll it for a while (a few microseconds of latency) before falling back on
+// hipStreamSynchronize, whose wake-up costs ~20 us -- three of those per frame on the compute() path.
+// (A short pure spin, then the core is offered to other threads between polls: with several trackers
+// per GPU plus their flow and prefactor helper threads on a CPU-quota'd host the pollers must not take
+// the cores away from the threads that queue the launches.)
+static inline hipError_t stream_wait(hipStream_t s)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const auto t_yield = t0 + std::chrono::microseconds(50), t_give_up = t0 + std::chrono::milliseconds(20);
+    bool polite = false;
+    for (int spin = 0;; spin++) {
+        const hipError_t e = hipStreamQuery(s);
+        if (e != hipErrorNotReady) return e;
+        if (polite) std::this_thread::yield();
+        else __builtin_ia32_pause();
+        if ((spin & 15) == 15) {
+            const auto now = std::chrono::steady_clock::now();
+            if (now > t_give_up) return hipStreamSynchronize(s);
+            polite = now > t_yield;
+        }
+    }
+}
+
+template <typename T>
+static int upload(HmOwner &own, T **dst, const T *src, size_t n)
+{
+    HM_HIP(own.alloc(dst, (n ? n : 1) * sizeof(T)));
+    if (n) HM_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return HM_OK;
+}
+
+// The filter's kernels that the readout launches (a view renders, the body map is a setup at X = uv).  Kernels are compiled
+// by one translation unit each (ekf_kernels.h: ekf.hip), so readout.hip queues them through these, defined in ekf.hip:
+// k_setup_all on T triangles of m at state X, and the full-frame render k_render<0> -- or k_render<1> with the label
+// palette when ids is given -- on stream st.  Internal to the library: not in include/hydra_mi.h.
+__attribute__((visibility("hidden"))) void ekf_queue_setup_all(hipStream_t st, const Mesh &m, const double *d_X, TriSetup *d_setup);
+__attribute__((visibility("hidden"))) void ekf_queue_render(hipStream_t st, const Mesh &m, const double *d_X, const TriSetup *d_setup,
+                                                            const Targets &out, const int *d_labels, int *d_ids);

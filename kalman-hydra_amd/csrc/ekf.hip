@@ -1,365 +1,24 @@
 // EKF measurement model on MI355X: host orchestration and C-ABI (include/hydra_mi.h).
 // Replaces reference renderer.py (OpenGL rasteriser), cuda.py and cuda_multi.py
 // (reduction kernels + PBO plumbing).
-#include "hm_common.h"
+#include "ctx.h"
 #include "ekf_kernels.h"
 #include "dense_kernels.h"
 #include "chol_flow_kernels.h"
 #include "project_kernels.h"
 #include "predict_kernels.h"
-#include "view_kernels.h"
-#include "body_kernels.h"
-#include "roi_kernels.h"
 #include "smooth_kernels.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstring>
-#include <functional>
-#include <mutex>
 #include <set>
 #include <thread>
 #include <utility>
 #include <vector>
 
-// A persistent helper thread of a handle: it queues launches the calling thread does not have to wait for (the tail of
-// hm_update_run: ~20 launches, ~80 us of host time at a frame boundary, where the caller's way to the NEXT frame's first
-// launches is what the device ends up waiting for).  One job at a time; every entry point joins it first (ctx_join).
-struct Helper {
-    std::thread th;
-    std::mutex m;
-    std::condition_variable cv;
-    std::function<int()> job;
-    bool posted = false, busy = false, quit = false;
-    int rc = HM_OK;
-    char err[512] = "";
-    void run()
-    {
-        std::unique_lock<std::mutex> lk(m);
-        for (;;) {
-            cv.wait(lk, [&] { return quit || posted; });
-            if (quit) return;
-            posted = false;
-            std::function<int()> f = std::move(job);
-            lk.unlock();
-            const int r = f();
-            if (r != HM_OK) snprintf(err, sizeof err, "%s", hm_last_error());
-            lk.lock();
-            rc = r;
-            busy = false;
-            cv.notify_all();
-        }
-    }
-    void post(std::function<int()> f)
-    {
-        std::unique_lock<std::mutex> lk(m);
-        if (!th.joinable()) th = std::thread([this] { run(); });
-        job = std::move(f);
-        posted = busy = true;
-        cv.notify_all();
-    }
-    // waits for the job in flight; its return code (reported once)
-    int wait()
-    {
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return !busy; });
-        const int r = rc;
-        rc = HM_OK;
-        return r;
-    }
-    void stop()
-    {
-        {
-            std::unique_lock<std::mutex> lk(m);
-            cv.wait(lk, [&] { return !busy; });
-            quit = true;
-            cv.notify_all();
-        }
-        if (th.joinable()) th.join();
-    }
-};
-
-struct hm_ctx {
-    int device, W, H, N, T, E, njobs;
-    HmOwner own{1};                  // every buffer, stream and event below (HYDRA_MI_POISON class 1)
-    Helper helper;
-    bool helper_used = false;
-    int tail_async = 1;              // hm_ctx_tune "tail_async": the tail of hm_update_run queued by the helper thread (same results)
-    double eps_Z, eps_J, eps_M;
-    hipStream_t stream;
-    // mesh
-    int *d_tri, *d_star_off, *d_star_tri, *d_edges;
-    int *d_nb_off = nullptr, *d_nb_u = nullptr, *d_nb_e = nullptr;   // per vertex: neighbours (ascending) and their edge jobs (k_solve_prep)
-    float *d_uv;
-    uint8_t *d_tex;
-    std::vector<int> edges;          // host copy, E*2
-    // observation
-    uint8_t *d_yim, *d_ym;
-    float *d_yfx, *d_yfy, *d_yfxm, *d_yfym;
-    bool obs_owned = true;           // false when set_observation_dev aliases caller memory
-    const uint8_t *o_yim, *o_ym;     // pointers in use (owned or caller's)
-    const float *o_yfx, *o_yfy;
-    bool have_tex, have_obs, have_ref;
-    // renders
-    Targets ref, P, Q;
-    TriSetup *d_setup, *d_cfgs;
-    int4 *d_ubox;
-    int *d_tlist = nullptr, *d_tcount = nullptr;   // ... and the list / count of the tiles with a non-zero word
-    unsigned *d_tmask = nullptr;     // per vertex and tile of its star region: the star triangles that can reach the tile (k_measure_vertex)
-    double *d_X, *d_out, *d_partial;
-    uint8_t *d_im8, *d_m8;
-    std::vector<double> X0;          // state of the reference render
-    // dense update on the device (n4 = 4N)
-    double *d_HTH;                   // dense HTH of the last measurement: zero outside the J pattern (cleared once;
-                                     // every pattern entry is rewritten by every measurement), used for nothing else
-    double *d_H, *d_Hz, *d_Hzc, *d_invW0, *d_Af[2], *d_T[2], *d_step, *d_Wtmp, *d_X0, *d_Xn, *d_Wprior, *d_gain, *d_Awork, *d_Lt[2];
-    std::vector<double> upd_X0;      // prior mean given to hm_update_begin
-    int upd_last = -1, upd_prev = -1;   // which d_Af holds the factor of the last / previous step (-1: none)
-    double *d_Wres;                  // the covariance resident on the device (the result of the last
-                                     // hm_cov_predict / hm_update_cov / hm_update_run): d_Wtmp, d_H or
-                                     // d_Wprior, or NULL when that buffer has been reused since
-    double *pin;                     // page-locked, device-mapped: hm_update_run's result blocks (host_block.h) -- per iteration
-                                     // [step (n4) | RES_HEAD values], then the tail block [Hzc (n4 x 4) | gains (3 x n4)], every value
-                                     // a pair of words -- and two words of scratch (pin_scratch)
-    size_t pin_n;
-    int *pin_scratch;                // ... where hm_measure / hm_update_step have a flag copied to
-    std::vector<double> resv, tailv; // the host's copies of the two blocks, taken when whole (hb_wait)
-    int result_delay = 0;            // test knob: the result kernels publish a block's last word first, the rest this many us later
-    // the tail block of the last hm_update_run (Hz components, gains): taken by hm_update_tail, or by hm_update_run itself
-    // when its caller wants them at once
-    bool tail_pending = false;
-    // the tail block belongs to the last hm_update_run, which succeeded: false from the entry of every hm_update_run until it
-    // has taken, queued or zero-filled the block (an update that fails leaves nothing for hm_update_tail to hand out)
-    bool tail_valid = false;
-    long long tail_ticket = 0;
-    hipStream_t tail_stream = nullptr;
-    const uint8_t *armed_mask = nullptr;     // hm_update_arm_mask: the next hm_update_run queues this mask's outline when its state is final
-    std::vector<int> sp_h_off, sp_h_bar, sp_h_other;   // host staging of the spring topology
-    std::vector<double> sp_h_blk;
-    std::vector<int32_t> sp_bars_cached;   // the springs whose topology is on the device (d_sp_off / _bar / _other)
-    std::vector<int> tri;            // host copy of the triangles (orientation test of hm_update_run)
-    DPool pool;                      // parked difference images (see ekf_kernels.h)
-    int *d_area;
-    int *d_sp_off, *d_sp_bar, *d_sp_other;
-    double *d_sp_blk;
-    bool upd_open;
-    bool prefactored;                // d_invW0 is the inverse of the resident covariance d_Wprior (hm_update_prefactor)
-    std::vector<double> h_partial;
-    int red_blocks = 512;
-    double *d_tpart = nullptr;       // per-tile partial sums of Renderer.error from k_render_iter (tiles x 4)
-    std::vector<double> h_tpart;
-    int ntiles = 0;
-    int render_rows = RI_H;          // strip height of k_render_iter (16 or 8)
-    // Renderer.error of the state hm_update_run kept, against the raw flow, from the render of its last iteration
-    // (hm_update_last_error): valid until the observation or anything else on the handle changes
-    bool last_err_valid = false;
-    double last_err[4] = {0, 0, 0, 0};
-    std::vector<double> last_err_X;
-    long long run_ticket;            // sequence number of hm_update_run's per-iteration result blocks
-    int vsplit = 5, esplit;          // workgroups per vertex / per edge job of the measurement (hm_ctx_tune)
-    // hm_update_arm_newton: what the next hm_update_run starts when its state is final
-    bool pn_armed = false;
-    void *pn_worker = nullptr;
-    std::vector<int32_t> pn_bars;
-    std::vector<double> pn_l0;
-    double pn_par[4] = {0, 0, 0, 0};
-    int pn_maxiter = 0;
-    // hm_update_arm_cov: the covariance half of the next frame's prediction queued by hm_update_run itself (pq = "pre-queued")
-    bool pq_armed = false;           // the next hm_update_run is asked to queue it
-    double pq_eps_F = 0.0;
-    bool pq_valid = false;           // queued and not yet taken: d_Wprior / d_invW0 hold the prediction made from ...
-    std::vector<double> pq_X, pq_l0; // ... this state, these springs and parameters (kappa, a, s, eps_F)
-    std::vector<int32_t> pq_bars;
-    double pq_par[4] = {0, 0, 0, 0};
-    // hm_newton_dev_start / _finish: the state prediction's Newton loop as a four-wave kernel on a stream of its own
-    hipStream_t stream3 = nullptr;
-    int *d_n4nbr = nullptr, *d_n4nbb = nullptr, *d_n4bars = nullptr;
-    double *d_n4l0 = nullptr;
-    int n4deg = 0;                   // padded degree of the table on the device (8 or 12), 0: this mesh does not fit the kernel
-    std::vector<int32_t> n4_bars;    // the springs the table was built for
-    std::vector<double> n4_l0;
-    double *pin_n4 = nullptr;        // page-locked: [X in (4N) | result block of 4N + 2 values (host_block.h): X out, iterations, failed]
-    double *d_n4X = nullptr;         // the same 4N + 2 values in device memory, for hm_chain_project
-    std::vector<double> n4v;         // the host's copy of that block
-    long long n4_ticket = 0;
-    bool n4_pending = false;
-    int newton_fail = 0;             // test knob: the next device predictions report a failed inner solve
-    hipEvent_t ev_n4 = nullptr, ev_pm = nullptr;     // the prediction's kernel / the chained projection have run
-    bool n4_ready = false;           // hm_newton_dev_start's stream, blocks and event are there
-    // hm_chain_project: projectmask of the prediction in flight queued behind it; the projected state (d_X0) is the
-    // prior mean of the next hm_update_run, which also collects what the two kernels report
-    bool chain_pending = false;
-    std::vector<double> chain_pred, chain_proj;     // ... the predicted / the projected state of the last chained update
-    int chain_its = 0, chain_moved = 0;
-    double *pin_blk = nullptr;       // page-locked staging of the spring blocks of that prediction
-    std::thread worker;              // hm_update_prefactor queues its launches from here while the caller predicts the state
-    bool worker_active;
-    int worker_rc;
-    char worker_err[512];
-    // the factorisation as one persistent launch (chol_flow_kernels.h) / its workgroups.  (192 workgroups: 304.9 -> 306.9 us
-    // per iteration with the filter alone, but 260.5 -> 264.2 and 318.6 -> 324.1 frames/s in the two benches -- the
-    // workgroups that poll for blocks take issue slots from the flow's kernels on every compute unit they sit on; 160 and
-    // 128 starve the chain: profiles/r04_ab_tunes.txt)
-    int chol_flow = 1, flow_wgs = 192;
-    int flow_stall = 0;              // test knob: FlowArgs.stall
-    int speculate = 1;               // hm_update_run queues the next iteration's measurement before it knows that there is one
-    double *d_flowP;                 // 3 x nb x 32 x 32 scratch of that launch
-    unsigned *d_flowctl;             // its task counter and time-out word
-    hipStream_t stream2;             // hm_ms_predict: the state prediction runs beside the covariance half of the update
-    // The tail of hm_update_run -- covariance of the kept state, gains, their result block, and the covariance half of the
-    // NEXT frame's prediction (queue_predict_ahead) -- runs on a stream of its own: beside the measurement hm_update_run
-    // queued for an iteration that did not happen, and beside the next frame's reference render and measurement, which
-    // need none of its buffers.  tail_on_stream4: it may still be running; `stream` waits for ev_tail (on the device)
-    // before anything there touches the dense buffers (ctx_join; hm_update_run itself only before its first solve).
-    hipStream_t stream4 = nullptr;
-    hipEvent_t ev_tail = nullptr;
-    bool tail_on_stream4 = false;
-    int tail_split = 1;              // hm_ctx_tune "tail_split": 0 keeps the tail on `stream` (same results either way)
-    int *d_nbars, *d_nvoff, *d_nvbar, *d_ninfo;     // its spring topology (bars, CSR of the bars of every vertex), result words
-    double *d_nl0, *d_nX;
-    bool newton_ready = false;       // hm_ms_predict's buffers are there and k_ms_newton may take its LDS
-    int *d_ids[3];                   // hm_jz_multi / hm_j_multi: id images of the reference and the two perturbed renders,
-    int *d_labels;                   // the label palette (T), per-label boxes and sums; allocated on first use
-    int4 *d_lbox;
-    double *d_lout;
-    std::vector<double> h_lout;
-    int2 *d_outline;                 // hm_project_mask: outline pixels (W*H), counters, uploaded mask; allocated on first use
-    int *d_outline_cnt;
-    uint8_t *d_pm_mask;
-    uint8_t *d_pm_flag = nullptr;    // border-pixel flags of that mask (W*H)
-    uint8_t *d_pm_pruned = nullptr;  // the mask after the reference's contour pruning (k_ccl_*): what the outline and the walk use
-    Ccl ccl = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};     // its working arrays
-    double *d_pm_X = nullptr;        // hm_project_mask's copy of the state (second stream)
-    double *pin_pm = nullptr;        // page-locked: [X in (4N) | result block of 4N + 1 values: projected X, vertices moved] (k_project_mask_host)
-    std::vector<double> pmv;         // the host's copy of that block
-    int *d_pm_done = nullptr;        // workgroups of k_project_mask_host that have finished
-    long long pm_ticket = 0;
-    bool pm_ready = false;           // project_buffers has built all of the above
-    bool outline_ready = false;      // the outline of the resident mask (o_ym) has been queued on the second stream
-    const uint8_t *prepared_mask = nullptr;   // hm_prepare_mask: the outline in the buffers is that of this mask (device memory)
-    hipEvent_t ev_outline = nullptr; // ... recorded behind every outline queued on the second stream
-    hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)
-    // hm_view / hm_view_dev / hm_view_forces: targets of their own, allocated on first use -- a view touches nothing the
-    // filter reads (its render, triangle setups, state copy and wireframe counts are all here)
-    Targets V = {nullptr, nullptr, nullptr, nullptr};
-    TriSetup *d_vsetup = nullptr;
-    int *d_vids = nullptr, *d_vlab = nullptr;
-    unsigned *d_vwire = nullptr, *d_vmm = nullptr;
-    double *d_vX = nullptr, *d_vforce = nullptr;
-    uint8_t *d_vout = nullptr;
-    hipEvent_t ev_view = nullptr;
-    // hm_body_*: the body-frame readout (body_kernels.h), buffers of its own allocated on first use -- it reads the state
-    // it is given and nothing else of the filter's
-    bool body_ready = false;         // the body map and its counts are there
-    TriSetup *d_bsetup = nullptr;
-    double *d_buvX = nullptr, *d_bX = nullptr;
-    int *d_btri = nullptr;           // triangle per pixel (W*H), -1: none
-    double2 *d_bbary = nullptr;      // l1, l2 per pixel
-    int4 *d_btidx = nullptr;         // vertex ids per triangle after the orientation swap
-    unsigned *d_btcnt = nullptr;     // pixels per triangle
-    std::vector<uint32_t> h_btcnt;
-    int *d_blab = nullptr;           // the label image (W*H) of hm_body_set_labels; body_L labels, 0: none set
-    int body_L = 0;
-    unsigned *d_blcnt = nullptr;     // pixels per label
-    uint8_t *d_bframe = nullptr, *d_bout = nullptr;     // hm_body_warp's frame and output (W*H, 3 W*H)
-    unsigned long long *d_bsum = nullptr;               // hm_body_warp's sums: T per triangle, then body_L per label
-    hipEvent_t ev_body = nullptr;    // recorded behind every queued warp (hm_body_warp_dev, hm_body_fence)
-    // hm_body_stats_*: sums of the registered video over the warps queued between begin and end
-    bool stats_on = false;
-    int stats_frames = 0;            // frames added since hm_body_stats_begin
-    int stats_cap = BODY_STATS_CAP;  // hm_ctx_tune "body_stats_cap" (tests lower it)
-    uint8_t *d_breg = nullptr;       // the registered plane (W*H) every warp writes while the statistics are on
-    unsigned *d_stsum = nullptr;     // s1, s2, cross[4]: 6 planes of W*H, body_stats_stride values apart
-    uint8_t *d_stmax = nullptr;      // W*H
-    double *d_stimg = nullptr;       // mean, std, corr: 3 planes of W*H (hm_body_stats_images / _peaks)
-    int *d_pkidx = nullptr, *d_pkcnt = nullptr;     // hm_body_stats_peaks: raster indices (W*H), their number
-    double *d_pkscore = nullptr;
-    // hm_body_rec_*: the registered video of the warps queued between begin and end, kept on the device (roi_kernels.h)
-    bool rec_on = false;
-    int rec_frames = 0;              // frames appended since hm_body_rec_begin
-    int rec_cap = 0;                 // frames the budget of hm_body_rec_begin holds
-    int rec_chunk = 0;               // hm_ctx_tune "body_rec_chunk": frames per chunk (0: REC_CHUNK_BYTES worth; tests lower it)
-    int rec_tp_frames = 32;          // hm_ctx_tune "rec_tp_frames": frames per workgroup of hm_body_rec_trace_products
-    unsigned long long rec_max = 0;  // the budget in bytes
-    RecBox rec_box = {0, 0, 0, 0, 0, 0, 0};
-    std::vector<uint8_t *> rec_chunks;
-    std::vector<int> h_btri;         // the body map on the host (the box, and the pixel counts of discs and rings)
-    uint8_t **d_rec_tab = nullptr;   // the chunks' addresses for the reductions
-    uint8_t *d_rec_tmp = nullptr;    // their arguments and results
-};
-
-static hipError_t alloc_targets(HmOwner &own, Targets &t, size_t n)
-{
-    hipError_t e = own.alloc(&t.acc, n * sizeof(int));
-    if (e == hipSuccess) e = own.alloc(&t.fx, n * sizeof(float));
-    if (e == hipSuccess) e = own.alloc(&t.fy, n * sizeof(float));
-    if (e == hipSuccess) e = own.alloc(&t.cnt, n * sizeof(int));
-    return e;
-}
-
-// the launches the helper thread is still queueing (the tail of the last update), and their failure, if any
-static int helper_join(hm_ctx *h)
-{
-    if (h->helper_used) {
-        const int rc = h->helper.wait();
-        if (rc != HM_OK) { hm_set_error("%s", h->helper.err); return rc; }
-    }
-    return HM_OK;
-}
-// Every entry point waits for the launches hm_update_prefactor is still queueing (one handle = one
-// stream = one thread at a time, as far as the device can tell) and reports their failure, if any.
-static int ctx_join(hm_ctx *h, bool lazy = false)
-{
-    if (!h) return HM_OK;
-    if (const int rc = helper_join(h)) return rc;
-    if (!lazy && h->tail_on_stream4) {
-        h->tail_on_stream4 = false;
-        if (hipSetDevice(h->device) != hipSuccess || hipStreamWaitEvent(h->stream, h->ev_tail, 0) != hipSuccess) {
-            hm_set_error("the handle's stream cannot wait for the tail of the last update");
-            return HM_ERR_HIP;
-        }
-    }
-    if (h->worker_active) {
-        h->worker.join();
-        h->worker_active = false;
-        if (h->worker_rc != HM_OK) {
-            const int rc = h->worker_rc;
-            h->worker_rc = HM_OK;
-            h->prefactored = false;
-            hm_set_error("%s", h->worker_err);
-            return rc;
-        }
-    }
-    return HM_OK;
-}
-#define HM_JOIN(h) do { int _j = ctx_join(h); if (_j) return _j; } while (0)
-// entry points of the frame loop that touch none of the tail's buffers (or wait for it themselves, where they do)
-#define HM_JOIN_LAZY(h) do { int _j = ctx_join(h, true); if (_j) return _j; } while (0)
-
-// Wait for the stream: poll it for a while (a few microseconds of latency) before falling back on
-// hipStreamSynchronize, whose wake-up costs ~20 us -- three of those per frame on the compute() path.
-// (A short pure spin, then the core is offered to other threads between polls: with several trackers
-// per GPU plus their flow and prefactor helper threads on a CPU-quota'd host the pollers must not take
-// the cores away from the threads that queue the launches.)
-static hipError_t stream_wait(hipStream_t s)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    const auto t_yield = t0 + std::chrono::microseconds(50), t_give_up = t0 + std::chrono::milliseconds(20);
-    bool polite = false;
-    for (int spin = 0;; spin++) {
-        const hipError_t e = hipStreamQuery(s);
-        if (e != hipErrorNotReady) return e;
-        if (polite) std::this_thread::yield();
-        else __builtin_ia32_pause();
-        if ((spin & 15) == 15) {
-            const auto now = std::chrono::steady_clock::now();
-            if (now > t_give_up) return hipStreamSynchronize(s);
-            polite = now > t_yield;
-        }
-    }
-}
+// (struct hm_ctx, ctx_join / HM_JOIN, stream_wait, upload: ctx.h)
 
 // Take values [first, first + n) of a result block in page-locked host memory (host_block.h) into `out` once every one of
 // their pairs carries the launch's stamp.  The last pair is looked at first (one pair of loads per poll while nothing is
@@ -440,13 +99,6 @@ static int ctx_free(hm_ctx *h)
     return HM_OK;
 }
 
-template <typename T>
-static int upload(HmOwner &own, T **dst, const T *src, size_t n)
-{
-    HM_HIP(own.alloc(dst, (n ? n : 1) * sizeof(T)));
-    if (n) HM_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return HM_OK;
-}
 
 extern "C" int hm_ctx_create(int device, int W, int H, int N, int T, const int32_t *tri, const float *uv, double eps_Z,
                              double eps_J, double eps_M, hm_ctx_t *out)
@@ -608,6 +260,19 @@ extern "C" int hm_ctx_create(int device, int W, int H, int N, int T, const int32
 
 extern "C" int hm_ctx_destroy(hm_ctx_t h) { return ctx_free(h); }
 
+// the launches of the filter's kernels that readout.hip queues (ctx.h)
+void ekf_queue_setup_all(hipStream_t st, const Mesh &m, const double *d_X, TriSetup *d_setup)
+{
+    hipLaunchKernelGGL(k_setup_all, dim3(hm_cdiv(m.T, 64)), dim3(64), 0, st, m, d_X, d_setup);
+}
+void ekf_queue_render(hipStream_t st, const Mesh &m, const double *d_X, const TriSetup *d_setup, const Targets &out,
+                      const int *d_labels, int *d_ids)
+{
+    const dim3 grid(hm_cdiv(m.W, EKF_TILE), hm_cdiv(m.H, EKF_TILE)), block(EKF_TILE, EKF_TILE);
+    if (d_ids) hipLaunchKernelGGL((k_render<1>), grid, block, 0, st, m, d_X, d_setup, out, d_labels, d_ids);
+    else hipLaunchKernelGGL((k_render<0>), grid, block, 0, st, m, d_X, d_setup, out, (const int *)nullptr, (int *)nullptr);
+}
+
 #ifdef HM_STAMP
 // development builds only: where k_render_iter writes its per-workgroup time stamps (device pointer, 8 words per workgroup)
 extern "C" int hm_debug_stamps(void *dev_ptr)
@@ -659,13 +324,13 @@ extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
         h->esplit = value;
     } else if (!strcmp(key, "body_stats_cap")) {       // tests only: frames one hm_body_stats accumulation takes
         HM_ARG(value >= 1 && value <= BODY_STATS_CAP, "hm_ctx_tune: body_stats_cap must be in 1..%d", BODY_STATS_CAP);
-        h->stats_cap = value;
+        h->body.stats_cap = value;
     } else if (!strcmp(key, "body_rec_chunk")) {       // tests only: frames per chunk of the next hm_body_rec_begin
         HM_ARG(value >= 0, "hm_ctx_tune: body_rec_chunk must be >= 0 (0: the default size)");
-        h->rec_chunk = value;
+        h->rec.chunk = value;
     } else if (!strcmp(key, "rec_tp_frames")) {        // frames per workgroup of hm_body_rec_trace_products
         HM_ARG(value >= 1 && value <= REC_TP_MAX, "hm_ctx_tune: rec_tp_frames must be in 1..%d", REC_TP_MAX);
-        h->rec_tp_frames = value;
+        h->rec.tp_frames = value;
     } else {
         hm_set_error("hm_ctx_tune: unknown key '%s'", key);
         return HM_ERR_ARG;
@@ -1577,12 +1242,12 @@ extern "C" int hm_update_arm_newton(hm_ctx_t h, void *worker, int n_bars, const 
 {
     HM_ARG(h && worker && n_bars >= 0 && bars && l0, "hm_update_arm_newton: bad argument");
     HM_JOIN_LAZY(h);                               // (the tail of the last update still reads what this call replaces)
-    h->pn_worker = worker;
+    h->armed.worker = worker;
     h->pn_bars.assign(bars, bars + 2 * (size_t)n_bars);
     h->pn_l0.assign(l0, l0 + n_bars);
     h->pn_par[0] = kappa; h->pn_par[1] = M; h->pn_par[2] = dt; h->pn_par[3] = tol;
     h->pn_maxiter = maxiter;
-    h->pn_armed = true;
+    h->armed.newton = true;
     return HM_OK;
 }
 
@@ -1593,7 +1258,7 @@ extern "C" int hm_update_arm_newton(hm_ctx_t h, void *worker, int n_bars, const 
 extern "C" int hm_update_arm_cov(hm_ctx_t h, double eps_F)
 {
     HM_ARG(h != nullptr, "hm_update_arm_cov: NULL handle");
-    h->pq_armed = true;
+    h->armed.cov = true;
     h->pq_eps_F = eps_F;
     return HM_OK;
 }
@@ -1608,7 +1273,7 @@ static int prepare_mask(hm_ctx *h, const uint8_t *d_y_m);
 extern "C" int hm_update_arm_mask(hm_ctx_t h, const uint8_t *d_y_m)
 {
     HM_ARG(h != nullptr, "hm_update_arm_mask: NULL handle");
-    h->armed_mask = d_y_m;
+    h->armed.mask = d_y_m;
     return HM_OK;
 }
 
@@ -1644,14 +1309,11 @@ extern "C" int hm_update_run(hm_ctx_t h, const double *W_prior, double *X, doubl
     // can fail, so that an error return never leaves a worker pointer or a mask address behind for a later call to start a
     // job on (the helper thread joined below touches none of these fields), and the tail block of the last update stops
     // being handed out
-    const bool pn_go = h->pn_armed;
-    void *const pn_worker = h->pn_worker;
-    h->pn_armed = false;
-    h->pn_worker = nullptr;
-    const bool pq_go = h->pq_armed && pn_go;
-    h->pq_armed = false;
-    const uint8_t *next_mask = h->armed_mask;
-    h->armed_mask = nullptr;
+    const Armed armed = std::exchange(h->armed, {});
+    const bool pn_go = armed.newton;
+    void *const pn_worker = armed.worker;
+    const bool pq_go = armed.cov && pn_go;
+    const uint8_t *next_mask = armed.mask;
     h->tail_valid = false;
     HM_JOIN_LAZY(h);                               // (the tail of the last update: waited for before the first solve below)
     HM_ARG(deltaX > 0 && max_iter >= 0, "hm_update_run: deltaX must be positive, max_iter >= 0");
@@ -2409,863 +2071,6 @@ extern "C" int hm_chain_states(hm_ctx_t h, double *predicted, double *projected,
     if (newton_iterations) *newton_iterations = h->chain_its;
     if (moved) *moved = h->chain_moved;
     return HM_OK;
-}
-
-// ---- views of a context (reference renderer.py:436-475 screenshot, :595-628 draw; kalman.py:638-674 plotforces) ------
-static int view_buffers(hm_ctx *h)
-{
-    const size_t n = (size_t)h->W * h->H;
-    HM_HIP(alloc_targets(h->own, h->V, n));
-    HM_HIP(h->own.alloc(&h->d_vsetup, (size_t)h->T * sizeof(TriSetup)));
-    HM_HIP(h->own.alloc(&h->d_vids, n * sizeof(int)));
-    HM_HIP(h->own.alloc(&h->d_vlab, (size_t)h->T * sizeof(int)));
-    HM_HIP(h->own.alloc(&h->d_vwire, n * sizeof(unsigned)));
-    HM_HIP(h->own.alloc(&h->d_vmm, 2 * sizeof(unsigned)));
-    HM_HIP(h->own.alloc(&h->d_vforce, (size_t)10 * h->N * sizeof(double)));
-    HM_HIP(h->own.alloc(&h->d_vout, 3 * n));
-    HM_HIP(h->own.event(&h->ev_view));
-    HM_HIP(h->own.alloc(&h->d_vX, (size_t)4 * h->N * sizeof(double)));
-    return HM_OK;
-}
-
-// Queue view `which` (VIEW_*) of state X (host) into d_out (device, W*H*3) on the handle's stream.  palette: the mask
-// view's label per triangle (NULL: -1, i.e. (255, 255, 255)).  forces (VIEW_FORCES_BASE): orig | pred | tv | fv | mv,
-// 2N doubles each, host.
-static int view_queue(hm_ctx *h, const double *X, int which, const int32_t *palette, const double *const forces[5],
-                      uint8_t *d_out, const char *who)
-{
-    HM_ARG(h && X && d_out, "%s: NULL argument", who);
-    HM_ARG(which >= VIEW_RAW && which <= VIEW_FORCES_BASE, "%s: view %d outside 0..%d", who, which, VIEW_FLOWY);
-    HM_JOIN_LAZY(h);
-    if (!h->have_tex) { hm_set_error("%s: hm_set_texture has not been called", who); return HM_ERR_STATE; }
-    if ((which == VIEW_OVERLAY || which == VIEW_FORCES_BASE) && !h->have_obs) {
-        hm_set_error("%s: the overlay shows the observed frame, and hm_set_observation has not been called", who);
-        return HM_ERR_STATE;
-    }
-    HM_HIP(hipSetDevice(h->device));
-    int rc = view_buffers(h);
-    if (rc) return rc;
-    const int n = h->W * h->H;
-    HM_HIP(hipMemcpyAsync(h->d_vX, X, (size_t)4 * h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    Mesh m = {h->W, h->H, h->N, h->T, h->d_tri, h->d_uv, h->d_tex};
-    hipLaunchKernelGGL(k_setup_all, dim3(hm_cdiv(h->T, 64)), dim3(64), 0, h->stream, m, (const double *)h->d_vX, h->d_vsetup);
-    const dim3 grid(hm_cdiv(h->W, EKF_TILE), hm_cdiv(h->H, EKF_TILE)), block(EKF_TILE, EKF_TILE);
-    if (which == VIEW_MASK) {
-        if (palette) HM_HIP(hipMemcpyAsync(h->d_vlab, palette, (size_t)h->T * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        else HM_HIP(hipMemsetAsync(h->d_vlab, 0xFF, (size_t)h->T * sizeof(int), h->stream));
-        hipLaunchKernelGGL((k_render<1>), grid, block, 0, h->stream, m, (const double *)h->d_vX, (const TriSetup *)h->d_vsetup,
-                           h->V, (const int *)h->d_vlab, h->d_vids);
-    } else {
-        hipLaunchKernelGGL((k_render<0>), grid, block, 0, h->stream, m, (const double *)h->d_vX, (const TriSetup *)h->d_vsetup,
-                           h->V, (const int *)nullptr, (int *)nullptr);
-    }
-    const bool wire = which == VIEW_TEXTURE || which == VIEW_OVERLAY || which == VIEW_MASK || which == VIEW_FORCES_BASE;
-    if (wire) {
-        HM_HIP(hipMemsetAsync(h->d_vwire, 0, (size_t)n * sizeof(unsigned), h->stream));
-        hipLaunchKernelGGL(k_view_wire, dim3(hm_cdiv(3 * h->T, 256 / VIEW_SEG_WAVE)), dim3(256), 0, h->stream,
-                           (const int *)h->d_tri, h->T, (const double *)h->d_vX, h->W, h->H, h->d_vwire);
-    }
-    ViewArgs a;
-    a.n = n; a.which = which;
-    a.acc = h->V.acc; a.cnt = h->V.cnt; a.ids = h->d_vids;
-    a.flow = which == VIEW_FLOWY ? h->V.fy : h->V.fx;
-    a.mm = h->d_vmm;
-    a.wire = wire ? h->d_vwire : nullptr;
-    a.obs = h->o_yim;
-    a.out = d_out;
-    if (which == VIEW_FLOWX || which == VIEW_FLOWY) {
-        HM_HIP(hipMemsetAsync(h->d_vmm, 0xFF, sizeof(unsigned), h->stream));
-        HM_HIP(hipMemsetAsync(h->d_vmm + 1, 0, sizeof(unsigned), h->stream));
-        hipLaunchKernelGGL(k_view_minmax, dim3(std::min(hm_cdiv(n, 256), 256)), dim3(256), 0, h->stream, a.flow, n, h->d_vmm);
-    }
-    hipLaunchKernelGGL(k_view_compose, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, a);
-    if (which == VIEW_FORCES_BASE) {
-        const size_t n2 = (size_t)2 * h->N;
-        for (int k = 0; k < 5; k++)
-            HM_HIP(hipMemcpyAsync(h->d_vforce + k * n2, forces[k], n2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        const double *o = h->d_vforce, *p = o + n2;
-        const dim3 ag(hm_cdiv(3 * h->N, 256 / VIEW_SEG_WAVE));
-        // reference kalman.py:654-661, in its order: prediction (white), template (blue), flow (green), mask (red) force
-        hipLaunchKernelGGL(k_view_arrows, ag, dim3(256), 0, h->stream, o, p, (const double *)nullptr, 0.0, h->N, h->W, h->H,
-                           make_uchar3(255, 255, 255), d_out);
-        hipLaunchKernelGGL(k_view_arrows, ag, dim3(256), 0, h->stream, p, (const double *)nullptr, (const double *)(p + n2), 10.0,
-                           h->N, h->W, h->H, make_uchar3(255, 0, 0), d_out);
-        hipLaunchKernelGGL(k_view_arrows, ag, dim3(256), 0, h->stream, p, (const double *)nullptr, (const double *)(p + 2 * n2),
-                           10.0, h->N, h->W, h->H, make_uchar3(0, 255, 0), d_out);
-        hipLaunchKernelGGL(k_view_arrows, ag, dim3(256), 0, h->stream, p, (const double *)nullptr, (const double *)(p + 3 * n2),
-                           10.0, h->N, h->W, h->H, make_uchar3(0, 0, 255), d_out);
-    }
-    HM_HIP(hipGetLastError());
-    return HM_OK;
-}
-
-static int view_download(hm_ctx *h, uint8_t *bgr)
-{
-    HM_HIP(hipMemcpyAsync(bgr, h->d_vout, (size_t)3 * h->W * h->H, hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-extern "C" int hm_view(hm_ctx_t h, const double *X, int which, const int32_t *palette, uint8_t *bgr)
-{
-    HM_ARG(h && bgr, "hm_view: NULL argument");
-    HM_ARG(which >= VIEW_RAW && which <= VIEW_FLOWY, "hm_view: view %d outside 0..%d", which, VIEW_FLOWY);
-    HM_JOIN_LAZY(h);                             // (view_buffers may create resources: the helper must not be queueing)
-    HM_HIP(hipSetDevice(h->device));
-    int rc = view_buffers(h);
-    if (rc) return rc;
-    rc = view_queue(h, X, which, palette, nullptr, h->d_vout, "hm_view");
-    if (rc) return rc;
-    return view_download(h, bgr);
-}
-
-extern "C" int hm_view_dev(hm_ctx_t h, const double *X, int which, const int32_t *palette, void *d_bgr, void *stream)
-{
-    HM_ARG(h && d_bgr, "hm_view_dev: NULL argument");
-    HM_ARG(which >= VIEW_RAW && which <= VIEW_FLOWY, "hm_view_dev: view %d outside 0..%d", which, VIEW_FLOWY);
-    int rc = view_queue(h, X, which, palette, nullptr, (uint8_t *)d_bgr, "hm_view_dev");
-    if (rc) return rc;
-    if (stream) {
-        HM_HIP(hipEventRecord(h->ev_view, h->stream));
-        HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_view, 0));
-    }
-    return HM_OK;
-}
-
-extern "C" int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, const double *pred, const double *tv,
-                              const double *fv, const double *mv, uint8_t *bgr)
-{
-    HM_ARG(h && bgr && orig && pred && tv && fv && mv, "hm_view_forces: NULL argument");
-    HM_JOIN_LAZY(h);                             // (view_buffers may create resources: the helper must not be queueing)
-    HM_HIP(hipSetDevice(h->device));
-    int rc = view_buffers(h);
-    if (rc) return rc;
-    const double *f[5] = {orig, pred, tv, fv, mv};
-    rc = view_queue(h, X, VIEW_FORCES_BASE, nullptr, f, h->d_vout, "hm_view_forces");
-    if (rc) return rc;
-    return view_download(h, bgr);
-}
-
-// ---- the body-frame readout (body_kernels.h) --------------------------------------------------------------------
-// The body map at X = uv (k_setup_all, then k_body_map), the pixels per triangle on the host.  Once per handle.
-static int body_map_build(hm_ctx *h)
-{
-    HM_HIP(hipSetDevice(h->device));
-    if (h->body_ready) return HM_OK;
-    const size_t n = (size_t)h->W * h->H;
-    HM_HIP(h->own.alloc(&h->d_bsetup, (size_t)h->T * sizeof(TriSetup)));
-    HM_HIP(h->own.alloc(&h->d_buvX, (size_t)4 * h->N * sizeof(double)));
-    HM_HIP(h->own.alloc(&h->d_bX, (size_t)2 * h->N * sizeof(double)));
-    HM_HIP(h->own.alloc(&h->d_btri, n * sizeof(int)));
-    HM_HIP(h->own.alloc(&h->d_bbary, n * sizeof(double2)));
-    HM_HIP(h->own.alloc(&h->d_btidx, (size_t)h->T * sizeof(int4)));
-    HM_HIP(h->own.alloc(&h->d_btcnt, (size_t)h->T * sizeof(unsigned)));
-    HM_HIP(h->own.alloc(&h->d_bsum, (size_t)(h->T + h->body_L) * sizeof(unsigned long long)));
-    HM_HIP(h->own.event(&h->ev_body));
-    Mesh m = {h->W, h->H, h->N, h->T, h->d_tri, h->d_uv, h->d_tex};
-    hipLaunchKernelGGL(k_body_uvX, dim3(hm_cdiv(4 * h->N, 256)), dim3(256), 0, h->stream, (const float *)h->d_uv, h->N, h->d_buvX);
-    hipLaunchKernelGGL(k_setup_all, dim3(hm_cdiv(h->T, 64)), dim3(64), 0, h->stream, m, (const double *)h->d_buvX, h->d_bsetup);
-    HM_HIP(hipMemsetAsync(h->d_btcnt, 0, (size_t)h->T * sizeof(unsigned), h->stream));
-    hipLaunchKernelGGL(k_body_map, dim3(hm_cdiv(h->W, EKF_TILE), hm_cdiv(h->H, EKF_TILE)), dim3(EKF_TILE, EKF_TILE), 0, h->stream,
-                       h->W, h->H, h->T, (const TriSetup *)h->d_bsetup, h->d_btri, h->d_bbary, h->d_btidx, h->d_btcnt);
-    HM_HIP(hipGetLastError());
-    h->h_btcnt.resize(h->T);
-    HM_HIP(hipMemcpyAsync(h->h_btcnt.data(), h->d_btcnt, (size_t)h->T * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    h->body_ready = true;
-    return HM_OK;
-}
-
-extern "C" int hm_body_map(hm_ctx_t h, int32_t *tri_of_pixel, uint32_t *tri_counts)
-{
-    HM_ARG(h != nullptr, "hm_body_map: NULL handle");
-    HM_JOIN_LAZY(h);                             // (body_map_build creates resources: the helper must not be queueing)
-    int rc = body_map_build(h);
-    if (rc) return rc;
-    if (tri_of_pixel) {
-        HM_HIP(hipMemcpyAsync(tri_of_pixel, h->d_btri, (size_t)h->W * h->H * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HM_HIP(hipStreamSynchronize(h->stream));
-    }
-    if (tri_counts) memcpy(tri_counts, h->h_btcnt.data(), (size_t)h->T * sizeof(uint32_t));
-    return HM_OK;
-}
-
-extern "C" int hm_body_set_labels(hm_ctx_t h, const int32_t *labels, int L, uint32_t *counts)
-{
-    HM_ARG(labels == nullptr || L >= 1, "hm_body_set_labels: %d labels (need at least 1 with a label image)", L);
-    HM_ARG(h != nullptr, "hm_body_set_labels: NULL handle");
-    const size_t n = (size_t)h->W * h->H;
-    if (labels) {
-        for (size_t p = 0; p < n; p++)
-            HM_ARG(labels[p] >= -1 && labels[p] < L, "hm_body_set_labels: label %d at pixel %zu outside -1..%d", (int)labels[p],
-                   p, L - 1);
-    }
-    HM_JOIN_LAZY(h);
-    int rc = body_map_build(h);
-    if (rc) return rc;
-    if (!labels) { h->body_L = 0; return HM_OK; }
-    HM_HIP(h->own.alloc(&h->d_blab, n * sizeof(int)));
-    HM_HIP(h->own.grow(&h->d_blcnt, (size_t)L * sizeof(unsigned)));
-    HM_HIP(h->own.grow(&h->d_bsum, (size_t)(h->T + L) * sizeof(unsigned long long)));
-    h->body_L = 0;                               // (until the label image and its counts are in place)
-    HM_HIP(hipMemcpyAsync(h->d_blab, labels, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HM_HIP(hipMemsetAsync(h->d_blcnt, 0, (size_t)L * sizeof(unsigned), h->stream));
-    hipLaunchKernelGGL(k_body_label_count, dim3(hm_cdiv((int)n, 256)), dim3(256), 0, h->stream, (const int *)h->d_btri,
-                       (const int *)h->d_blab, (int)n, h->d_blcnt);
-    HM_HIP(hipGetLastError());
-    if (counts) HM_HIP(hipMemcpyAsync(counts, h->d_blcnt, (size_t)L * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    h->body_L = L;
-    return HM_OK;
-}
-
-// the planes of the sums start 16 bytes aligned (k_body_stats_add moves four values at a time)
-static size_t body_stats_stride(const hm_ctx *h) { return ((size_t)h->W * h->H + 3) & ~(size_t)3; }
-static BodyStats body_stats_planes(const hm_ctx *h)
-{
-    const size_t ns = body_stats_stride(h);
-    return BodyStats{h->d_stsum, h->d_stsum + ns, h->d_stsum + 2 * ns, ns, h->d_stmax};
-}
-
-static int body_rec_slot(hm_ctx *h, const char *who, uint8_t **dst);
-
-// Queue the warp of frame d_frame (device) at state X (host, the first 2N values are read) on the handle's stream.
-static int body_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, uint8_t *d_out, int ch, unsigned long long *d_tsum,
-                      unsigned long long *d_lsum, const char *who)
-{
-    if (d_lsum && h->body_L == 0) { hm_set_error("%s: label sums asked for, and hm_body_set_labels has set no labels", who); return HM_ERR_STATE; }
-    if (h->stats_on && h->stats_frames >= h->stats_cap) {
-        hm_set_error("%s: the statistics hold %d frames, their capacity is %d (sums of 32 bits are exact up to %d frames): "
-                     "nothing added", who, h->stats_frames, h->stats_cap, BODY_STATS_CAP);
-        return HM_ERR_STATE;
-    }
-    uint8_t *rec_dst = nullptr;
-    if (h->rec_on) {                 // (before anything is queued: a refused warp leaves statistics and record as they were)
-        const int rc = body_rec_slot(h, who, &rec_dst);
-        if (rc) return rc;
-    }
-    const int n = h->W * h->H;
-    HM_HIP(hipMemcpyAsync(h->d_bX, X, (size_t)2 * h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (d_tsum) HM_HIP(hipMemsetAsync(d_tsum, 0, (size_t)h->T * sizeof(unsigned long long), h->stream));
-    if (d_lsum) HM_HIP(hipMemsetAsync(d_lsum, 0, (size_t)h->body_L * sizeof(unsigned long long), h->stream));
-    BodyWarpArgs a;
-    a.n = n; a.W = h->W; a.H = h->H; a.ch = ch;
-    a.tri_of = h->d_btri; a.bary = h->d_bbary; a.tidx = h->d_btidx;
-    a.X = h->d_bX; a.frame = d_frame; a.labels = h->d_blab;
-    a.out = d_out; a.tsum = d_tsum; a.lsum = d_lsum;
-    a.reg = h->stats_on || h->rec_on ? h->d_breg : nullptr;
-    hipLaunchKernelGGL(k_body_warp, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, a);
-    HM_HIP(hipGetLastError());
-    HM_HIP(hipEventRecord(h->ev_body, h->stream));
-    if (h->stats_on) {               // (behind the event: whoever waits for the warp's output does not wait for this)
-        const BodyStats st = body_stats_planes(h);
-        hipLaunchKernelGGL(k_body_stats_add, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, n, h->W,
-                           (const int *)h->d_btri, (const uint8_t *)h->d_breg, st);
-        HM_HIP(hipGetLastError());
-        h->stats_frames++;
-    }
-    if (h->rec_on) {                 // (behind the event as well)
-        const RecBox &b = h->rec_box;
-        hipLaunchKernelGGL(k_rec_copy, dim3(hm_cdiv((b.pitch >> 2) * b.bh, 256)), dim3(256), 0, h->stream, h->W, b,
-                           (const uint8_t *)h->d_breg, rec_dst);
-        HM_HIP(hipGetLastError());
-        h->rec_frames++;
-    }
-    return HM_OK;
-}
-
-extern "C" int hm_body_warp(hm_ctx_t h, const double *X, const uint8_t *frame, uint8_t *out, uint64_t *tri_sums,
-                            uint64_t *label_sums)
-{
-    HM_ARG(X && frame, "hm_body_warp: NULL state or frame");
-    HM_ARG(h != nullptr, "hm_body_warp: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_map_build(h);
-    if (rc) return rc;
-    if (label_sums && h->body_L == 0) { hm_set_error("hm_body_warp: label sums asked for, and hm_body_set_labels has set no labels"); return HM_ERR_STATE; }
-    const size_t n = (size_t)h->W * h->H;
-    HM_HIP(h->own.alloc(&h->d_bframe, n));
-    HM_HIP(h->own.alloc(&h->d_bout, 3 * n));
-    HM_HIP(hipMemcpyAsync(h->d_bframe, frame, n, hipMemcpyHostToDevice, h->stream));
-    unsigned long long *ts = h->d_bsum, *ls = h->d_bsum + h->T;
-    rc = body_queue(h, X, h->d_bframe, out ? h->d_bout : nullptr, 1, tri_sums ? ts : nullptr, label_sums ? ls : nullptr,
-                    "hm_body_warp");
-    if (rc) return rc;
-    if (out) HM_HIP(hipMemcpyAsync(out, h->d_bout, n, hipMemcpyDeviceToHost, h->stream));
-    if (tri_sums) HM_HIP(hipMemcpyAsync(tri_sums, ts, (size_t)h->T * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    if (label_sums) HM_HIP(hipMemcpyAsync(label_sums, ls, (size_t)h->body_L * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-extern "C" int hm_body_warp_dev(hm_ctx_t h, const double *X, const void *d_frame, void *d_out, int out_channels,
-                                void *d_tri_sums, void *d_label_sums, void *stream)
-{
-    HM_ARG(out_channels == 1 || out_channels == 3, "hm_body_warp_dev: out_channels %d (1 or 3)", out_channels);
-    HM_ARG(X && d_frame, "hm_body_warp_dev: NULL state or frame");
-    HM_ARG(((uintptr_t)d_out & 3) == 0, "hm_body_warp_dev: d_out is not 4-byte aligned");
-    HM_ARG(((uintptr_t)d_tri_sums & 7) == 0 && ((uintptr_t)d_label_sums & 7) == 0,
-           "hm_body_warp_dev: the sums are not 8-byte aligned");
-    HM_ARG(h != nullptr, "hm_body_warp_dev: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_map_build(h);
-    if (rc) return rc;
-    rc = body_queue(h, X, (const uint8_t *)d_frame, (uint8_t *)d_out, out_channels, (unsigned long long *)d_tri_sums,
-                    (unsigned long long *)d_label_sums, "hm_body_warp_dev");
-    if (rc) return rc;
-    if (stream) HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_body, 0));
-    return HM_OK;
-}
-
-extern "C" int hm_body_fence(hm_ctx_t h, void *stream)
-{
-    HM_ARG(h && stream, "hm_body_fence: NULL argument");
-    if (h->ev_body) {
-        HM_HIP(hipSetDevice(h->device));
-        HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_body, 0));
-    }
-    return HM_OK;
-}
-
-// ---- statistics of the registered video: sums per pixel, summary images, peaks (body_kernels.h) -------------------
-extern "C" int hm_body_stats_begin(hm_ctx_t h)
-{
-    HM_ARG(h != nullptr, "hm_body_stats_begin: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_map_build(h);
-    if (rc) return rc;
-    const size_t n = (size_t)h->W * h->H;
-    h->stats_on = false;                         // (until every buffer is there and zeroed)
-    HM_HIP(h->own.alloc(&h->d_breg, n));
-    const size_t ns = body_stats_stride(h);
-    HM_HIP(h->own.alloc(&h->d_stsum, 6 * ns * sizeof(unsigned)));
-    HM_HIP(h->own.alloc(&h->d_stmax, n));
-    HM_HIP(hipMemsetAsync(h->d_stsum, 0, 6 * ns * sizeof(unsigned), h->stream));
-    HM_HIP(hipMemsetAsync(h->d_stmax, 0, n, h->stream));
-    h->stats_frames = 0;
-    h->stats_on = true;
-    return HM_OK;
-}
-
-extern "C" int hm_body_stats_end(hm_ctx_t h)
-{
-    HM_ARG(h != nullptr, "hm_body_stats_end: NULL handle");
-    HM_JOIN_LAZY(h);
-    h->stats_on = false;
-    h->stats_frames = 0;
-    if (!h->d_stsum) return HM_OK;
-    HM_HIP(hipSetDevice(h->device));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    hipError_t e = h->rec_on ? hipSuccess : h->own.free(&h->d_breg);     // (the record's copy reads the same plane)
-    if (e == hipSuccess) e = h->own.free(&h->d_stsum);
-    if (e == hipSuccess) e = h->own.free(&h->d_stmax);
-    if (e == hipSuccess) e = h->own.free(&h->d_stimg);
-    if (e == hipSuccess) e = h->own.free(&h->d_pkidx);
-    if (e == hipSuccess) e = h->own.free(&h->d_pkscore);
-    if (e == hipSuccess) e = h->own.free(&h->d_pkcnt);
-    HM_HIP(e);
-    return HM_OK;
-}
-
-extern "C" int hm_body_stats_count(hm_ctx_t h, int *frames)
-{
-    HM_ARG(h && frames, "hm_body_stats_count: NULL argument");
-    HM_JOIN_LAZY(h);
-    *frames = h->stats_on ? h->stats_frames : 0;
-    return HM_OK;
-}
-
-static int body_stats_begun(hm_ctx *h, bool need_frames, const char *who)
-{
-    if (!h->stats_on) { hm_set_error("%s: no statistics (hm_body_stats_begin first)", who); return HM_ERR_STATE; }
-    if (need_frames && h->stats_frames < 1) { hm_set_error("%s: no frame added since hm_body_stats_begin", who); return HM_ERR_STATE; }
-    HM_HIP(hipSetDevice(h->device));
-    return HM_OK;
-}
-
-extern "C" int hm_body_stats_fetch(hm_ctx_t h, uint32_t *s1, uint32_t *s2, uint32_t *cross, uint8_t *vmax)
-{
-    HM_ARG(h != nullptr, "hm_body_stats_fetch: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_stats_begun(h, false, "hm_body_stats_fetch");
-    if (rc) return rc;
-    const size_t n = (size_t)h->W * h->H, b = n * sizeof(uint32_t);
-    const BodyStats st = body_stats_planes(h);
-    if (s1) HM_HIP(hipMemcpyAsync(s1, st.s1, b, hipMemcpyDeviceToHost, h->stream));
-    if (s2) HM_HIP(hipMemcpyAsync(s2, st.s2, b, hipMemcpyDeviceToHost, h->stream));
-    for (int d = 0; cross && d < 4; d++)
-        HM_HIP(hipMemcpyAsync(cross + d * n, st.cross + d * st.stride, b, hipMemcpyDeviceToHost, h->stream));
-    if (vmax) HM_HIP(hipMemcpyAsync(vmax, h->d_stmax, n, hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-// the three summary images of the sums so far into d_stimg, queued on the handle's stream
-static int body_stats_images_queue(hm_ctx *h)
-{
-    const size_t n = (size_t)h->W * h->H;
-    HM_HIP(h->own.alloc(&h->d_stimg, 3 * n * sizeof(double)));
-    BodyImages g;
-    g.n = (int)n; g.W = h->W; g.H = h->H; g.F = (double)h->stats_frames;
-    g.tri_of = h->d_btri;
-    g.st = body_stats_planes(h);
-    g.mean = h->d_stimg; g.sd = h->d_stimg + n; g.corr = h->d_stimg + 2 * n;
-    hipLaunchKernelGGL(k_body_stats_images, dim3(hm_cdiv((int)n, 256)), dim3(256), 0, h->stream, g);
-    HM_HIP(hipGetLastError());
-    return HM_OK;
-}
-
-extern "C" int hm_body_stats_images(hm_ctx_t h, double *mean, double *std, double *corr, uint8_t *vmax)
-{
-    HM_ARG(h != nullptr, "hm_body_stats_images: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_stats_begun(h, true, "hm_body_stats_images");
-    if (rc) return rc;
-    rc = body_stats_images_queue(h);
-    if (rc) return rc;
-    const size_t n = (size_t)h->W * h->H, b = n * sizeof(double);
-    if (mean) HM_HIP(hipMemcpyAsync(mean, h->d_stimg, b, hipMemcpyDeviceToHost, h->stream));
-    if (std) HM_HIP(hipMemcpyAsync(std, h->d_stimg + n, b, hipMemcpyDeviceToHost, h->stream));
-    if (corr) HM_HIP(hipMemcpyAsync(corr, h->d_stimg + 2 * n, b, hipMemcpyDeviceToHost, h->stream));
-    if (vmax) HM_HIP(hipMemcpyAsync(vmax, h->d_stmax, n, hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-extern "C" int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int cap, int32_t *index,
-                                   double *score, int *count)
-{
-    HM_ARG(which >= 0 && which <= 2, "hm_body_stats_peaks: score %d (0 corr, 1 std, 2 max - mean)", which);
-    HM_ARG(radius >= 1 && radius <= BODY_PEAK_RMAX, "hm_body_stats_peaks: radius %d outside 1..%d", radius, BODY_PEAK_RMAX);
-    HM_ARG(!(min_score != min_score), "hm_body_stats_peaks: min_score is NaN");
-    HM_ARG(cap >= 0 && (cap == 0 || (index && score)), "hm_body_stats_peaks: cap %d without arrays to fill", cap);
-    HM_ARG(h && count, "hm_body_stats_peaks: NULL argument");
-    HM_JOIN_LAZY(h);
-    int rc = body_stats_begun(h, true, "hm_body_stats_peaks");
-    if (rc) return rc;
-    rc = body_stats_images_queue(h);
-    if (rc) return rc;
-    const size_t n = (size_t)h->W * h->H;
-    HM_HIP(h->own.alloc(&h->d_pkidx, n * sizeof(int)));
-    HM_HIP(h->own.alloc(&h->d_pkscore, n * sizeof(double)));
-    HM_HIP(h->own.alloc(&h->d_pkcnt, sizeof(int)));
-    HM_HIP(hipMemsetAsync(h->d_pkcnt, 0, sizeof(int), h->stream));
-    BodyPeaks g;
-    g.W = h->W; g.H = h->H; g.which = which; g.radius = radius; g.cap = (int)n; g.min_score = min_score;
-    g.tri_of = h->d_btri;
-    g.mean = h->d_stimg; g.sd = h->d_stimg + n; g.corr = h->d_stimg + 2 * n; g.vmax = h->d_stmax;
-    g.count = h->d_pkcnt; g.index = h->d_pkidx; g.score = h->d_pkscore;
-    hipLaunchKernelGGL(k_body_peaks, dim3(hm_cdiv(h->W, BODY_PEAK_TILE), hm_cdiv(h->H, BODY_PEAK_TILE)),
-                       dim3(BODY_PEAK_TILE, BODY_PEAK_TILE), 0, h->stream, g);
-    HM_HIP(hipGetLastError());
-    int found = 0;
-    HM_HIP(hipMemcpyAsync(&found, h->d_pkcnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    if (found < 0 || (size_t)found > n) { hm_set_error("hm_body_stats_peaks: %d peaks reported for %zu pixels", found, n); return HM_ERR_HIP; }
-    std::vector<int> idx(found);
-    std::vector<double> sc(found);
-    if (found) {
-        HM_HIP(hipMemcpyAsync(idx.data(), h->d_pkidx, (size_t)found * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HM_HIP(hipMemcpyAsync(sc.data(), h->d_pkscore, (size_t)found * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HM_HIP(hipStreamSynchronize(h->stream));
-    }
-    // the waves arrive in any order: score descending, raster index ascending
-    std::vector<int> order(found);
-    for (int i = 0; i < found; i++) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return sc[a] != sc[b] ? sc[a] > sc[b] : idx[a] < idx[b]; });
-    for (int i = 0; i < found && i < cap; i++) {
-        index[i] = idx[order[i]];
-        score[i] = sc[order[i]];
-    }
-    *count = found;
-    return HM_OK;
-}
-
-// ---- the registered video kept on the device, and the reductions over it (roi_kernels.h) ---------------------------
-#define REC_CHUNK_BYTES ((size_t)64 << 20)
-#define REC_MAX_FRAMES (1 << 24)
-
-// stop recording and free the record (the caller has checked that there is one)
-static int body_rec_drop(hm_ctx *h)
-{
-    h->rec_on = false;
-    h->rec_frames = 0;
-    HM_HIP(hipSetDevice(h->device));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    hipError_t e = hipSuccess;
-    for (uint8_t *&c : h->rec_chunks) {
-        const hipError_t e1 = h->own.free(&c);
-        if (e == hipSuccess) e = e1;
-    }
-    h->rec_chunks.clear();
-    if (e == hipSuccess) e = h->own.free(&h->d_rec_tab);
-    if (e == hipSuccess) e = h->own.free(&h->d_rec_tmp);
-    if (e == hipSuccess && !h->stats_on) e = h->own.free(&h->d_breg);
-    HM_HIP(e);
-    return HM_OK;
-}
-
-extern "C" int hm_body_rec_begin(hm_ctx_t h, uint64_t max_bytes)
-{
-    HM_ARG(h != nullptr, "hm_body_rec_begin: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_map_build(h);
-    if (rc) return rc;
-    if (h->rec_on) {
-        rc = body_rec_drop(h);
-        if (rc) return rc;
-    }
-    const size_t n = (size_t)h->W * h->H;
-    if (h->h_btri.empty()) {
-        h->h_btri.resize(n);
-        HM_HIP(hipMemcpyAsync(h->h_btri.data(), h->d_btri, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HM_HIP(hipStreamSynchronize(h->stream));
-    }
-    int c0 = h->W, c1 = -1, r0 = h->H, r1 = -1;
-    for (int r = 0; r < h->H; r++)
-        for (int c = 0; c < h->W; c++)
-            if (h->h_btri[(size_t)r * h->W + c] >= 0) {
-                c0 = std::min(c0, c); c1 = std::max(c1, c);
-                r0 = std::min(r0, r); r1 = std::max(r1, r);
-            }
-    if (c1 < 0) c0 = c1 = r0 = r1 = 0;          // (an empty map: one pixel, registered as 0)
-    RecBox &b = h->rec_box;
-    b.c0 = c0; b.r0 = r0; b.bw = c1 - c0 + 1; b.bh = r1 - r0 + 1;
-    b.pitch = (b.bw + 3) & ~3;
-    b.fs = ((size_t)b.pitch * b.bh + 15) & ~(size_t)15;
-    b.fpc = h->rec_chunk > 0 ? h->rec_chunk : (int)std::max<size_t>(1, REC_CHUNK_BYTES / b.fs);
-    h->rec_max = max_bytes;
-    h->rec_cap = (int)std::min<unsigned long long>(max_bytes / b.fs, REC_MAX_FRAMES);
-    HM_HIP(h->own.alloc(&h->d_breg, n));
-    h->rec_frames = 0;
-    h->rec_on = true;
-    return HM_OK;
-}
-
-extern "C" int hm_body_rec_end(hm_ctx_t h)
-{
-    HM_ARG(h != nullptr, "hm_body_rec_end: NULL handle");
-    HM_JOIN_LAZY(h);
-    if (!h->rec_on) return HM_OK;
-    return body_rec_drop(h);
-}
-
-extern "C" int hm_body_rec_count(hm_ctx_t h, int *frames)
-{
-    HM_ARG(h && frames, "hm_body_rec_count: NULL argument");
-    HM_JOIN_LAZY(h);
-    *frames = h->rec_on ? h->rec_frames : 0;
-    return HM_OK;
-}
-
-// where the next frame of the record goes; allocates the chunk it starts
-static int body_rec_slot(hm_ctx *h, const char *who, uint8_t **dst)
-{
-    const RecBox &b = h->rec_box;
-    if (h->rec_frames >= h->rec_cap) {
-        hm_set_error("%s: the record holds %d frames of %zu bytes (a box of %d x %d pixels) and its budget of %llu bytes holds "
-                     "%d: nothing appended", who, h->rec_frames, b.fs, b.bw, b.bh, h->rec_max, h->rec_cap);
-        return HM_ERR_STATE;
-    }
-    const int ch = h->rec_frames / b.fpc;
-    if (ch == (int)h->rec_chunks.size()) {
-        const int frames = std::min(b.fpc, h->rec_cap - ch * b.fpc);
-        uint8_t *p = nullptr;
-        HM_HIP(h->own.alloc(&p, (size_t)frames * b.fs));
-        h->rec_chunks.push_back(p);
-    }
-    *dst = h->rec_chunks[ch] + (size_t)(h->rec_frames - ch * b.fpc) * b.fs;
-    return HM_OK;
-}
-
-static int body_rec_begun(hm_ctx *h, const char *who)
-{
-    if (!h->rec_on) { hm_set_error("%s: no record (hm_body_rec_begin first)", who); return HM_ERR_STATE; }
-    HM_HIP(hipSetDevice(h->device));
-    return HM_OK;
-}
-
-extern "C" int hm_body_rec_fetch(hm_ctx_t h, int k0, int n, uint8_t *out)
-{
-    HM_ARG(h != nullptr, "hm_body_rec_fetch: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_rec_begun(h, "hm_body_rec_fetch");
-    if (rc) return rc;
-    HM_ARG(k0 >= 0 && n >= 0 && k0 <= h->rec_frames && n <= h->rec_frames - k0,
-           "hm_body_rec_fetch: frames %d .. %d of a record of %d", k0, k0 + n - 1, h->rec_frames);
-    HM_ARG(out || n == 0, "hm_body_rec_fetch: NULL output");
-    HM_HIP(hipStreamSynchronize(h->stream));
-    const RecBox &b = h->rec_box;
-    const size_t px = (size_t)h->W * h->H;
-    for (int k = 0; k < n; k++) {
-        uint8_t *o = out + (size_t)k * px;
-        memset(o, 0, px);
-        const int ch = (k0 + k) / b.fpc;
-        const uint8_t *src = h->rec_chunks[ch] + (size_t)(k0 + k - ch * b.fpc) * b.fs;
-        HM_HIP(hipMemcpy2D(o + (size_t)b.r0 * h->W + b.c0, (size_t)h->W, src, (size_t)b.pitch, (size_t)b.bw, (size_t)b.bh,
-                           hipMemcpyDeviceToHost));
-    }
-    return HM_OK;
-}
-
-// a reduction may start: there are frames, and the chunks' addresses are on the device
-static int body_rec_ready(hm_ctx *h, const char *who)
-{
-    const int rc = body_rec_begun(h, who);
-    if (rc) return rc;
-    if (h->rec_frames < 1) { hm_set_error("%s: no frame recorded since hm_body_rec_begin", who); return HM_ERR_STATE; }
-    const size_t bytes = h->rec_chunks.size() * sizeof(uint8_t *);
-    HM_HIP(h->own.grow(&h->d_rec_tab, bytes));       // (every reduction waits for its results: nothing in flight reads it)
-    HM_HIP(hipMemcpyAsync(h->d_rec_tab, h->rec_chunks.data(), bytes, hipMemcpyHostToDevice, h->stream));
-    return HM_OK;
-}
-
-// the reductions' buffers, carved from one allocation (16-byte aligned pieces)
-struct RecCarve {
-    uint8_t *base;
-    size_t off;
-    template <typename T> T *take(size_t count)
-    {
-        off = (off + 15) & ~(size_t)15;
-        T *p = (T *)(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
-extern "C" int hm_body_rec_label_sums(hm_ctx_t h, const int32_t *labels, int L, uint64_t *out)
-{
-    HM_ARG(labels && out && L >= 1, "hm_body_rec_label_sums: NULL argument or %d labels", L);
-    HM_ARG(h != nullptr, "hm_body_rec_label_sums: NULL handle");
-    const size_t n = (size_t)h->W * h->H;
-    for (size_t p = 0; p < n; p++)
-        HM_ARG(labels[p] >= -1 && labels[p] < L, "hm_body_rec_label_sums: label %d at pixel %zu outside -1..%d", (int)labels[p],
-               p, L - 1);
-    HM_JOIN_LAZY(h);
-    int rc = body_rec_ready(h, "hm_body_rec_label_sums");
-    if (rc) return rc;
-    const RecBox &b = h->rec_box;
-    const int F = h->rec_frames, nb = b.pitch * b.bh;
-    int *d_img = nullptr, *d_lab = nullptr;
-    unsigned long long *d_sum = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        RecCarve cv = {pass ? h->d_rec_tmp : nullptr, 0};
-        d_img = cv.take<int>(n);
-        d_lab = cv.take<int>(nb);
-        d_sum = cv.take<unsigned long long>((size_t)F * L);
-        if (!pass) HM_HIP(h->own.grow(&h->d_rec_tmp, cv.off));
-    }
-    HM_HIP(hipMemcpyAsync(d_img, labels, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HM_HIP(hipMemsetAsync(d_sum, 0, (size_t)F * L * sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(k_rec_box_labels, dim3(hm_cdiv(nb, 256)), dim3(256), 0, h->stream, h->W, b, (const int *)h->d_btri,
-                       (const int *)d_img, d_lab);
-    hipLaunchKernelGGL(k_rec_label_sums, dim3(hm_cdiv(nb >> 2, 256), std::min(F, 1024)), dim3(256), 0, h->stream, b,
-                       (const uint8_t *const *)h->d_rec_tab, F, (const int *)d_lab, L, d_sum);
-    HM_HIP(hipGetLastError());
-    HM_HIP(hipMemcpyAsync(out, d_sum, (size_t)F * L * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-// seeds are pixels of the map
-static int body_rec_seeds(hm_ctx *h, int P, const int32_t *seeds, const char *who)
-{
-    for (int s = 0; s < P; s++) {
-        const int c = seeds[2 * s], r = seeds[2 * s + 1];
-        if (!(c >= 0 && c < h->W && r >= 0 && r < h->H && h->h_btri[(size_t)r * h->W + c] >= 0)) {
-            hm_set_error("%s: seed %d (column %d, row %d) is not a pixel of the body map", who, s, c, r);
-            return HM_ERR_ARG;
-        }
-    }
-    return HM_OK;
-}
-
-extern "C" int hm_body_rec_seed_sums(hm_ctx_t h, int P, const int32_t *seeds, double r_disc, double r_in, double r_out, int R,
-                                     uint32_t *n_T, uint32_t *n_G, uint64_t *T, uint64_t *G, int64_t *U, uint64_t *w1,
-                                     uint64_t *w2, int64_t *c, int64_t *u1, int64_t *u2)
-{
-    HM_ARG(P >= 1 && seeds, "hm_body_rec_seed_sums: %d seeds", P);
-    HM_ARG(r_disc >= 0.0 && r_disc <= REC_RMAX && r_in >= 0.0 && r_in <= r_out && r_out <= REC_RMAX,
-           "hm_body_rec_seed_sums: radii %g, %g, %g (need 0 <= r_disc <= %d and 0 <= r_in <= r_out <= %d)", r_disc, r_in, r_out,
-           REC_RMAX, REC_RMAX);
-    HM_ARG(R >= 0 && R <= REC_WIN_RMAX, "hm_body_rec_seed_sums: window radius %d outside 0..%d", R, REC_WIN_RMAX);
-    HM_ARG(h != nullptr, "hm_body_rec_seed_sums: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_rec_ready(h, "hm_body_rec_seed_sums");
-    if (rc) return rc;
-    rc = body_rec_seeds(h, P, seeds, "hm_body_rec_seed_sums");
-    if (rc) return rc;
-    const int F = h->rec_frames;
-    HM_ARG((long long)F * P < (1ll << 30), "hm_body_rec_seed_sums: %d frames x %d seeds", F, P);
-    // the pixels of every disc and ring, and the bound that keeps sum U^2 exact: |U| <= 255 n_T n_G
-    const double rd2 = r_disc * r_disc, ri2 = r_in * r_in, ro2 = r_out * r_out;
-    const int Rg = (int)std::max(r_disc, r_out);
-    std::vector<unsigned> cnt(2 * (size_t)P, 0);
-    for (int s = 0; s < P; s++) {
-        for (int dy = -Rg; dy <= Rg; dy++)
-            for (int dx = -Rg; dx <= Rg; dx++) {
-                const int x = seeds[2 * s] + dx, y = seeds[2 * s + 1] + dy;
-                if (x < 0 || x >= h->W || y < 0 || y >= h->H || h->h_btri[(size_t)y * h->W + x] < 0) continue;
-                const double d2 = (double)(dx * dx + dy * dy);
-                if (d2 <= rd2) cnt[s]++;
-                if (d2 >= ri2 && d2 <= ro2) cnt[P + s]++;
-            }
-        const unsigned __int128 m = (unsigned __int128)255 * cnt[s] * cnt[P + s];
-        HM_ARG(m * m * (unsigned __int128)F < ((unsigned __int128)1 << 63),
-               "hm_body_rec_seed_sums: seed %d: F (255 n_T n_G)^2 = %d (255 x %u x %u)^2 could pass 2^63", s, F, cnt[s], cnt[P + s]);
-    }
-    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
-    RecSeeds g;
-    RecWin q;
-    int2 *d_seeds = nullptr;
-    unsigned *d_cnt = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        RecCarve cv = {pass ? h->d_rec_tmp : nullptr, 0};
-        d_seeds = cv.take<int2>(P);
-        d_cnt = cv.take<unsigned>(2 * (size_t)P);
-        g.T = cv.take<unsigned long long>(fp);
-        g.G = cv.take<unsigned long long>(fp);
-        g.U = cv.take<long long>(fp);
-        q.w1 = cv.take<unsigned long long>(P * nw);
-        q.w2 = cv.take<unsigned long long>(P * nw);
-        q.c = cv.take<long long>(P * nw);
-        q.u1 = cv.take<long long>(P);
-        q.u2 = cv.take<long long>(P);
-        if (!pass) HM_HIP(h->own.grow(&h->d_rec_tmp, cv.off));
-    }
-    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    HM_HIP(hipMemcpyAsync(d_cnt, cnt.data(), 2 * (size_t)P * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
-    g.b = h->rec_box; g.chunks = (const uint8_t *const *)h->d_rec_tab; g.F = F; g.P = P; g.R = Rg;
-    g.seeds = d_seeds; g.rd2 = rd2; g.ri2 = ri2; g.ro2 = ro2; g.nT = d_cnt; g.nG = d_cnt + P;
-    hipLaunchKernelGGL(k_rec_seed_traces, dim3(hm_cdiv((int)fp, 4)), dim3(256), 0, h->stream, g);
-    q.b = h->rec_box; q.chunks = g.chunks; q.F = F; q.P = P; q.R = R; q.seeds = d_seeds; q.U = g.U;
-    hipLaunchKernelGGL(k_rec_window_sums, dim3(hm_cdiv((int)nw, 256), P), dim3(256), 0, h->stream, q);
-    HM_HIP(hipGetLastError());
-    if (n_T) memcpy(n_T, cnt.data(), (size_t)P * sizeof(uint32_t));
-    if (n_G) memcpy(n_G, cnt.data() + P, (size_t)P * sizeof(uint32_t));
-    if (T) HM_HIP(hipMemcpyAsync(T, g.T, fp * 8, hipMemcpyDeviceToHost, h->stream));
-    if (G) HM_HIP(hipMemcpyAsync(G, g.G, fp * 8, hipMemcpyDeviceToHost, h->stream));
-    if (U) HM_HIP(hipMemcpyAsync(U, g.U, fp * 8, hipMemcpyDeviceToHost, h->stream));
-    if (w1) HM_HIP(hipMemcpyAsync(w1, q.w1, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
-    if (w2) HM_HIP(hipMemcpyAsync(w2, q.w2, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
-    if (c) HM_HIP(hipMemcpyAsync(c, q.c, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
-    if (u1) HM_HIP(hipMemcpyAsync(u1, q.u1, (size_t)P * 8, hipMemcpyDeviceToHost, h->stream));
-    if (u2) HM_HIP(hipMemcpyAsync(u2, q.u2, (size_t)P * 8, hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-extern "C" int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds, int R, const uint16_t *weights, uint64_t *out)
-{
-    HM_ARG(P >= 1 && seeds && weights && out, "hm_body_rec_weighted_sums: NULL argument or %d seeds", P);
-    HM_ARG(R >= 0 && R <= REC_RMAX, "hm_body_rec_weighted_sums: window radius %d outside 0..%d", R, REC_RMAX);
-    HM_ARG(h != nullptr, "hm_body_rec_weighted_sums: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_rec_ready(h, "hm_body_rec_weighted_sums");
-    if (rc) return rc;
-    rc = body_rec_seeds(h, P, seeds, "hm_body_rec_weighted_sums");
-    if (rc) return rc;
-    const int F = h->rec_frames;
-    HM_ARG((long long)F * P < (1ll << 30), "hm_body_rec_weighted_sums: %d frames x %d seeds", F, P);
-    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
-    int2 *d_seeds = nullptr;
-    uint16_t *d_w = nullptr;
-    unsigned long long *d_out = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        RecCarve cv = {pass ? h->d_rec_tmp : nullptr, 0};
-        d_seeds = cv.take<int2>(P);
-        d_w = cv.take<uint16_t>(P * nw);
-        d_out = cv.take<unsigned long long>(fp);
-        if (!pass) HM_HIP(h->own.grow(&h->d_rec_tmp, cv.off));
-    }
-    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    HM_HIP(hipMemcpyAsync(d_w, weights, P * nw * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_rec_weighted_sums, dim3(hm_cdiv((int)fp, 4)), dim3(256), 0, h->stream, h->rec_box,
-                       (const uint8_t *const *)h->d_rec_tab, F, P, R, (const int2 *)d_seeds, (const uint16_t *)d_w, d_out);
-    HM_HIP(hipGetLastError());
-    HM_HIP(hipMemcpyAsync(out, d_out, fp * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-extern "C" int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seeds, int R, const int32_t *q, int64_t *out)
-{
-    HM_ARG(P >= 1 && seeds && q && out, "hm_body_rec_trace_products: NULL argument or %d seeds", P);
-    HM_ARG(R >= 0 && R <= REC_WIN_RMAX, "hm_body_rec_trace_products: window radius %d outside 0..%d", R, REC_WIN_RMAX);
-    HM_ARG(h != nullptr, "hm_body_rec_trace_products: NULL handle");
-    HM_JOIN_LAZY(h);
-    int rc = body_rec_ready(h, "hm_body_rec_trace_products");
-    if (rc) return rc;
-    rc = body_rec_seeds(h, P, seeds, "hm_body_rec_trace_products");
-    if (rc) return rc;
-    const int F = h->rec_frames;
-    HM_ARG((long long)F * P < (1ll << 30), "hm_body_rec_trace_products: %d frames x %d seeds", F, P);
-    // |v q| <= 255 x 2^31 per frame
-    HM_ARG((unsigned __int128)F * 255u * ((unsigned __int128)1 << 31) < ((unsigned __int128)1 << 63),
-           "hm_body_rec_trace_products: F x 255 x 2^31 = %d x 255 x 2^31 could pass 2^63", F);
-    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
-    const int tiles = hm_cdiv((int)nw, 64);
-    HM_ARG((long long)P * tiles < (1ll << 31), "hm_body_rec_trace_products: %d seeds x %d tiles of the window", P, tiles);
-    RecTP g;
-    int2 *d_seeds = nullptr;
-    int *d_q = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        RecCarve cv = {pass ? h->d_rec_tmp : nullptr, 0};
-        d_seeds = cv.take<int2>(P);
-        d_q = cv.take<int>(fp);
-        g.out = cv.take<unsigned long long>(P * nw);
-        if (!pass) HM_HIP(h->own.grow(&h->d_rec_tmp, cv.off));
-    }
-    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    HM_HIP(hipMemcpyAsync(d_q, q, fp * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HM_HIP(hipMemsetAsync(g.out, 0, P * nw * sizeof(unsigned long long), h->stream));
-    g.b = h->rec_box; g.chunks = (const uint8_t *const *)h->d_rec_tab; g.F = F; g.P = P; g.R = R;
-    g.tpf = h->rec_tp_frames; g.seeds = d_seeds; g.q = d_q;
-    const int runs = hm_cdiv(F, g.tpf);
-    hipLaunchKernelGGL(k_rec_trace_products, dim3(P * tiles, std::min(runs, 65535)), dim3(256), 0, h->stream, g);
-    HM_HIP(hipGetLastError());
-    HM_HIP(hipMemcpyAsync(out, g.out, P * nw * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-// ---- the flow tool's preview video (reference src/optical_flow_ext.cpp:172-281, 336-389) ---------------------------
-extern "C" int hm_flow_preview(int device, int n, int W, int H, int channels, const uint8_t *frames, const float *fx,
-                               const float *fy, uint8_t *out, int on_device, void *stream)
-{
-    HM_ARG(frames && fx && fy && out, "hm_flow_preview: NULL argument");
-    HM_ARG(n >= 1 && W >= 1 && H >= 1 && (channels == 1 || channels == 3),
-           "hm_flow_preview: bad size n=%d %dx%d channels=%d", n, W, H, channels);
-    HM_HIP(hipSetDevice(device));
-    const long long px = (long long)n * W * H;
-    const dim3 grid((unsigned)((px + 255) / 256));
-    if (on_device) {
-        hipLaunchKernelGGL(k_flow_preview, grid, dim3(256), 0, (hipStream_t)stream, frames, channels, fx, fy, px, out);
-        HM_HIP(hipGetLastError());
-        return HM_OK;
-    }
-    uint8_t *d_f = nullptr, *d_o = nullptr;
-    float *d_x = nullptr, *d_y = nullptr;
-    int rc = HM_OK;
-    auto run = [&]() -> int {
-        HM_HIP(hm_malloc((void **)&d_f, (size_t)px * channels));
-        HM_HIP(hm_malloc((void **)&d_o, (size_t)px * 3));
-        HM_HIP(hm_malloc((void **)&d_x, (size_t)px * sizeof(float)));
-        HM_HIP(hm_malloc((void **)&d_y, (size_t)px * sizeof(float)));
-        HM_HIP(hipMemcpy(d_f, frames, (size_t)px * channels, hipMemcpyHostToDevice));
-        HM_HIP(hipMemcpy(d_x, fx, (size_t)px * sizeof(float), hipMemcpyHostToDevice));
-        HM_HIP(hipMemcpy(d_y, fy, (size_t)px * sizeof(float), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_flow_preview, grid, dim3(256), 0, 0, (const uint8_t *)d_f, channels, (const float *)d_x,
-                           (const float *)d_y, px, d_o);
-        HM_HIP(hipGetLastError());
-        HM_HIP(hipMemcpy(out, d_o, (size_t)px * 3, hipMemcpyDeviceToHost));
-        return HM_OK;
-    };
-    rc = run();
-    void *ptrs[] = {d_f, d_o, d_x, d_y};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    return rc;
 }
 
 // ---- the Rauch-Tung-Striebel smoother (hm_smooth_*, include/hydra_mi.h) ------------------------------------------

@@ -9,187 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#define EKF_SUB 256
-#define EKF_MAX_STAR 24        // triangles around one vertex
-#define EKF_TILE 16
-#define EKF_MAX_TRI 4096
-
-struct TriSetup {              // one triangle in one configuration
-    // edge function E_k = ea*c + eb*r + ec at pixel (col c, row r).  Whole numbers kept as doubles:
-    // for coordinates within +-2^24 px every product and sum stays below 2^53, so binary64 evaluates
-    // them exactly -- the same values as 64-bit integers at the cost of two full-rate v_fma_f64
-    // (64-bit integer multiplies are built from quarter-rate 32-bit ones on gfx950).
-    double ea[3], eb[3], ec[3];
-    // ec + (1 if a zero edge value counts as inside, the top-left rule): E is a whole number, so
-    // "E > 0 or (E == 0 and top-left)" is the single comparison ea*c + eb*r + ecb > 0
-    double ecb[3];
-    int cmin, cmax, rmin, rmax;  // pixel bounding box (inclusive), empty if cmin > cmax (16-byte aligned: one scalar load)
-    int tl[3];                 // 1 if a zero edge value counts as inside (top-left edge)
-    float inv;                 // 1 / (2 area)
-    int i0, i1, i2;            // vertex ids after orientation normalisation
-    // attributes of the three vertices in that order: texture coordinates (pixels of the initial
-    // frame) and the two velocity render attributes vx, -vy.  Kept here so that a covered pixel
-    // needs no dependent global loads besides its texel.
-    float ux[3], uy[3], ax[3], ay[3];
-};
-
-__device__ __forceinline__ void d_tri_attr(TriSetup &s, const float *__restrict__ uv, const double *__restrict__ X, int N)
-{
-    const int id[3] = {s.i0, s.i1, s.i2};
-    for (int k = 0; k < 3; k++) {
-        s.ux[k] = uv[2 * id[k]];
-        s.uy[k] = uv[2 * id[k] + 1];
-        s.ax[k] = (float)X[2 * N + 2 * id[k]];
-        s.ay[k] = (float)(-X[2 * N + 2 * id[k] + 1]);
-    }
-}
-
-__device__ __forceinline__ long long d_snap(double x) { return (long long)rint(x * (double)EKF_SUB); }
-
-// Pixel bounding box (inclusive) of the triangle with snapped integer positions, as d_tri_setup keeps it: empty
-// (cmin > cmax) for a degenerate or out-of-range triangle.  One function for every caller: a tile that asks "can
-// this triangle reach me" gets the answer the setup itself would give.
-__device__ __forceinline__ bool d_tri_sane(long long x0, long long y0, long long x1, long long y1, long long x2, long long y2)
-{
-    const long long lim = (long long)1 << 32;     // 2^24 px in 1/256 px units: the exact range of the edge functions
-    return x0 > -lim && x0 < lim && y0 > -lim && y0 < lim && x1 > -lim && x1 < lim && y1 > -lim && y1 < lim &&
-           x2 > -lim && x2 < lim && y2 > -lim && y2 < lim;
-}
-__device__ __forceinline__ void d_tri_bbox(long long x0, long long y0, long long x1, long long y1, long long x2, long long y2,
-                                           int W, int H, int &cmin, int &cmax, int &rmin, int &rmax)
-{
-    cmin = 1; cmax = 0; rmin = 1; rmax = 0;
-    const long long area = d_tri_sane(x0, y0, x1, y1, x2, y2) ? (x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0) : 0;
-    if (area == 0) return;
-    long long xmin = x0 < x1 ? (x0 < x2 ? x0 : x2) : (x1 < x2 ? x1 : x2);
-    long long xmax = x0 > x1 ? (x0 > x2 ? x0 : x2) : (x1 > x2 ? x1 : x2);
-    long long ymin = y0 < y1 ? (y0 < y2 ? y0 : y2) : (y1 < y2 ? y1 : y2);
-    long long ymax = y0 > y1 ? (y0 > y2 ? y0 : y2) : (y1 > y2 ? y1 : y2);
-    // floor division by 256 (arithmetic shift), as in the oracle
-    long long cl = (xmin - 128) >> 8, ch = ((xmax - 128) >> 8) + 1;
-    long long rl = (ymin - 128) >> 8, rh = ((ymax - 128) >> 8) + 1;
-    if (cl < 0) cl = 0;
-    if (rl < 0) rl = 0;
-    if (ch > W - 1) ch = W - 1;
-    if (rh > H - 1) rh = H - 1;
-    cmin = (int)cl; cmax = (int)ch; rmin = (int)rl; rmax = (int)rh;
-}
-
-// Build the setup of triangle (v0,v1,v2) with snapped integer positions p[3][2].
-__device__ inline void d_tri_setup(TriSetup &s, int v0, int v1, int v2, long long x0, long long y0,
-                                   long long x1, long long y1, long long x2, long long y2, int W, int H)
-{
-    s.cmin = 1; s.cmax = 0; s.rmin = 1; s.rmax = 0;
-    const bool sane = d_tri_sane(x0, y0, x1, y1, x2, y2);
-    long long area = sane ? (x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0) : 0;
-    s.i0 = v0; s.i1 = v1; s.i2 = v2;
-    s.inv = 0.0f;
-    for (int k = 0; k < 3; k++) { s.ea[k] = 0.0; s.eb[k] = 0.0; s.ec[k] = -1.0; s.ecb[k] = -1.0; s.tl[k] = 0; }
-    if (area == 0) return;
-    d_tri_bbox(x0, y0, x1, y1, x2, y2, W, H, s.cmin, s.cmax, s.rmin, s.rmax);      // (the box does not depend on the orientation)
-    if (area < 0) {
-        long long t;
-        t = x1; x1 = x2; x2 = t;
-        t = y1; y1 = y2; y2 = t;
-        s.i1 = v2; s.i2 = v1;
-        area = -area;
-    }
-    // E0: edge 1->2 (weight of vertex 0), E1: edge 2->0, E2: edge 0->1
-    const long long ex[3] = {x2 - x1, x0 - x2, x1 - x0};
-    const long long ey[3] = {y2 - y1, y0 - y2, y1 - y0};
-    const long long ox[3] = {x1, x2, x0};
-    const long long oy[3] = {y1, y2, y0};
-    for (int k = 0; k < 3; k++) {
-        // E(px,py) = ex*(py-oy) - ey*(px-ox), px = 256 c + 128, py = 256 r + 128
-        s.ea[k] = (double)(-ey[k] * EKF_SUB);
-        s.eb[k] = (double)(ex[k] * EKF_SUB);
-        s.ec[k] = (double)(ex[k] * (128 - oy[k]) - ey[k] * (128 - ox[k]));
-        s.tl[k] = (ey[k] > 0) || (ey[k] == 0 && ex[k] < 0);
-        s.ecb[k] = s.ec[k] + (double)s.tl[k];
-    }
-    s.inv = 1.0f / (float)area;
-}
-
-// coverage of the pixel centre (dc, dr) without the bounding-box shortcut and without branches (for
-// pixels inside the frame the three edge tests imply the box); barycentrics separately
-__device__ __forceinline__ bool d_tri_cover(const TriSetup &s, double dc, double dr)
-{
-    const double e0 = fma(s.ea[0], dc, fma(s.eb[0], dr, s.ecb[0]));
-    const double e1 = fma(s.ea[1], dc, fma(s.eb[1], dr, s.ecb[1]));
-    const double e2 = fma(s.ea[2], dc, fma(s.eb[2], dr, s.ecb[2]));
-    return (e0 > 0.0) & (e1 > 0.0) & (e2 > 0.0);
-}
-// the same, handing back the values of edges 1 and 2 (with the top-left bias in: ecb): the barycentrics of a covered pixel
-// follow from them by taking the bias out again -- whole numbers below 2^53, so e - bias IS ea c + eb r + ec, exactly
-__device__ __forceinline__ bool d_tri_cover2(const TriSetup &s, double dc, double dr, double &e1, double &e2)
-{
-    const double e0 = fma(s.ea[0], dc, fma(s.eb[0], dr, s.ecb[0]));
-    e1 = fma(s.ea[1], dc, fma(s.eb[1], dr, s.ecb[1]));
-    e2 = fma(s.ea[2], dc, fma(s.eb[2], dr, s.ecb[2]));
-    return (e0 > 0.0) & (e1 > 0.0) & (e2 > 0.0);
-}
-__device__ __forceinline__ void d_tri_bary2(const TriSetup &s, double e1, double e2, float &l1, float &l2)
-{
-    l1 = (float)(e1 - (s.tl[1] ? 1.0 : 0.0)) * s.inv;
-    l2 = (float)(e2 - (s.tl[2] ? 1.0 : 0.0)) * s.inv;
-}
-__device__ __forceinline__ void d_tri_bary(const TriSetup &s, double dc, double dr, float &l1, float &l2)
-{
-    l1 = (float)fma(s.ea[1], dc, fma(s.eb[1], dr, s.ec[1])) * s.inv;
-    l2 = (float)fma(s.ea[2], dc, fma(s.eb[2], dr, s.ec[2])) * s.inv;
-}
-
-// coverage + barycentrics of pixel (c, r)
-__device__ __forceinline__ bool d_tri_eval(const TriSetup &s, int c, int r, float &l1, float &l2)
-{
-    if (c < s.cmin || c > s.cmax || r < s.rmin || r > s.rmax) return false;
-    const double dc = (double)c, dr = (double)r;
-    const double e0 = fma(s.ea[0], dc, fma(s.eb[0], dr, s.ec[0]));      // exact: see TriSetup
-    const double e1 = fma(s.ea[1], dc, fma(s.eb[1], dr, s.ec[1]));
-    const double e2 = fma(s.ea[2], dc, fma(s.eb[2], dr, s.ec[2]));
-    bool in = (e0 > 0 || (e0 == 0 && s.tl[0])) && (e1 > 0 || (e1 == 0 && s.tl[1])) &&
-              (e2 > 0 || (e2 == 0 && s.tl[2]));
-    if (!in) return false;
-    l1 = (float)e1 * s.inv;
-    l2 = (float)e2 * s.inv;
-    return true;
-}
-
-__device__ __forceinline__ float d_lerp(float a0, float a1, float a2, float l1, float l2)
-{
-    return (a0 + l1 * (a1 - a0)) + l2 * (a2 - a0);
-}
-
-// offset of the nearest texel in the initial frame
-__device__ __forceinline__ int d_texel_at(const TriSetup &s, float l1, float l2, int W, int H)
-{
-    float tx = d_lerp(s.ux[0], s.ux[1], s.ux[2], l1, l2);
-    float ty = d_lerp(s.uy[0], s.uy[1], s.uy[2], l1, l2);
-    int cx = (int)floorf(tx), cy = (int)floorf(ty);
-    cx = cx < 0 ? 0 : (cx > W - 1 ? W - 1 : cx);
-    cy = cy < 0 ? 0 : (cy > H - 1 ? H - 1 : cy);
-    return cy * W + cx;
-}
-__device__ __forceinline__ int d_texel(const uint8_t *__restrict__ tex, const TriSetup &s, float l1, float l2, int W,
-                                       int H)
-{
-    return tex[d_texel_at(s, l1, l2, W, H)];
-}
-
-struct Mesh {
-    int W, H, N, T;
-    const int *tri;           // T*3
-    const float *uv;          // N*2
-    const uint8_t *tex;       // W*H
-};
-
-// unclamped render targets: im = min(255, acc), m = cnt > 0 ? 255 : 0
-struct Targets {
-    int *acc;                 // sum of texels
-    float *fx, *fy;           // sums of interpolated vx, -vy
-    int *cnt;                 // covering triangles
-};
+#include "hm_types.h"     // TriSetup and its coverage rules, Mesh, Targets, DPool, RI_H
 
 // ---- per-triangle setup for a full render of state X --------------------------------
 __global__ void k_setup_all(Mesh m, const double *__restrict__ X, TriSetup *__restrict__ out)
@@ -586,15 +406,7 @@ __device__ inline void d_star_setups(TriSetup *dst, int ns, const int *tris, con
 // the two words before it touches the tile's planes.  Pixels of a padded tile that lie outside the frame are parked
 // as empty ones.
 #define POOL_EMPTY 0x7FFF
-struct DPool {
-    int *hdr;                 // N x 4: c0, r0, rw, rh of the region (all multiples of 8)
-    int *live;                // one word per tile of the pool (cap / 64)
-    const int *area;          // N region areas (k_star_regions); a region's offset is the sum of those before it
-    short2 *xi, *yi;          // (image, mask) numerators of D_{v,x} and D_{v,y}
-    float *xfx, *xfy, *yfx, *yfy, *vxfx, *vyfy;
-    long long cap;            // pixels in the pool
-    int *overflow;            // set to 1 if the regions do not fit
-};
+// (struct DPool: hm_types.h)
 
 __device__ __forceinline__ void d_park_empty(const DPool &P, long long pp)
 {
@@ -1079,7 +891,6 @@ __global__ __launch_bounds__(MEAS_NT) void k_measure_edge(MeasureArgs a)
 #define RI_CHUNK 32
 #define RI_GROUPS 256
 #define RI_W 64
-#define RI_H 16                        // strip height of the default launch (hm_ctx_tune "render_rows": 16 or 8)
 struct IterRenderArgs {
     Mesh m;
     const double *X;

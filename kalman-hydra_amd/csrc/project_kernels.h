@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "host_block.h"
+#include "hm_types.h"
 
 struct Outline {
     int2 *pts;       // capacity W*H: border pixels of the object
@@ -75,15 +76,7 @@ __global__ __launch_bounds__(OUTLINE_NT) void k_outline(const uint8_t *__restric
 //   k_ccl_select   the level-0 object with the largest area (ties: first in raster order);
 //   k_ccl_write    the pruned mask: inside that object's outer contour and not inside one of its holes of area >= 40.
 // All counts are whole numbers, areas are compared doubled (2 A = 2 inside -/+ boundary - 2): same decisions as the oracle.
-struct Ccl {
-    int *L;          // W*H: labels (pixel indices)
-    int *cnt;        // W*H, used at roots: pixels inside or on the component's contour
-    int *bnd;        // W*H, used at roots: boundary points of the contour (object: pixels 4-adjacent to the outside;
-                     // hole: pixels of the enclosing object 4-adjacent to it)
-    uint8_t *edge;   // W*H, used at background roots: 1 = reaches the frame edge
-    unsigned long long *best;     // [0]: (2 A << 32) | ~root of the best level-0 object so far
-    int W, H;
-};
+// (struct Ccl: hm_types.h)
 
 __device__ __forceinline__ int d_ccl_find(int *L, int i)
 {

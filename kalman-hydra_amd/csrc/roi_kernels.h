@@ -6,13 +6,7 @@
 // outside the map is registered as 0 (k_body_warp), so a sum over any set of box pixels is the sum over its map pixels:
 // the reductions look at the map only where they count pixels, which the host does.
 #pragma once
-#include "body_kernels.h"
-
-struct RecBox {
-    int c0, r0, bw, bh;                // the box in the frame: columns c0 .. c0 + bw - 1, rows r0 .. r0 + bh - 1
-    int pitch, fpc;                    // bytes per row, frames per chunk
-    size_t fs;                         // bytes per frame
-};
+#include "body_kernels.h"     // (struct RecBox, REC_TP_MAX: hm_types.h)
 
 __device__ __forceinline__ const uint8_t *d_rec_frame(const RecBox &b, const uint8_t *const *chunks, int k)
 {
@@ -202,7 +196,6 @@ __global__ __launch_bounds__(256) void k_rec_weighted_sums(RecBox b, const uint8
     if (lane == 0) out[(size_t)k * P + s] = sum;
 }
 
-#define REC_TP_MAX 1024                // the most frames of a workgroup's run (hm_ctx_tune "rec_tp_frames")
 
 struct RecTP {
     RecBox b;

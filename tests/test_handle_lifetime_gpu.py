@@ -5,10 +5,15 @@ a flow handle and drives every group of resources the filter handle builds on fi
 the streaming pipeline with its Newton worker attached (the prediction's stream and blocks, the tail's stream and event,
 the armed mask, the covariance prediction queued ahead), a projection onto a host mask and onto the mask in place,
 contour pruning, the multi-perturbation operators, two covariance predictions of which the second has more springs than
-any before it (the spring arrays grow), the views and the force plot; and a flow handle whose CU mask is changed and
-dropped.  Then everything is closed.  Free device memory after the last cycle is what it was after the first, or more:
-earlier tests of the same process may still give memory back (objects the collector frees late), which the collections
-here bring forward but cannot rule out; a handle that keeps what it built shows as less.
+any before it (the spring arrays grow), the views and the force plot, the body-frame readout -- the body map, a label
+image of a few discs, three warps with the statistics and a record of a few frames both on, the summary images, the
+peaks and one reduction of the record over a seed -- and a flow handle whose CU mask is changed and dropped.  Then
+everything is closed, the filter handle with its statistics and its record still open.  Free device memory after the last
+cycle is what it was after the first, or more: earlier tests of the same process may still give memory back (objects the
+collector frees late), which the collections here bring forward but cannot rule out; a handle that keeps what it built
+shows as less.  The statistics' sums and images are 48 MiB per handle at this size, more than the slack in one cycle; the
+record's few frames are less than the slack, so for the record this covers faults when the handle is destroyed, not
+leaks.
 """
 import ctypes
 import gc
@@ -38,7 +43,7 @@ def _free_device_memory():
 
 
 def _cycle(video, masks, centre, radius):
-    from hydra_mi import brox, kalman, mesh
+    from hydra_mi import body, brox, kalman, mesh
     from hydra_mi.pipeline import FlowEKFPipeline
     from oracle import partitions_ref
 
@@ -76,6 +81,22 @@ def _cycle(video, masks, centre, radius):
 
         assert R.view(X, "overlay").shape == (N_PX, N_PX, 3)
         assert R.view_forces(X, X, X, X, X, X).shape == (N_PX, N_PX, 3)
+
+        tri_of, _ = R.body_map()
+        cx, cy = centre
+        pts = np.array([(cx, cy), (cx - 0.3 * radius, cy), (cx, cy + 0.3 * radius)])
+        R.body_set_labels(body.disc_labels(tri_of, pts, 3.0), len(pts))
+        R.body_stats_begin()
+        R.body_rec_begin(body.record_bytes(tri_of, 4))
+        for k in range(3):
+            reg, _, ls = R.body_warp(X, video[k])
+            assert reg.shape == (N_PX, N_PX) and ls.shape == (len(pts),)
+        assert R.body_stats_images()[0].shape == (N_PX, N_PX)
+        assert R.body_stats_peaks("corr", 6)[2] >= 0
+        seed = np.array([[int(cx), int(cy)]], np.int32)
+        assert tri_of[seed[0, 1], seed[0, 0]] >= 0
+        assert R.body_rec_seed_sums(seed, 3.0, 6.0, 8.5, 4)["T"].shape == (3, 1)
+        assert R.body_stats_count() == 3 and R.body_rec_count() == 3     # (both still open when the handle is closed)
     finally:
         pipe.close()
         kf.close()
