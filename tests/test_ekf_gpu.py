@@ -442,8 +442,8 @@ def test_state_errors_are_loud(hm):
         renderer.Renderer(dm, np.zeros((4, 2)), np.zeros((64, 64, 2), np.float32), 64, tex, True, 0.0, 1, 1)
 
 
-# the last case has more than 248 vertices: 4N > 992, i.e. more than two column batches in k_back_row and a
-# block count that is not a power of two for the recursive inverse
+# 4N from 72 to 1380: k_tvec sums one to eleven row groups of 128 per column, k_ttt runs 1 to 44 steps per tile (fewer
+# than, exactly and many times its three products in flight), the factorisation 3 to 44 block columns
 # 4N = 72, 200, 632, 1380 and 160, 108, 308: last block of 8, 8, 24, 4 and 32 (none), 12, 20 rows
 @pytest.mark.parametrize("n,h0", [(64, 11.0), (96, 9.0), (160, 8.0), (256, 8.5), (64, 7.0), (96, 13.0), (128, 9.5)])
 def test_device_dense_update_matches_host_algebra(hm, n, h0):
@@ -1004,7 +1004,6 @@ def test_persistent_factorisation_equals_launch_per_step(hm, n, h0):
             assert all(np.array_equal(a, b) for a, b in zip(out[mode], got))          # and it repeats
         out[mode] = got
     assert all(np.array_equal(a, b) for a, b in zip(out[0], out[1]))
-    A = np.linalg.inv(W)
     assert np.isfinite(out[1][3]).all() and np.abs(out[1][3] - out[1][3].T).max() <= 1e-12 * np.abs(out[1][3]).max()
     with pytest.raises(RuntimeError):
         R.tune("chol_flow", 2)
