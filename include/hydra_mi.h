@@ -458,6 +458,47 @@ int hm_view_dev(hm_ctx_t h, const double *X, int which, const int32_t *palette, 
 int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, const double *pred, const double *tv,
                    const double *fv, const double *mv, uint8_t *bgr);
 
+/* The cell view: what is known about the body -- ROIs, demixed shapes, their activity -- painted onto a frame of
+ * the video at state X, on the animal as it moves (the reference paints its neurons onto every frame,
+ * synth.py:268-279).  H x W x 3 uint8, B, G, R, rows top to bottom, like every view; it has buffers of its own
+ * and changes nothing a measurement, update or prediction reads.  Per image pixel (row r, column c), in this order:
+ *   base      B = G = R = frame[r, c], the gray frame passed (not the handle's observation).
+ *   triangle  the lowest-indexed triangle that covers the pixel centre at X (the first 2N doubles of X, the
+ *             positions), by the render's rule as hm_body_map applies it at X = uv: positions snapped to
+ *             1/256 px, exact edge functions, top-left ties, orientation swap.  A triangle of area 0, or with a
+ *             vertex that is not finite or beyond +-2^24 px, is skipped; without a covering triangle the pixel
+ *             keeps the base.  l1 = e1 / area, l2 = e2 / area in binary64, vertex order i0, i1, i2 after the swap at X.
+ *   body pixel  bx = (Ux[i0] + l1 (Ux[i1] - Ux[i0])) + l2 (Ux[i2] - Ux[i0]), the same for by, in binary64 without
+ *             contraction, U the binary32 uv widened; the body pixel is column floor(bx), row floor(by); no
+ *             cell where either is not finite or off the frame.
+ *   layers    for j = 0 .. n_layers - 1 in order, s = labels[j][body pixel]; if s >= 0:
+ *             a = weights[j][body pixel] levels[s] (uint16 times uint8), D = 65535 * 255, and every channel becomes
+ *             (ch (D - a) + colour[s][ch] a + D / 2) / D in unsigned 64-bit integers.
+ *   outline   (flags bit 0) a body pixel with layer-0 label s >= 0 is an outline pixel when one of its four
+ *             neighbours has a different layer-0 label, a neighbour off the frame counting as different; an image
+ *             pixel that lands on one takes colour[s] outright (a silent cell stays visible).
+ *   wire      (flags bit 1) B = min(255, B + 128 count), the wireframe of hm_view.
+ *   markers   last: P points, image coordinates (x, y) as doubles (what following a body point through the mesh
+ *             gives), centre ((int)x, (int)y) truncated as C does, the filled disc dx^2 + dy^2 <= point_radius^2
+ *             in integers in the point's own B G R colour; a later point wins over an earlier one; a point that
+ *             is not finite or beyond +-2^20 px is skipped; pixels off the frame are not written.
+ * hm_view_set_cells: labels: n_layers (1..4) planes of W*H int32 in body coordinates, -1 none, labels 0 .. L-1;
+ * weights: the same planes as uint16, NULL: 65535 everywhere; colours: L x 3, B G R.  labels NULL clears the
+ * cells.  A label >= L or an n_layers outside 1..4 is HM_ERR_ARG (hm_last_error has the numbers).  The cells stay
+ * until they are set again or cleared.
+ * hm_view_cells: host arrays; frame W*H gray; levels: L bytes, NULL: 255 everywhere; P = 0 or points NULL: no
+ * markers; point_colours P x 3; bgr W*H*3.  Without cells and without points there is nothing to draw:
+ * HM_ERR_STATE.  A negative point_radius is HM_ERR_ARG.
+ * hm_view_cells_dev: d_frame and d_bgr (4-byte aligned) are device memory; queued on the handle's stream, it does
+ * not wait: X, levels, points and their colours are copied before it returns (the caller may overwrite them at
+ * once), the frame is read when the view runs; `stream` (may be NULL) waits for the view on the device, as in
+ * hm_view_dev. */
+int hm_view_set_cells(hm_ctx_t h, int n_layers, const int32_t *labels, const uint16_t *weights, int L, const uint8_t *colours);
+int hm_view_cells(hm_ctx_t h, const double *X, const uint8_t *frame, const uint8_t *levels, int flags,
+                  int P, const double *points, const uint8_t *point_colours, int point_radius, uint8_t *bgr);
+int hm_view_cells_dev(hm_ctx_t h, const double *X, const void *d_frame, const uint8_t *levels, int flags,
+                      int P, const double *points, const uint8_t *point_colours, int point_radius, void *d_bgr, void *stream);
+
 /* The body-frame readout: frames pulled back through the tracked mesh into the coordinates of its texture
  * (the frame-0 pixel grid of the initial vertices uv), the neuron-tracking layer the reference leaves
  * unbuilt (test_neurontracking.py:15; its synthetic neurons move with the animal, synth.py:219-266).

@@ -129,6 +129,10 @@ SIGNATURES = {
     "hm_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_view_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     "hm_view_forces": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hm_view_set_cells": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp]),
+    "hm_view_cells": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp]),
+    "hm_view_cells_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp,
+                                         c_vp]),
     "hm_body_map": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "hm_body_set_labels": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_body_warp": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

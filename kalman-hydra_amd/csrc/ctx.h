@@ -89,7 +89,24 @@ struct ViewState {
     double *X = nullptr, *force = nullptr;
     uint8_t *out = nullptr;
     hipEvent_t ev = nullptr;
+    // hm_view_set_cells / hm_view_cells*: the cells in body coordinates (they stay until set again or cleared) ...
+    int c_layers = 0, c_L = 0;       // layers 0: no cells set
+    bool c_weighted = false;         // c_w holds weights (else 65535 everywhere)
+    int *c_lab = nullptr;            // c_layers planes of W*H labels, -1: none
+    uint16_t *c_w = nullptr;         // the same planes of weights
+    uint8_t *c_col = nullptr;        // c_L x 3 colours, B G R
+    uint8_t *c_outline = nullptr;    // W*H: the outline pixels of layer 0 (k_view_cell_outline)
+    uint8_t *c_frame = nullptr;      // hm_view_cells' frame (W*H)
+    // ... and what changes with every frame -- X (2N doubles) | points (2P doubles) | levels (c_L) | point colours (3P) --
+    // copied into one of VIEW_CELL_SLOTS page-locked slots in turn and from there to c_in on the stream: the call returns
+    // with the caller's arrays free, and waits only when the copy out of the slot it is about to fill is still to run
+    uint8_t *c_in = nullptr;
+    uint8_t *c_slot[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t c_slot_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool c_slot_used[4] = {false, false, false, false};
+    int c_next = 0;
 };
+#define VIEW_CELL_SLOTS 4
 
 // hm_body_*: the body-frame readout (body_kernels.h), buffers of its own allocated on first use -- it reads the state
 // it is given and nothing else of the filter's

@@ -142,6 +142,140 @@ extern "C" int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, c
     return view_download(h, bgr);
 }
 
+// ---- the cell overlay (view_kernels.h: k_view_cells) ----------------------------------------------------------------
+extern "C" int hm_view_set_cells(hm_ctx_t h, int n_layers, const int32_t *labels, const uint16_t *weights, int L,
+                                 const uint8_t *colours)
+{
+    HM_ARG(h != nullptr, "hm_view_set_cells: NULL handle");
+    if (labels) {
+        HM_ARG(n_layers >= 1 && n_layers <= CV_MAX_LAYERS, "hm_view_set_cells: n_layers %d outside 1..%d", n_layers, CV_MAX_LAYERS);
+        HM_ARG(L >= 1 && colours, "hm_view_set_cells: %d labels (need at least 1) or no colours", L);
+        const size_t nl = (size_t)n_layers * h->W * h->H;
+        for (size_t p = 0; p < nl; p++)
+            HM_ARG(labels[p] >= -1 && labels[p] < L, "hm_view_set_cells: label %d at pixel %zu of layer %zu outside -1..%d",
+                   (int)labels[p], p % ((size_t)h->W * h->H), p / ((size_t)h->W * h->H), L - 1);
+    }
+    HM_JOIN_LAZY(h);
+    HM_HIP(hipSetDevice(h->device));
+    HM_HIP(hipStreamSynchronize(h->stream));          // (a view in flight reads the cells in place)
+    ViewState &v = h->view;
+    v.c_layers = 0;
+    if (!labels) return HM_OK;
+    const size_t n = (size_t)h->W * h->H, nl = (size_t)n_layers * n;
+    HM_HIP(h->own.grow(&v.c_lab, nl * sizeof(int)));
+    if (weights) HM_HIP(h->own.grow(&v.c_w, nl * sizeof(uint16_t)));
+    HM_HIP(h->own.grow(&v.c_col, (size_t)3 * L));
+    HM_HIP(h->own.alloc(&v.c_outline, n));
+    HM_HIP(hipMemcpyAsync(v.c_lab, labels, nl * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (weights) HM_HIP(hipMemcpyAsync(v.c_w, weights, nl * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(v.c_col, colours, (size_t)3 * L, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_view_cell_outline, dim3(hm_cdiv((int)n, 256)), dim3(256), 0, h->stream, (const int *)v.c_lab, h->W, h->H,
+                       v.c_outline);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipStreamSynchronize(h->stream));
+    v.c_weighted = weights != nullptr;
+    v.c_L = L;
+    v.c_layers = n_layers;
+    return HM_OK;
+}
+
+// Queue the cell view of frame d_frame (device) at state X (host) into d_out (device, W*H*3) on the handle's stream.
+static int view_cells_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, const uint8_t *levels, int flags, int P,
+                            const double *points, const uint8_t *point_colours, int radius, uint8_t *d_out, const char *who)
+{
+    ViewState &v = h->view;
+    if (!points) P = 0;
+    HM_ARG(X && d_frame && d_out, "%s: NULL state, frame or output", who);
+    HM_ARG(((uintptr_t)d_out & 3) == 0, "%s: the output is not 4-byte aligned", who);
+    HM_ARG(flags >= 0 && flags <= (CV_OUTLINE | CV_WIRE), "%s: flags %d outside 0..%d", who, flags, CV_OUTLINE | CV_WIRE);
+    HM_ARG(P >= 0 && (P == 0 || point_colours), "%s: %d points without colours", who, P);
+    HM_ARG(radius >= 0, "%s: point radius %d is negative", who, radius);
+    if (v.c_layers == 0 && P == 0) {
+        hm_set_error("%s: nothing to draw: hm_view_set_cells has set no cells and there are no points", who);
+        return HM_ERR_STATE;
+    }
+    HM_HIP(hipSetDevice(h->device));
+    const int n = h->W * h->H;
+    const bool cells = v.c_layers > 0, wire = (flags & CV_WIRE) != 0;
+    const int L = cells ? v.c_L : 0;
+    // the frame's block: X | points | levels | point colours
+    const size_t oX = 0, oP = (size_t)2 * h->N * sizeof(double), oL = oP + (size_t)2 * P * sizeof(double), oC = oL + (levels ? L : 0);
+    const size_t bytes = oC + (size_t)3 * P;
+    HM_HIP(h->own.event(&v.ev));
+    if (wire) HM_HIP(h->own.alloc(&v.wire, (size_t)n * sizeof(unsigned)));
+    const int s = v.c_next;
+    HM_HIP(h->own.event(&v.c_slot_ev[s]));
+    if (v.c_slot_used[s]) HM_HIP(hipEventSynchronize(v.c_slot_ev[s]));      // (the copy out of this slot has run)
+    v.c_slot_used[s] = false;
+    HM_HIP(h->own.host_grow(&v.c_slot[s], bytes, hipHostMallocDefault));
+    {
+        const auto it = h->own.mem.find(v.c_in);
+        if (!v.c_in || it == h->own.mem.end() || it->second.bytes < bytes) {
+            HM_HIP(hipStreamSynchronize(h->stream));      // (a view in flight reads the block that grows)
+            HM_HIP(h->own.grow(&v.c_in, bytes));
+        }
+    }
+    uint8_t *slot = v.c_slot[s];
+    memcpy(slot + oX, X, oP);
+    if (P) memcpy(slot + oP, points, (size_t)2 * P * sizeof(double));
+    if (levels && L) memcpy(slot + oL, levels, (size_t)L);
+    if (P) memcpy(slot + oC, point_colours, (size_t)3 * P);
+    HM_HIP(hipMemcpyAsync(v.c_in, slot, bytes, hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipEventRecord(v.c_slot_ev[s], h->stream));
+    v.c_slot_used[s] = true;
+    v.c_next = (s + 1) % VIEW_CELL_SLOTS;
+    const double *dX = (const double *)(v.c_in + oX);
+    if (wire) {
+        HM_HIP(hipMemsetAsync(v.wire, 0, (size_t)n * sizeof(unsigned), h->stream));
+        hipLaunchKernelGGL(k_view_wire, dim3(hm_cdiv(3 * h->T, 256 / VIEW_SEG_WAVE)), dim3(256), 0, h->stream,
+                           (const int *)h->d_tri, h->T, dX, h->W, h->H, v.wire);
+    }
+    CellViewArgs a;
+    a.W = h->W; a.H = h->H; a.T = cells ? h->T : 0; a.n_layers = v.c_layers; a.flags = flags;
+    a.tiles_x = hm_cdiv(h->W, CV_W);
+    a.tri = h->d_tri; a.uv = h->d_uv; a.X = dX; a.frame = d_frame;
+    a.labels = v.c_lab; a.weights = v.c_weighted ? v.c_w : nullptr; a.colours = v.c_col;
+    a.levels = levels ? v.c_in + oL : nullptr;
+    a.outline = v.c_outline; a.wire = v.wire; a.out = d_out;
+    hipLaunchKernelGGL(k_view_cells, dim3(a.tiles_x * hm_cdiv(h->H, CV_H)), dim3(256), 0, h->stream, a);
+    if (P)
+        hipLaunchKernelGGL(k_view_cell_marks, dim3(hm_cdiv(P, 256 / VIEW_SEG_WAVE)), dim3(256), 0, h->stream, h->W, h->H, P, radius,
+                           (const double *)(v.c_in + oP), (const uint8_t *)(v.c_in + oC), d_out);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_view_cells(hm_ctx_t h, const double *X, const uint8_t *frame, const uint8_t *levels, int flags, int P,
+                             const double *points, const uint8_t *point_colours, int point_radius, uint8_t *bgr)
+{
+    HM_ARG(h && frame && bgr, "hm_view_cells: NULL argument");
+    HM_JOIN_LAZY(h);
+    HM_HIP(hipSetDevice(h->device));
+    const size_t n = (size_t)h->W * h->H;
+    HM_HIP(h->own.alloc(&h->view.c_frame, n));
+    HM_HIP(h->own.alloc(&h->view.out, 3 * n));
+    HM_HIP(hipMemcpyAsync(h->view.c_frame, frame, n, hipMemcpyHostToDevice, h->stream));
+    const int rc = view_cells_queue(h, X, h->view.c_frame, levels, flags, P, points, point_colours, point_radius, h->view.out,
+                                    "hm_view_cells");
+    if (rc) return rc;
+    return view_download(h, bgr);
+}
+
+extern "C" int hm_view_cells_dev(hm_ctx_t h, const double *X, const void *d_frame, const uint8_t *levels, int flags, int P,
+                                 const double *points, const uint8_t *point_colours, int point_radius, void *d_bgr, void *stream)
+{
+    HM_ARG(h != nullptr, "hm_view_cells_dev: NULL handle");
+    HM_JOIN_LAZY(h);
+    const int rc = view_cells_queue(h, X, (const uint8_t *)d_frame, levels, flags, P, points, point_colours, point_radius,
+                                    (uint8_t *)d_bgr, "hm_view_cells_dev");
+    if (rc) return rc;
+    if (stream) {
+        HM_HIP(hipEventRecord(h->view.ev, h->stream));
+        HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->view.ev, 0));
+    }
+    return HM_OK;
+}
+
 // ---- the body-frame readout (body_kernels.h) --------------------------------------------------------------------
 // The body map at X = uv (k_setup_all, then k_body_map), the pixels per triangle on the host.  Once per handle.
 static int body_map_build(hm_ctx *h)

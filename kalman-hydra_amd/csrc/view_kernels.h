@@ -4,6 +4,7 @@
 // except atan2f in the colour wheel, so a NumPy restatement reproduces it bit for bit (tests/view_ref.py).
 #pragma once
 #include "hm_common.h"
+#include "hm_types.h"
 
 #define VIEW_SEG_WAVE 64               // lanes per segment: a segment's pixels are spread over one wave
 #define VIEW_COORD_MAX 1048576.0       // segments with an end point beyond +-2^20 px are not drawn (a diverged state)
@@ -180,6 +181,231 @@ __global__ __launch_bounds__(256) void k_view_arrows(const double *__restrict__ 
     d_segment(ax, ay, bx, by, lane, W, H, [&](int p) {
         out[3 * (size_t)p] = colour.x; out[3 * (size_t)p + 1] = colour.y; out[3 * (size_t)p + 2] = colour.z;
     });
+}
+
+// ---- the cell overlay (hm_view_cells*): what roi / demix know about the body, painted onto the moving animal ----------
+// The inverse of k_body_warp: per pixel of the IMAGE at state X the body pixel under it, then that pixel's cells.  In this
+// order (include/hydra_mi.h has the rules in full; tests/cellview_ref.py restates them in NumPy, bit for bit):
+//   base      B = G = R = frame[r, c];
+//   triangle  the lowest-indexed triangle that covers the pixel centre at X, by the render's rule (d_snap, d_tri_setup,
+//             d_tri_cover2: nothing of it is restated here); skipped: area 0, a vertex that is not finite or outside
+//             d_tri_sane.  l1 = e1 / area, l2 = e2 / area in binary64 as k_body_map forms them;
+//   body pixel  (floor(bx), floor(by)), bx = (Ux[i0] + l1 (Ux[i1] - Ux[i0])) + l2 (Ux[i2] - Ux[i0]), U the binary32 uv
+//             widened; none when not finite or off the frame;
+//   layers    j = 0 .. n_layers - 1: s = labels[j][body pixel] >= 0: a = weights[j][body pixel] levels[s], D = 65535 * 255,
+//             ch = (ch (D - a) + colour[s][ch] a + D / 2) / D in unsigned 64-bit integers;
+//   outline   (CV_OUTLINE) an outline pixel of layer 0 (k_view_cell_outline) takes colour[s] outright;
+//   wire      (CV_WIRE) B = min(255, B + 128 count) of k_view_wire.
+// The markers are a launch of their own behind it (k_view_cell_marks).
+//
+// One CV_W x CV_H strip of the image per workgroup, four pixels per thread (column c0 + lane, rows r0 + wave + 4 j: a wave
+// gathers along a row), as k_render_iter's strips: every thread tests its share of the triangles' boxes against the
+// strip into an LDS bit set; the candidates -- in ascending index order, the rank among the set bits is the slot -- are set
+// up CV_CAP at a time into LDS by the threads that tested them, and every pixel without a triangle yet walks the batch in
+// order and keeps the first that covers it.  A strip with more candidates than CV_CAP takes more batches: there is no cap
+// (the bit set holds EKF_MAX_TRI triangles, all a handle can have).  The strip's colours are then staged in LDS and written
+// as whole dwords wherever a dword lies inside the strip's bytes of a row (3 CV_W = 192 bytes: 48 dwords when the row
+// starts on one), single bytes at the two ends where it does not -- any W, no tail of the image treated apart.
+#define CV_W 64
+#define CV_H 16
+#define CV_CAP 32                      // candidate triangles set up in LDS at a time
+#define CV_MAX_LAYERS 4
+#define CV_OUTLINE 1
+#define CV_WIRE 2
+#define CV_ROW_WORDS (3 * CV_W / 4 + 1)     // most dwords that 3 CV_W bytes starting anywhere touch
+
+struct CellViewArgs {
+    int W, H, T, n_layers, flags, tiles_x;      // T 0: no cells set (markers over the frame)
+    const int *tri;
+    const float *uv;
+    const double *X;                   // 2N positions
+    const uint8_t *frame;              // W x H gray
+    const int *labels;                 // n_layers planes of W*H, -1: none
+    const uint16_t *weights;           // the same planes, NULL: 65535 everywhere
+    const uint8_t *colours;            // L x 3, B G R
+    const uint8_t *levels;             // L, NULL: 255 everywhere
+    const uint8_t *outline;            // W*H: 1 on the outline pixels of layer 0
+    const unsigned *wire;              // wireframe counts (CV_WIRE)
+    uint8_t *out;                      // W*H*3, 4-byte aligned
+};
+
+struct CellShared {
+    unsigned mask[EKF_MAX_TRI / 32];
+    TriSetup cand[CV_CAP];
+    unsigned px[CV_H][CV_W];           // B | G << 8 | R << 16
+};
+
+// a vertex the snap may take: finite and within the range d_tri_sane accepts (anything beyond fails that test anyway)
+__device__ __forceinline__ bool d_cv_vertex_ok(double x, double y) { return fabs(x) <= 16777216.0 && fabs(y) <= 16777216.0; }
+
+__global__ __launch_bounds__(256) void k_view_cells(CellViewArgs a)
+{
+    __shared__ CellShared sh;
+    const int tid = threadIdx.x;
+    const int words = (a.T + 31) / 32;
+    for (int i = tid; i < words; i += 256) sh.mask[i] = 0;
+    __syncthreads();
+    const int c0 = ((int)blockIdx.x % a.tiles_x) * CV_W, r0 = ((int)blockIdx.x / a.tiles_x) * CV_H;
+    const double *__restrict__ X = a.X;
+    for (int t = tid; t < a.T; t += 256) {
+        const int v0 = a.tri[3 * t], v1 = a.tri[3 * t + 1], v2 = a.tri[3 * t + 2];
+        const double x0 = X[2 * v0], y0 = X[2 * v0 + 1], x1 = X[2 * v1], y1 = X[2 * v1 + 1], x2 = X[2 * v2], y2 = X[2 * v2 + 1];
+        if (!(d_cv_vertex_ok(x0, y0) && d_cv_vertex_ok(x1, y1) && d_cv_vertex_ok(x2, y2))) continue;
+        int cmin, cmax, rmin, rmax;
+        d_tri_bbox(d_snap(x0), d_snap(y0), d_snap(x1), d_snap(y1), d_snap(x2), d_snap(y2), a.W, a.H, cmin, cmax, rmin, rmax);
+        if (cmin <= cmax && cmax >= c0 && cmin < c0 + CV_W && rmax >= r0 && rmin < r0 + CV_H)
+            atomicOr(&sh.mask[t >> 5], 1u << (t & 31));
+    }
+    __syncthreads();
+    int total = 0;
+    for (int w = 0; w < words; w++) total += __popc(sh.mask[w]);
+    const int c = c0 + (tid & 63), rb = r0 + (tid >> 6);
+    constexpr int NPX = CV_W * CV_H / 256;
+    int bp[NPX];                       // the body pixel, -1: none; -2: no triangle found yet
+#pragma unroll
+    for (int j = 0; j < NPX; j++) bp[j] = -2;
+    for (int base = 0; base < total; base += CV_CAP) {
+        const int nch = min(CV_CAP, total - base);
+        for (int tb = tid; tb < a.T; tb += 256) {
+            const unsigned word = sh.mask[tb >> 5], bit = 1u << (tb & 31);
+            if (!(word & bit)) continue;
+            int rank = __popc(word & (bit - 1u));
+            for (int w = 0; w < (tb >> 5); w++) rank += __popc(sh.mask[w]);
+            if (rank < base || rank >= base + nch) continue;
+            const int v0 = a.tri[3 * tb], v1 = a.tri[3 * tb + 1], v2 = a.tri[3 * tb + 2];
+            TriSetup su;
+            d_tri_setup(su, v0, v1, v2, d_snap(X[2 * v0]), d_snap(X[2 * v0 + 1]), d_snap(X[2 * v1]), d_snap(X[2 * v1 + 1]),
+                        d_snap(X[2 * v2]), d_snap(X[2 * v2 + 1]), a.W, a.H);
+            const int id[3] = {su.i0, su.i1, su.i2};
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                su.ux[k] = a.uv[2 * id[k]]; su.uy[k] = a.uv[2 * id[k] + 1];
+                su.ax[k] = 0.0f; su.ay[k] = 0.0f;
+            }
+            sh.cand[rank - base] = su;
+        }
+        __syncthreads();
+        if (c < a.W)
+            for (int q = 0; q < nch; q++) {                // ascending triangle order
+                const TriSetup &su = sh.cand[q];
+#pragma unroll
+                for (int j = 0; j < NPX; j++) {
+                    const int r = rb + 4 * j;
+                    if (bp[j] != -2 || r >= a.H || c < su.cmin || c > su.cmax || r < su.rmin || r > su.rmax) continue;
+                    const double dc = (double)c, dr = (double)r;
+                    double e1, e2;
+                    if (!d_tri_cover2(su, dc, dr, e1, e2)) continue;
+                    // as k_body_map: whole numbers below 2^53, the area of the swapped order is their exact sum
+                    e1 -= su.tl[1] ? 1.0 : 0.0;
+                    e2 -= su.tl[2] ? 1.0 : 0.0;
+                    const double e0 = fma(su.ea[0], dc, fma(su.eb[0], dr, su.ec[0]));
+                    const double area = (e0 + e1) + e2;
+                    const double l1 = e1 / area, l2 = e2 / area;
+                    const double ux0 = (double)su.ux[0], uy0 = (double)su.uy[0];
+                    const double bx = (ux0 + l1 * ((double)su.ux[1] - ux0)) + l2 * ((double)su.ux[2] - ux0);
+                    const double by = (uy0 + l1 * ((double)su.uy[1] - uy0)) + l2 * ((double)su.uy[2] - uy0);
+                    // (a NaN fails every comparison; floor(b) in 0 .. W - 1 is 0 <= b < W)
+                    bp[j] = (bx >= 0.0 && bx < (double)a.W && by >= 0.0 && by < (double)a.H) ? (int)floor(by) * a.W + (int)floor(bx) : -1;
+                }
+            }
+        __syncthreads();
+    }
+    const size_t n = (size_t)a.W * a.H;
+    const unsigned long long D = 65535ull * 255ull;
+#pragma unroll
+    for (int j = 0; j < NPX; j++) {
+        const int r = rb + 4 * j;
+        if (c >= a.W || r >= a.H) continue;
+        const int p = r * a.W + c;
+        unsigned long long ch[3];
+        ch[0] = ch[1] = ch[2] = a.frame[p];
+        if (bp[j] >= 0) {
+            for (int k = 0; k < a.n_layers; k++) {
+                const int s = a.labels[k * n + bp[j]];
+                if (s < 0) continue;
+                const unsigned long long al = (unsigned long long)(a.weights ? a.weights[k * n + bp[j]] : 65535u) *
+                                              (unsigned long long)(a.levels ? a.levels[s] : 255u);
+#pragma unroll
+                for (int q = 0; q < 3; q++) ch[q] = (ch[q] * (D - al) + (unsigned long long)a.colours[3 * s + q] * al + D / 2) / D;
+            }
+            if ((a.flags & CV_OUTLINE) && a.outline[bp[j]]) {
+                const int s = a.labels[bp[j]];
+#pragma unroll
+                for (int q = 0; q < 3; q++) ch[q] = a.colours[3 * s + q];
+            }
+        }
+        unsigned b = (unsigned)ch[0];
+        if (a.flags & CV_WIRE) {
+            const unsigned wire = a.wire[p];
+            b = d_sat(b + (wire > 2u ? 256u : 128u * wire));
+        }
+        sh.px[r - r0][c - c0] = b | ((unsigned)ch[1] << 8) | ((unsigned)ch[2] << 16);
+    }
+    __syncthreads();
+    // the strip's bytes of row r: [3 (r W + c0), + 3 wv); whole dwords inside them as dwords, the ends byte by byte
+    const int wv = min(CV_W, a.W - c0), hv = min(CV_H, a.H - r0), nb = 3 * wv;
+    for (int i = tid; i < hv * CV_ROW_WORDS; i += 256) {
+        const int rr = i / CV_ROW_WORDS, k = i - rr * CV_ROW_WORDS;
+        const size_t b0 = 3 * ((size_t)(r0 + rr) * a.W + c0);
+        const size_t start = ((b0 >> 2) + k) << 2;
+        if (start >= b0 + nb) continue;
+        unsigned v = 0, in = 0;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const long long rel = (long long)(start + q) - (long long)b0;
+            if (rel < 0 || rel >= nb) continue;
+            const int pi = (int)rel / 3, cq = (int)rel - 3 * pi;
+            v |= ((sh.px[rr][pi] >> (8 * cq)) & 255u) << (8 * q);
+            in |= 1u << q;
+        }
+        if (in == 15u) *(unsigned *)(a.out + start) = v;
+        else
+            for (int q = 0; q < 4; q++)
+                if ((in >> q) & 1u) a.out[start + q] = (uint8_t)(v >> (8 * q));
+    }
+}
+
+// The outline plane of layer 0, once per hm_view_set_cells: a body pixel with label s >= 0 is an outline pixel when one
+// of its four neighbours has another label; a neighbour off the frame counts as another.
+__global__ __launch_bounds__(256) void k_view_cell_outline(const int *__restrict__ lab, int W, int H, uint8_t *__restrict__ out)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= W * H) return;
+    const int r = p / W, c = p - r * W, s = lab[p];
+    out[p] = s >= 0 && (c == 0 || lab[p - 1] != s || c == W - 1 || lab[p + 1] != s || r == 0 || lab[p - W] != s || r == H - 1 ||
+                        lab[p + W] != s);
+}
+
+// The markers (reference synth.py:268-279, cv2.circle filled): point i at ((int)x, (int)y), truncated as C does, the pixels
+// with dx^2 + dy^2 <= radius^2 in integers in its colour, pixels off the frame left out; a point that is not finite or
+// beyond +-2^20 px is skipped.  A later point wins over an earlier one: one wave per point, all in one launch, and a pixel
+// that a later point covers as well is left to that point -- every pixel has one writer, whatever order the waves run in.
+__global__ __launch_bounds__(256) void k_view_cell_marks(int W, int H, int P, int radius, const double *__restrict__ pts,
+                                                         const uint8_t *__restrict__ col, uint8_t *__restrict__ out)
+{
+    const int i = blockIdx.x * (256 / VIEW_SEG_WAVE) + threadIdx.x / VIEW_SEG_WAVE;
+    const int lane = threadIdx.x % VIEW_SEG_WAVE;
+    if (i >= P) return;
+    const double x = pts[2 * i], y = pts[2 * i + 1];
+    if (!(d_coord_ok(x) && d_coord_ok(y))) return;
+    const long long cx = (long long)x, cy = (long long)y, R = radius, R2 = R * R;
+    const long long xa = max(cx - R, 0ll), xb = min(cx + R, (long long)W - 1), ya = max(cy - R, 0ll), yb = min(cy + R, (long long)H - 1);
+    if (xa > xb || ya > yb) return;
+    const long long bw = xb - xa + 1, n = bw * (yb - ya + 1);
+    for (long long k = lane; k < n; k += VIEW_SEG_WAVE) {
+        const long long py = ya + k / bw, px = xa + k % bw;
+        if ((px - cx) * (px - cx) + (py - cy) * (py - cy) > R2) continue;
+        bool later = false;
+        for (int j = i + 1; j < P && !later; j++) {
+            const double xj = pts[2 * j], yj = pts[2 * j + 1];
+            if (!(d_coord_ok(xj) && d_coord_ok(yj))) continue;
+            const long long dx = px - (long long)xj, dy = py - (long long)yj;
+            later = dx * dx + dy * dy <= R2;
+        }
+        if (later) continue;
+        const size_t o = 3 * ((size_t)py * W + (size_t)px);
+        out[o] = col[3 * i]; out[o + 1] = col[3 * i + 1]; out[o + 2] = col[3 * i + 2];
+    }
 }
 
 // ---- the flow tool's preview: frame blended with the flow in the Middlebury colour code ------------------------------

@@ -335,13 +335,23 @@ class VideoTap:
 
     def frame(self, X):
         """Queue the overlay of state X as the next video frame."""
+        self.push(lambda d, stream: self.r.view_dev(X, "overlay", d, stream))
+
+    def push(self, queue_view):
+        """Queue the next video frame: queue_view(d_out, stream) queues a view of the renderer into the device slot d_out
+        (W*H*3 bytes) and makes `stream` wait for it, as Renderer.view_dev does."""
         if self._error is not None:
             raise self._error
         self._free.acquire()
         s = self._next % self.slots
         self._next += 1
         d = self._dev[s].ptr
-        self.r.view_dev(X, "overlay", d, self._stream)
+        try:
+            queue_view(d, self._stream)
+        except Exception:
+            self._next -= 1
+            self._free.release()
+            raise
         _lib.check(_lib.lib().hm_dev_download_async(self.device, self._pin.value + s * self.n, d, self.n, self._stream),
                    "hm_dev_download_async")
         self._q.put(s)

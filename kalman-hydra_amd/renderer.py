@@ -172,6 +172,69 @@ class Renderer:
                    "hm_view_forces")
         return out
 
+    # -- the cell view (hm_view_set_cells, hm_view_cells*; hydra_mi.cellview) ------------------------------
+    def view_set_cells(self, labels, weights=None, colours=None):
+        """The cells of the cell view, in body coordinates: labels (n_layers, H, W) or (H, W) int32, -1: none (None
+        clears them); weights: the same shape, uint16 (None: 65535 everywhere); colours (L, 3) uint8, B G R, one per
+        label.  They stay until set again."""
+        self._cells_L = 0
+        if labels is None:
+            _lib.check(_lib.lib().hm_view_set_cells(self._h, 0, None, None, 0, None), "hm_view_set_cells")
+            return
+        lab = np.ascontiguousarray(labels, np.int32)
+        lab = lab[None] if lab.ndim == 2 else lab
+        if lab.ndim != 3 or lab.shape[1:] != (self.ny, self.nx):
+            raise ValueError("label planes of shape %r for %dx%d frames" % (lab.shape, self.nx, self.ny))
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.uint16).reshape(lab.shape)
+        col = np.ascontiguousarray(colours, np.uint8).reshape(-1, 3)
+        _lib.check(_lib.lib().hm_view_set_cells(self._h, int(lab.shape[0]), _lib.ptr(lab), _lib.ptr(w), int(col.shape[0]),
+                                                _lib.ptr(col)), "hm_view_set_cells")
+        self._cells_L = int(col.shape[0])
+
+    def _view_cells_args(self, X, levels, outline, wire, points, point_colours, point_radius):
+        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+        if x.shape[0] < 2 * self.n:
+            raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
+        lv = None
+        if levels is not None:
+            lv = np.ascontiguousarray(levels, np.uint8).reshape(-1)
+            if lv.shape[0] != getattr(self, "_cells_L", 0):    # (the library reads L bytes there)
+                raise ValueError("%d levels for %d cells" % (lv.shape[0], getattr(self, "_cells_L", 0)))
+        pts = pc = None
+        P = 0
+        if points is not None and np.size(points):
+            pts = np.ascontiguousarray(points, np.float64).reshape(-1, 2)
+            P = int(pts.shape[0])
+            pc = np.ascontiguousarray(point_colours, np.uint8).reshape(-1, 3)
+            if pc.shape[0] != P:
+                raise ValueError("%d colours for %d points" % (pc.shape[0], P))
+        flags = (1 if outline else 0) | (2 if wire else 0)
+        return x, lv, flags, P, pts, pc, int(point_radius)
+
+    def view_cells(self, X, frame, levels=None, outline=True, wire=False, points=None, point_colours=None, point_radius=2):
+        """hm_view_cells: the cells set by view_set_cells and the markers `points` (P, 2) image coordinates, colours
+        (P, 3) B G R) painted onto the gray frame (H, W) uint8 at state X -> (H, W, 3) uint8, B G R.  levels: (L,) uint8,
+        the activity of every cell in this frame (None: 255)."""
+        x, lv, flags, P, pts, pc, rad = self._view_cells_args(X, levels, outline, wire, points, point_colours, point_radius)
+        f = np.ascontiguousarray(frame, np.uint8)
+        if f.shape != (self.ny, self.nx):
+            raise ValueError("frame of shape %r for %dx%d frames" % (f.shape, self.nx, self.ny))
+        out = np.empty((self.ny, self.nx, 3), np.uint8)
+        _lib.check(_lib.lib().hm_view_cells(self._h, _lib.ptr(x), _lib.ptr(f), _lib.ptr(lv), flags, P, _lib.ptr(pts), _lib.ptr(pc),
+                                            rad, _lib.ptr(out)), "hm_view_cells")
+        return out
+
+    def view_cells_dev(self, X, d_frame, d_out, levels=None, outline=True, wire=False, points=None, point_colours=None,
+                       point_radius=2, stream=None):
+        """hm_view_cells_dev: the same queued on the handle's stream, frame (W*H bytes) and output (W*H*3 bytes) device
+        addresses; it does not wait, and the host arrays may be overwritten at once; `stream` waits for it on the device."""
+        x, lv, flags, P, pts, pc, rad = self._view_cells_args(X, levels, outline, wire, points, point_colours, point_radius)
+        _lib.check(_lib.lib().hm_view_cells_dev(self._h, _lib.ptr(x), ctypes.c_void_p(int(d_frame)), _lib.ptr(lv), flags, P,
+                                                _lib.ptr(pts), _lib.ptr(pc), rad, ctypes.c_void_p(int(d_out)), stream),
+                   "hm_view_cells_dev")
+
     # -- the body-frame readout (hm_body_*; hydra_mi.body) ------------------------------------------------
     def body_map(self):
         """-> (triangle per pixel (H, W) int32, -1 outside the mesh; pixels per triangle (T,) uint32) at X = uv."""

@@ -48,6 +48,12 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
                      diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
                      memory per frame; a video beyond --smooth-max-gb fails before tracking starts.
+    --cells-video OUT.avi  after tracking: the cells on the moving animal (hydra_mi.cellview) -- every raw frame with the
+                     demixed shapes (--demix) or the ROIs (--rois) of the points blended in by their dF/F of that frame,
+                     outlined, and a marker on every tracked point; with --points or --find-points alone the markers only.
+                     Needs one of --points, --find-points, --rois, --demix.  Drawn at the smoothed states Xs with
+                     --smooth, else at the filtered ones (--cells-video-states filtered|smoothed overrides).  One more
+                     pass over the frames of the input video.
 """
 import argparse
 import os
@@ -56,6 +62,7 @@ import sys
 import numpy as np
 
 import hydra_mi  # noqa: F401
+from hydra_mi import cellview
 from hydra_mi import kalman
 from hydra_mi import demix
 from hydra_mi import roi
@@ -99,7 +106,18 @@ def main(argv=None):
     parser.add_argument("--demix-iters", default=6, type=int, help="rounds of shapes given traces, traces given shapes")
     parser.add_argument("--smooth", action="store_true", help="smooth the track backward: Xs, Xs_std in the states file")
     parser.add_argument("--smooth-max-gb", default=8.0, type=float, help="device memory the smoother may take (GiB)")
+    parser.add_argument("--cells-video", default=None, metavar="OUT.avi",
+                        help="after tracking, write the cells and tracked points painted onto the video (.avi); needs one "
+                             "of --points, --find-points, --rois, --demix; one more pass over the frames of the input video")
+    parser.add_argument("--cells-video-states", default=None, choices=("filtered", "smoothed"),
+                        help="the states the cells video is drawn at (default: smoothed with --smooth, else filtered)")
     args = parser.parse_args(argv)
+    if args.cells_video is not None and args.points is None and args.find_points is None:
+        parser.error("--cells-video draws cells or points: it needs one of --points, --find-points, --rois, --demix")
+    if args.cells_video_states is not None and args.cells_video is None:
+        parser.error("--cells-video-states goes with --cells-video")
+    if args.cells_video_states == "smoothed" and not args.smooth:
+        parser.error("--cells-video-states smoothed needs --smooth")
     if args.find_points is not None:
         if args.points is not None:
             parser.error("--find-points finds the points itself: not together with --points")
@@ -206,6 +224,7 @@ def main(argv=None):
         video.close()
         print("Overlay video: %d frames in %s" % (video.frames, args.fn_out))
     extra = {}
+    cv_cells = cv_levels = cv_points = None          # what --cells-video draws
     if body is not None:
         res = body.results()
         extra = {"tri_means": res["tri_means"], "tri_counts": res["tri_counts"]}
@@ -233,6 +252,8 @@ def main(argv=None):
         if args.points_out is not None:
             write_points_csv(args.points_out, found)
             print("Points found: %s" % args.points_out)
+    if args.cells_video is not None:
+        cv_points = found if find else points
     if body is not None and body.keep:
         pts = found if find else points
         inside = np.flatnonzero(body.locate(pts)[0] >= 0)
@@ -250,6 +271,18 @@ def main(argv=None):
                          roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
             print("ROIs: %d cells, %d..%d pixels, %d kept their disc" % (len(inside), e["roi_counts"].min(),
                                                                           e["roi_counts"].max(), e["seed_fallback"].sum()))
+            if args.cells_video is not None:
+                if args.demix:
+                    lab, w, dropped = cellview.layers_from_shapes(e["shapes_q"], roi.seeds_of(pts[inside]),
+                                                                  (e["shapes_q"].shape[1] - 1) // 2, (H, W))
+                    if dropped:
+                        print("Cells video: %d (pixel, cell) entries beyond two cells per pixel are not drawn" % dropped)
+                    cv_cells, cv_levels = (lab, w), cellview.levels(e["dff_demixed"])
+                else:
+                    cv_cells, cv_levels = cellview.layers_from_labels(e["roi_labels"]), cellview.levels(e["dff"])
+                cv_points = pts[inside]                            # (cell s and marker s share a colour)
+                if int(cv_cells[0].max()) + 1 != len(inside):      # (the last cells own no pixel: no level for them)
+                    cv_levels = cv_levels[:, :int(cv_cells[0].max()) + 1]
         kf.state.renderer.body_rec_end()
     if reg_video is not None:
         reg_video.close()
@@ -262,6 +295,14 @@ def main(argv=None):
             extra.update(Xs=np.zeros((0, 4 * kf.N)), Xs_std=np.zeros((0, 4 * kf.N)))
         sm.close()
         print("Smoothed track: Xs, Xs_std (%d frames)" % len(states))
+    if args.cells_video is not None and len(states):
+        use = args.cells_video_states or ("smoothed" if args.smooth else "filtered")
+        cv_states = extra["Xs"] if use == "smoothed" else states
+        if cv_cells is not None and int(cv_cells[0].max()) < 0:
+            cv_cells = cv_levels = None
+        n_cv = cellview.write_video(kf, cv_states, capture.frames[1:1 + len(states)], args.cells_video, cells=cv_cells,
+                                    levels=cv_levels, points=cv_points)       # state k: frame k + 1
+        print("Cells video: %d frames (%s states) in %s" % (n_cv, use, args.cells_video))
     np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri, **extra)
     print("Finished: %d frames, states in %s" % (len(states), args.fn_out))
     return 0
