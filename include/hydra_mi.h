@@ -600,6 +600,38 @@ int hm_body_rec_seed_sums(hm_ctx_t h, int P, const int32_t *seeds, double r_disc
 int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds, int R, const uint16_t *weights, uint64_t *out);
 int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seeds, int R, const int32_t *q, int64_t *out);
 
+/* Residual motion of the kept registered video: the shift of every patch of every frame found against a template
+ * and taken out of the record in place (hydra_mi/stabilize.py).  Waiting, errors and state are
+ * those of hm_body_rec_seed_sums: the calls wait for the warps queued so far and for their results, fail with
+ * HM_ERR_STATE before begin and while no frame is recorded, and with HM_ERR_ARG and the offending numbers in
+ * hm_last_error for an argument out of range.
+ * The patch grid: B is 4..64 and S is 0..8.  Patches of B x B body pixels tile the record's box (the bounding box of
+ * the body map) from its top-left corner; the last column and row of patches may be narrower; patches are indexed
+ * row-major.  The core of a patch is its pixels p for which every p + d, |dx| <= S and |dy| <= S, is on the frame and
+ * in the map: every shift therefore sums over the same n pixels.  n may be 0; then all of that patch's sums are 0.
+ *   match       `template` is W*H bytes in body coordinates.  Outputs are uint32, indexed
+ *               [frame - k0][patch][(dy + S)(2S + 1) + dx + S], over frames k0 .. k0 + n_frames - 1:
+ *                 A  = sum over the core of v_k(p + d) t(p),
+ *                 V1 = sum over the core of v_k(p + d),
+ *                 V2 = sum over the core of v_k(p + d)^2;
+ *               n_core is per patch.  Any output may be NULL.  All sums are exact: 255^2 64^2 < 2^32.  The frames
+ *               are split over the grid in runs of hm_ctx_tune "rec_tp_frames"; one slot per (frame, patch, shift),
+ *               no atomics: the result does not depend on order.
+ *   frame_sums  out[p] = sum over the frames k0 .. k0 + n_frames - 1 of v_k(p + d_k,patch(p)) as uint32, W*H values.
+ *               Off the map the value is 0.  A source pixel off the box or the map counts 0.  `shifts` are int8, laid
+ *               out [frame - k0][patch][2] as (dx, dy), each within +-16.  NULL means no shift, and B is then unused.
+ *               Refused with HM_ERR_ARG when n_frames 255 could pass 2^32.
+ *   shift       `shifts` covers all F frames.  The record is rewritten in place: v'_k(p) = v_k(p + d_k,patch(p)) where
+ *               p and p + d are both in the box and in the map, else 0; the result is as if every frame were gathered
+ *               from its own unshifted self (a scratch buffer of at most one chunk holds the frames as they were,
+ *               freed when the call returns, with an error too).  Every hm_body_rec_* call afterwards, fetch
+ *               included, sees the shifted frames.  Calling it again shifts what is there: NOT reversible (what a
+ *               shift moves off the box or the map is lost).  Nothing else on the handle changes. */
+int hm_body_rec_match(hm_ctx_t h, int k0, int n_frames, int B, int S, const uint8_t *tmpl, uint32_t *n_core, uint32_t *A,
+                      uint32_t *V1, uint32_t *V2);
+int hm_body_rec_frame_sums(hm_ctx_t h, int k0, int n_frames, int B, const int8_t *shifts, uint32_t *out);
+int hm_body_rec_shift(hm_ctx_t h, int B, const int8_t *shifts);
+
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
  * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the

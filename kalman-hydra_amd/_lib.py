@@ -154,6 +154,10 @@ SIGNATURES = {
                                              ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "hm_body_rec_weighted_sums": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_body_rec_trace_products": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "hm_body_rec_match": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp]),
+    "hm_body_rec_frame_sums": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "hm_body_rec_shift": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "hm_flow_preview": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                        c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_avi_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,

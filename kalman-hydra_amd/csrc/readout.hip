@@ -1,12 +1,13 @@
 // The readout of a filter handle: views (hm_view*), the body-frame readout and its statistics (hm_body_*, hm_body_stats_*),
 // the registered video kept on the device with its reductions (hm_body_rec_*), and the flow tool's preview.  Host
-// orchestration and C-ABI (include/hydra_mi.h); the kernels are in view_kernels.h, body_kernels.h and roi_kernels.h, which
-// this translation unit alone compiles.  Of the handle (ctx.h) it uses its own three members -- view, body, rec -- and reads
+// orchestration and C-ABI (include/hydra_mi.h); the kernels are in view_kernels.h, body_kernels.h, roi_kernels.h and
+// stab_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses its own three members -- view, body, rec -- and reads
 // W, H, N, T, device, own, stream, the mesh (d_tri, d_uv, d_tex) and, for the overlay view, have_tex, have_obs and o_yim.
 #include "ctx.h"
 #include "view_kernels.h"
 #include "body_kernels.h"
 #include "roi_kernels.h"
+#include "stab_kernels.h"
 #include <algorithm>
 #include <cstring>
 
@@ -630,6 +631,7 @@ static int body_rec_drop(hm_ctx *h)
     h->rec.chunks.clear();
     if (e == hipSuccess) e = h->own.free(&h->rec.tab);
     if (e == hipSuccess) e = h->own.free(&h->rec.tmp);
+    if (e == hipSuccess) e = h->own.free(&h->rec.scr);
     if (e == hipSuccess && !h->body.stats_on) e = h->own.free(&h->body.reg);
     HM_HIP(e);
     return HM_OK;
@@ -957,6 +959,169 @@ extern "C" int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seed
     HM_HIP(hipGetLastError());
     HM_HIP(hipMemcpyAsync(out, g.out, P * nw * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// ---- residual motion of the record: patch sums, sums at given shifts, the shift in place (stab_kernels.h) -----------
+#define STAB_SCRATCH_BYTES ((size_t)16 << 20)
+
+// the core of every patch on the host: core[y * pitch + x] = 1 where every box pixel within S of (x, y) is in the map
+// (two passes of prefix sums: rows, then columns); n_core: per patch
+static void stab_core(const hm_ctx *h, int B, int S, std::vector<uint8_t> &core, std::vector<uint32_t> &n_core)
+{
+    const RecBox &b = h->rec.box;
+    const int npx = hm_cdiv(b.bw, B), npy = hm_cdiv(b.bh, B), n1 = 2 * S + 1;
+    core.assign((size_t)b.pitch * b.bh, 0);
+    n_core.assign((size_t)npx * npy, 0);
+    std::vector<uint8_t> hor((size_t)b.bw * b.bh, 0);
+    std::vector<int> pre((size_t)std::max(b.bw, b.bh) + 1);
+    for (int y = 0; y < b.bh; y++) {
+        pre[0] = 0;
+        for (int x = 0; x < b.bw; x++) pre[x + 1] = pre[x] + (h->body.h_tri[(size_t)(b.r0 + y) * h->W + b.c0 + x] >= 0);
+        for (int x = S; x + S < b.bw; x++) hor[(size_t)y * b.bw + x] = pre[x + S + 1] - pre[x - S] == n1;
+    }
+    for (int x = 0; x < b.bw; x++) {
+        pre[0] = 0;
+        for (int y = 0; y < b.bh; y++) pre[y + 1] = pre[y] + hor[(size_t)y * b.bw + x];
+        for (int y = S; y + S < b.bh; y++)
+            if (pre[y + S + 1] - pre[y - S] == n1) {
+                core[(size_t)y * b.pitch + x] = 1;
+                n_core[(size_t)(y / B) * npx + x / B]++;
+            }
+    }
+}
+
+extern "C" int hm_body_rec_match(hm_ctx_t h, int k0, int n_frames, int B, int S, const uint8_t *tmpl, uint32_t *n_core,
+                                 uint32_t *A, uint32_t *V1, uint32_t *V2)
+{
+    HM_ARG(B >= STAB_BMIN && B <= STAB_BMAX, "hm_body_rec_match: patch size %d outside %d..%d", B, STAB_BMIN, STAB_BMAX);
+    HM_ARG(S >= 0 && S <= STAB_SMAX, "hm_body_rec_match: search radius %d outside 0..%d", S, STAB_SMAX);
+    HM_ARG(h && tmpl, "hm_body_rec_match: NULL handle or template");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_match");
+    if (rc) return rc;
+    HM_ARG(k0 >= 0 && n_frames >= 0 && k0 <= h->rec.frames && n_frames <= h->rec.frames - k0,
+           "hm_body_rec_match: frames %d .. %d of a record of %d", k0, k0 + n_frames - 1, h->rec.frames);
+    const RecBox &b = h->rec.box;
+    const int npx = hm_cdiv(b.bw, B), np = npx * hm_cdiv(b.bh, B), nsh = (2 * S + 1) * (2 * S + 1);
+    std::vector<uint8_t> core;
+    std::vector<uint32_t> cnt;
+    stab_core(h, B, S, core, cnt);
+    if (n_core) memcpy(n_core, cnt.data(), (size_t)np * sizeof(uint32_t));
+    if (n_frames == 0 || !(A || V1 || V2)) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const size_t n = (size_t)h->W * h->H, no = (size_t)n_frames * np * nsh;
+    StabMatch g;
+    uint8_t *d_tmpl = nullptr, *d_core = nullptr;
+    rc = body_rec_carve(h, [&](RecCarve &cv) {
+        d_tmpl = cv.take<uint8_t>(n);
+        d_core = cv.take<uint8_t>(core.size());
+        g.A = A ? cv.take<unsigned>(no) : nullptr;
+        g.V1 = V1 ? cv.take<unsigned>(no) : nullptr;
+        g.V2 = V2 ? cv.take<unsigned>(no) : nullptr;
+    });
+    if (rc) return rc;
+    HM_HIP(hipMemcpyAsync(d_tmpl, tmpl, n, hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_core, core.data(), core.size(), hipMemcpyHostToDevice, h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.W = h->W; g.k0 = k0; g.F = n_frames; g.tpf = h->rec.tp_frames;
+    g.B = B; g.S = S; g.npx = npx; g.np = np; g.tmpl = d_tmpl; g.core = d_core;
+    const int runs = hm_cdiv(n_frames, g.tpf);
+    hipLaunchKernelGGL(k_stab_match, dim3(np, std::min(runs, 65535)), dim3(256), stab_lds_bytes(B, S), h->stream, g);
+    HM_HIP(hipGetLastError());
+    if (A) HM_HIP(hipMemcpyAsync(A, g.A, no * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (V1) HM_HIP(hipMemcpyAsync(V1, g.V1, no * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (V2) HM_HIP(hipMemcpyAsync(V2, g.V2, no * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// every shift of `count` (dx, dy) pairs within +-STAB_DMAX
+static int stab_shifts_ok(const int8_t *shifts, size_t count, int np, const char *who)
+{
+    for (size_t i = 0; i < 2 * count; i++)
+        HM_ARG(shifts[i] >= -STAB_DMAX && shifts[i] <= STAB_DMAX, "%s: shift %d (%s of patch %zu, frame %zu of those given) outside -%d..%d",
+               who, (int)shifts[i], i & 1 ? "dy" : "dx", (i / 2) % (size_t)np, (i / 2) / (size_t)np, STAB_DMAX, STAB_DMAX);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_frame_sums(hm_ctx_t h, int k0, int n_frames, int B, const int8_t *shifts, uint32_t *out)
+{
+    HM_ARG(!shifts || (B >= STAB_BMIN && B <= STAB_BMAX), "hm_body_rec_frame_sums: patch size %d outside %d..%d", B, STAB_BMIN,
+           STAB_BMAX);
+    HM_ARG((long long)n_frames * 255 < (1ll << 32), "hm_body_rec_frame_sums: %d frames x 255 could pass 2^32", n_frames);
+    HM_ARG(h && out, "hm_body_rec_frame_sums: NULL handle or output");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_frame_sums");
+    if (rc) return rc;
+    HM_ARG(k0 >= 0 && n_frames >= 0 && k0 <= h->rec.frames && n_frames <= h->rec.frames - k0,
+           "hm_body_rec_frame_sums: frames %d .. %d of a record of %d", k0, k0 + n_frames - 1, h->rec.frames);
+    const RecBox &b = h->rec.box;
+    StabSum g;
+    g.B = shifts ? B : 1;
+    g.npx = hm_cdiv(b.bw, g.B); g.np = g.npx * hm_cdiv(b.bh, g.B);
+    const size_t n = (size_t)h->W * h->H, ns = shifts ? (size_t)n_frames * g.np : 0;
+    if (shifts) {
+        rc = stab_shifts_ok(shifts, ns, g.np, "hm_body_rec_frame_sums");
+        if (rc) return rc;
+    }
+    int8_t *d_sh = nullptr;
+    rc = body_rec_carve(h, [&](RecCarve &cv) {
+        g.out = cv.take<unsigned>(n);
+        d_sh = cv.take<int8_t>(2 * ns);
+    });
+    if (rc) return rc;
+    if (ns) HM_HIP(hipMemcpyAsync(d_sh, shifts, 2 * ns, hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(g.out, 0, n * sizeof(unsigned), h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.W = h->W; g.k0 = k0; g.F = n_frames;
+    g.tri_of = h->body.tri; g.shifts = ns ? d_sh : nullptr;
+    hipLaunchKernelGGL(k_stab_frame_sums, dim3(hm_cdiv(b.bw * b.bh, 256)), dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, g.out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_shift(hm_ctx_t h, int B, const int8_t *shifts)
+{
+    HM_ARG(B >= STAB_BMIN && B <= STAB_BMAX, "hm_body_rec_shift: patch size %d outside %d..%d", B, STAB_BMIN, STAB_BMAX);
+    HM_ARG(h && shifts, "hm_body_rec_shift: NULL handle or shifts");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_shift");
+    if (rc) return rc;
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames;
+    StabShift g;
+    g.b = b; g.W = h->W; g.B = B; g.npx = hm_cdiv(b.bw, B); g.np = g.npx * hm_cdiv(b.bh, B); g.tri_of = h->body.tri;
+    const size_t ns = (size_t)F * g.np;
+    rc = stab_shifts_ok(shifts, ns, g.np, "hm_body_rec_shift");
+    if (rc) return rc;
+    int8_t *d_sh = nullptr;
+    rc = body_rec_carve(h, [&](RecCarve &cv) { d_sh = cv.take<int8_t>(2 * ns); });
+    if (rc) return rc;
+    // runs of frames within a chunk: copied aside as they are, then gathered back into the record
+    const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(b.fpc, F), STAB_SCRATCH_BYTES / b.fs));
+    HM_HIP(h->own.grow(&h->rec.scr, (size_t)per * b.fs));
+    auto run = [&]() -> int {
+        HM_HIP(hipMemcpyAsync(d_sh, shifts, 2 * ns, hipMemcpyHostToDevice, h->stream));
+        const int blocks = hm_cdiv((b.pitch >> 2) * b.bh, 256);
+        for (int k = 0; k < F;) {
+            const int ch = k / b.fpc, m = std::min(per, std::min(F, (ch + 1) * b.fpc) - k);
+            uint8_t *dst = h->rec.chunks[ch] + (size_t)(k - ch * b.fpc) * b.fs;
+            HM_HIP(hipMemcpyAsync(h->rec.scr, dst, (size_t)m * b.fs, hipMemcpyDeviceToDevice, h->stream));
+            g.frames = m; g.shifts = d_sh + 2 * (size_t)k * g.np; g.src = h->rec.scr; g.dst = dst;
+            hipLaunchKernelGGL(k_stab_shift, dim3(blocks, std::min(m, 65535)), dim3(256), 0, h->stream, g);
+            HM_HIP(hipGetLastError());
+            k += m;
+        }
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    };
+    rc = run();
+    const hipError_t fe = h->own.free(&h->rec.scr);           // on the error paths too (the first error is the one reported)
+    if (rc) return rc;
+    HM_HIP(fe);
     return HM_OK;
 }
 

@@ -416,6 +416,73 @@ class Renderer:
                    "hm_body_rec_trace_products")
         return out
 
+    # -- residual motion of the record (hm_body_rec_match / _frame_sums / _shift; hydra_mi.stabilize) --
+    def body_rec_patches(self, B):
+        """-> (patches per row, patch rows) of the grid of B x B patches over the record's box (the bounding box of the
+        body map)"""
+        box = getattr(self, "_body_rec_box", None)
+        if box is None:                                          # (the map is the mesh at X = uv: fixed for the handle)
+            m = self.body_map()[0] >= 0
+            rows, cols = np.flatnonzero(m.any(1)), np.flatnonzero(m.any(0))
+            box = (int(cols[-1] - cols[0]) + 1, int(rows[-1] - rows[0]) + 1) if m.any() else (1, 1)
+            self._body_rec_box = box
+        B = int(B)
+        return (box[0] + B - 1) // B, (box[1] + B - 1) // B
+
+    def body_rec_match(self, template, B, S, k0=0, n=None, want=("A", "V1", "V2")):
+        """hm_body_rec_match: template (H, W) uint8 in body coordinates -> dict: n_core (patches,) uint32 and, of A, V1,
+        V2, those in `want` as (n, patches, (2S+1)^2) uint32: the sums over every patch's core of v(p + d) t(p),
+        v(p + d) and v(p + d)^2 for the frames k0 .. k0 + n - 1 (default: all from k0)."""
+        t = np.ascontiguousarray(template, np.uint8)
+        if t.shape != (self.ny, self.nx):
+            raise ValueError("template of shape %r for %dx%d frames" % (t.shape, self.nx, self.ny))
+        B, S = int(B), int(S)
+        if not (4 <= B <= 64 and 0 <= S <= 8):                   # (the call says so with its numbers; no grid to size for)
+            _lib.check(_lib.lib().hm_body_rec_match(self._h, int(k0), 0, B, S, _lib.ptr(t), None, None, None, None),
+                       "hm_body_rec_match")
+        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        npx, npy = self.body_rec_patches(B)
+        o = dict(n_core=np.empty(npx * npy, np.uint32))
+        for key in want:
+            o[key] = np.empty((max(n, 0), npx * npy, (2 * S + 1) ** 2), np.uint32)
+        _lib.check(_lib.lib().hm_body_rec_match(self._h, int(k0), n, B, S, _lib.ptr(t), _lib.ptr(o["n_core"]),
+                                                *[_lib.ptr(o.get(key)) for key in ("A", "V1", "V2")]), "hm_body_rec_match")
+        return o
+
+    def _body_shifts(self, shifts, B, who):
+        sh = np.asarray(shifts)
+        if sh.dtype != np.int8 or sh.ndim != 3 or sh.shape[2] != 2:
+            raise ValueError("%s: shifts %s of shape %r (need int8, (frames, patches, 2))" % (who, sh.dtype, sh.shape))
+        if 4 <= int(B) <= 64:
+            npx, npy = self.body_rec_patches(B)
+            if sh.shape[1] != npx * npy:
+                raise ValueError("%s: shifts for %d patches, the grid of %d px patches has %d" % (who, sh.shape[1], int(B),
+                                                                                                  npx * npy))
+        return np.ascontiguousarray(sh)
+
+    def body_rec_frame_sums(self, shifts=None, B=16, k0=0, n=None):
+        """hm_body_rec_frame_sums: -> (H, W) uint32, the sum over the frames k0 .. k0 + n - 1 of every map pixel taken at
+        its patch's shift of that frame; shifts (n, patches, 2) int8 (dx, dy), None: no shift."""
+        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        sh = None
+        if shifts is not None:
+            sh = self._body_shifts(shifts, B, "body_rec_frame_sums")
+            if sh.shape[0] != n:
+                raise ValueError("body_rec_frame_sums: shifts of %d frames for %d" % (sh.shape[0], n))
+        out = np.empty((self.ny, self.nx), np.uint32)
+        _lib.check(_lib.lib().hm_body_rec_frame_sums(self._h, int(k0), n, int(B), _lib.ptr(sh), _lib.ptr(out)),
+                   "hm_body_rec_frame_sums")
+        return out
+
+    def body_rec_shift(self, shifts, B):
+        """hm_body_rec_shift: rewrite the record in place, every map pixel of every frame taken at its patch's shift;
+        shifts (F, patches, 2) int8 (dx, dy) for all recorded frames.  Not reversible."""
+        sh = self._body_shifts(shifts, B, "body_rec_shift")
+        F = self.body_rec_count()
+        if F and sh.shape[0] != F:                               # (F 0: the call says why)
+            raise ValueError("body_rec_shift: shifts of %d frames for a record of %d" % (sh.shape[0], F))
+        _lib.check(_lib.lib().hm_body_rec_shift(self._h, int(B), _lib.ptr(sh)), "hm_body_rec_shift")
+
     def screenshot(self, saveall=True, basename="screenshot", X=None):
         """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask
         at state X (default: the vertex buffer) and returns the overlay.  Unlike the reference the names carry no

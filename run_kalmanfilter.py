@@ -44,6 +44,15 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
     --demix          --rois, and the overlapping cells demixed (hydra_mi.demix.extract: shapes and traces fitted in turn
                      to the kept video, --demix-iters rounds): demix_shapes (points x 17 x 17), demix_C, demix_dff
                      (frames x points), demix_change (the relative change of demix_C per round).
+    --stabilize      with --rois or --demix: before the cells are read out, take the residual motion out of the kept
+                     registered video (hydra_mi.stabilize): every patch of --stab-patch px (default 16) of every frame is
+                     matched against a template within +-(--stab-search) px (default 3) on the device and gathered at its best
+                     shift, --stab-passes times (default 1; from the second pass on the template is the mean of the
+                     stabilised frames).  The states file gets stab_shifts (frames x patches x 2, (dx, dy)), stab_score,
+                     stab_fallback (frames x patches).  Everything read from the kept record sees the stabilised frames:
+                     the roi_* and demix_* arrays and, with --find-points, point_means.  What is summed while tracking does
+                     not: tri_means, the summary images body_* and the points found in them, point_means of --points.
+                     --cells-video keeps drawing at the tracked states.
     --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
                      (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
                      diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
@@ -66,6 +75,7 @@ from hydra_mi import cellview
 from hydra_mi import kalman
 from hydra_mi import demix
 from hydra_mi import roi
+from hydra_mi import stabilize
 from hydra_mi.body import (BodyReadout, read_out, read_out_recorded, read_points_csv, record_bytes, write_points_csv,
                            write_points_txt)
 from hydra_mi.distmesh_dyn import DistMesh
@@ -104,6 +114,12 @@ def main(argv=None):
     parser.add_argument("--roi-alpha", default=0.7, type=float, help="share of the ring trace taken off the ROI trace")
     parser.add_argument("--demix", action="store_true", help="--rois, and overlapping cells demixed (demix_* arrays)")
     parser.add_argument("--demix-iters", default=6, type=int, help="rounds of shapes given traces, traces given shapes")
+    parser.add_argument("--stabilize", action="store_true",
+                        help="with --rois or --demix: stabilise the kept registered video before the cells are read out "
+                             "(stab_* arrays); --cells-video keeps drawing at the tracked states")
+    parser.add_argument("--stab-patch", default=16, type=int, help="edge of the patches that are matched (4..64 px)")
+    parser.add_argument("--stab-search", default=3, type=int, help="the shifts searched: +-N px (0..8)")
+    parser.add_argument("--stab-passes", default=1, type=int, help="passes of estimating the shifts")
     parser.add_argument("--smooth", action="store_true", help="smooth the track backward: Xs, Xs_std in the states file")
     parser.add_argument("--smooth-max-gb", default=8.0, type=float, help="device memory the smoother may take (GiB)")
     parser.add_argument("--cells-video", default=None, metavar="OUT.avi",
@@ -131,6 +147,11 @@ def main(argv=None):
             parser.error("--demix-iters needs at least one round")
     if args.rois and args.find_points is None and args.points is None:
         parser.error("--rois reads cells out: it needs --find-points or --points")
+    if args.stabilize:
+        if not args.rois:
+            parser.error("--stabilize works on the kept record: it needs --rois or --demix")
+        if not (4 <= args.stab_patch <= 64 and 0 <= args.stab_search <= 8 and args.stab_passes >= 1):
+            parser.error("--stabilize needs a --stab-patch in 4..64, a --stab-search in 0..8 and at least one pass")
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
 
@@ -165,8 +186,8 @@ def main(argv=None):
             probe = kf.state.renderer.body_map()[0]
             need = record_bytes(probe, max(capture.frames.shape[0] - 1, 1))
             if need > budget:
-                print("The registered video takes %d bytes on the device, --rois-max-gb allows %d: no ROIs, the disc "
-                      "read-out instead" % (need, budget))
+                print("The registered video takes %d bytes on the device, --rois-max-gb allows %d: no ROIs, %sthe disc "
+                      "read-out instead" % (need, budget, "no stabilisation, " if args.stabilize else ""))
                 keep = False
         body = BodyReadout(kf, points=points, point_radius=args.point_radius, video=reg_video, stats=find, keep=keep,
                            keep_bytes=budget)
@@ -233,6 +254,15 @@ def main(argv=None):
             fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
             write_points_txt(fn_pts, res["points"])
             print("Tracked points: %s" % fn_pts)
+    if args.stabilize and body is not None and body.keep and len(states):
+        # between tracking and everything that reads the kept record: the disc read-out of --find-points, roi.extract and
+        # demix.extract see the stabilised frames (what was summed while tracking -- tri_means, the summary images and the
+        # points found in them, point_means of --points -- saw the frames as the tracker registered them)
+        est = stabilize.stabilize(body, B=args.stab_patch, S=args.stab_search, passes=args.stab_passes)
+        extra.update(stab_shifts=est["shifts"], stab_score=est["score"], stab_fallback=est["fallback"])
+        print("Stabilised: %d patches of %d px, search %d, %d passes: %.1f %% fallbacks, mean |shift| %.3f px" % (
+            est["shifts"].shape[1], args.stab_patch, args.stab_search, args.stab_passes, 100.0 * est["fallback"].mean(),
+            np.abs(est["shifts"].astype(np.float64)).sum(2).mean()))
     if find:
         # the cells need the whole video and the traces need the cells: a second pass over the recorded states
         sm_img = body.summary()
