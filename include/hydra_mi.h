@@ -632,6 +632,43 @@ int hm_body_rec_match(hm_ctx_t h, int k0, int n_frames, int B, int S, const uint
 int hm_body_rec_frame_sums(hm_ctx_t h, int k0, int n_frames, int B, const int8_t *shifts, uint32_t *out);
 int hm_body_rec_shift(hm_ctx_t h, int B, const int8_t *shifts);
 
+/* The same residual motion taken out as a smooth sub-pixel shift field instead of one whole-pixel vector per patch
+ * (hydra_mi/stabilize.py mode="field"; tests/stabfield_ref.py restates it).  Exact integers
+ * throughout.  Waiting, state errors and argument errors are those of hm_body_rec_shift and hm_body_rec_frame_sums, with
+ * the offending numbers in hm_last_error: a patch size outside 4..64, a q outside +-256 (naming component, patch and
+ * frame), frames outside the record, a call before begin, a call on an empty record.
+ *   Sub-pixel estimate (host arithmetic on the match sums, in stabilize.py).  Per (frame, patch) and per axis, take s0,
+ *               the winning score, and s-, s+, the scores at the two neighbouring shifts along that axis.  The refinement
+ *               applies only when all of these hold: the winning shift is strictly inside the search on that axis
+ *               (|d| < S); both neighbours are valid; den = s- - 2 s0 + s+ < 0.  When it applies,
+ *               off = (s- - s+) / (2 den), clipped to +-0.5.  Otherwise off is 0.
+ *               q = 16 d + floor(16 off + 0.5) as int16, in 1/16 px.  A fallback patch has q = 0 and valid = 0.  Every
+ *               step is one binary64 operation in this order.
+ *   Field       Patch centres are where the patches measured.  For a box pixel at column x, per axis: u = 2x + 1 - B,
+ *               i = clamp(floor(u / 2B), 0, max(npx - 2, 0)), w1 = clamp(u - 2B i, 0, 2B), w0 = 2B - w1,
+ *               i1 = min(i + 1, npx - 1).  Rows are formed alike with npy.  The pixel sees the four patches
+ *               (iy|iy1, ix|ix1), each with weight wy wx valid(frame, patch).  Per component, num = sum w q and
+ *               den = sum w.  The shift is d(p) = floor((2 num + den) / (2 den)), floor division also for negative
+ *               numbers, and 0 when den = 0.  Inside the first and last half patch the field is constant.  An invalid
+ *               patch does not pull the field to zero: its neighbours fill it.  Magnitudes: w <= 4 B^2 = 16384,
+ *               |q| <= 256, four terms.  int32 is enough.
+ *   Sample      X = 16x + d_x(p), x0 = X >> 4 (arithmetic shift), fx = X & 15.  The y components are formed alike.
+ *               v'(p) = ((16 - fx)(16 - fy) v(x0, y0) + fx (16 - fy) v(x0 + 1, y0) + (16 - fx) fy v(x0, y0 + 1)
+ *                        + fx fy v(x0 + 1, y0 + 1) + 128) >> 8.
+ *               A source off the box counts 0.  Off the map the record already holds 0.  v' is written only where p is in
+ *               the map, and is 0 elsewhere, padding included.  With every q a multiple of 16 and every valid 1 inside
+ *               one patch, the sample reduces to the whole-pixel gather.
+ *   warp        `q` is int16 [frame][patch][2] as (dx, dy), each within +-256, for all F frames.  `valid` is uint8
+ *               [frame][patch].  The record is rewritten in place, every frame gathered from its own unwarped self (the
+ *               scratch buffer is hm_body_rec_shift's: at most 16 MiB, never more than a chunk, freed on every return
+ *               including errors).  Afterwards every hm_body_rec_* call, fetch included, sees the warped frames.  NOT
+ *               reversible.  Nothing else on the handle changes.  A refused warp changes nothing.
+ *   field_sums  out[p] = sum over the frames k0 .. k0 + n_frames - 1 of v'_k(p) at the field of each frame as uint32, W*H
+ *               values; `q` and `valid` are laid out [frame - k0][patch].  The template of pass p > 1 in field mode.
+ *               Refused with HM_ERR_ARG when n_frames 255 could pass 2^32. */
+int hm_body_rec_warp(hm_ctx_t h, int B, const int16_t *q, const uint8_t *valid);
+int hm_body_rec_field_sums(hm_ctx_t h, int k0, int n_frames, int B, const int16_t *q, const uint8_t *valid, uint32_t *out);
+
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
  * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the

@@ -158,6 +158,8 @@ SIGNATURES = {
                                          c_vp]),
     "hm_body_rec_frame_sums": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "hm_body_rec_shift": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
+    "hm_body_rec_warp": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp]),
+    "hm_body_rec_field_sums": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "hm_flow_preview": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                        c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_avi_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,

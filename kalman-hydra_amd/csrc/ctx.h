@@ -150,7 +150,7 @@ struct RecState {
     std::vector<uint8_t *> chunks;
     uint8_t **tab = nullptr;         // the chunks' addresses for the reductions
     uint8_t *tmp = nullptr;          // their arguments and results
-    uint8_t *scr = nullptr;          // hm_body_rec_shift: a run of frames as they were (freed when the call returns)
+    uint8_t *scr = nullptr;          // hm_body_rec_shift / _warp: a run of frames as they were (freed when the call returns)
 };
 
 struct hm_ctx {

@@ -962,7 +962,7 @@ extern "C" int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seed
     return HM_OK;
 }
 
-// ---- residual motion of the record: patch sums, sums at given shifts, the shift in place (stab_kernels.h) -----------
+// ---- residual motion of the record: patch sums, sums at given shifts, the shift in place, the smooth field (stab_kernels.h)
 #define STAB_SCRATCH_BYTES ((size_t)16 << 20)
 
 // the core of every patch on the host: core[y * pitch + x] = 1 where every box pixel within S of (x, y) is in the map
@@ -1112,6 +1112,97 @@ extern "C" int hm_body_rec_shift(hm_ctx_t h, int B, const int8_t *shifts)
             HM_HIP(hipMemcpyAsync(h->rec.scr, dst, (size_t)m * b.fs, hipMemcpyDeviceToDevice, h->stream));
             g.frames = m; g.shifts = d_sh + 2 * (size_t)k * g.np; g.src = h->rec.scr; g.dst = dst;
             hipLaunchKernelGGL(k_stab_shift, dim3(blocks, std::min(m, 65535)), dim3(256), 0, h->stream, g);
+            HM_HIP(hipGetLastError());
+            k += m;
+        }
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    };
+    rc = run();
+    const hipError_t fe = h->own.free(&h->rec.scr);           // on the error paths too (the first error is the one reported)
+    if (rc) return rc;
+    HM_HIP(fe);
+    return HM_OK;
+}
+
+// every q of `count` (dx, dy) pairs within +-STAB_QMAX; packed with its validity for the device
+static int stab_field_pack(const int16_t *q, const uint8_t *valid, size_t count, int np, const char *who, std::vector<unsigned> &qv)
+{
+    qv.resize(count);
+    for (size_t i = 0; i < count; i++) {
+        for (int c = 0; c < 2; c++)
+            HM_ARG(q[2 * i + c] >= -STAB_QMAX && q[2 * i + c] <= STAB_QMAX,
+                   "%s: q %d (%s of patch %zu, frame %zu of those given) outside -%d..%d", who, (int)q[2 * i + c], c ? "dy" : "dx",
+                   i % (size_t)np, i / (size_t)np, STAB_QMAX, STAB_QMAX);
+        qv[i] = stab_pack(q[2 * i], q[2 * i + 1], valid[i]);
+    }
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_field_sums(hm_ctx_t h, int k0, int n_frames, int B, const int16_t *q, const uint8_t *valid, uint32_t *out)
+{
+    HM_ARG(B >= STAB_BMIN && B <= STAB_BMAX, "hm_body_rec_field_sums: patch size %d outside %d..%d", B, STAB_BMIN, STAB_BMAX);
+    HM_ARG((long long)n_frames * 255 < (1ll << 32), "hm_body_rec_field_sums: %d frames x 255 could pass 2^32", n_frames);
+    HM_ARG(h && q && valid && out, "hm_body_rec_field_sums: NULL handle, q, valid or output");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_field_sums");
+    if (rc) return rc;
+    HM_ARG(k0 >= 0 && n_frames >= 0 && k0 <= h->rec.frames && n_frames <= h->rec.frames - k0,
+           "hm_body_rec_field_sums: frames %d .. %d of a record of %d", k0, k0 + n_frames - 1, h->rec.frames);
+    const RecBox &b = h->rec.box;
+    StabFieldSum g;
+    g.B = B; g.npx = hm_cdiv(b.bw, B); g.npy = hm_cdiv(b.bh, B); g.np = g.npx * g.npy;
+    const size_t n = (size_t)h->W * h->H, ns = (size_t)n_frames * g.np;
+    std::vector<unsigned> qv;
+    rc = stab_field_pack(q, valid, ns, g.np, "hm_body_rec_field_sums", qv);
+    if (rc) return rc;
+    unsigned *d_qv = nullptr;
+    rc = body_rec_carve(h, [&](RecCarve &cv) {
+        g.out = cv.take<unsigned>(n);
+        d_qv = cv.take<unsigned>(ns);
+    });
+    if (rc) return rc;
+    if (ns) HM_HIP(hipMemcpyAsync(d_qv, qv.data(), ns * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(g.out, 0, n * sizeof(unsigned), h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.W = h->W; g.k0 = k0; g.F = n_frames;
+    g.tri_of = h->body.tri; g.qv = d_qv;
+    hipLaunchKernelGGL(k_stab_field_sums, dim3(hm_cdiv(b.bw * b.bh, 256)), dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, g.out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_warp(hm_ctx_t h, int B, const int16_t *q, const uint8_t *valid)
+{
+    HM_ARG(B >= STAB_BMIN && B <= STAB_BMAX, "hm_body_rec_warp: patch size %d outside %d..%d", B, STAB_BMIN, STAB_BMAX);
+    HM_ARG(h && q && valid, "hm_body_rec_warp: NULL handle, q or valid");
+    HM_JOIN_LAZY(h);
+    int rc = body_rec_ready(h, "hm_body_rec_warp");
+    if (rc) return rc;
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames;
+    StabWarp g;
+    g.b = b; g.W = h->W; g.B = B; g.npx = hm_cdiv(b.bw, B); g.npy = hm_cdiv(b.bh, B); g.np = g.npx * g.npy; g.tri_of = h->body.tri;
+    const size_t ns = (size_t)F * g.np;
+    std::vector<unsigned> qv;
+    rc = stab_field_pack(q, valid, ns, g.np, "hm_body_rec_warp", qv);
+    if (rc) return rc;
+    unsigned *d_qv = nullptr;
+    rc = body_rec_carve(h, [&](RecCarve &cv) { d_qv = cv.take<unsigned>(ns); });
+    if (rc) return rc;
+    // runs of frames within a chunk: copied aside as they are, then sampled back into the record (as hm_body_rec_shift)
+    const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(b.fpc, F), STAB_SCRATCH_BYTES / b.fs));
+    HM_HIP(h->own.grow(&h->rec.scr, (size_t)per * b.fs));
+    auto run = [&]() -> int {
+        HM_HIP(hipMemcpyAsync(d_qv, qv.data(), ns * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+        const int blocks = hm_cdiv((b.pitch >> 2) * b.bh, 256);
+        for (int k = 0; k < F;) {
+            const int ch = k / b.fpc, m = std::min(per, std::min(F, (ch + 1) * b.fpc) - k);
+            uint8_t *dst = h->rec.chunks[ch] + (size_t)(k - ch * b.fpc) * b.fs;
+            HM_HIP(hipMemcpyAsync(h->rec.scr, dst, (size_t)m * b.fs, hipMemcpyDeviceToDevice, h->stream));
+            g.frames = m; g.qv = d_qv + (size_t)k * g.np; g.src = h->rec.scr; g.dst = dst;
+            hipLaunchKernelGGL(k_stab_warp, dim3(blocks, std::min(m, 65535)), dim3(256), 0, h->stream, g);
             HM_HIP(hipGetLastError());
             k += m;
         }

@@ -195,3 +195,152 @@ __global__ __launch_bounds__(256) void k_stab_shift(StabShift g)
         *(unsigned *)(g.dst + (size_t)j * g.b.fs + (size_t)y * g.b.pitch + x) = w;
     }
 }
+
+// ---- the smooth sub-pixel field (hm_body_rec_warp / _field_sums; tests/stabfield_ref.py) ------------------------------
+// The shift of a (frame, patch) in 1/16 px and its validity, one dword: dx + 256 in bits 0..9, dy + 256 in bits 10..19,
+// valid in bit 20 (the host packs it while it checks the range).
+#define STAB_QMAX 256
+__host__ __device__ inline unsigned stab_pack(int dx, int dy, int valid)
+{
+    return (unsigned)(dx + STAB_QMAX) | (unsigned)(dy + STAB_QMAX) << 10 | (valid ? 1u << 20 : 0u);
+}
+
+// One axis of the field at box coordinate x of a grid of n patches: the lower of the two patches the pixel lies between
+// and the weight w1 of the upper one, min(i + 1, n - 1), out of 2B (the lower one has 2B - w1).  Patch i is centred at
+// u = 2x + 1 - B = 2B i; the field is constant below the first centre and above the last.
+__device__ __forceinline__ void d_stab_axis(int x, int B, int n, int &i, int &w1)
+{
+    const int u = 2 * x + 1 - B;
+    i = u < 0 ? 0 : min(u / (2 * B), max(n - 2, 0));
+    w1 = min(max(u - 2 * B * i, 0), 2 * B);
+}
+
+struct StabField {
+    int p00, p01, p10, p11;            // the four patches (iy | iy1, ix | ix1)
+    int w00, w01, w10, w11;            // their weights wy wx, which sum to 4 B^2 <= 16384
+};
+
+__device__ __forceinline__ StabField d_stab_field(int iy, int wy1, int ix, int wx1, int B, int npx, int npy)
+{
+    const int iy1 = min(iy + 1, npy - 1), ix1 = min(ix + 1, npx - 1), wy0 = 2 * B - wy1, wx0 = 2 * B - wx1;
+    StabField f;
+    f.p00 = iy * npx + ix; f.p01 = iy * npx + ix1; f.p10 = iy1 * npx + ix; f.p11 = iy1 * npx + ix1;
+    f.w00 = wy0 * wx0; f.w01 = wy0 * wx1; f.w10 = wy1 * wx0; f.w11 = wy1 * wx1;
+    return f;
+}
+
+// The shift of a pixel in 1/16 px from the four packed (q, valid) of its patches: per component
+// floor((2 num + den) / (2 den)), num = sum w q, den = sum w over the valid ones; (0, 0) when none is valid.  With q + 256
+// in place of q the numerator is not negative (w <= 16384, q + 256 <= 512, four terms: below 2^25), so the floor is the
+// unsigned quotient, less 256.
+__device__ __forceinline__ void d_stab_shift_at(const StabField &f, unsigned a, unsigned b, unsigned c, unsigned d, int &dx, int &dy)
+{
+    const unsigned wa = (a >> 20 & 1u) * f.w00, wb = (b >> 20 & 1u) * f.w01, wc = (c >> 20 & 1u) * f.w10, wd = (d >> 20 & 1u) * f.w11;
+    const unsigned den = wa + wb + wc + wd;
+    dx = dy = 0;
+    if (!den) return;
+    const unsigned nx = wa * (a & 1023u) + wb * (b & 1023u) + wc * (c & 1023u) + wd * (d & 1023u);
+    const unsigned ny = wa * (a >> 10 & 1023u) + wb * (b >> 10 & 1023u) + wc * (c >> 10 & 1023u) + wd * (d >> 10 & 1023u);
+    dx = (int)((2 * nx + den) / (2 * den)) - STAB_QMAX;
+    dy = (int)((2 * ny + den) / (2 * den)) - STAB_QMAX;
+}
+
+// v'(p): the frame f (rows `pitch` apart, a box of bw x bh) sampled bilinearly at (16 x + dx, 16 y + dy) / 16; a source
+// off the box counts 0
+__device__ __forceinline__ unsigned d_stab_sample(const uint8_t *f, const RecBox &b, int x, int y, int dx, int dy)
+{
+    const int X = 16 * x + dx, Y = 16 * y + dy, x0 = X >> 4, y0 = Y >> 4, fx = X & 15, fy = Y & 15;
+    const bool cx0 = x0 >= 0 && x0 < b.bw, cx1 = x0 + 1 >= 0 && x0 + 1 < b.bw;
+    unsigned v00 = 0, v01 = 0, v10 = 0, v11 = 0;
+    if (y0 >= 0 && y0 < b.bh) {
+        const uint8_t *r = f + (size_t)y0 * b.pitch;
+        if (cx0) v00 = r[x0];
+        if (cx1) v01 = r[x0 + 1];
+    }
+    if (y0 + 1 >= 0 && y0 + 1 < b.bh) {
+        const uint8_t *r = f + (size_t)(y0 + 1) * b.pitch;
+        if (cx0) v10 = r[x0];
+        if (cx1) v11 = r[x0 + 1];
+    }
+    return ((16 - fx) * (16 - fy) * v00 + fx * (16 - fy) * v01 + (16 - fx) * fy * v10 + fx * fy * v11 + 128) >> 8;
+}
+
+struct StabWarp {
+    RecBox b;
+    int W, B, npx, npy, np, frames;    // frames: of this run
+    const int *tri_of;
+    const unsigned *qv;                // of the run's first frame on: frames x np packed (q, valid)
+    const uint8_t *src;                // the run's frames as they were (a copy)
+    uint8_t *dst;                      // the run's frames in the record
+};
+
+// dst_k(p) = src_k sampled at the field of frame k where p is in the map, else 0 (padding included); a dword of the
+// record per thread, blockIdx.y strides over the run's frames.  The patches and weights of the thread's four pixels do
+// not depend on the frame; neighbouring pixels between the same two patch columns share the four loads of the field.
+__global__ __launch_bounds__(256) void k_stab_warp(StabWarp g)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x, per_row = g.b.pitch >> 2;
+    if (q >= per_row * g.b.bh) return;
+    const int y = q / per_row, x = 4 * (q - y * per_row);
+    int iy, wy1, ix[4], wx1[4];
+    bool in[4];
+    d_stab_axis(y, g.B, g.npy, iy, wy1);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int xx = x + e;
+        in[e] = xx < g.b.bw && g.tri_of[(size_t)(g.b.r0 + y) * g.W + g.b.c0 + xx] >= 0;
+        d_stab_axis(xx, g.B, g.npx, ix[e], wx1[e]);
+    }
+    for (int j = blockIdx.y; j < g.frames; j += gridDim.y) {
+        const uint8_t *f = g.src + (size_t)j * g.b.fs;
+        const unsigned *qv = g.qv + (size_t)j * g.np;
+        unsigned w = 0, a = 0, b = 0, c = 0, d = 0;
+        int have = -1;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            if (!in[e]) continue;
+            const StabField fl = d_stab_field(iy, wy1, ix[e], wx1[e], g.B, g.npx, g.npy);
+            if (ix[e] != have) {
+                a = qv[fl.p00]; b = qv[fl.p01]; c = qv[fl.p10]; d = qv[fl.p11];
+                have = ix[e];
+            }
+            int dx, dy;
+            d_stab_shift_at(fl, a, b, c, d, dx, dy);
+            w |= d_stab_sample(f, g.b, x + e, y, dx, dy) << (8 * e);
+        }
+        *(unsigned *)(g.dst + (size_t)j * g.b.fs + (size_t)y * g.b.pitch + x) = w;
+    }
+}
+
+struct StabFieldSum {
+    RecBox b;
+    const uint8_t *const *chunks;
+    int W, k0, F;
+    int B, npx, npy, np;
+    const int *tri_of;
+    const unsigned *qv;                // F x np packed (q, valid)
+    unsigned *out;                     // W x H, zeroed by the caller
+};
+
+// out[p] = sum over the frames of v'_k(p), the frame sampled at its field, for the map pixels p of the box, a thread per
+// pixel.  The host has refused F 255 >= 2^32.
+__global__ __launch_bounds__(256) void k_stab_field_sums(StabFieldSum g)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= g.b.bw * g.b.bh) return;
+    const int y = i / g.b.bw, x = i - y * g.b.bw;
+    const size_t p = (size_t)(g.b.r0 + y) * g.W + g.b.c0 + x;
+    if (g.tri_of[p] < 0) return;
+    int iy, wy1, ix, wx1;
+    d_stab_axis(y, g.B, g.npy, iy, wy1);
+    d_stab_axis(x, g.B, g.npx, ix, wx1);
+    const StabField fl = d_stab_field(iy, wy1, ix, wx1, g.B, g.npx, g.npy);
+    unsigned sum = 0;
+    for (int j = 0; j < g.F; j++) {
+        const unsigned *qv = g.qv + (size_t)j * g.np;
+        int dx, dy;
+        d_stab_shift_at(fl, qv[fl.p00], qv[fl.p01], qv[fl.p10], qv[fl.p11], dx, dy);
+        sum += d_stab_sample(d_rec_frame(g.b, g.chunks, g.k0 + j), g.b, x, y, dx, dy);
+    }
+    g.out[p] = sum;
+}

@@ -416,7 +416,7 @@ class Renderer:
                    "hm_body_rec_trace_products")
         return out
 
-    # -- residual motion of the record (hm_body_rec_match / _frame_sums / _shift; hydra_mi.stabilize) --
+    # -- residual motion of the record (hm_body_rec_match / _frame_sums / _shift / _warp / _field_sums; hydra_mi.stabilize) --
     def body_rec_patches(self, B):
         """-> (patches per row, patch rows) of the grid of B x B patches over the record's box (the bounding box of the
         body map)"""
@@ -482,6 +482,41 @@ class Renderer:
         if F and sh.shape[0] != F:                               # (F 0: the call says why)
             raise ValueError("body_rec_shift: shifts of %d frames for a record of %d" % (sh.shape[0], F))
         _lib.check(_lib.lib().hm_body_rec_shift(self._h, int(B), _lib.ptr(sh)), "hm_body_rec_shift")
+
+    def _body_field(self, q, valid, B, who):
+        q, valid = np.asarray(q), np.asarray(valid)
+        if q.dtype != np.int16 or q.ndim != 3 or q.shape[2] != 2:
+            raise ValueError("%s: q %s of shape %r (need int16, (frames, patches, 2))" % (who, q.dtype, q.shape))
+        if valid.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)) or valid.shape != q.shape[:2]:
+            raise ValueError("%s: valid %s of shape %r for q of shape %r (need uint8 or bool, (frames, patches))" % (
+                who, valid.dtype, valid.shape, q.shape))
+        if 4 <= int(B) <= 64:
+            npx, npy = self.body_rec_patches(B)
+            if q.shape[1] != npx * npy:
+                raise ValueError("%s: q for %d patches, the grid of %d px patches has %d" % (who, q.shape[1], int(B), npx * npy))
+        return np.ascontiguousarray(q), np.ascontiguousarray(valid, np.uint8)
+
+    def body_rec_field_sums(self, q, valid, B, k0=0, n=None):
+        """hm_body_rec_field_sums: -> (H, W) uint32, the sum over the frames k0 .. k0 + n - 1 of every map pixel sampled at
+        the smooth field of that frame; q (n, patches, 2) int16 (dx, dy) in 1/16 px, valid (n, patches)."""
+        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        q, valid = self._body_field(q, valid, B, "body_rec_field_sums")
+        if q.shape[0] != n:
+            raise ValueError("body_rec_field_sums: q of %d frames for %d" % (q.shape[0], n))
+        out = np.empty((self.ny, self.nx), np.uint32)
+        _lib.check(_lib.lib().hm_body_rec_field_sums(self._h, int(k0), n, int(B), _lib.ptr(q), _lib.ptr(valid), _lib.ptr(out)),
+                   "hm_body_rec_field_sums")
+        return out
+
+    def body_rec_warp(self, q, valid, B):
+        """hm_body_rec_warp: rewrite the record in place, every map pixel of every frame sampled bilinearly at the smooth
+        field between the patches' shifts; q (F, patches, 2) int16 (dx, dy) in 1/16 px, valid (F, patches), for all
+        recorded frames.  Not reversible."""
+        q, valid = self._body_field(q, valid, B, "body_rec_warp")
+        F = self.body_rec_count()
+        if F and q.shape[0] != F:                                # (F 0: the call says why)
+            raise ValueError("body_rec_warp: q of %d frames for a record of %d" % (q.shape[0], F))
+        _lib.check(_lib.lib().hm_body_rec_warp(self._h, int(B), _lib.ptr(q), _lib.ptr(valid)), "hm_body_rec_warp")
 
     def screenshot(self, saveall=True, basename="screenshot", X=None):
         """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask

@@ -16,6 +16,14 @@ demix.extract read the stabilised record unchanged.
 The first template is one recorded frame (k_ref), not the mean of the unstabilised video: on a textured animal the mean is
 a blur that every frame locks onto at its most-visited shift.  A second pass matches against the rounded mean of the frames
 at the first pass's shifts.  tests/stab_ref.py restates all of it in NumPy.
+
+mode="field" takes the same motion out as a smooth sub-pixel shift field instead: every patch's shift is refined to 1/16 px
+by a parabola through its score and its two neighbours' per axis, the field is bilinear between the patch centres (a patch
+that fell back is filled in by its neighbours), and hm_body_rec_warp samples every frame bilinearly at it.  It is the
+better choice where the residual motion is smooth and below a pixel, which is what the tracker leaves; where regions move
+rigidly against each other with hard seams the patches are.  tests/stabfield_ref.py restates it.
+
+    est = stabilize.stabilize(body, mode="field")
 """
 import numpy as np
 
@@ -98,13 +106,44 @@ def choose(sc, n_core, S, min_score, n_min):
     return shifts, np.where(found, best, np.nan), fallback
 
 
+def subpixel(sc, shifts, fallback, S):
+    """The shifts refined to 1/16 px -> q (F, patches, 2) int16 (dx, dy).  sc (F, patches, (2S+1)^2) scores, -inf: invalid;
+    shifts and fallback as choose gives them.  Per axis, with s0 the winner's score and s-, s+ those of its two neighbours
+    along the axis: where the winner is strictly inside the search (|d| < S), both neighbours are valid and
+    den = s- - 2 s0 + s+ < 0, off = (s- - s+) / (2 den) clipped to +-0.5, else 0; q = 16 d + floor(16 off + 0.5).  A patch
+    that fell back has q = 0.  Every step is one binary64 operation in this order."""
+    n1 = 2 * S + 1
+    sh = np.asarray(shifts).astype(np.int64)
+    fb = np.asarray(fallback, bool)
+    idx = (sh[:, :, 1] + S) * n1 + sh[:, :, 0] + S
+    s0 = np.take_along_axis(sc, idx[:, :, None], 2)[:, :, 0]
+    q = np.zeros(sh.shape, np.int16)
+    for axis, step in ((0, 1), (1, n1)):
+        inside = (np.abs(sh[:, :, axis]) < S) & ~fb
+        lo = np.take_along_axis(sc, np.where(inside, idx - step, idx)[:, :, None], 2)[:, :, 0]
+        hi = np.take_along_axis(sc, np.where(inside, idx + step, idx)[:, :, None], 2)[:, :, 0]
+        ok = inside & (lo > -np.inf) & (hi > -np.inf) & (s0 > -np.inf)
+        lo, hi, mid = (np.where(ok, x, 0.0) for x in (lo, hi, s0))
+        den = (lo - 2.0 * mid) + hi
+        ok &= den < 0.0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            off = np.where(ok, (lo - hi) / (2.0 * den), 0.0)
+        off = np.minimum(np.maximum(off, -0.5), 0.5)
+        q[:, :, axis] = (16 * sh[:, :, axis] + np.floor(16.0 * off + 0.5).astype(np.int64)).astype(np.int16)
+    q[fb] = 0
+    return q
+
+
 def mean_template(sums, F):
     """The rounded mean of F frames from their per-pixel sums: (2 sum + F) // (2 F), uint8."""
     s = np.asarray(sums).astype(np.int64)
     return ((2 * s + F) // (2 * F)).astype(np.uint8)
 
 
-def estimate(body, B=16, S=3, k_ref=0, passes=1, min_score=None, n_min=None):
+MODES = ("patch", "field")
+
+
+def estimate(body, B=16, S=3, k_ref=0, passes=1, min_score=None, n_min=None, mode="patch"):
     """The shift of every patch of every frame a BodyReadout(keep=True) has recorded.  -> dict:
       shifts (F, patches, 2) int8 (dx, dy)   gather the patch at p + d (body_rec_shift does)
       score (F, patches) float64             the best normalised correlation with the template (NaN: no valid shift)
@@ -112,7 +151,12 @@ def estimate(body, B=16, S=3, k_ref=0, passes=1, min_score=None, n_min=None):
       n_core (patches,) uint32, grid (patch_grid), templates (one (H, W) uint8 per pass), B, S
     Pass 1 matches against record frame k_ref.  Pass p > 1 matches the ORIGINAL record against the rounded mean of the
     frames at the previous pass's shifts; its shifts replace the previous ones.  min_score None: DEFAULT_MIN_SCORE; n_min
-    None: B B / 4 core pixels."""
+    None: B B / 4 core pixels.
+    mode "field" adds q (F, patches, 2) int16, the shifts refined to 1/16 px (subpixel), valid (F, patches) uint8, the
+    patches that did not fall back, and mode; pass p > 1 then matches against the rounded mean of the frames sampled at the
+    previous pass's field (body_rec_field_sums)."""
+    if mode not in MODES:
+        raise ValueError("stabilize.estimate: mode %r (one of %s)" % (mode, ", ".join(MODES)))
     if not getattr(body, "keep", False):
         raise RuntimeError("stabilize.estimate: the readout was made without keep=True")
     r = body.r
@@ -132,12 +176,15 @@ def estimate(body, B=16, S=3, k_ref=0, passes=1, min_score=None, n_min=None):
     template = np.where(m, r.body_rec_fetch(int(k_ref), 1)[0], 0).astype(np.uint8)
     templates, out = [], None
     for p in range(passes):
-        if p > 0:
+        if p > 0 and mode == "field":
+            template = mean_template(r.body_rec_field_sums(out["q"], out["valid"], B), F)
+        elif p > 0:
             template = mean_template(r.body_rec_frame_sums(out["shifts"], B), F)
         templates.append(template)
         t = np.where(core, template, 0).astype(np.int64)
         St, Stt = _patch_sums(t, grid), _patch_sums(t * t, grid)
         shifts = np.zeros((F, npatch, 2), np.int8)
+        q = np.zeros((F, npatch, 2), np.int16)
         score = np.full((F, npatch), np.nan)
         fallback = np.zeros((F, npatch), bool)
         n_core = None
@@ -149,13 +196,21 @@ def estimate(body, B=16, S=3, k_ref=0, passes=1, min_score=None, n_min=None):
                 raise RuntimeError("stabilize.estimate: the cores of the patches differ between host and device")
             sc = scores(ms["A"], ms["V1"], ms["V2"], n_core, St, Stt)
             shifts[k0:k0 + n], score[k0:k0 + n], fallback[k0:k0 + n] = choose(sc, n_core, S, min_score, n_min)
+            if mode == "field":
+                q[k0:k0 + n] = subpixel(sc, shifts[k0:k0 + n], fallback[k0:k0 + n], S)
         out = dict(shifts=shifts, score=score, fallback=fallback, n_core=n_core, grid=grid, templates=templates, B=B, S=S)
+        if mode == "field":
+            out.update(q=q, valid=(~fallback).astype(np.uint8), mode=mode)
     return out
 
 
 def apply(body, est):
-    """Rewrite the record in place at the estimated shifts (hm_body_rec_shift; not reversible)."""
-    body.r.body_rec_shift(est["shifts"], est["B"])
+    """Rewrite the record in place at the estimated shifts (hm_body_rec_shift), or for an estimate of mode "field" at its
+    field (hm_body_rec_warp); not reversible."""
+    if est.get("mode", "patch") == "field":
+        body.r.body_rec_warp(est["q"], est["valid"], est["B"])
+    else:
+        body.r.body_rec_shift(est["shifts"], est["B"])
 
 
 def stabilize(body, **kw):

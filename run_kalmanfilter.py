@@ -53,6 +53,11 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      the roi_* and demix_* arrays and, with --find-points, point_means.  What is summed while tracking does
                      not: tri_means, the summary images body_* and the points found in them, point_means of --points.
                      --cells-video keeps drawing at the tracked states.
+                     --stab-mode field (default patch) takes the motion out as a smooth shift field instead of one whole
+                     pixel vector per patch: the shifts refined to 1/16 px, bilinear between the patch centres, fallback
+                     patches filled in by their neighbours, the frames sampled bilinearly.  The choice for the smooth
+                     sub-pixel motion a tracker leaves; patch for regions that move rigidly against each other.  The states
+                     file then also gets stab_q (frames x patches x 2, int16, (dx, dy) in 1/16 px).
     --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
                      (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
                      diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
@@ -120,6 +125,9 @@ def main(argv=None):
     parser.add_argument("--stab-patch", default=16, type=int, help="edge of the patches that are matched (4..64 px)")
     parser.add_argument("--stab-search", default=3, type=int, help="the shifts searched: +-N px (0..8)")
     parser.add_argument("--stab-passes", default=1, type=int, help="passes of estimating the shifts")
+    parser.add_argument("--stab-mode", default="patch", choices=stabilize.MODES,
+                        help="patch: one whole-pixel shift per patch; field: a smooth sub-pixel shift field between the patch "
+                             "centres (stab_q in the states file)")
     parser.add_argument("--smooth", action="store_true", help="smooth the track backward: Xs, Xs_std in the states file")
     parser.add_argument("--smooth-max-gb", default=8.0, type=float, help="device memory the smoother may take (GiB)")
     parser.add_argument("--cells-video", default=None, metavar="OUT.avi",
@@ -258,11 +266,15 @@ def main(argv=None):
         # between tracking and everything that reads the kept record: the disc read-out of --find-points, roi.extract and
         # demix.extract see the stabilised frames (what was summed while tracking -- tri_means, the summary images and the
         # points found in them, point_means of --points -- saw the frames as the tracker registered them)
-        est = stabilize.stabilize(body, B=args.stab_patch, S=args.stab_search, passes=args.stab_passes)
+        est = stabilize.stabilize(body, B=args.stab_patch, S=args.stab_search, passes=args.stab_passes, mode=args.stab_mode)
         extra.update(stab_shifts=est["shifts"], stab_score=est["score"], stab_fallback=est["fallback"])
-        print("Stabilised: %d patches of %d px, search %d, %d passes: %.1f %% fallbacks, mean |shift| %.3f px" % (
-            est["shifts"].shape[1], args.stab_patch, args.stab_search, args.stab_passes, 100.0 * est["fallback"].mean(),
-            np.abs(est["shifts"].astype(np.float64)).sum(2).mean()))
+        moved = est["shifts"].astype(np.float64)
+        if args.stab_mode == "field":
+            extra.update(stab_q=est["q"])
+            moved = est["q"].astype(np.float64) / 16.0
+        print("Stabilised%s: %d patches of %d px, search %d, %d passes: %.1f %% fallbacks, mean |shift| %.3f px" % (
+            " (field)" if args.stab_mode == "field" else "", est["shifts"].shape[1], args.stab_patch, args.stab_search,
+            args.stab_passes, 100.0 * est["fallback"].mean(), np.abs(moved).sum(2).mean()))
     if find:
         # the cells need the whole video and the traces need the cells: a second pass over the recorded states
         sm_img = body.summary()

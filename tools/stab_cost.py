@@ -7,9 +7,11 @@ of 64 and of 1024 frames.
 
 For each record length the tool starts `timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -- python
 tools/stab_cost.py --kernels-only --frames N` (a run of its own, no counters with it; the first run that fails ends the
-tool) and reads from its kernel_stats.csv the times of k_stab_match, k_stab_frame_sums and k_stab_shift.  Then, without the
-profiler, the wall time of stabilize.estimate (host arithmetic and copies included) beside roi.extract's on the same
-record.  From the match kernel's time: record bytes read per second (every patch reads its window, (B + 2S)^2 / B^2 of its
+tool) and reads from its kernel_stats.csv the times of k_stab_match, k_stab_frame_sums and k_stab_shift and, of the field
+mode, k_stab_field_sums and k_stab_warp; warp_over_shift is the ratio of the two kernels that rewrite the record (the same
+bytes written; the warp reads four source bytes per pixel instead of one, and the field).  Then, without the profiler, the
+wall time of stabilize.estimate and stabilize.apply in both modes (host arithmetic and copies included) beside
+roi.extract's on the same record.  From the match kernel's time: record bytes read per second (every patch reads its window, (B + 2S)^2 / B^2 of its
 own bytes) and byte products per second, F x map pixels x (2S + 1)^2 x 3 sums.  The video and the record are those of
 tools/demix_cost.py.  The result is one JSON file (default profiles/stab_cost.json).
 """
@@ -28,7 +30,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-KERNELS = ("k_stab_match", "k_stab_frame_sums", "k_stab_shift")
+KERNELS = ("k_stab_match", "k_stab_frame_sums", "k_stab_shift", "k_stab_field_sums", "k_stab_warp")
 B, S = 16, 3
 
 
@@ -37,7 +39,10 @@ def kernels_only(frames):
     kf, b, pts = record(frames)
     rd = kf.state.renderer
     npx, npy = rd.body_rec_patches(B)
-    sh = np.random.default_rng(1).integers(-S, S + 1, (frames, npx * npy, 2)).astype(np.int8)
+    rng = np.random.default_rng(1)
+    sh = rng.integers(-S, S + 1, (frames, npx * npy, 2)).astype(np.int8)
+    q = rng.integers(-16 * S, 16 * S + 1, (frames, npx * npy, 2)).astype(np.int16)
+    valid = (rng.random((frames, npx * npy)) < 0.6).astype(np.uint8)          # (about the share that does not fall back)
     t = rd.body_rec_fetch(0, 1)[0]
     block = min(frames, 64)
     for _ in range(3):
@@ -45,6 +50,8 @@ def kernels_only(frames):
             rd.body_rec_match(t, B, S, k0, min(block, frames - k0))
         rd.body_rec_frame_sums(sh, B)
         rd.body_rec_shift(sh, B)
+        rd.body_rec_field_sums(q, valid, B)
+        rd.body_rec_warp(q, valid, B)
     rd.body_rec_end()
     kf.close()
 
@@ -77,6 +84,9 @@ def main():
                     if row.get("Name", "").startswith(kernel + "("):
                         one[kernel] = {k: row[k] for k in ("Name", "Calls", "AverageNs", "MinNs", "MaxNs") if k in row}
                         one[kernel + "_us"] = float(row["AverageNs"]) / 1e3
+            if "k_stab_warp_us" in one and "k_stab_shift_us" in one:
+                # (both kernels are launched once per run of frames, the same runs: the averages compare like with like)
+                one["warp_over_shift"] = one["k_stab_warp_us"] / one["k_stab_shift_us"]
         rec["records"][str(frames)] = one
     from demix_cost import record                     # (the profiled runs are over: this process opens the GPU only now)
     from hydra_mi import roi, stabilize
@@ -94,8 +104,14 @@ def main():
         roi.extract(b, pts, alpha=1.0)
         one["roi_extract_wall_ms"] = 1e3 * (time.perf_counter() - t0)
         t0 = time.perf_counter()
+        est_f = stabilize.estimate(b, B=B, S=S, mode="field")
+        one["estimate_field_wall_ms"] = 1e3 * (time.perf_counter() - t0)
+        t0 = time.perf_counter()
         stabilize.apply(b, est)
         one["apply_wall_ms"] = 1e3 * (time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        stabilize.apply(b, est_f)                     # (on the shifted record: the cost does not depend on what it holds)
+        one["apply_field_wall_ms"] = 1e3 * (time.perf_counter() - t0)
         one["fallback_share"] = float(est["fallback"].mean())
         core = int(est["n_core"].sum())
         calls = -(-frames // min(frames, 64))         # (the kernel's time is per call: blocks of 64 frames in kernels_only)
