@@ -405,17 +405,23 @@ void *hm_ctx_stream(hm_ctx_t h);
  *     the prior mean the update keeps on the device; X (4N): x_k, the state the update kept.  HM_ERR_STATE: the record
  *     is full, or no update has run on the handle -- the record is left as it was.
  * run: the backward pass over the K frames recorded, on the filter's stream.  Pp_{k+1} is recomputed by the kernels
- *     and from the inputs of the forward prediction (same bits) and factored by the update's factorisation, per step;
+ *     and from the inputs of the forward prediction (same bits) and factored by the update's factorisation, per step
+ *     (Pp = L L^T, T = L^-1); G_k = (T F_k P_k)^T T is formed through the factor, inv(Pp) = T^T T never is;
  *     xs (K x 4N) always; want_cov != 0: var (K x 4N) = diag(Ps_k), and Ps_k replaces P_k in slot k (after such a run
  *     the record takes no more frames and cannot be run again).  want_cov = 0 needs matrix-vector products only and
  *     leaves the record as it is; its xs are bit-equal to those of a run with covariances.  HM_ERR_NUMERIC: some
- *     Pp_{k+1} is not positive definite.
+ *     Pp_{k+1} is not positive definite or not finite; the message names frame k+1 (the latest such frame), xs and
+ *     var hold no result.  After HM_ERR_NUMERIC with want_cov = 0 the record and the filter handle are as they were.
+ *     With want_cov != 0 the record is consumed, as after a run that succeeded: its slots were being overwritten from
+ *     the first step on, so record, run and prior return HM_ERR_STATE; fetch still gives x_k and m_k as recorded (and
+ *     the last slot, which no step writes); the filter handle is as it was.
  * count: the frames recorded and the capacity (either pointer may be NULL).
  * fetch: slot k (4N x 4N: P_k, or Ps_k after a run with covariances), x_k and m_k (4N each); any may be NULL.
  * prior: Pp_k (k >= 1) recomputed from slot k-1 as the backward pass does; HM_ERR_STATE after a run with covariances.
  * hm_op_smooth_gemm: the backward step's products on host n x n row-major arrays on the f64 matrix cores, for tests:
- *     which 0: out = A^T B (G = (F P)^T inv(Pp));  1: out = A (B - C) (E = G (Ps' - Pp));  2: out = C + A B^T formed
- *     for the lower triangle and mirrored (Ps = P + E G^T, exactly symmetric). */
+ *     which 0: out = A^T B;  1: out = A (B - C) (E = G (Ps' - Pp));  2: out = C + A B^T formed for the lower triangle
+ *     and mirrored (Ps = P + E G^T, exactly symmetric);  3: out = tril(A) B (Y = T (F P));  4: out = A^T tril(B)
+ *     (G = Y^T T) -- tril: what lies right of the diagonal is not read.  C may be NULL except for 1 and 2. */
 typedef struct hm_smooth *hm_smooth_t;
 int hm_smooth_create(hm_ctx_t ctx, int capacity, int n_bars, const int32_t *bars, const double *l0, double kappa,
                      double a, double s, double eps_F, hm_smooth_t *out);

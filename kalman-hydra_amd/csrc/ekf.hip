@@ -2094,8 +2094,8 @@ struct hm_smooth {
     double *d_blk = nullptr;         // cap x 3 n_bars
     int *d_off = nullptr, *d_bar = nullptr, *d_other = nullptr;                 // the springs of every vertex (spring_csr)
     // per backward step: F P, Pp, its factor (L, T = L^-1, the diagonal blocks' inverses Lt, the flow launch's scratch),
-    // inv(Pp), G, E, and three vectors (d, T d, T^T T d)
-    double *d_FP = nullptr, *d_Pp = nullptr, *d_L = nullptr, *d_T = nullptr, *d_inv = nullptr, *d_G = nullptr, *d_E = nullptr;
+    // Y = T F P, G, E, and three vectors (d, T d, T^T T d)
+    double *d_FP = nullptr, *d_Pp = nullptr, *d_L = nullptr, *d_T = nullptr, *d_Y = nullptr, *d_G = nullptr, *d_E = nullptr;
     double *d_Lt = nullptr, *d_flowP = nullptr, *d_vec = nullptr;
     unsigned *d_ctl = nullptr;       // the factorisation launch's task counter and time-out word
     int *d_flag = nullptr;           // 1 + the first frame whose Pp did not factor
@@ -2142,7 +2142,7 @@ extern "C" int hm_smooth_create(hm_ctx_t ctx, int capacity, int n_bars, const in
     take(&sm->d_off, (size_t)(N + 1) * sizeof(int), "the spring topology");
     take(&sm->d_bar, std::max<size_t>(1, 2 * (size_t)n_bars) * sizeof(int), "the spring topology");
     take(&sm->d_other, std::max<size_t>(1, 2 * (size_t)n_bars) * sizeof(int), "the spring topology");
-    double **work[] = {&sm->d_FP, &sm->d_Pp, &sm->d_L, &sm->d_T, &sm->d_inv, &sm->d_G, &sm->d_E};
+    double **work[] = {&sm->d_FP, &sm->d_Pp, &sm->d_L, &sm->d_T, &sm->d_Y, &sm->d_G, &sm->d_E};
     for (double **p : work) take(p, nn, "the work matrices");
     take(&sm->d_Lt, (size_t)nb * DNB * DNB * sizeof(double), "the factorisation");
     take(&sm->d_flowP, (size_t)3 * nb * DNB * DNB * sizeof(double), "the factorisation");
@@ -2317,10 +2317,12 @@ extern "C" int hm_smooth_run(hm_smooth_t sm, int want_cov, double *xs, double *v
         hipLaunchKernelGGL(k_sm_mvt, dim3(gv), dim3(256), 0, st, (const double *)sm->d_FP, (const double *)w,
                            (const double *)(sm->d_x + (size_t)k * n4), sm->d_xs + (size_t)k * n4, n4, 0);
         if (want_cov) {
-            // G = (F P)^T inv(Pp), E = G (Ps_{k+1} - Pp), Ps_k = P_k + E G^T in slot k
-            hipLaunchKernelGGL(k_ttt, dim3(nb, nb), dim3(256), 0, st, (const double *)sm->d_T, n4, sm->d_inv);
-            hipLaunchKernelGGL(k_sm_gemm<SM_TN>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_FP,
-                               (const double *)sm->d_inv, (const double *)nullptr, sm->d_G, n4);
+            // Y = T (F P), G = Y^T T = (F P)^T inv(Pp) through the factor (smooth_kernels.h: not through T^T T),
+            // E = G (Ps_{k+1} - Pp), Ps_k = P_k + E G^T in slot k
+            hipLaunchKernelGGL(k_sm_gemm<SM_LN>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_T,
+                               (const double *)sm->d_FP, (const double *)nullptr, sm->d_Y, n4);
+            hipLaunchKernelGGL(k_sm_gemm<SM_TL>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_Y,
+                               (const double *)sm->d_T, (const double *)nullptr, sm->d_G, n4);
             hipLaunchKernelGGL(k_sm_gemm<SM_NND>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_G, Ps1,
                                (const double *)sm->d_Pp, sm->d_E, n4);
             hipLaunchKernelGGL(k_sm_gemm<SM_SYM>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_E,
@@ -2338,19 +2340,20 @@ extern "C" int hm_smooth_run(hm_smooth_t sm, int want_cov, double *xs, double *v
     HM_HIP(hipStreamSynchronize(st));
     if (ctl[1]) { hm_set_error("hm_smooth_run: the factorisation launch gave up waiting for a block (chol_flow time-out)"); return HM_ERR_HIP; }
     if (flag) {
-        hm_set_error("hm_smooth_run: the predicted covariance Pp of frame %d is not positive definite", flag);
+        hm_set_error("hm_smooth_run: the predicted covariance Pp of frame %d is not positive definite", flag - 1);   // (k_sm_check: 1 + the frame)
         return HM_ERR_NUMERIC;
     }
     return HM_OK;
 }
 
-// The three products of the backward step on host arrays (n x n, row-major), for tests: which = SM_TN (out = A^T B),
-// SM_NND (out = A (B - C)), SM_SYM (out = C + A B^T from the lower tiles, mirrored)
+// The products of the backward step on host arrays (n x n, row-major), for tests: which = SM_TN (out = A^T B),
+// SM_NND (out = A (B - C)), SM_SYM (out = C + A B^T from the lower tiles, mirrored), SM_LN (out = tril(A) B),
+// SM_TL (out = A^T tril(B)); C is read by SM_NND and SM_SYM only
 extern "C" int hm_op_smooth_gemm(int device, int which, int n, const double *A, const double *B, const double *C, double *out)
 {
-    HM_ARG(which >= SM_TN && which <= SM_SYM, "hm_op_smooth_gemm: which %d outside 0..2", which);
+    HM_ARG(which >= SM_TN && which <= SM_TL, "hm_op_smooth_gemm: which %d outside 0..4", which);
     HM_ARG(n >= 1 && n <= 8192, "hm_op_smooth_gemm: n %d outside 1..8192", n);
-    HM_ARG(A && B && out && (which == SM_TN || C), "hm_op_smooth_gemm: NULL argument");
+    HM_ARG(A && B && out && ((which != SM_NND && which != SM_SYM) || C), "hm_op_smooth_gemm: NULL argument");
     HM_HIP(hipSetDevice(device));
     const size_t bytes = (size_t)n * n * sizeof(double);
     double *dA = nullptr, *dB = nullptr, *dC = nullptr, *dO = nullptr;
@@ -2363,6 +2366,12 @@ extern "C" int hm_op_smooth_gemm(int device, int which, int n, const double *A, 
         HM_HIP(hipMemcpy(dB, B, bytes, hipMemcpyHostToDevice));
         if (which == SM_TN) {
             hipLaunchKernelGGL(k_sm_gemm<SM_TN>, dim3(nb, nb), dim3(SM_NT), 0, 0, (const double *)dA, (const double *)dB,
+                               (const double *)nullptr, dO, n);
+        } else if (which == SM_LN) {
+            hipLaunchKernelGGL(k_sm_gemm<SM_LN>, dim3(nb, nb), dim3(SM_NT), 0, 0, (const double *)dA, (const double *)dB,
+                               (const double *)nullptr, dO, n);
+        } else if (which == SM_TL) {
+            hipLaunchKernelGGL(k_sm_gemm<SM_TL>, dim3(nb, nb), dim3(SM_NT), 0, 0, (const double *)dA, (const double *)dB,
                                (const double *)nullptr, dO, n);
         } else if (which == SM_NND) {
             HM_HIP(hm_malloc((void **)&dC, bytes, 4));

@@ -12,12 +12,19 @@
 #define SM_NT 256       // threads of a product workgroup
 
 // which product (hm_op_smooth_gemm `which`):
-//   SM_TN   out = A^T B             G = (F P)^T inv(Pp)     (F P from k_fw_rows; P symmetric, so P F^T = (F P)^T)
+//   SM_TN   out = A^T B
+//   SM_LN   out = tril(A) B         Y = T (F P)             (T = L^-1 of Pp = L L^T; F P from k_fw_rows)
+//   SM_TL   out = A^T tril(B)       G = Y^T T               (= (F P)^T T^T T = P F^T inv(Pp); P symmetric)
+//                                   tril: the entries right of the diagonal are not read (the factorisation leaves them
+//                                   unset) and the slabs that lie wholly right of it are skipped.  G is formed through
+//                                   the factor, never through inv(Pp) = T^T T: the rounding of T^T T is of the size of
+//                                   |T^T| |T|, which T (F P) -- the whitened F P -- is far below when Pp is badly scaled
+//                                   or F P nearly cancels against it, and Ps = P + E G^T is a difference of that size.
 //   SM_NND  out = A (B - C)         E = G (Ps' - Pp)
 //   SM_SYM  out = C + A B^T         Ps = P + E G^T: lower tiles only, each mirrored, so the result is exactly
 //                                   symmetric; out may be C (every element is read by the thread that writes it and
 //                                   by nobody else: the upper triangle is written, never read)
-enum { SM_TN = 0, SM_NND = 1, SM_SYM = 2 };
+enum { SM_TN = 0, SM_NND = 1, SM_SYM = 2, SM_LN = 3, SM_TL = 4 };
 
 template <int MODE>
 __global__ __launch_bounds__(SM_NT) void k_sm_gemm(const double *__restrict__ A, const double *__restrict__ B,
@@ -30,13 +37,18 @@ __global__ __launch_bounds__(SM_NT) void k_sm_gemm(const double *__restrict__ A,
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int i0 = I * DNB, j0 = J * DNB;
     d4_t acc = {0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < n; k0 += DNB) {
+    // (the triangular operand: column k <= row i0 + i of A, row k >= column j0 + j of B)
+    const int k_begin = MODE == SM_TL ? j0 : 0, k_end = MODE == SM_LN ? min(n, i0 + DNB) : n;
+    for (int k0 = k_begin; k0 < k_end; k0 += DNB) {
 #pragma unroll
         for (int q = 0; q < DNB * DNB / SM_NT; q++) {
             const int e = t + SM_NT * q, r = e / DNB, c = e % DNB;
             double x = 0.0, y = 0.0;
-            if (MODE == SM_TN) {            // X[k][i] = A[k0 + k][i0 + i], Y[k][j] = B[k0 + k][j0 + j]
+            if (MODE == SM_TN || MODE == SM_TL) {   // X[k][i] = A[k0 + k][i0 + i], Y[k][j] = B[k0 + k][j0 + j]
                 if (k0 + r < n && i0 + c < n) x = A[(size_t)(k0 + r) * n + i0 + c];
+                if (k0 + r < n && j0 + c < n && (MODE == SM_TN || j0 + c <= k0 + r)) y = B[(size_t)(k0 + r) * n + j0 + c];
+            } else if (MODE == SM_LN) {     // X[i][k] = A[i0 + i][k0 + k] (k <= i), Y[k][j] = B[k0 + k][j0 + j]
+                if (i0 + r < n && k0 + c <= i0 + r) x = A[(size_t)(i0 + r) * n + k0 + c];
                 if (k0 + r < n && j0 + c < n) y = B[(size_t)(k0 + r) * n + j0 + c];
             } else if (MODE == SM_NND) {    // X[i][k] = A[i0 + i][k0 + k], Y[k][j] = B - C at [k0 + k][j0 + j]
                 if (i0 + r < n && k0 + c < n) x = A[(size_t)(i0 + r) * n + k0 + c];
@@ -52,9 +64,9 @@ __global__ __launch_bounds__(SM_NT) void k_sm_gemm(const double *__restrict__ A,
             Y[r][c] = y;
         }
         __syncthreads();
-        if (MODE == SM_TN) {
+        if (MODE == SM_TN || MODE == SM_TL) {
             acc = d_mfma_tn(X, Y, wv, lane, acc);
-        } else if (MODE == SM_NND) {
+        } else if (MODE == SM_NND || MODE == SM_LN) {
             acc = d_mfma_nn(X, Y, wv, lane, acc);
         } else {
             const int i = 16 * (wv >> 1) + (lane & 15), j = 16 * (wv & 1) + (lane & 15), kq = lane >> 4;

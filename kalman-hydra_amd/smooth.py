@@ -6,7 +6,8 @@ after every ``kf.compute()``, what the update kept on the device -- the posterio
 update started from -- and the posterior mean x_k; ``run()`` then goes backward over the record on the device
 (hm_smooth_* in include/hydra_mi.h, csrc/smooth_kernels.h):
 
-    G_k  = P_k F_k^T Pp_{k+1}^-1,   Pp_{k+1} = F_k P_k F_k^T + Weps (recomputed, the forward prediction's bits)
+    G_k  = P_k F_k^T Pp_{k+1}^-1,   Pp_{k+1} = F_k P_k F_k^T + Weps (recomputed, the forward prediction's bits;
+                                    G_k through the Cholesky factor of Pp_{k+1}, its inverse is never formed)
     xs_k = x_k + G_k (xs_{k+1} - m_{k+1})
     Ps_k = P_k + G_k (Ps_{k+1} - Pp_{k+1}) G_k^T      (covariances=True)
 
@@ -174,8 +175,9 @@ class RTSSmoother:
 
 def gemm(which, A, B, C=None, device=0):
     """hm_op_smooth_gemm: the backward step's products on host arrays (tests).  which: "tn" A^T B, "nnd" A (B - C),
-    "sym" C + A B^T (lower triangle, mirrored)."""
-    code = {"tn": 0, "nnd": 1, "sym": 2}[which]
+    "sym" C + A B^T (lower triangle, mirrored), "ln" tril(A) B, "tl" A^T tril(B) (what lies right of the diagonal of the
+    triangular operand is not read)."""
+    code = {"tn": 0, "nnd": 1, "sym": 2, "ln": 3, "tl": 4}[which]
     A = np.ascontiguousarray(A, np.float64)
     B = np.ascontiguousarray(B, np.float64)
     C = None if C is None else np.ascontiguousarray(C, np.float64)

@@ -9,8 +9,14 @@ and the model F_k, Weps, backward for k = K-2 .. 0:
     Ps_k     = P_k + G_k (Ps_{k+1} - Pp_{k+1}) G_k^T
 
 with xs_{K-1} = x_{K-1}, Ps_{K-1} = P_{K-1}.  Test infrastructure: the package does not import it.
+
+smooth_ld is the same recursion in numpy.longdouble (the reference of tests/test_smooth_precision_*.py, with the
+inverse of tests/dense_ref.py), and the error measures next to it are taken where the smoother works: on the correction
+xs_k - x_k, a fraction of a pixel behind positions of tens of pixels, and on Ps_k scaled to a unit diagonal.
 """
 import numpy as np
+
+LD = np.longdouble
 
 
 def spring_blocks(bars, l0, kappa, X):
@@ -76,3 +82,76 @@ def smooth(P, x, m, F, Q, want_cov=True):
             Ps[k] = P[k] + G @ (Ps[k + 1] - Pp) @ G.T
         steps[k] = dict(Pp=Pp, G=G)
     return xs, (Ps if want_cov else None), steps
+
+
+# ---- the extended-precision reference and its error measures ------------------------------------------------------------
+def smooth_ld(P, x, m, F, Q, refine=2):
+    """The recursion of smooth() in numpy.longdouble, from the same binary64 inputs (F[k]: model_F at the recorded x_k,
+    promoted).  Pp = F P F^T + Q symmetrised, inv(Pp) from dense_ref.chol_inverse_ld, G = (inv(Pp) F P)^T.
+
+    -> dict: xs (K x n), Ps, Pp (lists of K; Pp[0] is None): the refined result (`refine` Newton-Schulz steps on every
+    inverse); xs_raw, Ps_raw: the whole recursion again with the raw inverses T^T T, for the reference's own
+    uncertainty (as dense_ref.reference does); kappas: per step k the kappa_2 of Pp_{k+1} scaled to a unit diagonal
+    (None for k = K-1); kappa: the largest of them.  FloatingPointError where a Pp has no Cholesky factor."""
+    import dense_ref
+    K = len(P)
+    xl = np.asarray(x, LD).reshape(K, -1)
+    ml = np.asarray(m, LD).reshape(K, -1)
+    out = dict(xs=np.empty_like(xl), xs_raw=np.empty_like(xl), Ps=[None] * K, Ps_raw=[None] * K, Pp=[None] * K,
+               kappas=[None] * K)
+    for key in ("xs", "xs_raw"):
+        out[key][K - 1] = xl[K - 1]
+    for key in ("Ps", "Ps_raw"):
+        out[key][K - 1] = np.asarray(P[K - 1], LD)
+    for k in range(K - 2, -1, -1):
+        Fk, Pk = np.asarray(F[k], LD), np.asarray(P[k], LD)
+        Qk = np.asarray(Q[k] if isinstance(Q, (list, tuple)) else Q, LD)
+        FP = Fk @ Pk
+        Pp = FP @ Fk.T + Qk
+        Pp = (Pp + Pp.T) / 2
+        raw, fine = dense_ref.chol_inverse_ld(Pp, refine)
+        out["Pp"][k + 1] = Pp
+        out["kappas"][k] = dense_ref._kappa_scaled(Pp, fine)
+        for inv, xs, Ps in ((fine, out["xs"], out["Ps"]), (raw, out["xs_raw"], out["Ps_raw"])):
+            G = (inv @ FP).T
+            xs[k] = xl[k] + G @ (xs[k + 1] - ml[k + 1])
+            Ps[k] = Pk + G @ (Ps[k + 1] - Pp) @ G.T
+    out["kappa"] = max(kp for kp in out["kappas"] if kp is not None)
+    return out
+
+
+def cov_err(C, Cref):
+    """max over i, j of |C - Cref|_ij / sqrt(Cref_ii Cref_jj): one frame's Ps_k, or a Pp_k"""
+    Cr = np.asarray(Cref, LD)
+    d = np.sqrt(np.diag(Cr))
+    return float(np.max(np.abs(np.asarray(C, LD) - Cr) / np.outer(d, d)))
+
+
+def mean_err(xs, x, xs_ref, Ps_ref):
+    """(position half, velocity half) of |d (c - c_ref)|_2 / |d c_ref|_2 for one frame: c = xs - x the correction the
+    smoother computes, c_ref = xs_ref - x, d = 1 / sqrt(diag Ps_ref)"""
+    xl = np.asarray(x, LD).reshape(-1)
+    d = 1 / np.sqrt(np.diag(np.asarray(Ps_ref, LD)))
+    cr = d * (np.asarray(xs_ref, LD).reshape(-1) - xl)
+    dc = d * (np.asarray(xs, LD).reshape(-1) - xl) - cr
+    h = xl.size // 2
+    return tuple(float(np.sqrt(dc[s] @ dc[s]) / np.sqrt(cr[s] @ cr[s])) for s in (slice(0, h), slice(h, None)))
+
+
+def whitened_correction_rms(x, xs_ref, Ps_ref):
+    """RMS of (xs_ref - x) / sqrt(diag Ps_ref) over one frame: what the relative mean measure divides by"""
+    c = (np.asarray(xs_ref, LD).reshape(-1) - np.asarray(x, LD).reshape(-1)) / np.sqrt(np.diag(np.asarray(Ps_ref, LD)))
+    return float(np.sqrt(np.mean(c * c)))
+
+
+def errors(xs, Ps, x, ref):
+    """per frame k = 0 .. K-2 the triple (mean error of the positions, of the velocities, covariance error) of a result
+    xs (K x n), Ps (K matrices) against smooth_ld's dict -> (K-1) x 3 array"""
+    K = len(ref["Ps"])
+    return np.array([mean_err(xs[k], x[k], ref["xs"][k], ref["Ps"][k]) + (cov_err(Ps[k], ref["Ps"][k]),)
+                     for k in range(K - 1)])
+
+
+def uncertainty(x, ref):
+    """the reference's own: its raw recursion against its refined one, in the same measures"""
+    return errors(ref["xs_raw"], ref["Ps_raw"], x, ref)

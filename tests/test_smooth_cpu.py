@@ -114,8 +114,11 @@ def test_argument_errors_do_not_need_a_gpu(hm):
     assert L.hm_smooth_count(None, None, None) == -1
     assert L.hm_smooth_destroy(None) == 0
     a = np.zeros((4, 4))
-    assert L.hm_op_smooth_gemm(0, 3, 4, _lib.ptr(a), _lib.ptr(a), _lib.ptr(a), _lib.ptr(a)) == -1
-    assert b"which 3" in L.hm_last_error()
+    assert L.hm_op_smooth_gemm(0, 5, 4, _lib.ptr(a), _lib.ptr(a), _lib.ptr(a), _lib.ptr(a)) == -1
+    assert b"which 5" in L.hm_last_error()
+    assert L.hm_op_smooth_gemm(0, -1, 4, _lib.ptr(a), _lib.ptr(a), _lib.ptr(a), _lib.ptr(a)) == -1
+    assert b"which -1" in L.hm_last_error()
+    assert L.hm_op_smooth_gemm(0, 2, 4, _lib.ptr(a), _lib.ptr(a), None, _lib.ptr(a)) == -1
     assert L.hm_op_smooth_gemm(0, 1, 4, _lib.ptr(a), _lib.ptr(a), None, _lib.ptr(a)) == -1
     assert L.hm_op_smooth_gemm(0, 0, 0, _lib.ptr(a), _lib.ptr(a), None, _lib.ptr(a)) == -1
 

@@ -127,6 +127,21 @@ def test_products_against_numpy_exactly(hm, n):
     assert np.array_equal(got, want)
 
 
+@pytest.mark.parametrize("n", [20, 32, 36, 100, 260])
+def test_triangular_products_against_numpy_exactly(hm, n):
+    """The two products G = (T F P)^T T is formed by, on integer data (exact): only the lower triangle of the triangular
+    operand counts -- what lies right of its diagonal is NaN here, as the factorisation may leave it, and must not reach
+    the result.  n = 20: one partial tile; 32: one tile; 36: a 4-row last tile; 100, 260: several tiles, none full at the
+    edge, so slabs left and right of the diagonal exist and the skipped ones are the right ones."""
+    from hydra_mi import smooth
+    rng = np.random.default_rng(1000 + n)
+    T, B = (rng.integers(-4, 5, (n, n)).astype(np.float64) for _ in range(2))
+    Tl = np.tril(T)
+    Tnan = np.where(np.tri(n, dtype=bool), T, np.nan)
+    assert np.array_equal(smooth.gemm("ln", Tnan, B), Tl @ B)
+    assert np.array_equal(smooth.gemm("tl", B, Tnan), B.T @ Tl)
+
+
 # ---- the forward track is untouched ---------------------------------------------------------------------------
 def test_recording_changes_nothing_config1(hm):
     from hydra_mi.smooth import RTSSmoother

@@ -10,7 +10,8 @@
 3. The kernel times come from a run of this tool under
    `rocprofv3 --kernel-trace --stats --output-format csv -- python tools/smooth_cost.py --frames 16` (KERNEL_CMD);
    --kernel-stats names the kernel_stats.csv it wrote, whose rows of the smoother's kernels go into the record with the
-   achieved f64 rate of the three products (2 n^3 flops each, n = 4N) against the chip's f64 matrix peak.
+   achieved f64 rate of the products (2 n^3 flops each, n = 4N; about half where an operand is triangular) against the
+   chip's f64 matrix peak.
 The record is one JSON file (default profiles/smooth_cost.json).
 """
 import argparse
@@ -108,8 +109,9 @@ def main():
         nb = -(-n4 // 32)
         for name, row in ks.items():
             if "k_sm_gemm" in name.split("(")[0]:
-                # SM_SYM (k_sm_gemm<2>) forms the lower tiles only
-                flops = 2.0 * n4 ** 3 * ((nb + 1) / (2.0 * nb) if "<2>" in name else 1.0)
+                # SM_SYM (k_sm_gemm<2>) forms the lower tiles only; SM_LN / SM_TL (<3>, <4>) skip the slabs right of
+                # the triangular operand's diagonal
+                flops = 2.0 * n4 ** 3 * ((nb + 1) / (2.0 * nb) if any(m in name for m in ("<2>", "<3>", "<4>")) else 1.0)
                 ns = float(row["AverageNs"])
                 row["tflops"] = flops / ns / 1e3
                 row["of_f64_matrix_peak"] = row["tflops"] / F64_MATRIX_PEAK_TFLOPS
