@@ -675,6 +675,34 @@ int hm_body_rec_shift(hm_ctx_t h, int B, const int8_t *shifts);
 int hm_body_rec_warp(hm_ctx_t h, int B, const int16_t *q, const uint8_t *valid);
 int hm_body_rec_field_sums(hm_ctx_t h, int k0, int n_frames, int B, const int16_t *q, const uint8_t *valid, uint32_t *out);
 
+/* A running baseline per pixel of the record, and the planes made from it (hydra_mi/detrend.py, DESIGN.md section 14;
+ * csrc/detrend_kernels.h; tests/detrend_ref.py restates the rule in NumPy).  Exact integers throughout.
+ *   Notation: F is the number of recorded frames and v_k(p) is the record's value.  half is 0..1024.  q is an integer
+ *   0..100.  floor is 1..255.  gain is 1..65535.  For frame k and box pixel p:
+ *   Window      frames a = max(0, k - half) .. b = min(F - 1, k + half).  It is clipped at the ends, as roi.baseline
+ *               clips.  n = b - a + 1.
+ *   Baseline    B_k(p) is the value at 0-based rank floor(q (n - 1) / 100) of the window's n values sorted ascending.
+ *               The rank is formed in integers.  This is np.percentile(..., method="lower"), not the linear rule: it
+ *               stays a uint8 and needs no rounding.
+ *   Excess      E_k(p) = max(v_k(p) - B_k(p), 0).
+ *   dF/F byte   D_k(p) = min(255, (gain E_k(p)) / max(B_k(p), floor)), computed by unsigned integer division.
+ *   Off the map and in the padding: v = 0, so B = E = D = 0 without a look at the map.
+ *   Four kinds of plane, `what`: 0 as recorded, 1 baseline, 2 excess, 3 dF/F byte.
+ *   planes      writes the frames k0 .. k0 + n_frames - 1 as full W x H planes into `out`, laid out as hm_body_rec_fetch
+ *               lays them out; what = 0 equals that call.  The windows reach outside [k0, k0 + n_frames) into the whole
+ *               record.
+ *   stats_add   adds every recorded frame's plane of that kind to the statistics of hm_body_stats_*, exactly as if it
+ *               had just been warped, in frame order: the sums and the count are the same, and images / peaks / fetch
+ *               work afterwards unchanged.  It needs the statistics begun (HM_ERR_STATE otherwise).  If count + F would
+ *               pass the capacity it fails with HM_ERR_STATE naming the numbers and adds nothing.
+ *   Both: waiting and state errors are those of hm_body_rec_seed_sums; an argument out of range is HM_ERR_ARG with the
+ *   numbers in hm_last_error.  The record, the map and the tracker do not change by a bit (the registered plane of the
+ *   last warp, which only the next warp reads again after rewriting it, is stats_add's work plane).  The frames are split
+ *   over the grid in runs of hm_ctx_tune "rec_bl_frames" (1..2^24, default 256: same results for every value); the scratch
+ *   follows hm_body_rec_shift's: at most 16 MiB (one frame at least), freed on every return including errors. */
+int hm_body_rec_planes(hm_ctx_t h, int k0, int n_frames, int what, int half, int q, int floor, int gain, uint8_t *out);
+int hm_body_rec_stats_add(hm_ctx_t h, int what, int half, int q, int floor, int gain);
+
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
  * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the

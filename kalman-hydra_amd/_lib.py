@@ -160,6 +160,9 @@ SIGNATURES = {
     "hm_body_rec_shift": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "hm_body_rec_warp": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_body_rec_field_sums": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "hm_body_rec_planes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, c_vp]),
+    "hm_body_rec_stats_add": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "hm_flow_preview": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                        c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_avi_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,

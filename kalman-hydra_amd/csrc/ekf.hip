@@ -331,6 +331,9 @@ extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
     } else if (!strcmp(key, "rec_tp_frames")) {        // frames per workgroup of hm_body_rec_trace_products
         HM_ARG(value >= 1 && value <= REC_TP_MAX, "hm_ctx_tune: rec_tp_frames must be in 1..%d", REC_TP_MAX);
         h->rec.tp_frames = value;
+    } else if (!strcmp(key, "rec_bl_frames")) {        // frames per run of the running baseline (same results for every value)
+        HM_ARG(value >= 1 && value <= REC_BL_MAX, "hm_ctx_tune: rec_bl_frames must be in 1..%d", REC_BL_MAX);
+        h->rec.bl_frames = value;
     } else {
         hm_set_error("hm_ctx_tune: unknown key '%s'", key);
         return HM_ERR_ARG;

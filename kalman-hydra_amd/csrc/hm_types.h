@@ -225,3 +225,4 @@ struct RecBox {
     size_t fs;                         // bytes per frame
 };
 #define REC_TP_MAX 1024                // the most frames of a workgroup's run (hm_ctx_tune "rec_tp_frames")
+#define REC_BL_MAX (1 << 24)           // the most frames of a run of k_rec_running (hm_ctx_tune "rec_bl_frames"; REC_MAX_FRAMES)

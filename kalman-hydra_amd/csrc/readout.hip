@@ -1,13 +1,14 @@
 // The readout of a filter handle: views (hm_view*), the body-frame readout and its statistics (hm_body_*, hm_body_stats_*),
 // the registered video kept on the device with its reductions (hm_body_rec_*), and the flow tool's preview.  Host
-// orchestration and C-ABI (include/hydra_mi.h); the kernels are in view_kernels.h, body_kernels.h, roi_kernels.h and
-// stab_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses its own three members -- view, body, rec -- and reads
+// orchestration and C-ABI (include/hydra_mi.h); the kernels are in view_kernels.h, body_kernels.h, roi_kernels.h,
+// stab_kernels.h and detrend_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses its own three members -- view, body, rec -- and reads
 // W, H, N, T, device, own, stream, the mesh (d_tri, d_uv, d_tex) and, for the overlay view, have_tex, have_obs and o_yim.
 #include "ctx.h"
 #include "view_kernels.h"
 #include "body_kernels.h"
 #include "roi_kernels.h"
 #include "stab_kernels.h"
+#include "detrend_kernels.h"
 #include <algorithm>
 #include <cstring>
 
@@ -1210,6 +1211,144 @@ extern "C" int hm_body_rec_warp(hm_ctx_t h, int B, const int16_t *q, const uint8
         return HM_OK;
     };
     rc = run();
+    const hipError_t fe = h->own.free(&h->rec.scr);           // on the error paths too (the first error is the one reported)
+    if (rc) return rc;
+    HM_HIP(fe);
+    return HM_OK;
+}
+
+// ---- the running baseline per pixel of the record: baseline, excess and dF/F planes (detrend_kernels.h) -------------
+static int det_args_ok(const char *who, int what, int half, int q, int floor, int gain)
+{
+    HM_ARG(what >= 0 && what <= 3, "%s: kind of plane %d outside 0..3 (0 as recorded, 1 baseline, 2 excess, 3 dF/F byte)", who, what);
+    HM_ARG(half >= 0 && half <= DET_HALF_MAX, "%s: half %d outside 0..%d", who, half, DET_HALF_MAX);
+    HM_ARG(q >= 0 && q <= 100, "%s: q %d outside 0..100", who, q);
+    HM_ARG(floor >= 1 && floor <= 255, "%s: floor %d outside 1..255", who, floor);
+    HM_ARG(gain >= 1 && gain <= 65535, "%s: gain %d outside 1..65535", who, gain);
+    return HM_OK;
+}
+
+// frames scratch of at most STAB_SCRATCH_BYTES holds (one frame at least), of `want` frames
+static int det_scratch_frames(const RecBox &b, int want)
+{
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(want, 1), STAB_SCRATCH_BYTES / b.fs));
+}
+
+// queue planes `what` (1..3) of the frames k .. k + m - 1 into dst (m frames in the record's layout)
+static int det_queue(hm_ctx *h, int k, int m, int what, int half, int q, int floor, int gain, uint8_t *dst)
+{
+    RecRunning g;
+    g.b = h->rec.box; g.chunks = (const uint8_t *const *)h->rec.tab; g.F = h->rec.frames; g.k0 = k; g.n = m;
+    g.run = h->rec.bl_frames; g.what = what; g.half = half; g.q = q; g.floor = floor; g.gain = gain; g.out = dst;
+    const int segs = hm_cdiv(g.b.pitch * g.b.bh, 64), runs = hm_cdiv(m, g.run);
+    hipLaunchKernelGGL(k_rec_running, dim3(segs, std::min(runs, 65535)), dim3(64), DET_LDS_BYTES, h->stream, g);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_planes(hm_ctx_t h, int k0, int n_frames, int what, int half, int q, int floor, int gain, uint8_t *out)
+{
+    int rc = det_args_ok("hm_body_rec_planes", what, half, q, floor, gain);
+    if (rc) return rc;
+    HM_ARG(h != nullptr, "hm_body_rec_planes: NULL handle");
+    HM_JOIN_LAZY(h);
+    rc = body_rec_ready(h, "hm_body_rec_planes");
+    if (rc) return rc;
+    HM_ARG(k0 >= 0 && n_frames >= 0 && k0 <= h->rec.frames && n_frames <= h->rec.frames - k0,
+           "hm_body_rec_planes: frames %d .. %d of a record of %d", k0, k0 + n_frames - 1, h->rec.frames);
+    HM_ARG(out || n_frames == 0, "hm_body_rec_planes: NULL output");
+    const RecBox &b = h->rec.box;
+    const size_t px = (size_t)h->W * h->H;
+    // one box frame on the device -> a full plane of the caller's (as hm_body_rec_fetch lays it out)
+    auto expand = [&](const uint8_t *src, uint8_t *o) -> int {
+        memset(o, 0, px);
+        HM_HIP(hipMemcpy2D(o + (size_t)b.r0 * h->W + b.c0, (size_t)h->W, src, (size_t)b.pitch, (size_t)b.bw, (size_t)b.bh,
+                           hipMemcpyDeviceToHost));
+        return HM_OK;
+    };
+    if (what == 0) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        for (int k = 0; k < n_frames; k++) {
+            const int ch = (k0 + k) / b.fpc;
+            rc = expand(h->rec.chunks[ch] + (size_t)(k0 + k - ch * b.fpc) * b.fs, out + (size_t)k * px);
+            if (rc) return rc;
+        }
+        return HM_OK;
+    }
+    const int per = det_scratch_frames(b, n_frames);
+    HM_HIP(h->own.grow(&h->rec.scr, (size_t)per * b.fs));
+    auto run = [&]() -> int {
+        for (int k = 0; k < n_frames;) {
+            const int m = std::min(per, n_frames - k);
+            int r = det_queue(h, k0 + k, m, what, half, q, floor, gain, h->rec.scr);
+            if (r) return r;
+            HM_HIP(hipStreamSynchronize(h->stream));
+            for (int j = 0; j < m; j++) {
+                r = expand(h->rec.scr + (size_t)j * b.fs, out + (size_t)(k + j) * px);
+                if (r) return r;
+            }
+            k += m;
+        }
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    };
+    rc = run();
+    const hipError_t fe = h->own.free(&h->rec.scr);           // on the error paths too (the first error is the one reported)
+    if (rc) return rc;
+    HM_HIP(fe);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_stats_add(hm_ctx_t h, int what, int half, int q, int floor, int gain)
+{
+    int rc = det_args_ok("hm_body_rec_stats_add", what, half, q, floor, gain);
+    if (rc) return rc;
+    HM_ARG(h != nullptr, "hm_body_rec_stats_add: NULL handle");
+    HM_JOIN_LAZY(h);
+    rc = body_rec_ready(h, "hm_body_rec_stats_add");
+    if (rc) return rc;
+    if (!h->body.stats_on) { hm_set_error("hm_body_rec_stats_add: no statistics (hm_body_stats_begin first)"); return HM_ERR_STATE; }
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames, n = h->W * h->H;
+    if (h->body.stats_frames + F > h->body.stats_cap) {
+        hm_set_error("hm_body_rec_stats_add: the statistics hold %d frames and the record %d, their capacity is %d (sums of 32 bits "
+                     "are exact up to %d frames): nothing added", h->body.stats_frames, F, h->body.stats_cap, BODY_STATS_CAP);
+        return HM_ERR_STATE;
+    }
+    const BodyStats st = body_stats_planes(h);
+    // a box frame pasted into the registered plane, then added as a warp's frame is
+    auto add = [&](const uint8_t *src) -> int {
+        hipLaunchKernelGGL(k_rec_paste, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, n, h->W, b, src, h->body.reg);
+        hipLaunchKernelGGL(k_body_stats_add, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, n, h->W,
+                           (const int *)h->body.tri, (const uint8_t *)h->body.reg, st);
+        HM_HIP(hipGetLastError());
+        h->body.stats_frames++;
+        return HM_OK;
+    };
+    if (what == 0) {
+        for (int k = 0; k < F; k++) {
+            const int ch = k / b.fpc;
+            rc = add(h->rec.chunks[ch] + (size_t)(k - ch * b.fpc) * b.fs);
+            if (rc) return rc;
+        }
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const int per = det_scratch_frames(b, F);
+    HM_HIP(h->own.grow(&h->rec.scr, (size_t)per * b.fs));
+    auto run = [&]() -> int {
+        for (int k = 0; k < F;) {
+            const int m = std::min(per, F - k);
+            int r = det_queue(h, k, m, what, half, q, floor, gain, h->rec.scr);     // (behind the adds that read the scratch)
+            for (int j = 0; !r && j < m; j++) r = add(h->rec.scr + (size_t)j * b.fs);
+            if (r) return r;
+            k += m;
+        }
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(h->stream);            // (nothing queued reads the scratch once it is freed)
     const hipError_t fe = h->own.free(&h->rec.scr);           // on the error paths too (the first error is the one reported)
     if (rc) return rc;
     HM_HIP(fe);

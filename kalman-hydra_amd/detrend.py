@@ -1,0 +1,90 @@
+"""A running baseline per pixel of the kept registered video: seeds that survive slow brightness changes, and a dF/F video.
+
+Bleaching and the slow brightening of tissue as the animal contracts are common to neighbouring pixels: they inflate the
+local correlation of the raw registered values everywhere, and seeds found there land on the drift instead of the cells.
+Here every pixel of the record a BodyReadout(keep=True) holds gets a baseline of its own -- the value at rank
+q (n - 1) // 100 of the n frames k - half .. k + half, clipped at the ends (np.percentile(method="lower")) -- on the
+device, in exact integers (hm_body_rec_planes / hm_body_rec_stats_add in include/hydra_mi.h, csrc/detrend_kernels.h;
+tests/detrend_ref.py restates it).  The excess max(v - baseline, 0) is what the summary images and the seeds are made
+from; the dF/F byte min(255, gain excess // max(baseline, floor)) is what the video shows.
+
+    body = BodyReadout(kf, keep=True)
+    for each frame: kf.compute(...); body.registered(kf.state.X, raw_frame)
+    points, scores = detrend.find_points(body, 12)            # seeds of the excess video
+    detrend.write_video(body, "dff.avi")                      # the dF/F video, grey, in the body frame
+
+The record stays raw: the ROI traces of hydra_mi.roi need the raw baseline for their denominator.
+"""
+import numpy as np
+
+from .videoio import AviWriter
+
+KINDS = ("recorded", "baseline", "excess", "dff")
+DEFAULT_HALF = 20          # frames either side of the window: wider windows leave drift in
+DEFAULT_Q = 10
+DEFAULT_FLOOR = 16         # grey levels: darker baselines do not blow the ratio up
+DEFAULT_GAIN = 255         # dF/F = 1 is white
+VIDEO_BYTES = 64 << 20     # host memory a block of write_video's planes takes at most
+
+
+def _check(who, what, half, q, floor=1, gain=1):
+    if what not in KINDS:
+        raise ValueError("%s: what %r (one of %s)" % (who, what, ", ".join(KINDS)))
+    for name, v, lo, hi in (("half", half, 0, 1024), ("q", q, 0, 100), ("floor", floor, 1, 255), ("gain", gain, 1, 65535)):
+        if int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s: %s %r outside %d..%d (a whole number)" % (who, name, v, lo, hi))
+
+
+def _record(who, body):
+    if not getattr(body, "keep", False):
+        raise RuntimeError("%s: the readout was made without keep=True" % who)
+    return body.r
+
+
+def blocks(frames, block):
+    """[(k0, n), ...]: `frames` frames walked in blocks of `block`"""
+    frames, block = int(frames), int(block)
+    if block < 1:
+        raise ValueError("blocks of %d frames" % block)
+    return [(k, min(block, frames - k)) for k in range(0, frames, block)]
+
+
+def summary(body, what="excess", half=DEFAULT_HALF, q=DEFAULT_Q, floor=DEFAULT_FLOOR, gain=DEFAULT_GAIN):
+    """The summary images of BodyReadout.summary for the planes of kind `what` of the kept record (all recorded frames):
+    {"frames": F, "mean", "std", "corr": (H, W) float64, NaN outside the mesh, "max": (H, W) uint8}.  Begins the
+    tracker's statistics afresh and leaves them holding these planes (find_points searches them); what
+    BodyReadout.summary returned before stays as it is in the caller's hands."""
+    _check("detrend.summary", what, half, q, floor, gain)
+    r = _record("detrend.summary", body)
+    r.body_stats_begin()
+    r.body_rec_stats_add(what, half, q, floor, gain)
+    mean, std, corr, vmax = r.body_stats_images()
+    return {"frames": r.body_stats_count(), "mean": mean, "std": std, "max": vmax, "corr": corr}
+
+
+def find_points(body, n, radius=6, score="corr", min_score=None, what="excess", half=DEFAULT_HALF, q=DEFAULT_Q):
+    """BodyReadout.find_points on the summary images of the planes of kind `what`: the n best local maxima of "corr",
+    "std" or "range" within (2 radius + 1)^2 windows -> (points (P <= n, 2) float64 at the pixel centres, scores (P,))."""
+    _check("detrend.find_points", what, half, q)
+    r = _record("detrend.find_points", body)
+    r.body_stats_begin()
+    r.body_rec_stats_add(what, half, q, DEFAULT_FLOOR, DEFAULT_GAIN)
+    idx, sc, _ = r.body_stats_peaks(score, radius, -np.inf if min_score is None else float(min_score), int(n))
+    rr, cc = np.divmod(idx.astype(np.int64), body.W)
+    return np.stack((cc + 0.5, rr + 0.5), 1).astype(np.float64).reshape(-1, 2), sc
+
+
+def write_video(body, path, half=DEFAULT_HALF, q=DEFAULT_Q, floor=DEFAULT_FLOOR, gain=DEFAULT_GAIN, block=None):
+    """The dF/F bytes of every recorded frame as a grey AVI (B = G = R) in the body frame -> frames written.  The planes
+    are fetched `block` frames at a time (default: VIDEO_BYTES worth), so host memory stays bounded for any record."""
+    _check("detrend.write_video", "dff", half, q, floor, gain)
+    r = _record("detrend.write_video", body)
+    F = r.body_rec_count()
+    if block is None:
+        block = max(1, VIDEO_BYTES // (body.W * body.H))
+    walk = blocks(F, block)
+    with AviWriter(path, body.W, body.H) as video:
+        for k0, n in walk:
+            for plane in r.body_rec_planes("dff", half, q, floor, gain, k0, n):
+                video.write(np.repeat(plane[:, :, None], 3, axis=2))
+        return video.frames

@@ -518,6 +518,28 @@ class Renderer:
             raise ValueError("body_rec_warp: q of %d frames for a record of %d" % (q.shape[0], F))
         _lib.check(_lib.lib().hm_body_rec_warp(self._h, int(B), _lib.ptr(q), _lib.ptr(valid)), "hm_body_rec_warp")
 
+    # -- the running baseline per pixel of the record (hm_body_rec_planes / _stats_add; hydra_mi.detrend) -----
+    PLANES = {"recorded": 0, "baseline": 1, "excess": 2, "dff": 3}
+
+    def body_rec_planes(self, what, half, q, floor=1, gain=1, k0=0, n=None):
+        """hm_body_rec_planes: -> (n, H, W) uint8, the planes of kind `what` ("recorded", "baseline", "excess", "dff", or
+        0..3) of the recorded frames k0 .. k0 + n - 1 (default: all from k0): the baseline is the value at rank
+        q (window - 1) // 100 of the frames k - half .. k + half of the whole record, the excess what lies above it, dff
+        min(255, gain excess // max(baseline, floor))."""
+        what = self.PLANES[what] if isinstance(what, str) else int(what)
+        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
+        _lib.check(_lib.lib().hm_body_rec_planes(self._h, int(k0), n, what, int(half), int(q), int(floor), int(gain),
+                                                 _lib.ptr(out)), "hm_body_rec_planes")
+        return out
+
+    def body_rec_stats_add(self, what, half, q, floor=1, gain=1):
+        """hm_body_rec_stats_add: add every recorded frame's plane of kind `what` (as body_rec_planes) to the statistics
+        begun with body_stats_begin, as if each had just been warped."""
+        what = self.PLANES[what] if isinstance(what, str) else int(what)
+        _lib.check(_lib.lib().hm_body_rec_stats_add(self._h, what, int(half), int(q), int(floor), int(gain)),
+                   "hm_body_rec_stats_add")
+
     def screenshot(self, saveall=True, basename="screenshot", X=None):
         """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask
         at state X (default: the vertex buffer) and returns the overlay.  Unlike the reference the names carry no

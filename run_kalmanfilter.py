@@ -58,6 +58,19 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      patches filled in by their neighbours, the frames sampled bilinearly.  The choice for the smooth
                      sub-pixel motion a tracker leaves; patch for regions that move rigidly against each other.  The states
                      file then also gets stab_q (frames x patches x 2, int16, (dx, dy) in 1/16 px).
+    --detrend        with --find-points: search the summary images of the excess video instead of the raw one (hydra_mi.detrend):
+                     every pixel of the kept registered video less its own running baseline, the value at rank
+                     q (n - 1) // 100 of the n frames k - half .. k + half (--detrend-half, default 20; --detrend-q, default
+                     10), computed on the device.  Seeds found this way survive bleaching and slow brightness changes of the
+                     tissue.  Keeps the registered video on the device as --rois does (same budget, --rois-max-gb; a video
+                     that does not fit is said to be so and searched raw).  The states file gets detrend_mean, detrend_std,
+                     detrend_max, detrend_corr, the summary images of the excess video; body_* stay those of the frames as
+                     tracked.  With --stabilize the record is stabilised first and the seeds are found after it.
+    --resummarize    with --stabilize, without --detrend: detrend_* are the summary images of the stabilised record as it is,
+                     and --find-points searches those.
+    --dff-video OUT.avi   the dF/F video in the body frame, grey: min(255, gain excess // max(baseline, floor)) per pixel
+                     (--dff-gain, default 255; --dff-floor, default 16; the window of --detrend-half, --detrend-q), of the
+                     stabilised record with --stabilize.  Keeps the registered video on the device as --rois does.
     --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
                      (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
                      diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
@@ -79,6 +92,7 @@ import hydra_mi  # noqa: F401
 from hydra_mi import cellview
 from hydra_mi import kalman
 from hydra_mi import demix
+from hydra_mi import detrend
 from hydra_mi import roi
 from hydra_mi import stabilize
 from hydra_mi.body import (BodyReadout, read_out, read_out_recorded, read_points_csv, record_bytes, write_points_csv,
@@ -128,6 +142,16 @@ def main(argv=None):
     parser.add_argument("--stab-mode", default="patch", choices=stabilize.MODES,
                         help="patch: one whole-pixel shift per patch; field: a smooth sub-pixel shift field between the patch "
                              "centres (stab_q in the states file)")
+    parser.add_argument("--detrend", action="store_true",
+                        help="with --find-points: find the cells in the excess video, every pixel less its running baseline "
+                             "(detrend_* arrays)")
+    parser.add_argument("--detrend-half", default=detrend.DEFAULT_HALF, type=int, help="frames either side of the baseline's window (0..1024)")
+    parser.add_argument("--detrend-q", default=detrend.DEFAULT_Q, type=int, help="the baseline's percentile (0..100, a whole number)")
+    parser.add_argument("--resummarize", action="store_true",
+                        help="with --stabilize: the summary images of the stabilised record (detrend_* arrays), searched by --find-points")
+    parser.add_argument("--dff-video", default=None, metavar="OUT.avi", help="write the dF/F video in the body frame here (.avi)")
+    parser.add_argument("--dff-floor", default=detrend.DEFAULT_FLOOR, type=int, help="the least denominator of dF/F (1..255 grey levels)")
+    parser.add_argument("--dff-gain", default=detrend.DEFAULT_GAIN, type=int, help="the byte dF/F = 1 becomes (1..65535)")
     parser.add_argument("--smooth", action="store_true", help="smooth the track backward: Xs, Xs_std in the states file")
     parser.add_argument("--smooth-max-gb", default=8.0, type=float, help="device memory the smoother may take (GiB)")
     parser.add_argument("--cells-video", default=None, metavar="OUT.avi",
@@ -155,8 +179,17 @@ def main(argv=None):
             parser.error("--demix-iters needs at least one round")
     if args.rois and args.find_points is None and args.points is None:
         parser.error("--rois reads cells out: it needs --find-points or --points")
+    if args.detrend and args.find_points is None:
+        parser.error("--detrend finds the cells in the excess video: it needs --find-points")
+    if args.resummarize and (not args.stabilize or args.detrend):
+        parser.error("--resummarize sums the stabilised record up: it needs --stabilize, and not --detrend")
+    keep_record = args.detrend or args.resummarize or args.dff_video is not None
+    if keep_record and not (0 <= args.detrend_half <= 1024 and 0 <= args.detrend_q <= 100 and 1 <= args.dff_floor <= 255
+                            and 1 <= args.dff_gain <= 65535):
+        parser.error("the running baseline needs a --detrend-half in 0..1024, a --detrend-q in 0..100, a --dff-floor in 1..255 "
+                     "and a --dff-gain in 1..65535")
     if args.stabilize:
-        if not args.rois:
+        if not (args.rois or keep_record):
             parser.error("--stabilize works on the kept record: it needs --rois or --demix")
         if not (4 <= args.stab_patch <= 64 and 0 <= args.stab_search <= 8 and args.stab_passes >= 1):
             parser.error("--stabilize needs a --stab-patch in 4..64, a --stab-search in 0..8 and at least one pass")
@@ -182,20 +215,22 @@ def main(argv=None):
     if args.name is not None:
         os.makedirs("screenshots", exist_ok=True)
     find = args.find_points is not None
-    readout = args.registered is not None or args.points is not None or find
+    readout = args.registered is not None or args.points is not None or find or keep_record
     points = read_points_csv(args.points)[1] if args.points is not None else None
     reg_video = AviWriter(args.registered, W, H) if args.registered is not None else None
 
     def make_body(kf):
         if not readout:
             return None
-        keep, budget = args.rois, int(args.rois_max_gb * (1 << 30))
+        keep, budget = args.rois or keep_record, int(args.rois_max_gb * (1 << 30))
         if keep:
             probe = kf.state.renderer.body_map()[0]
             need = record_bytes(probe, max(capture.frames.shape[0] - 1, 1))
             if need > budget:
                 print("The registered video takes %d bytes on the device, --rois-max-gb allows %d: no ROIs, %sthe disc "
                       "read-out instead" % (need, budget, "no stabilisation, " if args.stabilize else ""))
+                if keep_record:
+                    print("No running baseline either: no --detrend, --resummarize or --dff-video")
                 keep = False
         body = BodyReadout(kf, points=points, point_radius=args.point_radius, video=reg_video, stats=find, keep=keep,
                            keep_bytes=budget)
@@ -275,9 +310,25 @@ def main(argv=None):
         print("Stabilised%s: %d patches of %d px, search %d, %d passes: %.1f %% fallbacks, mean |shift| %.3f px" % (
             " (field)" if args.stab_mode == "field" else "", est["shifts"].shape[1], args.stab_patch, args.stab_search,
             args.stab_passes, 100.0 * est["fallback"].mean(), np.abs(moved).sum(2).mean()))
+    det_kind = "excess" if args.detrend else "recorded" if args.resummarize else None
+    if det_kind is not None and not (body is not None and body.keep and len(states)):
+        det_kind = None
+
+    def detrended_summary():
+        # the statistics begun afresh on the device and fed the kept record's planes: find_points below searches these
+        d_img = detrend.summary(body, det_kind, args.detrend_half, args.detrend_q)
+        extra.update(detrend_mean=d_img["mean"], detrend_std=d_img["std"], detrend_max=d_img["max"], detrend_corr=d_img["corr"])
+        if det_kind == "excess":
+            print("Detrended: the excess over the running baseline (half %d, q %d) of %d frames summed up" % (
+                args.detrend_half, args.detrend_q, d_img["frames"]))
+        else:
+            print("Resummarised: %d frames of the stabilised record summed up" % d_img["frames"])
+
     if find:
         # the cells need the whole video and the traces need the cells: a second pass over the recorded states
         sm_img = body.summary()
+        if det_kind is not None:
+            detrended_summary()
         found, scores = body.find_points(args.find_points, radius=args.find_radius, score=args.find_score)
         kf.state.renderer.body_stats_end()
         extra.update(body_mean=sm_img["mean"], body_std=sm_img["std"], body_max=sm_img["max"], body_corr=sm_img["corr"],
@@ -294,11 +345,17 @@ def main(argv=None):
         if args.points_out is not None:
             write_points_csv(args.points_out, found)
             print("Points found: %s" % args.points_out)
+    elif det_kind is not None:
+        detrended_summary()
+        kf.state.renderer.body_stats_end()
     if args.cells_video is not None:
         cv_points = found if find else points
     if body is not None and body.keep:
+        if args.dff_video is not None and len(states):
+            n_dff = detrend.write_video(body, args.dff_video, args.detrend_half, args.detrend_q, args.dff_floor, args.dff_gain)
+            print("dF/F video: %d frames in %s" % (n_dff, args.dff_video))
         pts = found if find else points
-        inside = np.flatnonzero(body.locate(pts)[0] >= 0)
+        inside = np.flatnonzero(body.locate(pts)[0] >= 0) if args.rois else []
         if len(inside) and len(states):
             if args.demix:
                 e = demix.extract(body, pts[inside], iters=args.demix_iters, r_disc=args.point_radius, thr=args.roi_thr,
