@@ -703,6 +703,39 @@ int hm_body_rec_field_sums(hm_ctx_t h, int k0, int n_frames, int B, const int16_
 int hm_body_rec_planes(hm_ctx_t h, int k0, int n_frames, int what, int half, int q, int floor, int gain, uint8_t *out);
 int hm_body_rec_stats_add(hm_ctx_t h, int what, int half, int q, int floor, int gain);
 
+/* The residual of the record: every recorded frame minus the light a model of the cells puts there (hydra_mi/residual.py,
+ * DESIGN.md section 15; csrc/residual_kernels.h; tests/residual_ref.py restates the rule in NumPy).  Exact integers.
+ *   labels, weights   n_layers (1..4) planes of W*H in body coordinates, exactly what hm_view_set_cells takes: int32 labels,
+ *               -1 none, 0 .. L-1 (L is 1..65536); uint16 weights, NULL: 65535 everywhere.
+ *   traces      F x L int32, row k for recorded frame k; F is the record's frame count, also for `planes`.
+ *   blank       W*H bytes, NULL: none.  offset is 0..255.
+ *   Rule        For recorded frame k and map pixel p, with record value v_k(p):
+ *               acc = sum_j weights[j][p] * traces[k][labels[j][p]], over the layers j with a label >= 0, in int64.  Since
+ *               4 * 65535 * 2^31 < 2^50, no order matters.
+ *               m = (acc + 2^23) >> 24, an arithmetic shift (floor): half a grey level goes up, -0.5 -> 0 and +0.5 -> 1.
+ *               A weight of 65535 with a trace of rint(l * 2^24 / 65535) takes off l grey levels.
+ *               r = offset + v_k(p) - m, and R_k(p) = min(255, max(0, r)).
+ *               R_k(p) = 0 where blank[p] != 0, outside the map, and in the padding.  A blanked pixel is constant: by the
+ *               rule of hm_body_stats_images it gets corr 0 and drops out of its neighbours' averages.
+ *               *clipped (may be NULL) is the number of (frame, map pixel, not blanked) with r outside 0..255, over the
+ *               frames the call covers.
+ *   planes      writes the frames k0 .. k0 + n_frames - 1 as full W x H planes into `out`, laid out as hm_body_rec_planes
+ *               lays them out.
+ *   stats_add   adds every recorded frame's residual plane to the statistics of hm_body_stats_*, exactly as
+ *               hm_body_rec_stats_add adds its planes: in frame order, the statistics begun (HM_ERR_STATE otherwise), and
+ *               if count + F would pass the capacity it fails with HM_ERR_STATE naming the numbers and adds nothing.
+ *   Both: HM_ERR_ARG with the numbers in hm_last_error for n_layers outside 1..4, L outside 1..65536, offset outside
+ *   0..255, NULL labels or traces (all four before the handle is looked at), a frame range outside the record, F L >= 2^30,
+ *   and a label outside -1..L-1 anywhere in the planes (checked on the host while the box is packed: nothing has run).
+ *   HM_ERR_STATE without a record or without a recorded frame.  The record, the map and the tracker do not change by a bit.
+ *   The frames are split over the grid in runs of hm_ctx_tune "rec_res_frames" (1..2^24, default 8: same results for
+ *   every value); the scratch follows hm_body_rec_planes': at most 16 MiB (one frame at least), freed on every return
+ *   including errors. */
+int hm_body_rec_residual_planes(hm_ctx_t h, int k0, int n_frames, int n_layers, const int32_t *labels, const uint16_t *weights,
+                                int L, const int32_t *traces, const uint8_t *blank, int offset, uint8_t *out, uint64_t *clipped);
+int hm_body_rec_residual_stats_add(hm_ctx_t h, int n_layers, const int32_t *labels, const uint16_t *weights, int L,
+                                   const int32_t *traces, const uint8_t *blank, int offset, uint64_t *clipped);
+
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
  * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the

@@ -334,6 +334,9 @@ extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
     } else if (!strcmp(key, "rec_bl_frames")) {        // frames per run of the running baseline (same results for every value)
         HM_ARG(value >= 1 && value <= REC_BL_MAX, "hm_ctx_tune: rec_bl_frames must be in 1..%d", REC_BL_MAX);
         h->rec.bl_frames = value;
+    } else if (!strcmp(key, "rec_res_frames")) {       // frames per run of the residual planes (same results for every value)
+        HM_ARG(value >= 1 && value <= REC_RES_MAX, "hm_ctx_tune: rec_res_frames must be in 1..%d", REC_RES_MAX);
+        h->rec.res_frames = value;
     } else {
         hm_set_error("hm_ctx_tune: unknown key '%s'", key);
         return HM_ERR_ARG;

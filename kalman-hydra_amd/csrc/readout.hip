@@ -9,6 +9,7 @@
 #include "roi_kernels.h"
 #include "stab_kernels.h"
 #include "detrend_kernels.h"
+#include "residual_kernels.h"
 #include <algorithm>
 #include <cstring>
 
@@ -1346,6 +1347,188 @@ extern "C" int hm_body_rec_stats_add(hm_ctx_t h, int what, int half, int q, int 
         }
         HM_HIP(hipStreamSynchronize(h->stream));
         return HM_OK;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(h->stream);            // (nothing queued reads the scratch once it is freed)
+    const hipError_t fe = h->own.free(&h->rec.scr);           // on the error paths too (the first error is the one reported)
+    if (rc) return rc;
+    HM_HIP(fe);
+    return HM_OK;
+}
+
+// ---- the residual of the record: what the cells' model leaves of every frame (residual_kernels.h) --------------------
+static int res_args_ok(const char *who, int n_layers, const int32_t *labels, int L, const int32_t *traces, int offset)
+{
+    HM_ARG(n_layers >= 1 && n_layers <= 4, "%s: %d layers outside 1..4", who, n_layers);
+    HM_ARG(L >= 1 && L <= REC_RES_LMAX, "%s: %d labels outside 1..%d", who, L, REC_RES_LMAX);
+    HM_ARG(offset >= 0 && offset <= 255, "%s: offset %d outside 0..255", who, offset);
+    HM_ARG(labels && traces, "%s: NULL labels or traces", who);
+    return HM_OK;
+}
+
+// The cells of the box, packed for k_rec_residual and sent to the device with the traces; a label outside -1 .. L - 1
+// anywhere in the planes is refused here.  Off the map and under a blank nothing is packed: a segment of such pixels
+// alone costs no layer.
+static int res_pack(hm_ctx *h, const char *who, int n_layers, const int32_t *labels, const uint16_t *weights, int L,
+                    const int32_t *traces, const uint8_t *blank, int offset, bool want_clipped, RecResidual &g)
+{
+    const RecBox &b = h->rec.box;
+    const size_t n = (size_t)h->W * h->H, npx = (size_t)b.pitch * b.bh;
+    const int F = h->rec.frames, segs = hm_cdiv((int)(npx >> 2), 64);
+    HM_ARG((long long)F * L < (1ll << 30), "%s: %d frames x %d labels", who, F, L);
+    for (int j = 0; j < n_layers; j++)
+        for (size_t p = 0; p < n; p++) {
+            const int s = labels[(size_t)j * n + p];
+            HM_ARG(s >= -1 && s < L, "%s: label %d at pixel %zu of layer %d outside -1..%d", who, s, p, j, L - 1);
+        }
+    std::vector<unsigned> lay((size_t)n_layers * npx, 0u);
+    std::vector<uint8_t> live(npx, 0), seg_nl(segs, 0);
+    for (int yb = 0; yb < b.bh; yb++)
+        for (int x = 0; x < b.bw; x++) {
+            const size_t p = (size_t)(b.r0 + yb) * h->W + b.c0 + x, i = (size_t)yb * b.pitch + x;
+            if (h->body.h_tri[p] < 0 || (blank && blank[p])) continue;
+            live[i] = 1;
+            for (int j = 0; j < n_layers; j++) {
+                const int s = labels[(size_t)j * n + p];
+                if (s < 0) continue;
+                lay[(size_t)j * npx + i] = ((unsigned)s << 16) | (weights ? (unsigned)weights[(size_t)j * n + p] : 65535u);
+                uint8_t &top = seg_nl[i >> 8];
+                top = std::max<uint8_t>(top, (uint8_t)(j + 1));
+            }
+        }
+    unsigned *d_lay = nullptr, *d_live = nullptr;
+    uint8_t *d_seg = nullptr;
+    int *d_tr = nullptr;
+    unsigned long long *d_clip = nullptr;
+    const int rc = body_rec_carve(h, [&](RecCarve &cv) {
+        d_lay = cv.take<unsigned>(lay.size());
+        d_live = cv.take<unsigned>(npx >> 2);
+        d_seg = cv.take<uint8_t>(segs);
+        d_tr = cv.take<int>((size_t)F * L);
+        d_clip = cv.take<unsigned long long>(1);
+    });
+    if (rc) return rc;
+    // (pageable sources: each copy has left the host array when the call returns)
+    HM_HIP(hipMemcpyAsync(d_lay, lay.data(), lay.size() * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_live, live.data(), npx, hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_seg, seg_nl.data(), (size_t)segs, hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_tr, traces, (size_t)F * L * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(d_clip, 0, sizeof(unsigned long long), h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.run = h->rec.res_frames; g.nl = n_layers; g.L = L; g.offset = offset;
+    g.lay = d_lay; g.live = d_live; g.seg_nl = d_seg; g.traces = d_tr; g.clipped = want_clipped ? d_clip : nullptr;
+    return HM_OK;
+}
+
+// queue the residual planes of the frames k .. k + m - 1 into dst (m frames in the record's layout)
+static int res_queue(hm_ctx *h, RecResidual g, int k, int m, uint8_t *dst)
+{
+    g.k0 = k; g.n = m; g.out = dst;
+    const int segs = hm_cdiv((g.b.pitch * g.b.bh) >> 2, 64), runs = hm_cdiv(m, g.run);
+    hipLaunchKernelGGL(k_rec_residual, dim3(segs, std::min(runs, 65535)), dim3(64), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+static int res_clipped(hm_ctx *h, const RecResidual &g, uint64_t *clipped)
+{
+    if (!clipped) return HM_OK;
+    unsigned long long c = 0;
+    HM_HIP(hipMemcpyAsync(&c, g.clipped, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    *clipped = c;
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_residual_planes(hm_ctx_t h, int k0, int n_frames, int n_layers, const int32_t *labels,
+                                           const uint16_t *weights, int L, const int32_t *traces, const uint8_t *blank,
+                                           int offset, uint8_t *out, uint64_t *clipped)
+{
+    int rc = res_args_ok("hm_body_rec_residual_planes", n_layers, labels, L, traces, offset);
+    if (rc) return rc;
+    HM_ARG(h != nullptr, "hm_body_rec_residual_planes: NULL handle");
+    HM_JOIN_LAZY(h);
+    rc = body_rec_ready(h, "hm_body_rec_residual_planes");
+    if (rc) return rc;
+    HM_ARG(k0 >= 0 && n_frames >= 0 && k0 <= h->rec.frames && n_frames <= h->rec.frames - k0,
+           "hm_body_rec_residual_planes: frames %d .. %d of a record of %d", k0, k0 + n_frames - 1, h->rec.frames);
+    HM_ARG(out || n_frames == 0, "hm_body_rec_residual_planes: NULL output");
+    RecResidual g;
+    rc = res_pack(h, "hm_body_rec_residual_planes", n_layers, labels, weights, L, traces, blank, offset, clipped != nullptr, g);
+    if (rc) return rc;
+    const RecBox &b = h->rec.box;
+    const size_t px = (size_t)h->W * h->H;
+    const int per = det_scratch_frames(b, n_frames);
+    HM_HIP(h->own.grow(&h->rec.scr, (size_t)per * b.fs));
+    auto run = [&]() -> int {
+        for (int k = 0; k < n_frames;) {
+            const int m = std::min(per, n_frames - k);
+            int r = res_queue(h, g, k0 + k, m, h->rec.scr);
+            if (r) return r;
+            HM_HIP(hipStreamSynchronize(h->stream));
+            for (int j = 0; j < m; j++) {
+                uint8_t *o = out + (size_t)(k + j) * px;
+                memset(o, 0, px);
+                HM_HIP(hipMemcpy2D(o + (size_t)b.r0 * h->W + b.c0, (size_t)h->W, h->rec.scr + (size_t)j * b.fs, (size_t)b.pitch,
+                                   (size_t)b.bw, (size_t)b.bh, hipMemcpyDeviceToHost));
+            }
+            k += m;
+        }
+        return res_clipped(h, g, clipped);
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(h->stream);
+    const hipError_t fe = h->own.free(&h->rec.scr);           // on the error paths too (the first error is the one reported)
+    if (rc) return rc;
+    HM_HIP(fe);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_residual_stats_add(hm_ctx_t h, int n_layers, const int32_t *labels, const uint16_t *weights, int L,
+                                              const int32_t *traces, const uint8_t *blank, int offset, uint64_t *clipped)
+{
+    int rc = res_args_ok("hm_body_rec_residual_stats_add", n_layers, labels, L, traces, offset);
+    if (rc) return rc;
+    HM_ARG(h != nullptr, "hm_body_rec_residual_stats_add: NULL handle");
+    HM_JOIN_LAZY(h);
+    rc = body_rec_ready(h, "hm_body_rec_residual_stats_add");
+    if (rc) return rc;
+    if (!h->body.stats_on) {
+        hm_set_error("hm_body_rec_residual_stats_add: no statistics (hm_body_stats_begin first)");
+        return HM_ERR_STATE;
+    }
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames, n = h->W * h->H;
+    if (h->body.stats_frames + F > h->body.stats_cap) {
+        hm_set_error("hm_body_rec_residual_stats_add: the statistics hold %d frames and the record %d, their capacity is %d (sums "
+                     "of 32 bits are exact up to %d frames): nothing added", h->body.stats_frames, F, h->body.stats_cap,
+                     BODY_STATS_CAP);
+        return HM_ERR_STATE;
+    }
+    RecResidual g;
+    rc = res_pack(h, "hm_body_rec_residual_stats_add", n_layers, labels, weights, L, traces, blank, offset, clipped != nullptr, g);
+    if (rc) return rc;
+    const BodyStats st = body_stats_planes(h);
+    const int per = det_scratch_frames(b, F);
+    HM_HIP(h->own.grow(&h->rec.scr, (size_t)per * b.fs));
+    auto run = [&]() -> int {
+        for (int k = 0; k < F;) {
+            const int m = std::min(per, F - k);
+            const int r = res_queue(h, g, k, m, h->rec.scr);                    // (behind the adds that read the scratch)
+            if (r) return r;
+            // a box frame pasted into the registered plane, then added as a warp's frame is (as hm_body_rec_stats_add)
+            for (int j = 0; j < m; j++) {
+                hipLaunchKernelGGL(k_rec_paste, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, n, h->W, b,
+                                   (const uint8_t *)(h->rec.scr + (size_t)j * b.fs), h->body.reg);
+                hipLaunchKernelGGL(k_body_stats_add, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, n, h->W,
+                                   (const int *)h->body.tri, (const uint8_t *)h->body.reg, st);
+                HM_HIP(hipGetLastError());
+                h->body.stats_frames++;
+            }
+            k += m;
+        }
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return res_clipped(h, g, clipped);
     };
     rc = run();
     if (rc) (void)hipStreamSynchronize(h->stream);            // (nothing queued reads the scratch once it is freed)

@@ -540,6 +540,48 @@ class Renderer:
         _lib.check(_lib.lib().hm_body_rec_stats_add(self._h, what, int(half), int(q), int(floor), int(gain)),
                    "hm_body_rec_stats_add")
 
+    # -- the residual of the record under a model of the cells (hm_body_rec_residual_*; hydra_mi.residual) -----
+    def _residual_args(self, who, labels, weights, traces, blank):
+        lab = np.ascontiguousarray(labels, np.int32)
+        lab = lab[None] if lab.ndim == 2 else lab
+        if lab.ndim != 3 or lab.shape[1:] != (self.ny, self.nx):
+            raise ValueError("%s: label planes of shape %r for %dx%d frames" % (who, lab.shape, self.nx, self.ny))
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint16)
+        if w is not None and w.size != lab.size:
+            raise ValueError("%s: weights of shape %r for labels of shape %r" % (who, w.shape, lab.shape))
+        tr = np.ascontiguousarray(traces, np.int32)
+        F = self.body_rec_count()
+        if tr.ndim != 2 or (F and tr.shape[0] != F):             # (F 0: the call says why)
+            raise ValueError("%s: traces of shape %r for a record of %d frames" % (who, tr.shape, F))
+        bl = None if blank is None else np.ascontiguousarray(blank, np.uint8)
+        if bl is not None and bl.shape != (self.ny, self.nx):
+            raise ValueError("%s: a blank plane of shape %r for %dx%d frames" % (who, bl.shape, self.nx, self.ny))
+        return lab, w, tr, bl
+
+    def body_rec_residual_planes(self, labels, weights, traces, blank=None, offset=64, k0=0, n=None):
+        """hm_body_rec_residual_planes: -> ((n, H, W) uint8, clipped): the recorded frames k0 .. k0 + n - 1 (default: all
+        from k0) minus the cells' light, min(255, max(0, offset + v - ((sum_j weights[j] traces[k, labels[j]] + 2^23) >>
+        24))), 0 off the map and where blank is set.  labels (n_layers, H, W) or (H, W) int32 (-1: none), weights the
+        same shape uint16 (None: 65535), as view_set_cells takes them; traces (F, L) int32 for all recorded frames."""
+        lab, w, tr, bl = self._residual_args("body_rec_residual_planes", labels, weights, traces, blank)
+        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
+        clipped = ctypes.c_uint64(0)
+        _lib.check(_lib.lib().hm_body_rec_residual_planes(self._h, int(k0), n, int(lab.shape[0]), _lib.ptr(lab), _lib.ptr(w),
+                                                          int(tr.shape[1]), _lib.ptr(tr), _lib.ptr(bl), int(offset),
+                                                          _lib.ptr(out), ctypes.byref(clipped)), "hm_body_rec_residual_planes")
+        return out, clipped.value
+
+    def body_rec_residual_stats_add(self, labels, weights, traces, blank=None, offset=64):
+        """hm_body_rec_residual_stats_add: add every recorded frame's residual plane (as body_rec_residual_planes) to the
+        statistics begun with body_stats_begin, as if each had just been warped -> clipped."""
+        lab, w, tr, bl = self._residual_args("body_rec_residual_stats_add", labels, weights, traces, blank)
+        clipped = ctypes.c_uint64(0)
+        _lib.check(_lib.lib().hm_body_rec_residual_stats_add(self._h, int(lab.shape[0]), _lib.ptr(lab), _lib.ptr(w),
+                                                             int(tr.shape[1]), _lib.ptr(tr), _lib.ptr(bl), int(offset),
+                                                             ctypes.byref(clipped)), "hm_body_rec_residual_stats_add")
+        return clipped.value
+
     def screenshot(self, saveall=True, basename="screenshot", X=None):
         """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask
         at state X (default: the vertex buffer) and returns the overlay.  Unlike the reference the names carry no

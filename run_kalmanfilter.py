@@ -71,6 +71,18 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
     --dff-video OUT.avi   the dF/F video in the body frame, grey: min(255, gain excess // max(baseline, floor)) per pixel
                      (--dff-gain, default 255; --dff-floor, default 16; the window of --detrend-half, --detrend-q), of the
                      stabilised record with --stabilize.  Keeps the registered video on the device as --rois does.
+    --find-min-score S   with --find-points: only local maxima that score at least S are points (default: no threshold).
+    --find-more ROUNDS   with --find-points and --find-min-score: look for cells hidden beside the ones found
+                     (hydra_mi.residual.find_more; implies --demix).  Up to ROUNDS times the points so far are demixed, the
+                     fitted light of their cells is taken out of the kept registered video on the device, a disc of
+                     --find-blank px (default 2) round every point is blanked, and the local maxima of --find-score of
+                     that residual video that reach S become points.  A round that adds none ends the search.
+                     found_points, found_scores and --points-out get all the points, the new ones last; the states file
+                     also gets residual_round (per point: the round that found it, 0 the first pass), residual_scores and
+                     residual_scores_round (every candidate's score and its round), residual_clipped (per round: values
+                     that left 0..255 before the clamp).  The demix_* arrays are those of all the points.
+    --residual-video OUT.avi   with --demix or --find-more: the registered video less the demixed cells' light plus 64,
+                     grey, in the body frame (hydra_mi.residual.write_video): what the model does not explain.
     --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
                      (frames x 4N, each frame's estimate from all frames) and Xs_std (the square roots of the
                      diagonals of the smoothed covariances).  The record of the filter takes (4N)^2 doubles of device
@@ -92,6 +104,7 @@ import hydra_mi  # noqa: F401
 from hydra_mi import cellview
 from hydra_mi import kalman
 from hydra_mi import demix
+from hydra_mi import residual
 from hydra_mi import detrend
 from hydra_mi import roi
 from hydra_mi import stabilize
@@ -126,6 +139,13 @@ def main(argv=None):
                         help="find the N best cells from the statistics of the registered video and read them out")
     parser.add_argument("--find-radius", default=6, type=int, help="half width of the window a cell is the maximum of (1..16)")
     parser.add_argument("--find-score", default="corr", choices=("corr", "std", "range"), help="the summary image searched")
+    parser.add_argument("--find-min-score", default=None, type=float, metavar="S", help="the least score of a point found")
+    parser.add_argument("--find-more", default=None, type=int, metavar="ROUNDS",
+                        help="rounds of looking for cells beside the found ones in the residual video of the demixed model "
+                             "(implies --demix, needs --find-min-score)")
+    parser.add_argument("--find-blank", default=residual.DEFAULT_BLANK, type=int, help="radius blanked round every known point (px)")
+    parser.add_argument("--residual-video", default=None, metavar="OUT.avi",
+                        help="write the registered video less the demixed cells here (.avi)")
     parser.add_argument("--points-out", default=None, help="write the points found here (CSV lines name,x,y)")
     parser.add_argument("--rois", action="store_true", help="footprints, ROIs and dF/F traces of the points (roi_* arrays)")
     parser.add_argument("--rois-max-gb", default=8.0, type=float, help="device memory the kept registered video may take (GiB)")
@@ -173,6 +193,16 @@ def main(argv=None):
             parser.error("--find-points needs N >= 1 and a --find-radius in 1..16")
     elif args.points_out is not None:
         parser.error("--points-out goes with --find-points")
+    if args.find_min_score is not None and (args.find_points is None or not np.isfinite(args.find_min_score)):
+        parser.error("--find-min-score is the least score of --find-points: it needs --find-points and a finite number")
+    if args.find_more is not None:
+        if args.find_points is None or args.find_min_score is None:
+            parser.error("--find-more looks beside the points found: it needs --find-points and --find-min-score")
+        if args.find_more < 1 or args.find_blank < 0:
+            parser.error("--find-more needs at least one round and a --find-blank >= 0")
+        args.demix = True
+    if args.residual_video is not None and not args.demix:
+        parser.error("--residual-video shows what the demixed model leaves: it needs --demix or --find-more")
     if args.demix:
         args.rois = True
         if args.demix_iters < 1:
@@ -289,6 +319,7 @@ def main(argv=None):
         print("Overlay video: %d frames in %s" % (video.frames, args.fn_out))
     extra = {}
     cv_cells = cv_levels = cv_points = None          # what --cells-video draws
+    more = None                                      # what --find-more found
     if body is not None:
         res = body.results()
         extra = {"tri_means": res["tri_means"], "tri_counts": res["tri_counts"]}
@@ -329,7 +360,20 @@ def main(argv=None):
         sm_img = body.summary()
         if det_kind is not None:
             detrended_summary()
-        found, scores = body.find_points(args.find_points, radius=args.find_radius, score=args.find_score)
+        found, scores = body.find_points(args.find_points, radius=args.find_radius, score=args.find_score,
+                                         min_score=args.find_min_score)
+        if args.find_more is not None and body.keep and len(states) and len(found):
+            # the cells beside the ones found: the demixed model taken out of the kept record, and searched again
+            more = residual.find_more(body, found, args.find_min_score, rounds=args.find_more, radius=args.find_radius,
+                                      score=args.find_score, blank=args.find_blank, iters=args.demix_iters,
+                                      r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
+            rs = more["scores"]
+            extra.update(residual_round=more["round"], residual_scores=np.concatenate(rs),
+                         residual_scores_round=np.concatenate([np.full(len(s), k + 1, np.int32) for k, s in enumerate(rs)]),
+                         residual_clipped=np.array(more["clipped"], np.uint64))
+            print("Found %d more points in %d rounds of the residual video (%d candidates refused, %d values clipped)" % (
+                len(more["points"]) - len(found), len(rs), len(more["refused"]), sum(more["clipped"])))
+            found, scores = more["points"], np.concatenate((scores, more["new_scores"]))
         kf.state.renderer.body_stats_end()
         extra.update(body_mean=sm_img["mean"], body_std=sm_img["std"], body_max=sm_img["max"], body_corr=sm_img["corr"],
                      found_points=found, found_scores=scores)
@@ -358,11 +402,17 @@ def main(argv=None):
         inside = np.flatnonzero(body.locate(pts)[0] >= 0) if args.rois else []
         if len(inside) and len(states):
             if args.demix:
-                e = demix.extract(body, pts[inside], iters=args.demix_iters, r_disc=args.point_radius, thr=args.roi_thr,
-                                  alpha=args.roi_alpha)
+                if more is not None and len(inside) == len(pts):           # (demixed already, with all the points)
+                    e = more["e"]
+                else:
+                    e = demix.extract(body, pts[inside], iters=args.demix_iters, r_disc=args.point_radius, thr=args.roi_thr,
+                                      alpha=args.roi_alpha)
                 extra.update(demix_shapes=e["shapes"], demix_C=e["C"], demix_dff=e["dff_demixed"],
                              demix_change=e["demix_change"])
                 print("Demixed: %d cells, %d rounds, last change %.3g" % (len(inside), args.demix_iters, e["demix_change"][-1]))
+                if args.residual_video is not None:
+                    n_res, n_clip = residual.write_video(body, args.residual_video, e, points=pts[inside])
+                    print("Residual video: %d frames in %s (%d values clipped)" % (n_res, args.residual_video, n_clip))
             else:
                 e = roi.extract(body, pts[inside], r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
             extra.update(roi_points=inside, roi_footprints=e["footprints"], roi_labels=e["roi_labels"],
