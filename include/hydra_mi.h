@@ -699,7 +699,9 @@ int hm_body_rec_field_sums(hm_ctx_t h, int k0, int n_frames, int B, const int16_
  *   numbers in hm_last_error.  The record, the map and the tracker do not change by a bit (the registered plane of the
  *   last warp, which only the next warp reads again after rewriting it, is stats_add's work plane).  The frames are split
  *   over the grid in runs of hm_ctx_tune "rec_bl_frames" (1..2^24, default 256: same results for every value); the scratch
- *   follows hm_body_rec_shift's: at most 16 MiB (one frame at least), freed on every return including errors. */
+ *   follows hm_body_rec_shift's: at most 16 MiB (one frame at least), freed on every return including errors.  (Tests set
+ *   that size with hm_ctx_tune "rec_scratch_bytes", 1..2^30, for every call that uses the scratch: same results for
+ *   every value.) */
 int hm_body_rec_planes(hm_ctx_t h, int k0, int n_frames, int what, int half, int q, int floor, int gain, uint8_t *out);
 int hm_body_rec_stats_add(hm_ctx_t h, int what, int half, int q, int floor, int gain);
 

@@ -13,37 +13,6 @@
 #include "hm_types.h"
 #include "view_kernels.h"
 
-// Sums of val over the lanes of a wave by key, NK keys per lane (-1: none), one integer atomic per distinct key: the
-// first lane with a key left names it, the lanes add what they hold under it, a wave reduction, the atomic.  Exact and
-// independent of the order.  Every lane of the wave must call it (a wave's sum of at most 64 NK values of <= 255 fits
-// 32 bits).
-template <int NK, typename S>
-__device__ __forceinline__ void d_peel_add(const int (&key)[NK], const unsigned (&val)[NK], S *__restrict__ sums)
-{
-    unsigned pend = 0;
-#pragma unroll
-    for (int j = 0; j < NK; j++)
-        if (key[j] >= 0) pend |= 1u << j;
-    const int lane = __lane_id();
-    for (;;) {
-        const unsigned long long act = __ballot(pend != 0);
-        if (act == 0) break;
-        const int lead = __ffsll((unsigned long long)act) - 1;
-        int mine = -1;
-#pragma unroll
-        for (int j = NK - 1; j >= 0; j--)
-            if ((pend >> j) & 1u) mine = key[j];
-        const int k = __shfl(mine, lead);
-        unsigned s = 0;
-#pragma unroll
-        for (int j = 0; j < NK; j++)
-            if (((pend >> j) & 1u) && key[j] == k) { s += val[j]; pend &= ~(1u << j); }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += (unsigned)__shfl_xor((int)s, o);
-        if (lane == lead) atomicAdd(&sums[k], (S)s);
-    }
-}
-
 // X = uv (binary32 promoted), velocities 0: the configuration the body map is taken at
 __global__ __launch_bounds__(256) void k_body_uvX(const float *__restrict__ uv, int N, double *__restrict__ X)
 {

@@ -1,7 +1,7 @@
 // The filter handle of libhydra_mi.so (hm_ctx) and the helpers every translation unit that works on one needs.  Private to
-// the library: ekf.hip (the filter, the smoother) and readout.hip (views, body-frame readout, record) include it, both built
-// by the one compiler command of the Makefile.  Everything defined here is static or a template; the two launchers at the
-// end are defined once, in ekf.hip.
+// the library: ekf.hip (the filter, the smoother), readout.hip (views, body-frame readout, statistics) and record.hip (the
+// kept record) include it, all built by the one compiler command of the Makefile.  Everything defined here is static or a
+// template; the hidden functions declared at the end are defined once, in the translation unit named there.
 #pragma once
 #include "hm_common.h"
 #include "hm_types.h"
@@ -130,7 +130,9 @@ struct BodyState {
     bool stats_on = false;
     int stats_frames = 0;            // frames added since hm_body_stats_begin
     int stats_cap = BODY_STATS_CAP;  // hm_ctx_tune "body_stats_cap" (tests lower it)
-    uint8_t *reg = nullptr;          // the registered plane (W*H) every warp writes while the statistics or the record are on
+    // the registered plane (W*H) every warp writes while the statistics or the record are on.  Whichever of the two goes
+    // last frees it: hm_body_stats_end unless rec.on, the record's end unless stats_on
+    uint8_t *reg = nullptr;
     unsigned *stsum = nullptr;       // s1, s2, cross[4]: 6 planes of W*H, body_stats_stride values apart
     uint8_t *stmax = nullptr;        // W*H
     double *stimg = nullptr;         // mean, std, corr: 3 planes of W*H (hm_body_stats_images / _peaks)
@@ -138,7 +140,7 @@ struct BodyState {
     double *pkscore = nullptr;
 };
 
-// hm_body_rec_*: the registered video of the warps queued between begin and end, kept on the device (roi_kernels.h)
+// hm_body_rec_*: the registered video of the warps queued between begin and end, kept on the device (record.hip)
 struct RecState {
     bool on = false;
     int frames = 0;                  // frames appended since hm_body_rec_begin
@@ -152,7 +154,10 @@ struct RecState {
     std::vector<uint8_t *> chunks;
     uint8_t **tab = nullptr;         // the chunks' addresses for the reductions
     uint8_t *tmp = nullptr;          // their arguments and results
-    uint8_t *scr = nullptr;          // hm_body_rec_shift / _warp: a run of frames as they were (freed when the call returns)
+    size_t scr_bytes = (size_t)16 << 20;     // hm_ctx_tune "rec_scratch_bytes": the most scratch of a call (one frame at least; tests lower it)
+    // a run of frames in the record's layout: as they were (hm_body_rec_shift / _warp), or the planes made of them
+    // (hm_body_rec_planes / _stats_add / _residual_*); there while such a call runs, freed when it returns
+    uint8_t *scr = nullptr;
 };
 
 struct hm_ctx {
@@ -314,14 +319,15 @@ struct hm_ctx {
     hipEvent_t ev_outline = nullptr; // ... recorded behind every outline queued on the second stream
     hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)
     // The readout: views, the body-frame readout with its statistics, the kept record.  Each has buffers of its own, allocated
-    // on first use through `own`, and touches nothing the filter reads (readout.hip has the code and names no other field
-    // of the handle than W, H, N, T, device, own, stream, d_tri, d_uv, d_tex and, for the overlay, have_tex, have_obs, o_yim).
+    // on first use through `own`, and touches nothing the filter reads (readout.hip and record.hip have the code and name no
+    // other field of the handle than W, H, N, T, device, own, stream, d_tri, d_uv, d_tex and, for the overlay, have_tex,
+    // have_obs, o_yim).
     ViewState view;
     BodyState body;
     RecState rec;
 };
 
-static hipError_t alloc_targets(HmOwner &own, Targets &t, size_t n)
+static inline hipError_t alloc_targets(HmOwner &own, Targets &t, size_t n)
 {
     hipError_t e = own.alloc(&t.acc, n * sizeof(int));
     if (e == hipSuccess) e = own.alloc(&t.fx, n * sizeof(float));
@@ -400,6 +406,19 @@ static int upload(HmOwner &own, T **dst, const T *src, size_t n)
     return HM_OK;
 }
 
+// n_layers planes of n labels each, every one within -1 .. L - 1.  n_layers 0: one plane, and the message names no layer.
+static inline int hm_labels_ok(const char *who, int n_layers, const int32_t *labels, size_t n, int L)
+{
+    const size_t all = (size_t)(n_layers ? n_layers : 1) * n;
+    for (size_t i = 0; i < all; i++) {
+        if (labels[i] >= -1 && labels[i] < L) continue;
+        if (n_layers) hm_set_error("%s: label %d at pixel %zu of layer %zu outside -1..%d", who, (int)labels[i], i % n, i / n, L - 1);
+        else hm_set_error("%s: label %d at pixel %zu outside -1..%d", who, (int)labels[i], i, L - 1);
+        return HM_ERR_ARG;
+    }
+    return HM_OK;
+}
+
 // The filter's kernels that the readout launches (a view renders, the body map is a setup at X = uv).  Kernels are compiled
 // by one translation unit each (ekf_kernels.h: ekf.hip), so readout.hip queues them through these, defined in ekf.hip:
 // k_setup_all on T triangles of m at state X, and the full-frame render k_render<0> -- or k_render<1> with the label
@@ -407,3 +426,13 @@ static int upload(HmOwner &own, T **dst, const T *src, size_t n)
 __attribute__((visibility("hidden"))) void ekf_queue_setup_all(hipStream_t st, const Mesh &m, const double *d_X, TriSetup *d_setup);
 __attribute__((visibility("hidden"))) void ekf_queue_render(hipStream_t st, const Mesh &m, const double *d_X, const TriSetup *d_setup,
                                                             const Targets &out, const int *d_labels, int *d_ids);
+
+// What crosses between readout.hip (the warp, the statistics) and record.hip (the kept record), in the same way.  Defined in
+// readout.hip: the body map, built once per handle; k_body_stats_add queued on the registered plane d_reg, and the frame
+// counted.  Defined in record.hip: where the next frame of the record goes (allocates the chunk it starts; called before
+// anything of a warp is queued, and may refuse: `who` names the caller in the error); k_rec_copy of the registered plane
+// queued into that slot, and the frame counted.
+__attribute__((visibility("hidden"))) int body_map_build(hm_ctx *h);
+__attribute__((visibility("hidden"))) int body_stats_queue_add(hm_ctx *h, const uint8_t *d_reg);
+__attribute__((visibility("hidden"))) int body_rec_slot(hm_ctx *h, const char *who, uint8_t **dst);
+__attribute__((visibility("hidden"))) int body_rec_queue_copy(hm_ctx *h, uint8_t *dst);

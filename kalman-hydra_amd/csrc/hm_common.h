@@ -29,6 +29,13 @@ void hm_set_error(const char *fmt, ...);
         }                                \
     } while (0)
 
+// return a failed call's code (the callee has set the error)
+#define HM_TRY(...)                      \
+    do {                                 \
+        const int _r = (__VA_ARGS__);    \
+        if (_r) return _r;               \
+    } while (0)
+
 static inline int hm_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Every device allocation of the library.  HYDRA_MI_POISON=<mask> (development aid) fills those of the classes in the

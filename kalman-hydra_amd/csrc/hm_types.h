@@ -1,7 +1,7 @@
 // Plain types, constants and __device__ inline helpers that more than one translation unit of libhydra_mi.so needs: what
 // the filter handle (ctx.h) holds by value, and what kernels on both sides of the filter / readout split use.  No
 // __global__ function lives here, so any translation unit may include it -- unlike the *_kernels.h headers, whose kernels
-// are not static: each of those is compiled by exactly one translation unit (ekf.hip or readout.hip).
+// are not static: each of those is compiled by exactly one translation unit (ekf.hip, readout.hip or record.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -214,9 +214,40 @@ struct Ccl {
     int W, H;
 };
 
-// ---- the body-frame readout (body_kernels.h, roi_kernels.h) -----------------------------------------------------------
+// ---- the body-frame readout and the kept record (body_kernels.h; roi_kernels.h and the record's other kernels) -------
 // most frames of one statistics accumulation: 65536 * 255^2 < 2^32, every sum is an exact uint32
 #define BODY_STATS_CAP 65536
+
+// Sums of val over the lanes of a wave by key, NK keys per lane (-1: none), one integer atomic per distinct key: the
+// first lane with a key left names it, the lanes add what they hold under it, a wave reduction, the atomic.  Exact and
+// independent of the order.  Every lane of the wave must call it (a wave's sum of at most 64 NK values of <= 255 fits
+// 32 bits).
+template <int NK, typename S>
+__device__ __forceinline__ void d_peel_add(const int (&key)[NK], const unsigned (&val)[NK], S *__restrict__ sums)
+{
+    unsigned pend = 0;
+#pragma unroll
+    for (int j = 0; j < NK; j++)
+        if (key[j] >= 0) pend |= 1u << j;
+    const int lane = __lane_id();
+    for (;;) {
+        const unsigned long long act = __ballot(pend != 0);
+        if (act == 0) break;
+        const int lead = __ffsll((unsigned long long)act) - 1;
+        int mine = -1;
+#pragma unroll
+        for (int j = NK - 1; j >= 0; j--)
+            if ((pend >> j) & 1u) mine = key[j];
+        const int k = __shfl(mine, lead);
+        unsigned s = 0;
+#pragma unroll
+        for (int j = 0; j < NK; j++)
+            if (((pend >> j) & 1u) && key[j] == k) { s += val[j]; pend &= ~(1u << j); }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += (unsigned)__shfl_xor((int)s, o);
+        if (lane == lead) atomicAdd(&sums[k], (S)s);
+    }
+}
 
 // the box of the body map that the record keeps per frame (roi_kernels.h has the layout)
 struct RecBox {

@@ -1,0 +1,869 @@
+// The registered video kept on the device (hm_body_rec_*): the record itself, the reductions over it, its residual motion
+// (match, shift, field, warp), the running baseline and the residual of the cells' model.  Host orchestration and C-ABI
+// (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h and residual_kernels.h, which
+// this translation unit alone compiles.  Of the handle (ctx.h) it uses rec, the body map (body.tri, body.h_tri), the
+// registered plane (body.reg) and the statistics' counters, and reads W, H, device, own and stream.  readout.hip queues the
+// warp: it reserves a frame's slot and queues the copy into it through body_rec_slot and body_rec_queue_copy, and this file
+// reaches the body map and the statistics through body_map_build and body_stats_queue_add (ctx.h).
+#include "ctx.h"
+#include "roi_kernels.h"
+#include "stab_kernels.h"
+#include "detrend_kernels.h"
+#include "residual_kernels.h"
+#include <algorithm>
+#include <cstring>
+
+#define REC_CHUNK_BYTES ((size_t)64 << 20)
+#define REC_MAX_FRAMES (1 << 24)
+
+// ---- what the calls below are made of ---------------------------------------------------------------------------------
+// frame k of the record (device)
+static uint8_t *rec_frame(const hm_ctx *h, int k)
+{
+    const RecBox &b = h->rec.box;
+    const int ch = k / b.fpc;
+    return h->rec.chunks[ch] + (size_t)(k - ch * b.fpc) * b.fs;
+}
+
+static int rec_range_ok(const hm_ctx *h, const char *who, int k0, int n)
+{
+    HM_ARG(k0 >= 0 && n >= 0 && k0 <= h->rec.frames && n <= h->rec.frames - k0, "%s: frames %d .. %d of a record of %d", who, k0,
+           k0 + n - 1, h->rec.frames);
+    return HM_OK;
+}
+
+// one box frame on the device -> a full W x H plane of the caller's, 0 outside the box
+static int rec_expand(const hm_ctx *h, const uint8_t *d_src, uint8_t *out_plane)
+{
+    const RecBox &b = h->rec.box;
+    memset(out_plane, 0, (size_t)h->W * h->H);
+    HM_HIP(hipMemcpy2D(out_plane + (size_t)b.r0 * h->W + b.c0, (size_t)h->W, d_src, (size_t)b.pitch, (size_t)b.bw, (size_t)b.bh,
+                       hipMemcpyDeviceToHost));
+    return HM_OK;
+}
+
+// the patches of B x B pixels that cover the box
+struct RecGrid { int npx, npy, np; };
+static RecGrid rec_grid(const RecBox &b, int B)
+{
+    const int npx = hm_cdiv(b.bw, B), npy = hm_cdiv(b.bh, B);
+    return RecGrid{npx, npy, npx * npy};
+}
+
+static int stab_patch_ok(const char *who, int B)
+{
+    HM_ARG(B >= STAB_BMIN && B <= STAB_BMAX, "%s: patch size %d outside %d..%d", who, B, STAB_BMIN, STAB_BMAX);
+    return HM_OK;
+}
+
+// a dword per thread of `frames` box frames
+static dim3 rec_dword_grid(const RecBox &b, int frames = 1) { return dim3(hm_cdiv((b.pitch >> 2) * b.bh, 256), std::min(frames, 65535)); }
+
+// Scratch for `want` frames in the record's layout -- as many of them as rec.scr_bytes hold, one at least -- around
+// body(per): rec.scr is there while it runs and freed when it returns, on the error paths too, once nothing queued reads
+// it any more.  The first error is the one reported.
+template <typename Body>
+static int rec_with_scratch(hm_ctx *h, int want, Body body)
+{
+    const RecBox &b = h->rec.box;
+    const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(want, 1), h->rec.scr_bytes / b.fs));
+    HM_HIP(h->own.grow(&h->rec.scr, (size_t)per * b.fs));
+    const int rc = body(per);
+    if (rc) (void)hipStreamSynchronize(h->stream);
+    const hipError_t fe = h->own.free(&h->rec.scr);
+    if (rc) return rc;
+    HM_HIP(fe);
+    return HM_OK;
+}
+
+// The frames k0 .. k0 + n - 1 as planes of some kind, in runs of at most `per`: fill(k, m, dst) queues the planes of frames
+// k .. k + m - 1 into the scratch, take(j, d_frame) gets the plane of frame k0 + j -- once the run is there if `wait`,
+// else take queues behind it.
+template <typename Fill, typename Take>
+static int rec_runs(hm_ctx *h, int per, int k0, int n, bool wait, Fill fill, Take take)
+{
+    for (int k = 0; k < n;) {
+        const int m = std::min(per, n - k);
+        HM_TRY(fill(k0 + k, m, h->rec.scr));
+        if (wait) HM_HIP(hipStreamSynchronize(h->stream));
+        for (int j = 0; j < m; j++) HM_TRY(take(k + j, (const uint8_t *)(h->rec.scr + (size_t)j * h->rec.box.fs)));
+        k += m;
+    }
+    return HM_OK;
+}
+
+// The whole record rewritten in place, in runs of at most `per` frames within a chunk: a run is copied aside as it is, then
+// launch(grid, src, dst, k, m) queues the kernel that writes frames k .. k + m - 1 (at dst) from the copy (src).
+template <typename Launch>
+static int rec_rewrite(hm_ctx *h, int per, Launch launch)
+{
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames;
+    for (int k = 0; k < F;) {
+        const int m = std::min(per, std::min(F, (k / b.fpc + 1) * b.fpc) - k);
+        uint8_t *dst = rec_frame(h, k);
+        HM_HIP(hipMemcpyAsync(h->rec.scr, dst, (size_t)m * b.fs, hipMemcpyDeviceToDevice, h->stream));
+        launch(rec_dword_grid(b, m), (const uint8_t *)h->rec.scr, dst, k, m);
+        HM_HIP(hipGetLastError());
+        k += m;
+    }
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// the statistics are on and have room for every frame of the record
+static int rec_stats_open(hm_ctx *h, const char *who)
+{
+    if (!h->body.stats_on) { hm_set_error("%s: no statistics (hm_body_stats_begin first)", who); return HM_ERR_STATE; }
+    if (h->body.stats_frames + h->rec.frames > h->body.stats_cap) {
+        hm_set_error("%s: the statistics hold %d frames and the record %d, their capacity is %d (sums of 32 bits are exact up to %d "
+                     "frames): nothing added", who, h->body.stats_frames, h->rec.frames, h->body.stats_cap, BODY_STATS_CAP);
+        return HM_ERR_STATE;
+    }
+    return HM_OK;
+}
+
+// a box frame pasted into the registered plane, then added to the statistics as a warp's frame is
+static int rec_stats_add_plane(hm_ctx *h, const uint8_t *d_box_frame)
+{
+    const int n = h->W * h->H;
+    hipLaunchKernelGGL(k_rec_paste, dim3(hm_cdiv(hm_cdiv(n, 4), 256)), dim3(256), 0, h->stream, n, h->W, h->rec.box, d_box_frame,
+                       h->body.reg);
+    return body_stats_queue_add(h, h->body.reg);
+}
+
+// ---- the record: begin, end, the slot and the copy of every warp, fetch (roi_kernels.h) -------------------------------
+// stop recording and free the record (the caller has checked that there is one)
+static int body_rec_drop(hm_ctx *h)
+{
+    h->rec.on = false;
+    h->rec.frames = 0;
+    HM_HIP(hipSetDevice(h->device));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    hipError_t e = hipSuccess;
+    for (uint8_t *&c : h->rec.chunks) {
+        const hipError_t e1 = h->own.free(&c);
+        if (e == hipSuccess) e = e1;
+    }
+    h->rec.chunks.clear();
+    if (e == hipSuccess) e = h->own.free(&h->rec.tab);
+    if (e == hipSuccess) e = h->own.free(&h->rec.tmp);       // (rec.scr: no call leaves it behind)
+    if (e == hipSuccess && !h->body.stats_on) e = h->own.free(&h->body.reg);     // (BodyState::reg has the rule)
+    HM_HIP(e);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_begin(hm_ctx_t h, uint64_t max_bytes)
+{
+    HM_ARG(h != nullptr, "hm_body_rec_begin: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_map_build(h));
+    if (h->rec.on) HM_TRY(body_rec_drop(h));
+    const size_t n = (size_t)h->W * h->H;
+    if (h->body.h_tri.empty()) {
+        h->body.h_tri.resize(n);
+        HM_HIP(hipMemcpyAsync(h->body.h_tri.data(), h->body.tri, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HM_HIP(hipStreamSynchronize(h->stream));
+    }
+    int c0 = h->W, c1 = -1, r0 = h->H, r1 = -1;
+    for (int r = 0; r < h->H; r++)
+        for (int c = 0; c < h->W; c++)
+            if (h->body.h_tri[(size_t)r * h->W + c] >= 0) {
+                c0 = std::min(c0, c); c1 = std::max(c1, c);
+                r0 = std::min(r0, r); r1 = std::max(r1, r);
+            }
+    if (c1 < 0) c0 = c1 = r0 = r1 = 0;          // (an empty map: one pixel, registered as 0)
+    RecBox &b = h->rec.box;
+    b.c0 = c0; b.r0 = r0; b.bw = c1 - c0 + 1; b.bh = r1 - r0 + 1;
+    b.pitch = (b.bw + 3) & ~3;
+    b.fs = ((size_t)b.pitch * b.bh + 15) & ~(size_t)15;
+    b.fpc = h->rec.chunk > 0 ? h->rec.chunk : (int)std::max<size_t>(1, REC_CHUNK_BYTES / b.fs);
+    h->rec.max = max_bytes;
+    h->rec.cap = (int)std::min<unsigned long long>(max_bytes / b.fs, REC_MAX_FRAMES);
+    HM_HIP(h->own.alloc(&h->body.reg, n));
+    h->rec.frames = 0;
+    h->rec.on = true;
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_end(hm_ctx_t h)
+{
+    HM_ARG(h != nullptr, "hm_body_rec_end: NULL handle");
+    HM_JOIN_LAZY(h);
+    if (!h->rec.on) return HM_OK;
+    return body_rec_drop(h);
+}
+
+extern "C" int hm_body_rec_count(hm_ctx_t h, int *frames)
+{
+    HM_ARG(h && frames, "hm_body_rec_count: NULL argument");
+    HM_JOIN_LAZY(h);
+    *frames = h->rec.on ? h->rec.frames : 0;
+    return HM_OK;
+}
+
+int body_rec_slot(hm_ctx *h, const char *who, uint8_t **dst)
+{
+    const RecBox &b = h->rec.box;
+    if (h->rec.frames >= h->rec.cap) {
+        hm_set_error("%s: the record holds %d frames of %zu bytes (a box of %d x %d pixels) and its budget of %llu bytes holds "
+                     "%d: nothing appended", who, h->rec.frames, b.fs, b.bw, b.bh, h->rec.max, h->rec.cap);
+        return HM_ERR_STATE;
+    }
+    const int ch = h->rec.frames / b.fpc;
+    if (ch == (int)h->rec.chunks.size()) {
+        const int frames = std::min(b.fpc, h->rec.cap - ch * b.fpc);
+        uint8_t *p = nullptr;
+        HM_HIP(h->own.alloc(&p, (size_t)frames * b.fs));
+        h->rec.chunks.push_back(p);
+    }
+    *dst = rec_frame(h, h->rec.frames);
+    return HM_OK;
+}
+
+int body_rec_queue_copy(hm_ctx *h, uint8_t *dst)
+{
+    hipLaunchKernelGGL(k_rec_copy, rec_dword_grid(h->rec.box), dim3(256), 0, h->stream, h->W, h->rec.box,
+                       (const uint8_t *)h->body.reg, dst);
+    HM_HIP(hipGetLastError());
+    h->rec.frames++;
+    return HM_OK;
+}
+
+static int body_rec_begun(hm_ctx *h, const char *who)
+{
+    if (!h->rec.on) { hm_set_error("%s: no record (hm_body_rec_begin first)", who); return HM_ERR_STATE; }
+    HM_HIP(hipSetDevice(h->device));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_fetch(hm_ctx_t h, int k0, int n, uint8_t *out)
+{
+    HM_ARG(h != nullptr, "hm_body_rec_fetch: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_begun(h, "hm_body_rec_fetch"));
+    HM_TRY(rec_range_ok(h, "hm_body_rec_fetch", k0, n));
+    HM_ARG(out || n == 0, "hm_body_rec_fetch: NULL output");
+    HM_HIP(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < n; k++) HM_TRY(rec_expand(h, rec_frame(h, k0 + k), out + (size_t)k * h->W * h->H));
+    return HM_OK;
+}
+
+// ---- the reductions over the record (roi_kernels.h) -------------------------------------------------------------------
+// a reduction may start: there are frames, and the chunks' addresses are on the device
+static int body_rec_ready(hm_ctx *h, const char *who)
+{
+    HM_TRY(body_rec_begun(h, who));
+    if (h->rec.frames < 1) { hm_set_error("%s: no frame recorded since hm_body_rec_begin", who); return HM_ERR_STATE; }
+    const size_t bytes = h->rec.chunks.size() * sizeof(uint8_t *);
+    HM_HIP(h->own.grow(&h->rec.tab, bytes));       // (every reduction waits for its results: nothing in flight reads it)
+    HM_HIP(hipMemcpyAsync(h->rec.tab, h->rec.chunks.data(), bytes, hipMemcpyHostToDevice, h->stream));
+    return HM_OK;
+}
+
+// the reductions' buffers, carved from one allocation (16-byte aligned pieces)
+struct RecCarve {
+    uint8_t *base;
+    size_t off;
+    template <typename T> T *take(size_t count)
+    {
+        off = (off + 15) & ~(size_t)15;
+        T *p = base ? (T *)(base + off) : nullptr;      // (no allocation yet: the pieces are only measured)
+        off += count * sizeof(T);
+        return p;
+    }
+};
+// Lay a reduction's buffers out in rec.tmp: `lay` takes its pieces from the RecCarve it is given, first to measure them,
+// then, once the allocation holds them all, for their addresses.
+template <typename Lay>
+static int body_rec_carve(hm_ctx *h, Lay lay)
+{
+    RecCarve cv = {nullptr, 0};
+    lay(cv);
+    HM_HIP(h->own.grow(&h->rec.tmp, cv.off));
+    cv = {h->rec.tmp, 0};
+    lay(cv);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_label_sums(hm_ctx_t h, const int32_t *labels, int L, uint64_t *out)
+{
+    HM_ARG(labels && out && L >= 1, "hm_body_rec_label_sums: NULL argument or %d labels", L);
+    HM_ARG(h != nullptr, "hm_body_rec_label_sums: NULL handle");
+    const size_t n = (size_t)h->W * h->H;
+    HM_TRY(hm_labels_ok("hm_body_rec_label_sums", 0, labels, n, L));
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_label_sums"));
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames, nb = b.pitch * b.bh;
+    int *d_img = nullptr, *d_lab = nullptr;
+    unsigned long long *d_sum = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_img = cv.take<int>(n);
+        d_lab = cv.take<int>(nb);
+        d_sum = cv.take<unsigned long long>((size_t)F * L);
+    }));
+    HM_HIP(hipMemcpyAsync(d_img, labels, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(d_sum, 0, (size_t)F * L * sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(k_rec_box_labels, dim3(hm_cdiv(nb, 256)), dim3(256), 0, h->stream, h->W, b, (const int *)h->body.tri,
+                       (const int *)d_img, d_lab);
+    hipLaunchKernelGGL(k_rec_label_sums, dim3(hm_cdiv(nb >> 2, 256), std::min(F, 1024)), dim3(256), 0, h->stream, b,
+                       (const uint8_t *const *)h->rec.tab, F, (const int *)d_lab, L, d_sum);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, d_sum, (size_t)F * L * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// What the reductions over seeds open with, in this order: the helper joined, a record with frames whose chunk table is on
+// the device (body_rec_ready), every seed a pixel of the map, and F P below 2^30 (the kernels index frame x seed in an int).
+static int body_rec_seeded(hm_ctx *h, int P, const int32_t *seeds, const char *who)
+{
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, who));
+    for (int s = 0; s < P; s++) {
+        const int c = seeds[2 * s], r = seeds[2 * s + 1];
+        if (!(c >= 0 && c < h->W && r >= 0 && r < h->H && h->body.h_tri[(size_t)r * h->W + c] >= 0)) {
+            hm_set_error("%s: seed %d (column %d, row %d) is not a pixel of the body map", who, s, c, r);
+            return HM_ERR_ARG;
+        }
+    }
+    HM_ARG((long long)h->rec.frames * P < (1ll << 30), "%s: %d frames x %d seeds", who, h->rec.frames, P);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_seed_sums(hm_ctx_t h, int P, const int32_t *seeds, double r_disc, double r_in, double r_out, int R,
+                                     uint32_t *n_T, uint32_t *n_G, uint64_t *T, uint64_t *G, int64_t *U, uint64_t *w1,
+                                     uint64_t *w2, int64_t *c, int64_t *u1, int64_t *u2)
+{
+    HM_ARG(P >= 1 && seeds, "hm_body_rec_seed_sums: %d seeds", P);
+    HM_ARG(r_disc >= 0.0 && r_disc <= REC_RMAX && r_in >= 0.0 && r_in <= r_out && r_out <= REC_RMAX,
+           "hm_body_rec_seed_sums: radii %g, %g, %g (need 0 <= r_disc <= %d and 0 <= r_in <= r_out <= %d)", r_disc, r_in, r_out,
+           REC_RMAX, REC_RMAX);
+    HM_ARG(R >= 0 && R <= REC_WIN_RMAX, "hm_body_rec_seed_sums: window radius %d outside 0..%d", R, REC_WIN_RMAX);
+    HM_ARG(h != nullptr, "hm_body_rec_seed_sums: NULL handle");
+    HM_TRY(body_rec_seeded(h, P, seeds, "hm_body_rec_seed_sums"));
+    const int F = h->rec.frames;
+    // the pixels of every disc and ring, and the bound that keeps sum U^2 exact: |U| <= 255 n_T n_G
+    const double rd2 = r_disc * r_disc, ri2 = r_in * r_in, ro2 = r_out * r_out;
+    const int Rg = (int)std::max(r_disc, r_out);
+    std::vector<unsigned> cnt(2 * (size_t)P, 0);
+    for (int s = 0; s < P; s++) {
+        for (int dy = -Rg; dy <= Rg; dy++)
+            for (int dx = -Rg; dx <= Rg; dx++) {
+                const int x = seeds[2 * s] + dx, y = seeds[2 * s + 1] + dy;
+                if (x < 0 || x >= h->W || y < 0 || y >= h->H || h->body.h_tri[(size_t)y * h->W + x] < 0) continue;
+                const double d2 = (double)(dx * dx + dy * dy);
+                if (d2 <= rd2) cnt[s]++;
+                if (d2 >= ri2 && d2 <= ro2) cnt[P + s]++;
+            }
+        const unsigned __int128 m = (unsigned __int128)255 * cnt[s] * cnt[P + s];
+        HM_ARG(m * m * (unsigned __int128)F < ((unsigned __int128)1 << 63),
+               "hm_body_rec_seed_sums: seed %d: F (255 n_T n_G)^2 = %d (255 x %u x %u)^2 could pass 2^63", s, F, cnt[s], cnt[P + s]);
+    }
+    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
+    RecSeeds g;
+    RecWin q;
+    int2 *d_seeds = nullptr;
+    unsigned *d_cnt = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_seeds = cv.take<int2>(P);
+        d_cnt = cv.take<unsigned>(2 * (size_t)P);
+        g.T = cv.take<unsigned long long>(fp);
+        g.G = cv.take<unsigned long long>(fp);
+        g.U = cv.take<long long>(fp);
+        q.w1 = cv.take<unsigned long long>(P * nw);
+        q.w2 = cv.take<unsigned long long>(P * nw);
+        q.c = cv.take<long long>(P * nw);
+        q.u1 = cv.take<long long>(P);
+        q.u2 = cv.take<long long>(P);
+    }));
+    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_cnt, cnt.data(), 2 * (size_t)P * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    g.b = h->rec.box; g.chunks = (const uint8_t *const *)h->rec.tab; g.F = F; g.P = P; g.R = Rg;
+    g.seeds = d_seeds; g.rd2 = rd2; g.ri2 = ri2; g.ro2 = ro2; g.nT = d_cnt; g.nG = d_cnt + P;
+    hipLaunchKernelGGL(k_rec_seed_traces, dim3(hm_cdiv((int)fp, 4)), dim3(256), 0, h->stream, g);
+    q.b = h->rec.box; q.chunks = g.chunks; q.F = F; q.P = P; q.R = R; q.seeds = d_seeds; q.U = g.U;
+    hipLaunchKernelGGL(k_rec_window_sums, dim3(hm_cdiv((int)nw, 256), P), dim3(256), 0, h->stream, q);
+    HM_HIP(hipGetLastError());
+    if (n_T) memcpy(n_T, cnt.data(), (size_t)P * sizeof(uint32_t));
+    if (n_G) memcpy(n_G, cnt.data() + P, (size_t)P * sizeof(uint32_t));
+    if (T) HM_HIP(hipMemcpyAsync(T, g.T, fp * 8, hipMemcpyDeviceToHost, h->stream));
+    if (G) HM_HIP(hipMemcpyAsync(G, g.G, fp * 8, hipMemcpyDeviceToHost, h->stream));
+    if (U) HM_HIP(hipMemcpyAsync(U, g.U, fp * 8, hipMemcpyDeviceToHost, h->stream));
+    if (w1) HM_HIP(hipMemcpyAsync(w1, q.w1, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
+    if (w2) HM_HIP(hipMemcpyAsync(w2, q.w2, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
+    if (c) HM_HIP(hipMemcpyAsync(c, q.c, P * nw * 8, hipMemcpyDeviceToHost, h->stream));
+    if (u1) HM_HIP(hipMemcpyAsync(u1, q.u1, (size_t)P * 8, hipMemcpyDeviceToHost, h->stream));
+    if (u2) HM_HIP(hipMemcpyAsync(u2, q.u2, (size_t)P * 8, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds, int R, const uint16_t *weights, uint64_t *out)
+{
+    HM_ARG(P >= 1 && seeds && weights && out, "hm_body_rec_weighted_sums: NULL argument or %d seeds", P);
+    HM_ARG(R >= 0 && R <= REC_RMAX, "hm_body_rec_weighted_sums: window radius %d outside 0..%d", R, REC_RMAX);
+    HM_ARG(h != nullptr, "hm_body_rec_weighted_sums: NULL handle");
+    HM_TRY(body_rec_seeded(h, P, seeds, "hm_body_rec_weighted_sums"));
+    const int F = h->rec.frames;
+    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
+    int2 *d_seeds = nullptr;
+    uint16_t *d_w = nullptr;
+    unsigned long long *d_out = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_seeds = cv.take<int2>(P);
+        d_w = cv.take<uint16_t>(P * nw);
+        d_out = cv.take<unsigned long long>(fp);
+    }));
+    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_w, weights, P * nw * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_rec_weighted_sums, dim3(hm_cdiv((int)fp, 4)), dim3(256), 0, h->stream, h->rec.box,
+                       (const uint8_t *const *)h->rec.tab, F, P, R, (const int2 *)d_seeds, (const uint16_t *)d_w, d_out);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, d_out, fp * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seeds, int R, const int32_t *q, int64_t *out)
+{
+    HM_ARG(P >= 1 && seeds && q && out, "hm_body_rec_trace_products: NULL argument or %d seeds", P);
+    HM_ARG(R >= 0 && R <= REC_WIN_RMAX, "hm_body_rec_trace_products: window radius %d outside 0..%d", R, REC_WIN_RMAX);
+    HM_ARG(h != nullptr, "hm_body_rec_trace_products: NULL handle");
+    HM_TRY(body_rec_seeded(h, P, seeds, "hm_body_rec_trace_products"));
+    const int F = h->rec.frames;
+    // |v q| <= 255 x 2^31 per frame
+    HM_ARG((unsigned __int128)F * 255u * ((unsigned __int128)1 << 31) < ((unsigned __int128)1 << 63),
+           "hm_body_rec_trace_products: F x 255 x 2^31 = %d x 255 x 2^31 could pass 2^63", F);
+    const size_t nw = (size_t)(2 * R + 1) * (2 * R + 1), fp = (size_t)F * P;
+    const int tiles = hm_cdiv((int)nw, 64);
+    HM_ARG((long long)P * tiles < (1ll << 31), "hm_body_rec_trace_products: %d seeds x %d tiles of the window", P, tiles);
+    RecTP g;
+    int2 *d_seeds = nullptr;
+    int *d_q = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_seeds = cv.take<int2>(P);
+        d_q = cv.take<int>(fp);
+        g.out = cv.take<unsigned long long>(P * nw);
+    }));
+    HM_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)P * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_q, q, fp * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(g.out, 0, P * nw * sizeof(unsigned long long), h->stream));
+    g.b = h->rec.box; g.chunks = (const uint8_t *const *)h->rec.tab; g.F = F; g.P = P; g.R = R;
+    g.tpf = h->rec.tp_frames; g.seeds = d_seeds; g.q = d_q;
+    const int runs = hm_cdiv(F, g.tpf);
+    hipLaunchKernelGGL(k_rec_trace_products, dim3(P * tiles, std::min(runs, 65535)), dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, g.out, P * nw * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// ---- residual motion of the record: patch sums, sums at given shifts, the shift in place, the smooth field (stab_kernels.h)
+// the core of every patch on the host: core[y * pitch + x] = 1 where every box pixel within S of (x, y) is in the map `tri`
+// (W values per row; two passes of prefix sums: rows, then columns); n_core: per patch
+static void stab_core(const RecBox &b, const int *tri, int W, int B, int S, std::vector<uint8_t> &core, std::vector<uint32_t> &n_core)
+{
+    const RecGrid gr = rec_grid(b, B);
+    const int n1 = 2 * S + 1;
+    core.assign((size_t)b.pitch * b.bh, 0);
+    n_core.assign((size_t)gr.np, 0);
+    std::vector<uint8_t> hor((size_t)b.bw * b.bh, 0);
+    std::vector<int> pre((size_t)std::max(b.bw, b.bh) + 1);
+    for (int y = 0; y < b.bh; y++) {
+        pre[0] = 0;
+        for (int x = 0; x < b.bw; x++) pre[x + 1] = pre[x] + (tri[(size_t)(b.r0 + y) * W + b.c0 + x] >= 0);
+        for (int x = S; x + S < b.bw; x++) hor[(size_t)y * b.bw + x] = pre[x + S + 1] - pre[x - S] == n1;
+    }
+    for (int x = 0; x < b.bw; x++) {
+        pre[0] = 0;
+        for (int y = 0; y < b.bh; y++) pre[y + 1] = pre[y] + hor[(size_t)y * b.bw + x];
+        for (int y = S; y + S < b.bh; y++)
+            if (pre[y + S + 1] - pre[y - S] == n1) {
+                core[(size_t)y * b.pitch + x] = 1;
+                n_core[(size_t)(y / B) * gr.npx + x / B]++;
+            }
+    }
+}
+
+extern "C" int hm_body_rec_match(hm_ctx_t h, int k0, int n_frames, int B, int S, const uint8_t *tmpl, uint32_t *n_core,
+                                 uint32_t *A, uint32_t *V1, uint32_t *V2)
+{
+    HM_TRY(stab_patch_ok("hm_body_rec_match", B));
+    HM_ARG(S >= 0 && S <= STAB_SMAX, "hm_body_rec_match: search radius %d outside 0..%d", S, STAB_SMAX);
+    HM_ARG(h && tmpl, "hm_body_rec_match: NULL handle or template");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_match"));
+    HM_TRY(rec_range_ok(h, "hm_body_rec_match", k0, n_frames));
+    const RecBox &b = h->rec.box;
+    const RecGrid gr = rec_grid(b, B);
+    const int nsh = (2 * S + 1) * (2 * S + 1);
+    std::vector<uint8_t> core;
+    std::vector<uint32_t> cnt;
+    stab_core(b, h->body.h_tri.data(), h->W, B, S, core, cnt);
+    if (n_core) memcpy(n_core, cnt.data(), (size_t)gr.np * sizeof(uint32_t));
+    if (n_frames == 0 || !(A || V1 || V2)) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const size_t n = (size_t)h->W * h->H, no = (size_t)n_frames * gr.np * nsh;
+    StabMatch g;
+    uint8_t *d_tmpl = nullptr, *d_core = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_tmpl = cv.take<uint8_t>(n);
+        d_core = cv.take<uint8_t>(core.size());
+        g.A = A ? cv.take<unsigned>(no) : nullptr;
+        g.V1 = V1 ? cv.take<unsigned>(no) : nullptr;
+        g.V2 = V2 ? cv.take<unsigned>(no) : nullptr;
+    }));
+    HM_HIP(hipMemcpyAsync(d_tmpl, tmpl, n, hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_core, core.data(), core.size(), hipMemcpyHostToDevice, h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.W = h->W; g.k0 = k0; g.F = n_frames; g.tpf = h->rec.tp_frames;
+    g.B = B; g.S = S; g.npx = gr.npx; g.np = gr.np; g.tmpl = d_tmpl; g.core = d_core;
+    const int runs = hm_cdiv(n_frames, g.tpf);
+    hipLaunchKernelGGL(k_stab_match, dim3(gr.np, std::min(runs, 65535)), dim3(256), stab_lds_bytes(B, S), h->stream, g);
+    HM_HIP(hipGetLastError());
+    if (A) HM_HIP(hipMemcpyAsync(A, g.A, no * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (V1) HM_HIP(hipMemcpyAsync(V1, g.V1, no * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (V2) HM_HIP(hipMemcpyAsync(V2, g.V2, no * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// every shift of `count` (dx, dy) pairs within +-STAB_DMAX
+static int stab_shifts_ok(const int8_t *shifts, size_t count, int np, const char *who)
+{
+    for (size_t i = 0; i < 2 * count; i++)
+        HM_ARG(shifts[i] >= -STAB_DMAX && shifts[i] <= STAB_DMAX, "%s: shift %d (%s of patch %zu, frame %zu of those given) outside -%d..%d",
+               who, (int)shifts[i], i & 1 ? "dy" : "dx", (i / 2) % (size_t)np, (i / 2) / (size_t)np, STAB_DMAX, STAB_DMAX);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_frame_sums(hm_ctx_t h, int k0, int n_frames, int B, const int8_t *shifts, uint32_t *out)
+{
+    if (shifts) HM_TRY(stab_patch_ok("hm_body_rec_frame_sums", B));
+    HM_ARG((long long)n_frames * 255 < (1ll << 32), "hm_body_rec_frame_sums: %d frames x 255 could pass 2^32", n_frames);
+    HM_ARG(h && out, "hm_body_rec_frame_sums: NULL handle or output");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_frame_sums"));
+    HM_TRY(rec_range_ok(h, "hm_body_rec_frame_sums", k0, n_frames));
+    const RecBox &b = h->rec.box;
+    StabSum g;
+    g.B = shifts ? B : 1;
+    const RecGrid gr = rec_grid(b, g.B);
+    g.npx = gr.npx; g.np = gr.np;
+    const size_t n = (size_t)h->W * h->H, ns = shifts ? (size_t)n_frames * g.np : 0;
+    if (shifts) HM_TRY(stab_shifts_ok(shifts, ns, g.np, "hm_body_rec_frame_sums"));
+    int8_t *d_sh = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        g.out = cv.take<unsigned>(n);
+        d_sh = cv.take<int8_t>(2 * ns);
+    }));
+    if (ns) HM_HIP(hipMemcpyAsync(d_sh, shifts, 2 * ns, hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(g.out, 0, n * sizeof(unsigned), h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.W = h->W; g.k0 = k0; g.F = n_frames;
+    g.tri_of = h->body.tri; g.shifts = ns ? d_sh : nullptr;
+    hipLaunchKernelGGL(k_stab_frame_sums, dim3(hm_cdiv(b.bw * b.bh, 256)), dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, g.out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_shift(hm_ctx_t h, int B, const int8_t *shifts)
+{
+    HM_TRY(stab_patch_ok("hm_body_rec_shift", B));
+    HM_ARG(h && shifts, "hm_body_rec_shift: NULL handle or shifts");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_shift"));
+    const RecBox &b = h->rec.box;
+    const RecGrid gr = rec_grid(b, B);
+    const int F = h->rec.frames;
+    StabShift g;
+    g.b = b; g.W = h->W; g.B = B; g.npx = gr.npx; g.np = gr.np; g.tri_of = h->body.tri;
+    const size_t ns = (size_t)F * g.np;
+    HM_TRY(stab_shifts_ok(shifts, ns, g.np, "hm_body_rec_shift"));
+    int8_t *d_sh = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) { d_sh = cv.take<int8_t>(2 * ns); }));
+    return rec_with_scratch(h, std::min(b.fpc, F), [&](int per) -> int {
+        HM_HIP(hipMemcpyAsync(d_sh, shifts, 2 * ns, hipMemcpyHostToDevice, h->stream));
+        return rec_rewrite(h, per, [&](dim3 grid, const uint8_t *src, uint8_t *dst, int k, int m) {
+            g.frames = m; g.shifts = d_sh + 2 * (size_t)k * g.np; g.src = src; g.dst = dst;
+            hipLaunchKernelGGL(k_stab_shift, grid, dim3(256), 0, h->stream, g);
+        });
+    });
+}
+
+// every q of `count` (dx, dy) pairs within +-STAB_QMAX; packed with its validity for the device
+static int stab_field_pack(const int16_t *q, const uint8_t *valid, size_t count, int np, const char *who, std::vector<unsigned> &qv)
+{
+    qv.resize(count);
+    for (size_t i = 0; i < count; i++) {
+        for (int c = 0; c < 2; c++)
+            HM_ARG(q[2 * i + c] >= -STAB_QMAX && q[2 * i + c] <= STAB_QMAX,
+                   "%s: q %d (%s of patch %zu, frame %zu of those given) outside -%d..%d", who, (int)q[2 * i + c], c ? "dy" : "dx",
+                   i % (size_t)np, i / (size_t)np, STAB_QMAX, STAB_QMAX);
+        qv[i] = stab_pack(q[2 * i], q[2 * i + 1], valid[i]);
+    }
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_field_sums(hm_ctx_t h, int k0, int n_frames, int B, const int16_t *q, const uint8_t *valid, uint32_t *out)
+{
+    HM_TRY(stab_patch_ok("hm_body_rec_field_sums", B));
+    HM_ARG((long long)n_frames * 255 < (1ll << 32), "hm_body_rec_field_sums: %d frames x 255 could pass 2^32", n_frames);
+    HM_ARG(h && q && valid && out, "hm_body_rec_field_sums: NULL handle, q, valid or output");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_field_sums"));
+    HM_TRY(rec_range_ok(h, "hm_body_rec_field_sums", k0, n_frames));
+    const RecBox &b = h->rec.box;
+    const RecGrid gr = rec_grid(b, B);
+    StabFieldSum g;
+    g.B = B; g.npx = gr.npx; g.npy = gr.npy; g.np = gr.np;
+    const size_t n = (size_t)h->W * h->H, ns = (size_t)n_frames * g.np;
+    std::vector<unsigned> qv;
+    HM_TRY(stab_field_pack(q, valid, ns, g.np, "hm_body_rec_field_sums", qv));
+    unsigned *d_qv = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        g.out = cv.take<unsigned>(n);
+        d_qv = cv.take<unsigned>(ns);
+    }));
+    if (ns) HM_HIP(hipMemcpyAsync(d_qv, qv.data(), ns * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(g.out, 0, n * sizeof(unsigned), h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.W = h->W; g.k0 = k0; g.F = n_frames;
+    g.tri_of = h->body.tri; g.qv = d_qv;
+    hipLaunchKernelGGL(k_stab_field_sums, dim3(hm_cdiv(b.bw * b.bh, 256)), dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, g.out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_warp(hm_ctx_t h, int B, const int16_t *q, const uint8_t *valid)
+{
+    HM_TRY(stab_patch_ok("hm_body_rec_warp", B));
+    HM_ARG(h && q && valid, "hm_body_rec_warp: NULL handle, q or valid");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_warp"));
+    const RecBox &b = h->rec.box;
+    const RecGrid gr = rec_grid(b, B);
+    const int F = h->rec.frames;
+    StabWarp g;
+    g.b = b; g.W = h->W; g.B = B; g.npx = gr.npx; g.npy = gr.npy; g.np = gr.np; g.tri_of = h->body.tri;
+    const size_t ns = (size_t)F * g.np;
+    std::vector<unsigned> qv;
+    HM_TRY(stab_field_pack(q, valid, ns, g.np, "hm_body_rec_warp", qv));
+    unsigned *d_qv = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) { d_qv = cv.take<unsigned>(ns); }));
+    return rec_with_scratch(h, std::min(b.fpc, F), [&](int per) -> int {
+        HM_HIP(hipMemcpyAsync(d_qv, qv.data(), ns * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+        return rec_rewrite(h, per, [&](dim3 grid, const uint8_t *src, uint8_t *dst, int k, int m) {
+            g.frames = m; g.qv = d_qv + (size_t)k * g.np; g.src = src; g.dst = dst;
+            hipLaunchKernelGGL(k_stab_warp, grid, dim3(256), 0, h->stream, g);
+        });
+    });
+}
+
+// ---- the running baseline per pixel of the record: baseline, excess and dF/F planes (detrend_kernels.h) -------------
+static int det_args_ok(const char *who, int what, int half, int q, int floor, int gain)
+{
+    HM_ARG(what >= 0 && what <= 3, "%s: kind of plane %d outside 0..3 (0 as recorded, 1 baseline, 2 excess, 3 dF/F byte)", who, what);
+    HM_ARG(half >= 0 && half <= DET_HALF_MAX, "%s: half %d outside 0..%d", who, half, DET_HALF_MAX);
+    HM_ARG(q >= 0 && q <= 100, "%s: q %d outside 0..100", who, q);
+    HM_ARG(floor >= 1 && floor <= 255, "%s: floor %d outside 1..255", who, floor);
+    HM_ARG(gain >= 1 && gain <= 65535, "%s: gain %d outside 1..65535", who, gain);
+    return HM_OK;
+}
+
+// the kind of plane and the baseline's parameters, as the two calls take them
+struct DetPlanes { int what, half, q, floor, gain; };
+
+// queue planes d.what (1..3) of the frames k .. k + m - 1 into dst (m frames in the record's layout)
+static int det_queue(hm_ctx *h, const DetPlanes &d, int k, int m, uint8_t *dst)
+{
+    RecRunning g;
+    g.b = h->rec.box; g.chunks = (const uint8_t *const *)h->rec.tab; g.F = h->rec.frames; g.k0 = k; g.n = m;
+    g.run = h->rec.bl_frames; g.what = d.what; g.half = d.half; g.q = d.q; g.floor = d.floor; g.gain = d.gain; g.out = dst;
+    const int segs = hm_cdiv(g.b.pitch * g.b.bh, 64), runs = hm_cdiv(m, g.run);
+    hipLaunchKernelGGL(k_rec_running, dim3(segs, std::min(runs, 65535)), dim3(64), DET_LDS_BYTES, h->stream, g);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_planes(hm_ctx_t h, int k0, int n_frames, int what, int half, int q, int floor, int gain, uint8_t *out)
+{
+    HM_TRY(det_args_ok("hm_body_rec_planes", what, half, q, floor, gain));
+    HM_ARG(h != nullptr, "hm_body_rec_planes: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_planes"));
+    HM_TRY(rec_range_ok(h, "hm_body_rec_planes", k0, n_frames));
+    HM_ARG(out || n_frames == 0, "hm_body_rec_planes: NULL output");
+    const size_t px = (size_t)h->W * h->H;
+    if (what == 0) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        for (int k = 0; k < n_frames; k++) HM_TRY(rec_expand(h, rec_frame(h, k0 + k), out + (size_t)k * px));
+        return HM_OK;
+    }
+    const DetPlanes d = {what, half, q, floor, gain};
+    return rec_with_scratch(h, n_frames, [&](int per) -> int {
+        HM_TRY(rec_runs(h, per, k0, n_frames, true, [&](int k, int m, uint8_t *dst) { return det_queue(h, d, k, m, dst); },
+                        [&](int j, const uint8_t *src) { return rec_expand(h, src, out + (size_t)j * px); }));
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    });
+}
+
+extern "C" int hm_body_rec_stats_add(hm_ctx_t h, int what, int half, int q, int floor, int gain)
+{
+    HM_TRY(det_args_ok("hm_body_rec_stats_add", what, half, q, floor, gain));
+    HM_ARG(h != nullptr, "hm_body_rec_stats_add: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_stats_add"));
+    HM_TRY(rec_stats_open(h, "hm_body_rec_stats_add"));
+    const int F = h->rec.frames;
+    if (what == 0) {
+        for (int k = 0; k < F; k++) HM_TRY(rec_stats_add_plane(h, rec_frame(h, k)));
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const DetPlanes d = {what, half, q, floor, gain};
+    return rec_with_scratch(h, F, [&](int per) -> int {
+        // (a run's planes are queued behind the adds that read the scratch)
+        HM_TRY(rec_runs(h, per, 0, F, false, [&](int k, int m, uint8_t *dst) { return det_queue(h, d, k, m, dst); },
+                        [&](int, const uint8_t *src) { return rec_stats_add_plane(h, src); }));
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    });
+}
+
+// ---- the residual of the record: what the cells' model leaves of every frame (residual_kernels.h) --------------------
+static int res_args_ok(const char *who, int n_layers, const int32_t *labels, int L, const int32_t *traces, int offset)
+{
+    HM_ARG(n_layers >= 1 && n_layers <= 4, "%s: %d layers outside 1..4", who, n_layers);
+    HM_ARG(L >= 1 && L <= REC_RES_LMAX, "%s: %d labels outside 1..%d", who, L, REC_RES_LMAX);
+    HM_ARG(offset >= 0 && offset <= 255, "%s: offset %d outside 0..255", who, offset);
+    HM_ARG(labels && traces, "%s: NULL labels or traces", who);
+    return HM_OK;
+}
+
+// The cells of the box as k_rec_residual reads them, from the caller's planes: per layer and box pixel the label and its
+// weight in one dword (lay), the pixels that count (live: in the map `tri` and not under a blank) and the layers a segment
+// of 256 pixels needs (seg_nl).  Off the map and under a blank nothing is packed: a segment of such pixels alone costs
+// no layer.  The labels are within -1 .. L - 1 (hm_labels_ok).
+static void res_pack_host(const RecBox &b, const int *tri, int W, int H, int n_layers, const int32_t *labels, const uint16_t *weights,
+                          const uint8_t *blank, std::vector<unsigned> &lay, std::vector<uint8_t> &live, std::vector<uint8_t> &seg_nl)
+{
+    const size_t n = (size_t)W * H, npx = (size_t)b.pitch * b.bh;
+    lay.assign((size_t)n_layers * npx, 0u);
+    live.assign(npx, 0);
+    seg_nl.assign(hm_cdiv((int)(npx >> 2), 64), 0);
+    for (int yb = 0; yb < b.bh; yb++)
+        for (int x = 0; x < b.bw; x++) {
+            const size_t p = (size_t)(b.r0 + yb) * W + b.c0 + x, i = (size_t)yb * b.pitch + x;
+            if (tri[p] < 0 || (blank && blank[p])) continue;
+            live[i] = 1;
+            for (int j = 0; j < n_layers; j++) {
+                const int s = labels[(size_t)j * n + p];
+                if (s < 0) continue;
+                lay[(size_t)j * npx + i] = ((unsigned)s << 16) | (weights ? (unsigned)weights[(size_t)j * n + p] : 65535u);
+                uint8_t &top = seg_nl[i >> 8];
+                top = std::max<uint8_t>(top, (uint8_t)(j + 1));
+            }
+        }
+}
+
+// The cells of the box, packed for k_rec_residual and sent to the device with the traces; a label outside -1 .. L - 1
+// anywhere in the planes is refused here.
+static int res_pack(hm_ctx *h, const char *who, int n_layers, const int32_t *labels, const uint16_t *weights, int L,
+                    const int32_t *traces, const uint8_t *blank, int offset, bool want_clipped, RecResidual &g)
+{
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames;
+    HM_ARG((long long)F * L < (1ll << 30), "%s: %d frames x %d labels", who, F, L);
+    HM_TRY(hm_labels_ok(who, n_layers, labels, (size_t)h->W * h->H, L));
+    std::vector<unsigned> lay;
+    std::vector<uint8_t> live, seg_nl;
+    res_pack_host(b, h->body.h_tri.data(), h->W, h->H, n_layers, labels, weights, blank, lay, live, seg_nl);
+    unsigned *d_lay = nullptr, *d_live = nullptr;
+    uint8_t *d_seg = nullptr;
+    int *d_tr = nullptr;
+    unsigned long long *d_clip = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_lay = cv.take<unsigned>(lay.size());
+        d_live = cv.take<unsigned>(live.size() >> 2);
+        d_seg = cv.take<uint8_t>(seg_nl.size());
+        d_tr = cv.take<int>((size_t)F * L);
+        d_clip = cv.take<unsigned long long>(1);
+    }));
+    // (pageable sources: each copy has left the host array when the call returns)
+    HM_HIP(hipMemcpyAsync(d_lay, lay.data(), lay.size() * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_live, live.data(), live.size(), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_seg, seg_nl.data(), seg_nl.size(), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_tr, traces, (size_t)F * L * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(d_clip, 0, sizeof(unsigned long long), h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.run = h->rec.res_frames; g.nl = n_layers; g.L = L; g.offset = offset;
+    g.lay = d_lay; g.live = d_live; g.seg_nl = d_seg; g.traces = d_tr; g.clipped = want_clipped ? d_clip : nullptr;
+    return HM_OK;
+}
+
+// queue the residual planes of the frames k .. k + m - 1 into dst (m frames in the record's layout)
+static int res_queue(hm_ctx *h, RecResidual g, int k, int m, uint8_t *dst)
+{
+    g.k0 = k; g.n = m; g.out = dst;
+    const int segs = hm_cdiv((g.b.pitch * g.b.bh) >> 2, 64), runs = hm_cdiv(m, g.run);
+    hipLaunchKernelGGL(k_rec_residual, dim3(segs, std::min(runs, 65535)), dim3(64), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+static int res_clipped(hm_ctx *h, const RecResidual &g, uint64_t *clipped)
+{
+    if (!clipped) return HM_OK;
+    unsigned long long c = 0;
+    HM_HIP(hipMemcpyAsync(&c, g.clipped, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    *clipped = c;
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_residual_planes(hm_ctx_t h, int k0, int n_frames, int n_layers, const int32_t *labels,
+                                           const uint16_t *weights, int L, const int32_t *traces, const uint8_t *blank,
+                                           int offset, uint8_t *out, uint64_t *clipped)
+{
+    HM_TRY(res_args_ok("hm_body_rec_residual_planes", n_layers, labels, L, traces, offset));
+    HM_ARG(h != nullptr, "hm_body_rec_residual_planes: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_residual_planes"));
+    HM_TRY(rec_range_ok(h, "hm_body_rec_residual_planes", k0, n_frames));
+    HM_ARG(out || n_frames == 0, "hm_body_rec_residual_planes: NULL output");
+    RecResidual g;
+    HM_TRY(res_pack(h, "hm_body_rec_residual_planes", n_layers, labels, weights, L, traces, blank, offset, clipped != nullptr, g));
+    const size_t px = (size_t)h->W * h->H;
+    return rec_with_scratch(h, n_frames, [&](int per) -> int {
+        HM_TRY(rec_runs(h, per, k0, n_frames, true, [&](int k, int m, uint8_t *dst) { return res_queue(h, g, k, m, dst); },
+                        [&](int j, const uint8_t *src) { return rec_expand(h, src, out + (size_t)j * px); }));
+        return res_clipped(h, g, clipped);
+    });
+}
+
+extern "C" int hm_body_rec_residual_stats_add(hm_ctx_t h, int n_layers, const int32_t *labels, const uint16_t *weights, int L,
+                                              const int32_t *traces, const uint8_t *blank, int offset, uint64_t *clipped)
+{
+    HM_TRY(res_args_ok("hm_body_rec_residual_stats_add", n_layers, labels, L, traces, offset));
+    HM_ARG(h != nullptr, "hm_body_rec_residual_stats_add: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_residual_stats_add"));
+    HM_TRY(rec_stats_open(h, "hm_body_rec_residual_stats_add"));
+    RecResidual g;
+    HM_TRY(res_pack(h, "hm_body_rec_residual_stats_add", n_layers, labels, weights, L, traces, blank, offset, clipped != nullptr, g));
+    const int F = h->rec.frames;
+    return rec_with_scratch(h, F, [&](int per) -> int {
+        // (a run's planes are queued behind the adds that read the scratch)
+        HM_TRY(rec_runs(h, per, 0, F, false, [&](int k, int m, uint8_t *dst) { return res_queue(h, g, k, m, dst); },
+                        [&](int, const uint8_t *src) { return rec_stats_add_plane(h, src); }));
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return res_clipped(h, g, clipped);
+    });
+}

@@ -19,7 +19,7 @@ struct RecResidual {
     int k0, n;                         // the frames written: k0 .. k0 + n - 1
     int run;                           // frames per run
     int nl, L, offset;
-    // The host packs all of these for the box (readout.hip: res_pack), pixels as in a record's frame (row pitch b.pitch):
+    // The host packs all of these for the box (record.hip: res_pack_host), pixels as in a record's frame (row pitch b.pitch):
     const unsigned *lay;               // nl planes of pitch * bh dwords: label << 16 | weight; 0 (label 0, weight 0) for none
     const unsigned *live;              // pitch * bh bytes: 1 for a map pixel that is not blanked, else 0
     const uint8_t *seg_nl;             // per segment of 64 dwords: the layers 0 .. seg_nl - 1 carry a label somewhere in it

@@ -6,7 +6,7 @@
 // outside the map is registered as 0 (k_body_warp), so a sum over any set of box pixels is the sum over its map pixels:
 // the reductions look at the map only where they count pixels, which the host does.
 #pragma once
-#include "body_kernels.h"     // (struct RecBox, REC_TP_MAX: hm_types.h)
+#include "hm_types.h"         // (struct RecBox, REC_TP_MAX, d_peel_add)
 
 __device__ __forceinline__ const uint8_t *d_rec_frame(const RecBox &b, const uint8_t *const *chunks, int k)
 {

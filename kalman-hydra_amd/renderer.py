@@ -218,9 +218,7 @@ class Renderer:
         (P, 3) B G R) painted onto the gray frame (H, W) uint8 at state X -> (H, W, 3) uint8, B G R.  levels: (L,) uint8,
         the activity of every cell in this frame (None: 255)."""
         x, lv, flags, P, pts, pc, rad = self._view_cells_args(X, levels, outline, wire, points, point_colours, point_radius)
-        f = np.ascontiguousarray(frame, np.uint8)
-        if f.shape != (self.ny, self.nx):
-            raise ValueError("frame of shape %r for %dx%d frames" % (f.shape, self.nx, self.ny))
+        f = self._plane(frame, np.uint8, "frame")
         out = np.empty((self.ny, self.nx, 3), np.uint8)
         _lib.check(_lib.lib().hm_view_cells(self._h, _lib.ptr(x), _lib.ptr(f), _lib.ptr(lv), flags, P, _lib.ptr(pts), _lib.ptr(pc),
                                             rad, _lib.ptr(out)), "hm_view_cells")
@@ -236,6 +234,17 @@ class Renderer:
                    "hm_view_cells_dev")
 
     # -- the body-frame readout (hm_body_*; hydra_mi.body) ------------------------------------------------
+    def _plane(self, a, dtype, what):
+        """-> `a` as a contiguous (H, W) array of dtype; `what` names it in the refusal"""
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != (self.ny, self.nx):
+            raise ValueError("%s of shape %r for %dx%d frames" % (what, a.shape, self.nx, self.ny))
+        return a
+
+    def _rec_n(self, k0, n):
+        """-> the number of frames of a range k0, n of the record (n None: all from k0)"""
+        return self.body_rec_count() - int(k0) if n is None else int(n)
+
     def body_map(self):
         """-> (triangle per pixel (H, W) int32, -1 outside the mesh; pixels per triangle (T,) uint32) at X = uv."""
         tri = np.empty((self.ny, self.nx), np.int32)
@@ -251,9 +260,7 @@ class Renderer:
         if labels is None:
             _lib.check(_lib.lib().hm_body_set_labels(self._h, None, 0, None), "hm_body_set_labels")
             return np.zeros(0, np.uint32)
-        lab = np.ascontiguousarray(labels, np.int32)
-        if lab.shape != (self.ny, self.nx):
-            raise ValueError("label image of shape %r for %dx%d frames" % (lab.shape, self.nx, self.ny))
+        lab = self._plane(labels, np.int32, "label image")
         cnt = np.empty(int(L), np.uint32)
         _lib.check(_lib.lib().hm_body_set_labels(self._h, _lib.ptr(lab), int(L), _lib.ptr(cnt)), "hm_body_set_labels")
         self._body_L = int(L)
@@ -270,9 +277,7 @@ class Renderer:
         x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
         if x.shape[0] < 2 * self.n:
             raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
-        f = np.ascontiguousarray(frame, np.uint8)
-        if f.shape != (self.ny, self.nx):
-            raise ValueError("frame of shape %r for %dx%d frames" % (f.shape, self.nx, self.ny))
+        f = self._plane(frame, np.uint8, "frame")
         out = np.empty((self.ny, self.nx), np.uint8)
         ts = np.empty(self.tri.shape[0], np.uint64)
         ls = np.empty(self._body_L, np.uint64) if self._body_L else None    # (the library writes L values there)
@@ -359,7 +364,7 @@ class Renderer:
 
     def body_rec_fetch(self, k0=0, n=None):
         """-> recorded frames k0 .. k0 + n - 1 (default: all from k0) as (n, H, W) uint8"""
-        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        n = self._rec_n(k0, n)
         out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
         _lib.check(_lib.lib().hm_body_rec_fetch(self._h, int(k0), n, _lib.ptr(out)), "hm_body_rec_fetch")
         return out
@@ -367,9 +372,7 @@ class Renderer:
     def body_rec_label_sums(self, labels, L):
         """hm_body_rec_label_sums: a label image (H, W) int32 given now -> (F, L) uint64, the sums per label of every
         recorded frame."""
-        lab = np.ascontiguousarray(labels, np.int32)
-        if lab.shape != (self.ny, self.nx):
-            raise ValueError("label image of shape %r for %dx%d frames" % (lab.shape, self.nx, self.ny))
+        lab = self._plane(labels, np.int32, "label image")
         out = np.empty((self.body_rec_count(), int(L)), np.uint64)
         _lib.check(_lib.lib().hm_body_rec_label_sums(self._h, _lib.ptr(lab), int(L), _lib.ptr(out)), "hm_body_rec_label_sums")
         return out
@@ -433,14 +436,12 @@ class Renderer:
         """hm_body_rec_match: template (H, W) uint8 in body coordinates -> dict: n_core (patches,) uint32 and, of A, V1,
         V2, those in `want` as (n, patches, (2S+1)^2) uint32: the sums over every patch's core of v(p + d) t(p),
         v(p + d) and v(p + d)^2 for the frames k0 .. k0 + n - 1 (default: all from k0)."""
-        t = np.ascontiguousarray(template, np.uint8)
-        if t.shape != (self.ny, self.nx):
-            raise ValueError("template of shape %r for %dx%d frames" % (t.shape, self.nx, self.ny))
+        t = self._plane(template, np.uint8, "template")
         B, S = int(B), int(S)
         if not (4 <= B <= 64 and 0 <= S <= 8):                   # (the call says so with its numbers; no grid to size for)
             _lib.check(_lib.lib().hm_body_rec_match(self._h, int(k0), 0, B, S, _lib.ptr(t), None, None, None, None),
                        "hm_body_rec_match")
-        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        n = self._rec_n(k0, n)
         npx, npy = self.body_rec_patches(B)
         o = dict(n_core=np.empty(npx * npy, np.uint32))
         for key in want:
@@ -463,7 +464,7 @@ class Renderer:
     def body_rec_frame_sums(self, shifts=None, B=16, k0=0, n=None):
         """hm_body_rec_frame_sums: -> (H, W) uint32, the sum over the frames k0 .. k0 + n - 1 of every map pixel taken at
         its patch's shift of that frame; shifts (n, patches, 2) int8 (dx, dy), None: no shift."""
-        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        n = self._rec_n(k0, n)
         sh = None
         if shifts is not None:
             sh = self._body_shifts(shifts, B, "body_rec_frame_sums")
@@ -499,7 +500,7 @@ class Renderer:
     def body_rec_field_sums(self, q, valid, B, k0=0, n=None):
         """hm_body_rec_field_sums: -> (H, W) uint32, the sum over the frames k0 .. k0 + n - 1 of every map pixel sampled at
         the smooth field of that frame; q (n, patches, 2) int16 (dx, dy) in 1/16 px, valid (n, patches)."""
-        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        n = self._rec_n(k0, n)
         q, valid = self._body_field(q, valid, B, "body_rec_field_sums")
         if q.shape[0] != n:
             raise ValueError("body_rec_field_sums: q of %d frames for %d" % (q.shape[0], n))
@@ -527,7 +528,7 @@ class Renderer:
         q (window - 1) // 100 of the frames k - half .. k + half of the whole record, the excess what lies above it, dff
         min(255, gain excess // max(baseline, floor))."""
         what = self.PLANES[what] if isinstance(what, str) else int(what)
-        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        n = self._rec_n(k0, n)
         out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
         _lib.check(_lib.lib().hm_body_rec_planes(self._h, int(k0), n, what, int(half), int(q), int(floor), int(gain),
                                                  _lib.ptr(out)), "hm_body_rec_planes")
@@ -553,9 +554,7 @@ class Renderer:
         F = self.body_rec_count()
         if tr.ndim != 2 or (F and tr.shape[0] != F):             # (F 0: the call says why)
             raise ValueError("%s: traces of shape %r for a record of %d frames" % (who, tr.shape, F))
-        bl = None if blank is None else np.ascontiguousarray(blank, np.uint8)
-        if bl is not None and bl.shape != (self.ny, self.nx):
-            raise ValueError("%s: a blank plane of shape %r for %dx%d frames" % (who, bl.shape, self.nx, self.ny))
+        bl = None if blank is None else self._plane(blank, np.uint8, "%s: a blank plane" % who)
         return lab, w, tr, bl
 
     def body_rec_residual_planes(self, labels, weights, traces, blank=None, offset=64, k0=0, n=None):
@@ -564,7 +563,7 @@ class Renderer:
         24))), 0 off the map and where blank is set.  labels (n_layers, H, W) or (H, W) int32 (-1: none), weights the
         same shape uint16 (None: 65535), as view_set_cells takes them; traces (F, L) int32 for all recorded frames."""
         lab, w, tr, bl = self._residual_args("body_rec_residual_planes", labels, weights, traces, blank)
-        n = self.body_rec_count() - int(k0) if n is None else int(n)
+        n = self._rec_n(k0, n)
         out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
         clipped = ctypes.c_uint64(0)
         _lib.check(_lib.lib().hm_body_rec_residual_planes(self._h, int(k0), n, int(lab.shape[0]), _lib.ptr(lab), _lib.ptr(w),

@@ -346,3 +346,43 @@ def test_cli_detrend_end_to_end(hm, tmp_path):
         assert all(np.array_equal(got[k][:, :, c], want[k]) for c in range(3)), k
     bad = subprocess.run(base + [out1, "--detrend"], capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert bad.returncode == 2 and "--detrend finds the cells in the excess video: it needs --find-points" in bad.stderr
+
+
+def _frame_bytes(m):
+    """bytes of one frame of the record: the map's bounding box, rows padded to 4 bytes, the frame to 16"""
+    cols, rows = np.flatnonzero(m.any(0)), np.flatnonzero(m.any(1))
+    pitch = (int(cols[-1] - cols[0]) + 1 + 3) & ~3
+    return (pitch * (int(rows[-1] - rows[0]) + 1) + 15) & ~15
+
+
+def test_every_scratch_size_gives_the_same_planes_and_statistics(hm):
+    """5 frames in chunks of 3, scratch for two frames (runs of 2, 2, 1), for less than one (the floor: one frame at a time)
+    and for all of them"""
+    kf, r, m, regs = _record("16", F=5, chunk=3)
+    fs = _frame_bytes(m)
+    want = {what: ref.planes(regs, m, what, 2, 50, 16, 255) for what in (1, 2, 3)}
+    stats = bs.accumulate(want[2], m)
+    assert want[2].any()
+    for scratch in (2 * fs, fs - 1, 16 << 20):
+        r.tune("rec_scratch_bytes", scratch)
+        for what in (1, 2, 3):
+            assert np.array_equal(r.body_rec_planes(what, 2, 50, 16, 255), want[what]), (scratch, what)
+            assert np.array_equal(r.body_rec_planes(what, 2, 50, 16, 255, 1, 4), want[what][1:]), (scratch, what)
+        r.body_stats_begin()
+        r.body_rec_stats_add(2, 2, 50, 16, 255)
+        assert r.body_stats_count() == 5
+        for g, w in zip(r.body_stats_fetch(), stats):
+            assert np.array_equal(g, w), scratch
+    assert np.array_equal(r.body_rec_fetch(), regs)
+    kf.close()
+
+
+def test_the_scratch_knob_refuses_what_is_outside_its_range(hm):
+    kf, r, m, regs = _record("16", F=1)
+    for v in (0, (1 << 30) + 1):
+        with pytest.raises(RuntimeError, match=r"code -1.*rec_scratch_bytes must be in 1\.\.%d" % (1 << 30)):
+            r.tune("rec_scratch_bytes", v)
+    r.tune("rec_scratch_bytes", 1)
+    r.tune("rec_scratch_bytes", 1 << 30)
+    r.tune("rec_scratch_bytes", 16 << 20)
+    kf.close()

@@ -25,9 +25,9 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
-def _record():
+def _record(F=F, chunk=2):
     """A 64 x 48 frame with a disc of a mesh (a box 41 px wide: the last dword of a row and the last segment of a frame are
-    partial; pixels of the box off the map), 7 random frames recorded at perturbed states in chunks of two frames
+    partial; pixels of the box off the map), F random frames recorded at perturbed states in chunks of `chunk` frames
     -> (kf, renderer, map, recorded frames)"""
     from hydra_mi import mesh
     dm = mesh.disk_mesh(31.5, 23.5, 20.3, 7.0)
@@ -37,7 +37,7 @@ def _record():
     r = kf.state.renderer
     m = r.body_map()[0] >= 0
     N = dm.size()
-    r.tune("body_rec_chunk", 2)
+    r.tune("body_rec_chunk", chunk)
     r.body_rec_begin()
     for k in range(F):
         f = rng.integers(0, 256, (H, W), dtype=np.uint8)
@@ -362,3 +362,39 @@ def test_cli_find_more_end_to_end(hm, tmp_path):
                         (["--find-points", "3", "--residual-video", "x.avi"], "it needs --demix or --find-more")):
         bad = subprocess.run(base + [out1] + flags, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
         assert bad.returncode == 2 and text in bad.stderr, flags
+
+
+def _frame_bytes(m):
+    """bytes of one frame of the record: the map's bounding box, rows padded to 4 bytes, the frame to 16"""
+    cols, rows = np.flatnonzero(m.any(0)), np.flatnonzero(m.any(1))
+    pitch = (int(cols[-1] - cols[0]) + 1 + 3) & ~3
+    return (pitch * (int(rows[-1] - rows[0]) + 1) + 15) & ~15
+
+
+def test_every_scratch_size_gives_the_same_planes_and_statistics(hm):
+    """5 frames in chunks of 3, scratch for two frames (runs of 2, 2, 1), for less than one (the floor: one frame at a time)
+    and for all of them"""
+    kf, r, m, regs = _record(F=5, chunk=3)
+    fs = _frame_bytes(m)
+    rng = np.random.default_rng(17)
+    lab, wt = _layers(_cells(m), 4, 5, rng)
+    tr = rng.integers(-450 * 256, 450 * 256, (5, 5)).astype(np.int32)
+    blank = np.zeros((H, W), np.uint8)
+    blank[22:26, 30:34] = 1
+    planes, clipped = ref.planes(regs, m, lab, wt, tr, blank, 64)
+    part = ref.planes(regs[1:], m, lab, wt, tr[1:], blank, 64)
+    stats = bs.accumulate(planes, m)
+    assert clipped > 0
+    for scratch in (2 * fs, fs - 1, 16 << 20):
+        r.tune("rec_scratch_bytes", scratch)
+        p, c = r.body_rec_residual_planes(lab, wt, tr, blank, 64)
+        assert np.array_equal(p, planes) and c == clipped, scratch
+        p, c = r.body_rec_residual_planes(lab, wt, tr, blank, 64, 1, 4)
+        assert np.array_equal(p, part[0]) and c == part[1], scratch
+        r.body_stats_begin()
+        assert r.body_rec_residual_stats_add(lab, wt, tr, blank, 64) == clipped, scratch
+        assert r.body_stats_count() == 5
+        for g, w in zip(r.body_stats_fetch(), stats):
+            assert np.array_equal(g, w), scratch
+    assert np.array_equal(r.body_rec_fetch(), regs)
+    kf.close()

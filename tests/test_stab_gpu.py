@@ -23,9 +23,9 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
-def _record(name, chunk=2, tp=3):
-    """A filter on the scene with every frame recorded twice, in chunks of two frames, runs of three frames per workgroup
-    (so that runs cross chunks) -> (kf, renderer, map, recorded frames)"""
+def _record(name, chunk=2, tp=3, F=None):
+    """A filter on the scene with every frame recorded twice (the first F of those, if given), in chunks of two frames, runs
+    of three frames per workgroup (so that runs cross chunks) -> (kf, renderer, map, recorded frames)"""
     dm, Xs, frames, f0 = cases.scene(name)
     kf = cases.make_filter(dm, f0)
     r = kf.state.renderer
@@ -33,9 +33,8 @@ def _record(name, chunk=2, tp=3):
     r.tune("body_rec_chunk", chunk)
     r.tune("rec_tp_frames", tp)
     r.body_rec_begin()
-    for rep in range(2):
-        for X, f in zip(Xs, frames):
-            r.body_warp(X, f)
+    for X, f in (2 * list(zip(Xs, frames)))[:F]:
+        r.body_warp(X, f)
     r.tune("body_rec_chunk", 0)
     regs = r.body_rec_fetch()
     assert not regs[:, ~m].any()
@@ -296,3 +295,34 @@ def test_cli_stabilize_end_to_end(hm, tmp_path):
     bad = subprocess.run(base + [out1, "--find-points", "3", "--stabilize"], capture_output=True, text=True, timeout=300,
                          cwd=str(tmp_path))
     assert bad.returncode == 2 and "--stabilize works on the kept record: it needs --rois or --demix" in bad.stderr
+
+
+def _frame_bytes(m):
+    """bytes of one frame of the record: the map's bounding box, rows padded to 4 bytes, the frame to 16"""
+    cols, rows = np.flatnonzero(m.any(0)), np.flatnonzero(m.any(1))
+    pitch = (int(cols[-1] - cols[0]) + 1 + 3) & ~3
+    return (pitch * (int(rows[-1] - rows[0]) + 1) + 15) & ~15
+
+
+def test_every_scratch_size_gives_the_same_shifted_record(hm):
+    """5 frames in chunks of 3, scratch for two frames (runs of 2, 1, 2: they stop at the chunk), for less than one (the
+    floor: one frame at a time) and for all of them"""
+    kf, r, m, regs = _record("16", chunk=3, F=5)
+    fs = _frame_bytes(m)
+    npatch = ref.patch_grid(m, 4)["npx"] * ref.patch_grid(m, 4)["npy"]
+    sh = np.random.default_rng(5).integers(-3, 4, (5, npatch, 2)).astype(np.int8)
+    want = ref.shift(regs, m, 4, sh)
+    assert regs.shape[0] == 5 and all((want[k] != regs[k]).any() for k in range(5))
+    dm, Xs, frames, f0 = cases.scene("16")
+    for scratch in (2 * fs, fs - 1, 16 << 20):
+        r.tune("rec_scratch_bytes", scratch)
+        r.body_rec_shift(sh, 4)
+        assert np.array_equal(r.body_rec_fetch(), want), scratch
+        r.tune("body_rec_chunk", 3)                                         # the record as it was
+        r.body_rec_begin()
+        for X, f in (2 * list(zip(Xs, frames)))[:5]:
+            r.body_warp(X, f)
+        r.tune("body_rec_chunk", 0)
+        assert np.array_equal(r.body_rec_fetch(), regs)
+    r.tune("rec_scratch_bytes", 16 << 20)
+    kf.close()

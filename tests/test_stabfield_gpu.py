@@ -25,18 +25,18 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
-def _fill(r, name, chunk=2):
-    """(re)start the record and record every frame of the scene twice, in chunks of two frames"""
+def _fill(r, name, chunk=2, F=None):
+    """(re)start the record and record every frame of the scene twice (the first F of those, if given), in chunks of two
+    frames"""
     dm, Xs, frames, f0 = cases.scene(name)
     r.tune("body_rec_chunk", chunk)
     r.body_rec_begin()
-    for rep in range(2):
-        for X, f in zip(Xs, frames):
-            r.body_warp(X, f)
+    for X, f in (2 * list(zip(Xs, frames)))[:F]:
+        r.body_warp(X, f)
     r.tune("body_rec_chunk", 0)
 
 
-def _record(name, chunk=2, tp=3):
+def _record(name, chunk=2, tp=3, F=None):
     """A filter on the scene with every frame recorded twice, in chunks of two frames, runs of three frames per workgroup
     (so that runs cross chunks) -> (kf, renderer, map, recorded frames)"""
     dm, Xs, frames, f0 = cases.scene(name)
@@ -44,7 +44,7 @@ def _record(name, chunk=2, tp=3):
     r = kf.state.renderer
     m = r.body_map()[0] >= 0
     r.tune("rec_tp_frames", tp)
-    _fill(r, name, chunk)
+    _fill(r, name, chunk, F)
     regs = r.body_rec_fetch()
     assert not regs[:, ~m].any()
     return kf, r, m, regs
@@ -302,3 +302,27 @@ def test_cli_stab_mode_field_end_to_end(hm, tmp_path):
     assert np.array_equal(z["roi_labels"], exp["roi_labels"]) and np.array_equal(z["roi_counts"], exp["roi_counts"])
     for key in ("roi_F", "roi_dff", "point_means"):
         assert not np.array_equal(z[key], zp[key]), key
+
+
+def _frame_bytes(m):
+    """bytes of one frame of the record: the map's bounding box, rows padded to 4 bytes, the frame to 16"""
+    cols, rows = np.flatnonzero(m.any(0)), np.flatnonzero(m.any(1))
+    pitch = (int(cols[-1] - cols[0]) + 1 + 3) & ~3
+    return (pitch * (int(rows[-1] - rows[0]) + 1) + 15) & ~15
+
+
+def test_every_scratch_size_gives_the_same_warped_record(hm):
+    """5 frames in chunks of 3, scratch for two frames (runs of 2, 1, 2: they stop at the chunk), for less than one (the
+    floor: one frame at a time) and for all of them"""
+    kf, r, m, regs = _record("16", chunk=3, F=5)
+    fs = _frame_bytes(m)
+    q, valid = _field(np.random.default_rng(6), 5, _npatch(m, 4), 48)
+    want = ref.warp(regs, m, 4, q, valid)
+    assert regs.shape[0] == 5 and (want != regs).any()
+    for scratch in (2 * fs, fs - 1, 16 << 20):
+        r.tune("rec_scratch_bytes", scratch)
+        r.body_rec_warp(q, valid, 4)
+        assert np.array_equal(r.body_rec_fetch(), want), scratch
+        _fill(r, "16", 3, 5)                                                # the record as it was
+    r.tune("rec_scratch_bytes", 16 << 20)
+    kf.close()
