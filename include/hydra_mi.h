@@ -533,6 +533,59 @@ int hm_body_warp_dev(hm_ctx_t h, const double *X, const void *d_frame, void *d_o
                      void *d_tri_sums, void *d_label_sums, void *stream);
 int hm_body_fence(hm_ctx_t h, void *stream);
 
+/* The deformation readout: how the tracked mesh stretches the body, which is what the tracker estimates and the
+ * reference never reports (it has the force arrows of plotforces alone).  The map body -> frame is affine on every
+ * triangle; per frame k and triangle t, in binary64, every step one correctly rounded operation in the order written,
+ * nothing contracted, + - * / sqrt fabs only (no hypot, atan2, log: angles are the caller's, on the host):
+ *   vertices  i0, i1, i2 of the body map (hm_body_map: the triangle's order after the orientation swap at X = uv);
+ *             U the binary32 uv widened; x the positions of frame k, x of vertex i at X[2 i], y at X[2 i + 1].
+ *   p = U1 - U0, q = U2 - U0, a = x1 - x0, b = x2 - x0;  d0 = p.x q.y - p.y q.x
+ *   F11 = (a.x q.y - b.x p.y) / d0    F12 = (b.x p.x - a.x q.x) / d0
+ *   F21 = (a.y q.y - b.y p.y) / d0    F22 = (b.y p.x - a.y q.x) / d0        the deformation gradient
+ *   J   = (a.x b.y - a.y b.x) / d0                                          the area ratio (< 0: the triangle is flipped)
+ *   c11 = F11 F11 + F21 F21,  c12 = F11 F12 + F21 F22,  c22 = F12 F12 + F22 F22
+ *   m = (c11 + c22) / 2,  d = (c11 - c22) / 2,  r = sqrt(d d + c12 c12)
+ *   l1 = sqrt(m + r)  the larger principal stretch;  l2 = |J| / l1 the smaller (0 where l1 == 0)
+ *   c2 = d / r, s2 = c12 / r  (1, 0 where r == 0): cosine and sine of TWICE the angle of the l1 axis in the body frame
+ *   tr = F11 + F22, sk = F21 - F12, s = sqrt(tr tr + sk sk);  rc = tr / s, rs = sk / s  (1, 0 where s == 0): cosine
+ *             and sine of the rotation of F's polar factor
+ * Seven doubles per (frame, triangle): J, l1, l2, c2, s2, rc, rs.  Where d0 == 0 or one of the six position
+ * coordinates is not finite all seven are NaN.
+ * hm_strain_tri: X n_frames rows of 4N doubles (the states as recorded; the 2N positions of a row are read), out
+ * n_frames x T x 7; one launch for all the frames.
+ * hm_strain_labels: the mean of J, l1, l2 over the body-map pixels of every label -- the local deformation under a
+ * cell.  labels: a W*H image in body coordinates as hm_body_set_labels takes it (-1 none, 0 .. L-1), or NULL: the
+ * image of the last hm_body_set_labels, whose L must be passed (none set: HM_ERR_STATE).  cnt[s, t] = the map pixels
+ * of label s in triangle t, n_s their sum over t:
+ *   out[k, s, j] = (sum of (double)cnt[s, t] * v[k, t, j] over the t with cnt[s, t] > 0 in ascending order, added one
+ *                  by one to 0.0) / (double)n_s,  j = J, l1, l2;
+ * no atomics, one accumulator per (k, s, j).  n_s == 0: NaN; a NaN triangle under a label makes that label NaN in that
+ * frame.  out n_frames x L x 3; counts (L, may be NULL): n_s.
+ * hm_view_strain: one of the three painted onto a frame of the video at state X; H x W x 3 uint8, B, G, R, like every
+ * view, with buffers of its own: it changes nothing a measurement, update or prediction reads.  Per image pixel:
+ *   base      B = G = R = frame[r, c], the gray frame passed.
+ *   triangle  the lowest-indexed triangle that covers the pixel centre at X, by the rule of hm_view_cells word for
+ *             word (positions snapped to 1/256 px, exact edge functions, top-left ties, orientation swap; a triangle
+ *             of area 0 or with a vertex not finite or beyond +-2^24 px is skipped); none: the pixel keeps the base.
+ *   level     of that triangle, in binary64: 128 + rint(gain (value - 1)), rint half to even, clamped to 0 .. 255;
+ *             value = J, l1 or l2 of the triangle at X as above for which = 0, 1, 2.  A level that is NaN (a NaN
+ *             value) keeps the base -- also where a later triangle covers the pixel as well.
+ *   colour    every channel becomes (ch (255 - alpha) + lut[level][ch] alpha + 127) / 255 in integers; lut 256 x 3
+ *             bytes, B G R.
+ *   wire      (flags bit 1, i.e. flags = 2) B = min(255, B + 128 count), the wireframe of hm_view.
+ * n_frames <= 0, which outside 0..2, alpha outside 0..255, a NULL lut, flags other than 0 or 2, a label >= L are
+ * HM_ERR_ARG (hm_last_error has the numbers); a failed allocation or launch is HM_ERR_HIP.
+ * hm_view_strain_dev: d_frame and d_bgr (4-byte aligned) are device memory; queued on the handle's stream, it does not
+ * wait (but for the body map, built by the first call that needs it): X and the lut are copied before it returns, the
+ * frame is read when the view runs; `stream` (may be NULL) waits for the view on the device, as in hm_view_dev.
+ * All buffers belong to the handle and are freed with it. */
+int hm_strain_tri(hm_ctx_t h, int n_frames, const double *X, double *out);
+int hm_strain_labels(hm_ctx_t h, int n_frames, const double *X, const int32_t *labels, int L, double *out, uint32_t *counts);
+int hm_view_strain(hm_ctx_t h, const double *X, const uint8_t *frame, int which, double gain, int alpha,
+                   const uint8_t *lut, int flags, uint8_t *bgr);
+int hm_view_strain_dev(hm_ctx_t h, const double *X, const void *d_frame, int which, double gain, int alpha,
+                       const uint8_t *lut, int flags, void *d_bgr, void *stream);
+
 /* Statistics of the registered video, for finding cells in the body frame.  Between begin and end every
  * hm_body_warp and hm_body_warp_dev adds its registered frame (also one called without an output), right
  * behind the warp on the handle's stream.  Per pixel p of the map, v_k the registered value of frame k:

@@ -133,6 +133,11 @@ SIGNATURES = {
     "hm_view_cells": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_view_cells_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp,
                                          c_vp]),
+    "hm_strain_tri": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp]),
+    "hm_strain_labels": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "hm_view_strain": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_vp, ctypes.c_int, c_vp]),
+    "hm_view_strain_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_vp, ctypes.c_int, c_vp,
+                                          c_vp]),
     "hm_body_map": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "hm_body_set_labels": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp]),
     "hm_body_warp": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

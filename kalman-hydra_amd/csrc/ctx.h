@@ -140,6 +140,16 @@ struct BodyState {
     double *pkscore = nullptr;
 };
 
+// hm_strain_*: the deformation readout (strain_kernels.h), buffers of its own, grown to the largest call so far
+struct StrainState {
+    double *X = nullptr;             // the states of a call (n_frames x 4N)
+    double *v = nullptr;             // J, l1, l2, c2, s2, rc, rs per frame and triangle (n_frames x T x 7)
+    int *off = nullptr, *ent_t = nullptr;            // cnt[s, t] of hm_strain_labels as compressed rows: L + 1 offsets, triangles,
+    unsigned *ent_c = nullptr, *n_s = nullptr;       // their pixel counts; the map pixels per label (L)
+    double *trace = nullptr;         // the traces per label (n_frames x L x 3)
+};
+#define STRAIN_MAX_GRID 2048         // workgroups of k_strain_tri / k_strain_label: they stride over what is beyond
+
 // hm_body_rec_*: the registered video of the warps queued between begin and end, kept on the device (record.hip)
 struct RecState {
     bool on = false;
@@ -318,12 +328,13 @@ struct hm_ctx {
     const uint8_t *prepared_mask = nullptr;   // hm_prepare_mask: the outline in the buffers is that of this mask (device memory)
     hipEvent_t ev_outline = nullptr; // ... recorded behind every outline queued on the second stream
     hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)
-    // The readout: views, the body-frame readout with its statistics, the kept record.  Each has buffers of its own, allocated
+    // The readout: views, the body-frame readout with its statistics, the deformation readout, the kept record.  Each has buffers of its own, allocated
     // on first use through `own`, and touches nothing the filter reads (readout.hip and record.hip have the code and name no
     // other field of the handle than W, H, N, T, device, own, stream, d_tri, d_uv, d_tex and, for the overlay, have_tex,
     // have_obs, o_yim).
     ViewState view;
     BodyState body;
+    StrainState strain;
     RecState rec;
 };
 

@@ -1,12 +1,14 @@
 // The readout of a filter handle: views (hm_view*), the body-frame readout and its statistics (hm_body_*, hm_body_stats_*),
-// and the flow tool's preview.  Host orchestration and C-ABI (include/hydra_mi.h); the kernels are in view_kernels.h and
-// body_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses view and body and reads W, H,
+// the deformation readout (hm_strain_*, hm_view_strain*) and the flow tool's preview.  Host orchestration and C-ABI
+// (include/hydra_mi.h); the kernels are in view_kernels.h, body_kernels.h and strain_kernels.h, which this translation unit
+// alone compiles.  Of the handle (ctx.h) it uses view, body and strain and reads W, H,
 // N, T, device, own, stream, the mesh (d_tri, d_uv, d_tex) and, for the overlay view, have_tex, have_obs and o_yim.  The
 // registered video kept on the device (hm_body_rec_*) is record.hip's: of rec, this file reads `on` alone, and a warp
 // reaches the record through body_rec_slot and body_rec_queue_copy (ctx.h).
 #include "ctx.h"
 #include "view_kernels.h"
 #include "body_kernels.h"
+#include "strain_kernels.h"
 #include <algorithm>
 #include <cstring>
 
@@ -176,6 +178,36 @@ extern "C" int hm_view_set_cells(hm_ctx_t h, int n_layers, const int32_t *labels
     return HM_OK;
 }
 
+// What a queued view reads of its caller's arrays goes through ViewState's slots: the next page-locked slot, free and at
+// least `bytes` long (waits only for the copy out of that very slot), with the device block c_in grown to hold it ...
+static int view_stage(hm_ctx *h, size_t bytes, uint8_t **slot)
+{
+    ViewState &v = h->view;
+    const int s = v.c_next;
+    HM_HIP(h->own.event(&v.c_slot_ev[s]));
+    if (v.c_slot_used[s]) HM_HIP(hipEventSynchronize(v.c_slot_ev[s]));      // (the copy out of this slot has run)
+    v.c_slot_used[s] = false;
+    HM_HIP(h->own.host_grow(&v.c_slot[s], bytes, hipHostMallocDefault));
+    const auto it = h->own.mem.find(v.c_in);
+    if (!v.c_in || it == h->own.mem.end() || it->second.bytes < bytes) {
+        HM_HIP(hipStreamSynchronize(h->stream));      // (a view in flight reads the block that grows)
+        HM_HIP(h->own.grow(&v.c_in, bytes));
+    }
+    *slot = v.c_slot[s];
+    return HM_OK;
+}
+// ... and, filled, copied to c_in on the handle's stream: the caller's arrays are free when this returns
+static int view_stage_send(hm_ctx *h, size_t bytes)
+{
+    ViewState &v = h->view;
+    const int s = v.c_next;
+    HM_HIP(hipMemcpyAsync(v.c_in, v.c_slot[s], bytes, hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipEventRecord(v.c_slot_ev[s], h->stream));
+    v.c_slot_used[s] = true;
+    v.c_next = (s + 1) % VIEW_CELL_SLOTS;
+    return HM_OK;
+}
+
 // Queue the cell view of frame d_frame (device) at state X (host) into d_out (device, W*H*3) on the handle's stream.
 static int view_cells_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, const uint8_t *levels, int flags, int P,
                             const double *points, const uint8_t *point_colours, int radius, uint8_t *d_out, const char *who)
@@ -200,27 +232,13 @@ static int view_cells_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, 
     const size_t bytes = oC + (size_t)3 * P;
     HM_HIP(h->own.event(&v.ev));
     if (wire) HM_HIP(h->own.alloc(&v.wire, (size_t)n * sizeof(unsigned)));
-    const int s = v.c_next;
-    HM_HIP(h->own.event(&v.c_slot_ev[s]));
-    if (v.c_slot_used[s]) HM_HIP(hipEventSynchronize(v.c_slot_ev[s]));      // (the copy out of this slot has run)
-    v.c_slot_used[s] = false;
-    HM_HIP(h->own.host_grow(&v.c_slot[s], bytes, hipHostMallocDefault));
-    {
-        const auto it = h->own.mem.find(v.c_in);
-        if (!v.c_in || it == h->own.mem.end() || it->second.bytes < bytes) {
-            HM_HIP(hipStreamSynchronize(h->stream));      // (a view in flight reads the block that grows)
-            HM_HIP(h->own.grow(&v.c_in, bytes));
-        }
-    }
-    uint8_t *slot = v.c_slot[s];
+    uint8_t *slot = nullptr;
+    HM_TRY(view_stage(h, bytes, &slot));
     memcpy(slot + oX, X, oP);
     if (P) memcpy(slot + oP, points, (size_t)2 * P * sizeof(double));
     if (levels && L) memcpy(slot + oL, levels, (size_t)L);
     if (P) memcpy(slot + oC, point_colours, (size_t)3 * P);
-    HM_HIP(hipMemcpyAsync(v.c_in, slot, bytes, hipMemcpyHostToDevice, h->stream));
-    HM_HIP(hipEventRecord(v.c_slot_ev[s], h->stream));
-    v.c_slot_used[s] = true;
-    v.c_next = (s + 1) % VIEW_CELL_SLOTS;
+    HM_TRY(view_stage_send(h, bytes));
     const double *dX = (const double *)(v.c_in + oX);
     if (wire) {
         HM_HIP(hipMemsetAsync(v.wire, 0, (size_t)n * sizeof(unsigned), h->stream));
@@ -441,6 +459,179 @@ extern "C" int hm_body_fence(hm_ctx_t h, void *stream)
     if (h->body.ev) {
         HM_HIP(hipSetDevice(h->device));
         HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->body.ev, 0));
+    }
+    return HM_OK;
+}
+
+// ---- the deformation readout (strain_kernels.h) ---------------------------------------------------------------------
+// n_frames rows of 4N doubles (host) into strain.X, k_strain_tri of all of them into strain.v (n_frames x T x 7), queued
+static int strain_queue_tri(hm_ctx *h, int n_frames, const double *X)
+{
+    StrainState &st = h->strain;
+    const size_t row = (size_t)4 * h->N, nx = (size_t)n_frames * row, nv = (size_t)n_frames * h->T * STRAIN_VALS;
+    {
+        // (a launch in flight reads the buffers that grow)
+        const auto ix = h->own.mem.find(st.X), iv = h->own.mem.find(st.v);
+        if (!st.X || !st.v || ix->second.bytes < nx * sizeof(double) || iv->second.bytes < nv * sizeof(double))
+            HM_HIP(hipStreamSynchronize(h->stream));
+    }
+    HM_HIP(h->own.grow(&st.X, nx * sizeof(double)));
+    HM_HIP(h->own.grow(&st.v, nv * sizeof(double)));
+    HM_HIP(hipMemcpyAsync(st.X, X, nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const long long total = (long long)n_frames * h->T;
+    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, STRAIN_MAX_GRID);
+    hipLaunchKernelGGL(k_strain_tri, dim3(grid), dim3(256), 0, h->stream, total, h->T, row, (const int4 *)h->body.tidx,
+                       (const float *)h->d_uv, (const double *)st.X, st.v);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_strain_tri(hm_ctx_t h, int n_frames, const double *X, double *out)
+{
+    HM_ARG(h && X && out, "hm_strain_tri: NULL argument");
+    HM_ARG(n_frames > 0, "hm_strain_tri: %d frames (need at least 1)", n_frames);
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_map_build(h));
+    HM_TRY(strain_queue_tri(h, n_frames, X));
+    HM_HIP(hipMemcpyAsync(out, h->strain.v, (size_t)n_frames * h->T * STRAIN_VALS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+extern "C" int hm_strain_labels(hm_ctx_t h, int n_frames, const double *X, const int32_t *labels, int L, double *out,
+                                uint32_t *counts)
+{
+    HM_ARG(h && X && out, "hm_strain_labels: NULL argument");
+    HM_ARG(n_frames > 0, "hm_strain_labels: %d frames (need at least 1)", n_frames);
+    HM_ARG(L >= 1, "hm_strain_labels: %d labels (need at least 1)", L);
+    const size_t n = (size_t)h->W * h->H;
+    if (labels) HM_TRY(hm_labels_ok("hm_strain_labels", 0, labels, n, L));
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_map_build(h));
+    StrainState &st = h->strain;
+    std::vector<int32_t> own;
+    if (!labels) {
+        if (h->body.L == 0) { hm_set_error("hm_strain_labels: no label image given, and hm_body_set_labels has set none"); return HM_ERR_STATE; }
+        HM_ARG(L == h->body.L, "hm_strain_labels: %d labels, the image of hm_body_set_labels has %d", L, h->body.L);
+        own.resize(n);
+        HM_HIP(hipMemcpyAsync(own.data(), h->body.lab, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        labels = own.data();
+    }
+    if (h->body.h_tri.empty()) {
+        h->body.h_tri.resize(n);
+        HM_HIP(hipMemcpyAsync(h->body.h_tri.data(), h->body.tri, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    HM_HIP(hipStreamSynchronize(h->stream));
+    // cnt[s, t] as compressed rows: the (label, triangle) pairs of the map's pixels sorted, runs of equal pairs counted
+    std::vector<uint64_t> key;
+    for (size_t p = 0; p < n; p++)
+        if (h->body.h_tri[p] >= 0 && labels[p] >= 0) key.push_back((uint64_t)labels[p] * h->T + h->body.h_tri[p]);
+    std::sort(key.begin(), key.end());
+    std::vector<int> off(L + 1, 0), ent_t;
+    std::vector<unsigned> ent_c, n_s(L, 0u);
+    for (size_t i = 0; i < key.size();) {
+        size_t j = i;
+        while (j < key.size() && key[j] == key[i]) j++;
+        const int s = (int)(key[i] / h->T);
+        ent_t.push_back((int)(key[i] % h->T));
+        ent_c.push_back((unsigned)(j - i));
+        off[s + 1]++;
+        n_s[s] += (unsigned)(j - i);
+        i = j;
+    }
+    for (int s = 0; s < L; s++) off[s + 1] += off[s];
+    const size_t ne = ent_t.size(), no = (size_t)n_frames * L * 3;
+    // (waits for the stream above: nothing in flight reads what grows here)
+    HM_HIP(h->own.grow(&st.off, (size_t)(L + 1) * sizeof(int)));
+    HM_HIP(h->own.grow(&st.n_s, (size_t)L * sizeof(unsigned)));
+    HM_HIP(h->own.grow(&st.ent_t, (ne + 1) * sizeof(int)));
+    HM_HIP(h->own.grow(&st.ent_c, (ne + 1) * sizeof(unsigned)));
+    HM_HIP(h->own.grow(&st.trace, no * sizeof(double)));
+    HM_HIP(hipMemcpyAsync(st.off, off.data(), (size_t)(L + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(st.n_s, n_s.data(), (size_t)L * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    if (ne) {
+        HM_HIP(hipMemcpyAsync(st.ent_t, ent_t.data(), ne * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HM_HIP(hipMemcpyAsync(st.ent_c, ent_c.data(), ne * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    }
+    HM_TRY(strain_queue_tri(h, n_frames, X));
+    const long long total = (long long)n_frames * L;
+    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, STRAIN_MAX_GRID);
+    hipLaunchKernelGGL(k_strain_label, dim3(grid), dim3(256), 0, h->stream, total, L, h->T, (const int *)st.off,
+                       (const int *)st.ent_t, (const unsigned *)st.ent_c, (const unsigned *)st.n_s, (const double *)st.v, st.trace);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipMemcpyAsync(out, st.trace, no * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));      // (the host vectors above are read until here)
+    if (counts) memcpy(counts, n_s.data(), (size_t)L * sizeof(uint32_t));
+    return HM_OK;
+}
+
+// Queue the strain view of frame d_frame (device) at state X (host) into d_out (device, W*H*3) on the handle's stream.
+static int view_strain_queue(hm_ctx *h, const double *X, const uint8_t *d_frame, int which, double gain, int alpha,
+                             const uint8_t *lut, int flags, uint8_t *d_out, const char *who)
+{
+    ViewState &v = h->view;
+    HM_ARG(X && d_frame && d_out, "%s: NULL state, frame or output", who);
+    HM_ARG(lut != nullptr, "%s: NULL lut (256 x 3 bytes, B G R)", who);
+    HM_ARG(which >= 0 && which <= 2, "%s: which %d outside 0..2 (J, l1, l2)", who, which);
+    HM_ARG(alpha >= 0 && alpha <= 255, "%s: alpha %d outside 0..255", who, alpha);
+    HM_ARG(flags == 0 || flags == CV_WIRE, "%s: flags %d (0, or %d: the wireframe)", who, flags, CV_WIRE);
+    HM_ARG(((uintptr_t)d_out & 3) == 0, "%s: the output is not 4-byte aligned", who);
+    HM_TRY(body_map_build(h));                        // (the first call on a handle waits for the map)
+    const int n = h->W * h->H;
+    const bool wire = (flags & CV_WIRE) != 0;
+    // the frame's block: X | lut
+    const size_t oL = (size_t)2 * h->N * sizeof(double), bytes = oL + 768;
+    HM_HIP(h->own.event(&v.ev));
+    if (wire) HM_HIP(h->own.alloc(&v.wire, (size_t)n * sizeof(unsigned)));
+    uint8_t *slot = nullptr;
+    HM_TRY(view_stage(h, bytes, &slot));
+    memcpy(slot, X, oL);
+    memcpy(slot + oL, lut, 768);
+    HM_TRY(view_stage_send(h, bytes));
+    const double *dX = (const double *)v.c_in;
+    if (wire) {
+        HM_HIP(hipMemsetAsync(v.wire, 0, (size_t)n * sizeof(unsigned), h->stream));
+        hipLaunchKernelGGL(k_view_wire, dim3(hm_cdiv(3 * h->T, 256 / VIEW_SEG_WAVE)), dim3(256), 0, h->stream,
+                           (const int *)h->d_tri, h->T, dX, h->W, h->H, v.wire);
+    }
+    StrainViewArgs a;
+    a.W = h->W; a.H = h->H; a.T = h->T; a.which = which; a.alpha = alpha; a.flags = flags;
+    a.tiles_x = hm_cdiv(h->W, CV_W);
+    a.gain = gain;
+    a.tri = h->d_tri; a.tidx = h->body.tidx; a.uv = h->d_uv; a.X = dX; a.frame = d_frame;
+    a.lut = v.c_in + oL; a.wire = v.wire; a.out = d_out;
+    hipLaunchKernelGGL(k_view_strain, dim3(a.tiles_x * hm_cdiv(h->H, CV_H)), dim3(256), 0, h->stream, a);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_view_strain(hm_ctx_t h, const double *X, const uint8_t *frame, int which, double gain, int alpha,
+                              const uint8_t *lut, int flags, uint8_t *bgr)
+{
+    HM_ARG(h && frame && bgr, "hm_view_strain: NULL argument");
+    HM_JOIN_LAZY(h);
+    HM_HIP(hipSetDevice(h->device));
+    const size_t n = (size_t)h->W * h->H;
+    HM_HIP(h->own.alloc(&h->view.c_frame, n));
+    HM_HIP(h->own.alloc(&h->view.out, 3 * n));
+    HM_HIP(hipMemcpyAsync(h->view.c_frame, frame, n, hipMemcpyHostToDevice, h->stream));
+    const int rc = view_strain_queue(h, X, h->view.c_frame, which, gain, alpha, lut, flags, h->view.out, "hm_view_strain");
+    if (rc) return rc;
+    return view_download(h, bgr);
+}
+
+extern "C" int hm_view_strain_dev(hm_ctx_t h, const double *X, const void *d_frame, int which, double gain, int alpha,
+                                  const uint8_t *lut, int flags, void *d_bgr, void *stream)
+{
+    HM_ARG(h != nullptr, "hm_view_strain_dev: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_HIP(hipSetDevice(h->device));
+    const int rc = view_strain_queue(h, X, (const uint8_t *)d_frame, which, gain, alpha, lut, flags, (uint8_t *)d_bgr,
+                                     "hm_view_strain_dev");
+    if (rc) return rc;
+    if (stream) {
+        HM_HIP(hipEventRecord(h->view.ev, h->stream));
+        HM_HIP(hipStreamWaitEvent((hipStream_t)stream, h->view.ev, 0));
     }
     return HM_OK;
 }

@@ -238,25 +238,62 @@ struct CellShared {
 // a vertex the snap may take: finite and within the range d_tri_sane accepts (anything beyond fails that test anyway)
 __device__ __forceinline__ bool d_cv_vertex_ok(double x, double y) { return fabs(x) <= 16777216.0 && fabs(y) <= 16777216.0; }
 
+// The two ends of a strip's workgroup, shared with k_view_strain (strain_kernels.h); all 256 threads call them.
+// The candidates of the strip at (c0, r0) into the bit set `mask` (LDS, cleared here): every thread tests its share of the
+// triangles' boxes at X; a triangle with a vertex the snap may not take is no candidate.
+__device__ __forceinline__ void d_cv_candidates(unsigned *mask, int T, const int *__restrict__ tri, const double *__restrict__ X,
+                                                int W, int H, int c0, int r0)
+{
+    const int tid = threadIdx.x;
+    const int words = (T + 31) / 32;
+    for (int i = tid; i < words; i += 256) mask[i] = 0;
+    __syncthreads();
+    for (int t = tid; t < T; t += 256) {
+        const int v0 = tri[3 * t], v1 = tri[3 * t + 1], v2 = tri[3 * t + 2];
+        const double x0 = X[2 * v0], y0 = X[2 * v0 + 1], x1 = X[2 * v1], y1 = X[2 * v1 + 1], x2 = X[2 * v2], y2 = X[2 * v2 + 1];
+        if (!(d_cv_vertex_ok(x0, y0) && d_cv_vertex_ok(x1, y1) && d_cv_vertex_ok(x2, y2))) continue;
+        int cmin, cmax, rmin, rmax;
+        d_tri_bbox(d_snap(x0), d_snap(y0), d_snap(x1), d_snap(y1), d_snap(x2), d_snap(y2), W, H, cmin, cmax, rmin, rmax);
+        if (cmin <= cmax && cmax >= c0 && cmin < c0 + CV_W && rmax >= r0 && rmin < r0 + CV_H)
+            atomicOr(&mask[t >> 5], 1u << (t & 31));
+    }
+    __syncthreads();
+}
+
+// The strip's colours px (LDS, B | G << 8 | R << 16; a barrier since they were written) into out: the strip's bytes of row r
+// are [3 (r W + c0), + 3 wv); whole dwords inside them as dwords, the ends byte by byte.
+__device__ __forceinline__ void d_cv_store(const unsigned (&px)[CV_H][CV_W], int W, int H, int c0, int r0, uint8_t *__restrict__ out)
+{
+    const int wv = min(CV_W, W - c0), hv = min(CV_H, H - r0), nb = 3 * wv;
+    for (int i = threadIdx.x; i < hv * CV_ROW_WORDS; i += 256) {
+        const int rr = i / CV_ROW_WORDS, k = i - rr * CV_ROW_WORDS;
+        const size_t b0 = 3 * ((size_t)(r0 + rr) * W + c0);
+        const size_t start = ((b0 >> 2) + k) << 2;
+        if (start >= b0 + nb) continue;
+        unsigned v = 0, in = 0;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const long long rel = (long long)(start + q) - (long long)b0;
+            if (rel < 0 || rel >= nb) continue;
+            const int pi = (int)rel / 3, cq = (int)rel - 3 * pi;
+            v |= ((px[rr][pi] >> (8 * cq)) & 255u) << (8 * q);
+            in |= 1u << q;
+        }
+        if (in == 15u) *(unsigned *)(out + start) = v;
+        else
+            for (int q = 0; q < 4; q++)
+                if ((in >> q) & 1u) out[start + q] = (uint8_t)(v >> (8 * q));
+    }
+}
+
 __global__ __launch_bounds__(256) void k_view_cells(CellViewArgs a)
 {
     __shared__ CellShared sh;
     const int tid = threadIdx.x;
     const int words = (a.T + 31) / 32;
-    for (int i = tid; i < words; i += 256) sh.mask[i] = 0;
-    __syncthreads();
     const int c0 = ((int)blockIdx.x % a.tiles_x) * CV_W, r0 = ((int)blockIdx.x / a.tiles_x) * CV_H;
     const double *__restrict__ X = a.X;
-    for (int t = tid; t < a.T; t += 256) {
-        const int v0 = a.tri[3 * t], v1 = a.tri[3 * t + 1], v2 = a.tri[3 * t + 2];
-        const double x0 = X[2 * v0], y0 = X[2 * v0 + 1], x1 = X[2 * v1], y1 = X[2 * v1 + 1], x2 = X[2 * v2], y2 = X[2 * v2 + 1];
-        if (!(d_cv_vertex_ok(x0, y0) && d_cv_vertex_ok(x1, y1) && d_cv_vertex_ok(x2, y2))) continue;
-        int cmin, cmax, rmin, rmax;
-        d_tri_bbox(d_snap(x0), d_snap(y0), d_snap(x1), d_snap(y1), d_snap(x2), d_snap(y2), a.W, a.H, cmin, cmax, rmin, rmax);
-        if (cmin <= cmax && cmax >= c0 && cmin < c0 + CV_W && rmax >= r0 && rmin < r0 + CV_H)
-            atomicOr(&sh.mask[t >> 5], 1u << (t & 31));
-    }
-    __syncthreads();
+    d_cv_candidates(sh.mask, a.T, a.tri, X, a.W, a.H, c0, r0);
     int total = 0;
     for (int w = 0; w < words; w++) total += __popc(sh.mask[w]);
     const int c = c0 + (tid & 63), rb = r0 + (tid >> 6);
@@ -342,27 +379,7 @@ __global__ __launch_bounds__(256) void k_view_cells(CellViewArgs a)
         sh.px[r - r0][c - c0] = b | ((unsigned)ch[1] << 8) | ((unsigned)ch[2] << 16);
     }
     __syncthreads();
-    // the strip's bytes of row r: [3 (r W + c0), + 3 wv); whole dwords inside them as dwords, the ends byte by byte
-    const int wv = min(CV_W, a.W - c0), hv = min(CV_H, a.H - r0), nb = 3 * wv;
-    for (int i = tid; i < hv * CV_ROW_WORDS; i += 256) {
-        const int rr = i / CV_ROW_WORDS, k = i - rr * CV_ROW_WORDS;
-        const size_t b0 = 3 * ((size_t)(r0 + rr) * a.W + c0);
-        const size_t start = ((b0 >> 2) + k) << 2;
-        if (start >= b0 + nb) continue;
-        unsigned v = 0, in = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const long long rel = (long long)(start + q) - (long long)b0;
-            if (rel < 0 || rel >= nb) continue;
-            const int pi = (int)rel / 3, cq = (int)rel - 3 * pi;
-            v |= ((sh.px[rr][pi] >> (8 * cq)) & 255u) << (8 * q);
-            in |= 1u << q;
-        }
-        if (in == 15u) *(unsigned *)(a.out + start) = v;
-        else
-            for (int q = 0; q < 4; q++)
-                if ((in >> q) & 1u) a.out[start + q] = (uint8_t)(v >> (8 * q));
-    }
+    d_cv_store(sh.px, a.W, a.H, c0, r0, a.out);
 }
 
 // The outline plane of layer 0, once per hm_view_set_cells: a body pixel with label s >= 0 is an outline pixel when one

@@ -297,6 +297,66 @@ class Renderer:
         """hm_body_fence: `stream` waits on the device for the last warp queued."""
         _lib.check(_lib.lib().hm_body_fence(self._h, stream), "hm_body_fence")
 
+    # -- the deformation readout (hm_strain_*, hm_view_strain*; hydra_mi.strain) ------------------------------
+    STRAIN_WHICH = {"J": 0, "l1": 1, "l2": 2}
+
+    def _states(self, states):
+        """-> `states` as a contiguous (frames, 4N) float64 array (one state: one row)"""
+        x = np.ascontiguousarray(states, np.float64)
+        x = x.reshape(1, -1) if x.ndim == 1 else x.reshape(x.shape[0], -1)
+        if x.shape[1] != 4 * self.n:
+            raise ValueError("states of %d entries for a mesh of %d vertices" % (x.shape[1], self.n))
+        return x
+
+    def strain_tri(self, states):
+        """hm_strain_tri: states (frames, 4N) -> (frames, T, 7) float64: J, l1, l2, c2, s2, rc, rs per frame and triangle."""
+        x = self._states(states)
+        out = np.empty((x.shape[0], self.tri.shape[0], 7), np.float64)
+        _lib.check(_lib.lib().hm_strain_tri(self._h, int(x.shape[0]), _lib.ptr(x), _lib.ptr(out)), "hm_strain_tri")
+        return out
+
+    def strain_labels(self, states, labels, L):
+        """hm_strain_labels: the mean J, l1, l2 over the body-map pixels of every label -> ((frames, L, 3) float64, map
+        pixels per label (L,) uint32).  labels: (H, W) int32 in body coordinates, -1: none; None: the label image in
+        place (body_set_labels), whose L is passed."""
+        x = self._states(states)
+        lab = None if labels is None else self._plane(labels, np.int32, "label image")
+        out = np.empty((x.shape[0], max(int(L), 0), 3), np.float64)
+        cnt = np.empty(max(int(L), 0), np.uint32)
+        _lib.check(_lib.lib().hm_strain_labels(self._h, int(x.shape[0]), _lib.ptr(x), _lib.ptr(lab), int(L), _lib.ptr(out),
+                                               _lib.ptr(cnt)), "hm_strain_labels")
+        return out, cnt
+
+    def _view_strain_args(self, X, which, lut, wire):
+        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+        if x.shape[0] < 2 * self.n:
+            raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
+        t = None
+        if lut is not None:
+            t = np.ascontiguousarray(lut, np.uint8)
+            if t.shape != (256, 3):
+                raise ValueError("a colour table of shape %r (256 x 3, B G R)" % (t.shape,))
+        return x, self.STRAIN_WHICH.get(which, which), t, 2 if wire else 0
+
+    def view_strain(self, X, frame, which="J", gain=256.0, alpha=128, lut=None, wire=False):
+        """hm_view_strain: J, l1 or l2 of the triangle under every pixel painted onto the gray frame (H, W) uint8 at state X
+        -> (H, W, 3) uint8, B G R: level = clamp(128 + rint(gain (value - 1)), 0, 255), colour lut[level] (256 x 3, B G R),
+        blended at alpha / 255."""
+        x, w, t, flags = self._view_strain_args(X, which, lut, wire)
+        f = self._plane(frame, np.uint8, "frame")
+        out = np.empty((self.ny, self.nx, 3), np.uint8)
+        _lib.check(_lib.lib().hm_view_strain(self._h, _lib.ptr(x), _lib.ptr(f), int(w), float(gain), int(alpha), _lib.ptr(t),
+                                             flags, _lib.ptr(out)), "hm_view_strain")
+        return out
+
+    def view_strain_dev(self, X, d_frame, d_out, which="J", gain=256.0, alpha=128, lut=None, wire=False, stream=None):
+        """hm_view_strain_dev: the same queued on the handle's stream, frame (W*H bytes) and output (W*H*3 bytes) device
+        addresses; it does not wait, and X and the table may be overwritten at once; `stream` waits for it on the device."""
+        x, w, t, flags = self._view_strain_args(X, which, lut, wire)
+        _lib.check(_lib.lib().hm_view_strain_dev(self._h, _lib.ptr(x), ctypes.c_void_p(int(d_frame)), int(w), float(gain),
+                                                 int(alpha), _lib.ptr(t), flags, ctypes.c_void_p(int(d_out)), stream),
+                   "hm_view_strain_dev")
+
     # -- statistics of the registered video (hm_body_stats_*; hydra_mi.body.BodyReadout(stats=True)) -------
     SCORES = {"corr": 0, "std": 1, "range": 2}
 

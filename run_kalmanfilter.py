@@ -93,6 +93,19 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      Needs one of --points, --find-points, --rois, --demix.  Drawn at the smoothed states Xs with
                      --smooth, else at the filtered ones (--cells-video-states filtered|smoothed overrides).  One more
                      pass over the frames of the input video.
+    --strain         the deformation of the tracked mesh (hydra_mi.strain): the states file gets strain_J (the area ratio of
+                     every triangle against the body frame), strain_l1, strain_l2 (its principal stretches), strain_axis (the
+                     direction of l1 in the body frame, radians), strain_rotation (frames x triangles) and strain_body_area
+                     (frames: the area of the whole mesh over its rest area) -- of the smoothed states Xs with --smooth, else
+                     of the filtered ones.  With cells (--points, --find-points, --rois, --demix) also strain_cell_J,
+                     strain_cell_l1, strain_cell_l2 (frames x cells): their mean over the pixels of every cell, the ROI
+                     with --rois, else the disc of --point-radius; and with dF/F traces (--rois, --demix) strain_artifact_r
+                     (cells): Pearson's r between a cell's local area ratio and its dF/F -- compressed tissue is brighter,
+                     so a cell whose trace follows its tissue's area change is suspect.  A diagnostic, not a correction.
+    --strain-video OUT.avi   after tracking: every raw frame with --strain-which (J, l1 or l2; default J) of the triangle under
+                     each pixel painted on, blue compressed, white unchanged, red stretched: level 128 + --strain-gain
+                     (value - 1) (default 256) of a 256-colour table, blended at --strain-alpha / 255 (default 128).  At the
+                     states --strain uses.  One more pass over the frames of the input video.
 """
 import argparse
 import os
@@ -108,6 +121,7 @@ from hydra_mi import residual
 from hydra_mi import detrend
 from hydra_mi import roi
 from hydra_mi import stabilize
+from hydra_mi import strain
 from hydra_mi.body import (BodyReadout, read_out, read_out_recorded, read_points_csv, record_bytes, write_points_csv,
                            write_points_txt)
 from hydra_mi.distmesh_dyn import DistMesh
@@ -179,7 +193,14 @@ def main(argv=None):
                              "of --points, --find-points, --rois, --demix; one more pass over the frames of the input video")
     parser.add_argument("--cells-video-states", default=None, choices=("filtered", "smoothed"),
                         help="the states the cells video is drawn at (default: smoothed with --smooth, else filtered)")
+    parser.add_argument("--strain", action="store_true", help="the deformation of every triangle, and of the tissue under every cell (strain_* arrays)")
+    parser.add_argument("--strain-video", default=None, metavar="OUT.avi", help="after tracking, write the strain painted onto the video (.avi)")
+    parser.add_argument("--strain-which", default="J", choices=strain.WHICH, help="what the strain video shows: area ratio or a principal stretch")
+    parser.add_argument("--strain-gain", default=strain.DEFAULT_GAIN, type=float, help="colour levels per unit of (value - 1)")
+    parser.add_argument("--strain-alpha", default=strain.DEFAULT_ALPHA, type=int, help="weight of the colour over the frame (0..255)")
     args = parser.parse_args(argv)
+    if not 0 <= args.strain_alpha <= 255 or not np.isfinite(args.strain_gain):
+        parser.error("the strain video needs a --strain-alpha in 0..255 and a finite --strain-gain")
     if args.cells_video is not None and args.points is None and args.find_points is None:
         parser.error("--cells-video draws cells or points: it needs one of --points, --find-points, --rois, --demix")
     if args.cells_video_states is not None and args.cells_video is None:
@@ -319,6 +340,7 @@ def main(argv=None):
         print("Overlay video: %d frames in %s" % (video.frames, args.fn_out))
     extra = {}
     cv_cells = cv_levels = cv_points = None          # what --cells-video draws
+    st_cells = st_dff = None                         # what --strain reads the tissue under: (labels or points), their dF/F
     more = None                                      # what --find-more found
     if body is not None:
         res = body.results()
@@ -394,6 +416,8 @@ def main(argv=None):
         kf.state.renderer.body_stats_end()
     if args.cells_video is not None:
         cv_points = found if find else points
+    if args.strain and (find or points is not None):
+        st_cells = {"points": found if find else points, "point_radius": args.point_radius}
     if body is not None and body.keep:
         if args.dff_video is not None and len(states):
             n_dff = detrend.write_video(body, args.dff_video, args.detrend_half, args.detrend_q, args.dff_floor, args.dff_gain)
@@ -420,6 +444,8 @@ def main(argv=None):
                          roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
             print("ROIs: %d cells, %d..%d pixels, %d kept their disc" % (len(inside), e["roi_counts"].min(),
                                                                           e["roi_counts"].max(), e["seed_fallback"].sum()))
+            if args.strain:                                        # (cell s: point inside[s], as the roi_* rows)
+                st_cells, st_dff = {"labels": e["roi_labels"], "L": len(inside)}, e["dff_demixed"] if args.demix else e["dff"]
             if args.cells_video is not None:
                 if args.demix:
                     lab, w, dropped = cellview.layers_from_shapes(e["shapes_q"], roi.seeds_of(pts[inside]),
@@ -452,6 +478,23 @@ def main(argv=None):
         n_cv = cellview.write_video(kf, cv_states, capture.frames[1:1 + len(states)], args.cells_video, cells=cv_cells,
                                     levels=cv_levels, points=cv_points)       # state k: frame k + 1
         print("Cells video: %d frames (%s states) in %s" % (n_cv, use, args.cells_video))
+    if (args.strain or args.strain_video is not None) and len(states):
+        st_states = extra["Xs"] if args.smooth else np.array(states)
+        if args.strain:
+            d = strain.triangles(kf, st_states)
+            extra.update(strain_J=d["J"], strain_l1=d["l1"], strain_l2=d["l2"], strain_axis=d["axis"],
+                         strain_rotation=d["rotation"], strain_body_area=d["body_area"])
+            print("Strain: %d triangles, body area %.4f .. %.4f of the rest area" % (d["J"].shape[1], np.nanmin(d["body_area"]),
+                                                                                      np.nanmax(d["body_area"])))
+            if st_cells is not None and (len(st_cells["points"]) if "points" in st_cells else st_cells["L"]):
+                c = strain.labels(kf, st_states, **st_cells)
+                extra.update(strain_cell_J=c["J"], strain_cell_l1=c["l1"], strain_cell_l2=c["l2"])
+                if st_dff is not None:
+                    extra.update(strain_artifact_r=strain.artifact_score(c["J"], st_dff))
+        if args.strain_video is not None:
+            n_sv = strain.write_video(kf, st_states, capture.frames[1:1 + len(states)], args.strain_video,
+                                      which=args.strain_which, gain=args.strain_gain, alpha=args.strain_alpha)     # state k: frame k + 1
+            print("Strain video: %d frames (%s) in %s" % (n_sv, args.strain_which, args.strain_video))
     np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri, **extra)
     print("Finished: %d frames, states in %s" % (len(states), args.fn_out))
     return 0
