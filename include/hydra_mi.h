@@ -647,7 +647,19 @@ int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int
  *                  repeats every iteration (hydra_mi/demix.py).  Exact while
  *                  F x 255 x 2^31 < 2^63, HM_ERR_ARG with the numbers beyond that and for a seed that is no pixel
  *                  of the map.  The frames are split over the grid in runs of hm_ctx_tune "rec_tp_frames" (1..1024,
- *                  default 32) and the partial sums meet in 64-bit integer atomics: the same result in any order. */
+ *                  default 32) and the partial sums meet in 64-bit integer atomics: the same result in any order.
+ *   trace_maps     L whole-number traces over all F recorded frames, q[k * L + s] (frame-major as in trace_products),
+ *                  |q| <= 32767 and L is 1..1024 -> every trace against every pixel of the record (hydra_mi/network.py,
+ *                  DESIGN.md section 17):
+ *                    c[s * W*H + p] = sum_k v_k(p) q[k * L + s] (int64),
+ *                    w1[p] = sum_k v_k(p),  w2[p] = sum_k v_k(p)^2 (uint64);
+ *                  full W*H planes as fetch gives them: 0 outside the box and outside the map.  Any output may be NULL.
+ *                  HM_ERR_ARG with the numbers for L out of range, for a |q| > 32767 (the first offender's frame and
+ *                  trace are named) and when F x F x 255 x 32767 >= 2^63: below that every sum and the host's
+ *                  F c - w1 u1 (u1 = sum_k q) are exact in 64 bits.  The traces are taken in groups of 8 and the frames
+ *                  are split over the grid in runs of hm_ctx_tune "rec_map_frames" (1..256, default 64); the partial
+ *                  sums of a run are 32-bit and meet in 64-bit integer atomics: the same result in any order and for
+ *                  every value of the key. */
 int hm_body_rec_begin(hm_ctx_t h, uint64_t max_bytes);
 int hm_body_rec_end(hm_ctx_t h);
 int hm_body_rec_count(hm_ctx_t h, int *frames);
@@ -658,6 +670,7 @@ int hm_body_rec_seed_sums(hm_ctx_t h, int P, const int32_t *seeds, double r_disc
                           uint64_t *w2, int64_t *c, int64_t *u1, int64_t *u2);
 int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds, int R, const uint16_t *weights, uint64_t *out);
 int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seeds, int R, const int32_t *q, int64_t *out);
+int hm_body_rec_trace_maps(hm_ctx_t h, int L, const int32_t *q, int64_t *c, uint64_t *w1, uint64_t *w2);
 
 /* Residual motion of the kept registered video: the shift of every patch of every frame found against a template
  * and taken out of the record in place (hydra_mi/stabilize.py).  Waiting, errors and state are

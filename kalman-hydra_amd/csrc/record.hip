@@ -1,6 +1,7 @@
 // The registered video kept on the device (hm_body_rec_*): the record itself, the reductions over it, its residual motion
 // (match, shift, field, warp), the running baseline and the residual of the cells' model.  Host orchestration and C-ABI
-// (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h and residual_kernels.h, which
+// (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h, residual_kernels.h and
+// network_kernels.h, which
 // this translation unit alone compiles.  Of the handle (ctx.h) it uses rec, the body map (body.tri, body.h_tri), the
 // registered plane (body.reg) and the statistics' counters, and reads W, H, device, own and stream.  readout.hip queues the
 // warp: it reserves a frame's slot and queues the copy into it through body_rec_slot and body_rec_queue_copy, and this file
@@ -10,6 +11,7 @@
 #include "stab_kernels.h"
 #include "detrend_kernels.h"
 #include "residual_kernels.h"
+#include "network_kernels.h"
 #include <algorithm>
 #include <cstring>
 
@@ -457,6 +459,66 @@ extern "C" int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seed
     HM_HIP(hipGetLastError());
     HM_HIP(hipMemcpyAsync(out, g.out, P * nw * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HM_HIP(hipStreamSynchronize(h->stream));
+    return HM_OK;
+}
+
+// ---- every trace against every pixel of the record (network_kernels.h) ------------------------------------------------
+// planes of the box on the device (rows of b.pitch values of 8 bytes) -> full W x H planes of the caller's, 0 outside the box
+static int rec_expand64(const hm_ctx *h, const unsigned long long *d_src, int planes, void *out)
+{
+    const RecBox &b = h->rec.box;
+    const size_t n = (size_t)h->W * h->H, nb = (size_t)b.pitch * b.bh;
+    memset(out, 0, (size_t)planes * n * 8);
+    for (int s = 0; s < planes; s++)
+        HM_HIP(hipMemcpy2D((uint64_t *)out + (size_t)s * n + (size_t)b.r0 * h->W + b.c0, (size_t)h->W * 8, d_src + (size_t)s * nb,
+                           (size_t)b.pitch * 8, (size_t)b.bw * 8, (size_t)b.bh, hipMemcpyDeviceToHost));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_trace_maps(hm_ctx_t h, int L, const int32_t *q, int64_t *c, uint64_t *w1, uint64_t *w2)
+{
+    HM_ARG(L >= 1 && L <= REC_MAP_LMAX, "hm_body_rec_trace_maps: %d traces outside 1..%d", L, REC_MAP_LMAX);
+    HM_ARG(h && q, "hm_body_rec_trace_maps: NULL handle or traces");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_trace_maps"));
+    const int F = h->rec.frames;
+    // |F c| and |w1 u1| <= F^2 x 255 x 32767
+    HM_ARG((unsigned __int128)F * F * 255u * (unsigned)REC_MAP_QMAX < ((unsigned __int128)1 << 63),
+           "hm_body_rec_trace_maps: F x F x 255 x 32767 = %d x %d x 255 x 32767 could pass 2^63", F, F);
+    const size_t fl = (size_t)F * L;
+    for (size_t i = 0; i < fl; i++)
+        HM_ARG(q[i] >= -REC_MAP_QMAX && q[i] <= REC_MAP_QMAX, "hm_body_rec_trace_maps: q %d (frame %zu, trace %zu) outside -%d..%d",
+               (int)q[i], i / (size_t)L, i % (size_t)L, REC_MAP_QMAX, REC_MAP_QMAX);
+    if (!(c || w1 || w2)) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const RecBox &b = h->rec.box;
+    const size_t nb = (size_t)b.pitch * b.bh;
+    const int groups = c ? hm_cdiv(L, REC_MAP_GROUP) : 1, runs = hm_cdiv(F, h->rec.map_frames);
+    RecMaps g;
+    int *d_q = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_q = cv.take<int>(c ? fl : 0);
+        g.c = c ? cv.take<unsigned long long>((size_t)L * nb) : nullptr;
+        g.w1 = w1 || w2 ? cv.take<unsigned long long>(nb) : nullptr;
+        g.w2 = w1 || w2 ? cv.take<unsigned long long>(nb) : nullptr;
+    }));
+    if (c) {
+        HM_HIP(hipMemcpyAsync(d_q, q, fl * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HM_HIP(hipMemsetAsync(g.c, 0, (size_t)L * nb * 8, h->stream));
+    }
+    if (g.w1) {
+        HM_HIP(hipMemsetAsync(g.w1, 0, nb * 8, h->stream));
+        HM_HIP(hipMemsetAsync(g.w2, 0, nb * 8, h->stream));
+    }
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.F = F; g.L = L; g.run = h->rec.map_frames; g.q = d_q;
+    hipLaunchKernelGGL(k_rec_trace_maps, dim3(hm_cdiv((int)(nb >> 2), 256), std::min(runs, 65535), groups), dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipStreamSynchronize(h->stream));
+    if (c) HM_TRY(rec_expand64(h, g.c, L, c));
+    if (w1) HM_TRY(rec_expand64(h, g.w1, 1, w1));
+    if (w2) HM_TRY(rec_expand64(h, g.w2, 1, w2));
     return HM_OK;
 }
 

@@ -479,6 +479,27 @@ class Renderer:
                    "hm_body_rec_trace_products")
         return out
 
+    def body_rec_trace_maps(self, q, want=("c", "w1", "w2")):
+        """hm_body_rec_trace_maps: L int32 traces, q (F, L) with |q| <= 32767 -> dict of those in `want`: c (L, H, W) int64,
+        the sum over the recorded frames of every pixel times every trace; w1, w2 (H, W) uint64, the sums of every pixel
+        and of its square (0 outside the map)."""
+        F = self.body_rec_count()
+        q = np.asarray(q)
+        if q.dtype != np.int32 or q.ndim != 2 or (F and q.shape[0] != F):          # (F 0: the call says why)
+            raise ValueError("traces %s of shape %r for %d frames (need int32, frames x traces)" % (q.dtype, q.shape, F))
+        q = np.ascontiguousarray(q)
+        L, H, W = q.shape[1], self.ny, self.nx
+        o = {}
+        if "c" in want:
+            o["c"] = np.empty((min(max(L, 0), 1024), H, W), np.int64)               # (L out of range: the call says so)
+        for key in ("w1", "w2"):
+            if key in want:
+                o[key] = np.empty((H, W), np.uint64)
+        _lib.check(_lib.lib().hm_body_rec_trace_maps(self._h, L, _lib.ptr(q), *[_lib.ptr(o[k]) if k in o else None
+                                                                                 for k in ("c", "w1", "w2")]),
+                   "hm_body_rec_trace_maps")
+        return o
+
     # -- residual motion of the record (hm_body_rec_match / _frame_sums / _shift / _warp / _field_sums; hydra_mi.stabilize) --
     def body_rec_patches(self, B):
         """-> (patches per row, patch rows) of the grid of B x B patches over the record's box (the bounding box of the

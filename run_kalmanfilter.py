@@ -106,6 +106,17 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      each pixel painted on, blue compressed, white unchanged, red stretched: level 128 + --strain-gain
                      (value - 1) (default 256) of a 256-colour table, blended at --strain-alpha / 255 (default 128).  At the
                      states --strain uses.  One more pass over the frames of the input video.
+    --network        with --rois or --demix: the cells that fire together (hydra_mi.network), from the dF/F of --demix if on,
+                     else of --rois, as it is.  net_r (cells x cells x 2 LAG + 1): Pearson's r of every pair of traces at
+                     the lags -LAG..LAG (--network-lag, default 10); net_labels (cells): the ensemble of every cell, the
+                     connected components of r at lag 0 >= --network-thr, -1 for a cell alone; net_ens_traces (ensembles x
+                     frames): their mean dF/F; net_lead_lag, net_lead_r (ensembles x ensembles): the lag at which the
+                     second follows the first best, and that r; net_rho (ensembles x H x W): the correlation of every pixel
+                     of the kept registered video with every ensemble's trace, made on the device and rounded to float32
+                     here; net_map (H x W, int16): per pixel the ensemble with the largest rho if that is >=
+                     --network-map-thr, else -1; with --strain also net_strain_r (ensembles x triangles): Pearson's r
+                     between an ensemble's trace and a triangle's area ratio.
+    --network-map OUT.png   with --network: net_map in the ensembles' colours over the mean registered frame.
 """
 import argparse
 import os
@@ -116,6 +127,7 @@ import numpy as np
 import hydra_mi  # noqa: F401
 from hydra_mi import cellview
 from hydra_mi import kalman
+from hydra_mi import network
 from hydra_mi import demix
 from hydra_mi import residual
 from hydra_mi import detrend
@@ -198,6 +210,12 @@ def main(argv=None):
     parser.add_argument("--strain-which", default="J", choices=strain.WHICH, help="what the strain video shows: area ratio or a principal stretch")
     parser.add_argument("--strain-gain", default=strain.DEFAULT_GAIN, type=float, help="colour levels per unit of (value - 1)")
     parser.add_argument("--strain-alpha", default=strain.DEFAULT_ALPHA, type=int, help="weight of the colour over the frame (0..255)")
+    parser.add_argument("--network", action="store_true", help="with --rois or --demix: ensembles of co-active cells, their lags and maps (net_* arrays)")
+    parser.add_argument("--network-thr", default=None, type=float, help="the least r at lag 0 that joins two cells (default %g)" % network.DEFAULT_THR)
+    parser.add_argument("--network-lag", default=network.DEFAULT_LAG, type=int, help="the lags looked at: +-N frames")
+    parser.add_argument("--network-map-thr", default=None, type=float,
+                        help="the least rho that gives a pixel to an ensemble (default %g)" % network.DEFAULT_MAP_THR)
+    parser.add_argument("--network-map", default=None, metavar="OUT.png", help="with --network: write the ensemble map here (.png)")
     args = parser.parse_args(argv)
     if not 0 <= args.strain_alpha <= 255 or not np.isfinite(args.strain_gain):
         parser.error("the strain video needs a --strain-alpha in 0..255 and a finite --strain-gain")
@@ -230,6 +248,12 @@ def main(argv=None):
             parser.error("--demix-iters needs at least one round")
     if args.rois and args.find_points is None and args.points is None:
         parser.error("--rois reads cells out: it needs --find-points or --points")
+    if args.network and not args.rois:
+        parser.error("--network reads the cells' traces: it needs --rois or --demix")
+    if args.network_map is not None and not args.network:
+        parser.error("--network-map draws the ensembles: it needs --network")
+    if args.network and (args.network_lag < 0 or any(t is not None and not np.isfinite(t) for t in (args.network_thr, args.network_map_thr))):
+        parser.error("--network needs a --network-lag >= 0 and finite thresholds")
     if args.detrend and args.find_points is None:
         parser.error("--detrend finds the cells in the excess video: it needs --find-points")
     if args.resummarize and (not args.stabilize or args.detrend):
@@ -444,6 +468,17 @@ def main(argv=None):
                          roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
             print("ROIs: %d cells, %d..%d pixels, %d kept their disc" % (len(inside), e["roi_counts"].min(),
                                                                           e["roi_counts"].max(), e["seed_fallback"].sum()))
+            if args.network:                                       # (cell s: point inside[s], as the roi_* rows)
+                net = network.extract(body, (e["dff_demixed"] if args.demix else e["dff"]).T, thr=args.network_thr,
+                                      max_lag=args.network_lag, map_thr=args.network_map_thr)
+                extra.update(net_r=net["r"], net_labels=net["labels"], net_ens_traces=net["ens_traces"],
+                             net_lead_lag=net["lead_lag"], net_lead_r=net["lead_r"], net_rho=net["rho"].astype(np.float32),
+                             net_map=net["map"])
+                print("Network: %d ensembles of %d cells, %d cells alone, %d pixels mapped" % (
+                    net["ens_traces"].shape[0], (net["labels"] >= 0).sum(), (net["labels"] < 0).sum(), (net["map"] >= 0).sum()))
+                if args.network_map is not None:
+                    network.colour_map(net["map"], net["gray"], args.network_map)
+                    print("Ensemble map: %s" % args.network_map)
             if args.strain:                                        # (cell s: point inside[s], as the roi_* rows)
                 st_cells, st_dff = {"labels": e["roi_labels"], "L": len(inside)}, e["dff_demixed"] if args.demix else e["dff"]
             if args.cells_video is not None:
@@ -486,6 +521,8 @@ def main(argv=None):
                          strain_rotation=d["rotation"], strain_body_area=d["body_area"])
             print("Strain: %d triangles, body area %.4f .. %.4f of the rest area" % (d["J"].shape[1], np.nanmin(d["body_area"]),
                                                                                       np.nanmax(d["body_area"])))
+            if "net_ens_traces" in extra:
+                extra.update(net_strain_r=network.strain_coupling(extra["net_ens_traces"], d["J"]))
             if st_cells is not None and (len(st_cells["points"]) if "points" in st_cells else st_cells["L"]):
                 c = strain.labels(kf, st_states, **st_cells)
                 extra.update(strain_cell_J=c["J"], strain_cell_l1=c["l1"], strain_cell_l2=c["l2"])
