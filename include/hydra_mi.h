@@ -659,7 +659,26 @@ int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int
  *                  F c - w1 u1 (u1 = sum_k q) are exact in 64 bits.  The traces are taken in groups of 8 and the frames
  *                  are split over the grid in runs of hm_ctx_tune "rec_map_frames" (1..256, default 64); the partial
  *                  sums of a run are 32-bit and meet in 64-bit integer atomics: the same result in any order and for
- *                  every value of the key. */
+ *                  every value of the key.
+ *   trace_null     a trace and its surrogates against every pixel, reduced to what a significance test needs
+ *                  (hydra_mi/network.py map_null).  q as for trace_maps, L is 2..4096: column 0 is
+ *                  the observed trace, columns 1 .. L - 1 its surrogates, however they were made.  vb[s] is the host's
+ *                  F u2 - u1^2 of column s (u1 = sum_k q, u2 = sum_k q^2) rounded to binary64.  With c_s, w1, w2 as above:
+ *                    num_s(p) = F c_s(p) - w1(p) u1_s,  a(p) = F w2(p) - w1(p)^2 (int64, exact under trace_maps' bound),
+ *                    rho_s(p) = (double)num_s(p) / sqrt((double)a(p) * vb[s]): one conversion each, one product, one
+ *                               square root, one division; 0.0 where a(p) = 0 or vb[s] = 0;
+ *                    tmax[s], tmin[s] = the largest and smallest rho_s(p) over the pixels of the map (L doubles each;
+ *                               NaN for a map without a pixel),
+ *                    ge[p] = the number of s >= 1 with num_s(p) >= num_0(p), le[p] that with num_s(p) <= num_0(p)
+ *                               (uint32, full W*H planes, 0 outside the map; whole numbers compared, a tie counts in both;
+ *                               a constant pixel has L - 1 in both).
+ *                  Any output may be NULL.  HM_ERR_ARG with the numbers for L out of range, for a |q| > 32767 (the first
+ *                  offender's frame and trace are named), for a vb that is negative or not finite (its column is named)
+ *                  and when F x F x 255 x 32767 >= 2^63.  vb is a whole number's rounding: one strictly between 0 and 1
+ *                  may make a product that rounds to 0 and a rho that is not finite.  A workgroup walks all frames for
+ *                  its pixels and 8 columns in runs of hm_ctx_tune "rec_null_frames" (1..256, default 256), 32-bit sums
+ *                  widened in registers between runs: the same bytes for every value of the key.  The record is not
+ *                  changed, and a refusal leaves it usable. */
 int hm_body_rec_begin(hm_ctx_t h, uint64_t max_bytes);
 int hm_body_rec_end(hm_ctx_t h);
 int hm_body_rec_count(hm_ctx_t h, int *frames);
@@ -671,6 +690,8 @@ int hm_body_rec_seed_sums(hm_ctx_t h, int P, const int32_t *seeds, double r_disc
 int hm_body_rec_weighted_sums(hm_ctx_t h, int P, const int32_t *seeds, int R, const uint16_t *weights, uint64_t *out);
 int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seeds, int R, const int32_t *q, int64_t *out);
 int hm_body_rec_trace_maps(hm_ctx_t h, int L, const int32_t *q, int64_t *c, uint64_t *w1, uint64_t *w2);
+int hm_body_rec_trace_null(hm_ctx_t h, int L, const int32_t *q, const double *vb, double *tmax, double *tmin,
+                           uint32_t *ge, uint32_t *le);
 
 /* Residual motion of the kept registered video: the shift of every patch of every frame found against a template
  * and taken out of the record in place (hydra_mi/stabilize.py).  Waiting, errors and state are

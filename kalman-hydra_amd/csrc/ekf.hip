@@ -340,6 +340,9 @@ extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
     } else if (!strcmp(key, "rec_map_frames")) {       // frames per run of the trace maps (same results for every value)
         HM_ARG(value >= 1 && value <= REC_MAP_MAX, "hm_ctx_tune: rec_map_frames must be in 1..%d", REC_MAP_MAX);
         h->rec.map_frames = value;
+    } else if (!strcmp(key, "rec_null_frames")) {      // frames per run of the surrogate reduction (same results for every value)
+        HM_ARG(value >= 1 && value <= REC_NULL_MAX, "hm_ctx_tune: rec_null_frames must be in 1..%d", REC_NULL_MAX);
+        h->rec.null_frames = value;
     } else if (!strcmp(key, "rec_scratch_bytes")) {    // tests only: the most scratch of a hm_body_rec_* call (same results for every value)
         HM_ARG(value >= 1 && value <= (1 << 30), "hm_ctx_tune: rec_scratch_bytes must be in 1..%d", 1 << 30);
         h->rec.scr_bytes = (size_t)value;

@@ -1,8 +1,8 @@
 // The registered video kept on the device (hm_body_rec_*): the record itself, the reductions over it, its residual motion
 // (match, shift, field, warp), the running baseline and the residual of the cells' model.  Host orchestration and C-ABI
 // (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h, residual_kernels.h and
-// network_kernels.h, which
-// this translation unit alone compiles.  Of the handle (ctx.h) it uses rec, the body map (body.tri, body.h_tri), the
+// network_kernels.h and network_null_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses
+// rec, the body map (body.tri, body.h_tri), the
 // registered plane (body.reg) and the statistics' counters, and reads W, H, device, own and stream.  readout.hip queues the
 // warp: it reserves a frame's slot and queues the copy into it through body_rec_slot and body_rec_queue_copy, and this file
 // reaches the body map and the statistics through body_map_build and body_stats_queue_add (ctx.h).
@@ -12,6 +12,8 @@
 #include "detrend_kernels.h"
 #include "residual_kernels.h"
 #include "network_kernels.h"
+#include "network_null_kernels.h"
+#include <cmath>
 #include <algorithm>
 #include <cstring>
 
@@ -463,15 +465,16 @@ extern "C" int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seed
 }
 
 // ---- every trace against every pixel of the record (network_kernels.h) ------------------------------------------------
-// planes of the box on the device (rows of b.pitch values of 8 bytes) -> full W x H planes of the caller's, 0 outside the box
-static int rec_expand64(const hm_ctx *h, const unsigned long long *d_src, int planes, void *out)
+// planes of the box on the device (rows of b.pitch values of 8 or 4 bytes) -> full W x H planes of the caller's, 0 outside the box
+template <typename T>
+static int rec_expand_planes(const hm_ctx *h, const T *d_src, int planes, void *out)
 {
     const RecBox &b = h->rec.box;
-    const size_t n = (size_t)h->W * h->H, nb = (size_t)b.pitch * b.bh;
-    memset(out, 0, (size_t)planes * n * 8);
+    const size_t n = (size_t)h->W * h->H, nb = (size_t)b.pitch * b.bh, es = sizeof(T);
+    memset(out, 0, (size_t)planes * n * es);
     for (int s = 0; s < planes; s++)
-        HM_HIP(hipMemcpy2D((uint64_t *)out + (size_t)s * n + (size_t)b.r0 * h->W + b.c0, (size_t)h->W * 8, d_src + (size_t)s * nb,
-                           (size_t)b.pitch * 8, (size_t)b.bw * 8, (size_t)b.bh, hipMemcpyDeviceToHost));
+        HM_HIP(hipMemcpy2D((T *)out + (size_t)s * n + (size_t)b.r0 * h->W + b.c0, (size_t)h->W * es, d_src + (size_t)s * nb,
+                           (size_t)b.pitch * es, (size_t)b.bw * es, (size_t)b.bh, hipMemcpyDeviceToHost));
     return HM_OK;
 }
 
@@ -516,9 +519,101 @@ extern "C" int hm_body_rec_trace_maps(hm_ctx_t h, int L, const int32_t *q, int64
     hipLaunchKernelGGL(k_rec_trace_maps, dim3(hm_cdiv((int)(nb >> 2), 256), std::min(runs, 65535), groups), dim3(256), 0, h->stream, g);
     HM_HIP(hipGetLastError());
     HM_HIP(hipStreamSynchronize(h->stream));
-    if (c) HM_TRY(rec_expand64(h, g.c, L, c));
-    if (w1) HM_TRY(rec_expand64(h, g.w1, 1, w1));
-    if (w2) HM_TRY(rec_expand64(h, g.w2, 1, w2));
+    if (c) HM_TRY(rec_expand_planes(h, g.c, L, c));
+    if (w1) HM_TRY(rec_expand_planes(h, g.w1, 1, w1));
+    if (w2) HM_TRY(rec_expand_planes(h, g.w2, 1, w2));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_trace_null(hm_ctx_t h, int L, const int32_t *q, const double *vb, double *tmax, double *tmin,
+                                      uint32_t *ge, uint32_t *le)
+{
+    HM_ARG(L >= 2 && L <= REC_NULL_LMAX, "hm_body_rec_trace_null: %d traces outside 2..%d", L, REC_NULL_LMAX);
+    HM_ARG(h && q && vb, "hm_body_rec_trace_null: NULL handle, traces or variances");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_trace_null"));
+    const int F = h->rec.frames;
+    // |F c| and |w1 u1| <= F^2 x 255 x 32767
+    HM_ARG((unsigned __int128)F * F * 255u * (unsigned)REC_MAP_QMAX < ((unsigned __int128)1 << 63),
+           "hm_body_rec_trace_null: F x F x 255 x 32767 = %d x %d x 255 x 32767 could pass 2^63", F, F);
+    const size_t fl = (size_t)F * L;
+    std::vector<long long> u1((size_t)L, 0);
+    std::vector<int> q0((size_t)F);
+    for (size_t i = 0; i < fl; i++) {
+        HM_ARG(q[i] >= -REC_MAP_QMAX && q[i] <= REC_MAP_QMAX, "hm_body_rec_trace_null: q %d (frame %zu, trace %zu) outside -%d..%d",
+               (int)q[i], i / (size_t)L, i % (size_t)L, REC_MAP_QMAX, REC_MAP_QMAX);
+        u1[i % (size_t)L] += q[i];
+    }
+    for (int k = 0; k < F; k++) q0[(size_t)k] = q[(size_t)k * L];
+    for (int s = 0; s < L; s++)
+        HM_ARG(vb[s] >= 0.0 && std::isfinite(vb[s]), "hm_body_rec_trace_null: vb %g (trace %d) is negative or not finite", vb[s], s);
+    if (!(tmax || tmin || ge || le)) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const RecBox &b = h->rec.box;
+    const size_t nb = (size_t)b.pitch * b.bh;
+    const bool keys = tmax || tmin;
+    RecMaps g;
+    RecNull a;
+    int *d_q = nullptr, *d_q0 = nullptr;
+    long long *d_u1 = nullptr;
+    double *d_vb = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_q = cv.take<int>(fl);
+        d_q0 = cv.take<int>((size_t)F);
+        d_u1 = cv.take<long long>((size_t)L);
+        d_vb = cv.take<double>((size_t)L);
+        g.c = cv.take<unsigned long long>(nb);
+        g.w1 = cv.take<unsigned long long>(nb);
+        g.w2 = cv.take<unsigned long long>(nb);
+        a.kmax = keys ? cv.take<unsigned long long>((size_t)L) : nullptr;
+        a.kmin = keys ? cv.take<unsigned long long>((size_t)L) : nullptr;
+        a.ge = ge ? cv.take<unsigned>(nb) : nullptr;
+        a.le = le ? cv.take<unsigned>(nb) : nullptr;
+    }));
+    HM_HIP(hipMemcpyAsync(d_q, q, fl * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_q0, q0.data(), (size_t)F * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_u1, u1.data(), (size_t)L * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemcpyAsync(d_vb, vb, (size_t)L * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(g.c, 0, nb * 8, h->stream));
+    HM_HIP(hipMemsetAsync(g.w1, 0, nb * 8, h->stream));
+    HM_HIP(hipMemsetAsync(g.w2, 0, nb * 8, h->stream));
+    if (keys) {
+        HM_HIP(hipMemsetAsync(a.kmax, 0, (size_t)L * 8, h->stream));          // the lowest key
+        HM_HIP(hipMemsetAsync(a.kmin, 0xff, (size_t)L * 8, h->stream));       // the highest
+    }
+    if (ge) HM_HIP(hipMemsetAsync(a.ge, 0, nb * sizeof(unsigned), h->stream));
+    if (le) HM_HIP(hipMemsetAsync(a.le, 0, nb * sizeof(unsigned), h->stream));
+    // column 0 alone through k_rec_trace_maps: c_0, w1, w2 of every pixel, which k_rec_trace_null reads at its end
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.F = F; g.L = 1; g.run = h->rec.map_frames; g.q = d_q0;
+    hipLaunchKernelGGL(k_rec_trace_maps, dim3(hm_cdiv((int)(nb >> 2), 256), std::min(hm_cdiv(F, g.run), 65535), 1), dim3(256), 0,
+                       h->stream, g);
+    a.b = b; a.chunks = g.chunks; a.F = F; a.L = L; a.run = h->rec.null_frames; a.W = h->W; a.q = d_q; a.u1 = d_u1; a.vb = d_vb;
+    a.tri = h->body.tri; a.c0 = g.c; a.w1 = g.w1; a.w2 = g.w2;
+    const long long wgs = (long long)hm_cdiv((int)(nb >> 2), 256) * hm_cdiv(L, REC_MAP_GROUP);
+    HM_ARG(wgs < (1ll << 31), "hm_body_rec_trace_null: %lld workgroups (a box of %d x %d pixels, %d traces)", wgs, b.bw, b.bh, L);
+    hipLaunchKernelGGL(k_rec_trace_null, dim3((unsigned)wgs), dim3(256), 0, h->stream, a);
+    HM_HIP(hipGetLastError());
+    std::vector<uint64_t> key(keys ? 2 * (size_t)L : 0);
+    if (keys) {
+        HM_HIP(hipMemcpyAsync(key.data(), a.kmax, (size_t)L * 8, hipMemcpyDeviceToHost, h->stream));
+        HM_HIP(hipMemcpyAsync(key.data() + L, a.kmin, (size_t)L * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HM_HIP(hipStreamSynchronize(h->stream));
+    // a key back to its double (d_null_key); one that no workgroup touched (a map without a pixel) is NaN
+    auto unkey = [](uint64_t k) {
+        const uint64_t u = (k >> 63) ? k & ~((uint64_t)1 << 63) : ~k;
+        double x;
+        memcpy(&x, &u, 8);
+        return k == 0 || k == ~(uint64_t)0 ? std::nan("") : x;
+    };
+    for (int s = 0; s < L; s++) {
+        if (tmax) tmax[s] = unkey(key[(size_t)s]);
+        if (tmin) tmin[s] = unkey(key[(size_t)L + s]);
+    }
+    if (ge) HM_TRY(rec_expand_planes(h, a.ge, 1, ge));
+    if (le) HM_TRY(rec_expand_planes(h, a.le, 1, le));
     return HM_OK;
 }
 

@@ -10,6 +10,9 @@ lags numbers.  Exact whole numbers come first, then one r
   coactivity      Pearson's r of every pair of traces at every lag -max_lag..max_lag
   ensembles       the connected components of the graph r(lag 0) >= thr: the cells that fire together
   ensemble_traces, lead_lag, ensemble_map, strain_coupling, colour_map; extract does all of it in turn
+  shifts, surrogates, map_null, coactivity_null   significance against circularly shifted traces: the null of a map is the
+                  largest rho over all its pixels per surrogate, reduced on the device (hm_body_rec_trace_null,
+                  csrc/network_null_kernels.h)
 
     body = BodyReadout(kf, keep=True, stats=True)
     ... track ...
@@ -20,7 +23,8 @@ lags numbers.  Exact whole numbers come first, then one r
     lag, peak = network.lead_lag(ens, 10)
     which = network.ensemble_map(network.maps(body, ens), 0.3)
 
-tests/network_ref.py restates every step in loops and Python integers; the two agree bit for bit.
+tests/network_ref.py and tests/network_null_ref.py restate every step in loops and Python integers; the two agree bit
+for bit.
 """
 import numpy as np
 
@@ -28,6 +32,8 @@ from . import cellview, videoio
 
 QMAX = 32767                          # the largest |q| hm_body_rec_trace_maps takes
 LMAX = 1024                           # the most traces of one call
+NULL_LMAX = 4096                      # the most columns hm_body_rec_trace_null takes: the trace and 4095 surrogates
+MIN_SHIFTS = 19                       # fewer surrogates cannot reach p = 0.05: (1 + 0) / (19 + 1)
 
 #: halfway between the lowest correlation of dF/F within a planted ensemble (0.682) and the highest between two
 #: ensembles (0.424) of the planted video with ensembles (tests/network_ref.py, seeds 0..4; tests/test_network_cpu.py
@@ -140,16 +146,21 @@ def coactivity(traces, max_lag=0):
     return r
 
 
-def ensembles(r0, thr=None):
+def ensembles(r0, thr=None, p=None, alpha=0.05):
     """The lag-0 correlations (K, K) -> a label per cell (K,) int32: the connected components of the graph with an edge
     where r0[i, j] >= thr or r0[j, i] >= thr, i != j, numbered by decreasing size, then by lowest member; a cell alone
-    gets -1.  NaN is no edge.  thr None: DEFAULT_THR."""
+    gets -1.  NaN is no edge.  thr None: DEFAULT_THR.  With p (K, K), the p-values of coactivity_null, an edge also needs
+    p[i, j] <= alpha or p[j, i] <= alpha."""
     thr = DEFAULT_THR if thr is None else float(thr)
     r0 = np.asarray(r0, np.float64)
     K = r0.shape[0]
     with np.errstate(invalid="ignore"):
         adj = r0 >= thr
     adj = (adj | adj.T) & ~np.eye(K, dtype=bool)
+    if p is not None:
+        with np.errstate(invalid="ignore"):
+            low = np.asarray(p, np.float64) <= float(alpha)
+        adj &= low | low.T
     comp = np.full(K, -1, np.int64)
     groups = []
     for i in range(K):
@@ -253,7 +264,109 @@ def colour_map(ensemble_map, gray, path=None):
     return out
 
 
-def extract(body, traces, thr=None, max_lag=DEFAULT_LAG, map_thr=None):
+def shifts(F, n, guard, seed=0):
+    """The circular shifts a null is made of -> sorted int64: the candidates are s in 1..F-1 with min(s, F - s) > guard
+    (a shift nearer to 0 leaves the surrogate correlated with the trace itself through its autocorrelation); all of them
+    if there are no more than n, else n drawn without replacement by np.random.default_rng(seed).choice and sorted.
+    Fewer than MIN_SHIFTS candidates raises: p = 0.05 cannot be reached."""
+    F, n, guard = int(F), int(n), int(guard)
+    cand = np.array([s for s in range(1, F) if min(s, F - s) > guard], np.int64)
+    if len(cand) < MIN_SHIFTS:
+        raise ValueError("network: %d circular shifts of %d frames beyond a guard of %d (need at least %d)" %
+                         (len(cand), F, guard, MIN_SHIFTS))
+    if len(cand) <= n:
+        return cand
+    return np.sort(np.random.default_rng(seed).choice(cand, size=n, replace=False))
+
+
+def surrogates(q_row, shifts):
+    """A quantised trace (F,) and S shifts -> (F, 1 + S) int32 as the device takes it: column 0 the trace, column j
+    np.roll(trace, shifts[j - 1])."""
+    q = np.asarray(q_row, np.int32).reshape(-1)
+    out = np.empty((q.shape[0], 1 + len(shifts)), np.int32)
+    out[:, 0] = q
+    for j, s in enumerate(shifts):
+        out[:, 1 + j] = np.roll(q, int(s))
+    return out
+
+
+def p_from_null(null, obs):
+    """(1 + #{s: null[s] >= obs}) / (S + 1) for every value of obs, float64: the count is of whole numbers, then one
+    division.  NaN where obs is NaN."""
+    null = np.sort(np.asarray(null, np.float64).reshape(-1))
+    obs = np.asarray(obs, np.float64)
+    S = null.shape[0]
+    count = S - np.searchsorted(null, np.where(np.isnan(obs), 0.0, obs), side="left")
+    return np.where(np.isnan(obs), np.nan, (1 + count).astype(np.float64) / np.float64(S + 1))
+
+
+def map_null(body, traces, n=1000, guard=DEFAULT_LAG, seed=0, alpha=0.05, rho=None):
+    """The significance of maps(body, traces) against circularly shifted traces -> dict:
+      rho (K, H, W)                 maps(body, traces)
+      shifts (S,) int64             shifts(F, n, guard, seed), the same for every trace
+      rho_max, rho_min (K, S)       per surrogate the largest and smallest rho over all pixels of the map
+      p_map (K, H, W) float64       (1 + #{s: rho_max[s] >= rho(p)}) / (S + 1): the family-wise p-value of a pixel, the
+                                    maximum over the whole map being the statistic; NaN outside the map
+      p_pix (K, H, W) float64       (1 + #{s: num_s(p) >= num_0(p)}) / (S + 1): the pixel against its own surrogates alone
+                                    (uncorrected; whole numbers compared); NaN outside the map
+      sig (K, H, W) bool            p_map <= alpha
+    Per trace one call of the device (hm_body_rec_trace_null): F x (S + 1) whole numbers go in, two planes of counts and
+    2 (S + 1) doubles come out.  The observed column's maximum must be the largest rho of `maps`, bit for bit.  `rho`: what
+    maps(body, traces) gave, for a caller that has it already."""
+    if not getattr(body, "keep", False):
+        raise RuntimeError("network.map_null: the readout was made without keep=True")
+    rho = maps(body, traces) if rho is None else np.asarray(rho, np.float64)
+    q = quantise(traces)
+    K, F = q.shape
+    sh = shifts(F, n, guard, seed)
+    S = len(sh)
+    if S + 1 > NULL_LMAX:
+        raise ValueError("network.map_null: %d surrogates (at most %d a call)" % (S, NULL_LMAX - 1))
+    m = body.tri_of_pixel >= 0
+    out = dict(rho=rho, shifts=sh, rho_max=np.empty((K, S)), rho_min=np.empty((K, S)), p_map=np.empty(rho.shape),
+               p_pix=np.empty(rho.shape), sig=np.empty(rho.shape, bool))
+    for k in range(K):
+        qs = [int(v) for v in q[k]]
+        vb = float(F * sum(v * v for v in qs) - sum(qs) ** 2)          # (a roll keeps both sums: every column's)
+        o = body.r.body_rec_trace_null(surrogates(q[k], sh), np.full(S + 1, vb))
+        assert o["tmax"][0] == np.nanmax(rho[k]) and o["tmin"][0] == np.nanmin(rho[k])
+        out["rho_max"][k], out["rho_min"][k] = o["tmax"][1:], o["tmin"][1:]
+        out["p_map"][k] = p_from_null(o["tmax"][1:], rho[k])
+        out["p_pix"][k] = np.where(m, (1 + o["ge"].astype(np.int64)).astype(np.float64) / np.float64(S + 1), np.nan)
+        with np.errstate(invalid="ignore"):
+            out["sig"][k] = out["p_map"][k] <= float(alpha)
+    return out
+
+
+def coactivity_null(traces, shifts):
+    """Traces (K, F) and S circular shifts -> p_r (K, K) float64: for every ordered pair i != j the observed
+    F sum(q_i q_j) - u1_i u1_j of the quantised traces (int64, exact: F below 92682) against the same with q_j rolled by
+    every shift: (1 + #{s: surrogate >= observed}) / (S + 1).  NaN on the diagonal and for a trace with a value that is
+    not finite."""
+    x = np.asarray(traces, np.float64)
+    if x.ndim != 2:
+        raise ValueError("network: traces of shape %r (need cells x frames)" % (x.shape,))
+    K, F = x.shape
+    if F * F * QMAX * QMAX >= 2 ** 63:
+        raise ValueError("network.coactivity_null: %d frames (F x F x 32767^2 could pass 2^63)" % F)
+    ok = np.isfinite(x).all(1)
+    q = np.zeros((K, F), np.int64)
+    q[ok] = quantise(x[ok])
+    u1 = q.sum(1)
+    S = len(shifts)
+    p = np.full((K, K), np.nan)
+    for j in np.flatnonzero(ok):
+        rolled = np.array([np.roll(q[j], int(s)) for s in shifts], np.int64).reshape(S, F)
+        for i in np.flatnonzero(ok):
+            if i == j:
+                continue
+            obs = F * (q[i] * q[j]).sum() - u1[i] * u1[j]
+            sur = F * (rolled * q[i][None, :]).sum(1) - u1[i] * u1[j]
+            p[i, j] = np.float64(1 + int((sur >= obs).sum())) / np.float64(S + 1)
+    return p
+
+
+def extract(body, traces, thr=None, max_lag=DEFAULT_LAG, map_thr=None, null=0, guard=DEFAULT_LAG, seed=0, alpha=0.05):
     """The whole readout of the traces (K, F) of the cells of a BodyReadout(keep=True) -> dict:
       r (K, K, 2 max_lag + 1) float64      coactivity; a trace with a value that is not finite correlates with nothing
       labels (K,) int32, ens_traces (E, F) ensembles(r at lag 0, thr) and their mean traces
@@ -261,7 +374,11 @@ def extract(body, traces, thr=None, max_lag=DEFAULT_LAG, map_thr=None):
       rho (E, H, W) float64                 maps(body, ens_traces)
       map (H, W) int16                      ensemble_map(rho, map_thr)
       gray (H, W) uint8                     the mean recorded frame, rint(w1 / F): what colour_map paints the map on
-    thr None: DEFAULT_THR; map_thr None: DEFAULT_MAP_THR."""
+    thr None: DEFAULT_THR; map_thr None: DEFAULT_MAP_THR.  With null > 0 also, against `null` circular shifts
+    (shifts(F, null, guard, seed)):
+      p_r (K, K)                            coactivity_null of the cells' traces
+      p_map (E, H, W), rho_max (E, S), sig (E, H, W) bool, shifts (S,)     map_null of the ensembles' traces at alpha
+      map_sig (H, W) int16                  `map` with -1 where the winning ensemble's pixel is not significant"""
     x = np.asarray(traces, np.float64)
     max_lag = int(max_lag)
     r = coactivity(x, max_lag)
@@ -272,5 +389,16 @@ def extract(body, traces, thr=None, max_lag=DEFAULT_LAG, map_thr=None):
     F = body.r.body_rec_count()
     w1 = body.r.body_rec_trace_maps(np.zeros((F, 1), np.int32), want=("w1",))["w1"]
     gray = np.rint(w1.astype(np.float64) / np.float64(F)).astype(np.uint8)
-    return dict(r=r, labels=labels, ens_traces=ens, lead_lag=lag, lead_r=peak, rho=rho,
-                map=ensemble_map(rho, DEFAULT_MAP_THR if map_thr is None else map_thr), gray=gray)
+    out = dict(r=r, labels=labels, ens_traces=ens, lead_lag=lag, lead_r=peak, rho=rho,
+               map=ensemble_map(rho, DEFAULT_MAP_THR if map_thr is None else map_thr), gray=gray)
+    if null > 0:
+        sh = shifts(F, null, guard, seed)
+        out.update(p_r=coactivity_null(x, sh), shifts=sh)
+        if len(ens):
+            mn = map_null(body, ens, null, guard, seed, alpha, rho=rho)
+            out.update(p_map=mn["p_map"], rho_max=mn["rho_max"], sig=mn["sig"])
+        else:
+            out.update(p_map=np.empty(rho.shape), rho_max=np.empty((0, len(sh))), sig=np.empty(rho.shape, bool))
+        won = np.take_along_axis(out["sig"], np.maximum(out["map"], 0).astype(np.int64)[None], 0)[0] if len(ens) else False
+        out["map_sig"] = np.where((out["map"] >= 0) & won, out["map"], -1).astype(np.int16)
+    return out

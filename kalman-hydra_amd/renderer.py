@@ -500,6 +500,32 @@ class Renderer:
                    "hm_body_rec_trace_maps")
         return o
 
+    def body_rec_trace_null(self, q, vb, want=("tmax", "tmin", "ge", "le")):
+        """hm_body_rec_trace_null: q (F, L) int32 with |q| <= 32767, column 0 the observed trace and the others its
+        surrogates, vb (L,) float64 = F u2 - u1^2 of every column -> dict of those in `want`: tmax, tmin (L,) float64, the
+        largest and smallest correlation of every column over the map; ge, le (H, W) uint32, per pixel the surrogates
+        whose numerator is >= and <= the observed one (0 outside the map)."""
+        F = self.body_rec_count()
+        q = np.asarray(q)
+        if q.dtype != np.int32 or q.ndim != 2 or (F and q.shape[0] != F):          # (F 0: the call says why)
+            raise ValueError("traces %s of shape %r for %d frames (need int32, frames x traces)" % (q.dtype, q.shape, F))
+        q = np.ascontiguousarray(q)
+        L, H, W = q.shape[1], self.ny, self.nx
+        vb = np.ascontiguousarray(vb, np.float64)
+        if vb.shape != (L,):
+            raise ValueError("vb of shape %r for %d traces" % (vb.shape, L))
+        o = {}
+        for key in ("tmax", "tmin"):
+            if key in want:
+                o[key] = np.empty(max(L, 0), np.float64)
+        for key in ("ge", "le"):
+            if key in want:
+                o[key] = np.empty((H, W), np.uint32)
+        _lib.check(_lib.lib().hm_body_rec_trace_null(self._h, L, _lib.ptr(q), _lib.ptr(vb),
+                                                     *[_lib.ptr(o[k]) if k in o else None for k in ("tmax", "tmin", "ge", "le")]),
+                   "hm_body_rec_trace_null")
+        return o
+
     # -- residual motion of the record (hm_body_rec_match / _frame_sums / _shift / _warp / _field_sums; hydra_mi.stabilize) --
     def body_rec_patches(self, B):
         """-> (patches per row, patch rows) of the grid of B x B patches over the record's box (the bounding box of the

@@ -116,7 +116,16 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      here; net_map (H x W, int16): per pixel the ensemble with the largest rho if that is >=
                      --network-map-thr, else -1; with --strain also net_strain_r (ensembles x triangles): Pearson's r
                      between an ensemble's trace and a triangle's area ratio.
-    --network-map OUT.png   with --network: net_map in the ensembles' colours over the mean registered frame.
+    --network-map OUT.png   with --network: net_map in the ensembles' colours over the mean registered frame (with
+                     --network-null: net_map_sig).
+    --network-null N   with --network: significance against N circular shifts of the traces (all of them if there are no
+                     more; a shift is at least --network-guard + 1 frames from 0 either way, default 10; drawn with
+                     --network-seed, default 0).  net_p_r (cells x cells): per ordered pair the share of shifted second
+                     traces that correlate with the first at least as well; net_rho_max (ensembles x shifts): per shifted
+                     ensemble trace the largest rho over the whole map, made on the device; net_p_map (ensembles x H x W,
+                     float32): the share of those maxima that reach the pixel's rho, a p-value that holds for the whole
+                     map at once; net_sig (bool): net_p_map <= --network-alpha (default 0.05); net_map_sig: net_map with
+                     -1 where the winning ensemble's pixel is not significant.
 """
 import argparse
 import os
@@ -216,6 +225,11 @@ def main(argv=None):
     parser.add_argument("--network-map-thr", default=None, type=float,
                         help="the least rho that gives a pixel to an ensemble (default %g)" % network.DEFAULT_MAP_THR)
     parser.add_argument("--network-map", default=None, metavar="OUT.png", help="with --network: write the ensemble map here (.png)")
+    parser.add_argument("--network-null", default=0, type=int, metavar="N",
+                        help="with --network: significance against N circularly shifted traces (net_p_r, net_p_map, net_rho_max, net_sig, net_map_sig)")
+    parser.add_argument("--network-alpha", default=0.05, type=float, help="with --network-null: the level a pixel is significant at")
+    parser.add_argument("--network-guard", default=network.DEFAULT_LAG, type=int, help="with --network-null: no shift within N frames of 0")
+    parser.add_argument("--network-seed", default=0, type=int, help="with --network-null: the seed the shifts are drawn with")
     args = parser.parse_args(argv)
     if not 0 <= args.strain_alpha <= 255 or not np.isfinite(args.strain_gain):
         parser.error("the strain video needs a --strain-alpha in 0..255 and a finite --strain-gain")
@@ -254,6 +268,10 @@ def main(argv=None):
         parser.error("--network-map draws the ensembles: it needs --network")
     if args.network and (args.network_lag < 0 or any(t is not None and not np.isfinite(t) for t in (args.network_thr, args.network_map_thr))):
         parser.error("--network needs a --network-lag >= 0 and finite thresholds")
+    if args.network_null and not args.network:
+        parser.error("--network-null tests the ensembles' maps: it needs --network")
+    if args.network_null < 0 or args.network_guard < 0 or not 0.0 < args.network_alpha <= 1.0:
+        parser.error("--network-null and --network-guard must be >= 0 and --network-alpha in (0, 1]")
     if args.detrend and args.find_points is None:
         parser.error("--detrend finds the cells in the excess video: it needs --find-points")
     if args.resummarize and (not args.stabilize or args.detrend):
@@ -470,14 +488,21 @@ def main(argv=None):
                                                                           e["roi_counts"].max(), e["seed_fallback"].sum()))
             if args.network:                                       # (cell s: point inside[s], as the roi_* rows)
                 net = network.extract(body, (e["dff_demixed"] if args.demix else e["dff"]).T, thr=args.network_thr,
-                                      max_lag=args.network_lag, map_thr=args.network_map_thr)
+                                      max_lag=args.network_lag, map_thr=args.network_map_thr, null=args.network_null,
+                                      guard=args.network_guard, seed=args.network_seed, alpha=args.network_alpha)
                 extra.update(net_r=net["r"], net_labels=net["labels"], net_ens_traces=net["ens_traces"],
                              net_lead_lag=net["lead_lag"], net_lead_r=net["lead_r"], net_rho=net["rho"].astype(np.float32),
                              net_map=net["map"])
                 print("Network: %d ensembles of %d cells, %d cells alone, %d pixels mapped" % (
                     net["ens_traces"].shape[0], (net["labels"] >= 0).sum(), (net["labels"] < 0).sum(), (net["map"] >= 0).sum()))
+                if args.network_null:
+                    extra.update(net_p_r=net["p_r"], net_p_map=net["p_map"].astype(np.float32), net_rho_max=net["rho_max"],
+                                 net_sig=net["sig"], net_map_sig=net["map_sig"])
+                    for k in range(net["rho_max"].shape[0]):
+                        print("Null: ensemble %d: the largest rho of %d shifted traces %.4f, %d significant pixels" % (
+                            k, net["rho_max"].shape[1], net["rho_max"][k].max(), net["sig"][k].sum()))
                 if args.network_map is not None:
-                    network.colour_map(net["map"], net["gray"], args.network_map)
+                    network.colour_map(net["map_sig"] if args.network_null else net["map"], net["gray"], args.network_map)
                     print("Ensemble map: %s" % args.network_map)
             if args.strain:                                        # (cell s: point inside[s], as the roi_* rows)
                 st_cells, st_dff = {"labels": e["roi_labels"], "L": len(inside)}, e["dff_demixed"] if args.demix else e["dff"]
