@@ -380,6 +380,8 @@ int hm_chain_states(hm_ctx_t h, double *predicted, double *projected, int *newto
  * state, gains, the next frame's covariance prediction) on a stream of its own or on the handle's (same results);
  * "newton_fail" = 1 (test knob): device state predictions report a failed inner solve */
 int hm_ctx_tune(hm_ctx_t h, const char *key, int value);
+/* the same with a value of 64 bits, for "rec_ev_bytes" (1..2^34); any other key takes what fits 32 bits, as hm_ctx_tune */
+int hm_ctx_tune64(hm_ctx_t h, const char *key, int64_t value);
 int hm_ctx_sync(hm_ctx_t h);
 void *hm_ctx_stream(hm_ctx_t h);
 
@@ -791,6 +793,45 @@ int hm_body_rec_field_sums(hm_ctx_t h, int k0, int n_frames, int B, const int16_
  *   every value.) */
 int hm_body_rec_planes(hm_ctx_t h, int k0, int n_frames, int what, int half, int q, int floor, int gain, uint8_t *out);
 int hm_body_rec_stats_add(hm_ctx_t h, int what, int half, int q, int floor, int gain);
+
+/* Events per pixel of the record: AR(1) deconvolution of every box pixel's planes of a kind (hydra_mi/events.py, DESIGN.md
+ * section 19; csrc/events_kernels.h; tests/events_ref.py restates the rule in Python floats).
+ *   All arithmetic is binary64, in exactly this order; the library is built with -ffp-contract=off, a lane works through
+ *   its pixel sequentially, and multiplication, addition and division are correctly rounded, so the device reproduces a
+ *   plain Python-float restatement bit for bit.  pos(a) below is a where a > 0 and +0 otherwise.
+ *   Input       The F recorded frames.  y_k(p) is the pixel's value in the plane of kind `what` (0 raw, 1 baseline, 2 excess,
+ *               3 dF/F byte) of frame k; half, q, floor, gain are exactly those of hm_body_rec_planes.  y_k(p) is an
+ *               integer 0..255 converted to double.  g (0 < g < 1), lam >= 0, s_min >= 0.
+ *   Powers      Formed on the host: pw[0] = 1, pw[l] = pw[l-1] g for l <= F; pw2[l] = pw[l] pw[l].  No pow anywhere.
+ *   Pool stack  AR(1) OASIS for min 1/2 sum (c_k - y_k)^2 + lam sum s_k with s_k = c_k - g c_{k-1} >= 0, on a stack of pools
+ *               (v, w, t, l).  For k = 0 .. F-1 push (y_k - lam (1 - g), 1, k, 1); the last frame pushes y_k - lam instead.
+ *               While there are two pools a (below) and b (top) with v_b < pw[l_a] v_a, merge b into a:
+ *                 num = w_a v_a + (pw[l_a] w_b) v_b,  den = w_a + pw2[l_a] w_b,
+ *                 v_a = num / den, w_a = den, l_a += l_b, then pop b.
+ *   Readout     For a pool i, c_{t_i + j} = pos(v_i) pw[j].  At the start of a pool i > 0:
+ *               s_{t_i} = pos(pos(v_i) - g (pos(v_{i-1}) pw[l_{i-1} - 1])).  s_k = 0 everywhere else, and s_0 = 0.
+ *   Results     Event byte E_k(p) = min(255, floor(s_k + 0.5)).  Event count n(p) = #{k : s_k >= s_min} as uint32 (with
+ *               s_min = 0 every frame of every box pixel counts: n = F).  Event sum S(p) = sum_k s_k, added in ascending
+ *               k, as double.  Off the map and in the padding y = 0 and so everything is 0; outside the box all is 0.
+ *   event_planes     writes the full W x H byte planes of E of the frames k0 .. k0 + n_frames - 1 into `out`, laid out as
+ *               hm_body_rec_planes lays them out.  The solution is that of the whole record whatever the window.
+ *   event_stats_add  adds every recorded frame's E plane to the statistics of hm_body_stats_*, exactly as
+ *               hm_body_rec_stats_add adds its planes (same state errors, same capacity rule).
+ *   event_sums       writes W x H planes of n (uint32) and S (double); either may be NULL.
+ *   All three: HM_ERR_ARG with the numbers in hm_last_error for detrend parameters that hm_body_rec_planes refuses, for g,
+ *   lam or s_min outside their range or not finite, for a frame range outside the record, and for a record of more than
+ *   65535 frames (the stack keeps frame numbers in 16 bits).  Waiting and state errors are those of hm_body_rec_planes.
+ *   The record, the map and the tracker do not change by a bit.  The pool stack takes 20 bytes per frame and pixel
+ *   (v, w: doubles at a pool's start; its length, 16 bits, at its start; its start, 16 bits, at its end) in a device work
+ *   buffer; the box is worked through in passes over as many 64-byte segments of the box frame as fit into hm_ctx_tune
+ *   "rec_ev_bytes" (hm_ctx_tune64: 1..2^34, default 2^34, one segment at least: same results for every value).  Beside it
+ *   the call holds the E bytes of the frames it covers (a twentieth of what their stack would take) and, for kinds 1..3,
+ *   the scratch of hm_body_rec_planes; all three are freed on every return including errors. */
+int hm_body_rec_event_planes(hm_ctx_t h, int k0, int n_frames, int what, int half, int q, int floor, int gain, double g,
+                             double lam, uint8_t *out);
+int hm_body_rec_event_stats_add(hm_ctx_t h, int what, int half, int q, int floor, int gain, double g, double lam);
+int hm_body_rec_event_sums(hm_ctx_t h, int what, int half, int q, int floor, int gain, double g, double lam, double s_min,
+                           uint32_t *count, double *sum);
 
 /* The residual of the record: every recorded frame minus the light a model of the cells puts there (hydra_mi/residual.py,
  * DESIGN.md section 15; csrc/residual_kernels.h; tests/residual_ref.py restates the rule in NumPy).  Exact integers.

@@ -115,6 +115,7 @@ SIGNATURES = {
                                      ctypes.c_int, ctypes.c_double, ctypes.c_double, c_vp, ctypes.POINTER(ctypes.c_int),
                                      ctypes.c_int]),
     "hm_ctx_tune": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_int]),
+    "hm_ctx_tune64": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_int64]),
     "hm_ctx_sync": (ctypes.c_int, [c_vp]),
     "hm_ctx_stream": (c_vp, [c_vp]),
     "hm_smooth_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
@@ -170,6 +171,12 @@ SIGNATURES = {
     "hm_body_rec_planes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, c_vp]),
     "hm_body_rec_stats_add": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "hm_body_rec_event_planes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_vp]),
+    "hm_body_rec_event_stats_add": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_double, ctypes.c_double]),
+    "hm_body_rec_event_sums": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_vp]),
     "hm_body_rec_residual_planes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp,
                                                    c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_body_rec_residual_stats_add": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int,

@@ -170,6 +170,13 @@ struct RecState {
     // a run of frames in the record's layout: as they were (hm_body_rec_shift / _warp), or the planes made of them
     // (hm_body_rec_planes / _stats_add / _residual_*); there while such a call runs, freed when it returns
     uint8_t *scr = nullptr;
+    // hm_body_rec_event_*: the most bytes of the pool stack of a pass (hm_ctx_tune "rec_ev_bytes", one segment at least).
+    // 16 GiB, the most the key admits: the kernels wait on dependent loads, so a pass is the faster the more waves it has
+    // (the box of a 1024^2 frame with 2 000 frames, 18 GB of stack: 37.6 ms a call in two passes against 55 ms in five at
+    // 4 GiB and 131 ms at 1 GiB).  The stack and the event bytes of the frames a call covers are
+    // there while the call runs and freed when it returns.
+    size_t ev_bytes = (size_t)16 << 30;
+    uint8_t *ev = nullptr, *ev_out = nullptr;
 };
 
 struct hm_ctx {

@@ -23,6 +23,7 @@ struct RecRunning {
     int F;                             // frames of the record: the windows reach over all of them
     int k0, n;                         // the frames written: k0 .. k0 + n - 1
     int run;                           // frames per run
+    int seg0;                          // the first segment of the launch: blockIdx.x counts from it
     int what, half, q, floor, gain;    // what: 1 baseline, 2 excess, 3 dF/F byte
     uint8_t *out;                      // n frames in the record's layout, fs bytes apart
 };
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(64) void k_rec_running(RecRunning g)
     unsigned *st_in = det_lds + DET_HIST_DWORDS, *st_out = st_in + 64, *st_cur = st_out + 64, *st_res = st_cur + 64;
     const uint8_t *b_in = (const uint8_t *)st_in, *b_out = (const uint8_t *)st_out, *b_cur = (const uint8_t *)st_cur;
     uint8_t *b_res = (uint8_t *)st_res;
-    const int sub = lane >> 4, dw = blockIdx.x * 16 + (lane & 15);
+    const int sub = lane >> 4, dw = (g.seg0 + blockIdx.x) * 16 + (lane & 15);
     const bool dw_ok = dw < (g.b.pitch * g.b.bh) >> 2;             // (the last segment may end beyond the frame)
     const int runs = (g.n + g.run - 1) / g.run;
     // dword `dw` of frame f where it is wanted, else 0

@@ -346,11 +346,27 @@ extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
     } else if (!strcmp(key, "rec_scratch_bytes")) {    // tests only: the most scratch of a hm_body_rec_* call (same results for every value)
         HM_ARG(value >= 1 && value <= (1 << 30), "hm_ctx_tune: rec_scratch_bytes must be in 1..%d", 1 << 30);
         h->rec.scr_bytes = (size_t)value;
+    } else if (!strcmp(key, "rec_ev_bytes")) {         // the most bytes of the pool stack of a pass of hm_body_rec_event_* (same results for every value)
+        HM_ARG(value >= 1, "hm_ctx_tune: rec_ev_bytes must be in 1..%lld", 1ll << 34);
+        h->rec.ev_bytes = (size_t)value;
     } else {
         hm_set_error("hm_ctx_tune: unknown key '%s'", key);
         return HM_ERR_ARG;
     }
     return HM_OK;
+}
+// the keys whose values pass 2^31 ("rec_ev_bytes"); every other key as hm_ctx_tune takes it
+extern "C" int hm_ctx_tune64(hm_ctx_t h, const char *key, int64_t value)
+{
+    HM_ARG(h != nullptr && key != nullptr, "hm_ctx_tune: NULL argument");
+    if (!strcmp(key, "rec_ev_bytes")) {
+        HM_JOIN(h);
+        HM_ARG(value >= 1 && value <= (1ll << 34), "hm_ctx_tune: rec_ev_bytes must be in 1..%lld", 1ll << 34);
+        h->rec.ev_bytes = (size_t)value;
+        return HM_OK;
+    }
+    HM_ARG(value >= INT32_MIN && value <= INT32_MAX, "hm_ctx_tune: %s = %lld does not fit 32 bits", key, (long long)value);
+    return hm_ctx_tune(h, key, (int)value);
 }
 extern "C" void *hm_ctx_stream(hm_ctx_t h)
 {

@@ -1,6 +1,6 @@
 // The registered video kept on the device (hm_body_rec_*): the record itself, the reductions over it, its residual motion
-// (match, shift, field, warp), the running baseline and the residual of the cells' model.  Host orchestration and C-ABI
-// (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h, residual_kernels.h and
+// (match, shift, field, warp), the running baseline, the events per pixel and the residual of the cells' model.  Host orchestration and C-ABI
+// (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h, events_kernels.h, residual_kernels.h and
 // network_kernels.h and network_null_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses
 // rec, the body map (body.tri, body.h_tri), the
 // registered plane (body.reg) and the statistics' counters, and reads W, H, device, own and stream.  readout.hip queues the
@@ -10,6 +10,7 @@
 #include "roi_kernels.h"
 #include "stab_kernels.h"
 #include "detrend_kernels.h"
+#include "events_kernels.h"
 #include "residual_kernels.h"
 #include "network_kernels.h"
 #include "network_null_kernels.h"
@@ -837,12 +838,14 @@ static int det_args_ok(const char *who, int what, int half, int q, int floor, in
 struct DetPlanes { int what, half, q, floor, gain; };
 
 // queue planes d.what (1..3) of the frames k .. k + m - 1 into dst (m frames in the record's layout)
-static int det_queue(hm_ctx *h, const DetPlanes &d, int k, int m, uint8_t *dst)
+// -- of the segments seg0 .. seg0 + nseg - 1 of the box frame alone if nseg > 0 (the rest of dst is left as it is)
+static int det_queue(hm_ctx *h, const DetPlanes &d, int k, int m, uint8_t *dst, int seg0 = 0, int nseg = 0)
 {
     RecRunning g;
     g.b = h->rec.box; g.chunks = (const uint8_t *const *)h->rec.tab; g.F = h->rec.frames; g.k0 = k; g.n = m;
     g.run = h->rec.bl_frames; g.what = d.what; g.half = d.half; g.q = d.q; g.floor = d.floor; g.gain = d.gain; g.out = dst;
-    const int segs = hm_cdiv(g.b.pitch * g.b.bh, 64), runs = hm_cdiv(m, g.run);
+    g.seg0 = seg0;
+    const int segs = nseg > 0 ? nseg : hm_cdiv(g.b.pitch * g.b.bh, 64), runs = hm_cdiv(m, g.run);
     hipLaunchKernelGGL(k_rec_running, dim3(segs, std::min(runs, 65535)), dim3(64), DET_LDS_BYTES, h->stream, g);
     HM_HIP(hipGetLastError());
     return HM_OK;
@@ -890,6 +893,149 @@ extern "C" int hm_body_rec_stats_add(hm_ctx_t h, int what, int half, int q, int 
         HM_TRY(rec_runs(h, per, 0, F, false, [&](int k, int m, uint8_t *dst) { return det_queue(h, d, k, m, dst); },
                         [&](int, const uint8_t *src) { return rec_stats_add_plane(h, src); }));
         HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    });
+}
+
+// ---- events per pixel of the record: AR(1) deconvolution of every pixel's planes of a kind (events_kernels.h) ---------
+struct EvParams { DetPlanes d; double g, lam, s_min; };
+
+static int ev_args_ok(const char *who, double g, double lam, double s_min)
+{
+    HM_ARG(std::isfinite(g) && g > 0.0 && g < 1.0, "%s: g %g outside 0 < g < 1", who, g);
+    HM_ARG(std::isfinite(lam) && lam >= 0.0, "%s: lam %g negative or not finite", who, lam);
+    HM_ARG(std::isfinite(s_min) && s_min >= 0.0, "%s: s_min %g negative or not finite", who, s_min);
+    return HM_OK;
+}
+
+// The pool stacks of every box pixel over all F frames, in passes over as many segments as rec.ev_bytes hold (one at
+// least), then done(E, cnt, sum): E the event bytes of the frames k0 .. k0 + n - 1 in the record's layout (NULL if n is 0),
+// cnt and sum per byte of a box frame (NULL unless want_sums), all on the device and complete.  A pass pushes the planes of
+// kind d.what batch by batch -- the scratch of hm_body_rec_planes, filled for the pass's segments alone -- or the record
+// itself for kind 0, then reads its pools out.  The stack, E and the scratch are freed on every return.
+template <typename Done>
+static int ev_call(hm_ctx *h, const char *who, const EvParams &p, int k0, int n, bool want_sums, Done done)
+{
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames;
+    HM_ARG(F <= EV_FMAX, "%s: a record of %d frames (the pool stack holds frame numbers in 16 bits: %d frames at most)", who, F, EV_FMAX);
+    const int segs = hm_cdiv(b.pitch * b.bh, 64);
+    const size_t seg_bytes = (size_t)EV_PX_BYTES * 64 * F;
+    const int per_pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)segs, h->rec.ev_bytes / seg_bytes));
+    std::vector<double> pw(2 * ((size_t)F + 1));
+    double *pw2 = pw.data() + F + 1;
+    pw[0] = 1.0;
+    for (int l = 1; l <= F; l++) pw[l] = pw[l - 1] * p.g;
+    for (int l = 0; l <= F; l++) pw2[l] = pw[l] * pw[l];
+    double *d_pw = nullptr, *d_sum = nullptr;
+    unsigned *d_cnt = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_pw = cv.take<double>(pw.size());
+        if (want_sums) {
+            d_cnt = cv.take<unsigned>((size_t)segs * 64);
+            d_sum = cv.take<double>((size_t)segs * 64);
+        }
+    }));
+    RecEvents e;
+    e.b = b; e.chunks = (const uint8_t *const *)h->rec.tab; e.src = nullptr; e.ks = 0; e.F = F;
+    e.g = p.g; e.mu = p.lam * (1.0 - p.g); e.lam = p.lam; e.pw = d_pw; e.pw2 = d_pw + F + 1;
+    auto passes = [&](int per) -> int {
+        for (int s0 = 0; s0 < segs; s0 += per_pass) {
+            const int ns = std::min(per_pass, segs - s0);
+            const size_t FP = (size_t)F * ns * 64;
+            e.seg0 = s0; e.nseg = ns;
+            e.v = (double *)h->rec.ev; e.w = e.v + FP; e.len = (uint16_t *)(e.w + FP); e.start = e.len + FP;
+            if (p.d.what == 0) hipLaunchKernelGGL(k_rec_ev_push, dim3(ns), dim3(64), 0, h->stream, e, 0, F);
+            else
+                for (int k = 0; k < F; k += per) {          // (a batch's planes are queued behind the push that read the scratch)
+                    const int m = std::min(per, F - k);
+                    HM_TRY(det_queue(h, p.d, k, m, h->rec.scr, s0, ns));
+                    e.src = h->rec.scr; e.ks = k;
+                    hipLaunchKernelGGL(k_rec_ev_push, dim3(ns), dim3(64), 0, h->stream, e, k, m);
+                }
+            hipLaunchKernelGGL(k_rec_ev_read, dim3(ns), dim3(64), 0, h->stream, e, k0, n, h->rec.ev_out, p.s_min, d_cnt, d_sum);
+            HM_HIP(hipGetLastError());
+        }
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    };
+    const int rc = [&]() -> int {
+        HM_HIP(h->own.grow(&h->rec.ev, (size_t)per_pass * seg_bytes));
+        if (n > 0) {
+            HM_HIP(h->own.grow(&h->rec.ev_out, (size_t)n * b.fs));
+            HM_HIP(hipMemsetAsync(h->rec.ev_out, 0, (size_t)n * b.fs, h->stream));
+        }
+        HM_HIP(hipMemcpyAsync(d_pw, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HM_TRY(p.d.what == 0 ? passes(0) : rec_with_scratch(h, F, passes));
+        return done((const uint8_t *)h->rec.ev_out, (const unsigned *)d_cnt, (const double *)d_sum);
+    }();
+    if (rc) (void)hipStreamSynchronize(h->stream);
+    const hipError_t fe = h->own.free(&h->rec.ev), fo = h->own.free(&h->rec.ev_out);
+    if (rc) return rc;
+    HM_HIP(fe);
+    HM_HIP(fo);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_event_planes(hm_ctx_t h, int k0, int n_frames, int what, int half, int q, int floor, int gain, double g,
+                                        double lam, uint8_t *out)
+{
+    HM_TRY(det_args_ok("hm_body_rec_event_planes", what, half, q, floor, gain));
+    HM_TRY(ev_args_ok("hm_body_rec_event_planes", g, lam, 0.0));
+    HM_ARG(h != nullptr, "hm_body_rec_event_planes: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_event_planes"));
+    HM_TRY(rec_range_ok(h, "hm_body_rec_event_planes", k0, n_frames));
+    HM_ARG(out || n_frames == 0, "hm_body_rec_event_planes: NULL output");
+    const size_t px = (size_t)h->W * h->H;
+    const EvParams p = {{what, half, q, floor, gain}, g, lam, 0.0};
+    return ev_call(h, "hm_body_rec_event_planes", p, k0, n_frames, false, [&](const uint8_t *E, const unsigned *, const double *) -> int {
+        for (int k = 0; k < n_frames; k++) HM_TRY(rec_expand(h, E + (size_t)k * h->rec.box.fs, out + (size_t)k * px));
+        return HM_OK;
+    });
+}
+
+extern "C" int hm_body_rec_event_stats_add(hm_ctx_t h, int what, int half, int q, int floor, int gain, double g, double lam)
+{
+    HM_TRY(det_args_ok("hm_body_rec_event_stats_add", what, half, q, floor, gain));
+    HM_TRY(ev_args_ok("hm_body_rec_event_stats_add", g, lam, 0.0));
+    HM_ARG(h != nullptr, "hm_body_rec_event_stats_add: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_event_stats_add"));
+    HM_TRY(rec_stats_open(h, "hm_body_rec_event_stats_add"));
+    const int F = h->rec.frames;
+    const EvParams p = {{what, half, q, floor, gain}, g, lam, 0.0};
+    return ev_call(h, "hm_body_rec_event_stats_add", p, 0, F, false, [&](const uint8_t *E, const unsigned *, const double *) -> int {
+        for (int k = 0; k < F; k++) HM_TRY(rec_stats_add_plane(h, E + (size_t)k * h->rec.box.fs));
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    });
+}
+
+extern "C" int hm_body_rec_event_sums(hm_ctx_t h, int what, int half, int q, int floor, int gain, double g, double lam, double s_min,
+                                      uint32_t *count, double *sum)
+{
+    HM_TRY(det_args_ok("hm_body_rec_event_sums", what, half, q, floor, gain));
+    HM_TRY(ev_args_ok("hm_body_rec_event_sums", g, lam, s_min));
+    HM_ARG(h != nullptr, "hm_body_rec_event_sums: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_event_sums"));
+    const EvParams p = {{what, half, q, floor, gain}, g, lam, s_min};
+    return ev_call(h, "hm_body_rec_event_sums", p, 0, 0, true, [&](const uint8_t *, const unsigned *d_cnt, const double *d_sum) -> int {
+        const RecBox &b = h->rec.box;
+        const size_t nb = (size_t)b.pitch * b.bh, px = (size_t)h->W * h->H;
+        std::vector<unsigned> cnt(nb);
+        std::vector<double> sm(nb);
+        HM_HIP(hipMemcpy(cnt.data(), d_cnt, nb * sizeof(unsigned), hipMemcpyDeviceToHost));
+        HM_HIP(hipMemcpy(sm.data(), d_sum, nb * sizeof(double), hipMemcpyDeviceToHost));
+        if (count) std::fill(count, count + px, 0u);
+        if (sum) std::fill(sum, sum + px, 0.0);
+        for (int yb = 0; yb < b.bh; yb++)
+            for (int x = 0; x < b.bw; x++) {
+                const size_t o = (size_t)(b.r0 + yb) * h->W + b.c0 + x, i = (size_t)yb * b.pitch + x;
+                if (count) count[o] = cnt[i];
+                if (sum) sum[o] = sm[i];
+            }
         return HM_OK;
     });
 }

@@ -648,6 +648,34 @@ class Renderer:
         _lib.check(_lib.lib().hm_body_rec_stats_add(self._h, what, int(half), int(q), int(floor), int(gain)),
                    "hm_body_rec_stats_add")
 
+    # -- events per pixel of the record: AR(1) deconvolution of the planes (hm_body_rec_event_*; hydra_mi.events) -----
+    def body_rec_event_planes(self, what, half, q, floor=1, gain=1, g=0.9, lam=0.0, k0=0, n=None):
+        """hm_body_rec_event_planes: -> (n, H, W) uint8, the event bytes min(255, floor(s + 0.5)) of the recorded frames
+        k0 .. k0 + n - 1 (default: all from k0): s the AR(1) deconvolution (decay g per frame, penalty lam) of every
+        pixel's planes of kind `what` (as body_rec_planes) over the whole record."""
+        what = self.PLANES[what] if isinstance(what, str) else int(what)
+        n = self._rec_n(k0, n)
+        out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
+        _lib.check(_lib.lib().hm_body_rec_event_planes(self._h, int(k0), n, what, int(half), int(q), int(floor), int(gain),
+                                                       float(g), float(lam), _lib.ptr(out)), "hm_body_rec_event_planes")
+        return out
+
+    def body_rec_event_stats_add(self, what, half, q, floor=1, gain=1, g=0.9, lam=0.0):
+        """hm_body_rec_event_stats_add: add every recorded frame's event plane (as body_rec_event_planes) to the statistics
+        begun with body_stats_begin, as if each had just been warped."""
+        what = self.PLANES[what] if isinstance(what, str) else int(what)
+        _lib.check(_lib.lib().hm_body_rec_event_stats_add(self._h, what, int(half), int(q), int(floor), int(gain), float(g),
+                                                          float(lam)), "hm_body_rec_event_stats_add")
+
+    def body_rec_event_sums(self, what, half, q, floor=1, gain=1, g=0.9, lam=0.0, s_min=1.0):
+        """hm_body_rec_event_sums: -> (count (H, W) uint32, sum (H, W) float64): per pixel the number of frames with
+        s >= s_min and the sum of s over the record (s as in body_rec_event_planes, before rounding)."""
+        what = self.PLANES[what] if isinstance(what, str) else int(what)
+        count, total = np.empty((self.ny, self.nx), np.uint32), np.empty((self.ny, self.nx), np.float64)
+        _lib.check(_lib.lib().hm_body_rec_event_sums(self._h, what, int(half), int(q), int(floor), int(gain), float(g), float(lam),
+                                                     float(s_min), _lib.ptr(count), _lib.ptr(total)), "hm_body_rec_event_sums")
+        return count, total
+
     # -- the residual of the record under a model of the cells (hm_body_rec_residual_*; hydra_mi.residual) -----
     def _residual_args(self, who, labels, weights, traces, blank):
         lab = np.ascontiguousarray(labels, np.int32)
@@ -830,7 +858,10 @@ class Renderer:
         return tok.fetch() if fetch else tok
 
     def tune(self, key, value):
-        _lib.check(_lib.lib().hm_ctx_tune(self._h, key.encode(), int(value)), "hm_ctx_tune")
+        if -2 ** 31 <= int(value) < 2 ** 31:
+            _lib.check(_lib.lib().hm_ctx_tune(self._h, key.encode(), int(value)), "hm_ctx_tune")
+        else:                                                    # ("rec_ev_bytes" reaches 2^34)
+            _lib.check(_lib.lib().hm_ctx_tune64(self._h, key.encode(), int(value)), "hm_ctx_tune")
 
     def project_mask(self, X, y_m=None):
         """KalmanFilter.projectmask (kalman.py:724-742) on the device -> (X projected, number of

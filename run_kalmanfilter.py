@@ -126,6 +126,19 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      float32): the share of those maxima that reach the pixel's rho, a p-value that holds for the whole
                      map at once; net_sig (bool): net_p_map <= --network-alpha (default 0.05); net_map_sig: net_map with
                      -1 where the winning ensemble's pixel is not significant.
+    --events         with --rois or --demix: the events behind the traces (hydra_mi.events), AR(1) deconvolution of the dF/F
+                     of --demix if on, else of --rois: c_k = g c_{k-1} + s_k with s >= 0, least squares with the penalty
+                     lambda on the events.  Per cell g from the trace's autocovariance (events.estimate_g), lambda and the
+                     least event that counts from its noise (events.noise, default_lam, default_smin), unless --events-g,
+                     --events-lambda, --events-smin fix them for all cells.  ev_g, ev_lambda (cells); ev_c, ev_s (cells x
+                     frames): the calcium and the events; ev_binary (bool): s >= s_min.  The same rule on every pixel of
+                     the dF/F bytes of the kept registered video, on the device, with one g (the median over the cells) and
+                     the cells' median lambda and s_min in bytes (x --dff-gain; s_min at least 1): ev_count_image (H x W,
+                     uint32: frames with an event >= s_min), ev_sum_image (H x W: the events summed, rounded to float32 here);
+                     ev_params: g, lambda, s_min of the pixels, then half, q, floor, gain of their dF/F bytes.  With
+                     --network also net_r_events: network.coactivity of ev_s, as net_r is of the traces.
+    --events-video OUT.avi   with --events: the event bytes min(255, floor(s + 0.5)) of every pixel and frame in the body
+                     frame, grey (hydra_mi.events.event_video), through the writer of --dff-video.
 """
 import argparse
 import os
@@ -140,6 +153,7 @@ from hydra_mi import network
 from hydra_mi import demix
 from hydra_mi import residual
 from hydra_mi import detrend
+from hydra_mi import events
 from hydra_mi import roi
 from hydra_mi import stabilize
 from hydra_mi import strain
@@ -230,6 +244,11 @@ def main(argv=None):
     parser.add_argument("--network-alpha", default=0.05, type=float, help="with --network-null: the level a pixel is significant at")
     parser.add_argument("--network-guard", default=network.DEFAULT_LAG, type=int, help="with --network-null: no shift within N frames of 0")
     parser.add_argument("--network-seed", default=0, type=int, help="with --network-null: the seed the shifts are drawn with")
+    parser.add_argument("--events", action="store_true", help="with --rois or --demix: events behind the dF/F traces and per pixel (ev_* arrays)")
+    parser.add_argument("--events-g", default=None, type=float, help="the decay per frame, 0 < g < 1 (default: estimated per cell)")
+    parser.add_argument("--events-lambda", default=None, type=float, help="the penalty on the events (default: from each cell's noise)")
+    parser.add_argument("--events-smin", default=None, type=float, help="the least event that counts (default: from each cell's noise)")
+    parser.add_argument("--events-video", default=None, metavar="OUT.avi", help="with --events: write the event video in the body frame here (.avi)")
     args = parser.parse_args(argv)
     if not 0 <= args.strain_alpha <= 255 or not np.isfinite(args.strain_gain):
         parser.error("the strain video needs a --strain-alpha in 0..255 and a finite --strain-gain")
@@ -262,6 +281,15 @@ def main(argv=None):
             parser.error("--demix-iters needs at least one round")
     if args.rois and args.find_points is None and args.points is None:
         parser.error("--rois reads cells out: it needs --find-points or --points")
+    if args.events and not args.rois:
+        parser.error("--events reads the cells' traces: it needs --rois or --demix")
+    if args.events_video is not None and not args.events:
+        parser.error("--events-video shows the events: it needs --events")
+    if args.events:
+        if args.events_g is not None and not 0.0 < args.events_g < 1.0:
+            parser.error("--events-g must lie inside 0 < g < 1")
+        if any(v is not None and not (np.isfinite(v) and v >= 0.0) for v in (args.events_lambda, args.events_smin)):
+            parser.error("--events-lambda and --events-smin must be finite and >= 0")
     if args.network and not args.rois:
         parser.error("--network reads the cells' traces: it needs --rois or --demix")
     if args.network_map is not None and not args.network:
@@ -277,7 +305,7 @@ def main(argv=None):
     if args.resummarize and (not args.stabilize or args.detrend):
         parser.error("--resummarize sums the stabilised record up: it needs --stabilize, and not --detrend")
     keep_record = args.detrend or args.resummarize or args.dff_video is not None
-    if keep_record and not (0 <= args.detrend_half <= 1024 and 0 <= args.detrend_q <= 100 and 1 <= args.dff_floor <= 255
+    if (keep_record or args.events) and not (0 <= args.detrend_half <= 1024 and 0 <= args.detrend_q <= 100 and 1 <= args.dff_floor <= 255
                             and 1 <= args.dff_gain <= 65535):
         parser.error("the running baseline needs a --detrend-half in 0..1024, a --detrend-q in 0..100, a --dff-floor in 1..255 "
                      "and a --dff-gain in 1..65535")
@@ -486,6 +514,29 @@ def main(argv=None):
                          roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
             print("ROIs: %d cells, %d..%d pixels, %d kept their disc" % (len(inside), e["roi_counts"].min(),
                                                                           e["roi_counts"].max(), e["seed_fallback"].sum()))
+            if args.events:                                        # (cell s: point inside[s], as the roi_* rows)
+                tr = np.ascontiguousarray((e["dff_demixed"] if args.demix else e["dff"]).T, np.float64)
+                fixed = lambda v, rule: np.full(len(tr), v, np.float64) if v is not None else np.array(rule, np.float64)
+                sig = [events.noise(x) for x in tr]
+                ev_g = fixed(args.events_g, [events.estimate_g(x) for x in tr])
+                ev_lam = fixed(args.events_lambda, [events.default_lam(g, sg) for g, sg in zip(ev_g, sig)])
+                ev_smin = fixed(args.events_smin, [events.default_smin(sg) for sg in sig])
+                ev_c, ev_s = events.deconvolve(tr, ev_g, ev_lam)
+                # every pixel of the dF/F bytes: one g, and the cells' median penalty and threshold in bytes
+                px = dict(what="dff", half=args.detrend_half, q=args.detrend_q, floor=args.dff_floor, gain=args.dff_gain)
+                g_px, lam_px = float(np.median(ev_g)), float(np.median(ev_lam)) * args.dff_gain
+                smin_px = max(1.0, float(np.median(ev_smin)) * args.dff_gain)
+                ev_n, ev_sum = events.count_image(body, g_px, lam_px, smin_px, **px)
+                extra.update(ev_g=ev_g, ev_lambda=ev_lam, ev_c=ev_c, ev_s=ev_s, ev_binary=events.binarise(ev_s, ev_smin),
+                             ev_count_image=ev_n, ev_sum_image=ev_sum.astype(np.float32),
+                             ev_params=np.array([g_px, lam_px, smin_px, px["half"], px["q"], px["floor"], px["gain"]], np.float64))
+                print("Events: %d cells, g %.3f..%.3f, %d events; per pixel g %.3f, lambda %.3g, s_min %.3g: %d events" % (
+                    len(tr), ev_g.min(), ev_g.max(), extra["ev_binary"].sum(), g_px, lam_px, smin_px, ev_n.sum()))
+                if args.network:
+                    extra.update(net_r_events=network.coactivity(ev_s, args.network_lag))
+                if args.events_video is not None:
+                    n_ev = events.event_video(body, args.events_video, g_px, lam_px, **px)
+                    print("Event video: %d frames in %s" % (n_ev, args.events_video))
             if args.network:                                       # (cell s: point inside[s], as the roi_* rows)
                 net = network.extract(body, (e["dff_demixed"] if args.demix else e["dff"]).T, thr=args.network_thr,
                                       max_lag=args.network_lag, map_thr=args.network_map_thr, null=args.network_null,
