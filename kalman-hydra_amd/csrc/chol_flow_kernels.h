@@ -47,16 +47,7 @@
 #define FLOW_SENTINEL 0x7FF8DEADBEEF0001ull       // a quiet NaN with a payload the hardware never generates
 #define FLOW_POLL_LIMIT 4000000                   // polls of one wait before it gives up (~seconds)
 
-struct FlowArgs {
-    const double *A;          // n x n matrix (+ right-hand-side rows up to nrows), read only
-    double *L;                // nrows x n: blocks below the block diagonal
-    double *Lt;               // nb x 32 x 32: T_c
-    double *Tinv;             // n x n: L^-1
-    double *P;                // 3 x nb x 32 x 32: block (c, c-1) before its triangular solve; Q_c; block (c, c-2) likewise (Y_c)
-    int n, nrows, nb, nbr;    // nbr: block rows including the right-hand-side rows
-    unsigned *ctl;            // [0] next task, [1] set when a wait timed out
-    int stall;                // test knob (hm_ctx_tune "chol_flow_stall"): the chain sleeps ~4 us x stall before every diagonal block
-};
+// (struct FlowArgs: hm_types.h -- smooth.hip fills one too)
 
 __device__ __forceinline__ unsigned long long flow_ld_bits(const double *p)
 {

@@ -1,11 +1,12 @@
 // The filter handle of libhydra_mi.so (hm_ctx) and the helpers every translation unit that works on one needs.  Private to
-// the library: ekf.hip (the filter, the smoother), readout.hip (views, body-frame readout, statistics) and record.hip (the
-// kept record) include it, all built by the one compiler command of the Makefile.  Everything defined here is static or a
-// template; the hidden functions declared at the end are defined once, in the translation unit named there.
+// the library: ekf.hip (the filter), smooth.hip (the smoother), readout.hip (views, body-frame readout, statistics) and
+// record.hip (the kept record) include it, all built by the one compiler command of the Makefile.  Everything defined here is
+// static or a template; the hidden functions declared at the end are defined once, in the translation unit named there.
 #pragma once
 #include "hm_common.h"
 #include "hm_types.h"
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -439,6 +440,40 @@ static inline int hm_labels_ok(const char *who, int n_layers, const int32_t *lab
     return HM_OK;
 }
 
+// The springs of every vertex (SpringTopo of k_fw_rows / k_pft_cols): off (N + 1) the CSR offsets, then per vertex its
+// springs in the order of `bars` -- bar: the spring's id, other: the vertex at its other end.  Vertex ids are checked by
+// the caller.  (Host arithmetic of the filter's prediction and of the smoother.)
+static inline void spring_csr(int N, int n_bars, const int32_t *bars, std::vector<int> &off, std::vector<int> &bar,
+                              std::vector<int> &other)
+{
+    off.assign(N + 1, 0);
+    for (int i = 0; i < n_bars; i++) {
+        off[bars[2 * i] + 1]++;
+        off[bars[2 * i + 1] + 1]++;
+    }
+    for (int v = 0; v < N; v++) off[v + 1] += off[v];
+    bar.resize(2 * (size_t)n_bars); other.resize(2 * (size_t)n_bars);
+    std::vector<int> fill(off.begin(), off.end() - 1);
+    for (int i = 0; i < n_bars; i++) {
+        const int p = bars[2 * i], q = bars[2 * i + 1];
+        bar[fill[p]] = i; other[fill[p]++] = q;
+        bar[fill[q]] = i; other[fill[q]++] = p;
+    }
+}
+
+// The per-spring blocks (Bxx, Bxy, Byy) of the force Jacobian at the vertices of X (kalman.py:892-901): bar i between
+// a and b, d = y_a - y_b, l = |d|:  B = k I + c d d^T,  k = kappa (1 - l0/l),  c = kappa l0 / l^3.
+static inline void spring_blocks(int n_bars, const int32_t *bars, const double *l0, double kappa, const double *X, double *blk)
+{
+    for (int i = 0; i < n_bars; i++) {
+        const int a = bars[2 * i], b = bars[2 * i + 1];
+        const double dx = X[2 * a] - X[2 * b], dy = X[2 * a + 1] - X[2 * b + 1];
+        const double l = std::sqrt(dx * dx + dy * dy);
+        const double k = kappa * (1.0 - l0[i] / l), c = kappa * l0[i] / (l * l * l);
+        blk[3 * i] = k + c * dx * dx; blk[3 * i + 1] = c * dx * dy; blk[3 * i + 2] = k + c * dy * dy;
+    }
+}
+
 // The filter's kernels that the readout launches (a view renders, the body map is a setup at X = uv).  Kernels are compiled
 // by one translation unit each (ekf_kernels.h: ekf.hip), so readout.hip queues them through these, defined in ekf.hip:
 // k_setup_all on T triangles of m at state X, and the full-frame render k_render<0> -- or k_render<1> with the label
@@ -446,6 +481,13 @@ static inline int hm_labels_ok(const char *who, int n_layers, const int32_t *lab
 __attribute__((visibility("hidden"))) void ekf_queue_setup_all(hipStream_t st, const Mesh &m, const double *d_X, TriSetup *d_setup);
 __attribute__((visibility("hidden"))) void ekf_queue_render(hipStream_t st, const Mesh &m, const double *d_X, const TriSetup *d_setup,
                                                             const Targets &out, const int *d_labels, int *d_ids);
+// The filter's launch sequences that the smoother repeats (dense_kernels.h, chol_flow_kernels.h: ekf.hip), both defined in
+// ekf.hip.  FP = F src by k_fw_rows, then dst = FP F^T + Weps by k_pft_cols, for the N vertices and springs tp.  The
+// factorisation of a.A as one persistent launch, k_chol_flow on wgs workgroups, behind k_flow_fill unless the caller's
+// own assembly pass has pre-filled its outputs (fill = false).
+__attribute__((visibility("hidden"))) void ekf_queue_fpft(hipStream_t st, const double *src, double *FP, double *dst, int N,
+                                                          const SpringTopo &tp, double a, double s, double eps_F);
+__attribute__((visibility("hidden"))) void ekf_queue_chol_flow(hipStream_t st, const FlowArgs &a, int wgs, bool fill);
 
 // What crosses between readout.hip (the warp, the statistics) and record.hip (the kept record), in the same way.  Defined in
 // readout.hip: the body map, built once per handle; k_body_stats_add queued on the registered plane d_reg, and the frame

@@ -17,7 +17,7 @@
 #include "ekf_kernels.h"      // d_tile_partial_sums (k_iter_result)
 #include "host_block.h"
 
-#define DNB 32          // block size
+// (DNB, the block size, d4_t, d_mfma_nn / d_mfma_tn and SpringTopo: hm_types.h -- smooth_kernels.h uses them too)
 #define TTT_PF 3        // block products whose operands are in flight (k_ttt)
 
 // 1/sqrt(d) from the hardware estimate (2^-24 relative) plus ONE third-order step, r (1 + e/2 + 3 e^2/8) with
@@ -68,7 +68,6 @@ __device__ __forceinline__ double d_readlane(double v, int lane)
 //       operand of row tile R is the very register that holds U for column tile R;
 //   rows j .. j+3 of T are final: U's T half.
 // 48 MFMAs and eight 4x4 factorisations instead of 32 column steps with 16 barriers: 3.5 us instead of 6.1.
-typedef double d4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ d4_t d_mfma4(double a, double b, d4_t c)
 {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -316,16 +315,6 @@ __device__ __forceinline__ d4_t d_mfma_nt(double (*X)[DNB + 1], double (*Y)[DNB 
     return c;
 }
 
-// the same for X Y
-__device__ __forceinline__ d4_t d_mfma_nn(double (*X)[DNB + 1], double (*Y)[DNB + 1], int wv, int lane, d4_t c)
-{
-    const int i = 16 * (wv >> 1) + (lane & 15), j = 16 * (wv & 1) + (lane & 15), kq = lane >> 4;
-#pragma unroll
-    for (int kk = 0; kk < DNB / 4; kk++)
-        c = __builtin_amdgcn_mfma_f64_16x16x4f64(X[i][4 * kk + kq], Y[4 * kk + kq][j], c, 0, 0, 0);
-    return c;
-}
-
 // the first diagonal block: the inverse of the factor of A_00 -> Lt[0]
 __global__ __launch_bounds__(64) void k_chol_first(const double *__restrict__ A, double *__restrict__ Lt, int n)
 {
@@ -517,15 +506,6 @@ __global__ __launch_bounds__(TV_COLS * TV_ROWS) void k_tvec(const double *__rest
 // term one 32x32x32 product on the f64 matrix cores.  The blocks come from memory written by other
 // XCDs (~1.7 us away), so three steps' worth of them are kept in flight in registers; LDS is double
 // buffered, one barrier per step.  Both mirror images are written (the host wants the full matrix).
-__device__ __forceinline__ d4_t d_mfma_tn(double (*X)[DNB + 1], double (*Y)[DNB + 1], int wv, int lane, d4_t c)
-{
-    const int i = 16 * (wv >> 1) + (lane & 15), j = 16 * (wv & 1) + (lane & 15), kq = lane >> 4;
-#pragma unroll
-    for (int kk = 0; kk < DNB / 4; kk++)
-        c = __builtin_amdgcn_mfma_f64_16x16x4f64(X[4 * kk + kq][i], Y[4 * kk + kq][j], c, 0, 0, 0);
-    return c;
-}
-
 __global__ __launch_bounds__(256) void k_ttt(const double *__restrict__ Tm, int n, double *__restrict__ W)
 {
     const int I = blockIdx.y, J = blockIdx.x;
@@ -708,13 +688,7 @@ __global__ __launch_bounds__(1024) void k_tail_result(const double *__restrict__
 // ---- covariance prediction W' = F W F^T + Weps on the device -------------------------------------------
 // F = [[I, a I], [A, I]] with A = s * dfdy, dfdy assembled from one symmetric 2x2 block per spring
 // (see predict.cpp): (dfdy M)[rows of vertex v] = - sum over springs (v,u) of B (M[rows v] - M[rows u]).
-// Weps = eps * [[I/4, I/2], [I/2, I]] (reference kalman.py:182).  n2 = 2N, n4 = 4N.
-struct SpringTopo {
-    const int *off;           // N+1: springs of each vertex
-    const int *bar;           // spring id
-    const int *other;         // the vertex at the other end
-    const double *blk;        // I x 3: Bxx, Bxy, Byy
-};
+// Weps = eps * [[I/4, I/2], [I/2, I]] (reference kalman.py:182).  n2 = 2N, n4 = 4N.  (SpringTopo: hm_types.h)
 
 // P = F W, one thread per (vertex, column)
 __global__ void k_fw_rows(const double *__restrict__ W, double *__restrict__ P, int N, SpringTopo tp, double a, double s)

@@ -1,13 +1,15 @@
 // EKF measurement model on MI355X: host orchestration and C-ABI (include/hydra_mi.h).
 // Replaces reference renderer.py (OpenGL rasteriser), cuda.py and cuda_multi.py
-// (reduction kernels + PBO plumbing).
+// (reduction kernels + PBO plumbing).  In this order: handle lifetime and tuning, render and measure, the dense update,
+// hm_update_run, covariance prediction, the Newton launches and the chained state path, mask projection.  The smoother
+// is in smooth.hip; it queues the two launch sequences it shares with the filter through ekf_queue_fpft and
+// ekf_queue_chol_flow, defined here (ctx.h).
 #include "ctx.h"
 #include "ekf_kernels.h"
 #include "dense_kernels.h"
 #include "chol_flow_kernels.h"
 #include "project_kernels.h"
 #include "predict_kernels.h"
-#include "smooth_kernels.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -283,90 +285,77 @@ extern "C" int hm_debug_stamps(void *dev_ptr)
 }
 #endif
 
+// The keys of hm_ctx_tune: a value is admitted when it is lo, lo + step, ... up to hi; `must` is the clause of the message
+// after "hm_ctx_tune: <key> " (NULL: "must be in lo..hi").
+#define TUNE_SET(field) [](hm_ctx *h, long long v) { h->field = (decltype(h->field))v; }
+static const struct TuneKey {
+    const char *key;
+    long long lo, hi;
+    int step;
+    void (*set)(hm_ctx *, long long);
+    const char *must;
+} tune_keys[] = {
+    {"measure_split", 1, MEAS_VSPLIT_MAX, 1, TUNE_SET(vsplit), nullptr},
+    {"edge_split", 1, MEAS_VSPLIT_MAX, 1, TUNE_SET(esplit), nullptr},
+    {"chol_flow", 0, 1, 1, TUNE_SET(chol_flow), "must be 0 (one launch per block step) or 1 (one persistent launch)"},
+    // at least two: the first workgroup becomes the chain of the diagonal blocks and waits for blocks that only the task
+    // workgroups produce
+    {"chol_flow_wgs", 2, 2048, 1, TUNE_SET(flow_wgs), "must be in 2..2048 (the chain workgroup and at least one task workgroup)"},
+    {"render_rows", 8, 16, 8, TUNE_SET(render_rows), "must be 8 or 16"},
+    {"chol_flow_stall", 0, 100000, 1, TUNE_SET(flow_stall), nullptr},          // tests only: results must not depend on it
+    {"result_delay", 0, 5000, 1, TUNE_SET(result_delay), "must be in 0..5000 (microseconds)"},   // tests only: likewise (host_block.h)
+    {"tail_async", 0, 1, 1, TUNE_SET(tail_async), "must be 0 or 1"},          // same results either way
+    {"tail_split", 0, 1, 1, TUNE_SET(tail_split), "must be 0 or 1"},          // same results either way
+    {"newton_fail", 0, 1, 1, TUNE_SET(newton_fail), "must be 0 or 1"},        // tests only: the device predictions report a failed inner solve
+    {"speculate", 0, 1, 1, TUNE_SET(speculate), "must be 0 or 1"},            // same results either way
+    {"body_stats_cap", 1, BODY_STATS_CAP, 1, TUNE_SET(body.stats_cap), nullptr},   // tests only: frames one hm_body_stats accumulation takes
+    {"body_rec_chunk", 0, INT32_MAX, 1, TUNE_SET(rec.chunk), "must be >= 0 (0: the default size)"},   // tests only: frames per chunk of the next hm_body_rec_begin
+    {"rec_tp_frames", 1, REC_TP_MAX, 1, TUNE_SET(rec.tp_frames), nullptr},     // frames per workgroup of hm_body_rec_trace_products
+    // frames per run of the running baseline, the residual planes, the trace maps, the surrogate reduction (same results for every value)
+    {"rec_bl_frames", 1, REC_BL_MAX, 1, TUNE_SET(rec.bl_frames), nullptr},
+    {"rec_res_frames", 1, REC_RES_MAX, 1, TUNE_SET(rec.res_frames), nullptr},
+    {"rec_map_frames", 1, REC_MAP_MAX, 1, TUNE_SET(rec.map_frames), nullptr},
+    {"rec_null_frames", 1, REC_NULL_MAX, 1, TUNE_SET(rec.null_frames), nullptr},
+    {"rec_scratch_bytes", 1, 1 << 30, 1, TUNE_SET(rec.scr_bytes), nullptr},    // tests only: the most scratch of a hm_body_rec_* call (same results for every value)
+    // the most bytes of the pool stack of a pass of hm_body_rec_event_* (same results for every value); past 2^31: hm_ctx_tune64
+    {"rec_ev_bytes", 1, 1ll << 34, 1, TUNE_SET(rec.ev_bytes), nullptr},
+};
+#undef TUNE_SET
+static const TuneKey *tune_find(const char *key)
+{
+    for (const TuneKey &k : tune_keys)
+        if (!strcmp(key, k.key)) return &k;
+    return nullptr;
+}
+// both entry points end here (the handle joined)
+static int tune_set(hm_ctx *h, const char *key, long long value)
+{
+    const TuneKey *k = tune_find(key);
+    HM_ARG(k != nullptr, "hm_ctx_tune: unknown key '%s'", key);
+    if (value < k->lo || value > k->hi || (value - k->lo) % k->step) {
+        if (k->must) hm_set_error("hm_ctx_tune: %s %s", key, k->must);
+        else hm_set_error("hm_ctx_tune: %s must be in %lld..%lld", key, k->lo, k->hi);
+        return HM_ERR_ARG;
+    }
+    k->set(h, value);
+    return HM_OK;
+}
+
 extern "C" int hm_ctx_tune(hm_ctx_t h, const char *key, int value)
 {
     HM_ARG(h != nullptr && key != nullptr, "hm_ctx_tune: NULL argument");
     HM_JOIN(h);
-    if (!strcmp(key, "measure_split")) {
-        HM_ARG(value >= 1 && value <= MEAS_VSPLIT_MAX, "hm_ctx_tune: measure_split must be in 1..%d", MEAS_VSPLIT_MAX);
-        h->vsplit = value;
-    } else if (!strcmp(key, "chol_flow")) {
-        HM_ARG(value == 0 || value == 1, "hm_ctx_tune: chol_flow must be 0 (one launch per block step) or 1 (one persistent launch)");
-        h->chol_flow = value;
-    } else if (!strcmp(key, "chol_flow_wgs")) {
-        // at least two: the first workgroup becomes the chain of the diagonal blocks and waits for blocks that only
-        // the task workgroups produce
-        HM_ARG(value >= 2 && value <= 2048, "hm_ctx_tune: chol_flow_wgs must be in 2..2048 (the chain workgroup and at least one task workgroup)");
-        h->flow_wgs = value;
-    } else if (!strcmp(key, "render_rows")) {
-        HM_ARG(value == 8 || value == 16, "hm_ctx_tune: render_rows must be 8 or 16");
-        h->render_rows = value;
-    } else if (!strcmp(key, "chol_flow_stall")) {      // tests only: results must not depend on it
-        HM_ARG(value >= 0 && value <= 100000, "hm_ctx_tune: chol_flow_stall must be in 0..100000");
-        h->flow_stall = value;
-    } else if (!strcmp(key, "result_delay")) {         // tests only: results must not depend on it (host_block.h)
-        HM_ARG(value >= 0 && value <= 5000, "hm_ctx_tune: result_delay must be in 0..5000 (microseconds)");
-        h->result_delay = value;
-    } else if (!strcmp(key, "tail_async")) {           // same results either way
-        HM_ARG(value == 0 || value == 1, "hm_ctx_tune: tail_async must be 0 or 1");
-        h->tail_async = value;
-    } else if (!strcmp(key, "tail_split")) {           // same results either way
-        HM_ARG(value == 0 || value == 1, "hm_ctx_tune: tail_split must be 0 or 1");
-        h->tail_split = value;
-    } else if (!strcmp(key, "newton_fail")) {          // tests only: the device predictions report a failed inner solve
-        HM_ARG(value == 0 || value == 1, "hm_ctx_tune: newton_fail must be 0 or 1");
-        h->newton_fail = value;
-    } else if (!strcmp(key, "speculate")) {            // same results either way
-        HM_ARG(value == 0 || value == 1, "hm_ctx_tune: speculate must be 0 or 1");
-        h->speculate = value;
-    } else if (!strcmp(key, "edge_split")) {
-        HM_ARG(value >= 1 && value <= MEAS_VSPLIT_MAX, "hm_ctx_tune: edge_split must be in 1..%d", MEAS_VSPLIT_MAX);
-        h->esplit = value;
-    } else if (!strcmp(key, "body_stats_cap")) {       // tests only: frames one hm_body_stats accumulation takes
-        HM_ARG(value >= 1 && value <= BODY_STATS_CAP, "hm_ctx_tune: body_stats_cap must be in 1..%d", BODY_STATS_CAP);
-        h->body.stats_cap = value;
-    } else if (!strcmp(key, "body_rec_chunk")) {       // tests only: frames per chunk of the next hm_body_rec_begin
-        HM_ARG(value >= 0, "hm_ctx_tune: body_rec_chunk must be >= 0 (0: the default size)");
-        h->rec.chunk = value;
-    } else if (!strcmp(key, "rec_tp_frames")) {        // frames per workgroup of hm_body_rec_trace_products
-        HM_ARG(value >= 1 && value <= REC_TP_MAX, "hm_ctx_tune: rec_tp_frames must be in 1..%d", REC_TP_MAX);
-        h->rec.tp_frames = value;
-    } else if (!strcmp(key, "rec_bl_frames")) {        // frames per run of the running baseline (same results for every value)
-        HM_ARG(value >= 1 && value <= REC_BL_MAX, "hm_ctx_tune: rec_bl_frames must be in 1..%d", REC_BL_MAX);
-        h->rec.bl_frames = value;
-    } else if (!strcmp(key, "rec_res_frames")) {       // frames per run of the residual planes (same results for every value)
-        HM_ARG(value >= 1 && value <= REC_RES_MAX, "hm_ctx_tune: rec_res_frames must be in 1..%d", REC_RES_MAX);
-        h->rec.res_frames = value;
-    } else if (!strcmp(key, "rec_map_frames")) {       // frames per run of the trace maps (same results for every value)
-        HM_ARG(value >= 1 && value <= REC_MAP_MAX, "hm_ctx_tune: rec_map_frames must be in 1..%d", REC_MAP_MAX);
-        h->rec.map_frames = value;
-    } else if (!strcmp(key, "rec_null_frames")) {      // frames per run of the surrogate reduction (same results for every value)
-        HM_ARG(value >= 1 && value <= REC_NULL_MAX, "hm_ctx_tune: rec_null_frames must be in 1..%d", REC_NULL_MAX);
-        h->rec.null_frames = value;
-    } else if (!strcmp(key, "rec_scratch_bytes")) {    // tests only: the most scratch of a hm_body_rec_* call (same results for every value)
-        HM_ARG(value >= 1 && value <= (1 << 30), "hm_ctx_tune: rec_scratch_bytes must be in 1..%d", 1 << 30);
-        h->rec.scr_bytes = (size_t)value;
-    } else if (!strcmp(key, "rec_ev_bytes")) {         // the most bytes of the pool stack of a pass of hm_body_rec_event_* (same results for every value)
-        HM_ARG(value >= 1, "hm_ctx_tune: rec_ev_bytes must be in 1..%lld", 1ll << 34);
-        h->rec.ev_bytes = (size_t)value;
-    } else {
-        hm_set_error("hm_ctx_tune: unknown key '%s'", key);
-        return HM_ERR_ARG;
-    }
-    return HM_OK;
+    return tune_set(h, key, value);
 }
 // the keys whose values pass 2^31 ("rec_ev_bytes"); every other key as hm_ctx_tune takes it
 extern "C" int hm_ctx_tune64(hm_ctx_t h, const char *key, int64_t value)
 {
     HM_ARG(h != nullptr && key != nullptr, "hm_ctx_tune: NULL argument");
-    if (!strcmp(key, "rec_ev_bytes")) {
-        HM_JOIN(h);
-        HM_ARG(value >= 1 && value <= (1ll << 34), "hm_ctx_tune: rec_ev_bytes must be in 1..%lld", 1ll << 34);
-        h->rec.ev_bytes = (size_t)value;
-        return HM_OK;
-    }
-    HM_ARG(value >= INT32_MIN && value <= INT32_MAX, "hm_ctx_tune: %s = %lld does not fit 32 bits", key, (long long)value);
-    return hm_ctx_tune(h, key, (int)value);
+    const TuneKey *k = tune_find(key);
+    if (!k || k->hi <= INT32_MAX)
+        HM_ARG(value >= INT32_MIN && value <= INT32_MAX, "hm_ctx_tune: %s = %lld does not fit 32 bits", key, (long long)value);
+    HM_JOIN(h);
+    return tune_set(h, key, value);
 }
 extern "C" void *hm_ctx_stream(hm_ctx_t h)
 {
@@ -475,13 +464,11 @@ extern "C" int hm_set_observation(hm_ctx_t h, const uint8_t *y_im, const float *
     HM_HIP(hipMemcpyAsync(h->d_yfx, y_fx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HM_HIP(hipMemcpyAsync(h->d_yfy, y_fy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     h->o_yim = h->d_yim; h->o_ym = h->d_ym; h->o_yfx = h->d_yfx; h->o_yfy = h->d_yfy;
-    int rc = finish_observation(h);
-    if (rc) return rc;
+    HM_TRY(finish_observation(h));
     HM_HIP(hipStreamSynchronize(h->stream));
     h->outline_ready = false;
     if (h->d_outline) {              // a tracker that projects onto the mask: its outline, ahead of hm_project_mask
-        rc = queue_outline(h, h->o_ym);
-        if (rc) return rc;
+        HM_TRY(queue_outline(h, h->o_ym));
         h->outline_ready = true;
     }
     return HM_OK;
@@ -494,14 +481,12 @@ extern "C" int hm_set_observation_dev(hm_ctx_t h, const uint8_t *d_y_im, const f
     HM_JOIN_LAZY(h);
     HM_HIP(hipSetDevice(h->device));
     h->o_yim = d_y_im; h->o_ym = d_y_m; h->o_yfx = d_y_fx; h->o_yfy = d_y_fy;
-    int rc = finish_observation(h);
-    if (rc) return rc;
+    HM_TRY(finish_observation(h));
     h->outline_ready = false;
     if (h->d_outline && h->prepared_mask == d_y_m) {      // hm_prepare_mask queued the outline of exactly this mask ahead
         h->outline_ready = true;
     } else if (h->d_outline) {       // as in hm_set_observation: the caller's mask is complete in device memory by contract
-        rc = queue_outline(h, h->o_ym);
-        if (rc) return rc;
+        HM_TRY(queue_outline(h, h->o_ym));
         h->outline_ready = true;
     }
     h->prepared_mask = nullptr;
@@ -584,8 +569,7 @@ extern "C" int hm_render(hm_ctx_t h, const double *X, uint8_t *im, float *fx, fl
     HM_JOIN(h);
     NEED_TEX(h, "hm_render");
     HM_HIP(hipSetDevice(h->device));
-    int rc = render_into(h, X, h->P);
-    if (rc) return rc;
+    HM_TRY(render_into(h, X, h->P));
     const int n = h->W * h->H;
     hipLaunchKernelGGL(k_resolve, dim3(hm_cdiv(n, 256)), dim3(256), 0, h->stream, h->P, h->d_im8, h->d_m8, n);
     if (im) HM_HIP(hipMemcpyAsync(im, h->d_im8, n, hipMemcpyDeviceToHost, h->stream));
@@ -610,8 +594,7 @@ extern "C" int hm_initjacobian(hm_ctx_t h, const double *X, int masked)
     NEED_TEX(h, "hm_initjacobian");
     NEED_OBS(h, "hm_initjacobian");
     HM_HIP(hipSetDevice(h->device));
-    int rc = render_into(h, X, h->ref);
-    if (rc) return rc;
+    HM_TRY(render_into(h, X, h->ref));
     HM_HIP(hipStreamSynchronize(h->stream));
     h->X0.assign(X, X + 4 * h->N);
     h->have_ref = true;
@@ -636,13 +619,11 @@ extern "C" int hm_jz(hm_ctx_t h, const double *Xp, int masked, double *jz, doubl
     HM_JOIN(h);
     NEED_REF(h, "hm_jz");
     HM_HIP(hipSetDevice(h->device));
-    int rc = render_into(h, Xp, h->P);
-    if (rc) return rc;
+    HM_TRY(render_into(h, Xp, h->P));
     hipLaunchKernelGGL(k_jz, dim3(h->red_blocks), dim3(RED_NT), 0, h->stream, h->ref, h->P, obs_of(h, masked),
                        h->W * h->H, h->d_partial);
     double s[4];
-    rc = collect4(h, s);
-    if (rc) return rc;
+    HM_TRY(collect4(h, s));
     double c[4] = {s[0] / h->eps_Z, s[1] / h->eps_J, -s[2] / h->eps_J, s[3] / h->eps_M};
     if (jzc) for (int k = 0; k < 4; k++) jzc[k] = c[k];
     if (jz) *jz = ((c[0] + c[1]) + c[2]) + c[3];
@@ -659,16 +640,13 @@ extern "C" int hm_j(hm_ctx_t h, const double *X, double deltaX, int i, int j, do
     std::vector<double> Xp(X, X + 4 * h->N), Xq(X, X + 4 * h->N);
     Xp[i] += deltaX;
     Xq[j] += deltaX;
-    int rc = render_into(h, Xp.data(), h->P);
-    if (rc) return rc;
+    HM_TRY(render_into(h, Xp.data(), h->P));
     HM_HIP(hipStreamSynchronize(h->stream));     // d_X is reused by the second render
-    rc = render_into(h, Xq.data(), h->Q);
-    if (rc) return rc;
+    HM_TRY(render_into(h, Xq.data(), h->Q));
     hipLaunchKernelGGL(k_j, dim3(h->red_blocks), dim3(RED_NT), 0, h->stream, h->ref, h->P, h->Q, h->W * h->H,
                        h->d_partial);
     double s[4];
-    rc = collect4(h, s);
-    if (rc) return rc;
+    HM_TRY(collect4(h, s));
     *out = ((s[0] / h->eps_Z + s[1] / h->eps_J) + s[2] / h->eps_J) + s[3] / h->eps_M;
     return HM_OK;
 }
@@ -732,9 +710,8 @@ extern "C" int hm_jz_multi(hm_ctx_t h, const double *Xp, int masked, const int32
     NEED_REF(h, "hm_jz_multi");
     HM_HIP(hipSetDevice(h->device));
     const double *states[2] = {h->X0.data(), Xp};
-    int rc = multi_setup(h, labels, n_labels, states, 2);
-    if (rc) return rc;
-    rc = render_ids(h, h->X0.data(), h->ref, h->d_ids[0], true);               // the reference render's ids (its targets stand)
+    HM_TRY(multi_setup(h, labels, n_labels, states, 2));
+    int rc = render_ids(h, h->X0.data(), h->ref, h->d_ids[0], true);               // the reference render's ids (its targets stand)
     if (rc == HM_OK) rc = render_ids(h, Xp, h->P, h->d_ids[1], false);
     if (rc) return rc;
     MultiArgs a = {h->ref, h->P, h->P, h->d_ids[0], h->d_ids[1], h->d_ids[1], obs_of(h, masked), h->W, h->d_lbox, h->d_lout};
@@ -767,9 +744,8 @@ extern "C" int hm_j_multi(hm_ctx_t h, const double *X, double deltaX, int n_pair
         Xq[ee[2 * k + 1]] += deltaX;                                        // all second indices at once (:1004-1007)
     }
     const double *states[3] = {h->X0.data(), Xp.data(), Xq.data()};
-    int rc = multi_setup(h, labels, n_labels, states, 3);
-    if (rc) return rc;
-    rc = render_ids(h, h->X0.data(), h->ref, h->d_ids[0], true);
+    HM_TRY(multi_setup(h, labels, n_labels, states, 3));
+    int rc = render_ids(h, h->X0.data(), h->ref, h->d_ids[0], true);
     if (rc == HM_OK) rc = render_ids(h, Xp.data(), h->P, h->d_ids[1], false);
     if (rc == HM_OK) rc = render_ids(h, Xq.data(), h->Q, h->d_ids[2], false);
     if (rc) return rc;
@@ -799,8 +775,7 @@ extern "C" int hm_error(hm_ctx_t h, const double *X, int masked, double err[4], 
     // the launch and the order of additions of the update loop (k_render_iter, strip partials in the fixed two-level
     // order): the error of a state is the same number whether an iteration of hm_update_run reports it or this call
     HM_HIP(hipMemcpyAsync(h->d_X, X, (size_t)4 * h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    int rc = render_iter(h, h->d_X, h->P, true, masked, false, 2.0);
-    if (rc) return rc;
+    HM_TRY(render_iter(h, h->d_X, h->P, true, masked, false, 2.0));
     const int n = h->W * h->H;
     if (fx) HM_HIP(hipMemcpyAsync(fx, h->P.fx, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (fy) HM_HIP(hipMemcpyAsync(fy, h->P.fy, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -820,8 +795,7 @@ static int measure_dev(hm_ctx *h, const double *dX, bool ref_ready, double delta
                        bool scatter = true)
 {
     if (!ref_ready) {                             // the reference render, and the star regions with it when they are wanted too
-        int rc = render_iter(h, dX, h->ref, false, masked, !regions_ready, deltaX);
-        if (rc) return rc;
+        HM_TRY(render_iter(h, dX, h->ref, false, masked, !regions_ready, deltaX));
         regions_ready = true;
     }
     MeasureArgs a;
@@ -878,8 +852,7 @@ extern "C" int hm_measure(hm_ctx_t h, const double *X, double deltaX, int masked
     const size_t n4 = (size_t)4 * h->N;
     int *ovf = h->pin_scratch;
     for (int attempt = 0;; attempt++) {              // (once more after the pool has been grown)
-        int rc = measure_on_device(h, X, deltaX, masked);
-        if (rc) return rc;
+        HM_TRY(measure_on_device(h, X, deltaX, masked));
         // the flag lands in the handle's pinned block, not in this frame: an error return below must not leave a
         // copy in flight towards a dead stack slot
         *ovf = 0;
@@ -887,8 +860,7 @@ extern "C" int hm_measure(hm_ctx_t h, const double *X, double deltaX, int masked
         HM_HIP(hipStreamSynchronize(h->stream));
         if (!*ovf) break;
         if (attempt) { hm_set_error("hm_measure: the star regions do not fit the difference-image pool"); return HM_ERR_STATE; }
-        rc = pool_grow(h, "hm_measure");
-        if (rc) return rc;
+        HM_TRY(pool_grow(h, "hm_measure"));
     }
     HM_HIP(hipMemcpyAsync(Hz, h->d_Hz, n4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (Hzc) HM_HIP(hipMemcpyAsync(Hzc, h->d_Hzc, n4 * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -917,9 +889,7 @@ static void chol_factor(hm_ctx *h, double *A, double *L, double *Lt, double *T, 
         // one persistent launch: the block operations below as tasks that hand their results over through memory
         // (chol_flow_kernels.h); the same bits as the launch-per-step form.  first_done: the caller's assembly pass
         // (k_assemble_flow) has pre-filled the outputs
-        FlowArgs a = {A, L, Lt, T, h->d_flowP, n, nrows, nb, nbr, h->d_flowctl, h->flow_stall};
-        if (!first_done) hipLaunchKernelGGL(k_flow_fill, dim3(nrows + FLOW_FILL_WGS), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_chol_flow, dim3(h->flow_wgs), dim3(FLOW_NT), 0, st, a);
+        ekf_queue_chol_flow(st, FlowArgs{A, L, Lt, T, h->d_flowP, n, nrows, nb, nbr, h->d_flowctl, h->flow_stall}, h->flow_wgs, !first_done);
         return;
     }
     if (!first_done) hipLaunchKernelGGL(k_chol_first, dim3(1), dim3(64), 0, st, A, Lt, n);
@@ -1065,12 +1035,8 @@ static int update_begin(hm_ctx *h, const double *W_prior, const double *X0)
     h->pq_valid = false;                         // (a prediction queued ahead that nobody took: d_Wres is still the posterior)
     const bool taken = h->prefactored && !W_prior && h->d_Wres == h->d_Wprior;
     if (!taken) {
-        int rc = ctx_join(h);                    // (the tail of the last update is rewriting what prior_inverse rewrites)
-        if (rc) return rc;
-    }
-    if (!taken) {
-        int rc = prior_inverse(h, W_prior);
-        if (rc) return rc;
+        HM_TRY(ctx_join(h));                     // (the tail of the last update is rewriting what prior_inverse rewrites)
+        HM_TRY(prior_inverse(h, W_prior));
     }
     h->prefactored = false;
     if (X0) {
@@ -1098,8 +1064,7 @@ extern "C" int hm_update_step(hm_ctx_t h, const double *X, double deltaX, int ma
     int rc = HM_OK;
     const int slot = h->upd_last == 0 ? 1 : 0;
     for (int attempt = 0;; attempt++) {              // (once more after the pool of difference images has been grown)
-    rc = measure_on_device(h, X, deltaX, masked, false);   // leaves X in d_X; the job sums go straight into the system
-    if (rc) return rc;
+    HM_TRY(measure_on_device(h, X, deltaX, masked, false));   // leaves X in d_X; the job sums go straight into the system
     double *rhs_row = solve_step(h, slot, deltaX);
     HM_HIP(hipGetLastError());
     HM_HIP(hipMemcpyAsync(step, rhs_row, (size_t)n4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1123,11 +1088,9 @@ extern "C" int hm_update_step(hm_ctx_t h, const double *X, double deltaX, int ma
     }
     if (!*ovf) break;
     if (attempt) { hm_set_error("hm_update_step: the star regions do not fit the difference-image pool"); return HM_ERR_STATE; }
-    rc = pool_grow(h, "hm_update_step");
-    if (rc) return rc;
+    HM_TRY(pool_grow(h, "hm_update_step"));
     }
-    rc = flow_status(h, "hm_update_step");
-    if (rc) return rc;
+    HM_TRY(flow_status(h, "hm_update_step"));
     h->upd_prev = h->upd_last;
     h->upd_last = slot;
     return HM_OK;
@@ -1179,10 +1142,8 @@ extern "C" int hm_project_mask(hm_ctx_t h, const uint8_t *y_m, double *X, int *m
     // needs the mask and the predicted state only, and in a frame of the filter it comes while the covariance half of
     // the update (hm_update_prefactor: ~0.25 ms of launches) is still being queued and run on the first stream --
     // behind those it would have its caller wait for them.
-    int rc = ensure_stream2(h);
-    if (rc) return rc;
-    rc = project_buffers(h);
-    if (rc) return rc;
+    HM_TRY(ensure_stream2(h));
+    HM_TRY(project_buffers(h));
     hipStream_t s = h->stream2;
     const size_t n = (size_t)h->W * h->H;
     const size_t n4 = (size_t)4 * h->N, xb = n4 * sizeof(double);
@@ -1192,8 +1153,7 @@ extern "C" int hm_project_mask(hm_ctx_t h, const uint8_t *y_m, double *X, int *m
         // first time); the state goes through page-locked memory both ways, the result as a block the host takes when
         // it is whole (host_block.h) -- one launch and no copy operations on the way (0.15 -> ~0.03 ms per frame of the streaming pipeline).
         if (!h->outline_ready) {
-            rc = queue_outline(h, h->o_ym);
-            if (rc) return rc;
+            HM_TRY(queue_outline(h, h->o_ym));
             h->outline_ready = true;
         }
         memcpy(h->pin_pm, X, xb);
@@ -1201,8 +1161,7 @@ extern "C" int hm_project_mask(hm_ctx_t h, const uint8_t *y_m, double *X, int *m
         hipLaunchKernelGGL(k_project_mask_host, dim3(h->N), dim3(PROJ_NT), 0, s, a, (const double *)h->pin_pm, h->pin_pm + n4, (double *)nullptr,
                            (double *)nullptr, h->d_pm_done, (double)(++h->pm_ticket), h->result_delay);
         HM_HIP(hipGetLastError());
-        rc = hb_wait(s, h->pin_pm + n4, 0, n4 + 1, hb_stamp(h->pm_ticket), h->pmv.data(), "hm_project_mask");
-        if (rc) return rc;
+        HM_TRY(hb_wait(s, h->pin_pm + n4, 0, n4 + 1, hb_stamp(h->pm_ticket), h->pmv.data(), "hm_project_mask"));
         const int nmoved = (int)h->pmv[n4];
         if (nmoved) memcpy(X, h->pmv.data(), xb);
         if (moved) *moved = nmoved;
@@ -1212,8 +1171,7 @@ extern "C" int hm_project_mask(hm_ctx_t h, const uint8_t *y_m, double *X, int *m
     HM_HIP(h->own.alloc(&h->d_pm_mask, n));
     HM_HIP(hipMemcpyAsync(h->d_pm_mask, y_m, n, hipMemcpyHostToDevice, s));
     const uint8_t *mask = h->d_pm_mask;
-    rc = queue_outline(h, mask);
-    if (rc) return rc;
+    HM_TRY(queue_outline(h, mask));
     HM_HIP(hipMemcpyAsync(h->d_pm_X, X, xb, hipMemcpyHostToDevice, s));
     ProjArgs a = {h->d_pm_pruned, h->W, h->H, h->N, o, h->d_pm_X};
     hipLaunchKernelGGL(k_project_mask, dim3(h->N), dim3(PROJ_NT), 0, s, a);
@@ -1234,16 +1192,13 @@ extern "C" int hm_prune_mask(hm_ctx_t h, const uint8_t *y_m, uint8_t *out)
     HM_ARG(h && y_m && out, "hm_prune_mask: NULL argument");
     HM_JOIN_LAZY(h);
     HM_HIP(hipSetDevice(h->device));
-    int rc = ensure_stream2(h);
-    if (rc) return rc;
-    rc = project_buffers(h);
-    if (rc) return rc;
+    HM_TRY(ensure_stream2(h));
+    HM_TRY(project_buffers(h));
     const size_t n = (size_t)h->W * h->H;
     h->outline_ready = false;                    // the buffers are about to hold the outline of the caller's mask
     HM_HIP(h->own.alloc(&h->d_pm_mask, n));
     HM_HIP(hipMemcpyAsync(h->d_pm_mask, y_m, n, hipMemcpyHostToDevice, h->stream2));
-    rc = queue_outline(h, h->d_pm_mask);
-    if (rc) return rc;
+    HM_TRY(queue_outline(h, h->d_pm_mask));
     HM_HIP(hipMemcpyAsync(out, h->d_pm_pruned, n, hipMemcpyDeviceToHost, h->stream2));
     HM_HIP(hipStreamSynchronize(h->stream2));
     return HM_OK;
@@ -1323,8 +1278,7 @@ extern "C" int hm_update_tail(hm_ctx_t h, double *Hzc, double *gains)
     const size_t n4 = (size_t)4 * h->N;
     if (h->tail_pending) {
         HM_HIP(hipSetDevice(h->device));
-        const int rc = hb_wait(h->tail_stream, h->pin + 2 * (n4 + RES_HEAD), 0, n4 * 7, hb_stamp(h->tail_ticket), h->tailv.data(), "hm_update_tail");
-        if (rc) return rc;
+        HM_TRY(hb_wait(h->tail_stream, h->pin + 2 * (n4 + RES_HEAD), 0, n4 * 7, hb_stamp(h->tail_ticket), h->tailv.data(), "hm_update_tail"));
         h->tail_pending = false;
     }
     if (Hzc) memcpy(Hzc, h->tailv.data(), n4 * 4 * sizeof(double));
@@ -1332,320 +1286,445 @@ extern "C" int hm_update_tail(hm_ctx_t h, double *Hzc, double *gains)
     return HM_OK;
 }
 
-extern "C" int hm_update_run(hm_ctx_t h, const double *W_prior, double *X, double deltaX, int masked, int max_iter,
-                             double reltol, int info[4], double *errs, double *Hzc, double *gains, double *W_out)
+// ---- hm_update_run: the state of one call, its phases, the driver ---------------------------------------------------------
+struct UpdateArgs {
+    const double *W_prior;
+    double *X;
+    double deltaX;
+    int masked, max_iter;
+    double reltol;
+    double *errs, *Hzc, *gains, *W_out;
+};
+struct UpdateRun {
+    hm_ctx *const h;
+    const UpdateArgs a;
+    // What hm_update_arm_newton / _arm_cov / _arm_mask armed is for THIS call only: taken out of the handle before anything
+    // can fail (constructing this is the first thing hm_update_run does with a handle that is not NULL), so that an error
+    // return never leaves a worker pointer or a mask address behind for a later call to start a job on (the helper thread
+    // joined in update_enter touches none of these fields).
+    const Armed armed;
+    const uint8_t *next_mask;        // the armed mask as long as its outline is still to be queued
+    const int n4;
+    // hm_chain_project: the prior mean is being left in d_X0 by the kernels of the state path, X is output only; collected:
+    // the host has what those kernels report (chain_collect) -- X0 / Xcur / Xold are empty until then
+    bool chained = false, collected = false;
+    std::vector<double> X0, Xcur, Xold;          // the prior mean, the iterate, the last iterate that was accepted
+    int niter = 0, accepted = 0;
+    bool reverted = false, conv = false;
+    bool ref_ready = false;          // h->ref holds the render of the iterate in d_X
+    bool regions_ahead = false;      // the iteration in flight has the star regions of the next measurement computed with its render
+    // The measurement at the new iterate has been queued already -- behind k_iter_result, before the host has seen that
+    // iteration's result, on the assumption that the loop goes on (it does 7 times out of 8): the device goes from one
+    // iteration into the next without the ~14 us it takes the host to notice the result block, decide and launch.  ref / P
+    // and d_X / d_Xn are swapped when it is queued (SpecSwap); an iteration that turns out to be the last swaps them back
+    // (the wasted measurement only wrote job sums and parked differences nobody reads, and the launches behind it on this
+    // stream -- the covariance of the kept state -- are not what the next frame waits for).
+    bool measured_ahead = false;
+    bool grown = false;              // the pool has been grown for the iteration in flight: it does not overflow twice
+    double eold = 0.0;
+    int slot = 0;                    // the factor slot of the iteration in flight
+    // HYDRA_MI_TRACE, read once per call (update_enter); the stage clock (ms since update_enter had the handle to itself),
+    // the moment an iteration's launches were queued
+    bool dbg = false;
+    std::chrono::steady_clock::time_point t_enter, t_queued;
+    double stage[5] = {0, 0, 0, 0, 0};
+
+    UpdateRun(hm_ctx *h, const UpdateArgs &a)
+        : h(h), a(a), armed(std::exchange(h->armed, {})), next_mask(armed.mask), n4(4 * h->N) {}
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count(); }
+    const double *res() const { return h->resv.data(); }      // this call's copy of an iteration's block, taken when whole
+    double *pin_tail() const { return h->pin + 2 * ((size_t)n4 + RES_HEAD); }
+};
+
+// ref / P and d_X / d_Xn of the handle swapped for the length of one iteration: set() when the next measurement is queued
+// ahead, keep() when the iteration ends in "go on with the next one" -- the new iterate becomes the point of the next
+// measurement and its render is already there: swapped once, now or by set(), and left so.  Every other way out of the
+// iteration -- converged, reverted, an overflow (undo(), before anything else is queued), any error return -- puts them back.
+struct SpecSwap {
+    hm_ctx *const h;
+    bool swapped = false;
+    explicit SpecSwap(hm_ctx *h) : h(h) {}
+    SpecSwap(const SpecSwap &) = delete;
+    SpecSwap &operator=(const SpecSwap &) = delete;
+    ~SpecSwap() { undo(); }
+    void flip() { std::swap(h->ref, h->P); std::swap(h->d_X, h->d_Xn); }
+    void set() { flip(); swapped = true; }
+    void undo() { if (swapped) flip(); swapped = false; }
+    void keep() { if (!swapped) flip(); swapped = false; }
+};
+
+// chained: what the prediction's and the projection's kernels report (host_block.h), waited for on the host while the
+// first iteration runs; leaves X0 / Xcur / Xold and the handle's copies of them.  2: the prediction's inner solve gave up
+// (never observed) -- the caller predicts on the host and calls again.
+static int chain_collect(UpdateRun &u)
 {
-    HM_ARG(h && X && info, "hm_update_run: NULL argument");
-    // what hm_update_arm_newton / _arm_cov / _arm_mask armed is for THIS call only: taken out of the handle before anything
-    // can fail, so that an error return never leaves a worker pointer or a mask address behind for a later call to start a
-    // job on (the helper thread joined below touches none of these fields), and the tail block of the last update stops
-    // being handed out
-    const Armed armed = std::exchange(h->armed, {});
-    const bool pn_go = armed.newton;
-    void *const pn_worker = armed.worker;
-    const bool pq_go = armed.cov && pn_go;
-    const uint8_t *next_mask = armed.mask;
+    hm_ctx *h = u.h;
+    const int n4 = u.n4;
+    int r = hb_wait(h->stream3, h->pin_n4 + n4, 0, (size_t)n4 + 2, hb_stamp(h->n4_ticket), h->n4v.data(), "hm_update_run (state prediction)");
+    h->n4_pending = false;
+    if (r) return r;
+    HM_TRY(hb_wait(h->stream3, h->pin_pm + n4, 0, (size_t)n4 + 1, hb_stamp(h->pm_ticket), h->pmv.data(), "hm_update_run (projectmask)"));
+    h->chain_pred.assign(h->n4v.begin(), h->n4v.begin() + n4);
+    h->chain_proj.assign(h->pmv.begin(), h->pmv.begin() + n4);
+    h->chain_its = (int)h->n4v[n4];
+    h->chain_moved = (int)h->pmv[n4];
+    if (h->n4v[n4 + 1] != 0.0) return 2;
+    u.X0 = h->chain_proj; u.Xcur = u.X0; u.Xold = u.X0;
+    h->upd_X0 = u.X0;
+    h->X0 = u.X0;
+    u.collected = true;
+    return HM_OK;
+}
+
+// Entry (u.armed is out of the handle already).  Stops the tail block of the last update being handed out, joins the helper
+// thread, clears what the last update and the calls since left pending; then queues hm_update_begin's launches and, unless
+// chained, the copy of the prior mean into the first iterate.  Waits for nothing on the device.
+static int update_enter(UpdateRun &u)
+{
+    hm_ctx *h = u.h;
     h->tail_valid = false;
-    HM_JOIN_LAZY(h);                               // (the tail of the last update: waited for before the first solve below)
-    HM_ARG(deltaX > 0 && max_iter >= 0, "hm_update_run: deltaX must be positive, max_iter >= 0");
-    // hm_chain_project: the prior mean is being left in d_X0 by the kernels of the state path; X is output only
-    const bool chained = h->chain_pending;
+    HM_JOIN_LAZY(h);                               // (the tail of the last update: waited for before the first solve)
+    HM_ARG(u.a.deltaX > 0 && u.a.max_iter >= 0, "hm_update_run: deltaX must be positive, max_iter >= 0");
+    u.chained = h->chain_pending;
     h->chain_pending = false;
     h->last_err_valid = false;
     h->pq_valid = false;                           // (after the join: the last update's tail may have queued a prediction)
     h->tail_pending = false;                       // (the block of the last update is about to be overwritten)
     NEED_TEX(h, "hm_update_run");
     NEED_OBS(h, "hm_update_run");
-    const bool dbg = getenv("HYDRA_MI_TRACE") != nullptr;
-    const auto dbg_a = std::chrono::steady_clock::now();
-    auto dbg_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg_a).count(); };
-    double dbg_stage[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int rc = update_begin(h, W_prior, chained ? nullptr : X);
-    if (rc) return rc;
-    dbg_stage[0] = dbg_ms();
-    const int N = h->N, n4 = 4 * N;
-    std::vector<double> X0, Xcur, Xold;
-    if (!chained) { X0.assign(X, X + n4); Xcur = X0; Xold = X0; }
-    // chained: what the prediction's and the projection's kernels report (host_block.h), taken while the first iteration
-    // runs.  2: the prediction's inner solve gave up (never observed) -- the caller predicts on the host and calls again.
-    auto chain_collect = [&]() -> int {
-        int r = hb_wait(h->stream3, h->pin_n4 + n4, 0, (size_t)n4 + 2, hb_stamp(h->n4_ticket), h->n4v.data(), "hm_update_run (state prediction)");
-        h->n4_pending = false;
-        if (r) return r;
-        r = hb_wait(h->stream3, h->pin_pm + n4, 0, (size_t)n4 + 1, hb_stamp(h->pm_ticket), h->pmv.data(), "hm_update_run (projectmask)");
-        if (r) return r;
-        h->chain_pred.assign(h->n4v.begin(), h->n4v.begin() + n4);
-        h->chain_proj.assign(h->pmv.begin(), h->pmv.begin() + n4);
-        h->chain_its = (int)h->n4v[n4];
-        h->chain_moved = (int)h->pmv[n4];
-        if (h->n4v[n4 + 1] != 0.0) return 2;
-        X0 = h->chain_proj; Xcur = X0; Xold = X0;
-        h->upd_X0 = X0;
-        h->X0 = X0;
-        return HM_OK;
-    };
-    bool collected = !chained;
+    u.dbg = getenv("HYDRA_MI_TRACE") != nullptr;
+    u.t_enter = std::chrono::steady_clock::now();
+    HM_TRY(update_begin(h, u.a.W_prior, u.chained ? nullptr : u.a.X));
+    u.stage[0] = u.ms();
+    u.collected = !u.chained;
     // (chained: the projection's kernel has written the first iterate, d_X, next to the prior mean)
-    if (!chained) HM_HIP(hipMemcpyAsync(h->d_X, h->d_X0, (size_t)n4 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    double *const pin_res = h->pin, *const pin_tail = h->pin + 2 * ((size_t)n4 + RES_HEAD);
-    const double *const res = h->resv.data();        // this call's copy of an iteration's block, taken when whole
-    int niter = 0, accepted = 0;
-    bool reverted = false, conv = false, ref_ready = false, regions_ahead = false, grown = false;
-    double eold = 0.0;
-    // spec: the measurement at the new iterate has been queued already -- behind k_iter_result, before the host has seen
-    // that iteration's result, on the assumption that the loop goes on (it does 7 times out of 8): the device goes from
-    // one iteration into the next without the ~14 us it takes the host to notice the result block, decide and launch.  ref / P
-    // and d_X / d_Xn are swapped when it is queued; an iteration that turns out to be the last swaps them back (the
-    // wasted measurement only wrote job sums and parked differences nobody reads, and the launches behind it on this
-    // stream -- the covariance of the kept state -- are not what the next frame waits for).
-    bool spec = false;
-    auto unspec = [&]() {
-        if (spec) { std::swap(h->ref, h->P); std::swap(h->d_X, h->d_Xn); spec = false; }
-    };
-    for (int it = 0; it < max_iter; it++) {
-        if (!spec) {
-            rc = measure_dev(h, h->d_X, ref_ready, deltaX, masked, regions_ahead, false);
-            if (rc) return rc;
-        }
-        spec = false;
-        if (next_mask && it == 0) {
-            // The next frame's mask (hm_update_arm_mask): its pruning and outline (~0.2 ms of kernels on the second
-            // stream) start when this frame's first measurement has run -- beside the first factorisation, which leaves
-            // the chip idle -- not beside the first render and measurement, and not in the window between two frames,
-            // where they slowed the state prediction's one workgroup down (0.33 instead of 0.27 ms)
-            // (the event now; the launches when this iteration's own launches are queued and the host has nothing to do
-            // but wait: eight launches here kept the first system of the frame waiting for the host, ~17 us per iteration
-            // on average in the kernel trace)
-            HM_HIP(h->own.event(&h->ev_m0));
-            HM_HIP(hipEventRecord(h->ev_m0, h->stream));
-        }
-        if (collected) h->X0 = Xcur;               // the state of the reference render (hm_jz / hm_j)
-        h->have_ref = true;
-        const int slot = h->upd_last == 0 ? 1 : 0;
-        rc = ctx_join(h);                          // the tail of the last update may still be writing inv(W) and the factor slots
-        if (rc) return rc;
-        double *rhs_row = solve_step(h, slot, deltaX);
-        // the new iterate: its render, the partial sums of Renderer.error (kalman.py:813) and, as extra workgroups of
-        // the same launch, the star regions of the next measurement (they need the new iterate only; wasted when the
-        // loop ends here)
-        regions_ahead = it + 1 < max_iter;
-        rc = render_iter(h, h->d_Xn, h->P, true, masked, regions_ahead, deltaX);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_iter_result, dim3(1), dim3(256), 0, h->stream, rhs_row, n4, h->d_tpart,
-                           render_strips(h), h->pool.overflow, (const unsigned *)h->d_flowctl, pin_res, (double)(++h->run_ticket),
-                           h->result_delay);
-        HM_HIP(hipGetLastError());
-        if (h->speculate && regions_ahead) {
-            std::swap(h->ref, h->P);
-            std::swap(h->d_X, h->d_Xn);
-            spec = true;
-            rc = measure_dev(h, h->d_X, true, deltaX, masked, true, false);
-            if (rc) { unspec(); return rc; }
-        }
-        const auto dbg_t0 = std::chrono::steady_clock::now();
-        if (next_mask && it == 0) {
-            rc = ensure_stream2(h);
-            if (rc == HM_OK) { HM_HIP(hipStreamWaitEvent(h->stream2, h->ev_m0, 0)); rc = prepare_mask(h, next_mask); }
-            if (rc) { unspec(); return rc; }
-            next_mask = nullptr;
-        }
-        if (!collected) {
-            rc = chain_collect();
-            if (rc) { unspec(); (void)hipStreamSynchronize(h->stream); return rc; }
-            collected = true;
-        }
-        rc = hb_wait(h->stream, pin_res, 0, (size_t)n4 + RES_HEAD, hb_stamp(h->run_ticket), h->resv.data(), "hm_update_run");
-        if (rc) { unspec(); return rc; }
-        if (getenv("HYDRA_MI_TRACE")) {
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg_t0).count();
-            if (ms > 1.5) fprintf(stderr, "[hydra_mi] hm_update_run: iteration %d waited %.2f ms for its result\n", it, ms);
-        }
-        if (res[n4 + 4] != 0.0) {
-            unspec();
-            // the star regions of this measurement did not fit the pool of difference images: grow it and take the
-            // iteration again (nothing of it has been kept; the regions the failed pass computed for its -- meaningless
-            // -- next iterate are computed anew)
-            if (grown) { hm_set_error("hm_update_run: the star regions do not fit the difference-image pool"); return HM_ERR_STATE; }
-            if (regions_ahead) {
-                // d_area no longer describes the measurement that overflowed: this iteration's render launch has put the
-                // regions of its (meaningless) new iterate there.  Those of the iterate that was measured, again:
-                MeasureArgs a;
-                measure_args(h, h->d_X, deltaX, masked, a);
-                hipLaunchKernelGGL(k_star_regions, dim3(h->N), dim3(REGION_NT), 0, h->stream, a, h->d_area);
-                HM_HIP(hipGetLastError());
-            }
-            HM_HIP(hipStreamSynchronize(h->stream));
-            rc = pool_grow(h, "hm_update_run");
-            if (rc) return rc;
-            grown = true;
-            regions_ahead = false;
-            HM_HIP(hipMemsetAsync(h->d_flowctl, 0, 4 * sizeof(unsigned), h->stream));      // (a NaN system may have timed out)
-            it--;
-            continue;
-        }
-        grown = false;
+    if (!u.chained) {
+        u.X0.assign(u.a.X, u.a.X + u.n4); u.Xcur = u.X0; u.Xold = u.X0;
+        HM_HIP(hipMemcpyAsync(h->d_X, h->d_X0, (size_t)u.n4 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
+    return HM_OK;
+}
+
+// Queues iteration `it` on the handle's stream and waits for nothing: the measurement at d_X unless the last iteration
+// queued it ahead; on iteration 0 the ev_m0 record when a mask is armed; the join with the last update's tail; the system
+// and its solve (d_Xn = the new iterate); the render of the new iterate with its error sums and the star regions of the
+// next measurement; the result block; and, ahead of that block's arrival, the next measurement with the swap.
+static int update_queue_iteration(UpdateRun &u, int it, SpecSwap &swap)
+{
+    hm_ctx *h = u.h;
+    if (!u.measured_ahead) HM_TRY(measure_dev(h, h->d_X, u.ref_ready, u.a.deltaX, u.a.masked, u.regions_ahead, false));
+    u.measured_ahead = false;
+    if (u.next_mask && it == 0) {
+        // The next frame's mask (hm_update_arm_mask): its pruning and outline (~0.2 ms of kernels on the second
+        // stream) start when this frame's first measurement has run -- beside the first factorisation, which leaves
+        // the chip idle -- not beside the first render and measurement, and not in the window between two frames,
+        // where they slowed the state prediction's one workgroup down (0.33 instead of 0.27 ms)
+        // (the event now; the launches when this iteration's own launches are queued and the host has nothing to do
+        // but wait (update_meanwhile): eight launches here kept the first system of the frame waiting for the host,
+        // ~17 us per iteration on average in the kernel trace)
+        HM_HIP(h->own.event(&h->ev_m0));
+        HM_HIP(hipEventRecord(h->ev_m0, h->stream));
+    }
+    if (u.collected) h->X0 = u.Xcur;               // the state of the reference render (hm_jz / hm_j)
+    h->have_ref = true;
+    u.slot = h->upd_last == 0 ? 1 : 0;
+    HM_TRY(ctx_join(h));                           // the tail of the last update may still be writing inv(W) and the factor slots
+    double *rhs_row = solve_step(h, u.slot, u.a.deltaX);
+    // the new iterate: its render, the partial sums of Renderer.error (kalman.py:813) and, as extra workgroups of
+    // the same launch, the star regions of the next measurement (they need the new iterate only; wasted when the
+    // loop ends here)
+    u.regions_ahead = it + 1 < u.a.max_iter;
+    HM_TRY(render_iter(h, h->d_Xn, h->P, true, u.a.masked, u.regions_ahead, u.a.deltaX));
+    hipLaunchKernelGGL(k_iter_result, dim3(1), dim3(256), 0, h->stream, rhs_row, u.n4, h->d_tpart,
+                       render_strips(h), h->pool.overflow, (const unsigned *)h->d_flowctl, h->pin, (double)(++h->run_ticket),
+                       h->result_delay);
+    HM_HIP(hipGetLastError());
+    if (h->speculate && u.regions_ahead) {
+        swap.set();
+        u.measured_ahead = true;
+        HM_TRY(measure_dev(h, h->d_X, true, u.a.deltaX, u.a.masked, true, false));
+    }
+    u.t_queued = std::chrono::steady_clock::now();
+    return HM_OK;
+}
+
+// What the host does while the device works on iteration `it`: the armed mask's launches on the second stream, behind
+// ev_m0 (iteration 0), and the result blocks of a chained prior (chain_collect, which waits for them; when that fails the
+// stream is waited for, so that nothing of this call stays in flight).
+static int update_meanwhile(UpdateRun &u, int it)
+{
+    hm_ctx *h = u.h;
+    if (u.next_mask && it == 0) {
+        HM_TRY(ensure_stream2(h));
+        HM_HIP(hipStreamWaitEvent(h->stream2, h->ev_m0, 0));
+        HM_TRY(prepare_mask(h, u.next_mask));
+        u.next_mask = nullptr;
+    }
+    if (!u.collected) {
+        const int rc = chain_collect(u);
+        if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+    }
+    return HM_OK;
+}
+
+// Waits for the iteration's result block (hb_wait) and counts the iteration -- or, when its star regions did not fit the
+// pool of difference images, undoes the swap, waits for the stream, grows the pool and asks for the iteration again
+// (nothing of it has been kept; the regions the failed pass computed for its -- meaningless -- next iterate are computed anew).
+enum class Taken { go_on, retry };
+static int update_take_result(UpdateRun &u, int it, SpecSwap &swap, Taken *out)
+{
+    hm_ctx *h = u.h;
+    const int n4 = u.n4;
+    HM_TRY(hb_wait(h->stream, h->pin, 0, (size_t)n4 + RES_HEAD, hb_stamp(h->run_ticket), h->resv.data(), "hm_update_run"));
+    if (u.dbg) {
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u.t_queued).count();
+        if (ms > 1.5) fprintf(stderr, "[hydra_mi] hm_update_run: iteration %d waited %.2f ms for its result\n", it, ms);
+    }
+    if (u.res()[n4 + 4] == 0.0) {
+        u.grown = false;
         h->upd_prev = h->upd_last;
-        h->upd_last = slot;
-        niter++;
-        if (res[n4 + 7] != 0.0) {
-            unspec();
-            hm_set_error("hm_update_run: the factorisation launch gave up waiting for a block (chol_flow time-out)");
-            return HM_ERR_HIP;
-        }
-        bool finite = true;
-        for (int i = 0; i < n4; i++) finite = finite && std::isfinite(res[i]);
-        if (!finite) {
-            unspec();
-            hm_set_error("hm_update_run: the update system inv(W) + HTH is not positive definite "
-                         "(non-finite state, covariance or observation?)");
-            return HM_ERR_NUMERIC;
-        }
-        for (int i = 0; i < n4; i++) Xcur[i] = X0[i] + res[i];
-        if (errs) for (int k = 0; k < 4; k++) errs[4 * it + k] = res[n4 + k];
-        // a triangle that flipped: back to the last good state (kalman.py:806-811)
-        bool flipped = false;
-        for (int t = 0; t < h->T && !flipped; t++) {
-            const int a = h->tri[3 * t], b = h->tri[3 * t + 1], c = h->tri[3 * t + 2];
-            const double ax = Xcur[2 * b] - Xcur[2 * a], ay = Xcur[2 * b + 1] - Xcur[2 * a + 1];
-            const double bx = Xcur[2 * c] - Xcur[2 * a], by = Xcur[2 * c + 1] - Xcur[2 * a + 1];
-            flipped = ax * by - ay * bx < 0.0;
-        }
-        if (flipped) {
-            unspec();
-            Xcur = Xold;
-            reverted = true;
-            break;
-        }
-        // the error sums of the image and mask terms are whole numbers (the reference truncates
-        // them to int before combining, kalman.py:813-816)
-        const double e_im = std::trunc(res[n4]), e_m = std::trunc(res[n4 + 3]);
-        const double enew = std::sqrt(e_im * e_im + res[n4 + 1] * res[n4 + 1] + res[n4 + 2] * res[n4 + 2] + e_m * e_m);
-        accepted++;
-        if (std::fabs(enew - eold) / enew < reltol) { unspec(); conv = true; break; }
-        eold = enew;
-        Xold = Xcur;
-        // the new iterate becomes the point of the next measurement; its render is already there
-        if (!spec) {
-            std::swap(h->ref, h->P);
-            std::swap(h->d_X, h->d_Xn);
-        }
-        ref_ready = true;
-        h->X0 = Xcur;
+        h->upd_last = u.slot;
+        u.niter++;
+        *out = Taken::go_on;
+        return HM_OK;
     }
-    unspec();                                      // (max_iter reached: regions_ahead was false, nothing was queued)
-    if (!collected) {                              // (max_iter = 0)
-        rc = chain_collect();
-        if (rc) return rc;
+    swap.undo();
+    u.measured_ahead = false;
+    if (u.grown) { hm_set_error("hm_update_run: the star regions do not fit the difference-image pool"); return HM_ERR_STATE; }
+    if (u.regions_ahead) {
+        // d_area no longer describes the measurement that overflowed: this iteration's render launch has put the
+        // regions of its (meaningless) new iterate there.  Those of the iterate that was measured, again:
+        MeasureArgs a;
+        measure_args(h, h->d_X, u.a.deltaX, u.a.masked, a);
+        hipLaunchKernelGGL(k_star_regions, dim3(h->N), dim3(REGION_NT), 0, h->stream, a, h->d_area);
+        HM_HIP(hipGetLastError());
     }
-    dbg_stage[1] = dbg_ms();
-    // the state is final: a caller that armed it gets the next frame's state prediction started now, on its worker
-    // thread, beside the covariance launches below (hm_update_arm_newton)
-    if (pn_go) {
-        rc = hm_ms_newton_start(pn_worker, N, (int)h->pn_l0.size(), h->pn_bars.data(), h->pn_l0.data(), h->pn_par[0],
-                                h->pn_par[1], h->pn_par[2], h->pn_maxiter, h->pn_par[3], Xcur.data());
-        if (rc) return rc;
+    HM_HIP(hipStreamSynchronize(h->stream));
+    HM_TRY(pool_grow(h, "hm_update_run"));
+    u.grown = true;
+    u.regions_ahead = false;
+    HM_HIP(hipMemsetAsync(h->d_flowctl, 0, 4 * sizeof(unsigned), h->stream));      // (a NaN system may have timed out)
+    *out = Taken::retry;
+    return HM_OK;
+}
+
+// The reference's acceptance logic on the block just taken (host arithmetic only): the time-out word and the finite check
+// (errors), Xcur = X0 + step, errs, a flipped triangle (back to the last good state), the truncated error norm and the
+// reltol test.  go_on leaves the new iterate as the point of the next measurement (the caller keeps the swap).
+enum class Verdict { go_on, reverted, converged };
+static int update_judge(UpdateRun &u, int it, Verdict *out)
+{
+    hm_ctx *h = u.h;
+    const int n4 = u.n4;
+    const double *res = u.res();
+    if (res[n4 + 7] != 0.0) {
+        hm_set_error("hm_update_run: the factorisation launch gave up waiting for a block (chol_flow time-out)");
+        return HM_ERR_HIP;
     }
-    dbg_stage[2] = dbg_ms();
-    // covariance of the state that is kept (kalman.py:806-811, 826)
+    bool finite = true;
+    for (int i = 0; i < n4; i++) finite = finite && std::isfinite(res[i]);
+    if (!finite) {
+        hm_set_error("hm_update_run: the update system inv(W) + HTH is not positive definite "
+                     "(non-finite state, covariance or observation?)");
+        return HM_ERR_NUMERIC;
+    }
+    for (int i = 0; i < n4; i++) u.Xcur[i] = u.X0[i] + res[i];
+    if (u.a.errs) for (int k = 0; k < 4; k++) u.a.errs[4 * it + k] = res[n4 + k];
+    // a triangle that flipped: back to the last good state (kalman.py:806-811)
+    bool flipped = false;
+    for (int t = 0; t < h->T && !flipped; t++) {
+        const int a = h->tri[3 * t], b = h->tri[3 * t + 1], c = h->tri[3 * t + 2];
+        const double ax = u.Xcur[2 * b] - u.Xcur[2 * a], ay = u.Xcur[2 * b + 1] - u.Xcur[2 * a + 1];
+        const double bx = u.Xcur[2 * c] - u.Xcur[2 * a], by = u.Xcur[2 * c + 1] - u.Xcur[2 * a + 1];
+        flipped = ax * by - ay * bx < 0.0;
+    }
+    if (flipped) {
+        u.Xcur = u.Xold;
+        u.reverted = true;
+        *out = Verdict::reverted;
+        return HM_OK;
+    }
+    // the error sums of the image and mask terms are whole numbers (the reference truncates
+    // them to int before combining, kalman.py:813-816)
+    const double e_im = std::trunc(res[n4]), e_m = std::trunc(res[n4 + 3]);
+    const double enew = std::sqrt(e_im * e_im + res[n4 + 1] * res[n4 + 1] + res[n4 + 2] * res[n4 + 2] + e_m * e_m);
+    u.accepted++;
+    if (std::fabs(enew - u.eold) / enew < u.a.reltol) {
+        u.conv = true;
+        *out = Verdict::converged;
+        return HM_OK;
+    }
+    u.eold = enew;
+    u.Xold = u.Xcur;
+    u.ref_ready = true;
+    h->X0 = u.Xcur;
+    *out = Verdict::go_on;
+    return HM_OK;
+}
+
+// The state is final (Xcur): collects a chained prior that no iteration collected (max_iter = 0), and a caller that armed
+// it gets the next frame's state prediction started now, on its worker thread, beside the covariance launches of the tail
+// (hm_update_arm_newton).
+static int update_state_final(UpdateRun &u)
+{
+    hm_ctx *h = u.h;
+    if (!u.collected) HM_TRY(chain_collect(u));
+    u.stage[1] = u.ms();
+    if (u.armed.newton)
+        HM_TRY(hm_ms_newton_start(u.armed.worker, h->N, (int)h->pn_l0.size(), h->pn_bars.data(), h->pn_l0.data(), h->pn_par[0],
+                                  h->pn_par[1], h->pn_par[2], h->pn_maxiter, h->pn_par[3], u.Xcur.data()));
+    u.stage[2] = u.ms();
+    return HM_OK;
+}
+
+// The launches of the tail over a plain struct of values: the helper thread runs them after hm_update_run has returned, so
+// its closure holds a copy of this struct and of Xk, the state that is kept, and refers to nothing of the call's frame.
+struct TailJob {
+    hm_ctx *h;
+    const uint8_t *next_mask;        // an armed mask no iteration has queued (an update without iterations)
+    int which;                       // hm_update_cov's: -1 the prior, 0 the last step, 1 the step before
+    hipStream_t ts;
+    int niter, n4;
+    double *pin_tail;
+    long long ticket;
+    double *W_out;
+    bool ahead;                      // queue the covariance half of the next frame's prediction (hm_update_arm_cov)
+    double eps_F;
+};
+// On ts: the covariance of the kept state; with iterations the gains and the tail's result block; the copy to W_out; the
+// prediction ahead; on stream4 the ev_tail record.  Before them, on the second stream, the next frame's outline.  Waits
+// for nothing.
+static int tail_launches(const TailJob &j, const std::vector<double> &Xk)
+{
+    hm_ctx *h = j.h;
+    const int n4 = j.n4;
+    HM_HIP(hipSetDevice(h->device));
+    if (j.next_mask) HM_TRY(prepare_mask(h, j.next_mask));       // the next frame's outline, beside the prediction (hm_update_arm_mask)
+    HM_TRY(update_cov_on(h, j.which, nullptr, j.ts));
+    if (j.niter > 0) {
+        // gains and Hz components go to the host as a result block of their own (host_block.h), as the iterations'
+        // results do: two blit launches and the wake-up from a stream synchronisation less per frame
+        hipLaunchKernelGGL(k_gains, dim3(n4), dim3(256), 0, j.ts, h->d_Wres, h->d_Hzc, n4, h->d_gain);
+        hipLaunchKernelGGL(k_tail_result, dim3(1), dim3(1024), 0, j.ts, h->d_Hzc, h->d_gain, n4, j.pin_tail, (double)j.ticket,
+                           h->result_delay);
+    }
+    if (j.W_out) HM_HIP(hipMemcpyAsync(j.W_out, h->d_Wres, (size_t)n4 * n4 * sizeof(double), hipMemcpyDeviceToHost, j.ts));
+    HM_HIP(hipGetLastError());
+    if (j.ahead)                                   // behind the launches above (hm_update_arm_cov)
+        HM_TRY(queue_predict_ahead(h, Xk.data(), (int)h->pn_l0.size(), h->pn_bars.data(), h->pn_l0.data(), h->pn_par[0],
+                                   h->pn_par[1], h->pn_par[2], j.eps_F, j.ts));
+    if (j.ts != h->stream) {
+        HM_HIP(hipEventRecord(h->ev_tail, j.ts));
+        h->tail_on_stream4 = true;
+    }
+    return HM_OK;
+}
+
+// The tail: the covariance of the state that is kept (kalman.py:806-811, 826), the gains, the prediction ahead.  Chooses
+// the slot and the stream, takes the ticket, queues the launches (itself or through the helper thread) and hands the
+// tail's block out in one of three ways: deferred to hm_update_tail, waited for here (hb_wait), or after the stream has
+// been waited for when the caller wants the covariance on the host.
+static int update_tail(UpdateRun &u)
+{
+    hm_ctx *h = u.h;
+    const int n4 = u.n4;
     int which = -1;                                // -1: the prior
-    if (reverted) which = accepted == 0 ? -1 : 1;
-    else which = niter == 0 ? -1 : 0;
+    if (u.reverted) which = u.accepted == 0 ? -1 : 1;
+    else which = u.niter == 0 ? -1 : 0;
     // The tail runs on a stream of its own (stream4) when the caller does not want the covariance on the host: everything
     // it reads is complete -- the host has seen the result block of the last iteration, whose kernel is behind all of
     // them on `stream` -- and what is still queued on `stream` (the measurement of an iteration that does not happen)
     // and what the next frame queues there first (reference render, measurement) touch none of its buffers; `stream` waits
     // for its end (ev_tail, on the device) before the next solve (ctx_join).
     hipStream_t ts = h->stream;
-    rc = ctx_join(h);                              // (a tail nobody has joined since: an update without iterations)
-    if (rc) return rc;
-    if (!W_out && h->tail_split) {
+    HM_TRY(ctx_join(h));                           // (a tail nobody has joined since: an update without iterations)
+    if (!u.a.W_out && h->tail_split) {
         HM_HIP(h->own.stream(&h->stream4));
         HM_HIP(h->own.event(&h->ev_tail));
         ts = h->stream4;
     }
-    const long long tail_ticket = niter > 0 ? ++h->run_ticket : h->run_ticket;
-    const double eps_F = h->pq_eps_F;
-    const bool ahead = pq_go && h->chol_flow && which >= 0 && niter > 0 && !W_out;
-    // the launches of the tail; Xk: the state that is kept
-    auto tail = [h, next_mask, which, ts, niter, n4, pin_tail, tail_ticket, W_out, ahead, eps_F](const std::vector<double> &Xk) -> int {
-        HM_HIP(hipSetDevice(h->device));
-        int r = HM_OK;
-        if (next_mask) {                           // the next frame's outline, beside the prediction (hm_update_arm_mask)
-            r = prepare_mask(h, next_mask);
-            if (r) return r;
-        }
-        r = update_cov_on(h, which, nullptr, ts);
-        if (r) return r;
-        if (niter > 0) {
-            // gains and Hz components go to the host as a result block of their own (host_block.h), as the iterations'
-            // results do: two blit launches and the wake-up from a stream synchronisation less per frame
-            hipLaunchKernelGGL(k_gains, dim3(n4), dim3(256), 0, ts, h->d_Wres, h->d_Hzc, n4, h->d_gain);
-            hipLaunchKernelGGL(k_tail_result, dim3(1), dim3(1024), 0, ts, h->d_Hzc, h->d_gain, n4, pin_tail, (double)tail_ticket,
-                               h->result_delay);
-        }
-        if (W_out) HM_HIP(hipMemcpyAsync(W_out, h->d_Wres, (size_t)n4 * n4 * sizeof(double), hipMemcpyDeviceToHost, ts));
-        HM_HIP(hipGetLastError());
-        if (ahead) {
-            // the covariance half of the next frame's prediction, behind the launches above (hm_update_arm_cov)
-            r = queue_predict_ahead(h, Xk.data(), (int)h->pn_l0.size(), h->pn_bars.data(), h->pn_l0.data(), h->pn_par[0],
-                                    h->pn_par[1], h->pn_par[2], eps_F, ts);
-            if (r) return r;
-        }
-        if (ts != h->stream) {
-            HM_HIP(hipEventRecord(h->ev_tail, ts));
-            h->tail_on_stream4 = true;
-        }
-        return HM_OK;
-    };
-    dbg_stage[3] = dbg_ms();
-    if (niter > 0 && !W_out && !Hzc && !gains) {
+    const long long ticket = u.niter > 0 ? ++h->run_ticket : h->run_ticket;
+    const bool ahead = u.armed.cov && u.armed.newton && h->chol_flow && which >= 0 && u.niter > 0 && !u.a.W_out;
+    const TailJob job = {h, u.next_mask, which, ts, u.niter, n4, u.pin_tail(), ticket, u.a.W_out, ahead, h->pq_eps_F};
+    u.stage[3] = u.ms();
+    if (u.niter > 0 && !u.a.W_out && !u.a.Hzc && !u.a.gains) {
         // nobody wants the gains now: they are taken when asked for (hm_update_tail) and the caller gets on with its next
         // frame -- the tail's ~20 launches are queued by the handle's helper thread (every entry point joins it first)
         h->tail_pending = true;
-        h->tail_ticket = tail_ticket;
+        h->tail_ticket = ticket;
         h->tail_stream = ts;
         if (h->tail_async) {
             h->helper_used = true;
-            h->helper.post([tail, Xk = Xcur]() { return tail(Xk); });
+            h->helper.post([job, Xk = u.Xcur]() { return tail_launches(job, Xk); });
         } else {
-            rc = tail(Xcur);
-            if (rc) return rc;
+            HM_TRY(tail_launches(job, u.Xcur));
         }
-    } else if (niter > 0 && !W_out) {
-        rc = tail(Xcur);
-        if (rc) return rc;
-        rc = hb_wait(ts, pin_tail, 0, (size_t)n4 * 7, hb_stamp(tail_ticket), h->tailv.data(), "hm_update_run");
-        if (rc) return rc;
+    } else if (u.niter > 0 && !u.a.W_out) {
+        HM_TRY(tail_launches(job, u.Xcur));
+        HM_TRY(hb_wait(ts, job.pin_tail, 0, (size_t)n4 * 7, hb_stamp(ticket), h->tailv.data(), "hm_update_run"));
     } else {
-        rc = tail(Xcur);
-        if (rc) return rc;
+        HM_TRY(tail_launches(job, u.Xcur));
         HM_HIP(stream_wait(ts));
-        if (niter > 0 && !hb_take(pin_tail, 0, (size_t)n4 * 7, hb_stamp(tail_ticket), h->tailv.data())) {
+        if (u.niter > 0 && !hb_take(job.pin_tail, 0, (size_t)n4 * 7, hb_stamp(ticket), h->tailv.data())) {
             hm_set_error("hm_update_run: the gains did not arrive although the stream has completed");
             return HM_ERR_HIP;
         }
     }
-    dbg_stage[4] = dbg_ms();
-    if (dbg && dbg_stage[4] > 5.0)
+    u.stage[4] = u.ms();
+    if (u.dbg && u.stage[4] > 5.0)
         fprintf(stderr, "[hydra_mi] hm_update_run %d iterations: begin %.2f loop-end %.2f newton-started %.2f tail-queued %.2f tail-done %.2f ms\n",
-                niter, dbg_stage[0], dbg_stage[1], dbg_stage[2], dbg_stage[3], dbg_stage[4]);
-    if (niter > 0) {
-        if (Hzc) memcpy(Hzc, h->tailv.data(), (size_t)n4 * 4 * sizeof(double));
-        if (gains) memcpy(gains, h->tailv.data() + (size_t)n4 * 4, (size_t)n4 * 3 * sizeof(double));
+                u.niter, u.stage[0], u.stage[1], u.stage[2], u.stage[3], u.stage[4]);
+    return HM_OK;
+}
+
+// What the caller gets: Hzc / gains (zeros for an update without iterations), X, info[]; and on the handle the tail block
+// marked valid and the error sums of the kept state when it is the last iterate.  Host only.
+static void update_finish(UpdateRun &u, int info[4])
+{
+    hm_ctx *h = u.h;
+    const size_t n4 = u.n4;
+    if (u.niter > 0) {
+        if (u.a.Hzc) memcpy(u.a.Hzc, h->tailv.data(), n4 * 4 * sizeof(double));
+        if (u.a.gains) memcpy(u.a.gains, h->tailv.data() + n4 * 4, n4 * 3 * sizeof(double));
     } else {
-        if (Hzc) memset(Hzc, 0, (size_t)n4 * 4 * sizeof(double));
-        if (gains) memset(gains, 0, (size_t)n4 * 3 * sizeof(double));
+        if (u.a.Hzc) memset(u.a.Hzc, 0, n4 * 4 * sizeof(double));
+        if (u.a.gains) memset(u.a.gains, 0, n4 * 3 * sizeof(double));
         std::fill(h->tailv.begin(), h->tailv.end(), 0.0);
     }
     h->tail_valid = true;                          // (taken, queued for hm_update_tail, or zeros)
-    memcpy(X, Xcur.data(), (size_t)n4 * sizeof(double));
-    info[0] = niter; info[1] = accepted; info[2] = reverted ? 1 : 0; info[3] = conv ? 1 : 0;
-    if (niter > 0 && !reverted) {
+    memcpy(u.a.X, u.Xcur.data(), n4 * sizeof(double));
+    info[0] = u.niter; info[1] = u.accepted; info[2] = u.reverted ? 1 : 0; info[3] = u.conv ? 1 : 0;
+    if (u.niter > 0 && !u.reverted) {
         // the state that is kept is the last iterate: its render produced Renderer.error against the raw flow as well
+        const double *res = u.res();
         h->last_err[0] = res[n4]; h->last_err[1] = res[n4 + 8]; h->last_err[2] = res[n4 + 9]; h->last_err[3] = res[n4 + 3];
-        h->last_err_X = Xcur;
+        h->last_err_X = u.Xcur;
         h->last_err_valid = true;
     }
+}
+
+extern "C" int hm_update_run(hm_ctx_t h, const double *W_prior, double *X, double deltaX, int masked, int max_iter,
+                             double reltol, int info[4], double *errs, double *Hzc, double *gains, double *W_out)
+{
+    HM_ARG(h && X && info, "hm_update_run: NULL argument");
+    UpdateRun u(h, {W_prior, X, deltaX, masked, max_iter, reltol, errs, Hzc, gains, W_out});      // (takes h->armed: first)
+    HM_TRY(update_enter(u));
+    for (int it = 0; it < max_iter;) {
+        SpecSwap swap(h);                          // (put back on every way out of this block but keep())
+        HM_TRY(update_queue_iteration(u, it, swap));
+        HM_TRY(update_meanwhile(u, it));
+        Taken taken = Taken::go_on;
+        HM_TRY(update_take_result(u, it, swap, &taken));
+        if (taken == Taken::retry) continue;
+        Verdict verdict = Verdict::go_on;
+        HM_TRY(update_judge(u, it, &verdict));
+        if (verdict != Verdict::go_on) break;
+        swap.keep();
+        it++;
+    }
+    HM_TRY(update_state_final(u));
+    HM_TRY(update_tail(u));
+    update_finish(u, info);
     return HM_OK;
 }
 
@@ -1662,27 +1741,21 @@ extern "C" int hm_update_last_error(hm_ctx_t h, const double *X, double err[4])
     return HM_OK;
 }
 
-// The springs of every vertex (SpringTopo of k_fw_rows / k_pft_cols): off (N + 1) the CSR offsets, then per vertex its
-// springs in the order of `bars` -- bar: the spring's id, other: the vertex at its other end.  Vertex ids are checked by
-// the caller.
-static void spring_csr(int N, int n_bars, const int32_t *bars, std::vector<int> &off, std::vector<int> &bar,
-                       std::vector<int> &other)
+// the launch sequences the smoother repeats (ctx.h)
+void ekf_queue_fpft(hipStream_t st, const double *src, double *FP, double *dst, int N, const SpringTopo &tp, double a, double s,
+                    double eps_F)
 {
-    off.assign(N + 1, 0);
-    for (int i = 0; i < n_bars; i++) {
-        off[bars[2 * i] + 1]++;
-        off[bars[2 * i + 1] + 1]++;
-    }
-    for (int v = 0; v < N; v++) off[v + 1] += off[v];
-    bar.resize(2 * (size_t)n_bars); other.resize(2 * (size_t)n_bars);
-    std::vector<int> fill(off.begin(), off.end() - 1);
-    for (int i = 0; i < n_bars; i++) {
-        const int p = bars[2 * i], q = bars[2 * i + 1];
-        bar[fill[p]] = i; other[fill[p]++] = q;
-        bar[fill[q]] = i; other[fill[q]++] = p;
-    }
+    const dim3 grid(hm_cdiv(4 * N, 256), N);
+    hipLaunchKernelGGL(k_fw_rows, grid, dim3(256), 0, st, src, FP, N, tp, a, s);
+    hipLaunchKernelGGL(k_pft_cols, grid, dim3(256), 0, st, (const double *)FP, dst, N, tp, a, s, eps_F);
+}
+void ekf_queue_chol_flow(hipStream_t st, const FlowArgs &a, int wgs, bool fill)
+{
+    if (fill) hipLaunchKernelGGL(k_flow_fill, dim3(a.nrows + FLOW_FILL_WGS), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_chol_flow, dim3(wgs), dim3(FLOW_NT), 0, st, a);
 }
 
+// (spring_csr, spring_blocks: ctx.h)
 // Covariance prediction W' = F W F^T + Weps (kalman.py:717, 863) on the device.
 //   W_in   : the covariance to propagate (host), or NULL to use the one hm_update_cov returned last,
 //            which is still on the device;
@@ -1738,10 +1811,7 @@ static int cov_predict_core(hm_ctx *h, const double *W_in, int n_bars, const int
         src = h->d_H;
     }
     SpringTopo tp = {h->d_sp_off, h->d_sp_bar, h->d_sp_other, h->d_sp_blk};
-    double *P = h->d_Awork;                      // scratch
-    double *dst = ahead ? h->d_Wprior : h->d_Wtmp;
-    hipLaunchKernelGGL(k_fw_rows, dim3(hm_cdiv(n4, 256), N), dim3(256), 0, st, src, P, N, tp, a, s);
-    hipLaunchKernelGGL(k_pft_cols, dim3(hm_cdiv(n4, 256), N), dim3(256), 0, st, P, dst, N, tp, a, s, eps_F);
+    ekf_queue_fpft(st, src, h->d_Awork, ahead ? h->d_Wprior : h->d_Wtmp, N, tp, a, s, eps_F);      // (d_Awork: scratch)
     HM_HIP(hipGetLastError());
     if (ahead) return HM_OK;
     if (W_out) HM_HIP(hipMemcpyAsync(W_out, h->d_Wtmp, nn, hipMemcpyDeviceToHost, st));
@@ -1765,19 +1835,6 @@ extern "C" int hm_cov_predict(hm_ctx_t h, const double *W_in, int n_bars, const 
     return cov_predict_core(h, W_in, n_bars, bars, blocks, a, s, eps_F, W_out, false);
 }
 
-// The per-spring blocks (Bxx, Bxy, Byy) of the force Jacobian at the vertices of X (kalman.py:892-901): bar i between
-// a and b, d = y_a - y_b, l = |d|:  B = k I + c d d^T,  k = kappa (1 - l0/l),  c = kappa l0 / l^3.
-static void spring_blocks(int n_bars, const int32_t *bars, const double *l0, double kappa, const double *X, double *blk)
-{
-    for (int i = 0; i < n_bars; i++) {
-        const int a = bars[2 * i], b = bars[2 * i + 1];
-        const double dx = X[2 * a] - X[2 * b], dy = X[2 * a + 1] - X[2 * b + 1];
-        const double l = std::sqrt(dx * dx + dy * dy);
-        const double k = kappa * (1.0 - l0[i] / l), c = kappa * l0[i] / (l * l * l);
-        blk[3 * i] = k + c * dx * dx; blk[3 * i + 1] = c * dx * dy; blk[3 * i + 2] = k + c * dy * dy;
-    }
-}
-
 // hm_update_run, armed by hm_update_arm_newton + hm_update_arm_cov, when its state is final and the covariance of that
 // state (d_Wres) is queued: the covariance half of the NEXT frame's prediction -- W' = F W F^T + Weps with F at this
 // state (hm_cov_predict) and the factorisation / inverse of W' the next update starts with (hm_update_prefactor) --
@@ -1792,10 +1849,9 @@ static int queue_predict_ahead(hm_ctx *h, const double *X, int n_bars, const int
     HM_HIP(h->own.host_grow(&h->pin_blk, 3 * (size_t)n_bars * sizeof(double), hipHostMallocDefault));
     spring_blocks(n_bars, bars, l0, kappa, X, h->pin_blk);
     double *const post = h->d_Wres;
-    int rc = cov_predict_core(h, nullptr, n_bars, bars, h->pin_blk, dt, dt / M, eps_F, nullptr, true, st);
-    if (rc) return rc;
+    HM_TRY(cov_predict_core(h, nullptr, n_bars, bars, h->pin_blk, dt, dt / M, eps_F, nullptr, true, st));
     h->d_Wres = h->d_Wprior;                     // (prior_inverse: the prior is where it belongs already)
-    rc = prior_inverse(h, nullptr, st);
+    const int rc = prior_inverse(h, nullptr, st);
     h->d_Wres = post;
     if (rc) return rc;
     h->upd_open = false;                         // the factor slots and d_Wprior belong to the next update now
@@ -1854,7 +1910,7 @@ extern "C" int hm_ms_predict(hm_ctx_t h, int n_bars, const int32_t *bars, const 
     const size_t lds = ((size_t)34 * N + (size_t)7 * n_bars + 8) * sizeof(double) + ((size_t)N + 1 + 4 * (size_t)n_bars) * sizeof(int);
     const bool on_device = lds <= 160 * 1024;
     if (on_device) {
-        { const int rc2 = ensure_stream2(h); if (rc2) return rc2; }
+        HM_TRY(ensure_stream2(h));
         if (!h->newton_ready) {
             HM_HIP(h->own.alloc(&h->d_nX, (size_t)n4 * sizeof(double)));
             HM_HIP(h->own.alloc(&h->d_nvoff, (size_t)(N + 1) * sizeof(int)));
@@ -2034,13 +2090,10 @@ extern "C" int hm_chain_project(hm_ctx_t h)
     NEED_OBS(h, "hm_chain_project");
     if (!h->n4_pending || !h->d_n4X) return 1;
     HM_HIP(hipSetDevice(h->device));
-    int rc = ensure_stream2(h);
-    if (rc) return rc;
-    rc = project_buffers(h);
-    if (rc) return rc;
+    HM_TRY(ensure_stream2(h));
+    HM_TRY(project_buffers(h));
     if (!h->outline_ready) {
-        rc = queue_outline(h, h->o_ym);
-        if (rc) return rc;
+        HM_TRY(queue_outline(h, h->o_ym));
         h->outline_ready = true;
     }
     const size_t n4 = (size_t)4 * h->N;
@@ -2077,14 +2130,11 @@ extern "C" int hm_prepare_mask(hm_ctx_t h, const uint8_t *d_y_m)
 static int prepare_mask(hm_ctx *h, const uint8_t *d_y_m)
 {
     HM_HIP(hipSetDevice(h->device));
-    int rc = ensure_stream2(h);
-    if (rc) return rc;
-    rc = project_buffers(h);
-    if (rc) return rc;
+    HM_TRY(ensure_stream2(h));
+    HM_TRY(project_buffers(h));
     // the projection of the CURRENT frame may still be reading the outline buffers on the prediction's stream
     if (h->ev_pm && h->pm_ticket > 0) HM_HIP(hipStreamWaitEvent(h->stream2, h->ev_pm, 0));
-    rc = queue_outline(h, d_y_m);
-    if (rc) return rc;
+    HM_TRY(queue_outline(h, d_y_m));
     h->outline_ready = false;                    // (the buffers no longer hold the outline of the observation in place)
     h->prepared_mask = d_y_m;
     return HM_OK;
@@ -2102,324 +2152,4 @@ extern "C" int hm_chain_states(hm_ctx_t h, double *predicted, double *projected,
     if (newton_iterations) *newton_iterations = h->chain_its;
     if (moved) *moved = h->chain_moved;
     return HM_OK;
-}
-
-// ---- the Rauch-Tung-Striebel smoother (hm_smooth_*, include/hydra_mi.h) ------------------------------------------
-// A record of the filter's per-frame results -- P_k (the covariance the update kept), x_k, the prior mean m_k the
-// update started from -- and the backward recursion over it, all on the device.  What the record does not hold is
-// recomputed: Pp_{k+1} = F_k P_k F_k^T + Weps by k_fw_rows / k_pft_cols from slot k and the spring blocks at x_k (the
-// launches and inputs of the forward prediction, so the same bits), its factor and inverse by the factorisation the
-// update uses.  The buffers belong to the smoother (its own HmOwner); the filter's are only read, and only by the
-// copies hm_smooth_record queues.
-struct hm_smooth {
-    hm_ctx *ctx;
-    int device, cap, K = 0, N, n4, n_bars;
-    double kappa, a, s, eps_F;
-    HmOwner own{1};
-    std::vector<int32_t> bars;
-    std::vector<double> l0;
-    std::vector<double> hx;          // cap x n4: x_k as given to hm_smooth_record
-    std::vector<double> hblk;        // cap x 3 n_bars: the spring blocks (Bxx, Bxy, Byy) at x_k
-    double *d_P = nullptr;           // cap slots of n4 x n4: P_k; Ps_k after a run with covariances
-    double *d_m = nullptr, *d_x = nullptr, *d_xs = nullptr, *d_var = nullptr;   // cap x n4 each
-    double *d_blk = nullptr;         // cap x 3 n_bars
-    int *d_off = nullptr, *d_bar = nullptr, *d_other = nullptr;                 // the springs of every vertex (spring_csr)
-    // per backward step: F P, Pp, its factor (L, T = L^-1, the diagonal blocks' inverses Lt, the flow launch's scratch),
-    // Y = T F P, G, E, and three vectors (d, T d, T^T T d)
-    double *d_FP = nullptr, *d_Pp = nullptr, *d_L = nullptr, *d_T = nullptr, *d_Y = nullptr, *d_G = nullptr, *d_E = nullptr;
-    double *d_Lt = nullptr, *d_flowP = nullptr, *d_vec = nullptr;
-    unsigned *d_ctl = nullptr;       // the factorisation launch's task counter and time-out word
-    int *d_flag = nullptr;           // 1 + the first frame whose Pp did not factor
-    hipEvent_t ev_mean = nullptr, ev_cov = nullptr;   // behind the copies of m_k / of P_k
-    bool smoothed_cov = false;       // the slots hold Ps_k (or, after a failed run, partly): nothing more to record or run
-};
-
-extern "C" int hm_smooth_create(hm_ctx_t ctx, int capacity, int n_bars, const int32_t *bars, const double *l0,
-                                double kappa, double a, double s, double eps_F, hm_smooth_t *out)
-{
-    HM_ARG(out != nullptr, "hm_smooth_create: NULL output pointer");
-    *out = nullptr;
-    HM_ARG(capacity >= 2, "hm_smooth_create: capacity %d: a record needs at least 2 frames", capacity);
-    HM_ARG(ctx != nullptr, "hm_smooth_create: NULL filter handle");
-    HM_ARG(n_bars >= 0 && (n_bars == 0 || (bars && l0)), "hm_smooth_create: bad springs");
-    const int N = ctx->N, n4 = 4 * N;
-    for (int i = 0; i < 2 * n_bars; i++)
-        HM_ARG(bars[i] >= 0 && bars[i] < N, "hm_smooth_create: spring %d refers to vertex %d (mesh of %d)", i / 2, bars[i], N);
-    HM_JOIN(ctx);
-    HM_HIP(hipSetDevice(ctx->device));
-    hm_smooth *sm = new hm_smooth();
-    sm->ctx = ctx; sm->device = ctx->device; sm->cap = capacity; sm->N = N; sm->n4 = n4; sm->n_bars = n_bars;
-    sm->kappa = kappa; sm->a = a; sm->s = s; sm->eps_F = eps_F;
-    if (n_bars > 0) { sm->bars.assign(bars, bars + 2 * (size_t)n_bars); sm->l0.assign(l0, l0 + n_bars); }
-    const size_t nn = (size_t)n4 * n4 * sizeof(double), nv = (size_t)n4 * sizeof(double);
-    const int nb = hm_cdiv(n4, DNB);
-    int rc = HM_OK;
-    auto fail = [&](const char *what, size_t bytes, hipError_t e) {
-        hm_set_error("hm_smooth_create: %s: %zu bytes of device memory (%d frames of %d x %d doubles): %s", what, bytes,
-                     capacity, n4, n4, hipGetErrorString(e));
-        rc = HM_ERR_HIP;
-    };
-    auto take = [&](auto **p, size_t bytes, const char *what) {
-        if (rc) return;
-        const hipError_t e = sm->own.alloc(p, bytes);
-        if (e != hipSuccess) fail(what, bytes, e);
-    };
-    take(&sm->d_P, nn * capacity, "the covariance record");
-    take(&sm->d_m, nv * capacity, "the prior means");
-    take(&sm->d_x, nv * capacity, "the posterior means");
-    take(&sm->d_xs, nv * capacity, "the smoothed means");
-    take(&sm->d_var, nv * capacity, "the smoothed variances");
-    take(&sm->d_blk, std::max<size_t>(1, 3 * (size_t)n_bars * capacity) * sizeof(double), "the spring blocks");
-    take(&sm->d_off, (size_t)(N + 1) * sizeof(int), "the spring topology");
-    take(&sm->d_bar, std::max<size_t>(1, 2 * (size_t)n_bars) * sizeof(int), "the spring topology");
-    take(&sm->d_other, std::max<size_t>(1, 2 * (size_t)n_bars) * sizeof(int), "the spring topology");
-    double **work[] = {&sm->d_FP, &sm->d_Pp, &sm->d_L, &sm->d_T, &sm->d_Y, &sm->d_G, &sm->d_E};
-    for (double **p : work) take(p, nn, "the work matrices");
-    take(&sm->d_Lt, (size_t)nb * DNB * DNB * sizeof(double), "the factorisation");
-    take(&sm->d_flowP, (size_t)3 * nb * DNB * DNB * sizeof(double), "the factorisation");
-    take(&sm->d_vec, 3 * nv, "the work vectors");
-    take(&sm->d_ctl, 4 * sizeof(unsigned), "the factorisation");
-    take(&sm->d_flag, sizeof(int), "the status word");
-    if (!rc) {
-        hipError_t e = sm->own.event(&sm->ev_mean);
-        if (e == hipSuccess) e = sm->own.event(&sm->ev_cov);
-        std::vector<int> off, bar, other;
-        spring_csr(N, n_bars, bars, off, bar, other);
-        if (e == hipSuccess) e = hipMemcpy(sm->d_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess && n_bars > 0) e = hipMemcpy(sm->d_bar, bar.data(), bar.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess && n_bars > 0) e = hipMemcpy(sm->d_other, other.data(), other.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { hm_set_error("hm_smooth_create: %s", hipGetErrorString(e)); rc = HM_ERR_HIP; }
-    }
-    if (rc) {
-        sm->own.release();
-        delete sm;
-        return rc;
-    }
-    sm->hx.reserve((size_t)capacity * n4);
-    sm->hblk.reserve((size_t)capacity * 3 * n_bars);
-    *out = sm;
-    return HM_OK;
-}
-
-extern "C" int hm_smooth_destroy(hm_smooth_t sm)
-{
-    if (!sm) return HM_OK;
-    (void)hipSetDevice(sm->device);
-    sm->own.release();               // (hipFree waits for the device: no copy into the record is still in flight)
-    delete sm;
-    return HM_OK;
-}
-
-extern "C" int hm_smooth_count(hm_smooth_t sm, int *frames, int *capacity)
-{
-    HM_ARG(sm != nullptr, "hm_smooth_count: NULL handle");
-    if (frames) *frames = sm->K;
-    if (capacity) *capacity = sm->cap;
-    return HM_OK;
-}
-
-extern "C" int hm_smooth_record(hm_smooth_t sm, const double *X)
-{
-    HM_ARG(sm && X, "hm_smooth_record: NULL argument");
-    hm_ctx *h = sm->ctx;
-    if (sm->smoothed_cov) { hm_set_error("hm_smooth_record: the record has been smoothed with covariances"); return HM_ERR_STATE; }
-    if (sm->K >= sm->cap) {
-        hm_set_error("hm_smooth_record: the record is full (%d frames)", sm->cap);
-        return HM_ERR_STATE;
-    }
-    HM_JOIN_LAZY(h);                 // (the helper thread has queued the tail of the last update)
-    const int n4 = sm->n4, k = sm->K;
-    if (!h->d_Wres || h->upd_X0.size() != (size_t)n4) {
-        hm_set_error("hm_smooth_record: no update has run on the filter handle");
-        return HM_ERR_STATE;
-    }
-    HM_HIP(hipSetDevice(h->device));
-    // m_k: the prior mean the update started from, where the update keeps it (d_X0: given to hm_update_begin, or left by
-    // the chained projection).  The next chained projection rewrites it on stream3: that stream waits for the copy.
-    HM_HIP(hipMemcpyAsync(sm->d_m + (size_t)k * n4, h->d_X0, (size_t)n4 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HM_HIP(hipEventRecord(sm->ev_mean, h->stream));
-    if (h->stream3) HM_HIP(hipStreamWaitEvent(h->stream3, sm->ev_mean, 0));
-    // P_k: the covariance the update kept, behind the tail that forms it (ctx_join: `stream` waits for stream4), ahead of
-    // the next tail (stream4 waits for the copy) and of everything the handle's own stream does next
-    HM_JOIN(h);
-    HM_HIP(hipMemcpyAsync(sm->d_P + (size_t)k * n4 * n4, h->d_Wres, (size_t)n4 * n4 * sizeof(double), hipMemcpyDeviceToDevice,
-                          h->stream));
-    HM_HIP(hipEventRecord(sm->ev_cov, h->stream));
-    if (h->stream4) HM_HIP(hipStreamWaitEvent(h->stream4, sm->ev_cov, 0));
-    sm->hx.insert(sm->hx.end(), X, X + n4);
-    sm->hblk.resize((size_t)(k + 1) * 3 * sm->n_bars);
-    if (sm->n_bars > 0)
-        spring_blocks(sm->n_bars, sm->bars.data(), sm->l0.data(), sm->kappa, X, sm->hblk.data() + (size_t)k * 3 * sm->n_bars);
-    sm->K = k + 1;
-    return HM_OK;
-}
-
-// Pp_{k+1} = F_k P_k F_k^T + Weps into d_Pp, F P into d_FP (slot k must hold P_k)
-static void smooth_predict(hm_smooth *sm, int k, hipStream_t st)
-{
-    const int N = sm->N, n4 = sm->n4;
-    SpringTopo tp = {sm->d_off, sm->d_bar, sm->d_other, sm->d_blk + (size_t)k * 3 * sm->n_bars};
-    const double *P = sm->d_P + (size_t)k * n4 * n4;
-    hipLaunchKernelGGL(k_fw_rows, dim3(hm_cdiv(n4, 256), N), dim3(256), 0, st, P, sm->d_FP, N, tp, sm->a, sm->s);
-    hipLaunchKernelGGL(k_pft_cols, dim3(hm_cdiv(n4, 256), N), dim3(256), 0, st, (const double *)sm->d_FP, sm->d_Pp, N, tp,
-                       sm->a, sm->s, sm->eps_F);
-}
-
-static int smooth_upload_blocks(hm_smooth *sm, hipStream_t st)
-{
-    if (sm->n_bars > 0)
-        HM_HIP(hipMemcpyAsync(sm->d_blk, sm->hblk.data(), sm->hblk.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    return HM_OK;
-}
-
-extern "C" int hm_smooth_prior(hm_smooth_t sm, int k, double *Pp_out)
-{
-    HM_ARG(sm && Pp_out, "hm_smooth_prior: NULL argument");
-    HM_ARG(k >= 1 && k < sm->K, "hm_smooth_prior: frame %d outside 1..%d", k, sm->K - 1);
-    if (sm->smoothed_cov) { hm_set_error("hm_smooth_prior: the record has been smoothed with covariances"); return HM_ERR_STATE; }
-    hm_ctx *h = sm->ctx;
-    HM_JOIN(h);
-    HM_HIP(hipSetDevice(h->device));
-    const size_t n4 = sm->n4;
-    int rc = smooth_upload_blocks(sm, h->stream);
-    if (rc) return rc;
-    smooth_predict(sm, k - 1, h->stream);
-    HM_HIP(hipGetLastError());
-    HM_HIP(hipMemcpyAsync(Pp_out, sm->d_Pp, n4 * n4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    return HM_OK;
-}
-
-extern "C" int hm_smooth_fetch(hm_smooth_t sm, int k, double *P_out, double *x_out, double *m_out)
-{
-    HM_ARG(sm != nullptr, "hm_smooth_fetch: NULL handle");
-    HM_ARG(k >= 0 && k < sm->K, "hm_smooth_fetch: frame %d outside 0..%d", k, sm->K - 1);
-    hm_ctx *h = sm->ctx;
-    HM_JOIN(h);
-    HM_HIP(hipSetDevice(h->device));
-    const size_t n4 = sm->n4;
-    if (P_out) HM_HIP(hipMemcpyAsync(P_out, sm->d_P + k * n4 * n4, n4 * n4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (m_out) HM_HIP(hipMemcpyAsync(m_out, sm->d_m + k * n4, n4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HM_HIP(hipStreamSynchronize(h->stream));
-    if (x_out) memcpy(x_out, sm->hx.data() + k * n4, n4 * sizeof(double));
-    return HM_OK;
-}
-
-extern "C" int hm_smooth_run(hm_smooth_t sm, int want_cov, double *xs, double *var)
-{
-    HM_ARG(sm && xs && (!want_cov || var), "hm_smooth_run: NULL argument");
-    if (sm->K < 1) { hm_set_error("hm_smooth_run: nothing recorded"); return HM_ERR_STATE; }
-    if (sm->smoothed_cov) { hm_set_error("hm_smooth_run: the record has been smoothed with covariances already"); return HM_ERR_STATE; }
-    hm_ctx *h = sm->ctx;
-    HM_JOIN(h);
-    HM_HIP(hipSetDevice(h->device));
-    hipStream_t st = h->stream;
-    const int n4 = sm->n4, K = sm->K, nb = hm_cdiv(n4, DNB);
-    const size_t nn = (size_t)n4 * n4;
-    int rc = smooth_upload_blocks(sm, st);
-    if (rc) return rc;
-    HM_HIP(hipMemcpyAsync(sm->d_x, sm->hx.data(), (size_t)K * n4 * sizeof(double), hipMemcpyHostToDevice, st));
-    HM_HIP(hipMemsetAsync(sm->d_ctl, 0, 4 * sizeof(unsigned), st));
-    HM_HIP(hipMemsetAsync(sm->d_flag, 0, sizeof(int), st));
-    // the last frame: xs = x, Ps = P
-    HM_HIP(hipMemcpyAsync(sm->d_xs + (size_t)(K - 1) * n4, sm->d_x + (size_t)(K - 1) * n4, (size_t)n4 * sizeof(double),
-                          hipMemcpyDeviceToDevice, st));
-    const int gv = hm_cdiv(n4, 256);
-    if (want_cov) {
-        sm->smoothed_cov = true;     // (from here on the slots are being overwritten)
-        hipLaunchKernelGGL(k_sm_diag, dim3(gv), dim3(256), 0, st, (const double *)(sm->d_P + (K - 1) * nn), sm->d_var + (size_t)(K - 1) * n4, n4);
-    }
-    double *d = sm->d_vec, *u = sm->d_vec + n4, *w = sm->d_vec + 2 * n4;
-    for (int k = K - 2; k >= 0; k--) {
-        double *P = sm->d_P + k * nn;
-        const double *Ps1 = sm->d_P + (k + 1) * nn;
-        smooth_predict(sm, k, st);
-        // Pp = L L^T: T = L^-1 (the update's factorisation, one persistent launch)
-        FlowArgs fa = {sm->d_Pp, sm->d_L, sm->d_Lt, sm->d_T, sm->d_flowP, n4, n4, nb, nb, sm->d_ctl, 0};
-        hipLaunchKernelGGL(k_flow_fill, dim3(n4 + FLOW_FILL_WGS), dim3(256), 0, st, fa);
-        hipLaunchKernelGGL(k_chol_flow, dim3(h->flow_wgs), dim3(FLOW_NT), 0, st, fa);
-        hipLaunchKernelGGL(k_sm_check, dim3(gv), dim3(256), 0, st, (const double *)sm->d_T, n4, k + 1, sm->d_flag);
-        // xs_k = x_k + (F P)^T T^T T (xs_{k+1} - m_{k+1}): matrix-vector products only
-        hipLaunchKernelGGL(k_sm_sub, dim3(gv), dim3(256), 0, st, (const double *)(sm->d_xs + (size_t)(k + 1) * n4),
-                           (const double *)(sm->d_m + (size_t)(k + 1) * n4), d, n4);
-        hipLaunchKernelGGL(k_sm_trmv, dim3(n4), dim3(256), 0, st, (const double *)sm->d_T, (const double *)d, u, n4);
-        hipLaunchKernelGGL(k_sm_mvt, dim3(gv), dim3(256), 0, st, (const double *)sm->d_T, (const double *)u,
-                           (const double *)nullptr, w, n4, 1);
-        hipLaunchKernelGGL(k_sm_mvt, dim3(gv), dim3(256), 0, st, (const double *)sm->d_FP, (const double *)w,
-                           (const double *)(sm->d_x + (size_t)k * n4), sm->d_xs + (size_t)k * n4, n4, 0);
-        if (want_cov) {
-            // Y = T (F P), G = Y^T T = (F P)^T inv(Pp) through the factor (smooth_kernels.h: not through T^T T),
-            // E = G (Ps_{k+1} - Pp), Ps_k = P_k + E G^T in slot k
-            hipLaunchKernelGGL(k_sm_gemm<SM_LN>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_T,
-                               (const double *)sm->d_FP, (const double *)nullptr, sm->d_Y, n4);
-            hipLaunchKernelGGL(k_sm_gemm<SM_TL>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_Y,
-                               (const double *)sm->d_T, (const double *)nullptr, sm->d_G, n4);
-            hipLaunchKernelGGL(k_sm_gemm<SM_NND>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_G, Ps1,
-                               (const double *)sm->d_Pp, sm->d_E, n4);
-            hipLaunchKernelGGL(k_sm_gemm<SM_SYM>, dim3(nb, nb), dim3(SM_NT), 0, st, (const double *)sm->d_E,
-                               (const double *)sm->d_G, (const double *)P, P, n4);
-            hipLaunchKernelGGL(k_sm_diag, dim3(gv), dim3(256), 0, st, (const double *)P, sm->d_var + (size_t)k * n4, n4);
-        }
-        HM_HIP(hipGetLastError());
-    }
-    unsigned ctl[4] = {0, 0, 0, 0};
-    int flag = 0;
-    HM_HIP(hipMemcpyAsync(xs, sm->d_xs, (size_t)K * n4 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (want_cov) HM_HIP(hipMemcpyAsync(var, sm->d_var, (size_t)K * n4 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HM_HIP(hipMemcpyAsync(ctl, sm->d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HM_HIP(hipMemcpyAsync(&flag, sm->d_flag, sizeof flag, hipMemcpyDeviceToHost, st));
-    HM_HIP(hipStreamSynchronize(st));
-    if (ctl[1]) { hm_set_error("hm_smooth_run: the factorisation launch gave up waiting for a block (chol_flow time-out)"); return HM_ERR_HIP; }
-    if (flag) {
-        hm_set_error("hm_smooth_run: the predicted covariance Pp of frame %d is not positive definite", flag - 1);   // (k_sm_check: 1 + the frame)
-        return HM_ERR_NUMERIC;
-    }
-    return HM_OK;
-}
-
-// The products of the backward step on host arrays (n x n, row-major), for tests: which = SM_TN (out = A^T B),
-// SM_NND (out = A (B - C)), SM_SYM (out = C + A B^T from the lower tiles, mirrored), SM_LN (out = tril(A) B),
-// SM_TL (out = A^T tril(B)); C is read by SM_NND and SM_SYM only
-extern "C" int hm_op_smooth_gemm(int device, int which, int n, const double *A, const double *B, const double *C, double *out)
-{
-    HM_ARG(which >= SM_TN && which <= SM_TL, "hm_op_smooth_gemm: which %d outside 0..4", which);
-    HM_ARG(n >= 1 && n <= 8192, "hm_op_smooth_gemm: n %d outside 1..8192", n);
-    HM_ARG(A && B && out && ((which != SM_NND && which != SM_SYM) || C), "hm_op_smooth_gemm: NULL argument");
-    HM_HIP(hipSetDevice(device));
-    const size_t bytes = (size_t)n * n * sizeof(double);
-    double *dA = nullptr, *dB = nullptr, *dC = nullptr, *dO = nullptr;
-    const int nb = hm_cdiv(n, DNB);
-    auto run = [&]() -> int {
-        HM_HIP(hm_malloc((void **)&dA, bytes, 4));
-        HM_HIP(hm_malloc((void **)&dB, bytes, 4));
-        HM_HIP(hm_malloc((void **)&dO, bytes, 4));
-        HM_HIP(hipMemcpy(dA, A, bytes, hipMemcpyHostToDevice));
-        HM_HIP(hipMemcpy(dB, B, bytes, hipMemcpyHostToDevice));
-        if (which == SM_TN) {
-            hipLaunchKernelGGL(k_sm_gemm<SM_TN>, dim3(nb, nb), dim3(SM_NT), 0, 0, (const double *)dA, (const double *)dB,
-                               (const double *)nullptr, dO, n);
-        } else if (which == SM_LN) {
-            hipLaunchKernelGGL(k_sm_gemm<SM_LN>, dim3(nb, nb), dim3(SM_NT), 0, 0, (const double *)dA, (const double *)dB,
-                               (const double *)nullptr, dO, n);
-        } else if (which == SM_TL) {
-            hipLaunchKernelGGL(k_sm_gemm<SM_TL>, dim3(nb, nb), dim3(SM_NT), 0, 0, (const double *)dA, (const double *)dB,
-                               (const double *)nullptr, dO, n);
-        } else if (which == SM_NND) {
-            HM_HIP(hm_malloc((void **)&dC, bytes, 4));
-            HM_HIP(hipMemcpy(dC, C, bytes, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_sm_gemm<SM_NND>, dim3(nb, nb), dim3(SM_NT), 0, 0, (const double *)dA, (const double *)dB,
-                               (const double *)dC, dO, n);
-        } else {                     // in place, as the backward step runs it
-            HM_HIP(hipMemcpy(dO, C, bytes, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_sm_gemm<SM_SYM>, dim3(nb, nb), dim3(SM_NT), 0, 0, (const double *)dA, (const double *)dB,
-                               (const double *)dO, dO, n);
-        }
-        HM_HIP(hipGetLastError());
-        HM_HIP(hipMemcpy(out, dO, bytes, hipMemcpyDeviceToHost));
-        return HM_OK;
-    };
-    const int rc = run();
-    for (double *p : {dA, dB, dC, dO})
-        if (p) (void)hipFree(p);
-    return rc;
 }

@@ -1,7 +1,7 @@
 // Plain types, constants and __device__ inline helpers that more than one translation unit of libhydra_mi.so needs: what
 // the filter handle (ctx.h) holds by value, and what kernels on both sides of the filter / readout split use.  No
 // __global__ function lives here, so any translation unit may include it -- unlike the *_kernels.h headers, whose kernels
-// are not static: each of those is compiled by exactly one translation unit (ekf.hip, readout.hip or record.hip).
+// are not static: each of those is compiled by exactly one translation unit (ekf.hip, smooth.hip, readout.hip or record.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -202,6 +202,53 @@ struct DPool {
 };
 
 #define RI_H 16                        // strip height of the default launch (hm_ctx_tune "render_rows": 16 or 8)
+
+// ---- the dense f64 algebra (kernels: dense_kernels.h, chol_flow_kernels.h in ekf.hip; smooth_kernels.h in smooth.hip) ----
+#define DNB 32          // block size
+
+// the accumulator of v_mfma_f64_16x16x4_f64 (dense_kernels.h has the layout)
+typedef double d4_t __attribute__((ext_vector_type(4)));
+
+// One 16x16 tile of X Y for 32x32 blocks X, Y in LDS on the f64 matrix cores (v_mfma_f64_16x16x4_f64, eight k-steps):
+// wave wv computes tile (wv >> 1, wv & 1); element e of the result sits at row 16 (wv >> 1) + (lane >> 4) + 4 e, column
+// 16 (wv & 1) + (lane & 15).  (X Y^T: d_mfma_nt, dense_kernels.h)
+__device__ __forceinline__ d4_t d_mfma_nn(double (*X)[DNB + 1], double (*Y)[DNB + 1], int wv, int lane, d4_t c)
+{
+    const int i = 16 * (wv >> 1) + (lane & 15), j = 16 * (wv & 1) + (lane & 15), kq = lane >> 4;
+#pragma unroll
+    for (int kk = 0; kk < DNB / 4; kk++)
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(X[i][4 * kk + kq], Y[4 * kk + kq][j], c, 0, 0, 0);
+    return c;
+}
+// the same for X^T Y
+__device__ __forceinline__ d4_t d_mfma_tn(double (*X)[DNB + 1], double (*Y)[DNB + 1], int wv, int lane, d4_t c)
+{
+    const int i = 16 * (wv >> 1) + (lane & 15), j = 16 * (wv & 1) + (lane & 15), kq = lane >> 4;
+#pragma unroll
+    for (int kk = 0; kk < DNB / 4; kk++)
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(X[4 * kk + kq][i], Y[4 * kk + kq][j], c, 0, 0, 0);
+    return c;
+}
+
+// the springs of every vertex, as the covariance prediction's kernels read them (k_fw_rows / k_pft_cols, dense_kernels.h)
+struct SpringTopo {
+    const int *off;           // N+1: springs of each vertex
+    const int *bar;           // spring id
+    const int *other;         // the vertex at the other end
+    const double *blk;        // I x 3: Bxx, Bxy, Byy
+};
+
+// the factorisation as one persistent launch (k_flow_fill / k_chol_flow, chol_flow_kernels.h)
+struct FlowArgs {
+    const double *A;          // n x n matrix (+ right-hand-side rows up to nrows), read only
+    double *L;                // nrows x n: blocks below the block diagonal
+    double *Lt;               // nb x 32 x 32: T_c
+    double *Tinv;             // n x n: L^-1
+    double *P;                // 3 x nb x 32 x 32: block (c, c-1) before its triangular solve; Q_c; block (c, c-2) likewise (Y_c)
+    int n, nrows, nb, nbr;    // nbr: block rows including the right-hand-side rows
+    unsigned *ctl;            // [0] next task, [1] set when a wait timed out
+    int stall;                // test knob (hm_ctx_tune "chol_flow_stall"): the chain sleeps ~4 us x stall before every diagonal block
+};
 
 // ---- working arrays of the mask's contour pruning (project_kernels.h) ------------------------------------------------
 struct Ccl {

@@ -1,13 +1,13 @@
-// Kernels of the Rauch-Tung-Striebel smoother (hm_smooth_*, ekf.hip): dense f64 products at n x n on the matrix cores
+// Kernels of the Rauch-Tung-Striebel smoother (hm_smooth_*, smooth.hip): dense f64 products at n x n on the matrix cores
 // and the matrix-vector products of the mean recursion.  gfx950 only.
 //
 // The products work on 32 x 32 output tiles, one workgroup of four waves per tile, each wave one 16 x 16 quarter
-// (v_mfma_f64_16x16x4_f64 through the LDS helpers of dense_kernels.h: element e of a lane sits at row
+// (v_mfma_f64_16x16x4_f64 through the LDS helpers of hm_types.h: element e of a lane sits at row
 // 16 (wv >> 1) + (lane >> 4) + 4 e, column 16 (wv & 1) + (lane & 15)).  The k loop takes 32-wide slabs of both
 // operands into LDS; entries past n are zeros, so n need not be a multiple of 16 or 32 and nothing is read or written
 // outside the n x n arrays.
 #pragma once
-#include "dense_kernels.h"
+#include "hm_types.h"
 
 #define SM_NT 256       // threads of a product workgroup
 

@@ -855,7 +855,7 @@ class IteratedMSKalmanFilter(IteratedKalmanFilter):
         l = np.sqrt((d * d).sum(axis=1))
         l0 = st.l0[:, 0]
         k = self.kappa * (1 - l0 / l)
-        c = self.kappa * l0 / (l * l * l)           # (the operations of the native spring_blocks, csrc/ekf.hip: same bits)
+        c = self.kappa * l0 / (l * l * l)           # (the operations of the native spring_blocks, csrc/ctx.h: same bits)
         return np.column_stack((k + c * d[:, 0] * d[:, 0], c * d[:, 0] * d[:, 1], k + c * d[:, 1] * d[:, 1]))
 
     def _bar_pattern(self):

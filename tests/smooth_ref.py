@@ -20,7 +20,7 @@ LD = np.longdouble
 
 
 def spring_blocks(bars, l0, kappa, X):
-    """Per spring (Bxx, Bxy, Byy) of dfdy at the vertices of X (csrc/ekf.hip spring_blocks)."""
+    """Per spring (Bxx, Bxy, Byy) of dfdy at the vertices of X (csrc/ctx.h spring_blocks)."""
     X = np.asarray(X, np.float64).reshape(-1)
     bars = np.asarray(bars).reshape(-1, 2)
     a, b = bars[:, 0], bars[:, 1]
