@@ -695,6 +695,33 @@ int hm_body_rec_trace_maps(hm_ctx_t h, int L, const int32_t *q, int64_t *c, uint
 int hm_body_rec_trace_null(hm_ctx_t h, int L, const int32_t *q, const double *vb, double *tmax, double *tmin,
                            uint32_t *ge, uint32_t *le);
 
+/* The record against the deformation of its own tissue, and the deformation's brightness taken out of it in place
+ * (hydra_mi/deform.py; csrc/deform_kernels.h; tests/deform_ref.py restates both calls in NumPy).
+ * Exact integers throughout.  Notation as above: F recorded frames, v_k(p) the record's byte.  t(p) = tri_of_pixel[p], the
+ * body map's triangle of pixel p: the index hm_body_map returns, the same t as in hm_strain_tri, -1 off the map.  T must be
+ * the handle's number of triangles: otherwise HM_ERR_ARG with both numbers.  Waiting and state errors are those of
+ * hm_body_rec_seed_sums; a refusal leaves the record usable.
+ *   tri_maps    every pixel against the trace of its own triangle.  q[k * T + t] are whole numbers, |q| <= 32767:
+ *                 c[p]  = sum_k v_k(p) q[k * T + t(p)]  (int64),
+ *                 w1[p] = sum_k v_k(p),  w2[p] = sum_k v_k(p)^2  (uint64);
+ *               one full W*H plane each, 0 outside the map and the box.  Any output may be NULL.  The record is not changed.
+ *               HM_ERR_ARG with the numbers for a |q| > 32767 (the first offender's frame and triangle are named) and when
+ *               F x F x 255 x 32767 >= 2^63, the bound of trace_maps: below it every sum and the host's F c - w1 u1_t
+ *               (u1_t = sum_k q[k * T + t]) are exact in 64 bits.  The frames are split over the grid in runs of
+ *               hm_ctx_tune "rec_tm_frames" (1..256, default 64); the partial sums of a run are 32-bit and meet in 64-bit
+ *               integer atomics: the same result in any order and for every value of the key.  (trace_maps with L = T
+ *               traces would do T times the work and return T planes, of which a pixel needs one.)
+ *   tri_gain    m[k * T + t] is uint16, 0..65535.  The record is rewritten in place: for every frame k and map pixel p
+ *                 v_k(p) <- min(255, (v_k(p) m[k * T + t(p)] + 2048) >> 12)   in unsigned 32-bit integers,
+ *               a gain of m / 4096: 0 to just under 16, m = 4096 the identity (the rule returns v exactly).  Pixels off the
+ *               map and the padding stay 0.  *clipped (may be NULL) is the number of (frame, pixel) values whose unclamped
+ *               result exceeded 255.  The rule is pointwise: the frames are rewritten where they lie, no scratch.  Every
+ *               hm_body_rec_* call afterwards, fetch included, sees the rewritten frames.  NOT reversible, as
+ *               hm_body_rec_shift is not (what the rounding and the clamp merge stays merged).  Nothing else on the handle
+ *               changes. */
+int hm_body_rec_tri_maps(hm_ctx_t h, int T, const int32_t *q, int64_t *c, uint64_t *w1, uint64_t *w2);
+int hm_body_rec_tri_gain(hm_ctx_t h, int T, const uint16_t *m, uint64_t *clipped);
+
 /* Residual motion of the kept registered video: the shift of every patch of every frame found against a template
  * and taken out of the record in place (hydra_mi/stabilize.py).  Waiting, errors and state are
  * those of hm_body_rec_seed_sums: the calls wait for the warps queued so far and for their results, fail with

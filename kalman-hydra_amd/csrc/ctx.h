@@ -162,6 +162,7 @@ struct RecState {
     int res_frames = 8;              // hm_ctx_tune "rec_res_frames": frames per run of k_rec_residual (hm_body_rec_residual_*)
     int map_frames = 64;             // hm_ctx_tune "rec_map_frames": frames per run of k_rec_trace_maps (hm_body_rec_trace_maps)
     int null_frames = 256;           // hm_ctx_tune "rec_null_frames": frames per run of k_rec_trace_null (hm_body_rec_trace_null)
+    int tm_frames = 64;              // hm_ctx_tune "rec_tm_frames": frames per run of k_rec_tri_maps (hm_body_rec_tri_maps)
     unsigned long long max = 0;      // the budget in bytes
     RecBox box = {0, 0, 0, 0, 0, 0, 0};
     std::vector<uint8_t *> chunks;

@@ -307,4 +307,5 @@ struct RecBox {
 #define REC_RES_MAX (1 << 24)          // the most frames of a run of k_rec_residual (hm_ctx_tune "rec_res_frames"; REC_MAX_FRAMES)
 #define REC_MAP_MAX 256                // the most frames of a run of k_rec_trace_maps (hm_ctx_tune "rec_map_frames"): 32-bit sums hold
 #define REC_NULL_MAX 256               // the most frames of a run of k_rec_trace_null (hm_ctx_tune "rec_null_frames"): 255 x 32767 x 256 < 2^31
+#define REC_TM_MAX 256                 // the most frames of a run of k_rec_tri_maps (hm_ctx_tune "rec_tm_frames"): 255 x 32767 x 256 < 2^31
 #define REC_RES_LMAX 65536             // hm_body_rec_residual_*: a label 0 .. L - 1 shares a dword with its 16-bit weight

@@ -1,7 +1,7 @@
 // The registered video kept on the device (hm_body_rec_*): the record itself, the reductions over it, its residual motion
 // (match, shift, field, warp), the running baseline, the events per pixel and the residual of the cells' model.  Host orchestration and C-ABI
 // (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h, events_kernels.h, residual_kernels.h and
-// network_kernels.h and network_null_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses
+// network_kernels.h, network_null_kernels.h and deform_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses
 // rec, the body map (body.tri, body.h_tri), the
 // registered plane (body.reg) and the statistics' counters, and reads W, H, device, own and stream.  readout.hip queues the
 // warp: it reserves a frame's slot and queues the copy into it through body_rec_slot and body_rec_queue_copy, and this file
@@ -14,6 +14,7 @@
 #include "residual_kernels.h"
 #include "network_kernels.h"
 #include "network_null_kernels.h"
+#include "deform_kernels.h"
 #include <cmath>
 #include <algorithm>
 #include <cstring>
@@ -615,6 +616,106 @@ extern "C" int hm_body_rec_trace_null(hm_ctx_t h, int L, const int32_t *q, const
     }
     if (ge) HM_TRY(rec_expand_planes(h, a.ge, 1, ge));
     if (le) HM_TRY(rec_expand_planes(h, a.le, 1, le));
+    return HM_OK;
+}
+
+// ---- the record against the deformation of its own tissue (deform_kernels.h) -----------------------------------------
+// What both calls open with: T is the handle's number of triangles, the helper joined, a record with frames.
+static int rec_tri_open(hm_ctx *h, const char *who, int T)
+{
+    HM_ARG(T == h->T, "%s: %d triangles given, the mesh has %d", who, T, h->T);
+    HM_JOIN_LAZY(h);
+    return body_rec_ready(h, who);
+}
+
+// queue t(p), the body map cut to the box (-1 in the padding and off the map), into d_tri
+static void rec_tri_plane(hm_ctx *h, int *d_tri)
+{
+    const RecBox &b = h->rec.box;
+    const int nb = b.pitch * b.bh;
+    hipLaunchKernelGGL(k_rec_box_labels, dim3(hm_cdiv(nb, 256)), dim3(256), 0, h->stream, h->W, b, (const int *)h->body.tri,
+                       (const int *)h->body.tri, d_tri);
+}
+
+extern "C" int hm_body_rec_tri_maps(hm_ctx_t h, int T, const int32_t *q, int64_t *c, uint64_t *w1, uint64_t *w2)
+{
+    HM_ARG(h && q, "hm_body_rec_tri_maps: NULL handle or traces");
+    HM_TRY(rec_tri_open(h, "hm_body_rec_tri_maps", T));
+    const int F = h->rec.frames;
+    // |F c| and |w1 u1| <= F^2 x 255 x 32767
+    HM_ARG((unsigned __int128)F * F * 255u * (unsigned)REC_TM_QMAX < ((unsigned __int128)1 << 63),
+           "hm_body_rec_tri_maps: F x F x 255 x 32767 = %d x %d x 255 x 32767 could pass 2^63", F, F);
+    const size_t ft = (size_t)F * T;
+    std::vector<int16_t> q16(ft);
+    for (size_t i = 0; i < ft; i++) {
+        HM_ARG(q[i] >= -REC_TM_QMAX && q[i] <= REC_TM_QMAX, "hm_body_rec_tri_maps: q %d (frame %zu, triangle %zu) outside -%d..%d",
+               (int)q[i], i / (size_t)T, i % (size_t)T, REC_TM_QMAX, REC_TM_QMAX);
+        q16[i] = (int16_t)q[i];
+    }
+    if (!(c || w1 || w2)) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const RecBox &b = h->rec.box;
+    const size_t nb = (size_t)b.pitch * b.bh;
+    RecTriMaps g;
+    int *d_tri = nullptr;
+    int16_t *d_q = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_tri = cv.take<int>(nb);
+        d_q = cv.take<int16_t>(c ? ft : 0);
+        g.c = c ? cv.take<unsigned long long>(nb) : nullptr;
+        g.w1 = w1 || w2 ? cv.take<unsigned long long>(nb) : nullptr;
+        g.w2 = w1 || w2 ? cv.take<unsigned long long>(nb) : nullptr;
+    }));
+    rec_tri_plane(h, d_tri);
+    if (c) {
+        HM_HIP(hipMemcpyAsync(d_q, q16.data(), ft * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+        HM_HIP(hipMemsetAsync(g.c, 0, nb * 8, h->stream));
+    }
+    if (g.w1) {
+        HM_HIP(hipMemsetAsync(g.w1, 0, nb * 8, h->stream));
+        HM_HIP(hipMemsetAsync(g.w2, 0, nb * 8, h->stream));
+    }
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.F = F; g.T = T; g.run = h->rec.tm_frames; g.tri = d_tri; g.q = d_q;
+    const dim3 grid(hm_cdiv((int)(nb >> 2), 256), std::min(hm_cdiv(F, g.run), 65535));
+    if (c) hipLaunchKernelGGL(k_rec_tri_maps<1>, grid, dim3(256), 0, h->stream, g);
+    else hipLaunchKernelGGL(k_rec_tri_maps<0>, grid, dim3(256), 0, h->stream, g);
+    HM_HIP(hipGetLastError());
+    HM_HIP(hipStreamSynchronize(h->stream));
+    if (c) HM_TRY(rec_expand_planes(h, g.c, 1, c));
+    if (w1) HM_TRY(rec_expand_planes(h, g.w1, 1, w1));
+    if (w2) HM_TRY(rec_expand_planes(h, g.w2, 1, w2));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_tri_gain(hm_ctx_t h, int T, const uint16_t *m, uint64_t *clipped)
+{
+    HM_ARG(h && m, "hm_body_rec_tri_gain: NULL handle or gains");
+    HM_TRY(rec_tri_open(h, "hm_body_rec_tri_gain", T));
+    const RecBox &b = h->rec.box;
+    const int F = h->rec.frames;
+    const size_t nb = (size_t)b.pitch * b.bh, ft = (size_t)F * T;
+    RecTriGain g;
+    int *d_tri = nullptr;
+    uint16_t *d_m = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        d_tri = cv.take<int>(nb);
+        d_m = cv.take<uint16_t>(ft);
+        g.clipped = cv.take<unsigned long long>(1);
+    }));
+    rec_tri_plane(h, d_tri);
+    HM_HIP(hipMemcpyAsync(d_m, m, ft * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    HM_HIP(hipMemsetAsync(g.clipped, 0, sizeof(unsigned long long), h->stream));
+    g.b = b; g.chunks = (uint8_t *const *)h->rec.tab; g.F = F; g.T = T; g.tri = d_tri; g.m = d_m;
+    const int chunks = hm_cdiv(F, b.fpc), groups = hm_cdiv(std::min(F, b.fpc), REC_TG_FRAMES);
+    hipLaunchKernelGGL(k_rec_tri_gain, dim3(hm_cdiv((int)(nb >> 2), 256), std::min(groups, 65535), std::min(chunks, 65535)), dim3(256), 0,
+                       h->stream, g);
+    HM_HIP(hipGetLastError());
+    unsigned long long n = 0;
+    HM_HIP(hipMemcpyAsync(&n, g.clipped, sizeof n, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
+    if (clipped) *clipped = n;
     return HM_OK;
 }
 

@@ -626,6 +626,38 @@ class Renderer:
             raise ValueError("body_rec_warp: q of %d frames for a record of %d" % (q.shape[0], F))
         _lib.check(_lib.lib().hm_body_rec_warp(self._h, int(B), _lib.ptr(q), _lib.ptr(valid)), "hm_body_rec_warp")
 
+    # -- the record against the deformation of its own tissue (hm_body_rec_tri_maps / _tri_gain; hydra_mi.deform) --
+    def _tri_table(self, a, dtype, who):
+        """-> `a` as a contiguous (F, T) array of exactly `dtype`, one row per recorded frame and a column per triangle"""
+        a = np.asarray(a)
+        F, T = self.body_rec_count(), self.tri.shape[0]
+        if a.dtype != dtype or a.ndim != 2 or a.shape[1] != T or (F and a.shape[0] != F):     # (F 0: the call says why)
+            raise ValueError("%s: %s of shape %r for %d frames and %d triangles (need %s, frames x triangles)" % (
+                who, a.dtype, a.shape, F, T, np.dtype(dtype).name))
+        return np.ascontiguousarray(a)
+
+    def body_rec_tri_maps(self, q, want=("c", "w1", "w2")):
+        """hm_body_rec_tri_maps: one int32 trace per triangle, q (F, T) with |q| <= 32767 -> (c, w1, w2): c (H, W) int64, the
+        sum over the recorded frames of every pixel times the trace of its own triangle; w1, w2 (H, W) uint64, the sums of
+        every pixel and of its square (0 outside the map); None for one that is not in `want`."""
+        q = self._tri_table(q, np.int32, "body_rec_tri_maps")
+        H, W = self.ny, self.nx
+        o = {"c": np.empty((H, W), np.int64) if "c" in want else None}
+        for key in ("w1", "w2"):
+            o[key] = np.empty((H, W), np.uint64) if key in want else None
+        _lib.check(_lib.lib().hm_body_rec_tri_maps(self._h, q.shape[1], _lib.ptr(q), _lib.ptr(o["c"]), _lib.ptr(o["w1"]),
+                                                   _lib.ptr(o["w2"])), "hm_body_rec_tri_maps")
+        return o["c"], o["w1"], o["w2"]
+
+    def body_rec_tri_gain(self, m):
+        """hm_body_rec_tri_gain: rewrite the record in place, every map pixel of every frame times the gain of its own
+        triangle in that frame, min(255, (v m + 2048) >> 12); m (F, T) uint16, 4096 the identity -> the number of values
+        that were clipped at 255.  Not reversible."""
+        m = self._tri_table(m, np.uint16, "body_rec_tri_gain")
+        n = ctypes.c_uint64(0)
+        _lib.check(_lib.lib().hm_body_rec_tri_gain(self._h, m.shape[1], _lib.ptr(m), ctypes.byref(n)), "hm_body_rec_tri_gain")
+        return int(n.value)
+
     # -- the running baseline per pixel of the record (hm_body_rec_planes / _stats_add; hydra_mi.detrend) -----
     PLANES = {"recorded": 0, "baseline": 1, "excess": 2, "dff": 3}
 

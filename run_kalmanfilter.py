@@ -58,6 +58,14 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      patches filled in by their neighbours, the frames sampled bilinearly.  The choice for the smooth
                      sub-pixel motion a tracker leaves; patch for regions that move rigidly against each other.  The states
                      file then also gets stab_q (frames x patches x 2, int16, (dx, dy) in 1/16 px).
+    --deform-correct with --rois or --demix: take the brightness of compressed tissue out of the kept registered video
+                     (hydra_mi.deform), after --stabilize and before everything that reads the record: every pixel of every
+                     frame times (J / Jref)^gamma of its home triangle, J the triangle's area ratio at the filtered states the
+                     frames were warped with (also with --smooth), Jref its median, gamma fitted from the triangles' mean
+                     brightness (--deform-gamma G: taken as given, 0..3).  The states file gets deform_gamma, deform_fit_r2,
+                     deform_gain (frames x triangles, uint16, 4096 = 1), deform_clipped, and deform_r_before,
+                     deform_r_after: every pixel's correlation with its triangle's Jref / J either side of the correction.
+                     What is summed while tracking keeps the uncorrected frames: tri_means, body_*, point_means of --points.
     --detrend        with --find-points: search the summary images of the excess video instead of the raw one (hydra_mi.detrend):
                      every pixel of the kept registered video less its own running baseline, the value at rank
                      q (n - 1) // 100 of the n frames k - half .. k + half (--detrend-half, default 20; --detrend-q, default
@@ -152,6 +160,7 @@ from hydra_mi import kalman
 from hydra_mi import network
 from hydra_mi import demix
 from hydra_mi import residual
+from hydra_mi import deform
 from hydra_mi import detrend
 from hydra_mi import events
 from hydra_mi import roi
@@ -211,6 +220,11 @@ def main(argv=None):
     parser.add_argument("--stab-mode", default="patch", choices=stabilize.MODES,
                         help="patch: one whole-pixel shift per patch; field: a smooth sub-pixel shift field between the patch "
                              "centres (stab_q in the states file)")
+    parser.add_argument("--deform-correct", action="store_true",
+                        help="with --rois or --demix: correct the kept registered video for tissue compression before the cells "
+                             "are read out (deform_* arrays)")
+    parser.add_argument("--deform-gamma", default=None, type=float, metavar="G",
+                        help="with --deform-correct: the exponent of brightness ~ J^-G (0..3) instead of the fitted one")
     parser.add_argument("--detrend", action="store_true",
                         help="with --find-points: find the cells in the excess video, every pixel less its running baseline "
                              "(detrend_* arrays)")
@@ -314,6 +328,10 @@ def main(argv=None):
             parser.error("--stabilize works on the kept record: it needs --rois or --demix")
         if not (4 <= args.stab_patch <= 64 and 0 <= args.stab_search <= 8 and args.stab_passes >= 1):
             parser.error("--stabilize needs a --stab-patch in 4..64, a --stab-search in 0..8 and at least one pass")
+    if args.deform_correct and not (args.rois or keep_record):
+        parser.error("--deform-correct works on the kept record: it needs --rois or --demix")
+    if args.deform_gamma is not None and not (args.deform_correct and 0.0 <= args.deform_gamma <= deform.GAMMA_MAX):
+        parser.error("--deform-gamma needs --deform-correct and an exponent in 0..%g" % deform.GAMMA_MAX)
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
 
@@ -349,7 +367,8 @@ def main(argv=None):
             need = record_bytes(probe, max(capture.frames.shape[0] - 1, 1))
             if need > budget:
                 print("The registered video takes %d bytes on the device, --rois-max-gb allows %d: no ROIs, %sthe disc "
-                      "read-out instead" % (need, budget, "no stabilisation, " if args.stabilize else ""))
+                      "read-out instead" % (need, budget, ("no stabilisation, " if args.stabilize else "") +
+                                            ("no deformation correction, " if args.deform_correct else "")))
                 if keep_record:
                     print("No running baseline either: no --detrend, --resummarize or --dff-video")
                 keep = False
@@ -433,6 +452,20 @@ def main(argv=None):
         print("Stabilised%s: %d patches of %d px, search %d, %d passes: %.1f %% fallbacks, mean |shift| %.3f px" % (
             " (field)" if args.stab_mode == "field" else "", est["shifts"].shape[1], args.stab_patch, args.stab_search,
             args.stab_passes, 100.0 * est["fallback"].mean(), np.abs(moved).sum(2).mean()))
+    if args.deform_correct and body is not None and body.keep and len(states):
+        # after the stabiliser, before everything that reads the kept record; at the filtered states, those the frames were
+        # warped with.  The stabiliser has moved pixels by a few px, across triangle seams too: the gain is that of the
+        # pixel's home triangle regardless.
+        dc = deform.correct(body, np.array(states), gamma=args.deform_gamma)
+        extra.update(deform_gamma=np.float64(dc["gamma"]), deform_fit_r2=np.float64(dc["fit_r2"]), deform_gain=dc["gain"],
+                     deform_clipped=np.uint64(dc["clipped"]), deform_r_before=dc["r_before"].astype(np.float32),
+                     deform_r_after=dc["r_after"].astype(np.float32))
+        with np.errstate(invalid="ignore"):
+            med = [float(np.nanmedian(np.abs(dc[key]))) if np.isfinite(dc[key]).any() else np.nan for key in ("r_before", "r_after")]
+        print("Deformation corrected: gamma %.3f (%s, r2 %.3f), gains %.3f .. %.3f over %d triangles, %d values clipped, "
+              "median |r| with the area change %.3f -> %.3f" % (
+                  dc["gamma"], "fitted" if dc["fitted"] else "given" if args.deform_gamma is not None else "nothing to fit from",
+                  dc["fit_r2"], dc["gain"].min() / 4096.0, dc["gain"].max() / 4096.0, dc["gain"].shape[1], dc["clipped"], *med))
     det_kind = "excess" if args.detrend else "recorded" if args.resummarize else None
     if det_kind is not None and not (body is not None and body.keep and len(states)):
         det_kind = None
