@@ -448,19 +448,28 @@ int hm_op_smooth_gemm(int device, int which, int n, const double *A, const doubl
  *          3 mask     R = 255 inside the mesh, G = label / 256, B = label % 256 of the palette
  *                     (`palette`: one label per triangle, -1 or NULL: 255, 255), plus the wireframe
  *          4 flowx, 5 flowy  the rendered flow plane, floor(255 (p - min) / (max - min)) in f64
- *                     (0 where max == min), in all three channels
+ *                     (0 where max == min), in all three channels.  min and max are taken over the
+ *                     finite pixels of the plane: a pixel that is NaN or +-inf (a diverged state: a
+ *                     velocity beyond binary32) takes no part in them and shows 0; with no finite
+ *                     pixel, or max == min (-0 equals +0), every pixel shows 0
  * The wireframe: the three edges of every triangle (interior edges twice), end points rint(vertex),
  * pixel i = 0..n, n = max(|dx|, |dy|): x0 + floor((2 i dx + n) / (2 n)); B = min(255, B + 128 count).
- * Segments with an end point beyond +-2^20 px are not drawn.
- * hm_view_dev writes into device memory d_bgr and does not wait; `stream` (may be NULL) waits for
- * the view on the device, so a copy queued there reads it whole.  The observed frame is read when
- * the view runs: keep it in place until then.
+ * A triangle whose vertices round to one pixel counts three there.  Segments are clipped to the frame
+ * pixel by pixel; one with an end point that is NaN, infinite or, after rounding, beyond +-2^20 px
+ * (exactly 2^20 is drawn) is left out whole.  Where triangles overlap, G and B of the mask view are the
+ * sums of their colours, each saturated at 255, as the mask render has them.
+ * hm_view_dev writes into device memory d_bgr (W*H*3 bytes for any W*H, 4-byte aligned: HM_ERR_ARG
+ * otherwise) and does not wait; `stream` (may be NULL) waits for the view on the device, so a copy
+ * queued there reads it whole.  The observed frame is read when the view runs: keep it in place until
+ * then.
  * hm_view_forces: the overlay with every channel halved, then the arrows of plotforces in four layers,
  * each over the one before: orig -> pred white, pred -> pred + 10 tv (255, 0, 0), + 10 fv (0, 255, 0),
  * + 10 mv (0, 0, 255) (B, G, R); orig, pred, tv, fv, mv: the 2N vertex coordinates.  End points are
  * truncated as C int() does; the head is two segments from the tip at +-45 degrees, 0.1 of the shaft:
  * tip + rint(K (dx - dy), K (dy + dx)) and tip + rint(K (dx + dy), K (dy - dx)), (dx, dy) = start - tip,
- * K = 0.1 sqrt(1/2).  Not the reference's: no 2x upscale, thickness 1, no legend text. */
+ * K = 0.1 sqrt(1/2).  An arrow with an end point (before truncation) that is NaN, infinite or beyond
+ * +-2^20 is left out, heads included; one of length 0 is the pixel of its start; what falls off the
+ * frame is clipped.  Not the reference's: no 2x upscale, thickness 1, no legend text. */
 int hm_view(hm_ctx_t h, const double *X, int which, const int32_t *palette, uint8_t *bgr);
 int hm_view_dev(hm_ctx_t h, const double *X, int which, const int32_t *palette, void *d_bgr, void *stream);
 int hm_view_forces(hm_ctx_t h, const double *X, const double *orig, const double *pred, const double *tv,

@@ -121,6 +121,7 @@ extern "C" int hm_view_dev(hm_ctx_t h, const double *X, int which, const int32_t
 {
     HM_ARG(h && d_bgr, "hm_view_dev: NULL argument");
     HM_ARG(which >= VIEW_RAW && which <= VIEW_FLOWY, "hm_view_dev: view %d outside 0..%d", which, VIEW_FLOWY);
+    HM_ARG(((uintptr_t)d_bgr & 3) == 0, "hm_view_dev: d_bgr is not 4-byte aligned");      // (k_view_compose writes dwords)
     int rc = view_queue(h, X, which, palette, nullptr, (uint8_t *)d_bgr, "hm_view_dev");
     if (rc) return rc;
     if (stream) {

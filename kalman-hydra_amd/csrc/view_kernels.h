@@ -2,6 +2,9 @@
 // flow tool (reference src/optical_flow_ext.cpp:172-281, 336-389) as kernels.  Every view is H x W x 3 uint8, B, G, R,
 // rows top to bottom.  Everything below is exact integer or f64 arithmetic (the library builds with -ffp-contract=off),
 // except atan2f in the colour wheel, so a NumPy restatement reproduces it bit for bit (tests/view_ref.py).
+// The flow views (flowx, flowy) show floor(255 (p - min) / (max - min)) with min and max over the FINITE pixels of the
+// plane: a pixel that is NaN or +-inf takes no part in them and shows 0; with no finite pixel, or max == min (-0 == +0),
+// every pixel shows 0.  No conversion of a NaN or an infinity to an integer is ever formed.
 #pragma once
 #include "hm_common.h"
 #include "hm_types.h"
@@ -47,7 +50,9 @@ __global__ __launch_bounds__(256) void k_view_wire(const int *__restrict__ tri, 
               [&](int p) { atomicAdd(&count[p], 1u); });
 }
 
-// min / max of a float plane as order-preserving unsigned keys (mm[0] = min key, mm[1] = max key; NaNs are skipped)
+// min / max of a float plane as order-preserving unsigned keys (mm[0] = min key, mm[1] = max key).  A value that is not
+// finite (NaN, +-inf: a diverged state's velocities) takes no part; with no finite value at all mm[0] > mm[1] stays.
+__device__ __forceinline__ bool d_ffinite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ unsigned d_fkey(float f)
 {
     const unsigned u = __float_as_uint(f);
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(256) void k_view_minmax(const float *__restrict__ p
     unsigned lo = 0xffffffffu, hi = 0u;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const float v = p[i];
-        if (v != v) continue;
+        if (!d_ffinite(v)) continue;
         const unsigned k = d_fkey(v);
         lo = min(lo, k);
         hi = max(hi, k);
@@ -112,7 +117,7 @@ __device__ __forceinline__ unsigned d_view_px(const ViewArgs &a, int p, float fm
     case VIEW_FLOWY: {
         unsigned v = 0;
         const float f = a.flow[p];
-        if (fmax != fmin && f == f) v = (unsigned)floor(255.0 * ((double)f - (double)fmin) / ((double)fmax - (double)fmin));
+        if (fmax != fmin && d_ffinite(f)) v = (unsigned)floor(255.0 * ((double)f - (double)fmin) / ((double)fmax - (double)fmin));
         b = g = r = v;
         break;
     }

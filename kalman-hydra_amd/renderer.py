@@ -151,7 +151,8 @@ class Renderer:
         return out
 
     def view_dev(self, X, which, d_out, stream=None):
-        """hm_view_dev: queue the view into device memory d_out (W*H*3 bytes); `stream` waits for it on the device."""
+        """hm_view_dev: queue the view into device memory d_out (W*H*3 bytes, 4-byte aligned); `stream` waits for it on
+        the device."""
         from .videoio import VIEWS
         x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
         pal = self._view_palette() if which == "mask" else None

@@ -51,17 +51,25 @@ def _blue(base, wire):
 
 
 def norm_plane(p):
-    """floor(255 (p - min) / (max - min)) in f64, 0 when max == min"""
+    """floor(255 (p - min) / (max - min)) in f64, min and max over the finite pixels.  A pixel that is not finite (NaN,
+    +-inf) takes no part in them and shows 0; with no finite pixel, or max == min (-0 == +0), every pixel shows 0.  No
+    non-finite value is ever converted to an integer."""
     p = np.asarray(p, np.float32)
-    lo, hi = np.float64(np.nanmin(p)), np.float64(np.nanmax(p))
+    fin = np.isfinite(p)
+    out = np.zeros(p.shape, np.uint8)
+    if not fin.any():
+        return out
+    q = p[fin].astype(np.float64)
+    lo, hi = q.min(), q.max()
     if hi == lo:
-        return np.zeros(p.shape, np.uint8)
-    return np.floor(255.0 * (p.astype(np.float64) - lo) / (hi - lo)).astype(np.uint8)
+        return out
+    out[fin] = np.floor(255.0 * (q - lo) / (hi - lo)).astype(np.int64).astype(np.uint8)
+    return out
 
 
-def view(which, render, tri, X, obs=None, ids=None):
+def view(which, render, tri, X, obs=None, ids=None, wire=None):
     """render: Renderer.render() at X -> (im, fx, fy, m); obs: the observed frame (overlay);
-    ids: 256 G + B of the mask palette per pixel (mask view)"""
+    ids: 256 G + B of the mask palette per pixel (mask view); wire: wire_count(tri, X, W, H) where the caller has it"""
     im, fx, fy, m = render
     H, W = im.shape
     if which == "raw":
@@ -69,15 +77,23 @@ def view(which, render, tri, X, obs=None, ids=None):
     if which in ("flowx", "flowy"):
         v = norm_plane(fx if which == "flowx" else fy)
         return _stack(v, v, v)
-    wire = wire_count(tri, X, W, H)
+    if wire is None:
+        wire = wire_count(tri, X, W, H)
     if which == "texture":
         return _stack(_blue(im, wire), im, im)
     if which == "overlay":
         return _stack(_blue(np.zeros_like(im), wire), im, np.asarray(obs, np.uint8))
     if which == "mask":
-        ids = np.asarray(ids, np.int64)
-        return _stack(_blue(ids % 256, wire), ids // 256, np.where(m > 0, 255, 0))
+        return ids_view(ids, wire, m)
     raise ValueError(which)
+
+
+def ids_view(ids, wire, m):
+    """The mask view of a per-pixel id image (256 G + B of the mask render, oracle/ekf_ref.render(..., labels=palette)[4]),
+    the wireframe counts and the mask render m: B = min(255, id % 256 + 128 wire), G = id // 256, R = 255 where m > 0"""
+    ids = np.asarray(ids, np.int64)
+    assert ids.min() >= 0 and ids.max() <= 65535
+    return _stack(_blue(ids % 256, np.asarray(wire, np.int64)), ids // 256, np.where(np.asarray(m) > 0, 255, 0))
 
 
 def uniform_ids(m, label):
@@ -152,9 +168,34 @@ def wheel(fx, fy):
     return out
 
 
-def flow_preview(frames, fx, fy):
+def wheel64(fx, fy):
+    """The wheel once more, in binary64 throughout and with Python's own atan2, written independently of `wheel` (a
+    direct table lookup per vector, no masks): what the colour code means, free of binary32 rounding.  Where `wheel`
+    and the kernel differ by an ulp of atan2f, both stay within one level of this."""
+    import math
+    fx = np.asarray(fx, np.float32)
+    fy = np.asarray(fy, np.float32)
+    tab = wheel_table()
+    out = np.zeros(fx.shape + (3,), np.uint8)
+    for idx in np.ndindex(fx.shape):
+        x, y = float(fx[idx]), float(fy[idx])
+        if not (math.isfinite(x) and math.isfinite(y) and abs(x) < 1e9 and abs(y) < 1e9):
+            continue
+        ux, uy = x / 15.0, y / 15.0
+        rad = math.sqrt(ux * ux + uy * uy)
+        fk = (math.atan2(-uy, -ux) / math.pi + 1.0) / 2.0 * 54.0
+        k0 = int(fk)
+        f = fk - k0
+        for b in range(3):
+            col = (1.0 - f) * tab[k0, b] / 255.0 + f * tab[(k0 + 1) % 55, b] / 255.0
+            col = rad * col if rad <= 1.0 else 0.75 * col
+            out[idx + (2 - b,)] = int(255.0 * col)
+    return out
+
+
+def flow_preview(frames, fx, fy, wheel_fn=wheel):
     f = np.asarray(frames, np.int64)
     if f.ndim == fx.ndim:
         f = np.repeat(f[..., None], 3, axis=-1)
-    w = wheel(fx, fy).astype(np.int64)
+    w = wheel_fn(fx, fy).astype(np.int64)
     return ((2 * (2 * f + 3 * w) + 5) // 10).astype(np.uint8)
