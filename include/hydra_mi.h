@@ -922,6 +922,81 @@ int hm_avi_open(const char *path, int W, int H, int fps, uint64_t riff_limit, hm
 int hm_avi_write(hm_avi_t avi, const uint8_t *bgr);
 int hm_avi_close(hm_avi_t avi);
 
+/* The same container around compressed frames.  codec HM_AVI_RAW: exactly hm_avi_open (frames through hm_avi_write).
+ * codec HM_AVI_MJPG: Motion-JPEG, one complete JPEG file per frame through hm_avi_write_chunk(data, n), n in 1..2^31-1.
+ * The stream's fccHandler and biCompression are 'MJPG' (biBitCount 24, biSizeImage that of the raw frame), dwSampleSize is 0,
+ * the chunks are '00dc', written as they come and followed by one zero byte when n is odd; 'idx1' (first RIFF, every
+ * entry with AVIIF_KEYFRAME) and 'ix00' hold each chunk's own n, 'indx' names '00dc'.  dwSuggestedBufferSize (avih and
+ * strh: the largest n + 8) and dwMaxBytesPerSec (the largest n x fps) are patched at close.  A chunk that would take the
+ * RIFF past riff_limit (0: 1 GiB; at least 16384), counted with its padding and the indexes as hm_avi_write counts, opens
+ * the next 'AVIX' RIFF; a single chunk larger than the limit gets a RIFF to itself.  hm_avi_write refuses a file opened
+ * for MJPG and hm_avi_write_chunk one opened raw (HM_ERR_ARG); any other codec is refused with its number. */
+#define HM_AVI_RAW 0
+#define HM_AVI_MJPG 1
+int hm_avi_open_codec(const char *path, int W, int H, int fps, uint64_t riff_limit, int codec, hm_avi_t *out);
+int hm_avi_write_chunk(hm_avi_t avi, const uint8_t *data, uint64_t n);
+
+/* Motion-JPEG: a baseline sequential JPEG encoder (ITU-T T.81) on the device, for the frames the views leave there.
+ * Integers only; tests/mjpeg_ref.py restates every rule below and the device gives the same bytes.
+ *
+ *   Frame       H x W x channels bytes, rows top to bottom; channels 1 (grey, one component) or 3 (B G R in memory, coded
+ *               as Y Cb Cr, every component at full resolution: 4:4:4).
+ *   Colour      Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *               Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *               Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16        (>>: arithmetic; all in 0..255)
+ *               With one channel the sample is the byte.  128 is taken off every sample: s in -128..127.
+ *   Blocks      bw = ceil(W / 8) by bh = ceil(H / 8) blocks of 8 x 8; pixels past the frame repeat its last column and row.
+ *   DCT         T[u][x] = rint(2^13 (c(u) / 2) cos((2x + 1) u pi / 16)), c(0) = 1 / sqrt 2, c(u > 0) = 1.
+ *               rows:    r[y][u]  = (sum_x T[u][x] s[y][x] + 2^10) >> 11      (two fractional bits are kept)
+ *               columns: c8[v][u] = (sum_y T[v][y] r[y][u] + 2^11) >> 12      (v: vertical frequency)
+ *               c8 is the coefficient in eighths, c = c8 / 8: the quantiser sees three fractional bits, as libjpeg's does.
+ *               32-bit sums; DESIGN section 21 shows that none overflows and bounds |c - exact| by E = 0.66.
+ *   Tables      Quantisation: Annex K tables K.1 (Y, grey) and K.2 (Cb, Cr) scaled as libjpeg does: s = 5000 / quality
+ *               (integer division) below quality 50, else 200 - 2 quality; q = min(255, max(1, (v s + 50) / 100)).
+ *               Huffman: the typical tables K.3 - K.6, table 0 for Y / grey and table 1 for Cb and Cr.
+ *   Quantise    k = sign(c) floor((2 |c| + q) / (2 q)), in integers sign(c8) ((2 |c8| + 8 q) / (16 q)) with integer
+ *               division; then zigzag order.
+ *   Coding      Per block: the DC difference to the previous block of the same component in the restart interval (0 for
+ *               the first) as its category's code and the category's low bits (of diff - 1 when negative); the AC
+ *               coefficients as (run, size) codes with the value's low bits likewise, ZRL (F0) for every 16 zeros of a
+ *               run before a non-zero coefficient, EOB (00) if and only if the block ends in a zero.  With three
+ *               components the blocks of a position follow each other: Y, Cb, Cr.  Bits fill bytes from the most
+ *               significant end.
+ *   Intervals   A restart interval is restart_rows rows of blocks (the last may have fewer): ri = bw min(restart_rows, bh)
+ *               positions.  It ends padded to a byte with 1-bits; every FF byte of it (the padded one included) is
+ *               followed by 00; RSTm (FF D0+m, m = the interval's index mod 8) follows every interval but the last,
+ *               EOI (FF D9) the last.  The DC prediction starts again at 0.
+ *   Header      SOI; APP0 JFIF 1.01, no units, 1:1; DQT table 0 (and 1 with three components), 8-bit, zigzag order;
+ *               SOF0 (8 bits, H, W, components 1.. with sampling 1x1 and tables 0, 1, 1); DHT DC 0, AC 0 (then DC 1, AC 1
+ *               with three components), one segment each; DRI ri; SOS (components with tables 00, 11, 11; 0, 63, 0).
+ *   Stream      what follows the header: the intervals with their markers, EOI included, dense.
+ *
+ * hm_mjpeg_create   builds the tables and the header on the host; nothing runs on the device before the first encode,
+ *               which allocates the handle's buffers there (128 bytes of coefficients and 208 of bit buffer per block).
+ *               HM_ERR_ARG with the numbers in hm_last_error for W or H outside 1..32767, channels not 1 or 3, quality
+ *               outside 1..100, restart_rows < 1, ri > 65535 (DRI is a 16-bit field), and a frame whose stream could
+ *               reach 2^31 bytes.
+ * hm_mjpeg_header   copies the header (SOI through SOS) and gives its length in *n; buf NULL: the length alone; a cap
+ *               below it is refused.
+ * hm_mjpeg_max_bytes  the largest file a frame can code to: the header, 416 bytes per block (64 coefficients of at most
+ *               26 bits, every byte stuffed) and a marker per interval.
+ * hm_mjpeg_encode_dev  queues the encode of the frame at device address d_frame on `stream` and returns.  The stream
+ *               (no header) goes to `out`, device or page-locked host memory of `cap` bytes; its size to *size_word,
+ *               device or page-locked host memory, written by the last launch.  The size is known on the device before a
+ *               byte is written: a stream larger than cap is not written at all and the size word (> cap) says so.  The
+ *               handle's bit buffer is all zero between frames (the launch that reads it clears it), so no frame sees
+ *               another's bits.  One encode of a handle at a time: queue them on one stream, or order them yourself.
+ * hm_mjpeg_encode   host frame in, whole JPEG file (header + stream) out, synchronous, on a stream of the handle's own.
+ *               *n is the file's size also when it does not fit: then HM_ERR_ARG names both numbers and `out` is untouched.
+ * Plain HIP: vector stores and ordinary atomics (atomicOr into the bit buffer, one LDS atomicAdd). */
+typedef struct hm_mjpeg *hm_mjpeg_t;
+int hm_mjpeg_create(int device, int W, int H, int channels, int quality, int restart_rows, hm_mjpeg_t *out);
+int hm_mjpeg_destroy(hm_mjpeg_t enc);
+int hm_mjpeg_header(hm_mjpeg_t enc, uint8_t *buf, uint64_t cap, uint64_t *n);
+uint64_t hm_mjpeg_max_bytes(hm_mjpeg_t enc);
+int hm_mjpeg_encode_dev(hm_mjpeg_t enc, const void *d_frame, void *out, uint64_t cap, uint32_t *size_word, void *stream);
+int hm_mjpeg_encode(hm_mjpeg_t enc, const uint8_t *frame, uint8_t *out, uint64_t cap, uint64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,16 @@ SIGNATURES = {
                                    ctypes.POINTER(c_vp)]),
     "hm_avi_write": (ctypes.c_int, [c_vp, c_vp]),
     "hm_avi_close": (ctypes.c_int, [c_vp]),
+    "hm_avi_open_codec": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int,
+                                         ctypes.POINTER(c_vp)]),
+    "hm_avi_write_chunk": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64]),
+    "hm_mjpeg_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(c_vp)]),
+    "hm_mjpeg_destroy": (ctypes.c_int, [c_vp]),
+    "hm_mjpeg_header": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "hm_mjpeg_max_bytes": (ctypes.c_uint64, [c_vp]),
+    "hm_mjpeg_encode_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "hm_mjpeg_encode": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 _lib = None

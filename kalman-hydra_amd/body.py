@@ -251,7 +251,7 @@ class BodyReadout:
         reg, ts, ls = self.r.body_warp(X, frame)
         self._keep(X, ts, ls)
         if self.video is not None:
-            self.video.write(np.repeat(reg[:, :, None], 3, axis=2))
+            self.video.write(reg if getattr(self.video, "channels", 3) == 1 else np.repeat(reg[:, :, None], 3, axis=2))
         return reg, _means(ts, self.tri_counts), _means(ls, self.label_counts) if ls is not None else np.zeros(0)
 
     def _own_labels(self):
@@ -356,7 +356,11 @@ class BodyTap:
     sums, and the registered frame as B = G = R when the readout has a video --, copied into page-locked memory on a copy
     stream of its own that waits for the warp, and taken by a writer thread (sums into the readout's rows, frames into
     the video).  The frame ring may reuse the slot of a frame the warp reads only after the warp: ``frame`` hands the
-    ring a fence (hm_body_fence) that its copy stream waits on before its next upload."""
+    ring a fence (hm_body_fence) that its copy stream waits on before its next upload.
+
+    With an MJPEG video the warp writes the registered frame with as many channels as the video codes (one for a grey
+    video), the video's encoder is queued behind it on the same stream, and only the sums are downloaded with the slot:
+    the writer thread copies the stream's own bytes (videoio.MjpegSlots)."""
 
     def __init__(self, body, device=0, slots=4):
         import queue
@@ -365,14 +369,24 @@ class BodyTap:
         self.npx = r.nx * r.ny
         self.ns = 8 * (body.T + body.L)                 # a slot: the sums (8-byte aligned), then the frame, if any
         self.nv = 3 * self.npx if body.video is not None else 0
+        self.ch = 3
+        self._mj = None
+        if body.video is not None and getattr(body.video, "mjpeg", False):
+            from .videoio import MjpegSlots
+            self.ch = body.video.channels
+            self.nv = self.ch * self.npx
+            self._mj = MjpegSlots(body.video.encoder, self.slots, device)
         self.stride = self.ns + self.nv
         L = _lib.lib()
         self._stream = _lib.c_vp()
         _lib.check(L.hm_copy_stream_create(self.device, ctypes.byref(self._stream)), "hm_copy_stream_create")
         self._pin = _lib.c_vp()
+        # (MJPEG: the frame stays on the device, with the stream the encoder makes of it behind it)
+        self.nd = self.ns if self._mj is not None else self.stride            # bytes of a slot that are downloaded
         _lib.check(L.hm_host_alloc(self.slots * self.stride, ctypes.byref(self._pin)), "hm_host_alloc")
         from .pipeline import DeviceBuffer
-        self._dev = [DeviceBuffer(self.stride, device) for _ in range(self.slots)]
+        self._dev = [DeviceBuffer(self.stride + (self._mj.cap if self._mj is not None else 0), device)
+                     for _ in range(self.slots)]
         self._free = threading.Semaphore(self.slots)
         self._q = queue.Queue()
         self._next = 0
@@ -394,10 +408,12 @@ class BodyTap:
         b = self.b
         self.b._keep(X, None, None)
         row = len(b._rows) - 1
-        b.r.body_warp_dev(X, d_frame, d + self.ns if self.nv else None, 3, d, d + 8 * b.T if b.L else None, self._stream)
+        b.r.body_warp_dev(X, d_frame, d + self.ns if self.nv else None, self.ch, d, d + 8 * b.T if b.L else None, self._stream)
         if ring is not None:
             ring.fence_after(lambda st: b.r.body_fence(st))
-        _lib.check(_lib.lib().hm_dev_download_async(self.device, self._pin.value + s * self.stride, d, self.stride,
+        if self._mj is not None:
+            b.video.encoder.encode_dev(d + self.ns, d + self.stride, self._mj.cap, self._mj.size_word(s), self._stream)
+        _lib.check(_lib.lib().hm_dev_download_async(self.device, self._pin.value + s * self.stride, d, self.nd,
                                                     self._stream), "hm_dev_download_async")
         self._q.put((s, row))
 
@@ -416,7 +432,9 @@ class BodyTap:
                                                 shape=(self.b.T + self.b.L,)).copy()
                     self.b._rows[row][1] = blk[:self.b.T]
                     self.b._rows[row][2] = blk[self.b.T:] if self.b.L else None
-                    if self.nv:
+                    if self._mj is not None:
+                        self._mj.finish(s, self._dev[s].ptr + self.stride, self.b.video)
+                    elif self.nv:
                         self.b.video.write_ptr(base + self.ns)
             except Exception as e:          # noqa: BLE001 -- reported by the next frame() / close()
                 self._error = e
@@ -446,6 +464,8 @@ class BodyTap:
                 self._stream = None
             for b in self._dev:
                 b.close()
+            if self._mj is not None:
+                self._mj.close()
             if self._pin:
                 L.hm_host_free(self._pin)
                 self._pin = None

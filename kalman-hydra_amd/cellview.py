@@ -83,9 +83,10 @@ def levels(dff, lo=10.0, hi=99.0):
 
 
 def write_video(kf_or_renderer, states, source, path, cells=None, levels=None, points=None, point_radius=2, outline=True,
-                wire=False, fps=20):
+                wire=False, fps=20, video_opts=None):
     """The overlay video of a finished track: frame k of `source` (``frame_at(k)`` -> raw frame, ...; or an array
-    (frames, H, W) uint8) with the cells and markers at states[k], written to the uncompressed AVI `path`.
+    (frames, H, W) uint8) with the cells and markers at states[k], written to the AVI `path` (uncompressed; video_opts: AviWriter's codec
+    options, e.g. dict(codec="mjpeg", quality=90)).
 
     cells: (labels, weights) as layers_from_* give them, or a label image (H, W); None: markers only.  levels: (F, L)
     uint8 (None: 255).  points: (P, 2) body coordinates, followed through the mesh (body.locate / body.track); each
@@ -116,7 +117,7 @@ def write_video(kf_or_renderer, states, source, path, cells=None, levels=None, p
         t, ids, l1, l2 = _body.locate(r.uv, r.tri, pts)
         loc, colours = (ids, l1, l2, t >= 0), palette(pts.shape[0])
     n = r.nx * r.ny
-    writer = AviWriter(path, r.nx, r.ny, fps=fps)
+    writer = AviWriter(path, r.nx, r.ny, fps=fps, **(video_opts or {}))
     tap = VideoTap(r, writer)
     d_frames = [DeviceBuffer(n, tap.device) for _ in range(tap.slots)]     # a frame is read when its view runs
     try:

@@ -830,3 +830,243 @@ extern "C" int hm_flow_preview(int device, int n, int W, int H, int channels, co
     return rc;
 }
 
+
+// ---- Motion-JPEG: the baseline JPEG encoder of the video writer (mjpeg_kernels.h) ----------------
+#include "mjpeg_kernels.h"
+
+namespace {
+
+// ITU-T T.81 Annex K: table K.1 / K.2 (natural order) and the typical Huffman tables K.3 - K.6
+const uint8_t MJ_QUANT[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
+     100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+const uint8_t MJ_DC_BITS[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t MJ_DC_VALS[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t MJ_AC_BITS[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+const uint8_t MJ_AC_VALS[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+     0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+     0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+     0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+     0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
+
+// canonical codes of a table given as BITS / HUFFVAL (T.81 Annex C)
+template <typename Code, typename Len>
+void mj_huffman(const uint8_t bits[16], const uint8_t *vals, Code *code, Len *len)
+{
+    unsigned c = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; l++) {
+        for (int i = 0; i < bits[l - 1]; i++, k++) {
+            code[vals[k]] = (Code)c++;
+            len[vals[k]] = (Len)l;
+        }
+        c <<= 1;
+    }
+}
+
+}  // namespace
+
+struct hm_mjpeg {
+    int device = 0, quality = 0, restart_rows = 1;
+    MjGeo g{};
+    MjTables tab{};
+    std::vector<uint8_t> header;
+    uint64_t max_stream = 0;
+    HmOwner own{1};
+    // built by the first encode
+    MjTables *d_tab = nullptr;
+    int16_t *d_coef = nullptr;
+    uint16_t *d_acbits = nullptr;
+    unsigned *d_bitbuf = nullptr, *d_ibits = nullptr, *d_isize = nullptr, *d_ioff = nullptr;
+    bool ready = false;
+    // hm_mjpeg_encode's own
+    hipStream_t stream = nullptr;
+    uint8_t *d_frame = nullptr, *d_out = nullptr;
+    unsigned *d_size = nullptr;
+};
+
+static void mj_header(hm_mjpeg *e)
+{
+    std::vector<uint8_t> &h = e->header;
+    auto seg = [&](uint8_t marker, const std::vector<uint8_t> &body) {
+        h.push_back(0xFF); h.push_back(marker);
+        const size_t n = body.size() + 2;
+        h.push_back((uint8_t)(n >> 8)); h.push_back((uint8_t)n);
+        h.insert(h.end(), body.begin(), body.end());
+    };
+    const int C = e->g.C, sets = C == 3 ? 2 : 1;
+    h.push_back(0xFF); h.push_back(0xD8);                                                       // SOI
+    seg(0xE0, {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});                              // APP0: JFIF 1.01, 1:1
+    for (int s = 0; s < sets; s++) {                                                            // DQT, 8 bits, zigzag order
+        std::vector<uint8_t> b{(uint8_t)s};
+        for (int k = 0; k < 64; k++) b.push_back((uint8_t)e->tab.quant[s][k]);
+        seg(0xDB, b);
+    }
+    {                                                                                           // SOF0
+        std::vector<uint8_t> b{8, (uint8_t)(e->g.H >> 8), (uint8_t)e->g.H, (uint8_t)(e->g.W >> 8), (uint8_t)e->g.W, (uint8_t)C};
+        for (int c = 0; c < C; c++) { b.push_back((uint8_t)(c + 1)); b.push_back(0x11); b.push_back(c ? 1 : 0); }
+        seg(0xC0, b);
+    }
+    for (int s = 0; s < sets; s++) {                                                            // DHT: DC then AC of each set
+        std::vector<uint8_t> b{(uint8_t)s};
+        b.insert(b.end(), MJ_DC_BITS[s], MJ_DC_BITS[s] + 16);
+        b.insert(b.end(), MJ_DC_VALS, MJ_DC_VALS + 12);
+        seg(0xC4, b);
+        std::vector<uint8_t> a{(uint8_t)(0x10 | s)};
+        a.insert(a.end(), MJ_AC_BITS[s], MJ_AC_BITS[s] + 16);
+        a.insert(a.end(), MJ_AC_VALS[s], MJ_AC_VALS[s] + 162);
+        seg(0xC4, a);
+    }
+    seg(0xDD, {(uint8_t)(e->g.ri >> 8), (uint8_t)e->g.ri});                                     // DRI
+    {                                                                                           // SOS
+        std::vector<uint8_t> b{(uint8_t)C};
+        for (int c = 0; c < C; c++) { b.push_back((uint8_t)(c + 1)); b.push_back(c ? 0x11 : 0x00); }
+        b.push_back(0); b.push_back(63); b.push_back(0);
+        seg(0xDA, b);
+    }
+}
+
+extern "C" int hm_mjpeg_create(int device, int W, int H, int channels, int quality, int restart_rows, hm_mjpeg_t *out)
+{
+    HM_ARG(out, "hm_mjpeg_create: out is NULL");
+    *out = nullptr;
+    HM_ARG(W >= 1 && H >= 1 && W <= 32767 && H <= 32767, "hm_mjpeg_create: frame size %dx%d outside 1..32767", W, H);
+    HM_ARG(channels == 1 || channels == 3, "hm_mjpeg_create: %d channels, not 1 or 3", channels);
+    HM_ARG(quality >= 1 && quality <= 100, "hm_mjpeg_create: quality %d outside 1..100", quality);
+    HM_ARG(restart_rows >= 1, "hm_mjpeg_create: restart_rows %d below 1", restart_rows);
+    const int bw = (W + 7) / 8, bh = (H + 7) / 8;
+    const long long ri = (long long)bw * std::min(restart_rows, bh);
+    HM_ARG(ri <= 65535, "hm_mjpeg_create: %lld blocks in a restart interval (%d across, %d rows), more than 65535", ri, bw,
+           std::min(restart_rows, bh));
+    hm_mjpeg *e = new hm_mjpeg();
+    e->device = device; e->quality = quality; e->restart_rows = restart_rows;
+    MjGeo &g = e->g;
+    g.W = W; g.H = H; g.C = channels; g.bw = bw; g.bh = bh;
+    g.ri = (int)ri;
+    g.n_mcu = bw * bh;
+    g.n_int = (g.n_mcu + g.ri - 1) / g.ri;
+    e->max_stream = (uint64_t)g.n_mcu * channels * (8 * MJ_BLOCK_WORDS) + 2ull * g.n_int;
+    if (e->max_stream >= (1ull << 31)) {
+        hm_set_error("hm_mjpeg_create: a frame of %dx%d x %d can code to %llu bytes, 2^31 or more", W, H, channels,
+                     (unsigned long long)e->max_stream);
+        delete e;
+        return HM_ERR_ARG;
+    }
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int s = 0; s < 2; s++) {
+        for (int i = 0; i < 64; i++)
+            e->tab.quant[s][mj_zigzag_pos(i)] = (uint16_t)std::min(255, std::max(1, (MJ_QUANT[s][i] * scale + 50) / 100));
+        mj_huffman(MJ_DC_BITS[s], MJ_DC_VALS, e->tab.dc_code[s], e->tab.dc_len[s]);
+        mj_huffman(MJ_AC_BITS[s], MJ_AC_VALS[s], e->tab.ac_code[s], e->tab.ac_len[s]);
+    }
+    mj_header(e);
+    *out = e;
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_destroy(hm_mjpeg_t e)
+{
+    if (!e) return HM_OK;
+    if (!e->own.mem.empty() || !e->own.streams.empty()) {      // (also what a first encode that failed part-way left)
+        (void)hipSetDevice(e->device);
+        (void)hipDeviceSynchronize();           // (encodes queued on the callers' streams read the handle's buffers)
+        e->own.release();
+    }
+    delete e;
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_header(hm_mjpeg_t e, uint8_t *buf, uint64_t cap, uint64_t *n)
+{
+    HM_ARG(e && n, "hm_mjpeg_header: NULL argument");
+    *n = e->header.size();
+    if (!buf) return HM_OK;                     // (the size alone)
+    HM_ARG(cap >= e->header.size(), "hm_mjpeg_header: the header has %zu bytes, the buffer %llu", e->header.size(),
+           (unsigned long long)cap);
+    memcpy(buf, e->header.data(), e->header.size());
+    return HM_OK;
+}
+
+extern "C" uint64_t hm_mjpeg_max_bytes(hm_mjpeg_t e) { return e ? e->header.size() + e->max_stream : 0; }
+
+static int mj_buffers(hm_mjpeg *e)
+{
+    if (e->ready) return HM_OK;
+    const MjGeo &g = e->g;
+    const size_t nblk = (size_t)g.n_mcu * g.C;
+    HM_HIP(e->own.alloc(&e->d_tab, sizeof(MjTables)));
+    HM_HIP(e->own.alloc(&e->d_coef, nblk * 64 * sizeof(int16_t)));
+    HM_HIP(e->own.alloc(&e->d_acbits, nblk * sizeof(uint16_t)));
+    HM_HIP(e->own.alloc(&e->d_bitbuf, nblk * MJ_BLOCK_WORDS * sizeof(unsigned)));
+    HM_HIP(e->own.alloc(&e->d_ibits, (size_t)g.n_int * sizeof(unsigned)));
+    HM_HIP(e->own.alloc(&e->d_isize, (size_t)g.n_int * sizeof(unsigned)));
+    HM_HIP(e->own.alloc(&e->d_ioff, ((size_t)g.n_int + 1) * sizeof(unsigned)));
+    HM_HIP(hipMemcpy(e->d_tab, &e->tab, sizeof(MjTables), hipMemcpyHostToDevice));
+    HM_HIP(hipMemset(e->d_bitbuf, 0, nblk * MJ_BLOCK_WORDS * sizeof(unsigned)));     // k_mjpeg_pack keeps it zero
+    HM_HIP(hipDeviceSynchronize());
+    e->ready = true;
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_encode_dev(hm_mjpeg_t e, const void *d_frame, void *out, uint64_t cap, uint32_t *size_word, void *stream)
+{
+    HM_ARG(e && d_frame && out && size_word, "hm_mjpeg_encode_dev: NULL argument");
+    HM_HIP(hipSetDevice(e->device));
+    HM_TRY(mj_buffers(e));
+    const MjGeo &g = e->g;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned cap32 = (unsigned)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+    hipLaunchKernelGGL(k_mjpeg_blocks, dim3((unsigned)hm_cdiv(g.n_mcu, mj_blocks_mcus(g.C))), dim3(MJ_THREADS), 0, s, g,
+                       (const MjTables *)e->d_tab, (const uint8_t *)d_frame, e->d_coef, e->d_acbits);
+    const int emit_threads = std::min(MJ_EMIT_MAX, (g.ri * g.C + 63) / 64 * 64);       // whole waves
+    hipLaunchKernelGGL(k_mjpeg_emit, dim3((unsigned)g.n_int), dim3((unsigned)emit_threads), 0, s, g, (const MjTables *)e->d_tab,
+                       (const int16_t *)e->d_coef, (const uint16_t *)e->d_acbits, e->d_bitbuf, e->d_ibits);
+    hipLaunchKernelGGL(k_mjpeg_count, dim3((unsigned)g.n_int), dim3(MJ_THREADS), 0, s, g, (const unsigned *)e->d_bitbuf,
+                       (const unsigned *)e->d_ibits, e->d_isize);
+    hipLaunchKernelGGL(k_mjpeg_offsets, dim3(1), dim3(MJ_THREADS), 0, s, g, (const unsigned *)e->d_isize, e->d_ioff);
+    hipLaunchKernelGGL(k_mjpeg_pack, dim3((unsigned)g.n_int), dim3(MJ_THREADS), 0, s, g, e->d_bitbuf, (const unsigned *)e->d_ibits,
+                       (const unsigned *)e->d_isize, (const unsigned *)e->d_ioff, (uint8_t *)out, cap32, (unsigned *)size_word);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_encode(hm_mjpeg_t e, const uint8_t *frame, uint8_t *out, uint64_t cap, uint64_t *n)
+{
+    HM_ARG(e && frame && out && n, "hm_mjpeg_encode: NULL argument");
+    *n = 0;
+    const size_t hdr = e->header.size();
+    HM_ARG(cap > hdr, "hm_mjpeg_encode: a buffer of %llu bytes does not hold the header's %zu", (unsigned long long)cap, hdr);
+    HM_HIP(hipSetDevice(e->device));
+    const size_t fb = (size_t)e->g.W * e->g.H * e->g.C;
+    const uint64_t room = std::min<uint64_t>(cap - hdr, e->max_stream);
+    HM_HIP(e->own.stream(&e->stream, false));
+    HM_HIP(e->own.alloc(&e->d_frame, fb));
+    HM_HIP(e->own.grow(&e->d_out, (size_t)room));
+    HM_HIP(e->own.alloc(&e->d_size, sizeof(unsigned)));
+    HM_HIP(hipMemcpyAsync(e->d_frame, frame, fb, hipMemcpyHostToDevice, e->stream));
+    HM_TRY(hm_mjpeg_encode_dev(e, e->d_frame, e->d_out, room, e->d_size, e->stream));
+    unsigned size = 0;
+    HM_HIP(hipMemcpyAsync(&size, e->d_size, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
+    HM_HIP(hipStreamSynchronize(e->stream));
+    *n = hdr + size;
+    HM_ARG(size <= room, "hm_mjpeg_encode: the frame codes to %zu + %u bytes, the buffer has %llu", hdr, size,
+           (unsigned long long)cap);
+    memcpy(out, e->header.data(), hdr);
+    HM_HIP(hipMemcpy(out + hdr, e->d_out, size, hipMemcpyDeviceToHost));
+    return HM_OK;
+}

@@ -17,7 +17,7 @@ The record stays raw: the ROI traces of hydra_mi.roi need the raw baseline for t
 """
 import numpy as np
 
-from .videoio import AviWriter
+from .videoio import AviWriter, grey_opts
 
 KINDS = ("recorded", "baseline", "excess", "dff")
 DEFAULT_HALF = 20          # frames either side of the window: wider windows leave drift in
@@ -74,8 +74,9 @@ def find_points(body, n, radius=6, score="corr", min_score=None, what="excess", 
     return np.stack((cc + 0.5, rr + 0.5), 1).astype(np.float64).reshape(-1, 2), sc
 
 
-def write_video(body, path, half=DEFAULT_HALF, q=DEFAULT_Q, floor=DEFAULT_FLOOR, gain=DEFAULT_GAIN, block=None):
-    """The dF/F bytes of every recorded frame as a grey AVI (B = G = R) in the body frame -> frames written.  The planes
+def write_video(body, path, half=DEFAULT_HALF, q=DEFAULT_Q, floor=DEFAULT_FLOOR, gain=DEFAULT_GAIN, block=None, video_opts=None):
+    """The dF/F bytes of every recorded frame as a grey AVI (B = G = R; video_opts: AviWriter's codec options, an MJPEG
+    video codes one component) in the body frame -> frames written.  The planes
     are fetched `block` frames at a time (default: VIDEO_BYTES worth), so host memory stays bounded for any record."""
     _check("detrend.write_video", "dff", half, q, floor, gain)
     r = _record("detrend.write_video", body)
@@ -83,8 +84,8 @@ def write_video(body, path, half=DEFAULT_HALF, q=DEFAULT_Q, floor=DEFAULT_FLOOR,
     if block is None:
         block = max(1, VIDEO_BYTES // (body.W * body.H))
     walk = blocks(F, block)
-    with AviWriter(path, body.W, body.H) as video:
+    with AviWriter(path, body.W, body.H, **grey_opts(video_opts)) as video:
         for k0, n in walk:
             for plane in r.body_rec_planes("dff", half, q, floor, gain, k0, n):
-                video.write(np.repeat(plane[:, :, None], 3, axis=2))
+                video.write_grey(plane)
         return video.frames

@@ -19,7 +19,7 @@ rule in binary64 for a handful of cell traces; the device runs the same rule on 
 import numpy as np
 
 from . import detrend
-from .videoio import AviWriter
+from .videoio import AviWriter, grey_opts
 
 G_MIN, G_MAX = 0.05, 0.98          # estimate_g keeps inside these
 LAM_Z = 2.0                        # default_lam: noise of this many sigma leaves no event in a long pool
@@ -162,8 +162,9 @@ def count_image(body, g, lam, s_min, what="dff", half=detrend.DEFAULT_HALF, q=de
 
 
 def event_video(body, path, g, lam, what="dff", half=detrend.DEFAULT_HALF, q=detrend.DEFAULT_Q, floor=detrend.DEFAULT_FLOOR,
-                gain=detrend.DEFAULT_GAIN, block=None):
-    """The event bytes of every recorded frame as a grey AVI (B = G = R) in the body frame -> frames written.  Through the
+                gain=detrend.DEFAULT_GAIN, block=None, video_opts=None):
+    """The event bytes of every recorded frame as a grey AVI (B = G = R; video_opts: AviWriter's codec options, an MJPEG
+    video codes one component) in the body frame -> frames written.  Through the
     writer of detrend.write_video, `block` frames at a time (default: VIDEO_BYTES worth).  Every block is cut from the
     solution of the whole record, which the device works out again for it: the event planes do not stay there between
     calls, so the blocks are larger than detrend.write_video's."""
@@ -171,8 +172,8 @@ def event_video(body, path, g, lam, what="dff", half=detrend.DEFAULT_HALF, q=det
     F = r.body_rec_count()
     if block is None:
         block = max(1, VIDEO_BYTES // (body.W * body.H))
-    with AviWriter(path, body.W, body.H) as video:
+    with AviWriter(path, body.W, body.H, **grey_opts(video_opts)) as video:
         for k0, n in detrend.blocks(F, block):
             for plane in r.body_rec_event_planes(what, half, q, floor, gain, g, lam, k0, n):
-                video.write(np.repeat(plane[:, :, None], 3, axis=2))
+                video.write_grey(plane)
         return video.frames

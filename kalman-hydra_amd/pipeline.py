@@ -309,7 +309,11 @@ class VideoTap:
     frame ended with is queued on the device (hm_view_dev, on the filter's stream, into a ring of device slots), copied
     into page-locked memory on a copy stream of its own, and appended to the AviWriter by a writer thread.  The filter's
     launches and the flow series never wait for the disk; only when all `slots` are still waiting to be written does the
-    next frame wait for the oldest.  close() drains the writer."""
+    next frame wait for the oldest.  close() drains the writer.
+
+    With an MJPEG writer (AviWriter(codec="mjpeg")) the frame never leaves the device: the writer's encoder is queued
+    behind the view on the same stream (write into the slot's stream area, size word into page-locked memory), and the
+    writer thread, once the stream has passed, copies exactly the stream's bytes (videoio.MjpegSlots) and appends them."""
 
     def __init__(self, renderer, writer, device=0, slots=4):
         import queue
@@ -322,8 +326,16 @@ class VideoTap:
         self._stream = _lib.c_vp()
         _lib.check(L.hm_copy_stream_create(self.device, ctypes.byref(self._stream)), "hm_copy_stream_create")
         self._pin = _lib.c_vp()
-        _lib.check(L.hm_host_alloc(self.slots * self.n, ctypes.byref(self._pin)), "hm_host_alloc")
-        self._dev = [DeviceBuffer(self.n, device) for _ in range(self.slots)]
+        self._mj = None
+        if getattr(writer, "mjpeg", False):
+            if writer.channels != 3:
+                raise ValueError("VideoTap: the views are B G R, the MJPEG video has %d channel" % writer.channels)
+            from .videoio import MjpegSlots
+            self._mj = MjpegSlots(writer.encoder, self.slots, device)
+            self._dev = [DeviceBuffer(self.n + self._mj.cap, device) for _ in range(self.slots)]
+        else:
+            _lib.check(L.hm_host_alloc(self.slots * self.n, ctypes.byref(self._pin)), "hm_host_alloc")
+            self._dev = [DeviceBuffer(self.n, device) for _ in range(self.slots)]
         self._free = threading.Semaphore(self.slots)
         self._q = queue.Queue()
         self._next = 0
@@ -332,6 +344,12 @@ class VideoTap:
         self._thread = threading.Thread(target=self._write_loop, name="hydra_mi-video", daemon=True)
         self._thread.start()
         _lib.register(self, 0)
+
+    @property
+    def bus_bytes(self):
+        """Bytes of video copied from the device so far: whole frames of a raw video, the streams (rounded up to
+        videoio.MJPEG_GRANULE) of an MJPEG one; the frames still in the ring are counted when they are written."""
+        return self._mj.copied if self._mj is not None else self.n * self.writer.frames
 
     def frame(self, X):
         """Queue the overlay of state X as the next video frame."""
@@ -352,8 +370,11 @@ class VideoTap:
             self._next -= 1
             self._free.release()
             raise
-        _lib.check(_lib.lib().hm_dev_download_async(self.device, self._pin.value + s * self.n, d, self.n, self._stream),
-                   "hm_dev_download_async")
+        if self._mj is not None:
+            self.writer.encoder.encode_dev(d, d + self.n, self._mj.cap, self._mj.size_word(s), self._stream)
+        else:
+            _lib.check(_lib.lib().hm_dev_download_async(self.device, self._pin.value + s * self.n, d, self.n, self._stream),
+                       "hm_dev_download_async")
         self._q.put(s)
 
     def _write_loop(self):
@@ -365,7 +386,10 @@ class VideoTap:
             try:
                 if self._error is None:
                     _lib.check(L.hm_copy_stream_sync(self.device, self._stream), "hm_copy_stream_sync")
-                    self.writer.write_ptr(self._pin.value + s * self.n)
+                    if self._mj is not None:
+                        self._mj.finish(s, self._dev[s].ptr + self.n, self.writer)
+                    else:
+                        self.writer.write_ptr(self._pin.value + s * self.n)
             except Exception as e:          # noqa: BLE001 -- reported by the next frame() / close()
                 self._error = e
             finally:
@@ -394,6 +418,8 @@ class VideoTap:
                 self._stream = None
             for b in self._dev:
                 b.close()
+            if self._mj is not None:
+                self._mj.close()
             if self._pin:
                 L.hm_host_free(self._pin)
                 self._pin = None
@@ -900,6 +926,11 @@ class FlowEKFPipeline:
         finally:
             if quiet:
                 gc.enable()
+
+    @property
+    def video_tap(self):
+        """The VideoTap of the last run(video=...), None before the first (its bus_bytes: what the video copied)."""
+        return getattr(self, "_tap", None)
 
     def _video_tap(self, writer):
         """the VideoTap of this writer, made on first use and kept across run() calls (closed by close())"""

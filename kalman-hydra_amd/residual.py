@@ -25,7 +25,7 @@ import math
 import numpy as np
 
 from . import cellview, demix, roi
-from .videoio import AviWriter
+from .videoio import AviWriter, grey_opts
 
 TBITS = 24                 # traces are scaled by 2^24: a weight of 65535 and a trace of rint(l 2^24 / 65535) take l levels off
 DEFAULT_BLANK = 2          # px round every known seed
@@ -198,8 +198,9 @@ def find_more(body, points, min_score, rounds=3, radius=6, score="corr", blank=D
     return out
 
 
-def write_video(body, path, e, blank=None, offset=DEFAULT_OFFSET, points=None, block=None):
-    """The residual planes of every recorded frame as a grey AVI (B = G = R) in the body frame -> (frames written,
+def write_video(body, path, e, blank=None, offset=DEFAULT_OFFSET, points=None, block=None, video_opts=None):
+    """The residual planes of every recorded frame as a grey AVI (B = G = R; video_opts: AviWriter's codec options, an
+    MJPEG video codes one component) in the body frame -> (frames written,
     clipped).  The planes are fetched `block` frames at a time (default: VIDEO_BYTES worth), so host memory stays bounded
     for any record.  blank None: the video shows the misfit round the seeds too."""
     r = _record("residual.write_video", body)
@@ -211,10 +212,10 @@ def write_video(body, path, e, blank=None, offset=DEFAULT_OFFSET, points=None, b
     if block < 1:
         raise ValueError("blocks of %d frames" % block)
     clipped = 0
-    with AviWriter(path, body.W, body.H) as video:
+    with AviWriter(path, body.W, body.H, **grey_opts(video_opts)) as video:
         for k0 in range(0, F, block):
             planes, c = r.body_rec_residual_planes(labels, weights, traces, bl, int(offset), k0, min(block, F - k0))
             clipped += c
             for plane in planes:
-                video.write(np.repeat(plane[:, :, None], 3, axis=2))
+                video.write_grey(plane)
         return video.frames, clipped

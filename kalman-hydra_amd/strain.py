@@ -116,10 +116,10 @@ def artifact_score(cell_J, dff):
 
 
 def write_video(kf_or_renderer, states, source, path, which="J", gain=DEFAULT_GAIN, alpha=DEFAULT_ALPHA, lut=None,
-                wire=False, fps=20):
+                wire=False, fps=20, video_opts=None):
     """The strain video of a finished track: frame k of `source` (``frame_at(k)`` -> raw frame, ...; or an array
     (frames, H, W) uint8) with `which` (J, l1, l2) of the mesh at states[k] painted on (Renderer.view_strain), written
-    to the uncompressed AVI `path` by the writer thread of a pipeline.VideoTap, as cellview.write_video does: the disk is
+    to the AVI `path` (uncompressed; video_opts: AviWriter's codec options) by the writer thread of a pipeline.VideoTap, as cellview.write_video does: the disk is
     not waited for.  Pass the smoothed states of a run that has them.  -> frames written."""
     from .pipeline import DeviceBuffer, VideoTap
     r = _renderer(kf_or_renderer)
@@ -128,7 +128,7 @@ def write_video(kf_or_renderer, states, source, path, which="J", gain=DEFAULT_GA
         raise ValueError("write_video: which %r (one of %s)" % (which, ", ".join(WHICH)))
     lut = default_lut() if lut is None else np.ascontiguousarray(lut, np.uint8)
     n = r.nx * r.ny
-    writer = AviWriter(path, r.nx, r.ny, fps=fps)
+    writer = AviWriter(path, r.nx, r.ny, fps=fps, **(video_opts or {}))
     tap = VideoTap(r, writer)
     d_frames = [DeviceBuffer(n, tap.device) for _ in range(tap.slots)]     # a frame is read when its view runs
     try:

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""optical_flow_ext.py <video> <output prefix> [alpha] [gamma] [scale_factor] [inner_it] [outer_it] [solver_it]
+"""optical_flow_ext.py [--video-codec raw|mjpeg] [--video-quality Q] <video> <output prefix> [alpha] [gamma] [scale_factor]
+                       [inner_it] [outer_it] [solver_it]
 
 The flow tool of the reference (reference src/optical_flow_ext.cpp:441-507) on MI355X:
 for every consecutive frame pair computes the Brox flow and writes
@@ -10,7 +11,8 @@ inner 10, outer 77, solver 10.  The video is a .npy / .npz array (frames, H, W[,
 `HYDRA_MI_FLOW_BATCH` (default 16) pairs -- they are independent.
 With HYDRA_MI_FLOW_PREVIEW=1 it also writes <prefix>.avi (:336-389): frame n is frame n + 1 as read blended
 0.4 / 0.6 with the flow of pair n in the Middlebury colour code, saturating at 15 px (hm_flow_preview; the AVI is
-the library's, uncompressed, 20 frames/s) -- the same bytes as the native tool writes.
+the library's, uncompressed, 20 frames/s) -- the same bytes as the native tool writes.  --video-codec mjpeg (default
+raw) writes the preview as Motion-JPEG at --video-quality (1..100, default 90) instead.
 """
 import os
 import sys
@@ -21,7 +23,33 @@ import hydra_mi  # noqa: F401
 from hydra_mi import brox, matio, pipeline, videoio
 
 
+def _video_opts(av):
+    """takes --video-codec / --video-quality out of the arguments -> (the rest, AviWriter's options or None on a bad one)"""
+    rest, opts = [], {}
+    it = iter(av)
+    for s in it:
+        if s in ("--video-codec", "--video-quality"):
+            v = next(it, None)
+            if v is None:
+                return rest, None
+            opts[s] = v
+        else:
+            rest.append(s)
+    codec = opts.get("--video-codec", "raw")
+    try:
+        quality = int(opts.get("--video-quality", "90"))
+    except ValueError:
+        return rest, None
+    if codec not in ("raw", "mjpeg") or not 1 <= quality <= 100:
+        return rest, None
+    return rest, (dict(codec="mjpeg", quality=quality) if codec == "mjpeg" else {})
+
+
 def main(av):
+    av, vopts = _video_opts(list(av))
+    if vopts is None:
+        sys.stderr.write("--video-codec is raw or mjpeg, --video-quality 1..100\n")
+        return 1
     if len(av) < 3:
         print(__doc__)
         return 1
@@ -49,7 +77,7 @@ def main(av):
         return 1
     preview = None
     if os.environ.get("HYDRA_MI_FLOW_PREVIEW", "") == "1":
-        preview = videoio.AviWriter(prefix + ".avi", a.shape[2], a.shape[1])
+        preview = videoio.AviWriter(prefix + ".avi", a.shape[2], a.shape[1], **vopts)
     for s in range(0, n, B):
         e = min(n, s + B)
         fx, fy = bf.calc_batch(np.ascontiguousarray(a[s:e]), np.ascontiguousarray(a[s + 1:e + 1]))

@@ -89,6 +89,12 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      also gets residual_round (per point: the round that found it, 0 the first pass), residual_scores and
                      residual_scores_round (every candidate's score and its round), residual_clipped (per round: values
                      that left 0..255 before the clamp).  The demix_* arrays are those of all the points.
+    --video-codec raw|mjpeg   the codec of every video this command writes (fn_out.avi, --registered, --dff-video,
+                     --residual-video, --cells-video, --strain-video, --events-video).  raw (default): uncompressed 24-bit
+                     AVI.  mjpeg: Motion-JPEG, every frame a baseline JPEG coded on the device (hydra_mi.videoio); the four
+                     grey videos (--registered, --dff-video, --residual-video, --events-video) are coded with one component.
+                     videoio.read_avi reads either back.
+    --video-quality Q   with --video-codec mjpeg: the JPEG quality, 1..100 (default 90)
     --residual-video OUT.avi   with --demix or --find-more: the registered video less the demixed cells' light plus 64,
                      grey, in the body frame (hydra_mi.residual.write_video): what the model does not explain.
     --smooth         also smooth the track backward (Rauch-Tung-Striebel, hydra_mi.smooth): the states file gets Xs
@@ -263,7 +269,15 @@ def main(argv=None):
     parser.add_argument("--events-lambda", default=None, type=float, help="the penalty on the events (default: from each cell's noise)")
     parser.add_argument("--events-smin", default=None, type=float, help="the least event that counts (default: from each cell's noise)")
     parser.add_argument("--events-video", default=None, metavar="OUT.avi", help="with --events: write the event video in the body frame here (.avi)")
+    parser.add_argument("--video-codec", default="raw", choices=("raw", "mjpeg"), help="the codec of every video written (default raw)")
+    parser.add_argument("--video-quality", default=90, type=int, help="with --video-codec mjpeg: JPEG quality 1..100 (default 90)")
     args = parser.parse_args(argv)
+    if not 1 <= args.video_quality <= 100:
+        parser.error("--video-quality is 1..100")
+    # (raw: the writers are called exactly as before)
+    vopts = dict(codec="mjpeg", quality=args.video_quality) if args.video_codec == "mjpeg" else {}
+    vkw = dict(video_opts=vopts) if vopts else {}
+    gopts = dict(vopts, channels=1) if vopts else {}
     if not 0 <= args.strain_alpha <= 255 or not np.isfinite(args.strain_gain):
         parser.error("the strain video needs a --strain-alpha in 0..255 and a finite --strain-gain")
     if args.cells_video is not None and args.points is None and args.find_points is None:
@@ -350,13 +364,13 @@ def main(argv=None):
     ret_flow, flowframe = flowstream.peek()
     states, errors = [], []
     H, W = frame.shape[:2]
-    video = AviWriter(args.fn_out, W, H) if args.fn_out.lower().endswith(".avi") else None
+    video = AviWriter(args.fn_out, W, H, **vopts) if args.fn_out.lower().endswith(".avi") else None
     if args.name is not None:
         os.makedirs("screenshots", exist_ok=True)
     find = args.find_points is not None
     readout = args.registered is not None or args.points is not None or find or keep_record
     points = read_points_csv(args.points)[1] if args.points is not None else None
-    reg_video = AviWriter(args.registered, W, H) if args.registered is not None else None
+    reg_video = AviWriter(args.registered, W, H, **gopts) if args.registered is not None else None
 
     def make_body(kf):
         if not readout:
@@ -523,7 +537,8 @@ def main(argv=None):
         st_cells = {"points": found if find else points, "point_radius": args.point_radius}
     if body is not None and body.keep:
         if args.dff_video is not None and len(states):
-            n_dff = detrend.write_video(body, args.dff_video, args.detrend_half, args.detrend_q, args.dff_floor, args.dff_gain)
+            n_dff = detrend.write_video(body, args.dff_video, args.detrend_half, args.detrend_q, args.dff_floor, args.dff_gain,
+                                          **vkw)
             print("dF/F video: %d frames in %s" % (n_dff, args.dff_video))
         pts = found if find else points
         inside = np.flatnonzero(body.locate(pts)[0] >= 0) if args.rois else []
@@ -538,7 +553,7 @@ def main(argv=None):
                              demix_change=e["demix_change"])
                 print("Demixed: %d cells, %d rounds, last change %.3g" % (len(inside), args.demix_iters, e["demix_change"][-1]))
                 if args.residual_video is not None:
-                    n_res, n_clip = residual.write_video(body, args.residual_video, e, points=pts[inside])
+                    n_res, n_clip = residual.write_video(body, args.residual_video, e, points=pts[inside], **vkw)
                     print("Residual video: %d frames in %s (%d values clipped)" % (n_res, args.residual_video, n_clip))
             else:
                 e = roi.extract(body, pts[inside], r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
@@ -568,7 +583,7 @@ def main(argv=None):
                 if args.network:
                     extra.update(net_r_events=network.coactivity(ev_s, args.network_lag))
                 if args.events_video is not None:
-                    n_ev = events.event_video(body, args.events_video, g_px, lam_px, **px)
+                    n_ev = events.event_video(body, args.events_video, g_px, lam_px, **px, **vkw)
                     print("Event video: %d frames in %s" % (n_ev, args.events_video))
             if args.network:                                       # (cell s: point inside[s], as the roi_* rows)
                 net = network.extract(body, (e["dff_demixed"] if args.demix else e["dff"]).T, thr=args.network_thr,
@@ -620,7 +635,7 @@ def main(argv=None):
         if cv_cells is not None and int(cv_cells[0].max()) < 0:
             cv_cells = cv_levels = None
         n_cv = cellview.write_video(kf, cv_states, capture.frames[1:1 + len(states)], args.cells_video, cells=cv_cells,
-                                    levels=cv_levels, points=cv_points)       # state k: frame k + 1
+                                    levels=cv_levels, points=cv_points, **vkw)       # state k: frame k + 1
         print("Cells video: %d frames (%s states) in %s" % (n_cv, use, args.cells_video))
     if (args.strain or args.strain_video is not None) and len(states):
         st_states = extra["Xs"] if args.smooth else np.array(states)
@@ -639,7 +654,7 @@ def main(argv=None):
                     extra.update(strain_artifact_r=strain.artifact_score(c["J"], st_dff))
         if args.strain_video is not None:
             n_sv = strain.write_video(kf, st_states, capture.frames[1:1 + len(states)], args.strain_video,
-                                      which=args.strain_which, gain=args.strain_gain, alpha=args.strain_alpha)     # state k: frame k + 1
+                                      which=args.strain_which, gain=args.strain_gain, alpha=args.strain_alpha, **vkw)     # state k: frame k + 1
             print("Strain video: %d frames (%s) in %s" % (n_sv, args.strain_which, args.strain_video))
     np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri, **extra)
     print("Finished: %d frames, states in %s" % (len(states), args.fn_out))
