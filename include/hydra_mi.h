@@ -689,7 +689,21 @@ int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int
  *                  may make a product that rounds to 0 and a rho that is not finite.  A workgroup walks all frames for
  *                  its pixels and 8 columns in runs of hm_ctx_tune "rec_null_frames" (1..256, default 256), 32-bit sums
  *                  widened in registers between runs: the same bytes for every value of the key.  The record is not
- *                  changed, and a refusal leaves it usable. */
+ *                  changed, and a refusal leaves it usable.
+ *   gram           the Gram matrix of frames of the record (hydra_mi/pca.py; csrc/gram_kernels.h).
+ *                  The call works on the frames f_i = k0 + i stride, i = 0 .. n - 1:
+ *                    G[i * n + j] = sum_p v_fi(p) v_fj(p) (int64), the full symmetric n x n matrix,
+ *                    s1[i] = sum_p v_fi(p) (uint64).
+ *                  The sums run over the box; pixels off the map are registered as 0, so they are also the sums over the
+ *                  map.  Either output may be NULL.  The record is not changed.  State errors and waiting are those of
+ *                  hm_body_rec_seed_sums.  HM_ERR_ARG, with the numbers, for n < 1; for n > 8192 (REC_GRAM_MAX: G is
+ *                  512 MiB there), refused on the number alone, before the frames are looked at; for stride < 1; for
+ *                  k0 < 0; and for a last frame k0 + (n - 1) stride >= F.  No magnitude bound is needed: 255^2 x box bytes
+ *                  is far below 2^63.  A refusal leaves the record usable.  The products are made by
+ *                  v_mfma_i32_16x16x64_i8 on x = v - 128 and corrected exactly on the device; the bytes of a frame are
+ *                  split over the grid in runs of hm_ctx_tune "rec_gram_bytes" (multiples of 64 in 64..131008, anything
+ *                  else refused; default 16384), the sums of a run are 32-bit (128^2 x 131008 < 2^31) and meet in 64-bit
+ *                  integer atomics: the same bytes in any order and for every value of the key. */
 int hm_body_rec_begin(hm_ctx_t h, uint64_t max_bytes);
 int hm_body_rec_end(hm_ctx_t h);
 int hm_body_rec_count(hm_ctx_t h, int *frames);
@@ -703,6 +717,7 @@ int hm_body_rec_trace_products(hm_ctx_t h, int P, const int32_t *seeds, int R, c
 int hm_body_rec_trace_maps(hm_ctx_t h, int L, const int32_t *q, int64_t *c, uint64_t *w1, uint64_t *w2);
 int hm_body_rec_trace_null(hm_ctx_t h, int L, const int32_t *q, const double *vb, double *tmax, double *tmin,
                            uint32_t *ge, uint32_t *le);
+int hm_body_rec_gram(hm_ctx_t h, int k0, int n, int stride, int64_t *G, uint64_t *s1);
 
 /* The record against the deformation of its own tissue, and the deformation's brightness taken out of it in place
  * (hydra_mi/deform.py; csrc/deform_kernels.h; tests/deform_ref.py restates both calls in NumPy).

@@ -162,6 +162,7 @@ SIGNATURES = {
     "hm_body_rec_trace_products": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_body_rec_trace_maps": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "hm_body_rec_trace_null": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hm_body_rec_gram": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "hm_body_rec_tri_maps": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "hm_body_rec_tri_gain": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_body_rec_match": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,

@@ -163,6 +163,7 @@ struct RecState {
     int map_frames = 64;             // hm_ctx_tune "rec_map_frames": frames per run of k_rec_trace_maps (hm_body_rec_trace_maps)
     int null_frames = 256;           // hm_ctx_tune "rec_null_frames": frames per run of k_rec_trace_null (hm_body_rec_trace_null)
     int tm_frames = 64;              // hm_ctx_tune "rec_tm_frames": frames per run of k_rec_tri_maps (hm_body_rec_tri_maps)
+    int gram_bytes = 16384;          // hm_ctx_tune "rec_gram_bytes": bytes per run of k_rec_gram (hm_body_rec_gram)
     unsigned long long max = 0;      // the budget in bytes
     RecBox box = {0, 0, 0, 0, 0, 0, 0};
     std::vector<uint8_t *> chunks;

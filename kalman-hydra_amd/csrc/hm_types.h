@@ -308,4 +308,10 @@ struct RecBox {
 #define REC_MAP_MAX 256                // the most frames of a run of k_rec_trace_maps (hm_ctx_tune "rec_map_frames"): 32-bit sums hold
 #define REC_NULL_MAX 256               // the most frames of a run of k_rec_trace_null (hm_ctx_tune "rec_null_frames"): 255 x 32767 x 256 < 2^31
 #define REC_TM_MAX 256                 // the most frames of a run of k_rec_tri_maps (hm_ctx_tune "rec_tm_frames"): 255 x 32767 x 256 < 2^31
+// hm_body_rec_gram: the most frames of one Gram matrix (G is 8192^2 x 8 bytes = 512 MiB there), and the most bytes of a run of
+// k_rec_gram (hm_ctx_tune "rec_gram_bytes", multiples of 64).  The run's 32-bit sums hold products of signed bytes x = v - 128,
+// |x_i x_j| <= 128^2: 128^2 x 131008 = 2 146 435 072 < 2^31, while 131072 bytes would be exactly 2^31 and a black frame (x = -128
+// everywhere) against itself reaches the bound.
+#define REC_GRAM_MAX 8192
+#define REC_GRAM_BYTES_MAX 131008
 #define REC_RES_LMAX 65536             // hm_body_rec_residual_*: a label 0 .. L - 1 shares a dword with its 16-bit weight

@@ -1,7 +1,7 @@
 // The registered video kept on the device (hm_body_rec_*): the record itself, the reductions over it, its residual motion
 // (match, shift, field, warp), the running baseline, the events per pixel and the residual of the cells' model.  Host orchestration and C-ABI
 // (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h, events_kernels.h, residual_kernels.h and
-// network_kernels.h, network_null_kernels.h and deform_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses
+// network_kernels.h, network_null_kernels.h, deform_kernels.h and gram_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses
 // rec, the body map (body.tri, body.h_tri), the
 // registered plane (body.reg) and the statistics' counters, and reads W, H, device, own and stream.  readout.hip queues the
 // warp: it reserves a frame's slot and queues the copy into it through body_rec_slot and body_rec_queue_copy, and this file
@@ -15,6 +15,7 @@
 #include "network_kernels.h"
 #include "network_null_kernels.h"
 #include "deform_kernels.h"
+#include "gram_kernels.h"
 #include <cmath>
 #include <algorithm>
 #include <cstring>
@@ -616,6 +617,46 @@ extern "C" int hm_body_rec_trace_null(hm_ctx_t h, int L, const int32_t *q, const
     }
     if (ge) HM_TRY(rec_expand_planes(h, a.ge, 1, ge));
     if (le) HM_TRY(rec_expand_planes(h, a.le, 1, le));
+    return HM_OK;
+}
+
+// ---- the Gram matrix of the record's frames (gram_kernels.h) ----------------------------------------------------------
+extern "C" int hm_body_rec_gram(hm_ctx_t h, int k0, int n, int stride, int64_t *G, uint64_t *s1)
+{
+    HM_ARG(n >= 1 && n <= REC_GRAM_MAX, "hm_body_rec_gram: %d frames outside 1..%d", n, REC_GRAM_MAX);
+    HM_ARG(stride >= 1, "hm_body_rec_gram: stride %d (need >= 1)", stride);
+    HM_ARG(k0 >= 0, "hm_body_rec_gram: first frame %d is negative", k0);
+    HM_ARG(h != nullptr, "hm_body_rec_gram: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, "hm_body_rec_gram"));
+    const int F = h->rec.frames;
+    const long long last = (long long)k0 + (long long)(n - 1) * stride;
+    HM_ARG(last < F, "hm_body_rec_gram: %d frames from %d in steps of %d end at frame %lld of a record of %d", n, k0, stride, last, F);
+    if (!(G || s1)) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const RecBox &b = h->rec.box;
+    const size_t nb = (size_t)b.pitch * b.bh, nn = (size_t)n * n;
+    RecGram g;
+    unsigned long long *d_s1 = nullptr;
+    HM_TRY(body_rec_carve(h, [&](RecCarve &cv) {
+        g.sx = cv.take<unsigned long long>((size_t)n);
+        d_s1 = cv.take<unsigned long long>(s1 ? (size_t)n : 0);
+        g.G = G ? cv.take<unsigned long long>(nn) : nullptr;
+    }));
+    HM_HIP(hipMemsetAsync(g.sx, 0, (size_t)n * 8, h->stream));
+    if (G) HM_HIP(hipMemsetAsync(g.G, 0, nn * 8, h->stream));
+    g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.k0 = k0; g.n = n; g.stride = stride; g.run = h->rec.gram_bytes;
+    const int nbk = hm_cdiv(n, GRAM_BLK), pairs = G ? nbk * (nbk + 1) / 2 : nbk;
+    const size_t runs = (nb + (size_t)g.run - 1) / (size_t)g.run;
+    hipLaunchKernelGGL(k_rec_gram, dim3(pairs, (unsigned)std::min<size_t>(runs, 65535)), dim3(256), 0, h->stream, g);
+    hipLaunchKernelGGL(k_rec_gram_fix, dim3(hm_cdiv(n, 256), std::min(n, 1024)), dim3(256), 0, h->stream, n, (long long)nb,
+                       (const long long *)g.sx, (long long *)g.G, s1 ? d_s1 : nullptr);
+    HM_HIP(hipGetLastError());
+    if (G) HM_HIP(hipMemcpyAsync(G, g.G, nn * 8, hipMemcpyDeviceToHost, h->stream));
+    if (s1) HM_HIP(hipMemcpyAsync(s1, d_s1, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HM_HIP(hipStreamSynchronize(h->stream));
     return HM_OK;
 }
 

@@ -527,6 +527,25 @@ class Renderer:
                    "hm_body_rec_trace_null")
         return o
 
+    def body_rec_gram(self, k0=0, n=None, stride=1, want=("G", "s1")):
+        """hm_body_rec_gram: the frames k0 + i stride, i < n (default: as many as the record holds from k0) -> dict of those
+        in `want`: G (n, n) int64, the sum over the pixels of the product of every two of the frames; s1 (n,) uint64, the
+        sum of every frame."""
+        k0, stride = int(k0), int(stride)
+        if n is None:
+            F = self.body_rec_count()
+            n = (F - 1 - k0) // stride + 1 if stride >= 1 and 0 <= k0 < F else 1          # (out of range: the call says why)
+        n = int(n)
+        m = min(max(n, 1), 8192)                                                       # (n out of range: the call says so)
+        o = {}
+        if "G" in want:
+            o["G"] = np.empty((m, m), np.int64)
+        if "s1" in want:
+            o["s1"] = np.empty(m, np.uint64)
+        _lib.check(_lib.lib().hm_body_rec_gram(self._h, k0, n, stride, *[_lib.ptr(o[k]) if k in o else None for k in ("G", "s1")]),
+                   "hm_body_rec_gram")
+        return o
+
     # -- residual motion of the record (hm_body_rec_match / _frame_sums / _shift / _warp / _field_sums; hydra_mi.stabilize) --
     def body_rec_patches(self, B):
         """-> (patches per row, patch rows) of the grid of B x B patches over the record's box (the bounding box of the

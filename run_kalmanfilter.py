@@ -153,6 +153,14 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      --network also net_r_events: network.coactivity of ev_s, as net_r is of the traces.
     --events-video OUT.avi   with --events: the event bytes min(255, floor(s + 0.5)) of every pixel and frame in the body
                      frame, grey (hydra_mi.events.event_video), through the writer of --dff-video.
+    --pca K          with --rois or --demix: the K dominant modes of the kept registered video with nobody naming a cell
+                     (hydra_mi.pca), from the Gram matrix of its frames made on the device's matrix cores; on the record as
+                     it stands after --stabilize and --deform-correct, before anything else reads it.  pca_lambda, pca_share
+                     (K): the eigenvalues of the video with every pixel's mean taken out, and their shares of its variance;
+                     pca_temporal (frames x K): the temporal vectors; pca_rho (K x H x W): every component's correlation
+                     image, rounded to float32 here; pca_frame_score (frames): per frame the median of Pearson's r over the
+                     pixels with every other frame, low where the track slipped.  At most 8192 frames.
+    --pca-frames     with --pca: also pca_frame_r (frames x frames, float32): Pearson's r of every two frames.
 """
 import argparse
 import os
@@ -164,6 +172,7 @@ import hydra_mi  # noqa: F401
 from hydra_mi import cellview
 from hydra_mi import kalman
 from hydra_mi import network
+from hydra_mi import pca
 from hydra_mi import demix
 from hydra_mi import residual
 from hydra_mi import deform
@@ -263,6 +272,9 @@ def main(argv=None):
                         help="with --network: significance against N circularly shifted traces (net_p_r, net_p_map, net_rho_max, net_sig, net_map_sig)")
     parser.add_argument("--network-alpha", default=0.05, type=float, help="with --network-null: the level a pixel is significant at")
     parser.add_argument("--network-guard", default=network.DEFAULT_LAG, type=int, help="with --network-null: no shift within N frames of 0")
+    parser.add_argument("--pca", default=None, type=int, metavar="K",
+                        help="with --rois or --demix: the K dominant modes of the kept registered video (pca_* arrays)")
+    parser.add_argument("--pca-frames", action="store_true", help="with --pca: also pca_frame_r, Pearson's r of every two frames")
     parser.add_argument("--network-seed", default=0, type=int, help="with --network-null: the seed the shifts are drawn with")
     parser.add_argument("--events", action="store_true", help="with --rois or --demix: events behind the dF/F traces and per pixel (ev_* arrays)")
     parser.add_argument("--events-g", default=None, type=float, help="the decay per frame, 0 < g < 1 (default: estimated per cell)")
@@ -346,11 +358,24 @@ def main(argv=None):
         parser.error("--deform-correct works on the kept record: it needs --rois or --demix")
     if args.deform_gamma is not None and not (args.deform_correct and 0.0 <= args.deform_gamma <= deform.GAMMA_MAX):
         parser.error("--deform-gamma needs --deform-correct and an exponent in 0..%g" % deform.GAMMA_MAX)
+    if args.pca is not None:
+        if not (args.rois or keep_record):
+            parser.error("--pca reads the kept record: it needs --rois or --demix")
+        if args.pca < 1:
+            parser.error("--pca needs at least one component")
+    if args.pca_frames and args.pca is None:
+        parser.error("--pca-frames adds the frame similarity: it needs --pca")
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
 
     capture = VideoStream(args.fn_in, args.threshold)          # reference run_kalmanfilter.py:58
     frame = capture.current_frame()
+    if args.pca is not None:                                   # before any tracking
+        n_rec = capture.frames.shape[0] - 1
+        if n_rec > pca.GRAM_MAX:
+            parser.error("--pca: a record of %d frames, one Gram matrix takes %d at the most" % (n_rec, pca.GRAM_MAX))
+        if args.pca > n_rec - 1:
+            parser.error("--pca: %d components of %d frames (need 1..%d)" % (args.pca, n_rec, n_rec - 1))
     mask, ctrs, fd = capture.backsub()
     distmesh = DistMesh(frame, h0=args.gridsize)               # reference run_kalmanfilter.py:62-63
     distmesh.createMesh(ctrs, fd, frame, plot=False)
@@ -480,6 +505,17 @@ def main(argv=None):
               "median |r| with the area change %.3f -> %.3f" % (
                   dc["gamma"], "fitted" if dc["fitted"] else "given" if args.deform_gamma is not None else "nothing to fit from",
                   dc["fit_r2"], dc["gain"].min() / 4096.0, dc["gain"].max() / 4096.0, dc["gain"].shape[1], dc["clipped"], *med))
+    if args.pca is not None and body is not None and body.keep and len(states):
+        # after the stabiliser and the deformation correction, before everything else that reads the kept record
+        pc = pca.pca(body, min(args.pca, max(len(states) - 1, 1)), frames=args.pca_frames)      # (a run that ended early)
+        extra.update(pca_lambda=pc["lam"], pca_share=pc["share"], pca_temporal=pc["temporal"],
+                     pca_rho=pc["rho"].astype(np.float32), pca_frame_score=pc["frame_score"])
+        if args.pca_frames:
+            extra.update(pca_frame_r=pc["frame_r"].astype(np.float32))
+        print("PCA: %d components of %d frames carry %s of the variance; lowest frame score %.3f at frame %d" % (
+            len(pc["lam"]), len(states), " ".join("%.4f" % v for v in pc["share"]),
+            np.nanmin(pc["frame_score"]) if np.isfinite(pc["frame_score"]).any() else np.nan,
+            int(np.nanargmin(pc["frame_score"])) + 1 if np.isfinite(pc["frame_score"]).any() else -1))
     det_kind = "excess" if args.detrend else "recorded" if args.resummarize else None
     if det_kind is not None and not (body is not None and body.keep and len(states)):
         det_kind = None
