@@ -55,6 +55,8 @@ int hm_host_free(void *ptr);
 int hm_dev_upload_async(int device, void *dst, const void *src, uint64_t bytes, void *stream);
 /* ... and back: device -> page-locked host memory on the caller's copy stream (the video of the pipeline) */
 int hm_dev_download_async(int device, void *dst, const void *src, uint64_t bytes, void *stream);
+/* ... and device -> device on that stream (the frame ring's mirror slots when the frames are decoded on the device) */
+int hm_dev_copy_async(int device, void *dst, const void *src, uint64_t bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * Brox optical flow.  Replaces cv::cuda::BroxOpticalFlow as used by
@@ -1011,6 +1013,90 @@ int hm_mjpeg_header(hm_mjpeg_t enc, uint8_t *buf, uint64_t cap, uint64_t *n);
 uint64_t hm_mjpeg_max_bytes(hm_mjpeg_t enc);
 int hm_mjpeg_encode_dev(hm_mjpeg_t enc, const void *d_frame, void *out, uint64_t cap, uint32_t *size_word, void *stream);
 int hm_mjpeg_encode(hm_mjpeg_t enc, const uint8_t *frame, uint8_t *out, uint64_t cap, uint64_t *n);
+
+/* Motion-JPEG, decoding: a baseline JPEG decoder on the device for the frames of an MJPG video, bit-equal to libjpeg's
+ * default ("islow") decoder.  tests/mjpeg_dec_ref.py restates every rule below; DESIGN section 23.
+ *
+ *   Accepted    Baseline sequential DCT (SOF0), 8 bits; one component, or three (Y Cb Cr) in one interleaved scan with luma
+ *               sampling factors 1 or 2 each way and chroma 1 x 1 (4:4:4, 4:2:2 either way, 4:2:0); up to four 8-bit
+ *               quantisation tables; Huffman tables from DHT segments anywhere before SOS, and for a table the scan names
+ *               but no DHT defined the Annex K table of its class and index (K.3 - K.6; index 0 or 1); DRI of any value or
+ *               none; APPn, COM and other segments with a length are skipped; FF fill bytes before a marker are allowed.
+ *               With one component the sampling factors mean nothing: an MCU is one block.
+ *   Refused     on the host, HM_ERR_ARG with the marker or field in hm_last_error: SOF1 and above, DAC, a precision other
+ *               than 8, a 16-bit DQT, two or four components, a scan that does not hold every component (several scans), a
+ *               second SOS, other sampling factors, a scan that is not 0..63 / 0, any marker but RSTn and EOI inside the
+ *               scan, and (by the decoder) a frame size other than the handle's.
+ *   Output      the one component, or of three the luma plane (what libjpeg gives for grey output, PIL's
+ *               draft("L", size)); chroma blocks are Huffman-decoded to step over them and never transformed.  On in-gamut
+ *               colours this is within rounding of rint(0.114 B + 0.587 G + 0.299 R) of the decoded colours; where the
+ *               colour conversion clamps R, G or B it is not (up to 16 grey levels on saturated noise).
+ *   Intervals   The host scans the entropy-coded segment once for markers (FF followed by neither 00 nor FF).  With DRI = Ri
+ *               the RSTn found must number ceil(MCUs / Ri) - 1 and run 0..7 in turn, else the frame is refused; interval i
+ *               is the bytes between the markers, [start, end), and begins at MCU i Ri.  Without DRI the frame is one
+ *               interval.  EOI ends the last; a file cut before EOI ends it with the file.
+ *   Entropy     Per interval, DC predictions from 0.  A block: the DC category t (Huffman) and t bits (EXTEND), added to the
+ *               component's prediction in 32-bit wrap, the coefficient being the low 16 bits; then (run, size) symbols:
+ *               size 0 with run 15 moves 16 places (ZRL), size 0 otherwise ends the block, else run places are skipped and
+ *               size bits give the coefficient.  An MCU is hs x vs luma blocks, rows first, then one Cb and one Cr block.
+ *               Bytes: FF 00 is the data byte FF; an FF that no 00 follows ends the interval's data.
+ *   Bad         An interval is bad from the block in which a code is of no table, a DC category is above 11 or an AC size
+ *               above 10, a run or ZRL leaves index 63, or a bit is needed after the data ended.  That block and the rest
+ *               of the interval are all-zero coefficients (grey 128); the frame's status word counts its bad intervals.
+ *   Transform   coefficient x table entry, then libjpeg's jidctint.c: columns first, CONST_BITS 13, PASS1_BITS 2, descale
+ *               by 11 (pass 1) and 18 (pass 2) with rounding, the result through x & 1023 into the range-limit table
+ *               centred on 128.  All sums in 32-bit two's-complement wrap (uint32_t).  Equal to libjpeg for every stream
+ *               whose dequantised coefficients fit 16 bits (every stream an encoder writes); beyond, this is the rule.
+ *   Planes      the grey frame and, when their addresses are given, mask = frame > threshold (0 or 1) and shown =
+ *               mask x frame; every plane W x H at the caller's row pitch, frames of a run frame_stride bytes apart.
+ *
+ * hm_mjpeg_probe    host only: what the headers and the marker scan say.  hm_mjpeg_intervals: the interval table, three
+ *               words (start, end, first MCU) per interval.
+ * hm_mjpeg_dec_create  W, H in 1..32767, max_run (frames per hm_mjpeg_decode_run_dev) in 1..64; nothing runs on the device
+ *               before the first decode, which allocates the handle's buffers (128 bytes of coefficients per luma block
+ *               and frame of a run).  One owner for buffers, streams and events, released by hm_mjpeg_dec_destroy.
+ * hm_mjpeg_dec_tune    "entropy": HM_MJPEG_ENTROPY_AUTO / _HOST / _DEVICE: where the intervals are Huffman-decoded; both
+ *               give the same coefficients.  "auto_intervals": the intervals per frame from which AUTO takes the device
+ *               path, default 512 (measured at 1024^2: DESIGN section 23); 0: the device path exactly when the frame has a
+ *               DRI.  "pool": threads of the host path, 1..16, default 4, a frame at a time each; they are started by the
+ *               first run that needs them and sleep between runs.  On the host path the CPU does the Huffman decoding and
+ *               the coefficients are uploaded (hm_mjpeg_dec_uploaded).
+ * hm_mjpeg_dec_entropy_host  host only: the coefficients of every luma block in scan order (MCU by MCU), 64 each in zigzag
+ *               order, and the number of bad intervals.  coef: cap values, 8-byte aligned.
+ * hm_mjpeg_decode_run_dev  parses the frames (refusing before anything is queued), queues copies and two launches on
+ *               `stream` and returns: the planes of frame i at d_frame / d_mask / d_shown + i frame_stride (mask and shown
+ *               may be NULL), status_words[i] (device or page-locked memory, may be NULL) the frame's bad intervals.  No
+ *               state is carried between frames.  Staging is page-locked and used in turns of two; after the first decode
+ *               nothing is allocated unless a run has more bytes or intervals than any before.
+ * hm_mjpeg_dec_uploaded  the bytes that hm_mjpeg_decode_run_dev queued from host to device, in the last run and in all
+ *               runs of the handle (either pointer may be NULL).  Per frame of a run that is a descriptor of
+ *               HM_MJPEG_DESC_BYTES (scan, quantisation table, decode tables) and then, on the device entropy path, the
+ *               file's bytes rounded up to a multiple of 16 and 12 bytes per interval; on the host entropy path the Huffman
+ *               decoding has run on the CPU and the coefficients cross instead, 128 bytes per luma block of the scan,
+ *               which is 2 bytes per pixel of the padded frame and more than the file.
+ * hm_mjpeg_decode   one frame to host memory (W x H bytes), synchronous, on a stream of the handle's own; *bad (may be
+ *               NULL) the bad intervals; with strict != 0 a frame with bad intervals is HM_ERR_ARG (out is still written).
+ * Plain HIP: vector stores (32-bit words where base, stride and pitch are multiples of 4, else bytes), one atomicAdd. */
+typedef struct hm_mjpeg_info {
+    int32_t W, H, components, hs, vs, ri;       /* hs, vs: luma blocks of an MCU; ri: the DRI value, 0 without */
+    uint32_t intervals, mcus;
+} hm_mjpeg_info;
+#define HM_MJPEG_DESC_BYTES 5608
+#define HM_MJPEG_ENTROPY_AUTO 0
+#define HM_MJPEG_ENTROPY_HOST 1
+#define HM_MJPEG_ENTROPY_DEVICE 2
+typedef struct hm_mjpeg_dec *hm_mjpeg_dec_t;
+int hm_mjpeg_probe(const uint8_t *file, uint64_t n, hm_mjpeg_info *info);
+int hm_mjpeg_intervals(const uint8_t *file, uint64_t n, uint32_t *table, uint64_t cap);
+int hm_mjpeg_dec_create(int device, int W, int H, int max_run, hm_mjpeg_dec_t *out);
+int hm_mjpeg_dec_destroy(hm_mjpeg_dec_t dec);
+int hm_mjpeg_dec_tune(hm_mjpeg_dec_t dec, const char *name, int value);
+int hm_mjpeg_dec_entropy_host(hm_mjpeg_dec_t dec, const uint8_t *file, uint64_t n, int16_t *coef, uint64_t cap, uint32_t *bad);
+int hm_mjpeg_decode_run_dev(hm_mjpeg_dec_t dec, int nframes, const uint8_t *const *files, const uint64_t *sizes, void *d_frame,
+                            void *d_mask, void *d_shown, uint64_t frame_stride, uint64_t pitch, int threshold,
+                            uint32_t *status_words, void *stream);
+int hm_mjpeg_dec_uploaded(hm_mjpeg_dec_t dec, uint64_t *last_run, uint64_t *total);
+int hm_mjpeg_decode(hm_mjpeg_dec_t dec, const uint8_t *file, uint64_t n, uint8_t *out, int strict, uint32_t *bad);
 
 #ifdef __cplusplus
 }

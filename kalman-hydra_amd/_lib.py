@@ -36,6 +36,7 @@ SIGNATURES = {
     "hm_host_free": (ctypes.c_int, [c_vp]),
     "hm_dev_upload_async": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, ctypes.c_uint64, c_vp]),
     "hm_dev_download_async": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, ctypes.c_uint64, c_vp]),
+    "hm_dev_copy_async": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, ctypes.c_uint64, c_vp]),
     "hm_brox_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(c_vp)]),
@@ -200,6 +201,17 @@ SIGNATURES = {
     "hm_mjpeg_max_bytes": (ctypes.c_uint64, [c_vp]),
     "hm_mjpeg_encode_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp]),
     "hm_mjpeg_encode": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "hm_mjpeg_probe": (ctypes.c_int, [c_vp, ctypes.c_uint64, c_vp]),
+    "hm_mjpeg_intervals": (ctypes.c_int, [c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64]),
+    "hm_mjpeg_dec_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "hm_mjpeg_dec_destroy": (ctypes.c_int, [c_vp]),
+    "hm_mjpeg_dec_tune": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_int]),
+    "hm_mjpeg_dec_entropy_host": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64,
+                                                 ctypes.POINTER(ctypes.c_uint32)]),
+    "hm_mjpeg_decode_run_dev": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.c_int, c_vp, c_vp]),
+    "hm_mjpeg_dec_uploaded": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "hm_mjpeg_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 _lib = None

@@ -140,6 +140,14 @@ extern "C" int hm_dev_download_async(int device, void *dst, const void *src, uin
     return HM_OK;
 }
 
+extern "C" int hm_dev_copy_async(int device, void *dst, const void *src, uint64_t bytes, void *stream)
+{
+    HM_ARG(dst && src && stream, "hm_dev_copy_async: NULL pointer");
+    HM_HIP(hipSetDevice(device));
+    HM_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return HM_OK;
+}
+
 // ---- geometry -----------------------------------------------------------------------
 static Geo make_geo(int w, int h)
 {

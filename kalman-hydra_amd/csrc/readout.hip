@@ -833,53 +833,8 @@ extern "C" int hm_flow_preview(int device, int n, int W, int H, int channels, co
 
 // ---- Motion-JPEG: the baseline JPEG encoder of the video writer (mjpeg_kernels.h) ----------------
 #include "mjpeg_kernels.h"
+#include "mjpeg_tables.h"
 
-namespace {
-
-// ITU-T T.81 Annex K: table K.1 / K.2 (natural order) and the typical Huffman tables K.3 - K.6
-const uint8_t MJ_QUANT[2][64] = {
-    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
-     100, 103, 99},
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-const uint8_t MJ_DC_BITS[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
-const uint8_t MJ_DC_VALS[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-const uint8_t MJ_AC_BITS[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
-const uint8_t MJ_AC_VALS[2][162] = {
-    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
-     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
-     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
-     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
-     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
-     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
-     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
-    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
-     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
-     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
-     0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
-     0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
-     0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
-     0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
-
-// canonical codes of a table given as BITS / HUFFVAL (T.81 Annex C)
-template <typename Code, typename Len>
-void mj_huffman(const uint8_t bits[16], const uint8_t *vals, Code *code, Len *len)
-{
-    unsigned c = 0;
-    int k = 0;
-    for (int l = 1; l <= 16; l++) {
-        for (int i = 0; i < bits[l - 1]; i++, k++) {
-            code[vals[k]] = (Code)c++;
-            len[vals[k]] = (Len)l;
-        }
-        c <<= 1;
-    }
-}
-
-}  // namespace
 
 struct hm_mjpeg {
     int device = 0, quality = 0, restart_rows = 1;
@@ -1068,5 +1023,266 @@ extern "C" int hm_mjpeg_encode(hm_mjpeg_t e, const uint8_t *frame, uint8_t *out,
            (unsigned long long)cap);
     memcpy(out, e->header.data(), hdr);
     HM_HIP(hipMemcpy(out + hdr, e->d_out, size, hipMemcpyDeviceToHost));
+    return HM_OK;
+}
+
+
+// ---- Motion-JPEG, decoding (mjpeg_dec_kernels.h, mjpeg_dec.cpp) -----------------------------------
+#include "mjpeg_dec_kernels.h"
+#include <string>
+
+static_assert(sizeof(MjdFrame) == HM_MJPEG_DESC_BYTES, "hydra_mi.h states the size of a frame's descriptor");
+
+struct hm_mjpeg_dec {
+    int device = 0, W = 0, H = 0, max_run = 1;
+    int entropy = HM_MJPEG_ENTROPY_AUTO, pool = 4;                          // hm_mjpeg_dec_tune
+    int auto_intervals = 512;                    // hm_mjpeg_dec_tune "auto_intervals": measured, DESIGN section 23 (256: the host pool still wins)
+    size_t blk_cap = 0;                          // luma blocks of a frame's slot in the coefficient buffer
+    HmOwner own{1};
+    std::vector<MjdParsed> parsed;               // per frame of a run, reused
+    MjdPool *workers = nullptr;                  // the host entropy path's threads: started by the first run that needs them
+    uint64_t last_h2d = 0, total_h2d = 0;        // bytes the last run, and all runs, queued host-to-device
+    // built by the first decode; the byte and interval buffers grow when a run is larger than any before
+    bool ready = false;
+    MjdFrame *d_frames = nullptr;
+    MjdInterval *d_iv = nullptr;
+    uint8_t *d_bytes = nullptr;
+    int16_t *d_coef = nullptr;
+    unsigned *d_bad = nullptr;
+    size_t iv_cap = 0, bytes_cap = 0;
+    struct Stage {                               // page-locked; two, used in turn, so that a run never writes what the copies
+        MjdFrame *frames = nullptr;              // of the run before may still read
+        MjdInterval *iv = nullptr;
+        uint8_t *bytes = nullptr;
+        int16_t *coef = nullptr;                 // host entropy path only
+        hipEvent_t copied = nullptr;
+        bool used = false;
+    } stage[2];
+    int turn = 0;
+    // hm_mjpeg_decode's own
+    hipStream_t stream = nullptr;
+    uint8_t *d_out = nullptr;
+    uint32_t *d_status = nullptr;
+};
+
+extern "C" int hm_mjpeg_dec_create(int device, int W, int H, int max_run, hm_mjpeg_dec_t *out)
+{
+    HM_ARG(out, "hm_mjpeg_dec_create: out is NULL");
+    *out = nullptr;
+    HM_ARG(W >= 1 && H >= 1 && W <= 32767 && H <= 32767, "hm_mjpeg_dec_create: frame size %dx%d outside 1..32767", W, H);
+    HM_ARG(max_run >= 1 && max_run <= 64, "hm_mjpeg_dec_create: max_run %d outside 1..64", max_run);
+    hm_mjpeg_dec *d = new hm_mjpeg_dec();
+    d->device = device; d->W = W; d->H = H; d->max_run = max_run;
+    d->blk_cap = (size_t)(2 * ((W + 15) / 16)) * (size_t)(2 * ((H + 15) / 16));        // covers every accepted sampling
+    d->parsed.resize((size_t)max_run);
+    *out = d;
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_dec_destroy(hm_mjpeg_dec_t d)
+{
+    if (!d) return HM_OK;
+    if (!d->own.mem.empty() || !d->own.streams.empty() || !d->own.events.empty()) {
+        (void)hipSetDevice(d->device);
+        (void)hipDeviceSynchronize();           // (decodes queued on the callers' streams read the handle's buffers)
+        d->own.release();
+    }
+    delete d->workers;
+    delete d;
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_dec_uploaded(hm_mjpeg_dec_t d, uint64_t *last_run, uint64_t *total)
+{
+    HM_ARG(d, "hm_mjpeg_dec_uploaded: NULL handle");
+    if (last_run) *last_run = d->last_h2d;
+    if (total) *total = d->total_h2d;
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_dec_tune(hm_mjpeg_dec_t d, const char *name, int value)
+{
+    HM_ARG(d && name, "hm_mjpeg_dec_tune: NULL argument");
+    const std::string n(name);
+    if (n == "entropy") {
+        HM_ARG(value >= HM_MJPEG_ENTROPY_AUTO && value <= HM_MJPEG_ENTROPY_DEVICE, "hm_mjpeg_dec_tune: entropy %d is none of 0 auto, 1 host, 2 device", value);
+        d->entropy = value;
+    } else if (n == "pool") {
+        HM_ARG(value >= 1 && value <= 16, "hm_mjpeg_dec_tune: pool %d outside 1..16", value);
+        d->pool = value;
+    } else if (n == "auto_intervals") {
+        HM_ARG(value >= 0, "hm_mjpeg_dec_tune: auto_intervals %d below 0", value);
+        d->auto_intervals = value;
+    } else {
+        HM_ARG(false, "hm_mjpeg_dec_tune: no tune named '%s' (entropy, pool, auto_intervals)", name);
+    }
+    return HM_OK;
+}
+
+static int mjd_parse_for(hm_mjpeg_dec *d, const char *who, const uint8_t *file, uint64_t n, MjdParsed *p)
+{
+    HM_TRY(mjd_parse(file, n, p));
+    HM_ARG(p->W == d->W && p->H == d->H, "%s: a frame of %dx%d for a decoder of %dx%d", who, p->W, p->H, d->W, d->H);
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_dec_entropy_host(hm_mjpeg_dec_t d, const uint8_t *file, uint64_t n, int16_t *coef, uint64_t cap,
+                                         uint32_t *bad)
+{
+    HM_ARG(d && file && coef && bad, "hm_mjpeg_dec_entropy_host: NULL argument");
+    MjdParsed &p = d->parsed[0];
+    HM_TRY(mjd_parse_for(d, "hm_mjpeg_dec_entropy_host", file, n, &p));
+    const uint64_t need = (uint64_t)p.frame.scan.n_mcu * p.hs * p.vs * 64;
+    HM_ARG(cap >= need, "hm_mjpeg_dec_entropy_host: %llu coefficients, room for %llu", (unsigned long long)need, (unsigned long long)cap);
+    HM_ARG(((uintptr_t)coef & 7) == 0, "hm_mjpeg_dec_entropy_host: coef is not 8-byte aligned");
+    *bad = mjd_entropy_host(p, file, coef);
+    return HM_OK;
+}
+
+static int mjd_buffers(hm_mjpeg_dec *d)
+{
+    if (d->ready) return HM_OK;
+    const size_t run = (size_t)d->max_run;
+    HM_HIP(d->own.alloc(&d->d_frames, run * sizeof(MjdFrame)));
+    HM_HIP(d->own.alloc(&d->d_coef, run * d->blk_cap * 64 * sizeof(int16_t)));
+    HM_HIP(d->own.alloc(&d->d_bad, run * sizeof(unsigned)));
+    for (hm_mjpeg_dec::Stage &s : d->stage) {
+        HM_HIP(d->own.host_alloc(&s.frames, run * sizeof(MjdFrame), hipHostMallocDefault));
+        HM_HIP(d->own.event(&s.copied));
+    }
+    HM_HIP(hipMemset(d->d_bad, 0, run * sizeof(unsigned)));       // k_mjdec_idct keeps it zero
+    HM_HIP(hipDeviceSynchronize());
+    d->ready = true;
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_decode_run_dev(hm_mjpeg_dec_t d, int nframes, const uint8_t *const *files, const uint64_t *sizes,
+                                       void *d_frame, void *d_mask, void *d_shown, uint64_t frame_stride, uint64_t pitch,
+                                       int threshold, uint32_t *status_words, void *stream)
+{
+    HM_ARG(d && files && sizes && d_frame, "hm_mjpeg_decode_run_dev: NULL argument");
+    HM_ARG(nframes >= 1 && nframes <= d->max_run, "hm_mjpeg_decode_run_dev: %d frames outside 1..max_run = %d", nframes, d->max_run);
+    HM_ARG(pitch >= (uint64_t)d->W, "hm_mjpeg_decode_run_dev: a row pitch of %llu for rows of %d", (unsigned long long)pitch, d->W);
+    HM_ARG(nframes == 1 || frame_stride >= pitch * (uint64_t)(d->H - 1) + (uint64_t)d->W,
+           "hm_mjpeg_decode_run_dev: a frame stride of %llu for frames of %d rows at pitch %llu", (unsigned long long)frame_stride, d->H,
+           (unsigned long long)pitch);
+    // the frames: parsed and refused before anything is queued
+    size_t n_iv = 0, n_bytes = 0, n_host = 0;
+    unsigned max_int = 0, max_blk = 0;
+    for (int i = 0; i < nframes; i++) {
+        HM_ARG(files[i], "hm_mjpeg_decode_run_dev: frame %d is NULL", i);
+        MjdParsed &p = d->parsed[(size_t)i];
+        HM_TRY(mjd_parse_for(d, "hm_mjpeg_decode_run_dev", files[i], sizes[i], &p));
+        MjdFrame &f = p.frame;
+        const bool dev = d->entropy == HM_MJPEG_ENTROPY_DEVICE ||
+                         (d->entropy == HM_MJPEG_ENTROPY_AUTO && (d->auto_intervals > 0 ? f.n_int >= (unsigned)d->auto_intervals : p.ri != 0));
+        f.dev_entropy = dev ? 1 : 0;
+        f.bad_host = 0;
+        f.int_off = (uint32_t)n_iv;
+        f.data_off = (uint32_t)n_bytes;
+        const unsigned nblk = f.scan.n_mcu * (unsigned)(p.hs * p.vs);
+        HM_ARG(nblk <= d->blk_cap, "hm_mjpeg_decode_run_dev: %u blocks in frame %d, room for %zu", nblk, i, d->blk_cap);
+        max_blk = std::max(max_blk, nblk);
+        if (dev) {
+            n_iv += f.n_int;
+            n_bytes += ((size_t)sizes[i] + 15) & ~(size_t)15;
+            max_int = std::max(max_int, f.n_int);
+        } else {
+            n_host++;
+        }
+    }
+    HM_ARG(n_bytes < (1ull << 32), "hm_mjpeg_decode_run_dev: %zu bytes in a run, 2^32 or more", n_bytes);
+    HM_HIP(hipSetDevice(d->device));
+    HM_TRY(mjd_buffers(d));
+    hipStream_t s = (hipStream_t)stream;
+    hm_mjpeg_dec::Stage &st = d->stage[d->turn];
+    d->turn ^= 1;
+    if (st.used) HM_HIP(hipEventSynchronize(st.copied));          // (the copies of the run before last: long done)
+    if (n_iv) {
+        HM_HIP(d->own.host_grow(&st.iv, n_iv * sizeof(MjdInterval), hipHostMallocDefault));
+        HM_HIP(d->own.host_grow(&st.bytes, n_bytes, hipHostMallocDefault));
+        if (n_iv > d->iv_cap || n_bytes > d->bytes_cap) {
+            HM_HIP(hipDeviceSynchronize());                       // (queued decodes may read the buffers that move)
+            d->iv_cap = std::max(d->iv_cap, n_iv + n_iv / 2);
+            d->bytes_cap = std::max(d->bytes_cap, n_bytes + n_bytes / 2);
+            HM_HIP(d->own.grow(&d->d_iv, d->iv_cap * sizeof(MjdInterval)));
+            HM_HIP(d->own.grow(&d->d_bytes, d->bytes_cap));
+        }
+    }
+    if (n_host) {
+        HM_HIP(d->own.host_grow(&st.coef, (size_t)d->max_run * d->blk_cap * 64 * sizeof(int16_t), hipHostMallocDefault));
+        const MjdParsed *ps[64];
+        const uint8_t *fs[64];
+        int16_t *cs[64];
+        uint32_t bad[64];
+        int which[64], k = 0;
+        for (int i = 0; i < nframes; i++)
+            if (!d->parsed[(size_t)i].frame.dev_entropy) {
+                ps[k] = &d->parsed[(size_t)i]; fs[k] = files[i]; cs[k] = st.coef + (size_t)i * d->blk_cap * 64; which[k++] = i;
+            }
+        if (d->workers && d->workers->threads() != d->pool) { delete d->workers; d->workers = nullptr; }      // (re-tuned)
+        if (!d->workers) d->workers = new MjdPool(d->pool);
+        d->workers->run(k, ps, fs, cs, bad);
+        for (int j = 0; j < k; j++) d->parsed[(size_t)which[j]].frame.bad_host = bad[j];
+    }
+    for (int i = 0; i < nframes; i++) {
+        const MjdParsed &p = d->parsed[(size_t)i];
+        st.frames[i] = p.frame;
+        if (p.frame.dev_entropy) {
+            memcpy(st.iv + p.frame.int_off, p.intervals.data(), p.intervals.size() * sizeof(MjdInterval));
+            memcpy(st.bytes + p.frame.data_off, files[i], (size_t)sizes[i]);
+        }
+    }
+    uint64_t h2d = (uint64_t)nframes * sizeof(MjdFrame);         // every host-to-device copy below adds its size
+    HM_HIP(hipMemcpyAsync(d->d_frames, st.frames, (size_t)nframes * sizeof(MjdFrame), hipMemcpyHostToDevice, s));
+    if (n_iv) {
+        HM_HIP(hipMemcpyAsync(d->d_iv, st.iv, n_iv * sizeof(MjdInterval), hipMemcpyHostToDevice, s));
+        HM_HIP(hipMemcpyAsync(d->d_bytes, st.bytes, n_bytes, hipMemcpyHostToDevice, s));
+        h2d += n_iv * sizeof(MjdInterval) + n_bytes;
+    }
+    for (int i = 0; i < nframes; i++) {
+        const MjdFrame &f = d->parsed[(size_t)i].frame;
+        if (f.dev_entropy) continue;
+        const size_t at = (size_t)i * d->blk_cap * 64, count = (size_t)f.scan.n_mcu * (size_t)(f.scan.hs * f.scan.vs) * 64;
+        HM_HIP(hipMemcpyAsync(d->d_coef + at, st.coef + at, count * sizeof(int16_t), hipMemcpyHostToDevice, s));
+        h2d += count * sizeof(int16_t);
+    }
+    d->last_h2d = h2d;
+    d->total_h2d += h2d;
+    HM_HIP(hipEventRecord(st.copied, s));
+    st.used = true;
+    if (n_iv)
+        hipLaunchKernelGGL(k_mjdec_entropy, dim3((unsigned)hm_cdiv((int)max_int, MJD_ENT_THREADS), (unsigned)nframes), dim3(MJD_ENT_THREADS),
+                           0, s, (const MjdFrame *)d->d_frames, (const MjdInterval *)d->d_iv, (const uint8_t *)d->d_bytes, d->d_coef,
+                           d->blk_cap, d->d_bad);
+    MjdOut o{};
+    o.frame = (uint8_t *)d_frame; o.mask = (uint8_t *)d_mask; o.shown = (uint8_t *)d_shown;
+    o.frame_stride = (size_t)frame_stride; o.pitch = (size_t)pitch;
+    o.W = d->W; o.H = d->H; o.threshold = threshold;
+    o.words = (((uintptr_t)d_frame | (uintptr_t)d_mask | (uintptr_t)d_shown | (uintptr_t)frame_stride | (uintptr_t)pitch) & 3) == 0;
+    hipLaunchKernelGGL(k_mjdec_idct, dim3((unsigned)hm_cdiv((int)max_blk, MJD_IDCT_BLOCKS), (unsigned)nframes), dim3(MJD_IDCT_THREADS), 0, s,
+                       (const MjdFrame *)d->d_frames, (const int16_t *)d->d_coef, d->blk_cap, o, d->d_bad, status_words);
+    HM_HIP(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_mjpeg_decode(hm_mjpeg_dec_t d, const uint8_t *file, uint64_t n, uint8_t *out, int strict, uint32_t *bad)
+{
+    HM_ARG(d && file && out, "hm_mjpeg_decode: NULL argument");
+    if (bad) *bad = 0;
+    HM_HIP(hipSetDevice(d->device));
+    const size_t fb = (size_t)d->W * d->H;
+    HM_HIP(d->own.stream(&d->stream, false));
+    HM_HIP(d->own.alloc(&d->d_out, fb));
+    HM_HIP(d->own.alloc(&d->d_status, sizeof(uint32_t)));
+    const uint8_t *files[1] = {file};
+    const uint64_t sizes[1] = {n};
+    HM_TRY(hm_mjpeg_decode_run_dev(d, 1, files, sizes, d->d_out, nullptr, nullptr, fb, (uint64_t)d->W, 0, d->d_status, d->stream));
+    uint32_t status = 0;
+    HM_HIP(hipMemcpyAsync(&status, d->d_status, sizeof(status), hipMemcpyDeviceToHost, d->stream));
+    HM_HIP(hipMemcpyAsync(out, d->d_out, fb, hipMemcpyDeviceToHost, d->stream));
+    HM_HIP(hipStreamSynchronize(d->stream));
+    if (bad) *bad = status;
+    HM_ARG(!strict || status == 0, "hm_mjpeg_decode: %u bad restart intervals (malformed entropy-coded data)", status);
     return HM_OK;
 }

@@ -47,7 +47,19 @@ def load_video(fn, gray=True):
     """The whole video as gray frames (frames, H, W) uint8 (gray=False: as read, (frames, H, W[, 3]) B G R) -- shared by run_kalmanfilter.py and
     optical_flow_ext.py, so that the tracker sees the frames its flow was computed on.  Sources (no OpenCV on this
     path; reference renderer.py:745 opens anything cv2.VideoCapture can): a NumPy ``.npy`` / ``.npz`` array of shape
-    (frames, H, W[, 3]), or a multi-page TIFF stack (``.tif`` / ``.tiff``, 8-bit gray or RGB pages, read with PIL)."""
+    (frames, H, W[, 3]), a multi-page TIFF stack (``.tif`` / ``.tiff``, 8-bit gray or RGB pages, read with PIL), or an
+    ``.avi`` (videoio.AviReader): Motion-JPEG frames are decoded on the device in runs (videoio.MjpegDecoder) and
+    downloaded, uncompressed 24-bit frames are read on the host.  A Motion-JPEG file always gives gray frames, also with
+    gray=False: a colour file's luma plane, which is libjpeg's gray output -- there is no colour decode."""
+    if str(fn).lower().endswith(".avi"):
+        from .videoio import AviReader, decode_avi
+        with AviReader(fn) as reader:
+            if len(reader) < 1:
+                raise ValueError("%s: no frames" % fn)
+            if reader.mjpeg:
+                return decode_avi(reader)
+            a = np.stack([reader.frame_bgr(f) for f in range(len(reader))])
+        return np.ascontiguousarray(to_gray(a) if gray else a)
     if str(fn).lower().endswith((".tif", ".tiff")):
         from PIL import Image, ImageSequence
         with Image.open(fn) as im:
@@ -220,10 +232,12 @@ class FrameRing:
         self._stream = _lib.c_vp()
         _lib.check(_lib.lib().hm_copy_stream_create(self.device, ctypes.byref(self._stream)), "hm_copy_stream_create")
         self._nstage = max(2, self.extra + 2) if self.R < self.F else min(self.F, 16)                    # frames staged between two waits for the copy stream
-        self._stage = _lib.c_vp()
-        _lib.check(_lib.lib().hm_host_alloc(self._nstage * self.planes * self.n, ctypes.byref(self._stage)), "hm_host_alloc")
-        self._stage_np = np.ctypeslib.as_array(ctypes.cast(self._stage, ctypes.POINTER(ctypes.c_uint8)),
-                                               shape=(self._nstage, self.planes, self.n))
+        self._stage, self._stage_np = None, None
+        if not hasattr(source, "upload_run"):                    # (a source that fills the slots itself stages nothing here)
+            self._stage = _lib.c_vp()
+            _lib.check(_lib.lib().hm_host_alloc(self._nstage * self.planes * self.n, ctypes.byref(self._stage)), "hm_host_alloc")
+            self._stage_np = np.ctypeslib.as_array(ctypes.cast(self._stage, ctypes.POINTER(ctypes.c_uint8)),
+                                                   shape=(self._nstage, self.planes, self.n))
         self._staged = 0
         self.synced_hi = 0
         _lib.register(self, 4)
@@ -259,6 +273,12 @@ class FrameRing:
             hi = min(int(hi), self.F)
             if hi - keep_from > self.R:
                 raise RuntimeError("frame ring too small: frames %d..%d asked for, %d slots" % (keep_from, hi - 1, self.R))
+            if self.hi < hi and hasattr(self.src, "upload_run"):  # a source that fills the slots on the device (AviSource)
+                if self._fence is not None:
+                    self._fence(self._stream)
+                    self._fence = None
+                self.bytes_uploaded += self.src.upload_run(self.hi, hi, self)
+                self.hi = hi
             while self.hi < hi:
                 f = self.hi
                 if self._staged == self._nstage:                  # the staging block is full: wait for its copies

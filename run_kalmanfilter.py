@@ -4,7 +4,12 @@
 Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
 
     fn_in            input video.  No OpenCV here: a .npy / .npz array of shape (frames, H, W)
-                     or (frames, H, W, 3) (BGR, converted as cvtColor BGR2GRAY does), 8-bit
+                     or (frames, H, W, 3) (BGR, converted as cvtColor BGR2GRAY does), 8-bit; or an .avi,
+                     Motion-JPEG (decoded on the GPU, hydra_mi.videoio.MjpegDecoder; a colour file gives its
+                     luma plane) or uncompressed 24-bit.  With a Motion-JPEG file and the flow computed
+                     in-process, the decoder fills the pipeline's frame ring itself (videoio.AviSource): frames of
+                     512 or more restart intervals reach the GPU as JPEG bytes; for others the Huffman decoding
+                     runs on the CPU and the coefficients are uploaded, 2 bytes a pixel
     flow_in          optic flow path prefix: <flow_in>_%03d_x.mat / _y.mat as written by the
                      flow tool (optical_flow_ext.py); if no flow files exist the flow is
                      computed in-process with the same Brox defaults, streamed to the filter on
@@ -454,7 +459,14 @@ def main(argv=None):
         print("Cannot read flow stream at %s*: computing Brox flow in-process" % args.flow_in)
         kf = kalman.IteratedMSKalmanFilter(distmesh, frame, np.zeros(frame.shape + (2,), np.float32), cuda=args.cuda,
                                            sparse=True, multi=True)
-        pipe = FlowEKFPipeline(kf, capture)          # frames, masks and background-subtracted frames read from the stream
+        source = capture                             # frames, masks and background-subtracted frames read from the stream
+        if str(args.fn_in).lower().endswith(".avi"):
+            from hydra_mi.videoio import AviReader, AviSource
+            with AviReader(args.fn_in) as reader:
+                mjpeg = reader.mjpeg
+            if mjpeg:                                # the device decoder writes the frame ring's planes
+                source = AviSource(args.fn_in, args.threshold, frames=capture.frames)
+        pipe = FlowEKFPipeline(kf, source)
         body = make_body(kf)
         sm = make_smoother(kf)
 
@@ -463,6 +475,8 @@ def main(argv=None):
             keep(kf, e, k + 1)
         pipe.run(on_frame=on_frame, video=video, body=body, smoother=sm)
         pipe.close()
+        if source is not capture:
+            source.close()
     if video is not None:
         video.close()
         print("Overlay video: %d frames in %s" % (video.frames, args.fn_out))
