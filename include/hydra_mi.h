@@ -635,6 +635,13 @@ int hm_body_stats_peaks(hm_ctx_t h, int which, int radius, double min_score, int
  * allocated as it grows.  max_bytes is its budget: the warp that would pass it fails with HM_ERR_STATE, names
  * the numbers and appends nothing (nor adds to the statistics).  begin called again starts over; end stops
  * and frees (harmless when not begun); count gives the frames appended since begin.
+ * The box may touch the frame's border on any side (the padding of a row then lies beyond the row, on the last row
+ * beyond the plane: no call reads or writes a plane there).  A body map without a pixel (no pixel centre is covered by the
+ * mesh at X = uv) is not an error: the box is the one pixel (0, 0), registered as 0, frames of 16 bytes.  Every call then
+ * works as on any record and gives what the rules below give over no pixel: warps and fetches of zeros, sums, products,
+ * counts and Gram matrices of zeros, n_core = 0 in the one patch of every grid, shifts, warps and gains that change
+ * nothing (clipped = 0), statistics images NaN throughout and no peak, trace_null's tmax and tmin NaN; a call that takes
+ * seeds refuses every seed, as it refuses any seed that is no pixel of the map.
  * fetch: frames k0 .. k0 + n - 1 as full W*H planes (0 outside the box), equal to what the warps returned.
  * The reductions run over all F recorded frames, wait for the warps queued so far and for their results, and
  * fail with HM_ERR_STATE before begin and while no frame is recorded.  v_k(p) is the registered value of
