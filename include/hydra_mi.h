@@ -1105,6 +1105,59 @@ int hm_mjpeg_decode_run_dev(hm_mjpeg_dec_t dec, int nframes, const uint8_t *cons
 int hm_mjpeg_dec_uploaded(hm_mjpeg_dec_t dec, uint64_t *last_run, uint64_t *total);
 int hm_mjpeg_decode(hm_mjpeg_dec_t dec, const uint8_t *file, uint64_t n, uint8_t *out, int strict, uint32_t *bad);
 
+/* 16-bit input: frames of unsigned 16-bit pixels mapped to the 8 bits everything downstream works in, through one window
+ * for the whole recording chosen from its histogram.  tests/deep_ref.py restates every rule below; DESIGN section 24.
+ *
+ *   Histogram   h[v], v = 0..65535, counts the pixels of the frames given.  The counts are exact 64-bit integers.  It is
+ *               additive over calls until reset.
+ *   Window      Inputs are lo_ppm and hi_ppm, whole parts per million in 0..1 000 000.  N = sum h, and cum(v) = sum of
+ *               h[u] over u <= v.  lo is the least v with cum(v) > N lo_ppm // 10^6 (with lo_ppm = 10^6 there is none: then
+ *               lo = 65535, and the repair below applies).  hi is the least v with
+ *               cum(v) >= max(1, (N hi_ppm + 10^6 - 1) // 10^6).  If hi <= lo, then hi = lo + 1, capped at 65535 with
+ *               lo = 65534.  No floating point is used.  Defaults: lo_ppm = 1000 and hi_ppm = 999 990; these are policy,
+ *               not measurements, and every interface exposes them.  (The window is computed on the host, from
+ *               hm_deep_hist_get: hydra_mi.deepio.window.)
+ *   Table       lut[v] for all 65536 v, with t = min(max(v, lo), hi) - lo and D = hi - lo.  With gamma = 1 (the default),
+ *               lut[v] = (510 t + D) // (2 D): this rounds half up.  Otherwise lut[v] = floor(255 (t / D)^gamma + 0.5) in
+ *               binary64.  The host makes the table once (hydra_mi.deepio.make_lut); the device only applies it, so host
+ *               and device agree by construction.
+ *   Mapping     raw = lut[v], mask = raw > threshold, shown = mask ? raw : 0.  threshold is on the 8-bit scale, as the
+ *               tracker's -t is everywhere else.  swap = 1 exchanges the two bytes of v first, for big-endian files.  Per
+ *               frame there are two 32-bit counts: pixels with v < lo and pixels with v > hi.
+ *
+ * hm_deep_create  W, H in 1..32767, max_run (frames per hm_deep_map_run_dev) in 1..64; nothing runs on the device before
+ *               the first call that needs it, which allocates the handle's buffers: max_run frames of 16-bit pixels on
+ *               the device and twice that page-locked, the table, 65536 64-bit counts.  One owner for buffers, streams
+ *               and events, released by hm_deep_destroy.
+ * hm_deep_hist_reset / _add / _get  the histogram of the handle.  add takes nframes >= 1 dense frames of W x H uint16 in
+ *               host memory, works through them max_run frames at a time on a stream of the handle's own and returns when
+ *               they are counted.  get: hist[65536] and (samples may be NULL) the pixels counted, the sum of hist.
+ * hm_deep_set_lut  the table (65536 bytes, copied) and the window it was made for, 0 <= lo < hi <= 65535; lo >= hi is
+ *               HM_ERR_ARG with both numbers.  The device reads lut[min(max(v, lo), hi)], so only lut[lo .. hi] matters.
+ * hm_deep_map_run_dev  queues, on `stream`, the copy of nframes (1..max_run) dense host frames and one launch, and returns:
+ *               the planes of frame i at d_frame / d_mask / d_shown + i stride (stride >= W H bytes; mask and shown may be
+ *               NULL), rows dense, nothing outside W H bytes of each frame's plane written; d_status (device or page-locked
+ *               memory, may be NULL): 2 nframes words, frame i's pixels below lo and above hi.  Refused with the numbers in
+ *               hm_last_error: nframes outside 1..max_run, a threshold outside 0..255 (HM_ERR_ARG), no table set
+ *               (HM_ERR_STATE).  Staging is page-locked and used in turns of two; the host frames may be reused on return.
+ *               One map of a handle at a time: queue them on one stream, or order them yourself.
+ * hm_deep_map     one frame to host memory (W x H bytes, threshold 0, no mask), synchronous, on the handle's stream;
+ *               clipped (may be NULL): the two counts.
+ * hm_deep_uploaded  the bytes hm_deep_map_run_dev queued from host to device, in the last run and in all runs (either
+ *               pointer may be NULL): 2 W H per frame.
+ * Plain HIP, integers only: vector stores (8 bytes where the addresses allow, else bytes), LDS and global atomicAdd. */
+typedef struct hm_deep *hm_deep_t;
+int hm_deep_create(int device, int W, int H, int max_run, hm_deep_t *out);
+int hm_deep_destroy(hm_deep_t deep);
+int hm_deep_hist_reset(hm_deep_t deep);
+int hm_deep_hist_add(hm_deep_t deep, int64_t nframes, const uint16_t *host_frames, int swap);
+int hm_deep_hist_get(hm_deep_t deep, uint64_t *hist, uint64_t *samples);
+int hm_deep_set_lut(hm_deep_t deep, const uint8_t *lut, int lo, int hi);
+int hm_deep_map_run_dev(hm_deep_t deep, int nframes, const uint16_t *host_frames, int swap, void *d_frame, void *d_mask,
+                        void *d_shown, uint64_t stride, int threshold, uint32_t *d_status, void *stream);
+int hm_deep_map(hm_deep_t deep, const uint16_t *host_frame, int swap, uint8_t *out, uint32_t *clipped);
+int hm_deep_uploaded(hm_deep_t deep, uint64_t *last_run, uint64_t *total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,16 @@ SIGNATURES = {
                                                ctypes.c_int, c_vp, c_vp]),
     "hm_mjpeg_dec_uploaded": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "hm_mjpeg_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
+    "hm_deep_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "hm_deep_destroy": (ctypes.c_int, [c_vp]),
+    "hm_deep_hist_reset": (ctypes.c_int, [c_vp]),
+    "hm_deep_hist_add": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int]),
+    "hm_deep_hist_get": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "hm_deep_set_lut": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int]),
+    "hm_deep_map_run_dev": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_int,
+                                           c_vp, c_vp]),
+    "hm_deep_map": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "hm_deep_uploaded": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 _lib = None

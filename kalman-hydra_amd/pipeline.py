@@ -43,14 +43,28 @@ def to_gray(a):
     return a
 
 
-def load_video(fn, gray=True):
+def load_video(fn, gray=True, depth=None):
     """The whole video as gray frames (frames, H, W) uint8 (gray=False: as read, (frames, H, W[, 3]) B G R) -- shared by run_kalmanfilter.py and
     optical_flow_ext.py, so that the tracker sees the frames its flow was computed on.  Sources (no OpenCV on this
     path; reference renderer.py:745 opens anything cv2.VideoCapture can): a NumPy ``.npy`` / ``.npz`` array of shape
     (frames, H, W[, 3]), a multi-page TIFF stack (``.tif`` / ``.tiff``, 8-bit gray or RGB pages, read with PIL), or an
     ``.avi`` (videoio.AviReader): Motion-JPEG frames are decoded on the device in runs (videoio.MjpegDecoder) and
     downloaded, uncompressed 24-bit frames are read on the host.  A Motion-JPEG file always gives gray frames, also with
-    gray=False: a colour file's luma plane, which is libjpeg's gray output -- there is no colour decode."""
+    gray=False: a colour file's luma plane, which is libjpeg's gray output -- there is no colour decode.
+
+    16-bit input (a ``uint16`` array, a TIFF stack of 16-bit gray pages; hydra_mi.deepio) is mapped to 8 bits through one
+    window for the whole recording.  ``depth`` is None, {lo, hi, gamma} (the window itself) or {lo_ppm, hi_ppm, gamma}
+    (the shares, in parts per million, that the window leaves below lo and keeps up to hi; defaults 1000 and 999 990,
+    gamma 1).  Without lo and hi the window comes from the histogram of every pixel of every frame: a strided sample
+    of the frames can miss the rare bright burst, which is the signal, and the window would then saturate exactly there.
+    On a machine with a GPU the histogram and the mapping run on the device, without one in NumPy; the bytes are the
+    same.  ``depth`` does nothing to 8-bit input, which takes the path it always took."""
+    from . import deepio
+    deep = deepio.load_deep(fn, depth)
+    if deep is not None:
+        if isinstance(deep["source"], deepio.TiffStack):
+            deep["source"].close()
+        return deep["frames"]
     if str(fn).lower().endswith(".avi"):
         from .videoio import AviReader, decode_avi
         with AviReader(fn) as reader:

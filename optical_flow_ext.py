@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""optical_flow_ext.py [--video-codec raw|mjpeg] [--video-quality Q] <video> <output prefix> [alpha] [gamma] [scale_factor]
+"""optical_flow_ext.py [--video-codec raw|mjpeg] [--video-quality Q] [--depth-range LO,HI] [--depth-percentiles LO_PPM,HI_PPM]
+                       [--depth-gamma G] <video> <output prefix> [alpha] [gamma] [scale_factor]
                        [inner_it] [outer_it] [solver_it]
 
 The flow tool of the reference (reference src/optical_flow_ext.cpp:441-507) on MI355X:
@@ -13,6 +14,10 @@ With HYDRA_MI_FLOW_PREVIEW=1 it also writes <prefix>.avi (:336-389): frame n is 
 0.4 / 0.6 with the flow of pair n in the Middlebury colour code, saturating at 15 px (hm_flow_preview; the AVI is
 the library's, uncompressed, 20 frames/s) -- the same bytes as the native tool writes.  --video-codec mjpeg (default
 raw) writes the preview as Motion-JPEG at --video-quality (1..100, default 90) instead.
+A 16-bit video (a uint16 array, a TIFF stack of 16-bit gray pages) is mapped to 8 bits through one window for the whole
+recording (hydra_mi.deepio): --depth-range gives it, --depth-percentiles (parts per million, default 1000,999990) asks for
+the one of the recording's histogram, --depth-gamma bends the table; run_kalmanfilter.py takes the same flags and resolves
+them through the same function.
 """
 import os
 import sys
@@ -20,7 +25,7 @@ import sys
 import numpy as np
 
 import hydra_mi  # noqa: F401
-from hydra_mi import brox, matio, pipeline, videoio
+from hydra_mi import brox, deepio, matio, pipeline, videoio
 
 
 def _video_opts(av):
@@ -45,16 +50,37 @@ def _video_opts(av):
     return rest, (dict(codec="mjpeg", quality=quality) if codec == "mjpeg" else {})
 
 
+def _depth_opts(av):
+    """takes --depth-range / --depth-percentiles / --depth-gamma out of the arguments -> (the rest, load_video's depth);
+    ValueError for a bad one"""
+    rest, opts = [], {}
+    it = iter(av)
+    for s in it:
+        if s in ("--depth-range", "--depth-percentiles", "--depth-gamma"):
+            v = next(it, None)
+            if v is None:
+                raise ValueError("%s needs a value" % s)
+            opts[s] = v
+        else:
+            rest.append(s)
+    return rest, deepio.depth_option(opts.get("--depth-range"), opts.get("--depth-percentiles"), opts.get("--depth-gamma"))
+
+
 def main(av):
     av, vopts = _video_opts(list(av))
     if vopts is None:
         sys.stderr.write("--video-codec is raw or mjpeg, --video-quality 1..100\n")
         return 1
+    try:
+        av, depth = _depth_opts(av)
+    except ValueError as exc:
+        sys.stderr.write("%s\n" % exc)
+        return 1
     if len(av) < 3:
         print(__doc__)
         return 1
     try:                                             # BGR -> gray as cvtColor(BGR2GRAY) (:366-368)
-        raw = pipeline.load_video(av[1], gray=False)
+        raw = pipeline.load_video(av[1], gray=False, depth=depth)
         a = np.ascontiguousarray(pipeline.to_gray(raw))
     except (OSError, ValueError) as exc:
         sys.stderr.write("Failed to open the video: %s\n" % exc)

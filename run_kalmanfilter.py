@@ -166,6 +166,18 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      image, rounded to float32 here; pca_frame_score (frames): per frame the median of Pearson's r over the
                      pixels with every other frame, low where the track slipped.  At most 8192 frames.
     --pca-frames     with --pca: also pca_frame_r (frames x frames, float32): Pearson's r of every two frames.
+    --depth-range LO,HI   16-bit input (a uint16 .npy / .npz array, a TIFF stack of 16-bit gray pages; hydra_mi.deepio): the
+                     window that becomes 0..255, given outright.
+    --depth-percentiles LO_PPM,HI_PPM   16-bit input: the window from the histogram of every pixel of the recording,
+                     made on the device: LO_PPM parts per million of the pixels lie below lo, at most 10^6 - HI_PPM above
+                     hi (default 1000,999990).
+    --depth-gamma G  16-bit input: the exponent of the table between lo and hi (default 1: linear, rounded half up).
+                     optical_flow_ext.py takes the same three flags and resolves them through the same function, so the
+                     tracker sees the frames its flow was computed on.  With the flow computed in-process the 16-bit
+                     pixels themselves go to the GPU, 2 bytes a pixel, and the device maps them as they enter the frame
+                     ring (deepio.DeepSource).  The states file gains depth_lo, depth_hi, depth_gamma and depth_clipped
+                     (frames x 2: every frame's pixels below lo and above hi), and one warning line is printed when
+                     more than ten times the share the window allows of some frame's pixels lie above hi.
 """
 import argparse
 import os
@@ -175,6 +187,7 @@ import numpy as np
 
 import hydra_mi  # noqa: F401
 from hydra_mi import cellview
+from hydra_mi import deepio
 from hydra_mi import kalman
 from hydra_mi import network
 from hydra_mi import pca
@@ -193,6 +206,19 @@ from hydra_mi.pipeline import FlowEKFPipeline, VideoStream
 from hydra_mi.renderer import FlowStream
 from hydra_mi.smooth import RTSSmoother, check_budget
 from hydra_mi.videoio import AviWriter
+
+
+def add_depth_arguments(parser):
+    parser.add_argument("--depth-range", default=None, metavar="LO,HI", help="16-bit input: the window that becomes 0..255")
+    parser.add_argument("--depth-percentiles", default=None, metavar="LO_PPM,HI_PPM",
+                        help="16-bit input: the window from the recording's histogram, in parts per million (default %d,%d)"
+                        % (deepio.DEFAULT_LO_PPM, deepio.DEFAULT_HI_PPM))
+    parser.add_argument("--depth-gamma", default=None, metavar="G", help="16-bit input: the exponent of the table (default 1)")
+
+
+def depth_of(args):
+    """the ``depth`` of pipeline.load_video from the three flags (ValueError for a bad one)"""
+    return deepio.depth_option(args.depth_range, args.depth_percentiles, args.depth_gamma)
 
 
 def main(argv=None):
@@ -288,7 +314,12 @@ def main(argv=None):
     parser.add_argument("--events-video", default=None, metavar="OUT.avi", help="with --events: write the event video in the body frame here (.avi)")
     parser.add_argument("--video-codec", default="raw", choices=("raw", "mjpeg"), help="the codec of every video written (default raw)")
     parser.add_argument("--video-quality", default=90, type=int, help="with --video-codec mjpeg: JPEG quality 1..100 (default 90)")
+    add_depth_arguments(parser)
     args = parser.parse_args(argv)
+    try:
+        depth = depth_of(args)
+    except ValueError as exc:
+        parser.error(str(exc))
     if not 1 <= args.video_quality <= 100:
         parser.error("--video-quality is 1..100")
     # (raw: the writers are called exactly as before)
@@ -373,7 +404,21 @@ def main(argv=None):
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
 
-    capture = VideoStream(args.fn_in, args.threshold)          # reference run_kalmanfilter.py:58
+    deep = deepio.load_deep(args.fn_in, depth)                 # 16-bit input: mapped through its window; None for 8-bit
+    deep_stack = None                                          # the mapped file behind it, which DeepSource reads
+    if deep is not None:
+        deep_stack = deep["source"] if isinstance(deep["source"], deepio.TiffStack) else None
+        if not 0 <= args.threshold <= 255:                     # (the device compares on the 8-bit scale and refuses others)
+            if deep_stack is not None:
+                deep_stack.close()
+            parser.error("-t/--threshold %d: with 16-bit input the threshold lies in 0..255, the scale of the mapped frames"
+                         % args.threshold)
+        print("16-bit input: window %d..%d (gamma %g) becomes 0..255; %d pixels below it, %d above"
+              % (deep["lo"], deep["hi"], deep["gamma"], int(deep["clipped"][:, 0].sum()), int(deep["clipped"][:, 1].sum())))
+        warn = deepio.clip_warning(deep["clipped"], deep["frames"].shape[1] * deep["frames"].shape[2], deep["hi_ppm"])
+        if warn:
+            print(warn)
+    capture = VideoStream(args.fn_in if deep is None else deep["frames"], args.threshold)          # reference run_kalmanfilter.py:58
     frame = capture.current_frame()
     if args.pca is not None:                                   # before any tracking
         n_rec = capture.frames.shape[0] - 1
@@ -435,6 +480,8 @@ def main(argv=None):
 
     if ret_flow:
         # the reference's loop (:78-89): one flow file per frame
+        if deep_stack is not None:
+            deep_stack.close()                                 # (the mapped frames are all this loop reads)
         kf = kalman.IteratedMSKalmanFilter(distmesh, frame, flowframe, cuda=args.cuda, sparse=True, multi=True)
         body = make_body(kf)
         sm = make_smoother(kf)
@@ -466,27 +513,38 @@ def main(argv=None):
                 mjpeg = reader.mjpeg
             if mjpeg:                                # the device decoder writes the frame ring's planes
                 source = AviSource(args.fn_in, args.threshold, frames=capture.frames)
-        pipe = FlowEKFPipeline(kf, source)
-        body = make_body(kf)
-        sm = make_smoother(kf)
+        if deep is not None:                         # the device maps the 16-bit pixels into the frame ring's planes
+            source = deepio.DeepSource(deep["source"], deep["lut"], deep["lo"], deep["hi"], args.threshold, frames=capture.frames)
+        pipe = None
+        try:
+            pipe = FlowEKFPipeline(kf, source)
+            body = make_body(kf)
+            sm = make_smoother(kf)
 
-        def on_frame(k, e):
-            print("Frame %d" % (k + 1))
-            keep(kf, e, k + 1)
-        pipe.run(on_frame=on_frame, video=video, body=body, smoother=sm)
-        pipe.close()
-        if source is not capture:
-            source.close()
+            def on_frame(k, e):
+                print("Frame %d" % (k + 1))
+                keep(kf, e, k + 1)
+            pipe.run(on_frame=on_frame, video=video, body=body, smoother=sm)
+        finally:                                     # also when tracking fails: the pipeline first, then what fed it
+            if pipe is not None:
+                pipe.close()
+            if source is not capture:
+                source.close()
+            if deep_stack is not None:
+                deep_stack.close()
     if video is not None:
         video.close()
         print("Overlay video: %d frames in %s" % (video.frames, args.fn_out))
     extra = {}
+    if deep is not None:
+        extra.update(depth_lo=np.int32(deep["lo"]), depth_hi=np.int32(deep["hi"]), depth_gamma=np.float64(deep["gamma"]),
+                     depth_clipped=deep["clipped"])
     cv_cells = cv_levels = cv_points = None          # what --cells-video draws
     st_cells = st_dff = None                         # what --strain reads the tissue under: (labels or points), their dF/F
     more = None                                      # what --find-more found
     if body is not None:
         res = body.results()
-        extra = {"tri_means": res["tri_means"], "tri_counts": res["tri_counts"]}
+        extra.update(tri_means=res["tri_means"], tri_counts=res["tri_counts"])       # (beside depth_* of a 16-bit input)
         if points is not None:
             extra.update(points=res["points"], point_means=res["point_means"], point_counts=res["point_counts"])
             fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
