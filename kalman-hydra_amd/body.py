@@ -23,11 +23,10 @@ BodyReadout(kf, keep=True) keeps the registered video itself on the device (hm_b
 footprints, ROIs and neuropil-corrected dF/F traces from it, and the traces of points found afterwards need no second pass.
 """
 import ctypes
-import threading
 
 import numpy as np
 
-from . import _lib
+from .pipeline import SlotRing
 
 SUB = 256          # the render's sub-pixel grid (csrc/ekf_kernels.h EKF_SUB)
 
@@ -175,6 +174,11 @@ def _means(sums, counts):
         return np.where(c > 0, s / np.where(c > 0, c, 1.0), np.nan)
 
 
+def renderer_of(kf_or_renderer):
+    """The renderer.Renderer of a kalman.*KalmanFilter, or the renderer itself"""
+    return kf_or_renderer.state.renderer if hasattr(kf_or_renderer, "state") else kf_or_renderer
+
+
 class BodyReadout:
     """The body-frame readout of one tracker (a kalman.*KalmanFilter or a renderer.Renderer).
 
@@ -187,8 +191,7 @@ class BodyReadout:
 
     def __init__(self, kf_or_renderer, points=None, point_radius=3.0, labels=None, video=None, stats=False, keep=False,
                  keep_bytes=8 << 30):
-        r = kf_or_renderer.state.renderer if hasattr(kf_or_renderer, "state") else kf_or_renderer
-        self.r = r
+        r = self.r = renderer_of(kf_or_renderer)
         self.H, self.W, self.T = r.ny, r.nx, int(r.tri.shape[0])
         self.video = video
         if video is not None and (video.width, video.height) != (self.W, self.H):
@@ -280,8 +283,19 @@ class BodyReadout:
         if not self.stats:
             raise RuntimeError("BodyReadout.find_points: the readout was made without stats=True")
         idx, sc, _ = self.r.body_stats_peaks(score, radius, -np.inf if min_score is None else float(min_score), int(n))
-        rr, cc = np.divmod(idx.astype(np.int64), self.W)
-        return np.stack((cc + 0.5, rr + 0.5), 1).astype(np.float64).reshape(-1, 2), sc
+        return self.pixel_points(idx), sc
+
+    def pixel_points(self, idx):
+        """Raster indices (P,) of the body frame -> (P, 2) float64, the pixel centres (c + 0.5, r + 0.5)"""
+        rr, cc = np.divmod(np.asarray(idx).astype(np.int64), self.W)
+        return np.stack((cc + 0.5, rr + 0.5), 1).astype(np.float64).reshape(-1, 2)
+
+    def record(self, who):
+        """The renderer that holds this readout's kept record (keep=True); `who` names the caller in the refusal.
+        (Called as BodyReadout.record(body, who): a stand-in for a readout need carry `keep` and `r` alone.)"""
+        if not getattr(self, "keep", False):
+            raise RuntimeError("%s: the readout was made without keep=True" % who)
+        return self.r
 
     def results(self):
         """Arrays with one row per state passed: tri_sums / tri_means (F x T), tri_counts (T); with labels label_sums /
@@ -350,7 +364,7 @@ def read_out_recorded(body, states, points, point_radius=3.0):
     return {"points": pos, "point_means": means, "point_counts": counts}
 
 
-class BodyTap:
+class BodyTap(SlotRing):
     """The readout of a pipeline run (FlowEKFPipeline.run(body=...)): after every step the warp of the raw frame at the
     state the frame ended with is queued on the filter's stream (hm_body_warp_dev) into a ring of device slots -- its
     sums, and the registered frame as B = G = R when the readout has a video --, copied into page-locked memory on a copy
@@ -363,111 +377,47 @@ class BodyTap:
     the writer thread copies the stream's own bytes (videoio.MjpegSlots)."""
 
     def __init__(self, body, device=0, slots=4):
-        import queue
-        self.b, self.device, self.slots = body, int(device), int(slots)
+        self.b = body
         r = body.r
         self.npx = r.nx * r.ny
         self.ns = 8 * (body.T + body.L)                 # a slot: the sums (8-byte aligned), then the frame, if any
         self.nv = 3 * self.npx if body.video is not None else 0
         self.ch = 3
-        self._mj = None
-        if body.video is not None and getattr(body.video, "mjpeg", False):
-            from .videoio import MjpegSlots
+        mjpeg = body.video is not None and getattr(body.video, "mjpeg", False)
+        if mjpeg:
             self.ch = body.video.channels
             self.nv = self.ch * self.npx
-            self._mj = MjpegSlots(body.video.encoder, self.slots, device)
         self.stride = self.ns + self.nv
-        L = _lib.lib()
-        self._stream = _lib.c_vp()
-        _lib.check(L.hm_copy_stream_create(self.device, ctypes.byref(self._stream)), "hm_copy_stream_create")
-        self._pin = _lib.c_vp()
         # (MJPEG: the frame stays on the device, with the stream the encoder makes of it behind it)
-        self.nd = self.ns if self._mj is not None else self.stride            # bytes of a slot that are downloaded
-        _lib.check(L.hm_host_alloc(self.slots * self.stride, ctypes.byref(self._pin)), "hm_host_alloc")
-        from .pipeline import DeviceBuffer
-        self._dev = [DeviceBuffer(self.stride + (self._mj.cap if self._mj is not None else 0), device)
-                     for _ in range(self.slots)]
-        self._free = threading.Semaphore(self.slots)
-        self._q = queue.Queue()
-        self._next = 0
-        self._error = None
-        self._closed = False
-        self._thread = threading.Thread(target=self._write_loop, name="hydra_mi-body", daemon=True)
-        self._thread.start()
-        _lib.register(self, 0)
+        self.nd = self.ns if mjpeg else self.stride                           # bytes of a slot that are downloaded
+        SlotRing.__init__(self, "hydra_mi-body", device, slots, self.stride, self.stride, body.video.encoder if mjpeg else None)
 
     def frame(self, X, d_frame, ring=None):
         """Queue the readout of the raw frame at device address d_frame at state X (a frame of `ring`, if given)."""
-        if self._error is not None:
-            raise self._error
-        self.b._own_labels()                        # (the slot holds the sums of this readout's L labels)
-        self._free.acquire()
-        s = self._next % self.slots
-        self._next += 1
-        d = self._dev[s].ptr
-        b = self.b
-        self.b._keep(X, None, None)
-        row = len(b._rows) - 1
-        b.r.body_warp_dev(X, d_frame, d + self.ns if self.nv else None, self.ch, d, d + 8 * b.T if b.L else None, self._stream)
-        if ring is not None:
-            ring.fence_after(lambda st: b.r.body_fence(st))
-        if self._mj is not None:
-            b.video.encoder.encode_dev(d + self.ns, d + self.stride, self._mj.cap, self._mj.size_word(s), self._stream)
-        _lib.check(_lib.lib().hm_dev_download_async(self.device, self._pin.value + s * self.stride, d, self.nd,
-                                                    self._stream), "hm_dev_download_async")
-        self._q.put((s, row))
-
-    def _write_loop(self):
-        L = _lib.lib()
-        while True:
-            item = self._q.get()
-            if item is None:
-                return
-            s, row = item
-            try:
-                if self._error is None:
-                    _lib.check(L.hm_copy_stream_sync(self.device, self._stream), "hm_copy_stream_sync")
-                    base = self._pin.value + s * self.stride
-                    blk = np.ctypeslib.as_array(ctypes.cast(base, ctypes.POINTER(ctypes.c_uint64)),
-                                                shape=(self.b.T + self.b.L,)).copy()
-                    self.b._rows[row][1] = blk[:self.b.T]
-                    self.b._rows[row][2] = blk[self.b.T:] if self.b.L else None
-                    if self._mj is not None:
-                        self._mj.finish(s, self._dev[s].ptr + self.stride, self.b.video)
-                    elif self.nv:
-                        self.b.video.write_ptr(base + self.ns)
-            except Exception as e:          # noqa: BLE001 -- reported by the next frame() / close()
-                self._error = e
-            finally:
-                self._free.release()
-
-    def drain(self):
-        """Wait until every frame queued so far has been taken."""
-        for _ in range(self.slots):
-            self._free.acquire()
-        for _ in range(self.slots):
-            self._free.release()
-        if self._error is not None:
-            raise self._error
-
-    def close(self):
-        if self._closed:
-            return
-        self._closed = True
+        s, d = self._take()
         try:
-            self._q.put(None)
-            self._thread.join()
-        finally:
-            L = _lib.lib()
-            if self._stream:
-                L.hm_copy_stream_destroy(self.device, self._stream)
-                self._stream = None
-            for b in self._dev:
-                b.close()
+            b = self.b
+            b._own_labels()                         # (the slot holds the sums of this readout's L labels)
+            b._keep(X, None, None)
+            row = len(b._rows) - 1
+            b.r.body_warp_dev(X, d_frame, d + self.ns if self.nv else None, self.ch, d, d + 8 * b.T if b.L else None, self._stream)
+            if ring is not None:
+                ring.fence_after(lambda st: b.r.body_fence(st))
             if self._mj is not None:
-                self._mj.close()
-            if self._pin:
-                L.hm_host_free(self._pin)
-                self._pin = None
-        if self._error is not None:
-            raise self._error
+                b.video.encoder.encode_dev(d + self.ns, d + self.stride, self._mj.cap, self._mj.size_word(s), self._stream)
+            self._download(s, self.nd)
+        except Exception:
+            self._give_back()
+            raise
+        self._submit((s, row))
+
+    def _written(self, item):
+        s, row = item
+        b, base = self.b, self._pinned(s)
+        blk = np.ctypeslib.as_array(ctypes.cast(base, ctypes.POINTER(ctypes.c_uint64)), shape=(b.T + b.L,)).copy()
+        b._rows[row][1] = blk[:b.T]
+        b._rows[row][2] = blk[b.T:] if b.L else None
+        if self._mj is not None:
+            self._mj.finish(s, self._dev[s].ptr + self.stride, b.video)
+        elif self.nv:
+            b.video.write_ptr(base + self.ns)

@@ -10,7 +10,6 @@ image at a tracked state, the body pixel under it and blends the colours of the 
 import numpy as np
 
 from . import body as _body
-from .videoio import AviWriter
 
 #: twelve B G R colours far apart in hue, none of them gray (the frame under them is)
 _PALETTE = np.array([[0, 0, 255], [0, 255, 0], [255, 0, 0], [0, 255, 255], [255, 0, 255], [255, 255, 0],
@@ -92,9 +91,8 @@ def write_video(kf_or_renderer, states, source, path, cells=None, levels=None, p
     uint8 (None: 255).  points: (P, 2) body coordinates, followed through the mesh (body.locate / body.track); each
     gets its palette colour.  The frames are uploaded one by one, the views queued on the tracker's stream into a ring of
     device slots and written by the writer thread of a pipeline.VideoTap: the disk is not waited for.  -> frames written."""
-    from .pipeline import DeviceBuffer, VideoTap
-    r = kf_or_renderer.state.renderer if hasattr(kf_or_renderer, "state") else kf_or_renderer
-    frame_at = source.frame_at if hasattr(source, "frame_at") else (lambda k: (source[k],))
+    from .pipeline import write_painted_video
+    r = _body.renderer_of(kf_or_renderer)
     F = len(states)
     if cells is None and points is None:
         raise ValueError("write_video: neither cells nor points to draw")
@@ -116,30 +114,9 @@ def write_video(kf_or_renderer, states, source, path, cells=None, levels=None, p
         pts = np.asarray(points, np.float64).reshape(-1, 2)
         t, ids, l1, l2 = _body.locate(r.uv, r.tri, pts)
         loc, colours = (ids, l1, l2, t >= 0), palette(pts.shape[0])
-    n = r.nx * r.ny
-    writer = AviWriter(path, r.nx, r.ny, fps=fps, **(video_opts or {}))
-    tap = VideoTap(r, writer)
-    d_frames = [DeviceBuffer(n, tap.device) for _ in range(tap.slots)]     # a frame is read when its view runs
-    try:
-        for k in range(F):
-            X = np.asarray(states[k], np.float64).reshape(-1)
-            img = np.ascontiguousarray(np.asarray(frame_at(k)[0], np.uint8).reshape(r.ny, r.nx))
-            p = None if loc is None else _body.track(X[:2 * r.n], *loc)
 
-            def queue(d_out, stream, k=k, X=X, img=img, p=p):
-                # the slot of this frame is free: the view that read the frame uploaded there `slots` frames ago has
-                # been waited for by the writer.  upload() waits for the copy; the view is queued behind it.
-                d = d_frames[k % tap.slots]
-                d.upload(img)
-                r.view_cells_dev(X, d.ptr, d_out, None if levels is None else levels[k], outline, wire, p, colours, point_radius,
-                                 stream)
-            tap.push(queue)
-    finally:
-        try:
-            tap.close()
-        finally:
-            for b in d_frames:
-                b.close()
-            writer.close()
-            r.view_set_cells(None)
-    return writer.frames
+    def paint(k, X, d_frame, d_out, stream):
+        p = None if loc is None else _body.track(X[:2 * r.n], *loc)
+        r.view_cells_dev(X, d_frame, d_out, None if levels is None else levels[k], outline, wire, p, colours, point_radius,
+                         stream)
+    return write_painted_video(r, states, source, path, paint, fps, video_opts, done=lambda: r.view_set_cells(None))

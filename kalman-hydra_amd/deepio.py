@@ -507,22 +507,13 @@ class DeepSource:
     def upload_run(self, f0, f1, ring):
         """Queue frames f0 .. f1 - 1 into `ring` (a FrameRing) on its copy stream: runs of consecutive slots, one map
         each, then the mirror slots by device-to-device copies.  -> the bytes queued host-to-device, 2 W H per frame."""
-        L = _lib.lib()
-        n, R, sent = ring.n, ring.R, 0
-        shown = ring.planes == 3
-        f = f0
-        while f < f1:
-            s = f % R
-            k = min(self.run, f1 - f, R - s)
-            self.handle.map_run_dev(self.fr.block(f, f + k), self.fr.swap, ring.d_video.ptr + s * n, ring.d_masks.ptr + s * n,
-                                    ring.d_observed.ptr + s * n if shown else None, n,
-                                    int(np.floor(self.threshold)), self._pin.value + 8 * f, ring._stream)   # raw > t for integer raw
+        sent = 0
+        for f, k, s, mirror in ring.runs(f0, f1, self.run):
+            d_raw, d_mask, d_shown, stride, stream = ring.run_dev(s)
+            self.handle.map_run_dev(self.fr.block(f, f + k), self.fr.swap, d_raw, d_mask, d_shown, stride,
+                                    int(np.floor(self.threshold)), self._pin.value + 8 * f, stream)   # raw > t for integer raw
             sent += self.handle.uploaded()[0]
-            for t in range(s, min(s + k, ring.extra)):            # the mirror behind the ring
-                for buf in (ring.d_video, ring.d_masks) + ((ring.d_observed,) if shown else ()):
-                    _lib.check(L.hm_dev_copy_async(self.device, buf.ptr + (R + t) * n, buf.ptr + t * n, n, ring._stream),
-                               "hm_dev_copy_async")
-            f += k
+            ring.mirror(mirror)
         return sent
 
     def close(self):

@@ -16,6 +16,7 @@ arithmetic in NumPy binary64, nothing of it is compared to the device bit for bi
 import numpy as np
 
 from . import strain
+from .body import BodyReadout
 
 ONE = 4096                            # the gain that changes nothing: hm_body_rec_tri_gain works in 1/4096
 QMAX = 32767                          # the largest |q| hm_body_rec_tri_maps takes
@@ -24,9 +25,7 @@ GAMMA_MAX = 3.0
 
 
 def _kept(body, who):
-    if not getattr(body, "keep", False):
-        raise RuntimeError("deform.%s: the readout was made without keep=True" % who)
-    F = body.r.body_rec_count()
+    F = BodyReadout.record(body, "deform.%s" % who).body_rec_count()
     if F < 1:
         raise RuntimeError("deform.%s: no frame recorded" % who)
     return body.r, F

@@ -17,6 +17,7 @@ The record stays raw: the ROI traces of hydra_mi.roi need the raw baseline for t
 """
 import numpy as np
 
+from .body import BodyReadout
 from .videoio import AviWriter, grey_opts
 
 KINDS = ("recorded", "baseline", "excess", "dff")
@@ -35,12 +36,6 @@ def _check(who, what, half, q, floor=1, gain=1):
             raise ValueError("%s: %s %r outside %d..%d (a whole number)" % (who, name, v, lo, hi))
 
 
-def _record(who, body):
-    if not getattr(body, "keep", False):
-        raise RuntimeError("%s: the readout was made without keep=True" % who)
-    return body.r
-
-
 def blocks(frames, block):
     """[(k0, n), ...]: `frames` frames walked in blocks of `block`"""
     frames, block = int(frames), int(block)
@@ -49,13 +44,34 @@ def blocks(frames, block):
     return [(k, min(block, frames - k)) for k in range(0, frames, block)]
 
 
+def write_planes(body, path, fetch, video_bytes, block=None, video_opts=None):
+    """The grey AVI (B = G = R; an MJPEG video codes one component) of planes of the kept record, in the body frame:
+    the record is walked in blocks of `block` frames (default: video_bytes worth of planes), fetch(k0, n) gives the
+    (n, H, W) uint8 planes of a block -- or (planes, a count) -- and every plane is written -> (frames written, the
+    sum of the counts).  What detrend.write_video, events.event_video and residual.write_video share."""
+    F = body.r.body_rec_count()
+    if block is None:
+        block = max(1, video_bytes // (body.W * body.H))
+    walk = blocks(F, block)
+    total = 0
+    with AviWriter(path, body.W, body.H, **grey_opts(video_opts)) as video:
+        for k0, n in walk:
+            planes = fetch(k0, n)
+            if isinstance(planes, tuple):
+                planes, count = planes
+                total += count
+            for plane in planes:
+                video.write_grey(plane)
+        return video.frames, total
+
+
 def summary(body, what="excess", half=DEFAULT_HALF, q=DEFAULT_Q, floor=DEFAULT_FLOOR, gain=DEFAULT_GAIN):
     """The summary images of BodyReadout.summary for the planes of kind `what` of the kept record (all recorded frames):
     {"frames": F, "mean", "std", "corr": (H, W) float64, NaN outside the mesh, "max": (H, W) uint8}.  Begins the
     tracker's statistics afresh and leaves them holding these planes (find_points searches them); what
     BodyReadout.summary returned before stays as it is in the caller's hands."""
     _check("detrend.summary", what, half, q, floor, gain)
-    r = _record("detrend.summary", body)
+    r = BodyReadout.record(body, "detrend.summary")
     r.body_stats_begin()
     r.body_rec_stats_add(what, half, q, floor, gain)
     mean, std, corr, vmax = r.body_stats_images()
@@ -66,12 +82,11 @@ def find_points(body, n, radius=6, score="corr", min_score=None, what="excess", 
     """BodyReadout.find_points on the summary images of the planes of kind `what`: the n best local maxima of "corr",
     "std" or "range" within (2 radius + 1)^2 windows -> (points (P <= n, 2) float64 at the pixel centres, scores (P,))."""
     _check("detrend.find_points", what, half, q)
-    r = _record("detrend.find_points", body)
+    r = BodyReadout.record(body, "detrend.find_points")
     r.body_stats_begin()
     r.body_rec_stats_add(what, half, q, DEFAULT_FLOOR, DEFAULT_GAIN)
     idx, sc, _ = r.body_stats_peaks(score, radius, -np.inf if min_score is None else float(min_score), int(n))
-    rr, cc = np.divmod(idx.astype(np.int64), body.W)
-    return np.stack((cc + 0.5, rr + 0.5), 1).astype(np.float64).reshape(-1, 2), sc
+    return BodyReadout.pixel_points(body, idx), sc
 
 
 def write_video(body, path, half=DEFAULT_HALF, q=DEFAULT_Q, floor=DEFAULT_FLOOR, gain=DEFAULT_GAIN, block=None, video_opts=None):
@@ -79,13 +94,6 @@ def write_video(body, path, half=DEFAULT_HALF, q=DEFAULT_Q, floor=DEFAULT_FLOOR,
     video codes one component) in the body frame -> frames written.  The planes
     are fetched `block` frames at a time (default: VIDEO_BYTES worth), so host memory stays bounded for any record."""
     _check("detrend.write_video", "dff", half, q, floor, gain)
-    r = _record("detrend.write_video", body)
-    F = r.body_rec_count()
-    if block is None:
-        block = max(1, VIDEO_BYTES // (body.W * body.H))
-    walk = blocks(F, block)
-    with AviWriter(path, body.W, body.H, **grey_opts(video_opts)) as video:
-        for k0, n in walk:
-            for plane in r.body_rec_planes("dff", half, q, floor, gain, k0, n):
-                video.write_grey(plane)
-        return video.frames
+    r = BodyReadout.record(body, "detrend.write_video")
+    return write_planes(body, path, lambda k0, n: r.body_rec_planes("dff", half, q, floor, gain, k0, n), VIDEO_BYTES, block,
+                        video_opts)[0]

@@ -19,7 +19,7 @@ rule in binary64 for a handful of cell traces; the device runs the same rule on 
 import numpy as np
 
 from . import detrend
-from .videoio import AviWriter, grey_opts
+from .body import BodyReadout
 
 G_MIN, G_MAX = 0.05, 0.98          # estimate_g keeps inside these
 LAM_Z = 2.0                        # default_lam: noise of this many sigma leaves no event in a long pool
@@ -130,7 +130,7 @@ def binarise(s, s_min):
 def _record(who, body, what, half, q, floor, gain, g, lam):
     detrend._check(who, what, half, q, floor, gain)
     _check(who, g, lam)
-    return detrend._record(who, body)
+    return BodyReadout.record(body, who)
 
 
 def stats_add(body, g, lam, what="dff", half=detrend.DEFAULT_HALF, q=detrend.DEFAULT_Q, floor=detrend.DEFAULT_FLOOR,
@@ -147,8 +147,7 @@ def find_points(body, n, g, lam, radius=6, score="corr", min_score=None, **plane
     the events instead of the light -> (points (P <= n, 2) at the pixel centres, scores (P,))"""
     stats_add(body, g, lam, **planes)
     idx, sc, _ = body.r.body_stats_peaks(score, radius, -np.inf if min_score is None else float(min_score), int(n))
-    rr, cc = np.divmod(idx.astype(np.int64), body.W)
-    return np.stack((cc + 0.5, rr + 0.5), 1).astype(np.float64).reshape(-1, 2), sc
+    return BodyReadout.pixel_points(body, idx), sc
 
 
 def count_image(body, g, lam, s_min, what="dff", half=detrend.DEFAULT_HALF, q=detrend.DEFAULT_Q, floor=detrend.DEFAULT_FLOOR,
@@ -169,11 +168,5 @@ def event_video(body, path, g, lam, what="dff", half=detrend.DEFAULT_HALF, q=det
     solution of the whole record, which the device works out again for it: the event planes do not stay there between
     calls, so the blocks are larger than detrend.write_video's."""
     r = _record("events.event_video", body, what, half, q, floor, gain, g, lam)
-    F = r.body_rec_count()
-    if block is None:
-        block = max(1, VIDEO_BYTES // (body.W * body.H))
-    with AviWriter(path, body.W, body.H, **grey_opts(video_opts)) as video:
-        for k0, n in detrend.blocks(F, block):
-            for plane in r.body_rec_event_planes(what, half, q, floor, gain, g, lam, k0, n):
-                video.write_grey(plane)
-        return video.frames
+    return detrend.write_planes(body, path, lambda k0, n: r.body_rec_event_planes(what, half, q, floor, gain, g, lam, k0, n),
+                                VIDEO_BYTES, block, video_opts)[0]

@@ -29,6 +29,7 @@ for bit.
 import numpy as np
 
 from . import cellview, videoio
+from .body import BodyReadout
 
 QMAX = 32767                          # the largest |q| hm_body_rec_trace_maps takes
 LMAX = 1024                           # the most traces of one call
@@ -91,9 +92,7 @@ def maps(body, traces):
     """rho (K, H, W) float64: the correlation over the frames a BodyReadout(keep=True) has recorded of every pixel of the
     body map with every trace (K, F), the traces quantised (`quantise`).  0 where the pixel or the trace is constant, NaN
     outside the map.  The sums are made on the device, LMAX traces per call."""
-    if not getattr(body, "keep", False):
-        raise RuntimeError("network.maps: the readout was made without keep=True")
-    r = body.r
+    r = BodyReadout.record(body, "network.maps")
     F = r.body_rec_count()
     if F < 1:
         raise RuntimeError("network.maps: no frame recorded")
@@ -313,8 +312,7 @@ def map_null(body, traces, n=1000, guard=DEFAULT_LAG, seed=0, alpha=0.05, rho=No
     Per trace one call of the device (hm_body_rec_trace_null): F x (S + 1) whole numbers go in, two planes of counts and
     2 (S + 1) doubles come out.  The observed column's maximum must be the largest rho of `maps`, bit for bit.  `rho`: what
     maps(body, traces) gave, for a caller that has it already."""
-    if not getattr(body, "keep", False):
-        raise RuntimeError("network.map_null: the readout was made without keep=True")
+    BodyReadout.record(body, "network.map_null")
     rho = maps(body, traces) if rho is None else np.asarray(rho, np.float64)
     q = quantise(traces)
     K, F = q.shape

@@ -23,6 +23,7 @@ tests/pca_ref.py restates every step in loops and Python integers; the two agree
 import numpy as np
 
 from . import network
+from .body import BodyReadout
 
 GRAM_MAX = 8192                       # the most frames hm_body_rec_gram takes (REC_GRAM_MAX)
 
@@ -31,9 +32,7 @@ def gram(body, k0=0, n=None, stride=1):
     """-> (G (n, n) int64, s1 (n,) uint64) of the frames k0 + i stride, i < n, of the record a BodyReadout(keep=True) has
     kept (n None: as many as there are from k0): G[i, j] the sum over the pixels of the product of frames i and j, s1[i]
     the sum of frame i.  Made on the device."""
-    if not getattr(body, "keep", False):
-        raise RuntimeError("pca.gram: the readout was made without keep=True")
-    o = body.r.body_rec_gram(k0, n, stride)
+    o = BodyReadout.record(body, "pca.gram").body_rec_gram(k0, n, stride)
     return o["G"], o["s1"]
 
 

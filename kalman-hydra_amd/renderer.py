@@ -12,6 +12,10 @@ flowy; renderer.py:436-475, 595-628) and its force plot are composed on the devi
 as well (``view``, ``screenshot``, ``view_forces``); the on-screen canvas and its
 key bindings are not part of this build.
 
+This file holds the filter side; ``Renderer`` inherits the readout side from
+``readout.Readout`` (views, body, strain, statistics) and ``record.Record``
+(``body_rec_*``), as csrc/readout.hip and csrc/record.hip stand beside csrc/ekf.hip.
+
 Same method names and argument meaning as the reference:
 ``update_vertex_buffer``, ``render``, ``initjacobian``, ``jz``, ``jz_multi``,
 ``j``, ``j_multi``, ``error``, ``update_frame``, ``get_flow``; plus ``measure``,
@@ -27,6 +31,8 @@ import numpy as np
 
 from . import _lib
 from . import matio
+from .readout import Readout
+from .record import Record
 
 
 class ChainedPredictionFailed(RuntimeError):
@@ -34,7 +40,7 @@ class ChainedPredictionFailed(RuntimeError):
     solve had given up: nothing was updated; predict on the host and update again."""
 
 
-class Renderer:
+class Renderer(Readout, Record):
     def __init__(self, distmesh, vel, flow, nx, im1, cuda, eps_Z, eps_J, eps_M, labels=None, labels_hess=None,
                  Q=None, showtracking=False, force=None, multi=True, device=0):
         if not cuda:
@@ -61,6 +67,8 @@ class Renderer:
         self._h = h
         self.uv = uv                            # body coordinates of the readout (body.py)
         self._body_L, self._body_serial = 0, 0  # the label image of the readout in place (body_set_labels)
+        self._cells_L = 0                       # the cells of the cell view in place (view_set_cells)
+        self._body_rec_box = None               # the box of the kept record, once asked for (body_rec_patches)
         self._worker = None                     # a state-prediction worker attached to this handle (attach_worker)
         _lib.register(self, 2)
         _lib.check(L.hm_set_texture(self._h, _lib.ptr(np.ascontiguousarray(tex, np.uint8))), "hm_set_texture")
@@ -128,659 +136,6 @@ class Renderer:
         """reference renderer.py:666-672."""
         _, fx, fy, _ = self.render()
         return fx, fy
-
-    # -- views (reference renderer.py:436-475, 595-628) --------------------------------------------
-    def _view_palette(self):
-        """the mask view's face palette: hessfacecolors[:, :, 1] (renderer.py:624-628, 453), i.e. labels_hess[:, 1];
-        -1 (255, 255) for every triangle when there is no such column"""
-        lh = self.labels_hess
-        if lh is None or np.ndim(lh) != 2 or np.shape(lh)[1] < 2:
-            return None
-        return np.ascontiguousarray(np.asarray(lh)[:, 1], np.int32)
-
-    def view(self, X=None, which="overlay"):
-        """The view `which` (raw, overlay, texture, mask, flowx, flowy) at state X (default: the vertex buffer)
-        -> (H, W, 3) uint8, B G R (hm_view).  The overlay's red channel is the observed frame in place."""
-        from .videoio import VIEWS
-        x = self._X() if X is None else np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
-        if x.shape[0] != 4 * self.n:
-            raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
-        out = np.empty((self.ny, self.nx, 3), np.uint8)
-        pal = self._view_palette() if which == "mask" else None
-        _lib.check(_lib.lib().hm_view(self._h, _lib.ptr(x), VIEWS[which], _lib.ptr(pal), _lib.ptr(out)), "hm_view")
-        return out
-
-    def view_dev(self, X, which, d_out, stream=None):
-        """hm_view_dev: queue the view into device memory d_out (W*H*3 bytes, 4-byte aligned); `stream` waits for it on
-        the device."""
-        from .videoio import VIEWS
-        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
-        pal = self._view_palette() if which == "mask" else None
-        _lib.check(_lib.lib().hm_view_dev(self._h, _lib.ptr(x), VIEWS[which], _lib.ptr(pal), ctypes.c_void_p(int(d_out)),
-                                          stream), "hm_view_dev")
-
-    def view_forces(self, X, orig, pred, tv, fv, mv):
-        """The force plot of reference kalman.py:638-674 at state X (hm_view_forces): the overlay halved, then the
-        arrows orig -> pred (white), pred -> pred + 10 tv / fv / mv (blue, green, red).  Vectors: state-sized or
-        2N; the first 2N entries (the vertex coordinates) are used."""
-        n2 = 2 * self.n
-        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
-        f = [np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1)[:n2]) for a in (orig, pred, tv, fv, mv)]
-        if x.shape[0] != 4 * self.n or any(a.shape[0] != n2 for a in f):
-            raise ValueError("view_forces: states of 4N and vectors of at least 2N entries (N=%d)" % self.n)
-        out = np.empty((self.ny, self.nx, 3), np.uint8)
-        _lib.check(_lib.lib().hm_view_forces(self._h, _lib.ptr(x), *[_lib.ptr(a) for a in f], _lib.ptr(out)),
-                   "hm_view_forces")
-        return out
-
-    # -- the cell view (hm_view_set_cells, hm_view_cells*; hydra_mi.cellview) ------------------------------
-    def view_set_cells(self, labels, weights=None, colours=None):
-        """The cells of the cell view, in body coordinates: labels (n_layers, H, W) or (H, W) int32, -1: none (None
-        clears them); weights: the same shape, uint16 (None: 65535 everywhere); colours (L, 3) uint8, B G R, one per
-        label.  They stay until set again."""
-        self._cells_L = 0
-        if labels is None:
-            _lib.check(_lib.lib().hm_view_set_cells(self._h, 0, None, None, 0, None), "hm_view_set_cells")
-            return
-        lab = np.ascontiguousarray(labels, np.int32)
-        lab = lab[None] if lab.ndim == 2 else lab
-        if lab.ndim != 3 or lab.shape[1:] != (self.ny, self.nx):
-            raise ValueError("label planes of shape %r for %dx%d frames" % (lab.shape, self.nx, self.ny))
-        w = None
-        if weights is not None:
-            w = np.ascontiguousarray(weights, np.uint16).reshape(lab.shape)
-        col = np.ascontiguousarray(colours, np.uint8).reshape(-1, 3)
-        _lib.check(_lib.lib().hm_view_set_cells(self._h, int(lab.shape[0]), _lib.ptr(lab), _lib.ptr(w), int(col.shape[0]),
-                                                _lib.ptr(col)), "hm_view_set_cells")
-        self._cells_L = int(col.shape[0])
-
-    def _view_cells_args(self, X, levels, outline, wire, points, point_colours, point_radius):
-        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
-        if x.shape[0] < 2 * self.n:
-            raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
-        lv = None
-        if levels is not None:
-            lv = np.ascontiguousarray(levels, np.uint8).reshape(-1)
-            if lv.shape[0] != getattr(self, "_cells_L", 0):    # (the library reads L bytes there)
-                raise ValueError("%d levels for %d cells" % (lv.shape[0], getattr(self, "_cells_L", 0)))
-        pts = pc = None
-        P = 0
-        if points is not None and np.size(points):
-            pts = np.ascontiguousarray(points, np.float64).reshape(-1, 2)
-            P = int(pts.shape[0])
-            pc = np.ascontiguousarray(point_colours, np.uint8).reshape(-1, 3)
-            if pc.shape[0] != P:
-                raise ValueError("%d colours for %d points" % (pc.shape[0], P))
-        flags = (1 if outline else 0) | (2 if wire else 0)
-        return x, lv, flags, P, pts, pc, int(point_radius)
-
-    def view_cells(self, X, frame, levels=None, outline=True, wire=False, points=None, point_colours=None, point_radius=2):
-        """hm_view_cells: the cells set by view_set_cells and the markers `points` (P, 2) image coordinates, colours
-        (P, 3) B G R) painted onto the gray frame (H, W) uint8 at state X -> (H, W, 3) uint8, B G R.  levels: (L,) uint8,
-        the activity of every cell in this frame (None: 255)."""
-        x, lv, flags, P, pts, pc, rad = self._view_cells_args(X, levels, outline, wire, points, point_colours, point_radius)
-        f = self._plane(frame, np.uint8, "frame")
-        out = np.empty((self.ny, self.nx, 3), np.uint8)
-        _lib.check(_lib.lib().hm_view_cells(self._h, _lib.ptr(x), _lib.ptr(f), _lib.ptr(lv), flags, P, _lib.ptr(pts), _lib.ptr(pc),
-                                            rad, _lib.ptr(out)), "hm_view_cells")
-        return out
-
-    def view_cells_dev(self, X, d_frame, d_out, levels=None, outline=True, wire=False, points=None, point_colours=None,
-                       point_radius=2, stream=None):
-        """hm_view_cells_dev: the same queued on the handle's stream, frame (W*H bytes) and output (W*H*3 bytes) device
-        addresses; it does not wait, and the host arrays may be overwritten at once; `stream` waits for it on the device."""
-        x, lv, flags, P, pts, pc, rad = self._view_cells_args(X, levels, outline, wire, points, point_colours, point_radius)
-        _lib.check(_lib.lib().hm_view_cells_dev(self._h, _lib.ptr(x), ctypes.c_void_p(int(d_frame)), _lib.ptr(lv), flags, P,
-                                                _lib.ptr(pts), _lib.ptr(pc), rad, ctypes.c_void_p(int(d_out)), stream),
-                   "hm_view_cells_dev")
-
-    # -- the body-frame readout (hm_body_*; hydra_mi.body) ------------------------------------------------
-    def _plane(self, a, dtype, what):
-        """-> `a` as a contiguous (H, W) array of dtype; `what` names it in the refusal"""
-        a = np.ascontiguousarray(a, dtype)
-        if a.shape != (self.ny, self.nx):
-            raise ValueError("%s of shape %r for %dx%d frames" % (what, a.shape, self.nx, self.ny))
-        return a
-
-    def _rec_n(self, k0, n):
-        """-> the number of frames of a range k0, n of the record (n None: all from k0)"""
-        return self.body_rec_count() - int(k0) if n is None else int(n)
-
-    def body_map(self):
-        """-> (triangle per pixel (H, W) int32, -1 outside the mesh; pixels per triangle (T,) uint32) at X = uv."""
-        tri = np.empty((self.ny, self.nx), np.int32)
-        cnt = np.empty(self.tri.shape[0], np.uint32)
-        _lib.check(_lib.lib().hm_body_map(self._h, _lib.ptr(tri), _lib.ptr(cnt)), "hm_body_map")
-        return tri, cnt
-
-    def body_set_labels(self, labels, L):
-        """The label image (H, W) int32 of the label sums (-1: none; None clears) -> map pixels per label (L,) uint32.
-        The handle holds one label image: this replaces the one set before (body_labels names the one in place)."""
-        self._body_L = 0                          # (a failed call leaves no label count that could outgrow a buffer)
-        self._body_serial += 1
-        if labels is None:
-            _lib.check(_lib.lib().hm_body_set_labels(self._h, None, 0, None), "hm_body_set_labels")
-            return np.zeros(0, np.uint32)
-        lab = self._plane(labels, np.int32, "label image")
-        cnt = np.empty(int(L), np.uint32)
-        _lib.check(_lib.lib().hm_body_set_labels(self._h, _lib.ptr(lab), int(L), _lib.ptr(cnt)), "hm_body_set_labels")
-        self._body_L = int(L)
-        return cnt
-
-    @property
-    def body_labels(self):
-        """(labels L of the label image in place, 0: none; serial number of the body_set_labels call that set it)"""
-        return self._body_L, self._body_serial
-
-    def body_warp(self, X, frame):
-        """hm_body_warp: frame (H, W) uint8 pulled back through the mesh at state X -> (registered (H, W) uint8, sums per
-        triangle (T,) uint64, sums per label (L,) uint64 of the label image in place, or None when there is none)."""
-        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
-        if x.shape[0] < 2 * self.n:
-            raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
-        f = self._plane(frame, np.uint8, "frame")
-        out = np.empty((self.ny, self.nx), np.uint8)
-        ts = np.empty(self.tri.shape[0], np.uint64)
-        ls = np.empty(self._body_L, np.uint64) if self._body_L else None    # (the library writes L values there)
-        _lib.check(_lib.lib().hm_body_warp(self._h, _lib.ptr(x), _lib.ptr(f), _lib.ptr(out), _lib.ptr(ts), _lib.ptr(ls)),
-                   "hm_body_warp")
-        return out, ts, ls
-
-    def body_warp_dev(self, X, d_frame, d_out, channels, d_tri_sums, d_label_sums, stream=None):
-        """hm_body_warp_dev: device addresses (None: NULL); d_label_sums holds body_labels[0] values; `stream` waits for the
-        warp on the device."""
-        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
-        v = lambda a: None if a is None else ctypes.c_void_p(int(a))
-        _lib.check(_lib.lib().hm_body_warp_dev(self._h, _lib.ptr(x), v(d_frame), v(d_out), int(channels), v(d_tri_sums),
-                                               v(d_label_sums), stream), "hm_body_warp_dev")
-
-    def body_fence(self, stream):
-        """hm_body_fence: `stream` waits on the device for the last warp queued."""
-        _lib.check(_lib.lib().hm_body_fence(self._h, stream), "hm_body_fence")
-
-    # -- the deformation readout (hm_strain_*, hm_view_strain*; hydra_mi.strain) ------------------------------
-    STRAIN_WHICH = {"J": 0, "l1": 1, "l2": 2}
-
-    def _states(self, states):
-        """-> `states` as a contiguous (frames, 4N) float64 array (one state: one row)"""
-        x = np.ascontiguousarray(states, np.float64)
-        x = x.reshape(1, -1) if x.ndim == 1 else x.reshape(x.shape[0], -1)
-        if x.shape[1] != 4 * self.n:
-            raise ValueError("states of %d entries for a mesh of %d vertices" % (x.shape[1], self.n))
-        return x
-
-    def strain_tri(self, states):
-        """hm_strain_tri: states (frames, 4N) -> (frames, T, 7) float64: J, l1, l2, c2, s2, rc, rs per frame and triangle."""
-        x = self._states(states)
-        out = np.empty((x.shape[0], self.tri.shape[0], 7), np.float64)
-        _lib.check(_lib.lib().hm_strain_tri(self._h, int(x.shape[0]), _lib.ptr(x), _lib.ptr(out)), "hm_strain_tri")
-        return out
-
-    def strain_labels(self, states, labels, L):
-        """hm_strain_labels: the mean J, l1, l2 over the body-map pixels of every label -> ((frames, L, 3) float64, map
-        pixels per label (L,) uint32).  labels: (H, W) int32 in body coordinates, -1: none; None: the label image in
-        place (body_set_labels), whose L is passed."""
-        x = self._states(states)
-        lab = None if labels is None else self._plane(labels, np.int32, "label image")
-        out = np.empty((x.shape[0], max(int(L), 0), 3), np.float64)
-        cnt = np.empty(max(int(L), 0), np.uint32)
-        _lib.check(_lib.lib().hm_strain_labels(self._h, int(x.shape[0]), _lib.ptr(x), _lib.ptr(lab), int(L), _lib.ptr(out),
-                                               _lib.ptr(cnt)), "hm_strain_labels")
-        return out, cnt
-
-    def _view_strain_args(self, X, which, lut, wire):
-        x = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
-        if x.shape[0] < 2 * self.n:
-            raise ValueError("state of %d entries for a mesh of %d vertices" % (x.shape[0], self.n))
-        t = None
-        if lut is not None:
-            t = np.ascontiguousarray(lut, np.uint8)
-            if t.shape != (256, 3):
-                raise ValueError("a colour table of shape %r (256 x 3, B G R)" % (t.shape,))
-        return x, self.STRAIN_WHICH.get(which, which), t, 2 if wire else 0
-
-    def view_strain(self, X, frame, which="J", gain=256.0, alpha=128, lut=None, wire=False):
-        """hm_view_strain: J, l1 or l2 of the triangle under every pixel painted onto the gray frame (H, W) uint8 at state X
-        -> (H, W, 3) uint8, B G R: level = clamp(128 + rint(gain (value - 1)), 0, 255), colour lut[level] (256 x 3, B G R),
-        blended at alpha / 255."""
-        x, w, t, flags = self._view_strain_args(X, which, lut, wire)
-        f = self._plane(frame, np.uint8, "frame")
-        out = np.empty((self.ny, self.nx, 3), np.uint8)
-        _lib.check(_lib.lib().hm_view_strain(self._h, _lib.ptr(x), _lib.ptr(f), int(w), float(gain), int(alpha), _lib.ptr(t),
-                                             flags, _lib.ptr(out)), "hm_view_strain")
-        return out
-
-    def view_strain_dev(self, X, d_frame, d_out, which="J", gain=256.0, alpha=128, lut=None, wire=False, stream=None):
-        """hm_view_strain_dev: the same queued on the handle's stream, frame (W*H bytes) and output (W*H*3 bytes) device
-        addresses; it does not wait, and X and the table may be overwritten at once; `stream` waits for it on the device."""
-        x, w, t, flags = self._view_strain_args(X, which, lut, wire)
-        _lib.check(_lib.lib().hm_view_strain_dev(self._h, _lib.ptr(x), ctypes.c_void_p(int(d_frame)), int(w), float(gain),
-                                                 int(alpha), _lib.ptr(t), flags, ctypes.c_void_p(int(d_out)), stream),
-                   "hm_view_strain_dev")
-
-    # -- statistics of the registered video (hm_body_stats_*; hydra_mi.body.BodyReadout(stats=True)) -------
-    SCORES = {"corr": 0, "std": 1, "range": 2}
-
-    def body_stats_begin(self):
-        """hm_body_stats_begin: every body_warp / body_warp_dev from now on adds its registered frame; again: restart."""
-        _lib.check(_lib.lib().hm_body_stats_begin(self._h), "hm_body_stats_begin")
-
-    def body_stats_end(self):
-        """hm_body_stats_end: stop accumulating and free the sums (harmless when not begun)."""
-        _lib.check(_lib.lib().hm_body_stats_end(self._h), "hm_body_stats_end")
-
-    def body_stats_count(self):
-        """-> frames added since body_stats_begin"""
-        n = ctypes.c_int(0)
-        _lib.check(_lib.lib().hm_body_stats_count(self._h, ctypes.byref(n)), "hm_body_stats_count")
-        return n.value
-
-    def body_stats_fetch(self):
-        """-> (s1 (H, W) uint32, s2 (H, W) uint32, cross (4, H, W) uint32: right, down-right, down, down-left,
-        vmax (H, W) uint8) of the frames added so far; zeros outside the map."""
-        H, W = self.ny, self.nx
-        s1, s2 = np.empty((H, W), np.uint32), np.empty((H, W), np.uint32)
-        cross, vmax = np.empty((4, H, W), np.uint32), np.empty((H, W), np.uint8)
-        _lib.check(_lib.lib().hm_body_stats_fetch(self._h, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(cross), _lib.ptr(vmax)),
-                   "hm_body_stats_fetch")
-        return s1, s2, cross, vmax
-
-    def body_stats_images(self):
-        """-> (mean, std, corr (H, W) float64, NaN outside the map; max (H, W) uint8) of the frames added so far."""
-        H, W = self.ny, self.nx
-        mean, std, corr = (np.empty((H, W), np.float64) for _ in range(3))
-        vmax = np.empty((H, W), np.uint8)
-        _lib.check(_lib.lib().hm_body_stats_images(self._h, _lib.ptr(mean), _lib.ptr(std), _lib.ptr(corr), _lib.ptr(vmax)),
-                   "hm_body_stats_images")
-        return mean, std, corr, vmax
-
-    def body_stats_peaks(self, score="corr", radius=6, min_score=-np.inf, cap=None):
-        """hm_body_stats_peaks: the local maxima of a score image ("corr", "std", "range" = max - mean, or 0, 1, 2)
-        within (2 radius + 1)^2 windows -> (raster indices (P,) int32, scores (P,) float64, number found); score
-        descending, the first `cap` of them (None: all)."""
-        which = self.SCORES[score] if isinstance(score, str) else int(score)
-        cap = self.nx * self.ny if cap is None else int(cap)
-        idx, sc = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.float64)
-        n = ctypes.c_int(0)
-        _lib.check(_lib.lib().hm_body_stats_peaks(self._h, which, int(radius), float(min_score), cap, _lib.ptr(idx),
-                                                  _lib.ptr(sc), ctypes.byref(n)), "hm_body_stats_peaks")
-        k = min(n.value, cap)
-        return idx[:k].copy(), sc[:k].copy(), n.value
-
-    # -- the registered video kept on the device (hm_body_rec_*; hydra_mi.body.BodyReadout(keep=True), hydra_mi.roi) --
-    def body_rec_begin(self, max_bytes=8 << 30):
-        """hm_body_rec_begin: every body_warp / body_warp_dev from now on appends its registered frame to a record in device
-        memory of at most max_bytes; again: start over."""
-        _lib.check(_lib.lib().hm_body_rec_begin(self._h, int(max_bytes)), "hm_body_rec_begin")
-
-    def body_rec_end(self):
-        """hm_body_rec_end: stop recording and free the record (harmless when not begun)."""
-        _lib.check(_lib.lib().hm_body_rec_end(self._h), "hm_body_rec_end")
-
-    def body_rec_count(self):
-        """-> frames recorded since body_rec_begin"""
-        n = ctypes.c_int(0)
-        _lib.check(_lib.lib().hm_body_rec_count(self._h, ctypes.byref(n)), "hm_body_rec_count")
-        return n.value
-
-    def body_rec_fetch(self, k0=0, n=None):
-        """-> recorded frames k0 .. k0 + n - 1 (default: all from k0) as (n, H, W) uint8"""
-        n = self._rec_n(k0, n)
-        out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
-        _lib.check(_lib.lib().hm_body_rec_fetch(self._h, int(k0), n, _lib.ptr(out)), "hm_body_rec_fetch")
-        return out
-
-    def body_rec_label_sums(self, labels, L):
-        """hm_body_rec_label_sums: a label image (H, W) int32 given now -> (F, L) uint64, the sums per label of every
-        recorded frame."""
-        lab = self._plane(labels, np.int32, "label image")
-        out = np.empty((self.body_rec_count(), int(L)), np.uint64)
-        _lib.check(_lib.lib().hm_body_rec_label_sums(self._h, _lib.ptr(lab), int(L), _lib.ptr(out)), "hm_body_rec_label_sums")
-        return out
-
-    def body_rec_seed_sums(self, seeds, r_disc, r_in, r_out, R):
-        """hm_body_rec_seed_sums: seeds (P, 2) integer (column, row) map pixels -> dict: n_T, n_G (P,) uint32; T, G (F, P)
-        uint64 disc and ring sums; U (F, P) int64 = n_G T - n_T G; w1, w2 (P, 2R+1, 2R+1) uint64 and c (same, int64):
-        sums of v, v^2 and v U per window pixel; u1, u2 (P,) int64: sums of U and U^2."""
-        sd = np.ascontiguousarray(seeds, np.int32).reshape(-1, 2)
-        P, F, S = sd.shape[0], self.body_rec_count(), 2 * int(R) + 1
-        o = dict(n_T=np.empty(P, np.uint32), n_G=np.empty(P, np.uint32), T=np.empty((F, P), np.uint64),
-                 G=np.empty((F, P), np.uint64), U=np.empty((F, P), np.int64), w1=np.empty((P, S, S), np.uint64),
-                 w2=np.empty((P, S, S), np.uint64), c=np.empty((P, S, S), np.int64), u1=np.empty(P, np.int64),
-                 u2=np.empty(P, np.int64))
-        _lib.check(_lib.lib().hm_body_rec_seed_sums(self._h, P, _lib.ptr(sd), float(r_disc), float(r_in), float(r_out), int(R),
-                                                    *[_lib.ptr(o[k]) for k in ("n_T", "n_G", "T", "G", "U", "w1", "w2", "c",
-                                                                               "u1", "u2")]), "hm_body_rec_seed_sums")
-        return o
-
-    def body_rec_weighted_sums(self, seeds, weights, R):
-        """hm_body_rec_weighted_sums: weights (P, 2R+1, 2R+1) uint16 round the seeds -> (F, P) uint64 sums of weight x
-        value of every recorded frame."""
-        sd = np.ascontiguousarray(seeds, np.int32).reshape(-1, 2)
-        S = 2 * int(R) + 1
-        w = np.ascontiguousarray(weights, np.uint16)
-        if w.shape != (sd.shape[0], S, S):
-            raise ValueError("weights of shape %r for %d seeds and windows of %d x %d" % (w.shape, sd.shape[0], S, S))
-        out = np.empty((self.body_rec_count(), sd.shape[0]), np.uint64)
-        _lib.check(_lib.lib().hm_body_rec_weighted_sums(self._h, sd.shape[0], _lib.ptr(sd), int(R), _lib.ptr(w), _lib.ptr(out)),
-                   "hm_body_rec_weighted_sums")
-        return out
-
-    def body_rec_trace_products(self, seeds, q, R):
-        """hm_body_rec_trace_products: one int32 trace per seed, q (F, P) -> (P, 2R+1, 2R+1) int64, the sum over the
-        recorded frames of every window pixel times the seed's trace (0 off the frame and outside the map)."""
-        sd = np.ascontiguousarray(seeds, np.int32).reshape(-1, 2)
-        S, F = 2 * int(R) + 1, self.body_rec_count()
-        q = np.asarray(q)
-        if q.dtype != np.int32 or q.ndim != 2 or q.shape[1] != sd.shape[0] or (F and q.shape[0] != F):   # (F 0: the call says why)
-            raise ValueError("traces %s of shape %r for %d frames and %d seeds (need int32)" % (q.dtype, q.shape, F, sd.shape[0]))
-        q = np.ascontiguousarray(q)
-        out = np.empty((sd.shape[0], S, S), np.int64)
-        _lib.check(_lib.lib().hm_body_rec_trace_products(self._h, sd.shape[0], _lib.ptr(sd), int(R), _lib.ptr(q), _lib.ptr(out)),
-                   "hm_body_rec_trace_products")
-        return out
-
-    def body_rec_trace_maps(self, q, want=("c", "w1", "w2")):
-        """hm_body_rec_trace_maps: L int32 traces, q (F, L) with |q| <= 32767 -> dict of those in `want`: c (L, H, W) int64,
-        the sum over the recorded frames of every pixel times every trace; w1, w2 (H, W) uint64, the sums of every pixel
-        and of its square (0 outside the map)."""
-        F = self.body_rec_count()
-        q = np.asarray(q)
-        if q.dtype != np.int32 or q.ndim != 2 or (F and q.shape[0] != F):          # (F 0: the call says why)
-            raise ValueError("traces %s of shape %r for %d frames (need int32, frames x traces)" % (q.dtype, q.shape, F))
-        q = np.ascontiguousarray(q)
-        L, H, W = q.shape[1], self.ny, self.nx
-        o = {}
-        if "c" in want:
-            o["c"] = np.empty((min(max(L, 0), 1024), H, W), np.int64)               # (L out of range: the call says so)
-        for key in ("w1", "w2"):
-            if key in want:
-                o[key] = np.empty((H, W), np.uint64)
-        _lib.check(_lib.lib().hm_body_rec_trace_maps(self._h, L, _lib.ptr(q), *[_lib.ptr(o[k]) if k in o else None
-                                                                                 for k in ("c", "w1", "w2")]),
-                   "hm_body_rec_trace_maps")
-        return o
-
-    def body_rec_trace_null(self, q, vb, want=("tmax", "tmin", "ge", "le")):
-        """hm_body_rec_trace_null: q (F, L) int32 with |q| <= 32767, column 0 the observed trace and the others its
-        surrogates, vb (L,) float64 = F u2 - u1^2 of every column -> dict of those in `want`: tmax, tmin (L,) float64, the
-        largest and smallest correlation of every column over the map; ge, le (H, W) uint32, per pixel the surrogates
-        whose numerator is >= and <= the observed one (0 outside the map)."""
-        F = self.body_rec_count()
-        q = np.asarray(q)
-        if q.dtype != np.int32 or q.ndim != 2 or (F and q.shape[0] != F):          # (F 0: the call says why)
-            raise ValueError("traces %s of shape %r for %d frames (need int32, frames x traces)" % (q.dtype, q.shape, F))
-        q = np.ascontiguousarray(q)
-        L, H, W = q.shape[1], self.ny, self.nx
-        vb = np.ascontiguousarray(vb, np.float64)
-        if vb.shape != (L,):
-            raise ValueError("vb of shape %r for %d traces" % (vb.shape, L))
-        o = {}
-        for key in ("tmax", "tmin"):
-            if key in want:
-                o[key] = np.empty(max(L, 0), np.float64)
-        for key in ("ge", "le"):
-            if key in want:
-                o[key] = np.empty((H, W), np.uint32)
-        _lib.check(_lib.lib().hm_body_rec_trace_null(self._h, L, _lib.ptr(q), _lib.ptr(vb),
-                                                     *[_lib.ptr(o[k]) if k in o else None for k in ("tmax", "tmin", "ge", "le")]),
-                   "hm_body_rec_trace_null")
-        return o
-
-    def body_rec_gram(self, k0=0, n=None, stride=1, want=("G", "s1")):
-        """hm_body_rec_gram: the frames k0 + i stride, i < n (default: as many as the record holds from k0) -> dict of those
-        in `want`: G (n, n) int64, the sum over the pixels of the product of every two of the frames; s1 (n,) uint64, the
-        sum of every frame."""
-        k0, stride = int(k0), int(stride)
-        if n is None:
-            F = self.body_rec_count()
-            n = (F - 1 - k0) // stride + 1 if stride >= 1 and 0 <= k0 < F else 1          # (out of range: the call says why)
-        n = int(n)
-        m = min(max(n, 1), 8192)                                                       # (n out of range: the call says so)
-        o = {}
-        if "G" in want:
-            o["G"] = np.empty((m, m), np.int64)
-        if "s1" in want:
-            o["s1"] = np.empty(m, np.uint64)
-        _lib.check(_lib.lib().hm_body_rec_gram(self._h, k0, n, stride, *[_lib.ptr(o[k]) if k in o else None for k in ("G", "s1")]),
-                   "hm_body_rec_gram")
-        return o
-
-    # -- residual motion of the record (hm_body_rec_match / _frame_sums / _shift / _warp / _field_sums; hydra_mi.stabilize) --
-    def body_rec_patches(self, B):
-        """-> (patches per row, patch rows) of the grid of B x B patches over the record's box (the bounding box of the
-        body map)"""
-        box = getattr(self, "_body_rec_box", None)
-        if box is None:                                          # (the map is the mesh at X = uv: fixed for the handle)
-            m = self.body_map()[0] >= 0
-            rows, cols = np.flatnonzero(m.any(1)), np.flatnonzero(m.any(0))
-            box = (int(cols[-1] - cols[0]) + 1, int(rows[-1] - rows[0]) + 1) if m.any() else (1, 1)
-            self._body_rec_box = box
-        B = int(B)
-        return (box[0] + B - 1) // B, (box[1] + B - 1) // B
-
-    def body_rec_match(self, template, B, S, k0=0, n=None, want=("A", "V1", "V2")):
-        """hm_body_rec_match: template (H, W) uint8 in body coordinates -> dict: n_core (patches,) uint32 and, of A, V1,
-        V2, those in `want` as (n, patches, (2S+1)^2) uint32: the sums over every patch's core of v(p + d) t(p),
-        v(p + d) and v(p + d)^2 for the frames k0 .. k0 + n - 1 (default: all from k0)."""
-        t = self._plane(template, np.uint8, "template")
-        B, S = int(B), int(S)
-        if not (4 <= B <= 64 and 0 <= S <= 8):                   # (the call says so with its numbers; no grid to size for)
-            _lib.check(_lib.lib().hm_body_rec_match(self._h, int(k0), 0, B, S, _lib.ptr(t), None, None, None, None),
-                       "hm_body_rec_match")
-        n = self._rec_n(k0, n)
-        npx, npy = self.body_rec_patches(B)
-        o = dict(n_core=np.empty(npx * npy, np.uint32))
-        for key in want:
-            o[key] = np.empty((max(n, 0), npx * npy, (2 * S + 1) ** 2), np.uint32)
-        _lib.check(_lib.lib().hm_body_rec_match(self._h, int(k0), n, B, S, _lib.ptr(t), _lib.ptr(o["n_core"]),
-                                                *[_lib.ptr(o.get(key)) for key in ("A", "V1", "V2")]), "hm_body_rec_match")
-        return o
-
-    def _body_shifts(self, shifts, B, who):
-        sh = np.asarray(shifts)
-        if sh.dtype != np.int8 or sh.ndim != 3 or sh.shape[2] != 2:
-            raise ValueError("%s: shifts %s of shape %r (need int8, (frames, patches, 2))" % (who, sh.dtype, sh.shape))
-        if 4 <= int(B) <= 64:
-            npx, npy = self.body_rec_patches(B)
-            if sh.shape[1] != npx * npy:
-                raise ValueError("%s: shifts for %d patches, the grid of %d px patches has %d" % (who, sh.shape[1], int(B),
-                                                                                                  npx * npy))
-        return np.ascontiguousarray(sh)
-
-    def body_rec_frame_sums(self, shifts=None, B=16, k0=0, n=None):
-        """hm_body_rec_frame_sums: -> (H, W) uint32, the sum over the frames k0 .. k0 + n - 1 of every map pixel taken at
-        its patch's shift of that frame; shifts (n, patches, 2) int8 (dx, dy), None: no shift."""
-        n = self._rec_n(k0, n)
-        sh = None
-        if shifts is not None:
-            sh = self._body_shifts(shifts, B, "body_rec_frame_sums")
-            if sh.shape[0] != n:
-                raise ValueError("body_rec_frame_sums: shifts of %d frames for %d" % (sh.shape[0], n))
-        out = np.empty((self.ny, self.nx), np.uint32)
-        _lib.check(_lib.lib().hm_body_rec_frame_sums(self._h, int(k0), n, int(B), _lib.ptr(sh), _lib.ptr(out)),
-                   "hm_body_rec_frame_sums")
-        return out
-
-    def body_rec_shift(self, shifts, B):
-        """hm_body_rec_shift: rewrite the record in place, every map pixel of every frame taken at its patch's shift;
-        shifts (F, patches, 2) int8 (dx, dy) for all recorded frames.  Not reversible."""
-        sh = self._body_shifts(shifts, B, "body_rec_shift")
-        F = self.body_rec_count()
-        if F and sh.shape[0] != F:                               # (F 0: the call says why)
-            raise ValueError("body_rec_shift: shifts of %d frames for a record of %d" % (sh.shape[0], F))
-        _lib.check(_lib.lib().hm_body_rec_shift(self._h, int(B), _lib.ptr(sh)), "hm_body_rec_shift")
-
-    def _body_field(self, q, valid, B, who):
-        q, valid = np.asarray(q), np.asarray(valid)
-        if q.dtype != np.int16 or q.ndim != 3 or q.shape[2] != 2:
-            raise ValueError("%s: q %s of shape %r (need int16, (frames, patches, 2))" % (who, q.dtype, q.shape))
-        if valid.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)) or valid.shape != q.shape[:2]:
-            raise ValueError("%s: valid %s of shape %r for q of shape %r (need uint8 or bool, (frames, patches))" % (
-                who, valid.dtype, valid.shape, q.shape))
-        if 4 <= int(B) <= 64:
-            npx, npy = self.body_rec_patches(B)
-            if q.shape[1] != npx * npy:
-                raise ValueError("%s: q for %d patches, the grid of %d px patches has %d" % (who, q.shape[1], int(B), npx * npy))
-        return np.ascontiguousarray(q), np.ascontiguousarray(valid, np.uint8)
-
-    def body_rec_field_sums(self, q, valid, B, k0=0, n=None):
-        """hm_body_rec_field_sums: -> (H, W) uint32, the sum over the frames k0 .. k0 + n - 1 of every map pixel sampled at
-        the smooth field of that frame; q (n, patches, 2) int16 (dx, dy) in 1/16 px, valid (n, patches)."""
-        n = self._rec_n(k0, n)
-        q, valid = self._body_field(q, valid, B, "body_rec_field_sums")
-        if q.shape[0] != n:
-            raise ValueError("body_rec_field_sums: q of %d frames for %d" % (q.shape[0], n))
-        out = np.empty((self.ny, self.nx), np.uint32)
-        _lib.check(_lib.lib().hm_body_rec_field_sums(self._h, int(k0), n, int(B), _lib.ptr(q), _lib.ptr(valid), _lib.ptr(out)),
-                   "hm_body_rec_field_sums")
-        return out
-
-    def body_rec_warp(self, q, valid, B):
-        """hm_body_rec_warp: rewrite the record in place, every map pixel of every frame sampled bilinearly at the smooth
-        field between the patches' shifts; q (F, patches, 2) int16 (dx, dy) in 1/16 px, valid (F, patches), for all
-        recorded frames.  Not reversible."""
-        q, valid = self._body_field(q, valid, B, "body_rec_warp")
-        F = self.body_rec_count()
-        if F and q.shape[0] != F:                                # (F 0: the call says why)
-            raise ValueError("body_rec_warp: q of %d frames for a record of %d" % (q.shape[0], F))
-        _lib.check(_lib.lib().hm_body_rec_warp(self._h, int(B), _lib.ptr(q), _lib.ptr(valid)), "hm_body_rec_warp")
-
-    # -- the record against the deformation of its own tissue (hm_body_rec_tri_maps / _tri_gain; hydra_mi.deform) --
-    def _tri_table(self, a, dtype, who):
-        """-> `a` as a contiguous (F, T) array of exactly `dtype`, one row per recorded frame and a column per triangle"""
-        a = np.asarray(a)
-        F, T = self.body_rec_count(), self.tri.shape[0]
-        if a.dtype != dtype or a.ndim != 2 or a.shape[1] != T or (F and a.shape[0] != F):     # (F 0: the call says why)
-            raise ValueError("%s: %s of shape %r for %d frames and %d triangles (need %s, frames x triangles)" % (
-                who, a.dtype, a.shape, F, T, np.dtype(dtype).name))
-        return np.ascontiguousarray(a)
-
-    def body_rec_tri_maps(self, q, want=("c", "w1", "w2")):
-        """hm_body_rec_tri_maps: one int32 trace per triangle, q (F, T) with |q| <= 32767 -> (c, w1, w2): c (H, W) int64, the
-        sum over the recorded frames of every pixel times the trace of its own triangle; w1, w2 (H, W) uint64, the sums of
-        every pixel and of its square (0 outside the map); None for one that is not in `want`."""
-        q = self._tri_table(q, np.int32, "body_rec_tri_maps")
-        H, W = self.ny, self.nx
-        o = {"c": np.empty((H, W), np.int64) if "c" in want else None}
-        for key in ("w1", "w2"):
-            o[key] = np.empty((H, W), np.uint64) if key in want else None
-        _lib.check(_lib.lib().hm_body_rec_tri_maps(self._h, q.shape[1], _lib.ptr(q), _lib.ptr(o["c"]), _lib.ptr(o["w1"]),
-                                                   _lib.ptr(o["w2"])), "hm_body_rec_tri_maps")
-        return o["c"], o["w1"], o["w2"]
-
-    def body_rec_tri_gain(self, m):
-        """hm_body_rec_tri_gain: rewrite the record in place, every map pixel of every frame times the gain of its own
-        triangle in that frame, min(255, (v m + 2048) >> 12); m (F, T) uint16, 4096 the identity -> the number of values
-        that were clipped at 255.  Not reversible."""
-        m = self._tri_table(m, np.uint16, "body_rec_tri_gain")
-        n = ctypes.c_uint64(0)
-        _lib.check(_lib.lib().hm_body_rec_tri_gain(self._h, m.shape[1], _lib.ptr(m), ctypes.byref(n)), "hm_body_rec_tri_gain")
-        return int(n.value)
-
-    # -- the running baseline per pixel of the record (hm_body_rec_planes / _stats_add; hydra_mi.detrend) -----
-    PLANES = {"recorded": 0, "baseline": 1, "excess": 2, "dff": 3}
-
-    def body_rec_planes(self, what, half, q, floor=1, gain=1, k0=0, n=None):
-        """hm_body_rec_planes: -> (n, H, W) uint8, the planes of kind `what` ("recorded", "baseline", "excess", "dff", or
-        0..3) of the recorded frames k0 .. k0 + n - 1 (default: all from k0): the baseline is the value at rank
-        q (window - 1) // 100 of the frames k - half .. k + half of the whole record, the excess what lies above it, dff
-        min(255, gain excess // max(baseline, floor))."""
-        what = self.PLANES[what] if isinstance(what, str) else int(what)
-        n = self._rec_n(k0, n)
-        out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
-        _lib.check(_lib.lib().hm_body_rec_planes(self._h, int(k0), n, what, int(half), int(q), int(floor), int(gain),
-                                                 _lib.ptr(out)), "hm_body_rec_planes")
-        return out
-
-    def body_rec_stats_add(self, what, half, q, floor=1, gain=1):
-        """hm_body_rec_stats_add: add every recorded frame's plane of kind `what` (as body_rec_planes) to the statistics
-        begun with body_stats_begin, as if each had just been warped."""
-        what = self.PLANES[what] if isinstance(what, str) else int(what)
-        _lib.check(_lib.lib().hm_body_rec_stats_add(self._h, what, int(half), int(q), int(floor), int(gain)),
-                   "hm_body_rec_stats_add")
-
-    # -- events per pixel of the record: AR(1) deconvolution of the planes (hm_body_rec_event_*; hydra_mi.events) -----
-    def body_rec_event_planes(self, what, half, q, floor=1, gain=1, g=0.9, lam=0.0, k0=0, n=None):
-        """hm_body_rec_event_planes: -> (n, H, W) uint8, the event bytes min(255, floor(s + 0.5)) of the recorded frames
-        k0 .. k0 + n - 1 (default: all from k0): s the AR(1) deconvolution (decay g per frame, penalty lam) of every
-        pixel's planes of kind `what` (as body_rec_planes) over the whole record."""
-        what = self.PLANES[what] if isinstance(what, str) else int(what)
-        n = self._rec_n(k0, n)
-        out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
-        _lib.check(_lib.lib().hm_body_rec_event_planes(self._h, int(k0), n, what, int(half), int(q), int(floor), int(gain),
-                                                       float(g), float(lam), _lib.ptr(out)), "hm_body_rec_event_planes")
-        return out
-
-    def body_rec_event_stats_add(self, what, half, q, floor=1, gain=1, g=0.9, lam=0.0):
-        """hm_body_rec_event_stats_add: add every recorded frame's event plane (as body_rec_event_planes) to the statistics
-        begun with body_stats_begin, as if each had just been warped."""
-        what = self.PLANES[what] if isinstance(what, str) else int(what)
-        _lib.check(_lib.lib().hm_body_rec_event_stats_add(self._h, what, int(half), int(q), int(floor), int(gain), float(g),
-                                                          float(lam)), "hm_body_rec_event_stats_add")
-
-    def body_rec_event_sums(self, what, half, q, floor=1, gain=1, g=0.9, lam=0.0, s_min=1.0):
-        """hm_body_rec_event_sums: -> (count (H, W) uint32, sum (H, W) float64): per pixel the number of frames with
-        s >= s_min and the sum of s over the record (s as in body_rec_event_planes, before rounding)."""
-        what = self.PLANES[what] if isinstance(what, str) else int(what)
-        count, total = np.empty((self.ny, self.nx), np.uint32), np.empty((self.ny, self.nx), np.float64)
-        _lib.check(_lib.lib().hm_body_rec_event_sums(self._h, what, int(half), int(q), int(floor), int(gain), float(g), float(lam),
-                                                     float(s_min), _lib.ptr(count), _lib.ptr(total)), "hm_body_rec_event_sums")
-        return count, total
-
-    # -- the residual of the record under a model of the cells (hm_body_rec_residual_*; hydra_mi.residual) -----
-    def _residual_args(self, who, labels, weights, traces, blank):
-        lab = np.ascontiguousarray(labels, np.int32)
-        lab = lab[None] if lab.ndim == 2 else lab
-        if lab.ndim != 3 or lab.shape[1:] != (self.ny, self.nx):
-            raise ValueError("%s: label planes of shape %r for %dx%d frames" % (who, lab.shape, self.nx, self.ny))
-        w = None if weights is None else np.ascontiguousarray(weights, np.uint16)
-        if w is not None and w.size != lab.size:
-            raise ValueError("%s: weights of shape %r for labels of shape %r" % (who, w.shape, lab.shape))
-        tr = np.ascontiguousarray(traces, np.int32)
-        F = self.body_rec_count()
-        if tr.ndim != 2 or (F and tr.shape[0] != F):             # (F 0: the call says why)
-            raise ValueError("%s: traces of shape %r for a record of %d frames" % (who, tr.shape, F))
-        bl = None if blank is None else self._plane(blank, np.uint8, "%s: a blank plane" % who)
-        return lab, w, tr, bl
-
-    def body_rec_residual_planes(self, labels, weights, traces, blank=None, offset=64, k0=0, n=None):
-        """hm_body_rec_residual_planes: -> ((n, H, W) uint8, clipped): the recorded frames k0 .. k0 + n - 1 (default: all
-        from k0) minus the cells' light, min(255, max(0, offset + v - ((sum_j weights[j] traces[k, labels[j]] + 2^23) >>
-        24))), 0 off the map and where blank is set.  labels (n_layers, H, W) or (H, W) int32 (-1: none), weights the
-        same shape uint16 (None: 65535), as view_set_cells takes them; traces (F, L) int32 for all recorded frames."""
-        lab, w, tr, bl = self._residual_args("body_rec_residual_planes", labels, weights, traces, blank)
-        n = self._rec_n(k0, n)
-        out = np.empty((max(n, 0), self.ny, self.nx), np.uint8)
-        clipped = ctypes.c_uint64(0)
-        _lib.check(_lib.lib().hm_body_rec_residual_planes(self._h, int(k0), n, int(lab.shape[0]), _lib.ptr(lab), _lib.ptr(w),
-                                                          int(tr.shape[1]), _lib.ptr(tr), _lib.ptr(bl), int(offset),
-                                                          _lib.ptr(out), ctypes.byref(clipped)), "hm_body_rec_residual_planes")
-        return out, clipped.value
-
-    def body_rec_residual_stats_add(self, labels, weights, traces, blank=None, offset=64):
-        """hm_body_rec_residual_stats_add: add every recorded frame's residual plane (as body_rec_residual_planes) to the
-        statistics begun with body_stats_begin, as if each had just been warped -> clipped."""
-        lab, w, tr, bl = self._residual_args("body_rec_residual_stats_add", labels, weights, traces, blank)
-        clipped = ctypes.c_uint64(0)
-        _lib.check(_lib.lib().hm_body_rec_residual_stats_add(self._h, int(lab.shape[0]), _lib.ptr(lab), _lib.ptr(w),
-                                                             int(tr.shape[1]), _lib.ptr(tr), _lib.ptr(bl), int(offset),
-                                                             ctypes.byref(clipped)), "hm_body_rec_residual_stats_add")
-        return clipped.value
-
-    def screenshot(self, saveall=True, basename="screenshot", X=None):
-        """reference renderer.py:436-475: writes <basename>_<view>.png for flowx, flowy, raw, overlay, texture and mask
-        at state X (default: the vertex buffer) and returns the overlay.  Unlike the reference the names carry no
-        time stamp: a second call with the same basename overwrites.  saveall=False writes the overlay alone."""
-        from .videoio import write_png
-        views = ("flowx", "flowy", "raw", "overlay", "texture", "mask") if saveall else ("overlay",)
-        overlay = None
-        for v in views:
-            img = self.view(X, v)
-            write_png("%s_%s.png" % (basename, v), img)
-            if v == "overlay":
-                overlay = img
-        return overlay
 
     # -- observation ------------------------------------------------------------------------
     def update_frame(self, y_im, y_flow, y_m):

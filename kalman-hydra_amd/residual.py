@@ -24,20 +24,14 @@ import math
 
 import numpy as np
 
-from . import cellview, demix, roi
-from .videoio import AviWriter, grey_opts
+from . import cellview, demix, detrend, roi
+from .body import BodyReadout
 
 TBITS = 24                 # traces are scaled by 2^24: a weight of 65535 and a trace of rint(l 2^24 / 65535) take l levels off
 DEFAULT_BLANK = 2          # px round every known seed
 DEFAULT_OFFSET = 64        # grey levels added so that what the model overshoots by stays visible
 VIDEO_BYTES = 64 << 20     # host memory a block of write_video's planes takes at most
 _ROI_ARGS = ("r_disc", "r_in", "r_out", "R", "thr")
-
-
-def _record(who, body):
-    if not getattr(body, "keep", False):
-        raise RuntimeError("%s: the readout was made without keep=True" % who)
-    return body.r
 
 
 def _points_of(who, e, points):
@@ -111,7 +105,7 @@ def summary(body, e, blank=DEFAULT_BLANK, offset=DEFAULT_OFFSET, points=None):
     its seeds, None: e["points"]), a disc of `blank` px round every seed blanked (None: none) -> that dict plus "clipped"
     (values that left 0..255 before the clamp) and "dropped" ((pixel, cell) entries beyond the four layers).  Begins the
     tracker's statistics afresh and leaves them holding the residual video."""
-    r = _record("residual.summary", body)
+    r = BodyReadout.record(body, "residual.summary")
     labels, weights, traces, bl, dropped = _args("residual.summary", body, e, blank, offset, points)
     r.body_stats_begin()
     clipped = r.body_rec_residual_stats_add(labels, weights, traces, bl, int(offset))
@@ -149,7 +143,7 @@ def find_more(body, points, min_score, rounds=3, radius=6, score="corr", blank=D
     given), new_scores (the scores of the points added, in their order), scores [per round: the scores of its candidates, descending], accepted [per round: how many were taken],
     refused [(round, point (2,), score, reason)], clipped [per round], dropped, ended ("none accepted" or "rounds"),
     e: the last demix.extract dict, of all the points (with e["points"]), so the caller does not demix again."""
-    r = _record("residual.find_more", body)
+    r = BodyReadout.record(body, "residual.find_more")
     _check("residual.find_more", blank, offset)
     rounds = int(rounds)
     if rounds < 1:
@@ -176,7 +170,7 @@ def find_more(body, points, min_score, rounds=3, radius=6, score="corr", blank=D
         for i, v in zip(idx.tolist(), sc.tolist()):
             if max_new is not None and pts.shape[0] - n_given >= int(max_new):
                 break
-            cand = np.array([i % body.W + 0.5, i // body.W + 0.5])
+            cand = BodyReadout.pixel_points(body, [i])[0]
             if (roi.seeds_of(pts) == roi.seeds_of(cand)[0]).all(1).any():
                 out["refused"].append((rnd, cand, v, "seeded"))
                 continue
@@ -203,19 +197,7 @@ def write_video(body, path, e, blank=None, offset=DEFAULT_OFFSET, points=None, b
     MJPEG video codes one component) in the body frame -> (frames written,
     clipped).  The planes are fetched `block` frames at a time (default: VIDEO_BYTES worth), so host memory stays bounded
     for any record.  blank None: the video shows the misfit round the seeds too."""
-    r = _record("residual.write_video", body)
+    r = BodyReadout.record(body, "residual.write_video")
     labels, weights, traces, bl, _ = _args("residual.write_video", body, e, blank, offset, points)
-    F = r.body_rec_count()
-    if block is None:
-        block = max(1, VIDEO_BYTES // (body.W * body.H))
-    block = int(block)
-    if block < 1:
-        raise ValueError("blocks of %d frames" % block)
-    clipped = 0
-    with AviWriter(path, body.W, body.H, **grey_opts(video_opts)) as video:
-        for k0 in range(0, F, block):
-            planes, c = r.body_rec_residual_planes(labels, weights, traces, bl, int(offset), k0, min(block, F - k0))
-            clipped += c
-            for plane in planes:
-                video.write_grey(plane)
-        return video.frames, clipped
+    return detrend.write_planes(body, path, lambda k0, n: r.body_rec_residual_planes(labels, weights, traces, bl, int(offset), k0, n),
+                                VIDEO_BYTES, block, video_opts)

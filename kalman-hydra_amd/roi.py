@@ -20,6 +20,8 @@ tests/roi_ref.py restates every step in NumPy and Python integers; the two agree
 """
 import numpy as np
 
+from .body import BodyReadout
+
 #: halfway between the lowest footprint value within 2 px of a planted centre (0.542) and the highest on ring pixels
 #: (0.401) of the planted video with neuropil (tests/roi_ref.py, six seeds; tests/test_roi_cpu.py measures both)
 DEFAULT_THR = 0.47
@@ -167,9 +169,7 @@ def extract(body, points, r_disc=3.0, r_in=6.0, r_out=8.5, R=8, thr=None, alpha=
     F0 is the running q-th percentile of F_c over 2 half + 1 frames; F0_raw is the same percentile of F_roi, not of F_c: the
     corrected baseline is near zero when alpha takes the whole background away, and dividing by it would blow the ratio
     up.  thr None: DEFAULT_THR."""
-    if not getattr(body, "keep", False):
-        raise RuntimeError("roi.extract: the readout was made without keep=True")
-    r = body.r
+    r = BodyReadout.record(body, "roi.extract")
     F = r.body_rec_count()
     if F < 1:
         raise RuntimeError("roi.extract: no frame recorded")

@@ -27,6 +27,8 @@ rigidly against each other with hard seams the patches are (DESIGN.md section 13
 """
 import numpy as np
 
+from .body import BodyReadout
+
 #: halfway between the lowest best score of a correctly recovered patch (0.844) and the highest best score of a patch
 #: matched against the template of another video, with nothing to lock onto (0.288), on the planted video with jitter
 #: (tests/stab_ref.py, six seeds; tests/test_stab_cpu.py measures both)
@@ -157,9 +159,7 @@ def estimate(body, B=16, S=3, k_ref=0, passes=1, min_score=None, n_min=None, mod
     previous pass's field (body_rec_field_sums)."""
     if mode not in MODES:
         raise ValueError("stabilize.estimate: mode %r (one of %s)" % (mode, ", ".join(MODES)))
-    if not getattr(body, "keep", False):
-        raise RuntimeError("stabilize.estimate: the readout was made without keep=True")
-    r = body.r
+    r = BodyReadout.record(body, "stabilize.estimate")
     F = r.body_rec_count()
     if F < 1:
         raise RuntimeError("stabilize.estimate: no frame recorded")

@@ -12,15 +12,10 @@ ratio J, the principal stretches l1 >= l2, the axis of l1 in the body frame and 
 import numpy as np
 
 from . import body as _body
-from .videoio import AviWriter
 
 WHICH = ("J", "l1", "l2")
 DEFAULT_GAIN = 256.0        # levels per unit of (value - 1): 0.5 .. 1.5 fills the table
 DEFAULT_ALPHA = 128
-
-
-def _renderer(kf_or_renderer):
-    return kf_or_renderer.state.renderer if hasattr(kf_or_renderer, "state") else kf_or_renderer
 
 
 def default_lut():
@@ -57,7 +52,7 @@ def triangles(kf_or_renderer, states):
     (frames, triangles), NaN for a triangle that is collapsed in the body frame or has a vertex that is not finite;
     area0 (triangles,) the rest areas; body_area (frames,) the area of the whole mesh over its rest area,
     sum |area0| J / sum |area0| over the triangles that are not NaN; n_bad (frames,) the number of those that are."""
-    r = _renderer(kf_or_renderer)
+    r = _body.renderer_of(kf_or_renderer)
     v = r.strain_tri(states)
     area0 = rest_area(r.uv, r.tri)
     J = v[:, :, 0]
@@ -76,7 +71,7 @@ def labels(kf_or_renderer, states, labels=None, points=None, point_radius=3.0, L
     `points` (P, 2) (body.disc_labels: a cell for every point, NaN for one off the mesh), or, with neither, the label
     image in place on the handle (Renderer.body_set_labels).  L: the number of cells of a label image whose last cells may
     own no pixel (default: its largest label + 1)."""
-    r = _renderer(kf_or_renderer)
+    r = _body.renderer_of(kf_or_renderer)
     if labels is not None and points is not None:
         raise ValueError("strain.labels: a label image or points, not both")
     if points is not None:
@@ -121,31 +116,12 @@ def write_video(kf_or_renderer, states, source, path, which="J", gain=DEFAULT_GA
     (frames, H, W) uint8) with `which` (J, l1, l2) of the mesh at states[k] painted on (Renderer.view_strain), written
     to the AVI `path` (uncompressed; video_opts: AviWriter's codec options) by the writer thread of a pipeline.VideoTap, as cellview.write_video does: the disk is
     not waited for.  Pass the smoothed states of a run that has them.  -> frames written."""
-    from .pipeline import DeviceBuffer, VideoTap
-    r = _renderer(kf_or_renderer)
-    frame_at = source.frame_at if hasattr(source, "frame_at") else (lambda k: (source[k],))
+    from .pipeline import write_painted_video
+    r = _body.renderer_of(kf_or_renderer)
     if which not in WHICH:
         raise ValueError("write_video: which %r (one of %s)" % (which, ", ".join(WHICH)))
     lut = default_lut() if lut is None else np.ascontiguousarray(lut, np.uint8)
-    n = r.nx * r.ny
-    writer = AviWriter(path, r.nx, r.ny, fps=fps, **(video_opts or {}))
-    tap = VideoTap(r, writer)
-    d_frames = [DeviceBuffer(n, tap.device) for _ in range(tap.slots)]     # a frame is read when its view runs
-    try:
-        for k in range(len(states)):
-            X = np.asarray(states[k], np.float64).reshape(-1)
-            img = np.ascontiguousarray(np.asarray(frame_at(k)[0], np.uint8).reshape(r.ny, r.nx))
 
-            def queue(d_out, stream, k=k, X=X, img=img):
-                d = d_frames[k % tap.slots]              # free: the writer has waited for the view that read it
-                d.upload(img)
-                r.view_strain_dev(X, d.ptr, d_out, which, gain, alpha, lut, wire, stream)
-            tap.push(queue)
-    finally:
-        try:
-            tap.close()
-        finally:
-            for b in d_frames:
-                b.close()
-            writer.close()
-    return writer.frames
+    def paint(k, X, d_frame, d_out, stream):
+        r.view_strain_dev(X, d_frame, d_out, which, gain, alpha, lut, wire, stream)
+    return write_painted_video(r, states, source, path, paint, fps, video_opts)

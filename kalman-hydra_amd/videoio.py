@@ -688,22 +688,13 @@ class AviSource:
         """Queue frames f0 .. f1 - 1 into `ring` (a FrameRing) on its copy stream: runs of consecutive slots, one
         decode each, then the mirror slots by device-to-device copies.  -> the bytes queued host-to-device, as the
         decoder counted them."""
-        L = _lib.lib()
-        n, R, sent = ring.n, ring.R, 0
-        shown = ring.planes == 3
-        f = f0
-        while f < f1:
-            s = f % R
-            k = min(self.run, f1 - f, R - s)
+        sent = 0
+        for f, k, s, mirror in ring.runs(f0, f1, self.run):
+            d_raw, d_mask, d_shown, stride, stream = ring.run_dev(s)
             chunks = [self.reader.chunk(i) for i in range(f, f + k)]
-            sent += self.decoder.decode_run_dev(chunks, ring.d_video.ptr + s * n, ring.d_masks.ptr + s * n,
-                                                ring.d_observed.ptr + s * n if shown else None, n, ring.W,
-                                                int(np.floor(self.threshold)), None, ring._stream)   # frame > t for integer frames
-            for t in range(s, min(s + k, ring.extra)):            # the mirror behind the ring
-                for buf in (ring.d_video, ring.d_masks) + ((ring.d_observed,) if shown else ()):
-                    _lib.check(L.hm_dev_copy_async(self.device, buf.ptr + (R + t) * n, buf.ptr + t * n, n, ring._stream),
-                               "hm_dev_copy_async")
-            f += k
+            sent += self.decoder.decode_run_dev(chunks, d_raw, d_mask, d_shown, stride, ring.W,
+                                                int(np.floor(self.threshold)), None, stream)   # frame > t for integer frames
+            ring.mirror(mirror)
         return sent
 
     def close(self):
