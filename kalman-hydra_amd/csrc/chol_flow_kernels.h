@@ -39,8 +39,9 @@
 #define FLOW_NT 256
 #ifdef HM_STAMP
 // development builds only (tools/stamp_chol.py): clock stamps of the chain's columns, 8 words per column behind the
-// 4096 x 8 words k_render_iter uses
-#define HM_CHAIN_STAMP(c, k) do { if (g_stamp && (threadIdx.x & 63) == 0) g_stamp[(size_t)(4096 + (c)) * 8 + (k)] = clock64(); } while (0)
+// 4096 x 8 words k_render_iter uses (the same buffer: hm_debug_stamps sets this pointer and ekf_kernels.h' g_stamp)
+__device__ long long *g_chain_stamp;
+#define HM_CHAIN_STAMP(c, k) do { if (g_chain_stamp && (threadIdx.x & 63) == 0) g_chain_stamp[(size_t)(4096 + (c)) * 8 + (k)] = clock64(); } while (0)
 #else
 #define HM_CHAIN_STAMP(c, k) do { } while (0)
 #endif
@@ -476,7 +477,7 @@ __device__ __forceinline__ double d_job_sum(const double *__restrict__ out, int 
     return v;
 }
 
-#define PREP_MAX_ENTRIES (4 * (EKF_MAX_STAR + 2))
+// (PREP_MAX_ENTRIES: hm_types.h -- hm_ctx_create checks the mesh against it)
 __global__ __launch_bounds__(256) void k_solve_prep(PrepArgs p)
 {
     __shared__ double s_term[PREP_MAX_ENTRIES];

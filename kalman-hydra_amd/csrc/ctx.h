@@ -1,10 +1,13 @@
 // The filter handle of libhydra_mi.so (hm_ctx) and the helpers every translation unit that works on one needs.  Private to
-// the library: ekf.hip (the filter), smooth.hip (the smoother), readout.hip (views, body-frame readout, statistics) and
-// record.hip (the kept record) include it, all built by the one compiler command of the Makefile.  Everything defined here is
+// the library: the filter's four files -- ekf.hip (handle, renders, measurement), update.hip (the dense update), mask.hip
+// (pruning, outline, projection), predict_dev.hip (the prediction) -- and smooth.hip (the smoother), readout.hip (views,
+// body-frame readout, statistics) and record.hip (the kept record) include it, all built by the one compiler command of the
+// Makefile.  The filter's state is grouped by concern in structs, as the readout's is; each says which file writes it.  Everything defined here is
 // static or a template; the hidden functions declared at the end are defined once, in the translation unit named there.
 #pragma once
 #include "hm_common.h"
 #include "hm_types.h"
+#include "host_block.h"
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -182,121 +185,200 @@ struct RecState {
     uint8_t *ev = nullptr, *ev_out = nullptr;
 };
 
+// ---- the filter's state, grouped as the readout's is.  Each struct says who writes it. ----------------------------------------
+
+// The mask's pruning, its outline and projectmask (mask.hip; project_kernels.h), all allocated on first use (ready).  mask.hip
+// writes it; ekf.hip marks outline_ready / prepared when the observation changes; hm_update_run takes the projection's block.
+struct MaskState {
+    int2 *d_outline = nullptr;       // outline pixels (W*H) ...
+    int *d_outline_cnt = nullptr;    // ... and their counters
+    uint8_t *d_mask = nullptr;       // a caller's host mask, uploaded (hm_project_mask, hm_prune_mask)
+    uint8_t *d_flag = nullptr;       // border-pixel flags of the mask (W*H)
+    uint8_t *d_pruned = nullptr;     // the mask after the reference's contour pruning (k_ccl_*): what the outline and the walk use
+    Ccl ccl = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};     // its working arrays
+    double *d_X = nullptr;           // hm_project_mask's copy of the state (second stream)
+    double *pin = nullptr;           // page-locked: [X in (4N) | result block of 4N + 1 values: projected X, vertices moved] (k_project_mask_host)
+    std::vector<double> v;           // the host's copy of that block
+    int *d_done = nullptr;           // workgroups of k_project_mask_host that have finished
+    long long ticket = 0;
+    bool ready = false;              // project_buffers has built all of the above
+    bool outline_ready = false;      // the outline of the resident mask (o_ym) has been queued on the second stream
+    const uint8_t *prepared = nullptr;        // hm_prepare_mask: the outline in the buffers is that of this mask (device memory)
+    hipEvent_t ev_outline = nullptr; // ... recorded behind every outline queued on the second stream
+    hipEvent_t ev_pm = nullptr;      // the chained projection has run (hm_chain_project)
+};
+
+// hm_newton_dev_start / _finish: the state prediction's Newton loop as a four-wave kernel on a stream of its own
+// (predict_dev.hip writes it; hm_update_run and hm_chain_project read the prediction in flight)
+struct Newton4State {
+    hipStream_t stream = nullptr;
+    int *d_nbr = nullptr, *d_nbb = nullptr, *d_bars = nullptr;
+    double *d_l0 = nullptr;
+    int deg = 0;                     // padded degree of the table on the device (8 or 12), 0: this mesh does not fit the kernel
+    std::vector<int32_t> bars;       // the springs the table was built for
+    std::vector<double> l0;
+    double *pin = nullptr;           // page-locked: [X in (4N) | result block of 4N + 2 values (host_block.h): X out, iterations, failed]
+    double *d_X = nullptr;           // the same 4N + 2 values in device memory, for hm_chain_project
+    std::vector<double> v;           // the host's copy of that block
+    long long ticket = 0;
+    bool pending = false;
+    bool ready = false;              // hm_newton_dev_start's stream, blocks and event are there
+    hipEvent_t ev = nullptr;         // the prediction's kernel has run
+    int fail = 0;                    // test knob (hm_ctx_tune "newton_fail"): the next device predictions report a failed inner solve
+};
+
+// hm_ms_predict's own buffers (predict_dev.hip): the spring topology of k_ms_newton (bars, CSR of the bars of every vertex),
+// its state and result words
+struct NewtonState {
+    int *d_bars = nullptr, *d_voff = nullptr, *d_vbar = nullptr, *d_info = nullptr;
+    double *d_l0 = nullptr, *d_X = nullptr;
+    bool ready = false;              // the fixed-size buffers are there and k_ms_newton may take its LDS
+};
+
+// hm_chain_project: projectmask of the prediction in flight queued behind it; the projected state (d_X0) is the
+// prior mean of the next hm_update_run, which also collects what the two kernels report (update.hip writes the rest;
+// pending is set by mask.hip and cleared by every call that starts or ends a prediction)
+struct ChainState {
+    bool pending = false;
+    std::vector<double> pred, proj;  // ... the predicted / the projected state of the last chained update
+    int its = 0, moved = 0;
+};
+
+// The spring topology of the covariance prediction on the device, kept between frames, and its host staging
+// (predict_dev.hip: cov_predict_core, queue_predict_ahead)
+struct SpringState {
+    std::vector<int> h_off, h_bar, h_other;     // host staging of the topology: live until the copies ran
+    std::vector<double> h_blk;
+    std::vector<int32_t> bars_cached;           // the springs whose topology is on the device (d_off / d_bar / d_other)
+    int *d_off = nullptr, *d_bar = nullptr, *d_other = nullptr;
+    double *d_blk = nullptr;
+    double *pin_blk = nullptr;       // page-locked staging of the spring blocks of the prediction queued ahead
+};
+
+// hm_update_arm_newton: the springs and parameters of the prediction the next hm_update_run starts (armed.newton);
+// they stay: the tail on the helper thread reads them (update.hip)
+struct ArmedPrediction {
+    std::vector<int32_t> bars;
+    std::vector<double> l0;
+    double par[4] = {0, 0, 0, 0};    // kappa, M, dt, tol
+    int maxiter = 0;
+};
+
+// hm_update_arm_cov: the covariance half of the next frame's prediction queued by hm_update_run itself ("pre-queued";
+// predict_dev.hip writes it, every call that makes the prediction stale clears valid, hm_update_arm_cov sets eps_F)
+struct QueuedPrediction {
+    double eps_F = 0.0;
+    bool valid = false;              // queued and not yet taken: d_Wprior / d_invW0 hold the prediction made from ...
+    std::vector<double> X, l0;       // ... this state, these springs and parameters (kappa, a, s, eps_F)
+    std::vector<int32_t> bars;
+    double par[4] = {0, 0, 0, 0};
+};
+
+// The tail of hm_update_run -- covariance of the kept state, gains, their result block, and the covariance half of the
+// NEXT frame's prediction (queue_predict_ahead) -- runs on a stream of its own: beside the measurement hm_update_run
+// queued for an iteration that did not happen, and beside the next frame's reference render and measurement, which
+// need none of its buffers.  on_stream4: it may still be running; `stream` waits for ev (on the device)
+// before anything there touches the dense buffers (ctx_join; hm_update_run itself only before its first solve).
+// (update.hip writes it; ctx_join clears on_stream4.)
+struct TailState {
+    int async = 1;                   // hm_ctx_tune "tail_async": the tail queued by the helper thread (same results)
+    int split = 1;                   // hm_ctx_tune "tail_split": 0 keeps the tail on `stream` (same results either way)
+    hipStream_t stream4 = nullptr;
+    hipEvent_t ev = nullptr;
+    bool on_stream4 = false;
+    // the tail block of the last hm_update_run (Hz components, gains): taken by hm_update_tail, or by hm_update_run itself
+    // when its caller wants them at once
+    bool pending = false;
+    // the tail block belongs to the last hm_update_run, which succeeded: false from the entry of every hm_update_run until it
+    // has taken, queued or zero-filled the block (an update that fails leaves nothing for hm_update_tail to hand out)
+    bool valid = false;
+    long long ticket = 0;
+    hipStream_t stream = nullptr;    // the stream that block's kernel is on
+    std::vector<double> v;           // the host's copy of the block, taken when whole (hb_wait)
+};
+
+// hm_jz_multi / hm_j_multi (ekf.hip): id images of the reference and the two perturbed renders, the label palette (T),
+// per-label boxes and sums; allocated on first use
+struct MultiState {
+    int *d_ids[3] = {nullptr, nullptr, nullptr};
+    int *d_labels = nullptr;
+    int4 *d_lbox = nullptr;
+    double *d_lout = nullptr;
+    std::vector<double> h_lout;
+};
+
 struct hm_ctx {
-    int device, W, H, N, T, E, njobs;
+    int device = 0, W = 0, H = 0, N = 0, T = 0, E = 0, njobs = 0;
     HmOwner own{1};                  // every buffer, stream and event below (HYDRA_MI_POISON class 1)
     Helper helper;
     bool helper_used = false;
-    int tail_async = 1;              // hm_ctx_tune "tail_async": the tail of hm_update_run queued by the helper thread (same results)
-    double eps_Z, eps_J, eps_M;
-    hipStream_t stream;
+    double eps_Z = 0, eps_J = 0, eps_M = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;   // the second stream (mask.hip's ensure_stream2): the mask's launches, hm_ms_predict's state prediction
     // mesh
-    int *d_tri, *d_star_off, *d_star_tri, *d_edges;
+    int *d_tri = nullptr, *d_star_off = nullptr, *d_star_tri = nullptr, *d_edges = nullptr;
     int *d_nb_off = nullptr, *d_nb_u = nullptr, *d_nb_e = nullptr;   // per vertex: neighbours (ascending) and their edge jobs (k_solve_prep)
-    float *d_uv;
-    uint8_t *d_tex;
+    float *d_uv = nullptr;
+    uint8_t *d_tex = nullptr;
     std::vector<int> edges;          // host copy, E*2
+    std::vector<int> tri;            // host copy of the triangles (orientation test of hm_update_run)
     // observation
-    uint8_t *d_yim, *d_ym;
-    float *d_yfx, *d_yfy, *d_yfxm, *d_yfym;
+    uint8_t *d_yim = nullptr, *d_ym = nullptr;
+    float *d_yfx = nullptr, *d_yfy = nullptr, *d_yfxm = nullptr, *d_yfym = nullptr;
     bool obs_owned = true;           // false when set_observation_dev aliases caller memory
-    const uint8_t *o_yim, *o_ym;     // pointers in use (owned or caller's)
-    const float *o_yfx, *o_yfy;
-    bool have_tex, have_obs, have_ref;
-    // renders
-    Targets ref, P, Q;
-    TriSetup *d_setup, *d_cfgs;
-    int4 *d_ubox;
+    const uint8_t *o_yim = nullptr, *o_ym = nullptr;     // pointers in use (owned or caller's)
+    const float *o_yfx = nullptr, *o_yfy = nullptr;
+    bool have_tex = false, have_obs = false, have_ref = false;
+    // renders and measurement
+    Targets ref = {nullptr, nullptr, nullptr, nullptr}, P = {nullptr, nullptr, nullptr, nullptr}, Q = {nullptr, nullptr, nullptr, nullptr};
+    TriSetup *d_setup = nullptr, *d_cfgs = nullptr;
+    int4 *d_ubox = nullptr;
     int *d_tlist = nullptr, *d_tcount = nullptr;   // ... and the list / count of the tiles with a non-zero word
     unsigned *d_tmask = nullptr;     // per vertex and tile of its star region: the star triangles that can reach the tile (k_measure_vertex)
-    double *d_X, *d_out, *d_partial;
-    uint8_t *d_im8, *d_m8;
+    double *d_X = nullptr, *d_out = nullptr, *d_partial = nullptr;
+    uint8_t *d_im8 = nullptr, *d_m8 = nullptr;
     std::vector<double> X0;          // state of the reference render
-    // dense update on the device (n4 = 4N)
-    double *d_HTH;                   // dense HTH of the last measurement: zero outside the J pattern (cleared once;
-                                     // every pattern entry is rewritten by every measurement), used for nothing else
-    double *d_H, *d_Hz, *d_Hzc, *d_invW0, *d_Af[2], *d_T[2], *d_step, *d_Wtmp, *d_X0, *d_Xn, *d_Wprior, *d_gain, *d_Awork, *d_Lt[2];
-    std::vector<double> upd_X0;      // prior mean given to hm_update_begin
-    int upd_last = -1, upd_prev = -1;   // which d_Af holds the factor of the last / previous step (-1: none)
-    double *d_Wres;                  // the covariance resident on the device (the result of the last
-                                     // hm_cov_predict / hm_update_cov / hm_update_run): d_Wtmp, d_H or
-                                     // d_Wprior, or NULL when that buffer has been reused since
-    double *pin;                     // page-locked, device-mapped: hm_update_run's result blocks (host_block.h) -- per iteration
-                                     // [step (n4) | RES_HEAD values], then the tail block [Hzc (n4 x 4) | gains (3 x n4)], every value
-                                     // a pair of words -- and two words of scratch (pin_scratch)
-    size_t pin_n;
-    int *pin_scratch;                // ... where hm_measure / hm_update_step have a flag copied to
-    std::vector<double> resv, tailv; // the host's copies of the two blocks, taken when whole (hb_wait)
-    int result_delay = 0;            // test knob: the result kernels publish a block's last word first, the rest this many us later
-    // the tail block of the last hm_update_run (Hz components, gains): taken by hm_update_tail, or by hm_update_run itself
-    // when its caller wants them at once
-    bool tail_pending = false;
-    // the tail block belongs to the last hm_update_run, which succeeded: false from the entry of every hm_update_run until it
-    // has taken, queued or zero-filled the block (an update that fails leaves nothing for hm_update_tail to hand out)
-    bool tail_valid = false;
-    long long tail_ticket = 0;
-    hipStream_t tail_stream = nullptr;
-    Armed armed;                     // hm_update_arm_*: taken whole by the next hm_update_run
-    std::vector<int> sp_h_off, sp_h_bar, sp_h_other;   // host staging of the spring topology
-    std::vector<double> sp_h_blk;
-    std::vector<int32_t> sp_bars_cached;   // the springs whose topology is on the device (d_sp_off / _bar / _other)
-    std::vector<int> tri;            // host copy of the triangles (orientation test of hm_update_run)
-    DPool pool;                      // parked difference images (see ekf_kernels.h)
-    int *d_area;
-    int *d_sp_off, *d_sp_bar, *d_sp_other;
-    double *d_sp_blk;
-    bool upd_open;
-    bool prefactored;                // d_invW0 is the inverse of the resident covariance d_Wprior (hm_update_prefactor)
+    DPool pool = {};                 // parked difference images (see ekf_kernels.h)
+    int *d_area = nullptr;
     std::vector<double> h_partial;
     int red_blocks = 512;
     double *d_tpart = nullptr;       // per-tile partial sums of Renderer.error from k_render_iter (tiles x 4)
     std::vector<double> h_tpart;
     int ntiles = 0;
     int render_rows = RI_H;          // strip height of k_render_iter (16 or 8)
+    int vsplit = 5, esplit = 0;      // workgroups per vertex / per edge job of the measurement (hm_ctx_tune)
+    // dense update on the device (n4 = 4N)
+    double *d_HTH = nullptr;         // dense HTH of the last measurement: zero outside the J pattern (cleared once;
+                                     // every pattern entry is rewritten by every measurement), used for nothing else
+    double *d_H = nullptr, *d_Hz = nullptr, *d_Hzc = nullptr, *d_invW0 = nullptr, *d_Af[2] = {nullptr, nullptr}, *d_T[2] = {nullptr, nullptr},
+           *d_step = nullptr, *d_Wtmp = nullptr, *d_X0 = nullptr, *d_Xn = nullptr, *d_Wprior = nullptr, *d_gain = nullptr, *d_Awork = nullptr,
+           *d_Lt[2] = {nullptr, nullptr};
+    std::vector<double> upd_X0;      // prior mean given to hm_update_begin
+    int upd_last = -1, upd_prev = -1;   // which d_Af holds the factor of the last / previous step (-1: none)
+    double *d_Wres = nullptr;        // the covariance resident on the device (the result of the last
+                                     // hm_cov_predict / hm_update_cov / hm_update_run): d_Wtmp, d_H or
+                                     // d_Wprior, or NULL when that buffer has been reused since
+    double *pin = nullptr;           // page-locked, device-mapped: hm_update_run's result blocks (host_block.h) -- per iteration
+                                     // [step (n4) | RES_HEAD values], then the tail block [Hzc (n4 x 4) | gains (3 x n4)], every value
+                                     // a pair of words -- and two words of scratch (pin_scratch)
+    size_t pin_n = 0;
+    int *pin_scratch = nullptr;      // ... where hm_measure / hm_update_step have the pool's overflow flag copied to (with_pool_retry)
+    std::vector<double> resv;        // the host's copy of an iteration's block, taken when whole (hb_wait)
+    int result_delay = 0;            // test knob: the result kernels publish a block's last word first, the rest this many us later
+    Armed armed;                     // hm_update_arm_*: taken whole by the next hm_update_run
+    hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)
+    bool upd_open = false;
+    bool prefactored = false;        // d_invW0 is the inverse of the resident covariance d_Wprior (hm_update_prefactor)
     // Renderer.error of the state hm_update_run kept, against the raw flow, from the render of its last iteration
     // (hm_update_last_error): valid until the observation or anything else on the handle changes
     bool last_err_valid = false;
     double last_err[4] = {0, 0, 0, 0};
     std::vector<double> last_err_X;
-    long long run_ticket;            // sequence number of hm_update_run's per-iteration result blocks
-    int vsplit = 5, esplit;          // workgroups per vertex / per edge job of the measurement (hm_ctx_tune)
-    // hm_update_arm_newton: the springs and parameters of the prediction the next hm_update_run starts (armed.newton);
-    // they stay: the tail on the helper thread reads them
-    std::vector<int32_t> pn_bars;
-    std::vector<double> pn_l0;
-    double pn_par[4] = {0, 0, 0, 0};
-    int pn_maxiter = 0;
-    // hm_update_arm_cov: the covariance half of the next frame's prediction queued by hm_update_run itself (pq = "pre-queued")
-    double pq_eps_F = 0.0;
-    bool pq_valid = false;           // queued and not yet taken: d_Wprior / d_invW0 hold the prediction made from ...
-    std::vector<double> pq_X, pq_l0; // ... this state, these springs and parameters (kappa, a, s, eps_F)
-    std::vector<int32_t> pq_bars;
-    double pq_par[4] = {0, 0, 0, 0};
-    // hm_newton_dev_start / _finish: the state prediction's Newton loop as a four-wave kernel on a stream of its own
-    hipStream_t stream3 = nullptr;
-    int *d_n4nbr = nullptr, *d_n4nbb = nullptr, *d_n4bars = nullptr;
-    double *d_n4l0 = nullptr;
-    int n4deg = 0;                   // padded degree of the table on the device (8 or 12), 0: this mesh does not fit the kernel
-    std::vector<int32_t> n4_bars;    // the springs the table was built for
-    std::vector<double> n4_l0;
-    double *pin_n4 = nullptr;        // page-locked: [X in (4N) | result block of 4N + 2 values (host_block.h): X out, iterations, failed]
-    double *d_n4X = nullptr;         // the same 4N + 2 values in device memory, for hm_chain_project
-    std::vector<double> n4v;         // the host's copy of that block
-    long long n4_ticket = 0;
-    bool n4_pending = false;
-    int newton_fail = 0;             // test knob: the next device predictions report a failed inner solve
-    hipEvent_t ev_n4 = nullptr, ev_pm = nullptr;     // the prediction's kernel / the chained projection have run
-    bool n4_ready = false;           // hm_newton_dev_start's stream, blocks and event are there
-    // hm_chain_project: projectmask of the prediction in flight queued behind it; the projected state (d_X0) is the
-    // prior mean of the next hm_update_run, which also collects what the two kernels report
-    bool chain_pending = false;
-    std::vector<double> chain_pred, chain_proj;     // ... the predicted / the projected state of the last chained update
-    int chain_its = 0, chain_moved = 0;
-    double *pin_blk = nullptr;       // page-locked staging of the spring blocks of that prediction
+    long long run_ticket = 0;        // sequence number of hm_update_run's per-iteration result blocks
     std::thread worker;              // hm_update_prefactor queues its launches from here while the caller predicts the state
-    bool worker_active;
-    int worker_rc;
-    char worker_err[512];
+    bool worker_active = false;
+    int worker_rc = HM_OK;
+    char worker_err[512] = "";
     // the factorisation as one persistent launch (chol_flow_kernels.h) / its workgroups.  (192 workgroups: 304.9 -> 306.9 us
     // per iteration with the filter alone, but 260.5 -> 264.2 and 318.6 -> 324.1 frames/s in the two benches -- the
     // workgroups that poll for blocks take issue slots from the flow's kernels on every compute unit they sit on; 160 and
@@ -304,42 +386,18 @@ struct hm_ctx {
     int chol_flow = 1, flow_wgs = 192;
     int flow_stall = 0;              // test knob: FlowArgs.stall
     int speculate = 1;               // hm_update_run queues the next iteration's measurement before it knows that there is one
-    double *d_flowP;                 // 3 x nb x 32 x 32 scratch of that launch
-    unsigned *d_flowctl;             // its task counter and time-out word
-    hipStream_t stream2;             // hm_ms_predict: the state prediction runs beside the covariance half of the update
-    // The tail of hm_update_run -- covariance of the kept state, gains, their result block, and the covariance half of the
-    // NEXT frame's prediction (queue_predict_ahead) -- runs on a stream of its own: beside the measurement hm_update_run
-    // queued for an iteration that did not happen, and beside the next frame's reference render and measurement, which
-    // need none of its buffers.  tail_on_stream4: it may still be running; `stream` waits for ev_tail (on the device)
-    // before anything there touches the dense buffers (ctx_join; hm_update_run itself only before its first solve).
-    hipStream_t stream4 = nullptr;
-    hipEvent_t ev_tail = nullptr;
-    bool tail_on_stream4 = false;
-    int tail_split = 1;              // hm_ctx_tune "tail_split": 0 keeps the tail on `stream` (same results either way)
-    int *d_nbars, *d_nvoff, *d_nvbar, *d_ninfo;     // its spring topology (bars, CSR of the bars of every vertex), result words
-    double *d_nl0, *d_nX;
-    bool newton_ready = false;       // hm_ms_predict's buffers are there and k_ms_newton may take its LDS
-    int *d_ids[3];                   // hm_jz_multi / hm_j_multi: id images of the reference and the two perturbed renders,
-    int *d_labels;                   // the label palette (T), per-label boxes and sums; allocated on first use
-    int4 *d_lbox;
-    double *d_lout;
-    std::vector<double> h_lout;
-    int2 *d_outline;                 // hm_project_mask: outline pixels (W*H), counters, uploaded mask; allocated on first use
-    int *d_outline_cnt;
-    uint8_t *d_pm_mask;
-    uint8_t *d_pm_flag = nullptr;    // border-pixel flags of that mask (W*H)
-    uint8_t *d_pm_pruned = nullptr;  // the mask after the reference's contour pruning (k_ccl_*): what the outline and the walk use
-    Ccl ccl = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};     // its working arrays
-    double *d_pm_X = nullptr;        // hm_project_mask's copy of the state (second stream)
-    double *pin_pm = nullptr;        // page-locked: [X in (4N) | result block of 4N + 1 values: projected X, vertices moved] (k_project_mask_host)
-    std::vector<double> pmv;         // the host's copy of that block
-    int *d_pm_done = nullptr;        // workgroups of k_project_mask_host that have finished
-    long long pm_ticket = 0;
-    bool pm_ready = false;           // project_buffers has built all of the above
-    bool outline_ready = false;      // the outline of the resident mask (o_ym) has been queued on the second stream
-    const uint8_t *prepared_mask = nullptr;   // hm_prepare_mask: the outline in the buffers is that of this mask (device memory)
-    hipEvent_t ev_outline = nullptr; // ... recorded behind every outline queued on the second stream
-    hipEvent_t ev_m0 = nullptr;      // the first measurement of an update has run (hm_update_arm_mask)
+    double *d_flowP = nullptr;       // 3 x nb x 32 x 32 scratch of that launch
+    unsigned *d_flowctl = nullptr;   // its task counter and time-out word
+    // the filter's state by concern (the structs above)
+    MaskState mask;
+    Newton4State newton4;
+    NewtonState newton;
+    ChainState chain;
+    SpringState sp;
+    ArmedPrediction pn;
+    QueuedPrediction pq;
+    TailState tail;
+    MultiState multi;
     // The readout: views, the body-frame readout with its statistics, the deformation readout, the kept record.  Each has buffers of its own, allocated
     // on first use through `own`, and touches nothing the filter reads (readout.hip and record.hip have the code and name no
     // other field of the handle than W, H, N, T, device, own, stream, d_tri, d_uv, d_tex and, for the overlay, have_tex,
@@ -374,9 +432,9 @@ static int ctx_join(hm_ctx *h, bool lazy = false)
 {
     if (!h) return HM_OK;
     if (const int rc = helper_join(h)) return rc;
-    if (!lazy && h->tail_on_stream4) {
-        h->tail_on_stream4 = false;
-        if (hipSetDevice(h->device) != hipSuccess || hipStreamWaitEvent(h->stream, h->ev_tail, 0) != hipSuccess) {
+    if (!lazy && h->tail.on_stream4) {
+        h->tail.on_stream4 = false;
+        if (hipSetDevice(h->device) != hipSuccess || hipStreamWaitEvent(h->stream, h->tail.ev, 0) != hipSuccess) {
             hm_set_error("the handle's stream cannot wait for the tail of the last update");
             return HM_ERR_HIP;
         }
@@ -420,6 +478,42 @@ static inline hipError_t stream_wait(hipStream_t s)
         }
     }
 }
+
+// Take values [first, first + n) of a result block in page-locked host memory (host_block.h) into `out` once every one of
+// their pairs carries the launch's stamp.  The last pair is looked at first (one pair of loads per poll while nothing is
+// there yet); a block of which some words are still missing is simply looked at again -- no order of arrival is assumed.
+// A couple of microseconds against ~20 for waking up from a stream synchronisation, which remains as the fallback: after
+// 20 ms the stream is waited for (everything queued behind the block's kernel included) and a block that is not whole
+// then is an error.
+static inline int hb_wait(hipStream_t st, const double *blk, size_t first, size_t n, unsigned long long stamp, double *out, const char *who)
+{
+    const volatile unsigned long long *canary = (const volatile unsigned long long *)blk + 2 * (first + n - 1);
+    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_yield = t_start + std::chrono::microseconds(700), t_give_up = t_start + std::chrono::milliseconds(20);
+    bool polite = false;
+    for (int spin = 0;; spin++) {
+        if ((canary[0] ^ canary[1]) == stamp && hb_take(blk, first, n, stamp, out)) return HM_OK;
+        if (polite) std::this_thread::yield();
+        else __builtin_ia32_pause();
+        if ((spin & 255) == 255) {
+            const auto now = std::chrono::steady_clock::now();
+            if (now > t_give_up) break;
+            polite = now > t_yield;
+        }
+    }
+    HM_HIP(hipStreamSynchronize(st));
+    if (hb_take(blk, first, n, stamp, out)) return HM_OK;
+    hm_set_error("%s: a result block of the device is not whole although its stream has completed (stamp %016llx)", who, stamp);
+    return HM_ERR_HIP;
+}
+
+// what an entry point of the filter needs to have been called before it
+#define NEED_TEX(h, who) \
+    if (!(h)->have_tex) { hm_set_error(who ": hm_set_texture has not been called"); return HM_ERR_STATE; }
+#define NEED_OBS(h, who) \
+    if (!(h)->have_obs) { hm_set_error(who ": hm_set_observation has not been called"); return HM_ERR_STATE; }
+#define NEED_REF(h, who) \
+    if (!(h)->have_ref) { hm_set_error(who ": hm_initjacobian has not been called"); return HM_ERR_STATE; }
 
 template <typename T>
 static int upload(HmOwner &own, T **dst, const T *src, size_t n)
@@ -483,8 +577,62 @@ static inline void spring_blocks(int n_bars, const int32_t *bars, const double *
 __attribute__((visibility("hidden"))) void ekf_queue_setup_all(hipStream_t st, const Mesh &m, const double *d_X, TriSetup *d_setup);
 __attribute__((visibility("hidden"))) void ekf_queue_render(hipStream_t st, const Mesh &m, const double *d_X, const TriSetup *d_setup,
                                                             const Targets &out, const int *d_labels, int *d_ids);
-// The filter's launch sequences that the smoother repeats (dense_kernels.h, chol_flow_kernels.h: ekf.hip), both defined in
-// ekf.hip.  FP = F src by k_fw_rows, then dst = FP F^T + Weps by k_pft_cols, for the N vertices and springs tp.  The
+// What crosses between the filter's own translation units, in the same way.  Defined in ekf.hip (the measurement):
+// render_iter: the render of the device-resident state dX into t as one launch (k_render_iter), with the strips' partial sums
+// of Renderer.error and, as extra workgroups, the star regions of the measurement at dX; render_strips: its strips;
+// render_error_sums: those partial sums copied, waited for and added up into err (nothing stays in flight when it fails);
+// measure_dev: the measurement at dX, whose render is in h->ref (ref_ready) or is put there -- scatter: the job sums also go
+// to the dense HTH / Hz / Hzc; measure_on_device: the same at a host state, which becomes the state of the reference
+// render; queue_star_regions: k_star_regions at dX alone; pool_grow: room for the star regions a measurement reported
+// not to fit (the stream must be idle).
+__attribute__((visibility("hidden"))) int render_iter(hm_ctx *h, const double *dX, Targets t, bool with_err, int masked, bool regions, double deltaX);
+__attribute__((visibility("hidden"))) int render_strips(const hm_ctx *h);
+__attribute__((visibility("hidden"))) int render_error_sums(hm_ctx *h, const char *who, double err[4]);
+__attribute__((visibility("hidden"))) int measure_dev(hm_ctx *h, const double *dX, bool ref_ready, double deltaX, int masked,
+                                                      bool regions_ready = false, bool scatter = true);
+__attribute__((visibility("hidden"))) int measure_on_device(hm_ctx *h, const double *X, double deltaX, int masked, bool scatter = true);
+__attribute__((visibility("hidden"))) int queue_star_regions(hm_ctx *h, const double *dX, double deltaX, int masked);
+__attribute__((visibility("hidden"))) int pool_grow(hm_ctx *h, const char *who);
+// Defined in update.hip (the dense update): the covariance half of hm_update_begin on stream st (NULL: the handle's) -- the
+// prior (W_prior, or the resident covariance) into d_Wprior, its factor, inv(W) into d_invW0.
+__attribute__((visibility("hidden"))) int prior_inverse(hm_ctx *h, const double *W_prior, hipStream_t st = nullptr);
+#ifdef HM_STAMP
+__attribute__((visibility("hidden"))) int update_debug_stamps(long long *dev_ptr);     // hm_debug_stamps: chol_flow_kernels.h' pointer
+#endif
+// Defined in mask.hip (pruning, outline, projection): the handle's second stream, made on first use; the pruning and the
+// outline of a mask in device memory queued on it (the projection's buffers must be there: a non-NULL mask.d_outline says
+// so); hm_prepare_mask behind its argument checks.
+__attribute__((visibility("hidden"))) int ensure_stream2(hm_ctx *h);
+__attribute__((visibility("hidden"))) int queue_outline(hm_ctx *h, const uint8_t *mask);
+__attribute__((visibility("hidden"))) int prepare_mask(hm_ctx *h, const uint8_t *d_y_m);
+// Defined in predict_dev.hip (the prediction): the covariance half of the NEXT frame's prediction from the state X that
+// hm_update_run keeps, queued on st behind the covariance of that state (hm_update_arm_cov).
+__attribute__((visibility("hidden"))) int queue_predict_ahead(hm_ctx *h, const double *X, int n_bars, const int32_t *bars, const double *l0,
+                                                              double kappa, double M, double dt, double eps_F, hipStream_t st);
+
+// A measurement whose star regions may not fit the pool of difference images: body() queues it and what hangs on it, the copy
+// of the pool's overflow flag among them (pool_flag_queue), and returns with the stream idle.  When the flag is set the pool
+// is grown and body() runs once more.  The flag lands in the handle's pinned block, not in a caller's frame: an error return
+// must not leave a copy in flight towards a dead stack slot.
+static inline int pool_flag_queue(hm_ctx *h)
+{
+    HM_HIP(hipMemcpyAsync(h->pin_scratch, h->pool.overflow, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return HM_OK;
+}
+template <typename Body>
+static int with_pool_retry(hm_ctx *h, const char *who, Body body)
+{
+    for (int attempt = 0;; attempt++) {
+        *h->pin_scratch = 0;
+        HM_TRY(body());
+        if (!*h->pin_scratch) return HM_OK;
+        if (attempt) { hm_set_error("%s: the star regions do not fit the difference-image pool", who); return HM_ERR_STATE; }
+        HM_TRY(pool_grow(h, who));
+    }
+}
+
+// The filter's launch sequences that the smoother repeats (dense_kernels.h, chol_flow_kernels.h: update.hip), both defined in
+// update.hip.  FP = F src by k_fw_rows, then dst = FP F^T + Weps by k_pft_cols, for the N vertices and springs tp.  The
 // factorisation of a.A as one persistent launch, k_chol_flow on wgs workgroups, behind k_flow_fill unless the caller's
 // own assembly pass has pre-filled its outputs (fill = false).
 __attribute__((visibility("hidden"))) void ekf_queue_fpft(hipStream_t st, const double *src, double *FP, double *dst, int N,

@@ -14,7 +14,7 @@
 // do not depend on workgroup scheduling.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "ekf_kernels.h"      // d_tile_partial_sums (k_iter_result)
+#include "hm_types.h"         // DNB, d4_t, d_mfma_*, SpringTopo; RI_NV, RI_GROUPS, d_tile_partial_sums (k_iter_result)
 #include "host_block.h"
 
 // (DNB, the block size, d4_t, d_mfma_nn / d_mfma_tn and SpringTopo: hm_types.h -- smooth_kernels.h uses them too)
@@ -607,7 +607,7 @@ __global__ __launch_bounds__(256) void k_assemble(const double *__restrict__ inv
 // (spare) | factorisation time-out | flow x, flow y error sums against the raw flow].  One workgroup.  The host takes
 // the block when every pair carries this launch's stamp; nothing depends on the order the words arrive in (delay_us,
 // the test knob "result_delay", has the LAST value published first and everything else that much later).
-#define RES_HEAD 10           // doubles behind the step in a result block
+// (RES_HEAD, the doubles behind the step in a result block: hm_types.h -- hm_ctx_create sizes the page-locked blocks)
 
 __global__ __launch_bounds__(256) void k_iter_result(const double *__restrict__ step, int n, const double *__restrict__ partial,
                                                      int ntiles, const int *__restrict__ overflow,

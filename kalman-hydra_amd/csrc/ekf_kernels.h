@@ -435,29 +435,7 @@ struct MeasureArgs {
 };
 
 #define MEAS_NT 256
-#define MEAS_OUT 40
-#define MEAS_VSPLIT_MAX 16     // most workgroups per vertex job (their partial sums are added in order)
-// vertex job output layout (doubles): only the non-zero terms are accumulated, and only in the
-// combinations KFState.update uses -- 19 sums per thread instead of 38 keep the kernel under 128
-// VGPRs (four waves per SIMD):
-enum {
-    // jz, plus minus minus (the central difference of kalman.py:499-515 is linear in the sums): x and y
-    // per channel (Hzc wants the components), vx only has an fx term, vy only an fy term
-    A_X = 0, A_Y = 4, A_VX = 8, A_VY = 9,
-    // self block of HTH (forward differences): the four channels already weighted by 1/eps and added
-    A_XX = 10, A_XY = 11, A_YY = 12,
-    A_XVX = 13, A_YVX = 14,               // fx channel only (not weighted)
-    A_XVY = 15, A_YVY = 16,               // fy channel only
-    A_VXVX = 17, A_VYVY = 18,
-    A_NV = 19
-};
-enum {
-    // edge job (v,w): D_v,a * D_w,b
-    B_XX = 0, B_XY = 1, B_YX = 2, B_YY = 3,        // geometry x geometry: channels weighted by 1/eps and added
-    B_XVX = 4, B_YVX = 5, B_VXX = 6, B_VXY = 7, B_VXVX = 8,        // fx channel (not weighted)
-    B_XVY = 9, B_YVY = 10, B_VYX = 11, B_VYY = 12, B_VYVY = 13,    // fy channel
-    B_NV = 14
-};
+// (MEAS_OUT, MEAS_VSPLIT_MAX and the layout of the job sums, A_* / B_*: hm_types.h -- k_solve_prep reads them too)
 
 #define MEAS_NCFG 5            // reference, +x, -x, +y, -y of the vertex
 #define UBOX_STRIDE (EKF_MAX_STAR + 4)
@@ -889,7 +867,6 @@ __global__ __launch_bounds__(MEAS_NT) void k_measure_edge(MeasureArgs a)
 //       modulo 256 before the sum) are added up over the strip and stored as partial[strip]; the final sums
 //       are formed in a fixed two-level order (d_tile_partial_sums; hm_tile_partial_sums on the host).
 #define RI_CHUNK 32
-#define RI_GROUPS 256
 #define RI_W 64
 struct IterRenderArgs {
     Mesh m;
@@ -900,7 +877,7 @@ struct IterRenderArgs {
     double *partial;          // strips x RI_NV
     int tiles_x, tiles_y, with_err, n_regions;
 };
-#define RI_NV 6               // image, flow x, flow y, mask terms against `o`, then flow x, flow y against the raw flow
+// (RI_NV, RI_GROUPS and d_tile_partial_sums: hm_types.h -- k_iter_result adds the strips' sums up)
 struct RenderShared {
     unsigned mask[EKF_MAX_TRI / 32];
     TriSetup cand[RI_CHUNK];
@@ -1083,34 +1060,6 @@ __global__ __launch_bounds__(256, 4) void k_render_iter(IterRenderArgs r, Measur
     if (!r.with_err) return;
     d_block_reduce<RI_NV, 256>(e, sh.t.red, r.partial + RI_NV * (size_t)tile);
     HM_STAMP_AT(4);
-}
-
-// The RI_NV error sums from the per-strip partials, in a fixed order: thread g of RI_GROUPS adds the partials g,
-// g + RI_GROUPS, ... in ascending order, then the group sums are added in ascending order (hm_tile_partial_sums on
-// the host does the same additions).  sp: RI_GROUPS x RI_NV doubles of LDS; out[0..RI_NV-1] written by threads
-// 0..RI_NV-1 after a barrier inside.
-__device__ __forceinline__ void d_tile_partial_sums(const double *__restrict__ partial, int ntiles, double *sp, double *out)
-{
-    const int t = threadIdx.x;
-    if (t < RI_GROUPS) {
-        double s[RI_NV];
-#pragma unroll
-        for (int k = 0; k < RI_NV; k++) s[k] = 0.0;
-#pragma unroll 4
-        for (int i = t; i < ntiles; i += RI_GROUPS) {
-            const double2 *q = (const double2 *)(partial + RI_NV * (size_t)i);
-#pragma unroll
-            for (int k = 0; k < RI_NV / 2; k++) { const double2 v = q[k]; s[2 * k] += v.x; s[2 * k + 1] += v.y; }
-        }
-#pragma unroll
-        for (int k = 0; k < RI_NV; k++) sp[RI_NV * t + k] = s[k];
-    }
-    __syncthreads();
-    if (t < RI_NV) {
-        double s = 0.0;
-        for (int g = 0; g < RI_GROUPS; g++) s += sp[RI_NV * g + t];
-        out[t] = s;
-    }
 }
 
 // ---- job sums -> Hz, Hz components, dense HTH (device twin of the unpacking in KFState.update) -------

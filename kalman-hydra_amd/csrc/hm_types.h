@@ -1,7 +1,7 @@
 // Plain types, constants and __device__ inline helpers that more than one translation unit of libhydra_mi.so needs: what
 // the filter handle (ctx.h) holds by value, and what kernels on both sides of the filter / readout split use.  No
 // __global__ function lives here, so any translation unit may include it -- unlike the *_kernels.h headers, whose kernels
-// are not static: each of those is compiled by exactly one translation unit (ekf.hip, smooth.hip, readout.hip or record.hip).
+// are not static: each of those is compiled by exactly one translation unit (the Makefile lists them).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -203,7 +203,64 @@ struct DPool {
 
 #define RI_H 16                        // strip height of the default launch (hm_ctx_tune "render_rows": 16 or 8)
 
-// ---- the dense f64 algebra (kernels: dense_kernels.h, chol_flow_kernels.h in ekf.hip; smooth_kernels.h in smooth.hip) ----
+// ---- what the measurement (ekf_kernels.h: ekf.hip) hands to the dense update (dense_kernels.h, chol_flow_kernels.h: update.hip) ----
+#define MEAS_OUT 40                    // doubles of one workgroup's job sums (ekf_kernels.h has the layout)
+#define MEAS_VSPLIT_MAX 16             // most workgroups per vertex job (their partial sums are added in order)
+// vertex job output layout (doubles): only the non-zero terms are accumulated, and only in the
+// combinations KFState.update uses -- 19 sums per thread instead of 38 keep the kernel under 128
+// VGPRs (four waves per SIMD):
+enum {
+    // jz, plus minus minus (the central difference of kalman.py:499-515 is linear in the sums): x and y
+    // per channel (Hzc wants the components), vx only has an fx term, vy only an fy term
+    A_X = 0, A_Y = 4, A_VX = 8, A_VY = 9,
+    // self block of HTH (forward differences): the four channels already weighted by 1/eps and added
+    A_XX = 10, A_XY = 11, A_YY = 12,
+    A_XVX = 13, A_YVX = 14,               // fx channel only (not weighted)
+    A_XVY = 15, A_YVY = 16,               // fy channel only
+    A_VXVX = 17, A_VYVY = 18,
+    A_NV = 19
+};
+enum {
+    // edge job (v,w): D_v,a * D_w,b
+    B_XX = 0, B_XY = 1, B_YX = 2, B_YY = 3,        // geometry x geometry: channels weighted by 1/eps and added
+    B_XVX = 4, B_YVX = 5, B_VXX = 6, B_VXY = 7, B_VXVX = 8,        // fx channel (not weighted)
+    B_XVY = 9, B_YVY = 10, B_VYX = 11, B_VYY = 12, B_VYVY = 13,    // fy channel
+    B_NV = 14
+};
+#define PREP_MAX_ENTRIES (4 * (EKF_MAX_STAR + 2))      // most terms of a row of the system (k_solve_prep)
+#define RES_HEAD 10                    // doubles behind the step in a result block (k_iter_result)
+#define RI_GROUPS 256
+#define RI_NV 6               // image, flow x, flow y, mask terms against `o`, then flow x, flow y against the raw flow
+
+// The RI_NV error sums from the per-strip partials of k_render_iter, in a fixed order: thread g of RI_GROUPS adds the partials g,
+// g + RI_GROUPS, ... in ascending order, then the group sums are added in ascending order (hm_tile_partial_sums on
+// the host does the same additions).  sp: RI_GROUPS x RI_NV doubles of LDS; out[0..RI_NV-1] written by threads
+// 0..RI_NV-1 after a barrier inside.
+__device__ __forceinline__ void d_tile_partial_sums(const double *__restrict__ partial, int ntiles, double *sp, double *out)
+{
+    const int t = threadIdx.x;
+    if (t < RI_GROUPS) {
+        double s[RI_NV];
+#pragma unroll
+        for (int k = 0; k < RI_NV; k++) s[k] = 0.0;
+#pragma unroll 4
+        for (int i = t; i < ntiles; i += RI_GROUPS) {
+            const double2 *q = (const double2 *)(partial + RI_NV * (size_t)i);
+#pragma unroll
+            for (int k = 0; k < RI_NV / 2; k++) { const double2 v = q[k]; s[2 * k] += v.x; s[2 * k + 1] += v.y; }
+        }
+#pragma unroll
+        for (int k = 0; k < RI_NV; k++) sp[RI_NV * t + k] = s[k];
+    }
+    __syncthreads();
+    if (t < RI_NV) {
+        double s = 0.0;
+        for (int g = 0; g < RI_GROUPS; g++) s += sp[RI_NV * g + t];
+        out[t] = s;
+    }
+}
+
+// ---- the dense f64 algebra (kernels: dense_kernels.h, chol_flow_kernels.h in update.hip; smooth_kernels.h in smooth.hip) ----
 #define DNB 32          // block size
 
 // the accumulator of v_mfma_f64_16x16x4_f64 (dense_kernels.h has the layout)

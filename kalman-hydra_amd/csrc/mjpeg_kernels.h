@@ -1,5 +1,5 @@
 // Baseline JPEG encoder of the video writer (include/hydra_mi.h, "Motion-JPEG").  Compiled by
-// readout.hip alone.  Five launches per frame, all on the caller's stream:
+// mjpeg.hip alone.  Five launches per frame, all on the caller's stream:
 //   k_mjpeg_blocks   a workgroup stages the samples of 256 (grey) or 85 (colour) MCUs in LDS, every pixel loaded and
 //                    converted once; then one thread per 8x8 block of one component: DCT, quantisation, zigzag -> 64
 //                    int16 and the bit length of the block's AC code

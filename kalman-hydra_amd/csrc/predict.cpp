@@ -141,7 +141,7 @@ extern "C" int hm_ms_newton(int N, int I, const int32_t *bars, const double *l0,
 // the moment the update's last iteration has reported: hm_ms_newton for the NEXT frame can run on a host thread
 // while the device finishes the covariance of this one and the caller does its bookkeeping between frames.  One
 // persistent thread per worker object (posting a job costs a few microseconds; creating a thread per frame ~60).
-// (the device version of the loop: hm_newton_dev_start / _finish, csrc/ekf.hip; 1 = this job is for the host)
+// (the device version of the loop: hm_newton_dev_start / _finish, csrc/predict_dev.hip; 1 = this job is for the host)
 namespace {
 struct NewtonWorker {
     hm_ctx_t ctx = nullptr;          // hm_ms_worker_attach: jobs go to this handle's device when they fit its kernel

@@ -4,9 +4,9 @@
 // update started from -- and the backward recursion over it, all on the device.  What the record does not hold is
 // recomputed: Pp_{k+1} = F_k P_k F_k^T + Weps by k_fw_rows / k_pft_cols from slot k and the spring blocks at x_k (the
 // launches and inputs of the forward prediction, so the same bits), its factor and inverse by the factorisation the
-// update uses; both launch sequences are queued through ekf_queue_fpft and ekf_queue_chol_flow (ctx.h; ekf.hip compiles
+// update uses; both launch sequences are queued through ekf_queue_fpft and ekf_queue_chol_flow (ctx.h; update.hip compiles
 // their kernels).  The buffers belong to the smoother (its own HmOwner); the filter's are only read, and only by the
-// copies hm_smooth_record queues.  Of the filter handle (ctx.h) it reads device, N, stream, stream3, stream4, d_X0, d_Wres,
+// copies hm_smooth_record queues.  Of the filter handle (ctx.h) it reads device, N, stream, newton4.stream, tail.stream4, d_X0, d_Wres,
 // upd_X0 and flow_wgs, and joins it (ctx_join).
 #include "ctx.h"
 #include "smooth_kernels.h"
@@ -137,17 +137,17 @@ extern "C" int hm_smooth_record(hm_smooth_t sm, const double *X)
     }
     HM_HIP(hipSetDevice(h->device));
     // m_k: the prior mean the update started from, where the update keeps it (d_X0: given to hm_update_begin, or left by
-    // the chained projection).  The next chained projection rewrites it on stream3: that stream waits for the copy.
+    // the chained projection).  The next chained projection rewrites it on newton4.stream: that stream waits for the copy.
     HM_HIP(hipMemcpyAsync(sm->d_m + (size_t)k * n4, h->d_X0, (size_t)n4 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     HM_HIP(hipEventRecord(sm->ev_mean, h->stream));
-    if (h->stream3) HM_HIP(hipStreamWaitEvent(h->stream3, sm->ev_mean, 0));
-    // P_k: the covariance the update kept, behind the tail that forms it (ctx_join: `stream` waits for stream4), ahead of
-    // the next tail (stream4 waits for the copy) and of everything the handle's own stream does next
+    if (h->newton4.stream) HM_HIP(hipStreamWaitEvent(h->newton4.stream, sm->ev_mean, 0));
+    // P_k: the covariance the update kept, behind the tail that forms it (ctx_join: `stream` waits for tail.stream4), ahead of
+    // the next tail (tail.stream4 waits for the copy) and of everything the handle's own stream does next
     HM_JOIN(h);
     HM_HIP(hipMemcpyAsync(sm->d_P + (size_t)k * n4 * n4, h->d_Wres, (size_t)n4 * n4 * sizeof(double), hipMemcpyDeviceToDevice,
                           h->stream));
     HM_HIP(hipEventRecord(sm->ev_cov, h->stream));
-    if (h->stream4) HM_HIP(hipStreamWaitEvent(h->stream4, sm->ev_cov, 0));
+    if (h->tail.stream4) HM_HIP(hipStreamWaitEvent(h->tail.stream4, sm->ev_cov, 0));
     sm->hx.insert(sm->hx.end(), X, X + n4);
     sm->hblk.resize((size_t)(k + 1) * 3 * sm->n_bars);
     if (sm->n_bars > 0)

@@ -5,7 +5,8 @@ renderer.py:197-737) for the part that is on the hot path: the four off-screen
 renders of the textured mesh and the reductions against the observed frame
 that the reference splits between OpenGL (renderer.py:310-325) and the CUDA
 kernels of ``CUDAGL`` / ``CUDAGL_multi`` (cuda.py, cuda_multi.py).  Here both
-live in libhydra_mi.so (csrc/ekf.hip): a software rasteriser and fused
+live in libhydra_mi.so (csrc/ekf.hip; the dense update, the mask and the
+prediction in csrc/update.hip, mask.hip, predict_dev.hip): a software rasteriser and fused
 perturb-and-reduce kernels; nothing is rendered on a CPU and there is no
 fallback.  The views of the reference canvas (raw, overlay, texture, mask, flowx,
 flowy; renderer.py:436-475, 595-628) and its force plot are composed on the device
@@ -14,7 +15,7 @@ key bindings are not part of this build.
 
 This file holds the filter side; ``Renderer`` inherits the readout side from
 ``readout.Readout`` (views, body, strain, statistics) and ``record.Record``
-(``body_rec_*``), as csrc/readout.hip and csrc/record.hip stand beside csrc/ekf.hip.
+(``body_rec_*``), as csrc/readout.hip and csrc/record.hip stand beside the filter's files.
 
 Same method names and argument meaning as the reference:
 ``update_vertex_buffer``, ``render``, ``initjacobian``, ``jz``, ``jz_multi``,

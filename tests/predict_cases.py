@@ -20,7 +20,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 # IteratedMSKalmanFilter's parameters of the prediction (kappa, M, deltat, maxiter, tol)
 DEFAULTS = dict(kappa=-1.0, M=1.0, dt=0.05, maxiter=1000, tol=1e-4)
 
-# LDS limits of the two launchers (csrc/ekf.hip: hm_newton_dev_start, hm_ms_predict)
+# LDS limits of the two launchers (csrc/predict_dev.hip: hm_newton_dev_start, hm_ms_predict)
 NEWTON4_LDS_MAX = 64 * 1024
 NEWTON_LDS_MAX = 160 * 1024
 

@@ -1,5 +1,5 @@
 """Development aid: where a column of the chain of k_chol_flow spends its time.  Needs the instrumented build
-(hipcc ... -DHM_STAMP -shared brox.hip ekf.hip smooth.hip readout.hip record.hip predict.cpp -o build_exp/libhydra_mi_stamp.so): lane 0 of the chain's
+(hipcc ... -DHM_STAMP -shared brox.hip ekf.hip update.hip mask.hip predict_dev.hip smooth.hip readout.hip record.hip mjpeg.hip deep.hip predict.cpp avi.cpp mjpeg_dec.cpp -o build_exp/libhydra_mi_stamp.so): lane 0 of the chain's
 waves writes clock64() stamps per column -- 0 top of the column, 1 products done, 2 / 3 start / end of the B wave's
 eight strips, 5 T wave done with its stores, 7 prefetch of the next column's operands done, 6 after the closing barrier."""
 import ctypes, os, sys

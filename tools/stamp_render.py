@@ -1,5 +1,5 @@
 """Development aid: where the workgroups of k_render_iter spend their time.  Needs the instrumented build
-(hipcc ... -DHM_STAMP -shared brox.hip ekf.hip smooth.hip readout.hip record.hip predict.cpp -o build_exp/libhydra_mi_stamp.so): every workgroup writes
+(hipcc ... -DHM_STAMP -shared brox.hip ekf.hip update.hip mask.hip predict_dev.hip smooth.hip readout.hip record.hip mjpeg.hip deep.hip predict.cpp avi.cpp mjpeg_dec.cpp -o build_exp/libhydra_mi_stamp.so): every workgroup writes
 wall_clock64() stamps (100 MHz) at its start, after the triangle tests, after the pixel loop, before the reduction
 and at its end."""
 import ctypes, os, sys
