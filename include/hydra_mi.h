@@ -1158,6 +1158,52 @@ int hm_deep_map_run_dev(hm_deep_t deep, int nframes, const uint16_t *host_frames
 int hm_deep_map(hm_deep_t deep, const uint16_t *host_frame, int swap, uint8_t *out, uint32_t *clipped);
 int hm_deep_uploaded(hm_deep_t deep, uint64_t *last_run, uint64_t *total);
 
+/* Full-depth traces: a second pass over the 16-bit frames once the track and the cells are known.  The frames are uploaded
+ * run by run as above; only the body pixels that belong to some column (an ROI, a ring, a shape) are pulled back through
+ * the tracked mesh, by the body warp's own rule, and summed at full depth in exact integers.  Where the cells are stays
+ * the 8-bit pipeline's decision; only how bright they are is read again, from the camera's numbers.
+ * tests/deeptrace_ref.py restates every rule below; DESIGN section 25.
+ *
+ *   Value       For a body pixel p (raster index in body coordinates) and frame k, the full-depth registered value
+ *               v16_k(p) follows k_body_warp's rule (csrc/body_kernels.h, d_body_px).  It uses the same body map, the same
+ *               barycentrics and the same binary64 position, computed without contraction.  It takes the same bilinear
+ *               sample at (x - 0.5, y - 0.5), with texels clamped to the frame.  It rounds with the same rint, half to even.
+ *               The texels are the frame's unsigned 16-bit pixels.  With swap = 1 their two bytes are exchanged first, at
+ *               the gather, with no extra pass over the frame.  It is 0 off the map, and 0 where x or y is not finite or
+ *               lies beyond +-2^20 px.  The result lies in 0..65535.
+ *   Columns     A readout is C columns, 1 <= C <= 4096, in compressed-column form: col_ptr[C + 1] is int64, ascending,
+ *               with col_ptr[0] = 0; pix[M] is int32, each entry a raster index in 0..W H - 1; wt[M] is uint16
+ *               (M = col_ptr[C], at most 2^30).  A column may be empty, and a pixel may appear in any number of columns.
+ *               The sums are
+ *                   sums[k C + s] = sum over e in column s of wt[e] v16_k(pix[e])   (uint64).
+ *               An entry whose pixel is off the map adds 0.  No magnitude bound is needed: 2^30 entries x 65535^2 < 2^63.
+ *   Planes      Optionally, each frame's whole registered plane is returned: W H uint16 values, 0 off the map -- the
+ *               16-bit twin of hm_body_warp's out.
+ *
+ * Both calls take the deep handle and the filter handle.  The deep handle owns the upload path (its device copies of a
+ * run, its two page-locked staging blocks used in turn, an upload stream) and the columns, states, sums and planes on the
+ * device, all released by hm_deep_destroy; the filter handle owns the body map, built on first use as ever.  Both must be
+ * on one device and have one W x H: otherwise HM_ERR_ARG with both sizes.
+ * hm_deep_body_set_columns  copies the columns to the device; they stay until they are set again or cleared (pix NULL).
+ *               HM_ERR_ARG, with the numbers: C outside 1..4096; a col_ptr that does not start at 0 or is not ascending
+ *               (the column is named); more than 2^30 entries; a pix outside the frame (the entry is named).
+ * hm_deep_body_run  nframes >= 1 dense host frames of W x H uint16 (of any number: they are worked through max_run at a time)
+ *               and X, one state per frame, dense, 4N doubles each, of which the first 2N are read as hm_body_warp reads
+ *               them.  sums: nframes C values; planes: nframes W H values; either may be NULL, not both (HM_ERR_ARG).
+ *               Sums without columns set: HM_ERR_STATE.  Runs alternate between two device copies, so that the upload
+ *               of run i + 1 (from page-locked blocks, on the upload stream, queued before run i's downloads) is free to go
+ *               beside the kernels of run i (on the handle's stream): that is the intent, and whether the two overlap is
+ *               the runtime's to decide (DESIGN section 25 could not measure it).  Returns when everything
+ *               has been computed and downloaded; waits for the filter handle's helper, and for its stream only while the
+ *               map is built; changes nothing on the filter handle.  One call on a pair of handles at a time.
+ *               k_deep_cols (the sums): a wave takes one column of one frame and strides through its entries; a column of
+ *               more than hm_ctx_tune "deep_col_entries" (64..2^30, default 1024) entries is cut into pieces of that many
+ *               whose 64-bit partial sums meet in integer atomics: the same bytes for every value of the key.  A pixel in
+ *               several columns is warped once per column.  k_body_warp16 (the planes): 4 pixels a thread. */
+int hm_deep_body_set_columns(hm_deep_t deep, hm_ctx_t ctx, int C, const int64_t *col_ptr, const int32_t *pix, const uint16_t *wt);
+int hm_deep_body_run(hm_deep_t deep, hm_ctx_t ctx, int64_t nframes, const uint16_t *host_frames, int swap, const double *X,
+                     uint64_t *sums, uint16_t *planes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,8 @@ SIGNATURES = {
                                            c_vp, c_vp]),
     "hm_deep_map": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_deep_uploaded": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "hm_deep_body_set_columns": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "hm_deep_body_run": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -142,6 +142,10 @@ struct BodyState {
     double *stimg = nullptr;         // mean, std, corr: 3 planes of W*H (hm_body_stats_images / _peaks)
     int *pkidx = nullptr, *pkcnt = nullptr;             // hm_body_stats_peaks: raster indices (W*H), their number
     double *pkscore = nullptr;
+    // hm_deep_body_run (deep.hip, which borrows the map through body_map_view): the most entries of a column that one wave
+    // of k_deep_cols walks; a longer column is cut into pieces of this many (hm_ctx_tune "deep_col_entries": same bytes
+    // for every value)
+    int deep_col_entries = 1024;
 };
 
 // hm_strain_*: the deformation readout (strain_kernels.h), buffers of its own, grown to the largest call so far

@@ -3,8 +3,12 @@
 // One handle owns the device copy of a run's 16-bit pixels, the table, the 64-bit histogram, the clip words and two
 // page-locked staging blocks used in turn.  hm_deep_hist_add and hm_deep_map work on a stream of the handle's and return
 // when they are done; hm_deep_map_run_dev queues on the caller's stream and returns.
+// Full-depth traces (hm_deep_body_*; kernels in deeptrace_kernels.h, which this translation unit alone
+// compiles too): the same handle owns the columns, a second device copy of a run, the runs' states, sums and planes, an
+// upload stream and the events between it and `stream`; of the filter handle it borrows the body map (BodyMapView).
 #include "hm_common.h"
 #include "deep_kernels.h"
+#include "deeptrace_kernels.h"
 #include <algorithm>
 #include <cstring>
 
@@ -33,6 +37,21 @@ struct hm_deep {
     // hm_deep_hist_add's and hm_deep_map's own
     hipStream_t stream = nullptr;
     uint8_t *d_out = nullptr;
+    // hm_deep_body_*: the columns as set (col_ptr stays on the host: the pieces are cut from it) ...
+    int C = 0;
+    std::vector<int64_t> col_ptr;
+    int *d_pix = nullptr;
+    uint16_t *d_wt = nullptr;
+    DeepPiece *d_pieces = nullptr;               // ... cut for pieces_E entries a wave (0: to be cut)
+    int npieces = 0, pieces_E = 0;
+    bool any_split = false;
+    // ... and a run's second device copy (runs alternate between d_in and d_in2, so that the upload of one is free to go
+    // beside the kernels of the other), states (page-locked and on the device), sums and planes
+    uint16_t *d_in2 = nullptr, *d_planes = nullptr;
+    double *d_X[2] = {nullptr, nullptr}, *h_X[2] = {nullptr, nullptr};
+    unsigned long long *d_sums = nullptr;
+    hipStream_t up_stream = nullptr;             // the uploads; the kernels and the downloads are on `stream`
+    hipEvent_t uploaded[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
 };
 
 extern "C" int hm_deep_create(int device, int W, int H, int max_run, hm_deep_t *out)
@@ -224,5 +243,163 @@ extern "C" int hm_deep_uploaded(hm_deep_t d, uint64_t *last_run, uint64_t *total
     HM_ARG(d, "hm_deep_uploaded: NULL handle");
     if (last_run) *last_run = d->last_h2d;
     if (total) *total = d->total_h2d;
+    return HM_OK;
+}
+
+// ---- full-depth traces (deeptrace_kernels.h) ---------------------------------------------------------------------------
+static int deep_same_frame(const hm_deep *d, const BodyMapView &v, const char *who)
+{
+    HM_ARG(d->device == v.device && d->W == v.W && d->H == v.H,
+           "%s: the deep handle is %dx%d on device %d, the filter handle %dx%d on device %d: they must agree", who, d->W, d->H,
+           d->device, v.W, v.H, v.device);
+    return HM_OK;
+}
+
+extern "C" int hm_deep_body_set_columns(hm_deep_t d, hm_ctx_t h, int C, const int64_t *col_ptr, const int32_t *pix,
+                                        const uint16_t *wt)
+{
+    HM_ARG(d && h, "hm_deep_body_set_columns: NULL handle");
+    if (!pix) {                                  // clears
+        d->C = 0; d->col_ptr.clear(); d->npieces = 0; d->pieces_E = 0;
+        return HM_OK;
+    }
+    HM_ARG(C >= 1 && C <= 4096, "hm_deep_body_set_columns: %d columns outside 1..4096", C);
+    HM_ARG(col_ptr && wt, "hm_deep_body_set_columns: NULL col_ptr or wt");
+    HM_ARG(col_ptr[0] == 0, "hm_deep_body_set_columns: col_ptr[0] = %lld, not 0", (long long)col_ptr[0]);
+    for (int s = 0; s < C; s++)
+        HM_ARG(col_ptr[s + 1] >= col_ptr[s], "hm_deep_body_set_columns: col_ptr is not ascending at column %d: %lld after %lld", s,
+               (long long)col_ptr[s + 1], (long long)col_ptr[s]);
+    const int64_t M = col_ptr[C];
+    HM_ARG(M <= (int64_t)DEEP_COL_ENTRIES_MAX, "hm_deep_body_set_columns: %lld entries, at most %d", (long long)M, DEEP_COL_ENTRIES_MAX);
+    for (int64_t e = 0; e < M; e++)
+        HM_ARG(pix[e] >= 0 && (size_t)pix[e] < d->n, "hm_deep_body_set_columns: entry %lld is pixel %d, outside 0..%zu (a %dx%d frame)",
+               (long long)e, pix[e], d->n - 1, d->W, d->H);
+    BodyMapView v;
+    HM_TRY(body_map_view(h, &v));
+    HM_TRY(deep_same_frame(d, v, "hm_deep_body_set_columns"));
+    HM_TRY(deep_buffers(d));
+    HM_HIP(hipStreamSynchronize(d->stream));
+    d->C = 0;                                    // (until the columns are in place)
+    const size_t m = (size_t)std::max<int64_t>(M, 1);
+    HM_HIP(d->own.grow(&d->d_pix, m * sizeof(int)));
+    HM_HIP(d->own.grow(&d->d_wt, m * sizeof(uint16_t)));
+    if (M) {
+        HM_HIP(hipMemcpy(d->d_pix, pix, (size_t)M * sizeof(int), hipMemcpyHostToDevice));
+        HM_HIP(hipMemcpy(d->d_wt, wt, (size_t)M * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
+    d->col_ptr.assign(col_ptr, col_ptr + C + 1);
+    d->pieces_E = 0;
+    d->C = C;
+    return HM_OK;
+}
+
+// the columns cut into pieces of at most E entries, on the device
+static int deep_pieces(hm_deep *d, int E)
+{
+    if (d->pieces_E == E) return HM_OK;
+    std::vector<DeepPiece> pc;
+    d->any_split = false;
+    for (int s = 0; s < d->C; s++) {
+        const int64_t a = d->col_ptr[s], len = d->col_ptr[s + 1] - a;
+        if (len <= E) { pc.push_back(DeepPiece{(long long)a, (int)len, s}); continue; }
+        d->any_split = true;
+        for (int64_t o = 0; o < len; o += E)
+            pc.push_back(DeepPiece{(long long)(a + o), (int)std::min<int64_t>(E, len - o), (int)((unsigned)s | DEEP_PIECE_SPLIT)});
+    }
+    HM_HIP(hipStreamSynchronize(d->stream));     // (a launch before read the pieces in place)
+    HM_HIP(d->own.grow(&d->d_pieces, pc.size() * sizeof(DeepPiece)));
+    HM_HIP(hipMemcpy(d->d_pieces, pc.data(), pc.size() * sizeof(DeepPiece), hipMemcpyHostToDevice));
+    d->npieces = (int)pc.size();
+    d->pieces_E = E;
+    return HM_OK;
+}
+
+extern "C" int hm_deep_body_run(hm_deep_t d, hm_ctx_t h, int64_t nframes, const uint16_t *host_frames, int swap, const double *X,
+                                uint64_t *sums, uint16_t *planes)
+{
+    HM_ARG(d && h, "hm_deep_body_run: NULL handle");
+    HM_ARG(host_frames && X, "hm_deep_body_run: NULL frames or states");
+    HM_ARG(nframes >= 1, "hm_deep_body_run: %lld frames, at least 1 is needed", (long long)nframes);
+    HM_ARG(sums || planes, "hm_deep_body_run: neither sums nor planes asked for");
+    if (sums && d->C == 0) {
+        hm_set_error("hm_deep_body_run: sums asked for, and hm_deep_body_set_columns has set no columns");
+        return HM_ERR_STATE;
+    }
+    BodyMapView v;
+    HM_TRY(body_map_view(h, &v));
+    HM_TRY(deep_same_frame(d, v, "hm_deep_body_run"));
+    HM_TRY(deep_buffers(d));
+    const size_t run = (size_t)d->max_run, n = d->n, xs = (size_t)4 * v.N, C = (size_t)d->C;
+    HM_HIP(d->own.alloc(&d->d_in2, run * n * sizeof(uint16_t)));
+    HM_HIP(d->own.stream(&d->up_stream, false));
+    for (int b = 0; b < 2; b++) {
+        HM_HIP(d->own.grow(&d->d_X[b], run * xs * sizeof(double)));
+        HM_HIP(d->own.host_grow(&d->h_X[b], run * xs * sizeof(double), hipHostMallocDefault));
+        HM_HIP(d->own.event(&d->uploaded[b]));
+        HM_HIP(d->own.event(&d->consumed[b]));
+    }
+    if (sums) {
+        HM_HIP(d->own.grow(&d->d_sums, run * C * sizeof(unsigned long long)));
+        HM_TRY(deep_pieces(d, v.col_entries));
+    }
+    if (planes) HM_HIP(d->own.alloc(&d->d_planes, run * n * sizeof(uint16_t)));
+    uint16_t *const in[2] = {d->d_in, d->d_in2};
+    const int64_t runs = (nframes + d->max_run - 1) / d->max_run;
+    // the upload of run i: staged, then copied on the upload stream once the kernels of run i - 2 have read the copy it replaces
+    auto upload = [&](int64_t i) -> int {
+        const int b = (int)(i & 1);
+        const int64_t f0 = i * d->max_run;
+        const size_t k = (size_t)std::min<int64_t>(d->max_run, nframes - f0);
+        hm_deep::Stage *st;
+        HM_TRY(deep_stage(d, &st));
+        memcpy(st->px, host_frames + (size_t)f0 * n, k * n * sizeof(uint16_t));
+        if (i >= 2) HM_HIP(hipStreamWaitEvent(d->up_stream, d->consumed[b], 0));
+        HM_HIP(hipMemcpyAsync(in[b], st->px, k * n * sizeof(uint16_t), hipMemcpyHostToDevice, d->up_stream));
+        // (the states go through a page-locked block as the frames do: a copy from the caller's pageable memory could hold
+        // this thread until the stream reaches it)
+        if (i >= 2) HM_HIP(hipEventSynchronize(d->uploaded[b]));
+        memcpy(d->h_X[b], X + (size_t)f0 * xs, k * xs * sizeof(double));
+        HM_HIP(hipMemcpyAsync(d->d_X[b], d->h_X[b], k * xs * sizeof(double), hipMemcpyHostToDevice, d->up_stream));
+        HM_HIP(hipEventRecord(st->copied, d->up_stream));
+        st->used = true;
+        HM_HIP(hipEventRecord(d->uploaded[b], d->up_stream));
+        return HM_OK;
+    };
+    int rc = upload(0);
+    for (int64_t i = 0; i < runs && rc == HM_OK; i++) {
+        rc = [&]() -> int {
+            const int b = (int)(i & 1);
+            const int64_t f0 = i * d->max_run;
+            const size_t k = (size_t)std::min<int64_t>(d->max_run, nframes - f0);
+            HM_HIP(hipStreamWaitEvent(d->stream, d->uploaded[b], 0));
+            DeepWarp a;
+            a.n = (int)n; a.W = d->W; a.H = d->H; a.swap = swap ? 1 : 0;
+            a.tri_of = v.tri; a.bary = v.bary; a.tidx = v.tidx;
+            a.X = d->d_X[b]; a.xstride = xs; a.frames = in[b];
+            if (sums) {
+                // (the words the pieces of a split column add to; a whole column's word is stored, an empty column's too)
+                if (d->any_split) HM_HIP(hipMemsetAsync(d->d_sums, 0, k * C * sizeof(unsigned long long), d->stream));
+                hipLaunchKernelGGL(k_deep_cols, dim3((unsigned)hm_cdiv(d->npieces, DEEP_COL_WAVES), (unsigned)k), dim3(64 * DEEP_COL_WAVES),
+                                   0, d->stream, a, d->npieces, d->C, (const DeepPiece *)d->d_pieces, (const int *)d->d_pix,
+                                   (const uint16_t *)d->d_wt, d->d_sums);
+            }
+            if (planes)
+                hipLaunchKernelGGL(k_body_warp16, dim3((unsigned)hm_cdiv(hm_cdiv((int)n, 4), 256), (unsigned)k), dim3(256), 0, d->stream, a,
+                                   d->d_planes);
+            HM_HIP(hipGetLastError());
+            HM_HIP(hipEventRecord(d->consumed[b], d->stream));
+            if (i + 1 < runs) HM_TRY(upload(i + 1));           // (before the downloads into pageable memory, which may hold this thread)
+            if (sums)
+                HM_HIP(hipMemcpyAsync(sums + (size_t)f0 * C, d->d_sums, k * C * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+            if (planes)
+                HM_HIP(hipMemcpyAsync(planes + (size_t)f0 * n, d->d_planes, k * n * sizeof(uint16_t), hipMemcpyDeviceToHost, d->stream));
+            return HM_OK;
+        }();
+    }
+    // (also after a failure: nothing of this call is in flight when it returns)
+    const hipError_t e1 = hipStreamSynchronize(d->up_stream), e2 = hipStreamSynchronize(d->stream);
+    if (rc) return rc;
+    HM_HIP(e1);
+    HM_HIP(e2);
     return HM_OK;
 }

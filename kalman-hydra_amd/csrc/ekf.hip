@@ -277,6 +277,8 @@ static const struct TuneKey {
     {"newton_fail", 0, 1, 1, TUNE_SET(newton4.fail), "must be 0 or 1"},        // tests only: the device predictions report a failed inner solve
     {"speculate", 0, 1, 1, TUNE_SET(speculate), "must be 0 or 1"},            // same results either way
     {"body_stats_cap", 1, BODY_STATS_CAP, 1, TUNE_SET(body.stats_cap), nullptr},   // tests only: frames one hm_body_stats accumulation takes
+    // entries of a column per wave of k_deep_cols (hm_deep_body_run; same bytes for every value)
+    {"deep_col_entries", DEEP_COL_ENTRIES_MIN, DEEP_COL_ENTRIES_MAX, 1, TUNE_SET(body.deep_col_entries), nullptr},
     {"body_rec_chunk", 0, INT32_MAX, 1, TUNE_SET(rec.chunk), "must be >= 0 (0: the default size)"},   // tests only: frames per chunk of the next hm_body_rec_begin
     {"rec_tp_frames", 1, REC_TP_MAX, 1, TUNE_SET(rec.tp_frames), nullptr},     // frames per workgroup of hm_body_rec_trace_products
     // frames per run of the running baseline, the residual planes, the trace maps, the surrogate reduction (same results for every value)

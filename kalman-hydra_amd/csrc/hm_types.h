@@ -353,6 +353,26 @@ __device__ __forceinline__ void d_peel_add(const int (&key)[NK], const unsigned 
     }
 }
 
+// A coordinate of a diverged state: beyond +-2^20 px (or not finite) a segment is not drawn (view_kernels.h) and a body
+// pixel reads as 0 (body_kernels.h d_body_px, deeptrace_kernels.h d_deep_px: one rule, one helper)
+#define VIEW_COORD_MAX 1048576.0
+__device__ __forceinline__ bool d_coord_ok(double a) { return a >= -VIEW_COORD_MAX && a <= VIEW_COORD_MAX; }
+
+// What hm_deep_body_* (deep.hip) borrows of a filter handle: its device and sizes and the finished body map, which stay
+// the filter handle's.  body_map_view (readout.hip) waits for the handle's helper, builds the map on first use -- that
+// ends with the handle's stream idle, so the map is whole for any stream from then on -- and changes nothing else.
+struct BodyMapView {
+    int device, W, H, N, T;
+    const int *tri;                    // triangle per pixel (W*H), -1: none
+    const double2 *bary;
+    const int4 *tidx;                  // vertex ids per triangle
+    int col_entries;                   // hm_ctx_tune "deep_col_entries"
+};
+#define DEEP_COL_ENTRIES_MIN 64        // hm_ctx_tune "deep_col_entries": one stride of a wave at least
+#define DEEP_COL_ENTRIES_MAX (1 << 30) // ... and a column's most entries at most (never split)
+struct hm_ctx;
+__attribute__((visibility("hidden"))) int body_map_view(hm_ctx *h, BodyMapView *v);
+
 // the box of the body map that the record keeps per frame (roi_kernels.h has the layout)
 struct RecBox {
     int c0, r0, bw, bh;                // the box in the frame: columns c0 .. c0 + bw - 1, rows r0 .. r0 + bh - 1

@@ -323,6 +323,15 @@ int body_map_build(hm_ctx *h)
     return HM_OK;
 }
 
+// the finished map, lent to hm_deep_body_* (hm_types.h)
+int body_map_view(hm_ctx *h, BodyMapView *v)
+{
+    HM_JOIN_LAZY(h);                             // (body_map_build creates resources: the helper must not be queueing)
+    HM_TRY(body_map_build(h));
+    *v = BodyMapView{h->device, h->W, h->H, h->N, h->T, h->body.tri, h->body.bary, h->body.tidx, h->body.deep_col_entries};
+    return HM_OK;
+}
+
 extern "C" int hm_body_map(hm_ctx_t h, int32_t *tri_of_pixel, uint32_t *tri_counts)
 {
     HM_ARG(h != nullptr, "hm_body_map: NULL handle");

@@ -10,7 +10,7 @@
 #include "hm_types.h"
 
 #define VIEW_SEG_WAVE 64               // lanes per segment: a segment's pixels are spread over one wave
-#define VIEW_COORD_MAX 1048576.0       // segments with an end point beyond +-2^20 px are not drawn (a diverged state)
+// (VIEW_COORD_MAX and d_coord_ok: hm_types.h -- segments with an end point beyond +-2^20 px are not drawn)
 
 // pixel i (0..n) of the segment (x0, y0) -> (x0 + dx, y0 + dy), n = max(|dx|, |dy|): x0 + floor((2 i dx + n) / (2 n))
 __device__ __forceinline__ long long d_floordiv(long long a, long long b)
@@ -30,8 +30,6 @@ __device__ __forceinline__ void d_segment(long long x0, long long y0, long long 
         if (x >= 0 && x < W && y >= 0 && y < H) put((int)y * W + (int)x);
     }
 }
-
-__device__ __forceinline__ bool d_coord_ok(double a) { return a >= -VIEW_COORD_MAX && a <= VIEW_COORD_MAX; }
 
 // The wireframe: the three edges of every triangle (interior edges twice, as the reference's outline buffer has them,
 // renderer.py:595-605), end points rint(vertex), one wave per segment; every covered pixel counts one (integer atomics:

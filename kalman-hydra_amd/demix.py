@@ -110,6 +110,28 @@ def solve(L, d):
     return np.ascontiguousarray(x.T)
 
 
+def solve_traces(G, A, ws, gsum, ngs):
+    """Traces given shapes, from whole numbers: G (P, P) int64 = A_q^T A_q, A (P, S, S) int64 the quantised shapes, ws and
+    gsum (F, P) Python integers -- the sums over the shapes and over the rings of every frame --, ngs (P,) the ring counts
+    (0 counted as 1).  d = (n_G ws - sum a_q gsum) / n_G, G c = d by cholesky and solve, C = c sum a_q^2 / sum a_q.
+    -> (C (F, P) float64, sa (P,) the sums of the shapes, -1), or (None, sa, the index whose pivot is not positive).
+    (hydra_mi.deeptrace runs the same step on the sums of the 16-bit frames.)"""
+    P = G.shape[0]
+    F = ws.shape[0]
+    sa = [int(A[s].sum()) for s in range(P)]
+    d = np.empty((F, P))
+    for s in range(P):
+        d[:, s] = (ngs[s] * ws[:, s] - sa[s] * gsum[:, s]).astype(np.float64) / np.float64(ngs[s])
+    L, bad = cholesky(G.astype(np.float64))
+    if L is None:
+        return None, sa, bad
+    c = solve(L, d)
+    Cn = np.empty((F, P))
+    for s in range(P):
+        Cn[:, s] = c[:, s] * (np.float64(int(G[s, s])) / np.float64(sa[s]))
+    return Cn, sa, -1
+
+
 def _worst_pair(G):
     P = G.shape[0]
     best, pair = -1.0, (0, 0)
@@ -228,21 +250,14 @@ def extract(body, points, iters=6, keep=0.25, r_disc=3.0, r_in=6.0, r_out=8.5, R
                 if (s, t) in pairs:
                     rs, cs, rt, ct = pairs[s, t]
                     G[s, t] = (A[s][rs, cs] * A[t][rt, ct]).sum()
-        sa = [int(A[s].sum()) for s in range(P)]
         ws = roi._ints(r.body_rec_weighted_sums(seeds, a_q, R))
-        d = np.empty((F, P))
-        for s in range(P):
-            d[:, s] = (ngs[s] * ws[:, s] - sa[s] * gsum[:, s]).astype(np.float64) / np.float64(ngs[s])
-        L, bad = cholesky(G.astype(np.float64))
-        if L is None:
+        Cn, sa, bad = solve_traces(G, A, ws, gsum, ngs)
+        if Cn is None:
             (s, t), o = _worst_pair(G)
             raise np.linalg.LinAlgError("demix.extract: round %d: the shapes' overlap matrix does not factor at seed %d; seeds "
                                         "%d and %d overlap most (%.6f of the geometric mean of their own sums of squares)"
                                         % (it, bad, s, t, o))
-        c = solve(L, d)
-        Cn = np.empty((F, P))
         for s in range(P):
-            Cn[:, s] = c[:, s] * (np.float64(int(G[s, s])) / np.float64(sa[s]))
             unit[s] = (np.float64(AMAX) * np.float64(sa[s])) / np.float64(int(G[s, s]))
         diff = Cn - C
         den = math.sqrt(math.fsum((C * C).ravel().tolist()))

@@ -191,4 +191,4 @@ def extract(body, points, r_disc=3.0, r_in=6.0, r_out=8.5, R=8, thr=None, alpha=
         with np.errstate(invalid="ignore", divide="ignore"):
             dff[:, s] = (F_c[:, s] - baseline(F_c[:, s], q, half)) / baseline(F_roi[:, s], q, half)
     return dict(footprints=rho, roi_labels=labels, roi_counts=counts, ring_counts=ring_counts, F_roi=F_roi, F_np=F_np,
-                dff=dff, seed_fallback=fallback, seed_sums=ss)
+                dff=dff, seed_fallback=fallback, seed_sums=ss, seeds=seeds, ring_radii=np.array([r_in, r_out], np.float64))

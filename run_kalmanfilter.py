@@ -178,6 +178,14 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      ring (deepio.DeepSource).  The states file gains depth_lo, depth_hi, depth_gamma and depth_clipped
                      (frames x 2: every frame's pixels below lo and above hi), and one warning line is printed when
                      more than ten times the share the window allows of some frame's pixels lie above hi.
+    --deep-traces    16-bit input with --rois, --demix or --points: a second pass over the file once the track and the cells
+                     are known (hydra_mi.deeptrace).  The 16-bit frames are uploaded again, only the body pixels of the ROIs,
+                     rings and shapes are pulled back through the tracked mesh, and summed at full depth: deep_F_roi,
+                     deep_F_np, deep_dff (frames x cells) by the expressions of roi_F, roi_Fnp, roi_dff, with --demix also
+                     deep_demix_c; with --points alone deep_point_means.  Where the cells are stays the 8-bit pipeline's
+                     decision.  Refused with 8-bit input, and with --stabilize or --deform-correct, which rewrite the kept
+                     record in a way the second pass does not repeat.
+    --deep-offset N  with --deep-traces: the camera's black level, subtracted from the means before dF/F (default 0).
 """
 import argparse
 import os
@@ -188,6 +196,7 @@ import numpy as np
 import hydra_mi  # noqa: F401
 from hydra_mi import cellview
 from hydra_mi import deepio
+from hydra_mi import deeptrace
 from hydra_mi import kalman
 from hydra_mi import network
 from hydra_mi import pca
@@ -315,6 +324,10 @@ def main(argv=None):
     parser.add_argument("--video-codec", default="raw", choices=("raw", "mjpeg"), help="the codec of every video written (default raw)")
     parser.add_argument("--video-quality", default=90, type=int, help="with --video-codec mjpeg: JPEG quality 1..100 (default 90)")
     add_depth_arguments(parser)
+    parser.add_argument("--deep-traces", action="store_true",
+                        help="16-bit input with --rois, --demix or --points: the cells' traces read again from the 16-bit frames (deep_* arrays)")
+    parser.add_argument("--deep-offset", type=float, default=0.0, metavar="N",
+                        help="with --deep-traces: the camera's black level, subtracted from the means (default 0)")
     args = parser.parse_args(argv)
     try:
         depth = depth_of(args)
@@ -401,10 +414,26 @@ def main(argv=None):
             parser.error("--pca needs at least one component")
     if args.pca_frames and args.pca is None:
         parser.error("--pca-frames adds the frame similarity: it needs --pca")
+    if args.deep_traces:
+        if not (args.rois or args.points is not None):
+            parser.error("--deep-traces reads cells out of the 16-bit frames: it needs --rois, --demix or --points")
+        if args.stabilize:
+            parser.error("--deep-traces reads the frames as they were tracked: --stabilize rewrites the kept record, and the "
+                         "second pass does not repeat that")
+        if args.deform_correct:
+            parser.error("--deep-traces reads the frames as they were tracked: --deform-correct rewrites the kept record, and the "
+                         "second pass does not repeat that")
+        if not np.isfinite(args.deep_offset):
+            parser.error("--deep-offset needs a finite number")
+    elif args.deep_offset != 0.0:
+        parser.error("--deep-offset goes with --deep-traces")
     if len(sys.argv) == 1 and argv is None:
         print("No command line arguments provided, using defaults")
 
     deep = deepio.load_deep(args.fn_in, depth)                 # 16-bit input: mapped through its window; None for 8-bit
+    if args.deep_traces and deep is None:
+        parser.error("--deep-traces reads 16-bit frames: %s holds none (8-bit input has no more depth than the kept record)"
+                     % args.fn_in)
     deep_stack = None                                          # the mapped file behind it, which DeepSource reads
     if deep is not None:
         deep_stack = deep["source"] if isinstance(deep["source"], deepio.TiffStack) else None
@@ -550,6 +579,18 @@ def main(argv=None):
             fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
             write_points_txt(fn_pts, res["points"])
             print("Tracked points: %s" % fn_pts)
+            # the discs of the points, read from the 16-bit frames (with ROIs the cells' traces are read instead, below)
+            if args.deep_traces and not (args.rois and body.keep) and body.L > 0 and len(states):
+                src16 = deepio.open_deep(args.fn_in)
+                try:
+                    # (state k belongs to frame k + 1, also when the run ended before the file did)
+                    dsum = deeptrace.run(body, src16, states, deeptrace.columns(body.labels, body.L), first=1)
+                finally:
+                    if isinstance(src16, deepio.TiffStack):
+                        src16.close()
+                extra.update(deep_point_means=deeptrace.point_means(dsum, body.label_counts, args.deep_offset),
+                             deep_offset=np.float64(args.deep_offset))
+                print("Full-depth traces: the discs of %d points over %d frames" % (body.L, len(states)))
     if args.stabilize and body is not None and body.keep and len(states):
         # between tracking and everything that reads the kept record: the disc read-out of --find-points, roi.extract and
         # demix.extract see the stabilised frames (what was summed while tracking -- tri_means, the summary images and the
@@ -670,6 +711,20 @@ def main(argv=None):
                          roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
             print("ROIs: %d cells, %d..%d pixels, %d kept their disc" % (len(inside), e["roi_counts"].min(),
                                                                           e["roi_counts"].max(), e["seed_fallback"].sum()))
+            if args.deep_traces:                                   # the second pass: the same cells, the camera's numbers
+                src16 = deepio.open_deep(args.fn_in)
+                try:
+                    de = deeptrace.extract(body, src16, states, e, demixed=e if args.demix else None, alpha=args.roi_alpha,
+                                           offset=args.deep_offset, first=1)    # (state k belongs to frame k + 1)
+                finally:
+                    if isinstance(src16, deepio.TiffStack):
+                        src16.close()
+                extra.update(deep_F_roi=de["deep_F_roi"], deep_F_np=de["deep_F_np"], deep_dff=de["deep_dff"],
+                             deep_offset=np.float64(args.deep_offset))
+                if args.demix:
+                    extra.update(deep_demix_c=de["deep_demix_c"])
+                print("Full-depth traces: %d cells over %d frames, F_roi %.1f..%.1f" % (
+                    len(inside), len(states), np.nanmin(de["deep_F_roi"]), np.nanmax(de["deep_F_roi"])))
             if args.events:                                        # (cell s: point inside[s], as the roi_* rows)
                 tr = np.ascontiguousarray((e["dff_demixed"] if args.demix else e["dff"]).T, np.float64)
                 fixed = lambda v, rule: np.full(len(tr), v, np.float64) if v is not None else np.array(rule, np.float64)
@@ -764,6 +819,9 @@ def main(argv=None):
             n_sv = strain.write_video(kf, st_states, capture.frames[1:1 + len(states)], args.strain_video,
                                       which=args.strain_which, gain=args.strain_gain, alpha=args.strain_alpha, **vkw)     # state k: frame k + 1
             print("Strain video: %d frames (%s) in %s" % (n_sv, args.strain_which, args.strain_video))
+    if args.deep_traces and "deep_offset" not in extra:
+        print("Full-depth traces: nothing read: no frame was tracked, no point lies inside the mesh, or the registered video "
+              "did not fit and the points were found, not given")
     np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri, **extra)
     print("Finished: %d frames, states in %s" % (len(states), args.fn_out))
     return 0
