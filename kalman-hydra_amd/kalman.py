@@ -23,19 +23,25 @@ reference's.  What changes is where the work is done:
   operator applied bar by bar), the covariance prediction a device kernel (``hm_cov_predict``).
 
 There is no CPU measurement path: ``cuda=False`` raises.
+
+The filters take every step through one object, ``state.algebra``, decided once in the constructor of ``KFState``:
+the native ``Renderer`` itself, or -- when a caller supplies its own measurement object (``renderer=``, an object with
+``measure`` and ``error``; the CPU tests of the host logic do) -- a ``kalman_host.HostAlgebra`` around it, which offers
+the same step-wise verbs in NumPy / SciPy.  What only the native path has (the fused run, the arming calls, the worker
+on the device, the chain) is asked for with ``state.native``.  The mass-spring filter's state prediction started ahead
+of the frame that needs it has one owner, ``PredictionAhead``.
 """
+import contextlib
 import ctypes
-import os
 import sys
 import time
 
 import numpy as np
-import scipy.linalg as sla
 import scipy.sparse as sp
-import scipy.sparse.linalg as spla
 
 from . import _lib
-from .renderer import DeviceCovariance, Renderer, MaskedFlow, DeviceObservation
+from .kalman_host import HostAlgebra, _mask_distance  # noqa: F401 -- (_mask_distance: read from here by the host tests)
+from .renderer import ChainedPredictionFailed, DeviceCovariance, Renderer, MaskedFlow, DeviceObservation
 
 
 class Statistics:
@@ -60,77 +66,9 @@ class Statistics:
 
 stats = Statistics()
 
-# Host BLAS is only used when a caller supplies its own measurement object (the `renderer=` seam of
-# the constructors, which the CPU tests of the host logic use); the product path does its dense
-# algebra on the device.  For that seam: a default-sized BLAS thread team on a many-core host with a
-# small CPU quota (a container, the GPU box) is slower than a handful of threads by orders of
-# magnitude, so the team is capped (HYDRA_MI_BLAS_THREADS overrides the cap).
-try:
-    from threadpoolctl import ThreadpoolController as _ThreadpoolController
-except ImportError:                                   # pragma: no cover
-    _ThreadpoolController = None
-_BLAS_THREADS = int(os.environ.get("HYDRA_MI_BLAS_THREADS", "8"))
-
-
-def _spd_factor(A):
-    """Cholesky factor of the information matrix, or an LU factor if it is not positive definite
-    (the finite-difference HTH is symmetric but only approximately positive semi-definite)."""
-    try:
-        return ("cho", sla.cho_factor(A, lower=True, check_finite=False))
-    except np.linalg.LinAlgError:
-        return ("lu", sla.lu_factor(A, check_finite=False))
-
-
-def _factor_solve(fac, b):
-    kind, f = fac
-    if kind == "cho":
-        return sla.cho_solve(f, b, check_finite=False)
-    return sla.lu_solve(f, b, check_finite=False)
-
-
-def _spd_inverse(A):
-    """inv(A) for a symmetric matrix: through the Cholesky factor when A is positive definite."""
-    try:
-        c, info = sla.lapack.dpotrf(A, lower=1, clean=0, overwrite_a=0)
-        if info == 0:
-            inv, info = sla.lapack.dpotri(c, lower=1, overwrite_c=1)
-            if info == 0:
-                low = np.tril(inv)
-                return low + np.tril(inv, -1).T
-    except Exception:
-        pass
-    return np.linalg.inv(A)
-
-
-class _blas_cap:
-    """Cap the BLAS / OpenMP pools for the host algebra of one filter step.  The pools are looked up
-    once (threadpoolctl scans the loaded libraries, ~0.5 ms); filters whose algebra runs on the
-    device (enabled=False) skip it altogether."""
-    _controller = None
-
-    def __init__(self, enabled=True):
-        self._ctx = None
-        self._enabled = enabled and _ThreadpoolController is not None
-
-    def __enter__(self):
-        if not self._enabled:
-            return
-        if _blas_cap._controller is None:
-            _blas_cap._controller = _ThreadpoolController()
-        self._ctx = _blas_cap._controller.limit(limits=_BLAS_THREADS)
-        self._ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self._ctx is not None:
-            self._ctx.__exit__(*a)
-
 
 def _log(msg):
     sys.stdout.write(msg + "\n")
-
-
-def _rows_unique(a):
-    return np.unique(np.asarray(a), axis=0)
 
 
 class KFState:
@@ -169,7 +107,7 @@ class KFState:
         # bars that no remaining face uses are dropped (:163-175)
         t = self.tri
         allbars = np.vstack((t[:, [0, 1]], t[:, [1, 2]], t[:, [0, 2]]))
-        allbars = _rows_unique(np.sort(allbars, axis=1))
+        allbars = np.unique(np.sort(allbars, axis=1), axis=0)
         have = set(map(tuple, allbars))
         sel = np.array([tuple(bar) in have for bar in np.asarray(distmesh.bars)], bool)
         distmesh.bars = np.asarray(distmesh.bars)[sel]
@@ -214,6 +152,12 @@ class KFState:
         self.renderer = renderer if renderer is not None else Renderer(
             distmesh, self._vel, flow, self.nx, im, cuda, eps_Z, eps_J, eps_M, self.labels, self.labels_hess,
             self.Q, showtracking=False, device=device)
+        # the filters' steps go through `algebra`: the native renderer itself, or the host algebra around a measurement
+        # object that only offers measure / error; `native` stands for what only the former has (the fused run, the
+        # arming calls, the worker on the device, the chain)
+        self.native = isinstance(self.renderer, Renderer)
+        self.algebra = self.renderer if self.native else HostAlgebra(self.renderer)
+        self.host_cap = contextlib.nullcontext if self.native else self.algebra.blas_cap
 
         stats.meshpts = self.N
         stats.gridsize = getattr(distmesh, "h0", 0)
@@ -367,30 +311,16 @@ class KFState:
         dt = time.time() - t0
         stats.stateupdatetc[0] += dt
         stats.stateupdatetc[1] += 1
-        # the reference splits this time between its Jacobian and Hessian passes; here it is one launch
+        self.count_renders(dt)
+        return Hz, HTH, Hzc
+
+    def count_renders(self, dt):
+        """One call of renderer.measure in the counters: the reference splits this time between its Jacobian and
+        Hessian passes; here it is one launch."""
         stats.jacobianrenderstc[0] += dt / 2
         stats.jacobianrenderstc[1] += stats.jacinc[0]
         stats.hessianrenderstc[0] += dt / 2
         stats.hessianrenderstc[1] += stats.hessincsparse[0] if self.sparse else stats.hessinc[0]
-        return Hz, HTH, Hzc
-
-    # one perturbation per render, through the fine-grained operators (slow; used by the parity tests)
-    def _jacobian(self, y_im, y_flow, y_m, deltaX=2):
-        n = self.size()
-        Hz = np.zeros((n, 1))
-        Hzc = np.zeros((n, 4))
-        self.refresh()
-        self.renderer.initjacobian(y_im, y_flow, y_m)
-        for idx in range(n):
-            for sign in (+1, -1):
-                self.X[idx, 0] += sign * deltaX
-                hz, hzc = self.renderer.jz(self)
-                self.X[idx, 0] -= sign * deltaX
-                Hz[idx, 0] += sign * hz / deltaX
-                Hzc[idx, :] += sign * hzc / deltaX
-            Hz[idx, 0] /= 2
-            Hzc[idx, :] /= 2
-        return Hz, Hzc
 
     def _jacobian_multi(self, y_im, y_flow, y_m, deltaX=2):
         """reference kalman.py:452-489: the vertices of one partition (mutually non-adjacent, so their stars do
@@ -425,18 +355,6 @@ class KFState:
         self.refresh()
         return Hz, Hzc
 
-    def _hessian_sparse(self, y_im, y_flow, y_m, deltaX=2, pattern=None):
-        n = self.size()
-        HTH = np.zeros((n, n))
-        self.refresh()
-        self.renderer.initjacobian(y_im, y_flow, y_m)
-        for i in range(n):
-            for j in range(i, n):
-                if pattern is None or pattern[i, j] == 1:
-                    HTH[i, j] = self.renderer.j(self, deltaX, i, j) / deltaX / deltaX
-                    HTH[j, i] = HTH[i, j]
-        return HTH
-
     def _hessian_sparse_multi(self, y_im, y_flow, y_m, deltaX=2):
         """reference kalman.py:539-581: per partition of vertex pairs 16 x 2 renders, sums separated by pair label
         (Renderer.j_multi -> hm_j_multi)."""
@@ -461,9 +379,6 @@ class KFState:
                                 HTH[q2, q1] = HTH[q1, q2]
         self.refresh()
         return HTH
-
-    def _hessian(self, y_im, y_flow, y_m, deltaX=2):
-        return self._hessian_sparse(y_im, y_flow, y_m, deltaX, None)
 
 
 class KalmanFilter:
@@ -515,12 +430,12 @@ class KalmanFilter:
             y_flow, y_m = obs.raw, obs
             y_flow_mask = obs.masked if maskflow is True else obs.raw
         else:
-            self.state.renderer.update_frame(y_im, y_flow, y_m)
+            self.state.algebra.update_frame(y_im, y_flow, y_m)
             y_flow_mask = MaskedFlow(y_flow, y_m) if maskflow is True else y_flow
         r = self.state.renderer
         r.frame_in_place = True          # the operators below work on the frame just uploaded: no second copy
         try:
-            with _blas_cap(enabled=not hasattr(r, "update_run")):
+            with self.state.host_cap():
                 t0 = time.time()
                 if self._compute_chained(y_im, y_flow_mask, y_m):
                     t1 = t2 = t0 + (self._chain_predict_s or 0.0)
@@ -573,10 +488,7 @@ class KalmanFilter:
         self.orig_x = st.X.copy()
         st.X = st.F.dot(st.X)
         self.pred_x = st.X.copy()
-        if hasattr(st.renderer, "cov_predict"):
-            st.W = st.renderer.cov_predict(st._W, None, None, 1.0, 0.0, st.eps_F, fetch=False)
-        else:
-            st.W = st.F.dot(st.W.dot(st.F.T)) + st.Weps
+        st.W = st.algebra.cov_predict(st._W, None, None, 1.0, 0.0, st.eps_F, fetch=False)
         stats.statepredtime[0] += time.time() - t0
 
     def projectmask(self, y_m):
@@ -585,54 +497,28 @@ class KalmanFilter:
         The signed distance is the reference's (imgproc.py:195-235): the mask's contours pruned as there (:205-228: the
         largest object and its holes of area >= 40), then the distance to the polygon through the centres of the border
         pixels of what is left, negative inside (imgproc.outline_distance; on the device csrc/project_kernels.h, k_ccl_*
-        + k_outline + k_project_mask).  Steps, step size and the stale d / index set follow the reference."""
+        + k_outline + k_project_mask).  Steps, step size and the stale d / index set follow the reference
+        (hm_project_mask; HostAlgebra.project_mask)."""
         if y_m is None:
             return
-        r = self.state.renderer
-        if hasattr(r, "project_mask"):    # the same walk on the device (hm_project_mask)
-            X, moved = r.project_mask(self.state.X, None if isinstance(y_m, DeviceObservation) else y_m)
-            if moved:
-                self.state.X = X
-            self.proj_x, self.moved = np.array(self.state.X), moved
-            return
-        if isinstance(y_m, DeviceObservation):
-            y_m = y_m.y_m_host
-        p = self.state.vertices()
-        near = ~_inside(y_m, p)           # vertices whose four surrounding pixels are not all object
-        if not near.any():
-            return                        # d <= 0 everywhere: nothing to project
-        fd = _mask_distance(y_m)
-        ddeps = 1e-1
-        p_orig = p.copy()
-        d = np.zeros(len(p))              # surely-inside vertices have d <= 0: never selected below
-        d[near] = fd(p[near])
-        ix = d > 1
-        for _ in range(10):
-            if ix.any():
-                gx = (fd(p[ix] + [ddeps, 0]) - d[ix]) / ddeps
-                gy = (fd(p[ix] + [0, ddeps]) - d[ix]) / ddeps
-                g2 = gx ** 2 + gy ** 2
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    step = np.where(g2 > 0, d[ix] / g2, 0.0)
-                p[ix] -= (step * np.vstack((gx, gy))).T
-        self.state.X[0:2 * self.N] = p.reshape(-1, 1)
-        self.state.X[2 * self.N:] += (p - p_orig).reshape(-1, 1)
+        X, moved = self.state.algebra.project_mask(self.state.X, None if isinstance(y_m, DeviceObservation) else y_m)
+        if moved:
+            self.state.X = X
+        self.proj_x, self.moved = np.array(self.state.X), moved
 
     def update(self, y_im, y_flow, y_m):
         """Single EKF step in information form (:745-761): W = inv(inv(W) + HTH), X += W Hz."""
         st = self.state
         X, W = st.X, st.W
-        if hasattr(st.renderer, "update_step"):
-            st.renderer.update_begin(W, X)
-            step, Hzc, _ = st.renderer.update_step(st, y_im, y_flow, y_m, want_error=False)   # X0 - X = 0: step = W_new Hz
-            if not np.all(np.isfinite(step)):
-                raise FloatingPointError("information matrix of the update is not positive definite")
-            Wn = st.renderer.update_cov(0)
-            st.X = X + step
-        else:
-            Hz, HTH, Hzc = st.update(y_im, y_flow, y_m)
-            Wn = _spd_inverse(_spd_inverse(W) + HTH)
-            st.X = X + Wn.dot(Hz)
+        st.algebra.update_begin(W, X)
+        t0 = time.time()
+        step, Hzc, _ = st.algebra.update_step(st, y_im, y_flow, y_m, want_error=False)   # X0 - X = 0: step = W_new Hz
+        stats.stateupdatetc[0] += time.time() - t0
+        stats.stateupdatetc[1] += 1
+        if not np.all(np.isfinite(step)):
+            raise FloatingPointError("information matrix of the update is not positive definite")
+        Wn = st.algebra.update_cov(0)
+        st.X = X + step
         st.W = Wn
         self.tv = Wn.dot(Hzc[:, 0])
         self.fv = Wn.dot(Hzc[:, 1] + Hzc[:, 2])
@@ -657,7 +543,7 @@ class IteratedKalmanFilter(KalmanFilter):
 
     def _gain(self, k):
         if self._gains is None:
-            _, g = self.state.renderer.update_tail()
+            _, g = self.state.algebra.update_tail()
             self._gains = (g[0], g[1], g[2])
         return self._gains[k]
 
@@ -670,18 +556,17 @@ class IteratedKalmanFilter(KalmanFilter):
     fv = property(lambda self: self._gain(1), lambda self, v: self._set_gain(1, v))
     mv = property(lambda self: self._gain(2), lambda self, v: self._set_gain(2, v))
 
-
     def _update_fused(self, y_im, y_flow, y_m):
         """The whole loop below in one native call (hm_update_run): same numbers, the iterate and
         the covariance stay on the device."""
         st = self.state
         t0 = time.time()
         # (the gains -- tv, fv, mv below -- are fetched when somebody reads them: the call does not wait for their kernels)
-        lazy = bool(self.lazy_gains) and hasattr(st.renderer, "update_tail")
+        lazy = bool(self.lazy_gains)
         # (an update that raises leaves no gains of an earlier frame behind: tv / fv / mv then ask update_tail(), which
         # reports that the last update failed)
         self._gains = None
-        X, info, errs, Hzc, gains, W = st.renderer.update_run(st._W, st.X, y_im, y_flow, y_m, self.nI, self.reltol, tail=not lazy)
+        X, info, errs, Hzc, gains, W = st.algebra.update_run(st._W, st.X, y_im, y_flow, y_m, self.nI, self.reltol, tail=not lazy)
         stats.stateupdatetc[0] += time.time() - t0
         stats.stateupdatetc[1] += info["niter"]
         for i, e in enumerate(errs):
@@ -711,18 +596,11 @@ class IteratedKalmanFilter(KalmanFilter):
         factorisations run on the device (hm_update_begin / _step / _cov) and only the 4N-vector
         of the step crosses PCIe per iteration."""
         st = self.state
-        if self.fused_update and hasattr(st.renderer, "update_run"):
+        if self.fused_update and st.native:
             return self._update_fused(y_im, y_flow, y_m)
-        on_device = hasattr(st.renderer, "update_step")
         X = st.X
         X_orig, X_old = X.copy(), X.copy()
-        W_old = st._W
-        if on_device:
-            st.renderer.update_begin(W_old, X_orig)
-        else:
-            W_old = st.W
-            invW_orig = _spd_inverse(W_old)
-        A = A_old = None                 # host path: information matrices of X and X_old (None = the prior)
+        st.algebra.update_begin(st._W, X_orig)
         accepted = 0                     # iterations whose state was kept
         eold = 0.0
         conv = False
@@ -732,35 +610,26 @@ class IteratedKalmanFilter(KalmanFilter):
         for i in range(self.nI):
             self._say("   IEKF K = %d" % i)
             t0 = time.time()
-            step = None
-            if on_device:
-                step, Hzc, err = st.renderer.update_step(st, y_im, y_flow, y_m)
-                if not np.all(np.isfinite(step)):
-                    # inv(W) is positive definite and HTH is a Gram matrix of the difference images
-                    # (positive semi-definite), so this only happens with non-finite inputs
-                    raise FloatingPointError("the update system inv(W) + HTH is not positive definite "
-                                             "(non-finite state, covariance or observation?)")
-                dt = time.time() - t0
-                stats.stateupdatetc[0] += dt
-                stats.stateupdatetc[1] += 1
-            else:
-                Hz, HTH, Hzc = st.update(y_im, y_flow, y_m)
-                A = invW_orig + HTH
-                step = _factor_solve(_spd_factor(A), Hz - HTH.dot(X_orig - X))
+            step, Hzc, _ = st.algebra.update_step(st, y_im, y_flow, y_m)
+            if not np.all(np.isfinite(step)):
+                # inv(W) is positive definite and HTH is a Gram matrix of the difference images
+                # (positive semi-definite), so this only happens with non-finite inputs
+                raise FloatingPointError("the update system inv(W) + HTH is not positive definite "
+                                         "(non-finite state, covariance or observation?)")
+            stats.stateupdatetc[0] += time.time() - t0
+            stats.stateupdatetc[1] += 1
             X = X_orig + step
             st.X = X
             self.niter += 1
             st.update_orientation()
             if np.any(st.ori < 0):
                 st.X = X_old
-                A = A_old
                 reverted = True
                 self._say("** Mesh inconsistent ** Reverting to last good state and continuing")
                 break
-            if on_device:                # error of the new iterate came back with the step
-                e_im, e_fx, e_fy, e_m = err
-            else:
-                e_im, e_fx, e_fy, e_m, _, _ = st.renderer.error(st, y_im, y_flow, y_m, want_flow=False)
+            # the error of the iterate just stepped to: natively it came back with the step; a measurement object on the
+            # host is asked only now -- an iterate that is reverted is never rendered
+            e_im, e_fx, e_fy, e_m = st.algebra.step_error(st, y_im, y_flow, y_m)
             enew = float(np.sqrt(float(e_im) ** 2 + e_fx ** 2 + e_fy ** 2 + float(e_m) ** 2))
             self._say("-- e_im: %d, e_fx: %d, e_fy: %d, e_m: %d" % (e_im, e_fx, e_fy, e_m))
             accepted += 1
@@ -769,21 +638,134 @@ class IteratedKalmanFilter(KalmanFilter):
                 break
             eold = enew
             X_old = X.copy()
-            A_old = A
         stats.niter += self.niter
-        if on_device:
-            if reverted:
-                st.W = st.renderer.update_cov(-1 if accepted == 0 else 1, fetch=False)
-            else:
-                st.W = st.renderer.update_cov(-1 if self.niter == 0 else 0, fetch=False)
+        # the covariance of the state that is kept: of the last step (0), of the one before (1) or the prior (-1)
+        if reverted:
+            st.W = st.algebra.update_cov(-1 if accepted == 0 else 1, fetch=False)
         else:
-            st.W = W_old if A is None else _spd_inverse(A)
+            st.W = st.algebra.update_cov(-1 if self.niter == 0 else 0, fetch=False)
         self.reverted = reverted
         Wd = st.W
         self.tv = Wd.dot(Hzc[:, 0])
         self.fv = Wd.dot(Hzc[:, 1] + Hzc[:, 2])
         self.mv = Wd.dot(Hzc[:, 3])
         self.converged = conv
+
+
+class PredictionAhead:
+    """The state prediction of the mass-spring filter `kf` started ahead of the frame that needs it: the hm_ms_worker
+    handle (a host thread; attached to the renderer, its jobs run as one launch on the device), the inputs the job in
+    flight was started from, and what the fused update was armed with."""
+
+    def __init__(self, kf):
+        self._kf = kf
+        self._worker = None
+        self.attached = None             # the worker is attached to the renderer's device (None: not yet decided)
+        self._job = None                 # (X, bars, l0, parameters) the job in flight was started from
+        self._armed = None               # (bars, l0, parameters) the running update starts a job with (hm_update_arm_newton)
+        self.cov_armed = False           # ... and it queues the covariance half of the prediction as well (hm_update_arm_cov)
+
+    def inputs(self):
+        """(bars, l0, parameters) a job would be started from now."""
+        kf = self._kf
+        return (np.ascontiguousarray(kf._bars, np.int32).copy(), np.ascontiguousarray(kf.state.l0[:, 0], np.float64).copy(),
+                (float(kf.kappa), float(kf.M), float(kf.deltat), int(kf.maxiter), float(kf.tol)))
+
+    def _state(self):
+        return np.ascontiguousarray(self._kf.state.X.reshape(-1), np.float64).copy()
+
+    def worker(self):
+        st = self._kf.state
+        if self._worker is None:
+            w = ctypes.c_void_p()
+            _lib.check(_lib.lib().hm_ms_worker_create(ctypes.byref(w)), "hm_ms_worker_create")
+            self._worker = w
+            self.attached = None
+        dev = bool(self._kf.newton_on_device) and st.native
+        if dev != self.attached:
+            if st.native:
+                st.algebra.attach_worker(self._worker, dev)
+            self.attached = dev
+        return self._worker
+
+    def start(self):
+        """Start the prediction from the filter's state, springs and parameters as they are now (hm_ms_newton_start)."""
+        X = self._state()
+        bars, l0, par = self.inputs()
+        _lib.check(_lib.lib().hm_ms_newton_start(self.worker(), int(self._kf.state.N), int(bars.shape[0]), _lib.ptr(bars),
+                                                 _lib.ptr(l0), par[0], par[1], par[2], par[3], par[4], _lib.ptr(X)),
+                   "hm_ms_newton_start")
+        self._job = (X, bars, l0, par)
+
+    def arm(self, cov):
+        """Before a fused update: hm_update_run starts the job itself the moment the state it ends with is known, and
+        (cov) queues the covariance half of the next prediction behind its own launches."""
+        r = self._kf.state.algebra
+        bars, l0, par = self.inputs()
+        r.arm_newton(self.worker(), bars, l0, *par)
+        self._armed = (bars, l0, par)
+        if cov:
+            r.arm_cov(self._kf.state.eps_F)
+            self.cov_armed = True
+
+    def adopt(self):
+        """After the update that was armed: the job it started is the one in flight, from the state it ended with.
+        False: the update was not armed."""
+        if self._armed is None:
+            return False
+        self._job = (self._state(),) + self._armed
+        self._armed = None
+        return True
+
+    def matches(self):
+        """Are the state, the springs and the parameters still what the job in flight was started from?"""
+        if self._job is None:
+            return False
+        kf = self._kf
+        X0, bars0, l00, par0 = self._job
+        return (np.array_equal(X0, np.asarray(kf.state.X, np.float64).reshape(-1)) and np.array_equal(bars0, kf._bars)
+                and np.array_equal(l00, kf.state.l0[:, 0])
+                and par0 == (float(kf.kappa), float(kf.M), float(kf.deltat), int(kf.maxiter), float(kf.tol)))
+
+    def finish(self):
+        """Wait for the job in flight -> (X predicted [4N], Newton iterations)."""
+        out = np.empty(4 * self._kf.state.N)
+        its = ctypes.c_int()
+        self._job = None
+        _lib.check(_lib.lib().hm_ms_newton_finish(self._worker, _lib.ptr(out), ctypes.byref(its)), "hm_ms_newton_finish")
+        return out, its.value
+
+    def take(self):
+        """The result of the job in flight if it still matches the filter; else None (it is waited for and dropped)."""
+        if self._job is None:
+            return None
+        same = self.matches()
+        res = self.finish()
+        return res if same else None
+
+    def release(self):
+        """The job in flight is finished by someone else (the chained update, on the device)."""
+        self._job = None
+
+    def drain(self):
+        """After an update that failed: whether the job it was armed with was started is not known -- wait for it if it was."""
+        self.cov_armed = False
+        if self._armed is None:
+            return
+        self._armed = None
+        out = np.empty(4 * self._kf.state.N)
+        rc = _lib.lib().hm_ms_newton_finish(self._worker, _lib.ptr(out), None)
+        if rc != _lib.HM_ERR_STATE:          # (HM_ERR_STATE: this worker has never been given a job)
+            _lib.check(rc, "hm_ms_newton_finish")
+
+    def close(self):
+        if self._worker is not None:
+            st = self._kf.state
+            if st.native:
+                st.algebra.detach_worker(self._worker)
+            _lib.lib().hm_ms_worker_destroy(self._worker)
+            self._worker = None
+            self._job = self._armed = None
 
 
 class IteratedMSKalmanFilter(IteratedKalmanFilter):
@@ -800,7 +782,7 @@ class IteratedMSKalmanFilter(IteratedKalmanFilter):
         self.tol = 1e-4
         self.force = lambda l1, l2: -self.kappa * (l1 - l2)
         self.state.setforce(self.force)
-        self._bar_pattern()
+        self._bars = np.asarray(self.distmesh.bars, np.int64)
         # True: hm_ms_predict, the whole prediction in one native call with the Newton iterations of the state as a
         # single workgroup on the device.  Measured at 201 vertices (tools/predict_time.py): 1.21 ms against 0.68 ms
         # for the default below -- ~500 dependent conjugate-gradient steps of a 402-unknown system are ~2 us each
@@ -814,41 +796,17 @@ class IteratedMSKalmanFilter(IteratedKalmanFilter):
         # Weps at the state it ends with, and the factorisation of the result -- behind its own last launches
         # (hm_update_arm_cov); predict() takes it if the state, the springs and the parameters are still the same.
         self.cov_ahead = True
-        self._cov_armed = False
         # True: the prediction started ahead runs as one launch on the device (hm_ms_worker_attach: k_ms_newton4, four
         # waves, a vertex per lane) instead of on the worker's host thread, when the mesh fits the kernel (<= 256
         # vertices); the two agree to rounding
         self.newton_on_device = True
         # True: compute() chains predict -> projectmask -> update on the device when it can (_compute_chained)
         self.chain = True
-        self._worker_dev = None
-        self._worker, self._ahead, self._armed = None, None, None
-
-    def _jacobian(self):
-        """d f / d y of the spring force at the current vertices (:865-902), sparse.
-
-        The reference forms  -K [diag(kappa (1 - l0/l)) x I2] K^T - K diag(d) [dk x 1_2]  with
-        dk_i = kappa l0_i / l_i^3 * d_i^T (K^T)_i and d = K^T y, as dense products.  Bar i between
-        vertices a and b contributes the 2x2 block  B_i = k_i I + c_i d_i d_i^T  (k_i = kappa (1 - l0_i/l_i),
-        c_i = kappa l0_i / l_i^3) with sign - on (a,a), (b,b) and + on (a,b), (b,a); assembled here
-        directly from those blocks."""
-        st = self.state
-        bars = self._bars
-        y = st.vertices()
-        d = y[bars[:, 0]] - y[bars[:, 1]]
-        l = np.sqrt((d * d).sum(axis=1))
-        l0 = st.l0[:, 0]
-        k = self.kappa * (1 - l0 / l)
-        c = self.kappa * l0 / l ** 3
-        Bm = c[:, None, None] * (d[:, :, None] * d[:, None, :])
-        Bm[:, 0, 0] += k
-        Bm[:, 1, 1] += k
-        vals = np.concatenate((-Bm, -Bm, Bm, Bm)).reshape(-1)
-        n2 = 2 * st.N
-        return sp.csr_matrix((vals, (self._jrows, self._jcols)), shape=(n2, n2))
+        self._ahead = PredictionAhead(self)
 
     def _spring_blocks(self):
-        """Per spring the symmetric block (Bxx, Bxy, Byy) of dfdy at the current vertices (see _jacobian)."""
+        """Per spring the symmetric block (Bxx, Bxy, Byy) of dfdy at the current vertices: B = k I + c d d^T with
+        k = kappa (1 - l0/l), c = kappa l0 / l^3 (reference kalman.py:865-902; kalman_host._spring_jacobian assembles them)."""
         st = self.state
         y = st.vertices()
         d = y[self._bars[:, 0]] - y[self._bars[:, 1]]
@@ -858,109 +816,69 @@ class IteratedMSKalmanFilter(IteratedKalmanFilter):
         c = self.kappa * l0 / (l * l * l)           # (the operations of the native spring_blocks, csrc/ctx.h: same bits)
         return np.column_stack((k + c * d[:, 0] * d[:, 0], c * d[:, 0] * d[:, 1], k + c * d[:, 1] * d[:, 1]))
 
-    def _bar_pattern(self):
-        """Row / column indices of the four 2x2 blocks every bar contributes to dfdy."""
-        bars = np.asarray(self.distmesh.bars, np.int64)
-        self._bars = bars
-        a, b = bars[:, 0], bars[:, 1]
-        al = np.arange(2)
-        rows, cols = [], []
-        for (p, q) in ((a, a), (b, b), (a, b), (b, a)):
-            rows.append((2 * p[:, None, None] + al[None, :, None]) + 0 * al[None, None, :])
-            cols.append((2 * q[:, None, None] + al[None, None, :]) + 0 * al[None, :, None])
-        self._jrows = np.concatenate(rows).reshape(-1)
-        self._jcols = np.concatenate(cols).reshape(-1)
-
-    def _dfdx(self):
-        n2 = 2 * self.state.N
-        e = sp.eye(n2, format="csr")
-        A = self._jacobian() * (self.deltat / self.M)
-        return sp.bmat([[e, self.deltat * e], [A, e]], format="csr")
-
-    def _dgdx(self):
-        n2 = 2 * self.state.N
-        e = sp.eye(n2, format="csr")
-        A = self._jacobian() * (self.deltat / self.M)
-        return sp.bmat([[e, -self.deltat * e], [-A, e]], format="csc")
-
     def predict(self):
         t0 = time.time()
         st = self.state
         self.orig_x = st.X.copy()
         # F = [[I, dt I], [dt/M dfdy, I]] at the state before the step (:856)
-        if self.device_predict and hasattr(st.renderer, "ms_predict") and isinstance(st._W, DeviceCovariance):
-            self._take_ahead()               # a prediction started ahead on the host is not what this path uses
+        if self.device_predict and isinstance(st._W, DeviceCovariance):
+            self._ahead.take()               # a prediction started ahead on the host is not what this path uses
             # the whole prediction in one native call (hm_ms_predict): the Newton iterations of the state as one
             # workgroup on a second stream while the covariance prediction and, for the fused update, the
             # factorisation / inversion it starts with are queued on the filter's stream
-            st.X, self.newton_iterations, st.W = st.renderer.ms_predict(
+            st.X, self.newton_iterations, st.W = st.algebra.ms_predict(
                 st._W, st.X, self._bars, st.l0[:, 0], self.kappa, self.M, self.deltat, self.maxiter, self.tol, st.eps_F,
                 prefactor=self.fused_update)
-        elif hasattr(st.renderer, "cov_predict"):
+        else:
             # the covariance half first: it is queued on the device (prediction, then the
             # factorisation and inversion the update starts with) and runs while the host works
             # through the Newton iterations of the state
-            taken = None
-            if self._cov_armed and hasattr(st.renderer, "predict_take"):
-                # the update of the last frame queued exactly this behind its own launches (hm_update_arm_cov)
-                taken = st.renderer.predict_take(st._W, st.X, self._bars, st.l0[:, 0], self.kappa, self.deltat,
-                                                 self.deltat / self.M, st.eps_F)
-            self._cov_armed = False
-            if taken is not None:
-                st.W = taken
-            else:
-                blocks = self._spring_blocks()
-                st.W = st.renderer.cov_predict(st._W, self._bars, blocks, self.deltat, self.deltat / self.M, st.eps_F,
-                                               fetch=False)
-                if self.fused_update and hasattr(st.renderer, "update_prefactor"):
-                    st.renderer.update_prefactor(st._W)
+            self._predict_cov()
             self._newton()
-        else:
-            A = self._jacobian() * (self.deltat / self.M)
-            self._newton()
-            st.W = _fwft(A, self.deltat, st.W) + st.Weps
         self.pred_x = st.X.copy()
         stats.statepredtime[0] += time.time() - t0
+
+    def _predict_cov(self):
+        """The covariance half of the prediction, F W F^T + Weps at the state before the step: what the update of the
+        last frame queued behind its own launches (hm_update_arm_cov), if it was made from exactly this state, else
+        cov_predict now -- and, for the fused update, the factorisation / inversion it starts with (update_prefactor)."""
+        st = self.state
+        taken = None
+        if self._ahead.cov_armed:
+            taken = st.algebra.predict_take(st._W, st.X, self._bars, st.l0[:, 0], self.kappa, self.deltat,
+                                            self.deltat / self.M, st.eps_F)
+        self._ahead.cov_armed = False
+        if taken is not None:
+            st.W = taken
+        else:
+            blocks = self._spring_blocks()
+            st.W = st.algebra.cov_predict(st._W, self._bars, blocks, self.deltat, self.deltat / self.M, st.eps_F, fetch=False)
+            if self.fused_update and st.native:
+                st.algebra.update_prefactor(st._W)
 
     def _compute_chained(self, y_im, y_flow, y_m):
         """predict -> projectmask -> update (reference kalman.py:676-700) without the host between them: the state
         prediction started ahead on the device is still in flight or has just ended, projectmask of its result is queued
         behind it (hm_chain_project), the update takes the projected state from device memory as its prior mean and reports
         what the two kernels found (predicted / projected state, Newton iterations) with its own results.  The covariance
-        half of predict() is what it always is here (predict_take / cov_predict).  Same numbers as the three steps; taken
+        half of predict() is what it always is here (_predict_cov).  Same numbers as the three steps; taken
         when every precondition of theirs holds: fused update, prediction started ahead on the device from exactly the
         current state, springs and parameters, mask of the observation resident on the device.  chain = False switches it
         off."""
         st = self.state
-        r = st.renderer
+        ahead = self._ahead
         if not (self.chain and self.fused_update and self.predict_ahead and self.newton_on_device and not self.device_predict
-                and self._ahead is not None and self._worker_dev and isinstance(y_m, DeviceObservation)
-                and hasattr(r, "chain_project") and isinstance(st._W, DeviceCovariance)):
-            return False
-        X0, bars0, l00, par0 = self._ahead
-        if not (np.array_equal(X0, np.asarray(st.X, np.float64).reshape(-1)) and np.array_equal(bars0, self._bars)
-                and np.array_equal(l00, st.l0[:, 0])
-                and par0 == (float(self.kappa), float(self.M), float(self.deltat), int(self.maxiter), float(self.tol))):
+                and ahead.attached and isinstance(y_m, DeviceObservation)
+                and isinstance(st._W, DeviceCovariance) and ahead.matches()):
             return False
         t0 = time.time()
-        if not r.chain_project():            # nothing in flight after all
+        if not st.algebra.chain_project():   # nothing in flight after all
             return False
         self.orig_x = st.X.copy()
-        # covariance half of predict(), as there
-        taken = None
-        if self._cov_armed and hasattr(r, "predict_take"):
-            taken = r.predict_take(st._W, st.X, self._bars, st.l0[:, 0], self.kappa, self.deltat, self.deltat / self.M, st.eps_F)
-        self._cov_armed = False
-        if taken is not None:
-            st.W = taken
-        else:
-            st.W = r.cov_predict(st._W, self._bars, self._spring_blocks(), self.deltat, self.deltat / self.M, st.eps_F, fetch=False)
-            if hasattr(r, "update_prefactor"):
-                r.update_prefactor(st._W)
-        self._ahead = None
+        self._predict_cov()
+        ahead.release()
         self._chain_predict_s = time.time() - t0
         stats.statepredtime[0] += self._chain_predict_s
-        from .renderer import ChainedPredictionFailed
         try:
             self.update(y_im, y_flow, y_m)
         except ChainedPredictionFailed:
@@ -971,52 +889,24 @@ class IteratedMSKalmanFilter(IteratedKalmanFilter):
             self.projectmask(y_m)
             self.update(y_im, y_flow, y_m)
             return True
-        pred, proj, its, moved = r.chain_states()
+        pred, proj, its, moved = st.algebra.chain_states()
         self.pred_x = pred.reshape(-1, 1)
         self.proj_x = proj.reshape(-1, 1)
         self.newton_iterations = its
         self.moved = moved
         return True
 
-    def _ahead_inputs(self):
-        st = self.state
-        return (np.ascontiguousarray(self._bars, np.int32).copy(), np.ascontiguousarray(st.l0[:, 0], np.float64).copy(),
-                (float(self.kappa), float(self.M), float(self.deltat), int(self.maxiter), float(self.tol)))
-
-    def _get_worker(self):
-        if self._worker is None:
-            w = ctypes.c_void_p()
-            _lib.check(_lib.lib().hm_ms_worker_create(ctypes.byref(w)), "hm_ms_worker_create")
-            self._worker = w
-            self._worker_dev = None
-        dev = bool(self.newton_on_device) and hasattr(self.state.renderer, "attach_worker")
-        if dev != self._worker_dev:
-            if hasattr(self.state.renderer, "attach_worker"):
-                self.state.renderer.attach_worker(self._worker, dev)
-            self._worker_dev = dev
-        return self._worker
-
     def _update_fused(self, y_im, y_flow, y_m):
         """hm_update_run, armed (hm_update_arm_newton) to start the next frame's state prediction on the worker thread
         the moment the state it ends with is known -- before the covariance of that state is formed and fetched."""
-        r = self.state.renderer
-        if self.predict_ahead and not self.device_predict and hasattr(r, "arm_newton"):
-            bars, l0, par = self._ahead_inputs()
-            r.arm_newton(self._get_worker(), bars, l0, *par)
-            self._armed = (bars, l0, par)
-            if self.cov_ahead and hasattr(r, "arm_cov"):
-                r.arm_cov(self.state.eps_F)
-                self._cov_armed = True
-        if getattr(y_m, "next_mask", None) and hasattr(r, "arm_mask"):
-            r.arm_mask(y_m.next_mask)        # the next frame's outline: queued when this update has its final state
+        if self.predict_ahead and not self.device_predict:
+            self._ahead.arm(cov=self.cov_ahead)
+        if getattr(y_m, "next_mask", None):
+            self.state.algebra.arm_mask(y_m.next_mask)   # the next frame's outline: queued when this update has its final state
         try:
             IteratedKalmanFilter._update_fused(self, y_im, y_flow, y_m)
         except Exception:
-            self._cov_armed = False
-            if self._armed is not None:          # whether the job was started is not known: wait for it if it was
-                self._armed = None
-                tmp = np.empty(4 * self.state.N)
-                _lib.lib().hm_ms_newton_finish(self._worker, _lib.ptr(tmp), None)
+            self._ahead.drain()
             raise
 
     def _after_update(self):
@@ -1024,44 +914,13 @@ class IteratedMSKalmanFilter(IteratedKalmanFilter):
         (started by hm_update_run itself when armed, else here by hm_ms_newton_start) beside the end of this frame
         on the device and the caller's work between frames.  predict() takes the result if the state is still the
         one it was started from."""
-        if not self.predict_ahead or (self.device_predict and self._armed is None):
-            return
-        st = self.state
-        X = np.ascontiguousarray(st.X.reshape(-1), np.float64).copy()
-        if self._armed is not None:
-            bars, l0, par = self._armed
-            self._armed = None
-        else:
-            bars, l0, par = self._ahead_inputs()
-            _lib.check(_lib.lib().hm_ms_newton_start(self._get_worker(), int(st.N), int(bars.shape[0]), _lib.ptr(bars),
-                                                     _lib.ptr(l0), par[0], par[1], par[2], par[3], par[4], _lib.ptr(X)),
-                       "hm_ms_newton_start")
-        self._ahead = (X, bars, l0, par)
-
-    def _take_ahead(self):
-        """The prediction started by _after_update, if its inputs are what _newton would use now; else None (its
-        result is waited for and dropped)."""
-        if self._ahead is None:
-            return None
-        X0, bars0, l00, par0 = self._ahead
-        self._ahead = None
-        st = self.state
-        out = np.empty_like(X0)
-        its = ctypes.c_int()
-        _lib.check(_lib.lib().hm_ms_newton_finish(self._worker, _lib.ptr(out), ctypes.byref(its)), "hm_ms_newton_finish")
-        same = (np.array_equal(X0, np.asarray(st.X, np.float64).reshape(-1)) and np.array_equal(bars0, self._bars)
-                and np.array_equal(l00, st.l0[:, 0])
-                and par0 == (float(self.kappa), float(self.M), float(self.deltat), int(self.maxiter), float(self.tol)))
-        return (out, its.value) if same else None
+        if self.predict_ahead and not self._ahead.adopt() and not self.device_predict:
+            self._ahead.start()
 
     def close(self):
-        if getattr(self, "_worker", None) is not None:
-            r = getattr(getattr(self, "state", None), "renderer", None)
-            if r is not None and hasattr(r, "detach_worker"):
-                r.detach_worker(self._worker)
-            _lib.lib().hm_ms_worker_destroy(self._worker)
-            self._worker = None
-            self._ahead = None
+        ahead = getattr(self, "_ahead", None)
+        if ahead is not None:
+            ahead.close()
         KalmanFilter.close(self)
 
     def __del__(self):
@@ -1075,91 +934,17 @@ class IteratedMSKalmanFilter(IteratedKalmanFilter):
         code in libhydra_mi.so (csrc/predict.cpp: block-eliminated 2N x 2N system, spring operator
         applied bar by bar, conjugate gradients)."""
         st = self.state
-        ahead = self._take_ahead()
-        if ahead is not None:
-            self.newton_iterations = ahead[1]
-            st.X = ahead[0].reshape(-1, 1)
-            return
-        X = np.ascontiguousarray(st.X.reshape(-1), np.float64).copy()
-        bars = np.ascontiguousarray(self._bars, np.int32)
-        l0 = np.ascontiguousarray(st.l0[:, 0], np.float64)
-        its = ctypes.c_int()
-        if self.newton_on_device and hasattr(st.renderer, "attach_worker"):
+        res = self._ahead.take()
+        if res is None and self.newton_on_device and st.native:
             # the same launch a prediction started ahead would have been: the same bits with and without predict_ahead
-            w = self._get_worker()
-            L = _lib.lib()
-            _lib.check(L.hm_ms_newton_start(w, int(st.N), int(bars.shape[0]), _lib.ptr(bars), _lib.ptr(l0), float(self.kappa),
-                                            float(self.M), float(self.deltat), int(self.maxiter), float(self.tol), _lib.ptr(X)),
-                       "hm_ms_newton_start")
-            _lib.check(L.hm_ms_newton_finish(w, _lib.ptr(X), ctypes.byref(its)), "hm_ms_newton_finish")
-            self.newton_iterations = its.value
-            st.X = X.reshape(-1, 1)
-            return
-        _lib.check(_lib.lib().hm_ms_newton(int(st.N), int(bars.shape[0]), _lib.ptr(bars), _lib.ptr(l0),
-                                           float(self.kappa), float(self.M), float(self.deltat), int(self.maxiter),
-                                           float(self.tol), _lib.ptr(X), ctypes.byref(its)), "hm_ms_newton")
-        self.newton_iterations = its.value
-        st.X = X.reshape(-1, 1)
-
-
-def _solve_near_identity(S, b):
-    """Solve S s = b for S = I - dt^2/M dfdy: symmetric, eigenvalues within a few percent of 1
-    (dt^2 = 0.0025 times a spring Jacobian of norm ~ 2 x vertex degree), so conjugate gradients
-    reach the rounding floor in about ten sparse products; a sparse direct solve takes over if
-    they do not."""
-    b = np.asarray(b, np.float64).reshape(-1)
-    bn = np.linalg.norm(b)
-    if bn == 0.0:
-        return np.zeros((b.size, 1))
-    x = b.copy()                                   # S ~ I: b is already a good guess
-    r = b - S.dot(x)
-    p = r.copy()
-    rs = float(r.dot(r))
-    for _ in range(60):
-        if np.sqrt(rs) <= 1e-15 * bn:
-            return x.reshape(-1, 1)
-        Sp = S.dot(p)
-        alpha = rs / float(p.dot(Sp))
-        x += alpha * p
-        r -= alpha * Sp
-        rs_new = float(r.dot(r))
-        p = r + (rs_new / rs) * p
-        rs = rs_new
-    if np.sqrt(rs) <= 1e-13 * bn:
-        return x.reshape(-1, 1)
-    return spla.spsolve(S.tocsc(), b).reshape(-1, 1)
-
-
-def _fwft(A, a, W):
-    """F W F^T for F = [[I, a I], [A, I]] with A sparse (2N x 2N), by blocks."""
-    n2 = A.shape[0]
-    W11, W12, W21, W22 = W[:n2, :n2], W[:n2, n2:], W[n2:, :n2], W[n2:, n2:]
-    P11 = W11 + a * W21
-    P12 = W12 + a * W22
-    P21 = A.dot(np.ascontiguousarray(W11)) + W21
-    P22 = A.dot(np.ascontiguousarray(W12)) + W22
-    out = np.empty_like(W)
-    out[:n2, :n2] = P11 + a * P12
-    out[:n2, n2:] = A.dot(np.ascontiguousarray(P11.T)).T + P12
-    out[n2:, :n2] = P21 + a * P22
-    out[n2:, n2:] = A.dot(np.ascontiguousarray(P21.T)).T + P22
-    return out
-
-
-def _inside(y_m, p):
-    """Per vertex: do the four pixels around it all belong to the mask (then its distance is <= 0)."""
-    m = np.asarray(y_m)
-    H, W = m.shape
-    x0 = np.floor(p[:, 0]).astype(int)
-    y0 = np.floor(p[:, 1]).astype(int)
-    ok = (x0 >= 0) & (y0 >= 0) & (x0 + 1 < W) & (y0 + 1 < H)
-    xs, ys = np.clip(x0, 0, W - 2), np.clip(y0, 0, H - 2)
-    return ok & (m[ys, xs] > 0.5) & (m[ys, xs + 1] > 0.5) & (m[ys + 1, xs] > 0.5) & (m[ys + 1, xs + 1] > 0.5)
-
-
-def _mask_distance(y_m):
-    """Signed distance to the object's outline: positive outside the mask, negative inside -- the reference's fd
-    (imgproc.py:195-235: -cv2.pointPolygonTest of the contour through the object's border pixels), restated in
-    imgproc.outline_distance; what hm_project_mask evaluates on the device."""
-    from .imgproc import outline_distance
-    return outline_distance(y_m)
+            self._ahead.start()
+            res = self._ahead.finish()
+        if res is None:
+            X = np.ascontiguousarray(st.X.reshape(-1), np.float64).copy()
+            bars, l0, par = self._ahead.inputs()
+            its = ctypes.c_int()
+            _lib.check(_lib.lib().hm_ms_newton(int(st.N), int(bars.shape[0]), _lib.ptr(bars), _lib.ptr(l0), par[0], par[1],
+                                               par[2], par[3], par[4], _lib.ptr(X), ctypes.byref(its)), "hm_ms_newton")
+            res = X, its.value
+        self.newton_iterations = res[1]
+        st.X = res[0].reshape(-1, 1)

@@ -83,6 +83,7 @@ class Renderer(Readout, Record):
                 _lib.check(L.hm_ctx_tune(h, k.strip().encode(), int(v)), "hm_ctx_tune")
         self.frame_in_place = False             # set by KalmanFilter.compute() while the frame it uploaded is current
         self._cov_serial = 0                    # names the covariance resident on the device (DeviceCovariance)
+        self._step_err = None                   # the error sums the last update_step brought back (step_error)
         self.current_frame = tex
         self.current_flowx, self.current_flowy = flow[:, :, 0], flow[:, :, 1]
 
@@ -459,7 +460,14 @@ class Renderer(Readout, Record):
                                              _lib.ptr(step), _lib.ptr(Hzc), err if want_error else None),
                    "hm_update_step")
         e = (int(err[0]), err[1], err[2], int(err[3])) if want_error else None
+        self._step_err = e
         return step.reshape(-1, 1), Hzc, e
+
+    def step_error(self, state, y_im, y_flow, y_m):
+        """(e_im, e_fx, e_fy, e_m) of the iterate the last update_step stepped to: what came back with that step."""
+        if self._step_err is None:
+            raise RuntimeError("step_error: the last update_step was not asked for the error of its iterate")
+        return self._step_err
 
     def update_cov(self, which=0, fetch=True):
         """hm_update_cov: covariance of the last step (0), of the one before (1) or the prior (-1)."""
