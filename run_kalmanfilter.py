@@ -188,26 +188,15 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
     --deep-offset N  with --deep-traces: the camera's black level, subtracted from the means before dF/F (default 0).
 """
 import argparse
+import contextlib
 import os
 import sys
 
 import numpy as np
 
 import hydra_mi  # noqa: F401
-from hydra_mi import cellview
-from hydra_mi import deepio
-from hydra_mi import deeptrace
-from hydra_mi import kalman
-from hydra_mi import network
-from hydra_mi import pca
-from hydra_mi import demix
-from hydra_mi import residual
-from hydra_mi import deform
-from hydra_mi import detrend
-from hydra_mi import events
-from hydra_mi import roi
-from hydra_mi import stabilize
-from hydra_mi import strain
+from hydra_mi import (cellview, deepio, deeptrace, deform, demix, detrend, events, kalman, network, pca, residual, roi,
+                      stabilize, strain)
 from hydra_mi.body import (BodyReadout, read_out, read_out_recorded, read_points_csv, record_bytes, write_points_csv,
                            write_points_txt)
 from hydra_mi.distmesh_dyn import DistMesh
@@ -230,7 +219,7 @@ def depth_of(args):
     return deepio.depth_option(args.depth_range, args.depth_percentiles, args.depth_gamma)
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument("fn_in", default="./video/johntest_brightcontrast_short.npy", nargs="?",
                         help="input video file (.npy/.npz, frames x H x W[ x 3], uint8)")
@@ -328,7 +317,12 @@ def main(argv=None):
                         help="16-bit input with --rois, --demix or --points: the cells' traces read again from the 16-bit frames (deep_* arrays)")
     parser.add_argument("--deep-offset", type=float, default=0.0, metavar="N",
                         help="with --deep-traces: the camera's black level, subtracted from the means (default 0)")
-    args = parser.parse_args(argv)
+    return parser
+
+
+def check_args(parser, args):
+    """Every refusal that needs no file, in this order (where two apply, the first is the one the user reads), and the
+    implications: --find-more implies --demix implies --rois.  -> the derived options, the keywords of Run."""
     try:
         depth = depth_of(args)
     except ValueError as exc:
@@ -427,19 +421,59 @@ def main(argv=None):
             parser.error("--deep-offset needs a finite number")
     elif args.deep_offset != 0.0:
         parser.error("--deep-offset goes with --deep-traces")
-    if len(sys.argv) == 1 and argv is None:
-        print("No command line arguments provided, using defaults")
+    return dict(depth=depth, vopts=vopts, vkw=vkw, gopts=gopts, keep_record=keep_record)
 
-    deep = deepio.load_deep(args.fn_in, depth)                 # 16-bit input: mapped through its window; None for 8-bit
+
+class Run:
+    """One run of the command: what every stage takes and fills (DESIGN.md §26 says which stage sets what)."""
+
+    def __init__(self, parser, args, depth, vopts, vkw, gopts, keep_record):
+        self.parser, self.args, self.depth = parser, args, depth
+        self.vopts, self.vkw, self.gopts, self.keep_record = vopts, vkw, gopts, keep_record
+        self.find = args.find_points is not None
+        self.deep = self.deep_stack = self.video = self.reg_video = self.points = self.kf = self.body = self.sm = None
+        self.states, self.errors, self.extra = [], [], {}       # extra: the arrays of the states file after X, err, p, t
+        self.found = self.scores = self.more = self.e = None    # the points found, their scores, what --find-more found, the cells
+        self.inside = []                                        # the indices of the points inside the mesh: cell s is point inside[s]
+        self.cv_cells = self.cv_levels = self.cv_points = None  # what --cells-video draws when there are cells
+        self.st_cells = self.st_dff = None                      # what --strain reads the tissue under: the cells' labels, their dF/F
+
+    kept = property(lambda self: self.body is not None and self.body.keep)      # the registered video is kept on the device
+    record_ready = property(lambda self: self.kept and len(self.states) > 0)    # ... and holds a frame
+    pts = property(lambda self: self.found if self.find else self.points)       # the points found, else those given, else None
+    dff = property(lambda self: self.e["dff_demixed"] if self.args.demix else self.e["dff"])    # the cells' dF/F, frames x cells
+    tracked_frames = property(lambda self: self.capture.frames[1:1 + len(self.states)])         # state k: frame k + 1
+
+    @contextlib.contextmanager
+    def second_pass(self):
+        """the 16-bit frames of the input once more (--deep-traces); a TIFF stack is closed after it"""
+        src16 = deepio.open_deep(self.args.fn_in)
+        try:
+            yield src16
+        finally:
+            if isinstance(src16, deepio.TiffStack):
+                src16.close()
+
+    def keep_points(self, res):
+        """a disc read-out of the points: into the states file and <fn_out>_points.txt"""
+        self.extra.update(points=res["points"], point_means=res["point_means"], point_counts=res["point_counts"])
+        fn_pts = os.path.splitext(self.args.fn_out)[0] + "_points.txt"
+        write_points_txt(fn_pts, res["points"])
+        print("Tracked points: %s" % fn_pts)
+
+
+def open_input(run, args):
+    """The input, the mesh on its first frame, the flow files, the writers; and the four refusals that need the input."""
+    parser = run.parser
+    deep = run.deep = deepio.load_deep(args.fn_in, run.depth)  # 16-bit input: mapped through its window; None for 8-bit
     if args.deep_traces and deep is None:
         parser.error("--deep-traces reads 16-bit frames: %s holds none (8-bit input has no more depth than the kept record)"
                      % args.fn_in)
-    deep_stack = None                                          # the mapped file behind it, which DeepSource reads
-    if deep is not None:
-        deep_stack = deep["source"] if isinstance(deep["source"], deepio.TiffStack) else None
+    if deep is not None:                                       # (deep_stack: the mapped file behind it, which DeepSource reads)
+        run.deep_stack = deep["source"] if isinstance(deep["source"], deepio.TiffStack) else None
         if not 0 <= args.threshold <= 255:                     # (the device compares on the 8-bit scale and refuses others)
-            if deep_stack is not None:
-                deep_stack.close()
+            if run.deep_stack is not None:
+                run.deep_stack.close()
             parser.error("-t/--threshold %d: with 16-bit input the threshold lies in 0..255, the scale of the mapped frames"
                          % args.threshold)
         print("16-bit input: window %d..%d (gamma %g) becomes 0..255; %d pixels below it, %d above"
@@ -447,8 +481,10 @@ def main(argv=None):
         warn = deepio.clip_warning(deep["clipped"], deep["frames"].shape[1] * deep["frames"].shape[2], deep["hi_ppm"])
         if warn:
             print(warn)
-    capture = VideoStream(args.fn_in if deep is None else deep["frames"], args.threshold)          # reference run_kalmanfilter.py:58
-    frame = capture.current_frame()
+        run.extra.update(depth_lo=np.int32(deep["lo"]), depth_hi=np.int32(deep["hi"]), depth_gamma=np.float64(deep["gamma"]),
+                         depth_clipped=deep["clipped"])
+    capture = run.capture = VideoStream(args.fn_in if deep is None else deep["frames"], args.threshold)  # reference run_kalmanfilter.py:58
+    frame = run.frame = capture.current_frame()
     if args.pca is not None:                                   # before any tracking
         n_rec = capture.frames.shape[0] - 1
         if n_rec > pca.GRAM_MAX:
@@ -456,374 +492,430 @@ def main(argv=None):
         if args.pca > n_rec - 1:
             parser.error("--pca: %d components of %d frames (need 1..%d)" % (args.pca, n_rec, n_rec - 1))
     mask, ctrs, fd = capture.backsub()
-    distmesh = DistMesh(frame, h0=args.gridsize)               # reference run_kalmanfilter.py:62-63
-    distmesh.createMesh(ctrs, fd, frame, plot=False)
-    smooth_budget = int(args.smooth_max_gb * (1 << 30))
-    smooth_frames = 2
+    run.distmesh = DistMesh(frame, h0=args.gridsize)           # reference run_kalmanfilter.py:62-63
+    run.distmesh.createMesh(ctrs, fd, frame, plot=False)
+    run.smooth_budget, run.smooth_frames = int(args.smooth_max_gb * (1 << 30)), 2
     if args.smooth:
-        smooth_frames = max(capture.frames.shape[0] - 1, 2)    # one record per compute(), frames 1 .. F-1
-        check_budget(distmesh.size(), smooth_frames, smooth_budget)             # before any tracking
-
-    flowstream = FlowStream(args.flow_in)
-    ret_flow, flowframe = flowstream.peek()
-    states, errors = [], []
+        run.smooth_frames = max(capture.frames.shape[0] - 1, 2)                  # one record per compute(), frames 1 .. F-1
+        check_budget(run.distmesh.size(), run.smooth_frames, run.smooth_budget)  # before any tracking
+    run.flowstream = FlowStream(args.flow_in)
+    run.flow_ready, run.flowframe = run.flowstream.peek()
     H, W = frame.shape[:2]
-    video = AviWriter(args.fn_out, W, H, **vopts) if args.fn_out.lower().endswith(".avi") else None
+    run.video = AviWriter(args.fn_out, W, H, **run.vopts) if args.fn_out.lower().endswith(".avi") else None
     if args.name is not None:
         os.makedirs("screenshots", exist_ok=True)
-    find = args.find_points is not None
-    readout = args.registered is not None or args.points is not None or find or keep_record
-    points = read_points_csv(args.points)[1] if args.points is not None else None
-    reg_video = AviWriter(args.registered, W, H, **gopts) if args.registered is not None else None
+    run.points = read_points_csv(args.points)[1] if args.points is not None else None
+    run.reg_video = AviWriter(args.registered, W, H, **run.gopts) if args.registered is not None else None
 
-    def make_body(kf):
-        if not readout:
-            return None
-        keep, budget = args.rois or keep_record, int(args.rois_max_gb * (1 << 30))
-        if keep:
-            probe = kf.state.renderer.body_map()[0]
-            need = record_bytes(probe, max(capture.frames.shape[0] - 1, 1))
-            if need > budget:
-                print("The registered video takes %d bytes on the device, --rois-max-gb allows %d: no ROIs, %sthe disc "
-                      "read-out instead" % (need, budget, ("no stabilisation, " if args.stabilize else "") +
-                                            ("no deformation correction, " if args.deform_correct else "")))
-                if keep_record:
-                    print("No running baseline either: no --detrend, --resummarize or --dff-video")
-                keep = False
-        body = BodyReadout(kf, points=points, point_radius=args.point_radius, video=reg_video, stats=find, keep=keep,
-                           keep_bytes=budget)
-        for i in np.flatnonzero(body.outside):
-            print("Warning: point %d (%g, %g) lies outside the mesh: NaN in every frame" % (i, points[i, 0], points[i, 1]))
-        return body
 
-    def make_smoother(kf):
-        if not args.smooth:
-            return None
-        return RTSSmoother(kf, smooth_frames, covariances=True, max_bytes=smooth_budget)
+def make_body(run, args):
+    """The body-frame readout, None when no flag asks for one; a record beyond --rois-max-gb is said to be so and not kept."""
+    points = run.points
+    if not (args.registered is not None or points is not None or run.find or run.keep_record):
+        return None
+    keep, budget = args.rois or run.keep_record, int(args.rois_max_gb * (1 << 30))
+    if keep:
+        need = record_bytes(run.kf.state.renderer.body_map()[0], max(run.capture.frames.shape[0] - 1, 1))
+        if need > budget:
+            print("The registered video takes %d bytes on the device, --rois-max-gb allows %d: no ROIs, %sthe disc read-out instead" % (
+                need, budget, ("no stabilisation, " if args.stabilize else "") + ("no deformation correction, " if args.deform_correct else "")))
+            if run.keep_record:
+                print("No running baseline either: no --detrend, --resummarize or --dff-video")
+            keep = False
+    body = BodyReadout(run.kf, points=points, point_radius=args.point_radius, video=run.reg_video, stats=run.find, keep=keep, keep_bytes=budget)
+    for i in np.flatnonzero(body.outside):
+        print("Warning: point %d (%g, %g) lies outside the mesh: NaN in every frame" % (i, points[i, 0], points[i, 1]))
+    return body
 
-    def keep(kf, e, count):
-        states.append(kf.state.X.reshape(-1).copy())
-        errors.append([float(e[0]), float(e[1]), float(e[2]), float(e[3])])
-        if args.name is not None:                              # reference :89, imageoutput of compute()
-            kf.screenshots("screenshots/%s_frame_%d" % (args.name, count))
 
-    if ret_flow:
-        # the reference's loop (:78-89): one flow file per frame
-        if deep_stack is not None:
-            deep_stack.close()                                 # (the mapped frames are all this loop reads)
-        kf = kalman.IteratedMSKalmanFilter(distmesh, frame, flowframe, cuda=args.cuda, sparse=True, multi=True)
-        body = make_body(kf)
-        sm = make_smoother(kf)
-        count = 0
-        while capture.isOpened():
-            count += 1
-            ret, _, grayframe, m = capture.read()
-            ret_flow, flowframe = flowstream.read()
-            if ret is False or ret_flow is False:
-                break
-            print("Frame %d" % count)
-            keep(kf, kf.compute(grayframe, flowframe, m), count)
-            if sm is not None:
-                sm.record()
-            if video is not None:
-                video.write(kf.state.renderer.view(kf.state.X, "overlay"))
-            if body is not None:
-                body.frame(kf.state.X, capture.frame)            # the raw frame, as the pipeline reads it
-    else:
-        # no flow files: flow and filter in one process, the flow of the coming frames computed on the GPU
-        # beside the filter (hydra_mi.pipeline; replaces the file hand-off of reference README.md:26-31)
-        print("Cannot read flow stream at %s*: computing Brox flow in-process" % args.flow_in)
-        kf = kalman.IteratedMSKalmanFilter(distmesh, frame, np.zeros(frame.shape + (2,), np.float32), cuda=args.cuda,
+def make_smoother(run, args):
+    return RTSSmoother(run.kf, run.smooth_frames, covariances=True, max_bytes=run.smooth_budget) if args.smooth else None
+
+
+def keep_state(run, e, count):
+    run.states.append(run.kf.state.X.reshape(-1).copy())
+    run.errors.append([float(e[0]), float(e[1]), float(e[2]), float(e[3])])
+    if run.args.name is not None:                              # reference :89, imageoutput of compute()
+        run.kf.screenshots("screenshots/%s_frame_%d" % (run.args.name, count))
+
+
+def track_from_flow_files(run, args):
+    """the reference's loop (:78-89): one flow file per frame"""
+    capture = run.capture
+    if run.deep_stack is not None:
+        run.deep_stack.close()                                 # (the mapped frames are all this loop reads)
+    kf = run.kf = kalman.IteratedMSKalmanFilter(run.distmesh, run.frame, run.flowframe, cuda=args.cuda, sparse=True, multi=True)
+    body = run.body = make_body(run, args)
+    sm = run.sm = make_smoother(run, args)
+    count = 0
+    while capture.isOpened():
+        count += 1
+        ret, _, grayframe, m = capture.read()
+        ret_flow, flowframe = run.flowstream.read()
+        if ret is False or ret_flow is False:
+            break
+        print("Frame %d" % count)
+        keep_state(run, kf.compute(grayframe, flowframe, m), count)
+        if sm is not None:
+            sm.record()
+        if run.video is not None:
+            run.video.write(kf.state.renderer.view(kf.state.X, "overlay"))
+        if body is not None:
+            body.frame(kf.state.X, capture.frame)              # the raw frame, as the pipeline reads it
+
+
+def track_in_process(run, args):
+    """no flow files: flow and filter in one process, the flow of the coming frames computed on the GPU beside the filter
+    (hydra_mi.pipeline; replaces the file hand-off of reference README.md:26-31)"""
+    capture, deep = run.capture, run.deep
+    print("Cannot read flow stream at %s*: computing Brox flow in-process" % args.flow_in)
+    run.kf = kalman.IteratedMSKalmanFilter(run.distmesh, run.frame, np.zeros(run.frame.shape + (2,), np.float32), cuda=args.cuda,
                                            sparse=True, multi=True)
-        source = capture                             # frames, masks and background-subtracted frames read from the stream
-        if str(args.fn_in).lower().endswith(".avi"):
-            from hydra_mi.videoio import AviReader, AviSource
-            with AviReader(args.fn_in) as reader:
-                mjpeg = reader.mjpeg
-            if mjpeg:                                # the device decoder writes the frame ring's planes
-                source = AviSource(args.fn_in, args.threshold, frames=capture.frames)
-        if deep is not None:                         # the device maps the 16-bit pixels into the frame ring's planes
-            source = deepio.DeepSource(deep["source"], deep["lut"], deep["lo"], deep["hi"], args.threshold, frames=capture.frames)
-        pipe = None
-        try:
-            pipe = FlowEKFPipeline(kf, source)
-            body = make_body(kf)
-            sm = make_smoother(kf)
+    source = capture                                 # frames, masks and background-subtracted frames read from the stream
+    if str(args.fn_in).lower().endswith(".avi"):
+        from hydra_mi.videoio import AviReader, AviSource
+        with AviReader(args.fn_in) as reader:
+            mjpeg = reader.mjpeg
+        if mjpeg:                                    # the device decoder writes the frame ring's planes
+            source = AviSource(args.fn_in, args.threshold, frames=capture.frames)
+    if deep is not None:                             # the device maps the 16-bit pixels into the frame ring's planes
+        source = deepio.DeepSource(deep["source"], deep["lut"], deep["lo"], deep["hi"], args.threshold, frames=capture.frames)
+    pipe = None
+    try:
+        pipe = FlowEKFPipeline(run.kf, source)
+        run.body, run.sm = make_body(run, args), make_smoother(run, args)
 
-            def on_frame(k, e):
-                print("Frame %d" % (k + 1))
-                keep(kf, e, k + 1)
-            pipe.run(on_frame=on_frame, video=video, body=body, smoother=sm)
-        finally:                                     # also when tracking fails: the pipeline first, then what fed it
-            if pipe is not None:
-                pipe.close()
-            if source is not capture:
-                source.close()
-            if deep_stack is not None:
-                deep_stack.close()
-    if video is not None:
-        video.close()
-        print("Overlay video: %d frames in %s" % (video.frames, args.fn_out))
-    extra = {}
-    if deep is not None:
-        extra.update(depth_lo=np.int32(deep["lo"]), depth_hi=np.int32(deep["hi"]), depth_gamma=np.float64(deep["gamma"]),
-                     depth_clipped=deep["clipped"])
-    cv_cells = cv_levels = cv_points = None          # what --cells-video draws
-    st_cells = st_dff = None                         # what --strain reads the tissue under: (labels or points), their dF/F
-    more = None                                      # what --find-more found
-    if body is not None:
-        res = body.results()
-        extra.update(tri_means=res["tri_means"], tri_counts=res["tri_counts"])       # (beside depth_* of a 16-bit input)
-        if points is not None:
-            extra.update(points=res["points"], point_means=res["point_means"], point_counts=res["point_counts"])
-            fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
-            write_points_txt(fn_pts, res["points"])
-            print("Tracked points: %s" % fn_pts)
-            # the discs of the points, read from the 16-bit frames (with ROIs the cells' traces are read instead, below)
-            if args.deep_traces and not (args.rois and body.keep) and body.L > 0 and len(states):
-                src16 = deepio.open_deep(args.fn_in)
-                try:
-                    # (state k belongs to frame k + 1, also when the run ended before the file did)
-                    dsum = deeptrace.run(body, src16, states, deeptrace.columns(body.labels, body.L), first=1)
-                finally:
-                    if isinstance(src16, deepio.TiffStack):
-                        src16.close()
-                extra.update(deep_point_means=deeptrace.point_means(dsum, body.label_counts, args.deep_offset),
-                             deep_offset=np.float64(args.deep_offset))
-                print("Full-depth traces: the discs of %d points over %d frames" % (body.L, len(states)))
-    if args.stabilize and body is not None and body.keep and len(states):
-        # between tracking and everything that reads the kept record: the disc read-out of --find-points, roi.extract and
-        # demix.extract see the stabilised frames (what was summed while tracking -- tri_means, the summary images and the
-        # points found in them, point_means of --points -- saw the frames as the tracker registered them)
-        est = stabilize.stabilize(body, B=args.stab_patch, S=args.stab_search, passes=args.stab_passes, mode=args.stab_mode)
-        extra.update(stab_shifts=est["shifts"], stab_score=est["score"], stab_fallback=est["fallback"])
-        moved = est["shifts"].astype(np.float64)
-        if args.stab_mode == "field":
-            extra.update(stab_q=est["q"])
-            moved = est["q"].astype(np.float64) / 16.0
-        print("Stabilised%s: %d patches of %d px, search %d, %d passes: %.1f %% fallbacks, mean |shift| %.3f px" % (
-            " (field)" if args.stab_mode == "field" else "", est["shifts"].shape[1], args.stab_patch, args.stab_search,
-            args.stab_passes, 100.0 * est["fallback"].mean(), np.abs(moved).sum(2).mean()))
-    if args.deform_correct and body is not None and body.keep and len(states):
-        # after the stabiliser, before everything that reads the kept record; at the filtered states, those the frames were
-        # warped with.  The stabiliser has moved pixels by a few px, across triangle seams too: the gain is that of the
-        # pixel's home triangle regardless.
-        dc = deform.correct(body, np.array(states), gamma=args.deform_gamma)
-        extra.update(deform_gamma=np.float64(dc["gamma"]), deform_fit_r2=np.float64(dc["fit_r2"]), deform_gain=dc["gain"],
+        def on_frame(k, e):
+            print("Frame %d" % (k + 1))
+            keep_state(run, e, k + 1)
+        pipe.run(on_frame=on_frame, video=run.video, body=run.body, smoother=run.sm)
+    finally:                                         # also when tracking fails: the pipeline first, then what fed it
+        if pipe is not None:
+            pipe.close()
+        if source is not capture:
+            source.close()
+        if run.deep_stack is not None:
+            run.deep_stack.close()
+
+
+def stage_results(run, args):
+    body, extra = run.body, run.extra
+    if run.video is not None:
+        run.video.close()
+        print("Overlay video: %d frames in %s" % (run.video.frames, args.fn_out))
+    if body is None:
+        return
+    res = body.results()
+    extra.update(tri_means=res["tri_means"], tri_counts=res["tri_counts"])       # (beside depth_* of a 16-bit input)
+    if run.points is None:
+        return
+    run.keep_points(res)
+    # the discs of the points, read from the 16-bit frames (with ROIs the cells' traces are read instead, in stage_cells)
+    if args.deep_traces and not (args.rois and body.keep) and body.L > 0 and len(run.states):
+        with run.second_pass() as src16:
+            dsum = deeptrace.run(body, src16, run.states, deeptrace.columns(body.labels, body.L), first=1)   # (state k: frame k + 1)
+        extra.update(deep_point_means=deeptrace.point_means(dsum, body.label_counts, args.deep_offset), deep_offset=np.float64(args.deep_offset))
+        print("Full-depth traces: the discs of %d points over %d frames" % (body.L, len(run.states)))
+
+
+def stage_stabilize(run, args):
+    if not (args.stabilize and run.record_ready):
+        return
+    est = stabilize.stabilize(run.body, B=args.stab_patch, S=args.stab_search, passes=args.stab_passes, mode=args.stab_mode)
+    run.extra.update(stab_shifts=est["shifts"], stab_score=est["score"], stab_fallback=est["fallback"])
+    moved = est["shifts"].astype(np.float64)
+    if args.stab_mode == "field":
+        run.extra.update(stab_q=est["q"])
+        moved = est["q"].astype(np.float64) / 16.0
+    print("Stabilised%s: %d patches of %d px, search %d, %d passes: %.1f %% fallbacks, mean |shift| %.3f px" % (
+        " (field)" if args.stab_mode == "field" else "", est["shifts"].shape[1], args.stab_patch, args.stab_search,
+        args.stab_passes, 100.0 * est["fallback"].mean(), np.abs(moved).sum(2).mean()))
+
+
+def stage_deform_correct(run, args):
+    if not (args.deform_correct and run.record_ready):
+        return
+    dc = deform.correct(run.body, np.array(run.states), gamma=args.deform_gamma)        # at the filtered states: the frames were warped with them
+    run.extra.update(deform_gamma=np.float64(dc["gamma"]), deform_fit_r2=np.float64(dc["fit_r2"]), deform_gain=dc["gain"],
                      deform_clipped=np.uint64(dc["clipped"]), deform_r_before=dc["r_before"].astype(np.float32),
                      deform_r_after=dc["r_after"].astype(np.float32))
-        with np.errstate(invalid="ignore"):
-            med = [float(np.nanmedian(np.abs(dc[key]))) if np.isfinite(dc[key]).any() else np.nan for key in ("r_before", "r_after")]
-        print("Deformation corrected: gamma %.3f (%s, r2 %.3f), gains %.3f .. %.3f over %d triangles, %d values clipped, "
-              "median |r| with the area change %.3f -> %.3f" % (
-                  dc["gamma"], "fitted" if dc["fitted"] else "given" if args.deform_gamma is not None else "nothing to fit from",
-                  dc["fit_r2"], dc["gain"].min() / 4096.0, dc["gain"].max() / 4096.0, dc["gain"].shape[1], dc["clipped"], *med))
-    if args.pca is not None and body is not None and body.keep and len(states):
-        # after the stabiliser and the deformation correction, before everything else that reads the kept record
-        pc = pca.pca(body, min(args.pca, max(len(states) - 1, 1)), frames=args.pca_frames)      # (a run that ended early)
-        extra.update(pca_lambda=pc["lam"], pca_share=pc["share"], pca_temporal=pc["temporal"],
-                     pca_rho=pc["rho"].astype(np.float32), pca_frame_score=pc["frame_score"])
-        if args.pca_frames:
-            extra.update(pca_frame_r=pc["frame_r"].astype(np.float32))
-        print("PCA: %d components of %d frames carry %s of the variance; lowest frame score %.3f at frame %d" % (
-            len(pc["lam"]), len(states), " ".join("%.4f" % v for v in pc["share"]),
-            np.nanmin(pc["frame_score"]) if np.isfinite(pc["frame_score"]).any() else np.nan,
-            int(np.nanargmin(pc["frame_score"])) + 1 if np.isfinite(pc["frame_score"]).any() else -1))
-    det_kind = "excess" if args.detrend else "recorded" if args.resummarize else None
-    if det_kind is not None and not (body is not None and body.keep and len(states)):
-        det_kind = None
+    with np.errstate(invalid="ignore"):
+        med = [float(np.nanmedian(np.abs(dc[key]))) if np.isfinite(dc[key]).any() else np.nan for key in ("r_before", "r_after")]
+    print("Deformation corrected: gamma %.3f (%s, r2 %.3f), gains %.3f .. %.3f over %d triangles, %d values clipped, "
+          "median |r| with the area change %.3f -> %.3f" % (
+              dc["gamma"], "fitted" if dc["fitted"] else "given" if args.deform_gamma is not None else "nothing to fit from",
+              dc["fit_r2"], dc["gain"].min() / 4096.0, dc["gain"].max() / 4096.0, dc["gain"].shape[1], dc["clipped"], *med))
 
-    def detrended_summary():
-        # the statistics begun afresh on the device and fed the kept record's planes: find_points below searches these
-        d_img = detrend.summary(body, det_kind, args.detrend_half, args.detrend_q)
-        extra.update(detrend_mean=d_img["mean"], detrend_std=d_img["std"], detrend_max=d_img["max"], detrend_corr=d_img["corr"])
-        if det_kind == "excess":
-            print("Detrended: the excess over the running baseline (half %d, q %d) of %d frames summed up" % (
-                args.detrend_half, args.detrend_q, d_img["frames"]))
-        else:
-            print("Resummarised: %d frames of the stabilised record summed up" % d_img["frames"])
 
-    if find:
-        # the cells need the whole video and the traces need the cells: a second pass over the recorded states
-        sm_img = body.summary()
-        if det_kind is not None:
-            detrended_summary()
-        found, scores = body.find_points(args.find_points, radius=args.find_radius, score=args.find_score,
-                                         min_score=args.find_min_score)
-        if args.find_more is not None and body.keep and len(states) and len(found):
-            # the cells beside the ones found: the demixed model taken out of the kept record, and searched again
-            more = residual.find_more(body, found, args.find_min_score, rounds=args.find_more, radius=args.find_radius,
-                                      score=args.find_score, blank=args.find_blank, iters=args.demix_iters,
-                                      r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
-            rs = more["scores"]
-            extra.update(residual_round=more["round"], residual_scores=np.concatenate(rs),
-                         residual_scores_round=np.concatenate([np.full(len(s), k + 1, np.int32) for k, s in enumerate(rs)]),
-                         residual_clipped=np.array(more["clipped"], np.uint64))
-            print("Found %d more points in %d rounds of the residual video (%d candidates refused, %d values clipped)" % (
-                len(more["points"]) - len(found), len(rs), len(more["refused"]), sum(more["clipped"])))
-            found, scores = more["points"], np.concatenate((scores, more["new_scores"]))
-        kf.state.renderer.body_stats_end()
-        extra.update(body_mean=sm_img["mean"], body_std=sm_img["std"], body_max=sm_img["max"], body_corr=sm_img["corr"],
+def stage_pca(run, args):
+    if not (args.pca is not None and run.record_ready):
+        return
+    pc = pca.pca(run.body, min(args.pca, max(len(run.states) - 1, 1)), frames=args.pca_frames)      # (a run that ended early)
+    run.extra.update(pca_lambda=pc["lam"], pca_share=pc["share"], pca_temporal=pc["temporal"], pca_rho=pc["rho"].astype(np.float32),
+                     pca_frame_score=pc["frame_score"])
+    if args.pca_frames:
+        run.extra.update(pca_frame_r=pc["frame_r"].astype(np.float32))
+    print("PCA: %d components of %d frames carry %s of the variance; lowest frame score %.3f at frame %d" % (
+        len(pc["lam"]), len(run.states), " ".join("%.4f" % v for v in pc["share"]),
+        np.nanmin(pc["frame_score"]) if np.isfinite(pc["frame_score"]).any() else np.nan,
+        int(np.nanargmin(pc["frame_score"])) + 1 if np.isfinite(pc["frame_score"]).any() else -1))
+
+
+def detrended_summary(run, args, kind):
+    """the statistics begun afresh on the device and fed the kept record's planes: find_points searches these"""
+    d_img = detrend.summary(run.body, kind, args.detrend_half, args.detrend_q)
+    run.extra.update(detrend_mean=d_img["mean"], detrend_std=d_img["std"], detrend_max=d_img["max"], detrend_corr=d_img["corr"])
+    if kind == "excess":
+        print("Detrended: the excess over the running baseline (half %d, q %d) of %d frames summed up" % (
+            args.detrend_half, args.detrend_q, d_img["frames"]))
+    else:
+        print("Resummarised: %d frames of the stabilised record summed up" % d_img["frames"])
+
+
+def search_more(run, args, found, scores):
+    """the cells beside the ones found: the demixed model taken out of the kept record, and searched again"""
+    more = run.more = residual.find_more(run.body, found, args.find_min_score, rounds=args.find_more, radius=args.find_radius,
+                                         score=args.find_score, blank=args.find_blank, iters=args.demix_iters,
+                                         r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
+    rs = more["scores"]
+    run.extra.update(residual_round=more["round"], residual_scores=np.concatenate(rs),
+                     residual_scores_round=np.concatenate([np.full(len(s), k + 1, np.int32) for k, s in enumerate(rs)]),
+                     residual_clipped=np.array(more["clipped"], np.uint64))
+    print("Found %d more points in %d rounds of the residual video (%d candidates refused, %d values clipped)" % (
+        len(more["points"]) - len(found), len(rs), len(more["refused"]), sum(more["clipped"])))
+    return more["points"], np.concatenate((scores, more["new_scores"]))
+
+
+def stage_search(run, args):
+    """The summary images of --detrend or --resummarize, and with --find-points the search: the cells need the whole video
+    and the traces need the cells, so a second pass over the recorded states reads them out."""
+    body = run.body
+    kind = ("excess" if args.detrend else "recorded" if args.resummarize else None) if run.record_ready else None
+    if not run.find:
+        if kind is not None:
+            detrended_summary(run, args, kind)
+            run.kf.state.renderer.body_stats_end()
+        return
+    sm_img = body.summary()
+    if kind is not None:
+        detrended_summary(run, args, kind)
+    found, scores = body.find_points(args.find_points, radius=args.find_radius, score=args.find_score, min_score=args.find_min_score)
+    if args.find_more is not None and run.record_ready and len(found):
+        found, scores = search_more(run, args, found, scores)
+    run.found, run.scores = found, scores
+    run.kf.state.renderer.body_stats_end()
+    run.extra.update(body_mean=sm_img["mean"], body_std=sm_img["std"], body_max=sm_img["max"], body_corr=sm_img["corr"],
                      found_points=found, found_scores=scores)
-        print("Found %d points (%s, radius %d) in %d frames" % (len(found), args.find_score, args.find_radius, sm_img["frames"]))
-        if body.keep:                # the registered video is on the device: the discs are summed there
-            res = read_out_recorded(body, states, found, args.point_radius)
+    print("Found %d points (%s, radius %d) in %d frames" % (len(found), args.find_score, args.find_radius, sm_img["frames"]))
+    if body.keep:                # the registered video is on the device: the discs are summed there
+        res = read_out_recorded(body, run.states, found, args.point_radius)
+    else:
+        res = read_out(run.kf, run.states, run.tracked_frames, found, args.point_radius)
+    run.keep_points(res)
+    if args.points_out is not None:
+        write_points_csv(args.points_out, found)
+        print("Points found: %s" % args.points_out)
+
+
+def stage_cells(run, args):
+    """The dF/F video; the cells of the points inside the mesh, demixed (those of --find-more reused when they are all the
+    points) or ROIs; the residual video; the roi_* arrays; the same cells at full depth."""
+    body, extra, pts = run.body, run.extra, run.pts
+    if not run.kept:
+        return
+    if args.dff_video is not None and len(run.states):
+        n_dff = detrend.write_video(body, args.dff_video, args.detrend_half, args.detrend_q, args.dff_floor, args.dff_gain, **run.vkw)
+        print("dF/F video: %d frames in %s" % (n_dff, args.dff_video))
+    inside = run.inside = np.flatnonzero(body.locate(pts)[0] >= 0) if args.rois else []
+    if not (len(inside) and len(run.states)):
+        return
+    cell = dict(r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
+    if args.demix:
+        if run.more is not None and len(inside) == len(pts):           # (demixed already, with all the points)
+            e = run.more["e"]
         else:
-            res = read_out(kf, states, capture.frames[1:1 + len(states)], found, args.point_radius)    # state k: frame k + 1
-        extra.update(points=res["points"], point_means=res["point_means"], point_counts=res["point_counts"])
-        fn_pts = os.path.splitext(args.fn_out)[0] + "_points.txt"
-        write_points_txt(fn_pts, res["points"])
-        print("Tracked points: %s" % fn_pts)
-        if args.points_out is not None:
-            write_points_csv(args.points_out, found)
-            print("Points found: %s" % args.points_out)
-    elif det_kind is not None:
-        detrended_summary()
-        kf.state.renderer.body_stats_end()
-    if args.cells_video is not None:
-        cv_points = found if find else points
-    if args.strain and (find or points is not None):
-        st_cells = {"points": found if find else points, "point_radius": args.point_radius}
-    if body is not None and body.keep:
-        if args.dff_video is not None and len(states):
-            n_dff = detrend.write_video(body, args.dff_video, args.detrend_half, args.detrend_q, args.dff_floor, args.dff_gain,
-                                          **vkw)
-            print("dF/F video: %d frames in %s" % (n_dff, args.dff_video))
-        pts = found if find else points
-        inside = np.flatnonzero(body.locate(pts)[0] >= 0) if args.rois else []
-        if len(inside) and len(states):
-            if args.demix:
-                if more is not None and len(inside) == len(pts):           # (demixed already, with all the points)
-                    e = more["e"]
-                else:
-                    e = demix.extract(body, pts[inside], iters=args.demix_iters, r_disc=args.point_radius, thr=args.roi_thr,
-                                      alpha=args.roi_alpha)
-                extra.update(demix_shapes=e["shapes"], demix_C=e["C"], demix_dff=e["dff_demixed"],
-                             demix_change=e["demix_change"])
-                print("Demixed: %d cells, %d rounds, last change %.3g" % (len(inside), args.demix_iters, e["demix_change"][-1]))
-                if args.residual_video is not None:
-                    n_res, n_clip = residual.write_video(body, args.residual_video, e, points=pts[inside], **vkw)
-                    print("Residual video: %d frames in %s (%d values clipped)" % (n_res, args.residual_video, n_clip))
-            else:
-                e = roi.extract(body, pts[inside], r_disc=args.point_radius, thr=args.roi_thr, alpha=args.roi_alpha)
-            extra.update(roi_points=inside, roi_footprints=e["footprints"], roi_labels=e["roi_labels"],
-                         roi_counts=e["roi_counts"], roi_ring_counts=e["ring_counts"], roi_F=e["F_roi"], roi_Fnp=e["F_np"],
-                         roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
-            print("ROIs: %d cells, %d..%d pixels, %d kept their disc" % (len(inside), e["roi_counts"].min(),
-                                                                          e["roi_counts"].max(), e["seed_fallback"].sum()))
-            if args.deep_traces:                                   # the second pass: the same cells, the camera's numbers
-                src16 = deepio.open_deep(args.fn_in)
-                try:
-                    de = deeptrace.extract(body, src16, states, e, demixed=e if args.demix else None, alpha=args.roi_alpha,
-                                           offset=args.deep_offset, first=1)    # (state k belongs to frame k + 1)
-                finally:
-                    if isinstance(src16, deepio.TiffStack):
-                        src16.close()
-                extra.update(deep_F_roi=de["deep_F_roi"], deep_F_np=de["deep_F_np"], deep_dff=de["deep_dff"],
-                             deep_offset=np.float64(args.deep_offset))
-                if args.demix:
-                    extra.update(deep_demix_c=de["deep_demix_c"])
-                print("Full-depth traces: %d cells over %d frames, F_roi %.1f..%.1f" % (
-                    len(inside), len(states), np.nanmin(de["deep_F_roi"]), np.nanmax(de["deep_F_roi"])))
-            if args.events:                                        # (cell s: point inside[s], as the roi_* rows)
-                tr = np.ascontiguousarray((e["dff_demixed"] if args.demix else e["dff"]).T, np.float64)
-                fixed = lambda v, rule: np.full(len(tr), v, np.float64) if v is not None else np.array(rule, np.float64)
-                sig = [events.noise(x) for x in tr]
-                ev_g = fixed(args.events_g, [events.estimate_g(x) for x in tr])
-                ev_lam = fixed(args.events_lambda, [events.default_lam(g, sg) for g, sg in zip(ev_g, sig)])
-                ev_smin = fixed(args.events_smin, [events.default_smin(sg) for sg in sig])
-                ev_c, ev_s = events.deconvolve(tr, ev_g, ev_lam)
-                # every pixel of the dF/F bytes: one g, and the cells' median penalty and threshold in bytes
-                px = dict(what="dff", half=args.detrend_half, q=args.detrend_q, floor=args.dff_floor, gain=args.dff_gain)
-                g_px, lam_px = float(np.median(ev_g)), float(np.median(ev_lam)) * args.dff_gain
-                smin_px = max(1.0, float(np.median(ev_smin)) * args.dff_gain)
-                ev_n, ev_sum = events.count_image(body, g_px, lam_px, smin_px, **px)
-                extra.update(ev_g=ev_g, ev_lambda=ev_lam, ev_c=ev_c, ev_s=ev_s, ev_binary=events.binarise(ev_s, ev_smin),
-                             ev_count_image=ev_n, ev_sum_image=ev_sum.astype(np.float32),
-                             ev_params=np.array([g_px, lam_px, smin_px, px["half"], px["q"], px["floor"], px["gain"]], np.float64))
-                print("Events: %d cells, g %.3f..%.3f, %d events; per pixel g %.3f, lambda %.3g, s_min %.3g: %d events" % (
-                    len(tr), ev_g.min(), ev_g.max(), extra["ev_binary"].sum(), g_px, lam_px, smin_px, ev_n.sum()))
-                if args.network:
-                    extra.update(net_r_events=network.coactivity(ev_s, args.network_lag))
-                if args.events_video is not None:
-                    n_ev = events.event_video(body, args.events_video, g_px, lam_px, **px, **vkw)
-                    print("Event video: %d frames in %s" % (n_ev, args.events_video))
-            if args.network:                                       # (cell s: point inside[s], as the roi_* rows)
-                net = network.extract(body, (e["dff_demixed"] if args.demix else e["dff"]).T, thr=args.network_thr,
-                                      max_lag=args.network_lag, map_thr=args.network_map_thr, null=args.network_null,
-                                      guard=args.network_guard, seed=args.network_seed, alpha=args.network_alpha)
-                extra.update(net_r=net["r"], net_labels=net["labels"], net_ens_traces=net["ens_traces"],
-                             net_lead_lag=net["lead_lag"], net_lead_r=net["lead_r"], net_rho=net["rho"].astype(np.float32),
-                             net_map=net["map"])
-                print("Network: %d ensembles of %d cells, %d cells alone, %d pixels mapped" % (
-                    net["ens_traces"].shape[0], (net["labels"] >= 0).sum(), (net["labels"] < 0).sum(), (net["map"] >= 0).sum()))
-                if args.network_null:
-                    extra.update(net_p_r=net["p_r"], net_p_map=net["p_map"].astype(np.float32), net_rho_max=net["rho_max"],
-                                 net_sig=net["sig"], net_map_sig=net["map_sig"])
-                    for k in range(net["rho_max"].shape[0]):
-                        print("Null: ensemble %d: the largest rho of %d shifted traces %.4f, %d significant pixels" % (
-                            k, net["rho_max"].shape[1], net["rho_max"][k].max(), net["sig"][k].sum()))
-                if args.network_map is not None:
-                    network.colour_map(net["map_sig"] if args.network_null else net["map"], net["gray"], args.network_map)
-                    print("Ensemble map: %s" % args.network_map)
-            if args.strain:                                        # (cell s: point inside[s], as the roi_* rows)
-                st_cells, st_dff = {"labels": e["roi_labels"], "L": len(inside)}, e["dff_demixed"] if args.demix else e["dff"]
-            if args.cells_video is not None:
-                if args.demix:
-                    lab, w, dropped = cellview.layers_from_shapes(e["shapes_q"], roi.seeds_of(pts[inside]),
-                                                                  (e["shapes_q"].shape[1] - 1) // 2, (H, W))
-                    if dropped:
-                        print("Cells video: %d (pixel, cell) entries beyond two cells per pixel are not drawn" % dropped)
-                    cv_cells, cv_levels = (lab, w), cellview.levels(e["dff_demixed"])
-                else:
-                    cv_cells, cv_levels = cellview.layers_from_labels(e["roi_labels"]), cellview.levels(e["dff"])
-                cv_points = pts[inside]                            # (cell s and marker s share a colour)
-                if int(cv_cells[0].max()) + 1 != len(inside):      # (the last cells own no pixel: no level for them)
-                    cv_levels = cv_levels[:, :int(cv_cells[0].max()) + 1]
-        kf.state.renderer.body_rec_end()
-    if reg_video is not None:
-        reg_video.close()
-        print("Registered video: %d frames in %s" % (reg_video.frames, args.registered))
-    if sm is not None:
-        if len(sm) > 0:
-            xs, var = sm.run()
-            extra.update(Xs=xs, Xs_std=np.sqrt(var))
+            e = demix.extract(body, pts[inside], iters=args.demix_iters, **cell)
+        extra.update(demix_shapes=e["shapes"], demix_C=e["C"], demix_dff=e["dff_demixed"], demix_change=e["demix_change"])
+        print("Demixed: %d cells, %d rounds, last change %.3g" % (len(inside), args.demix_iters, e["demix_change"][-1]))
+        if args.residual_video is not None:
+            n_res, n_clip = residual.write_video(body, args.residual_video, e, points=pts[inside], **run.vkw)
+            print("Residual video: %d frames in %s (%d values clipped)" % (n_res, args.residual_video, n_clip))
+    else:
+        e = roi.extract(body, pts[inside], **cell)
+    run.e = e
+    extra.update(roi_points=inside, roi_footprints=e["footprints"], roi_labels=e["roi_labels"], roi_counts=e["roi_counts"],
+                 roi_ring_counts=e["ring_counts"], roi_F=e["F_roi"], roi_Fnp=e["F_np"], roi_dff=e["dff"], roi_seed_fallback=e["seed_fallback"])
+    print("ROIs: %d cells, %d..%d pixels, %d kept their disc" % (len(inside), e["roi_counts"].min(), e["roi_counts"].max(), e["seed_fallback"].sum()))
+    if args.deep_traces:                                               # the second pass: the same cells, the camera's numbers
+        with run.second_pass() as src16:
+            de = deeptrace.extract(body, src16, run.states, e, demixed=e if args.demix else None, alpha=args.roi_alpha,
+                                   offset=args.deep_offset, first=1)    # (state k belongs to frame k + 1)
+        extra.update(deep_F_roi=de["deep_F_roi"], deep_F_np=de["deep_F_np"], deep_dff=de["deep_dff"], deep_offset=np.float64(args.deep_offset))
+        if args.demix:
+            extra.update(deep_demix_c=de["deep_demix_c"])
+        print("Full-depth traces: %d cells over %d frames, F_roi %.1f..%.1f" % (
+            len(inside), len(run.states), np.nanmin(de["deep_F_roi"]), np.nanmax(de["deep_F_roi"])))
+
+
+def stage_events(run, args):
+    body, extra = run.body, run.extra
+    if run.e is None or not args.events:
+        return
+    tr = np.ascontiguousarray(run.dff.T, np.float64)
+    fixed = lambda v, rule: np.full(len(tr), v, np.float64) if v is not None else np.array(rule, np.float64)
+    sig = [events.noise(x) for x in tr]
+    ev_g = fixed(args.events_g, [events.estimate_g(x) for x in tr])
+    ev_lam = fixed(args.events_lambda, [events.default_lam(g, sg) for g, sg in zip(ev_g, sig)])
+    ev_smin = fixed(args.events_smin, [events.default_smin(sg) for sg in sig])
+    ev_c, ev_s = events.deconvolve(tr, ev_g, ev_lam)
+    # every pixel of the dF/F bytes: one g, and the cells' median penalty and threshold in bytes
+    px = dict(what="dff", half=args.detrend_half, q=args.detrend_q, floor=args.dff_floor, gain=args.dff_gain)
+    g_px, lam_px = float(np.median(ev_g)), float(np.median(ev_lam)) * args.dff_gain
+    smin_px = max(1.0, float(np.median(ev_smin)) * args.dff_gain)
+    ev_n, ev_sum = events.count_image(body, g_px, lam_px, smin_px, **px)
+    extra.update(ev_g=ev_g, ev_lambda=ev_lam, ev_c=ev_c, ev_s=ev_s, ev_binary=events.binarise(ev_s, ev_smin),
+                 ev_count_image=ev_n, ev_sum_image=ev_sum.astype(np.float32),
+                 ev_params=np.array([g_px, lam_px, smin_px, px["half"], px["q"], px["floor"], px["gain"]], np.float64))
+    print("Events: %d cells, g %.3f..%.3f, %d events; per pixel g %.3f, lambda %.3g, s_min %.3g: %d events" % (
+        len(tr), ev_g.min(), ev_g.max(), extra["ev_binary"].sum(), g_px, lam_px, smin_px, ev_n.sum()))
+    if args.network:
+        extra.update(net_r_events=network.coactivity(ev_s, args.network_lag))
+    if args.events_video is not None:
+        n_ev = events.event_video(body, args.events_video, g_px, lam_px, **px, **run.vkw)
+        print("Event video: %d frames in %s" % (n_ev, args.events_video))
+
+
+def stage_network(run, args):
+    if run.e is None or not args.network:
+        return
+    net = network.extract(run.body, run.dff.T, thr=args.network_thr, max_lag=args.network_lag, map_thr=args.network_map_thr,
+                          null=args.network_null, guard=args.network_guard, seed=args.network_seed, alpha=args.network_alpha)
+    run.extra.update(net_r=net["r"], net_labels=net["labels"], net_ens_traces=net["ens_traces"], net_lead_lag=net["lead_lag"],
+                     net_lead_r=net["lead_r"], net_rho=net["rho"].astype(np.float32), net_map=net["map"])
+    print("Network: %d ensembles of %d cells, %d cells alone, %d pixels mapped" % (
+        net["ens_traces"].shape[0], (net["labels"] >= 0).sum(), (net["labels"] < 0).sum(), (net["map"] >= 0).sum()))
+    if args.network_null:
+        run.extra.update(net_p_r=net["p_r"], net_p_map=net["p_map"].astype(np.float32), net_rho_max=net["rho_max"],
+                         net_sig=net["sig"], net_map_sig=net["map_sig"])
+        for k in range(net["rho_max"].shape[0]):
+            print("Null: ensemble %d: the largest rho of %d shifted traces %.4f, %d significant pixels" % (
+                k, net["rho_max"].shape[1], net["rho_max"][k].max(), net["sig"][k].sum()))
+    if args.network_map is not None:
+        network.colour_map(net["map_sig"] if args.network_null else net["map"], net["gray"], args.network_map)
+        print("Ensemble map: %s" % args.network_map)
+
+
+def stage_record_end(run, args):
+    """What --strain and --cells-video are handed of the cells; then the kept record is freed and the registered video closed."""
+    e, n = run.e, len(run.inside)
+    if e is not None and args.strain:
+        run.st_cells, run.st_dff = {"labels": e["roi_labels"], "L": n}, run.dff
+    if e is not None and args.cells_video is not None:
+        if args.demix:
+            lab, w, dropped = cellview.layers_from_shapes(e["shapes_q"], roi.seeds_of(run.pts[run.inside]),
+                                                          (e["shapes_q"].shape[1] - 1) // 2, run.frame.shape[:2])
+            if dropped:
+                print("Cells video: %d (pixel, cell) entries beyond two cells per pixel are not drawn" % dropped)
+            run.cv_cells, run.cv_levels = (lab, w), cellview.levels(e["dff_demixed"])
         else:
-            extra.update(Xs=np.zeros((0, 4 * kf.N)), Xs_std=np.zeros((0, 4 * kf.N)))
-        sm.close()
-        print("Smoothed track: Xs, Xs_std (%d frames)" % len(states))
-    if args.cells_video is not None and len(states):
-        use = args.cells_video_states or ("smoothed" if args.smooth else "filtered")
-        cv_states = extra["Xs"] if use == "smoothed" else states
-        if cv_cells is not None and int(cv_cells[0].max()) < 0:
-            cv_cells = cv_levels = None
-        n_cv = cellview.write_video(kf, cv_states, capture.frames[1:1 + len(states)], args.cells_video, cells=cv_cells,
-                                    levels=cv_levels, points=cv_points, **vkw)       # state k: frame k + 1
-        print("Cells video: %d frames (%s states) in %s" % (n_cv, use, args.cells_video))
-    if (args.strain or args.strain_video is not None) and len(states):
-        st_states = extra["Xs"] if args.smooth else np.array(states)
-        if args.strain:
-            d = strain.triangles(kf, st_states)
-            extra.update(strain_J=d["J"], strain_l1=d["l1"], strain_l2=d["l2"], strain_axis=d["axis"],
-                         strain_rotation=d["rotation"], strain_body_area=d["body_area"])
-            print("Strain: %d triangles, body area %.4f .. %.4f of the rest area" % (d["J"].shape[1], np.nanmin(d["body_area"]),
-                                                                                      np.nanmax(d["body_area"])))
-            if "net_ens_traces" in extra:
-                extra.update(net_strain_r=network.strain_coupling(extra["net_ens_traces"], d["J"]))
-            if st_cells is not None and (len(st_cells["points"]) if "points" in st_cells else st_cells["L"]):
-                c = strain.labels(kf, st_states, **st_cells)
-                extra.update(strain_cell_J=c["J"], strain_cell_l1=c["l1"], strain_cell_l2=c["l2"])
-                if st_dff is not None:
-                    extra.update(strain_artifact_r=strain.artifact_score(c["J"], st_dff))
-        if args.strain_video is not None:
-            n_sv = strain.write_video(kf, st_states, capture.frames[1:1 + len(states)], args.strain_video,
-                                      which=args.strain_which, gain=args.strain_gain, alpha=args.strain_alpha, **vkw)     # state k: frame k + 1
-            print("Strain video: %d frames (%s) in %s" % (n_sv, args.strain_which, args.strain_video))
-    if args.deep_traces and "deep_offset" not in extra:
+            run.cv_cells, run.cv_levels = cellview.layers_from_labels(e["roi_labels"]), cellview.levels(e["dff"])
+        run.cv_points = run.pts[run.inside]                    # (cell s and marker s share a colour)
+        if int(run.cv_cells[0].max()) + 1 != n:                # (the last cells own no pixel: no level for them)
+            run.cv_levels = run.cv_levels[:, :int(run.cv_cells[0].max()) + 1]
+    if run.kept:
+        run.kf.state.renderer.body_rec_end()
+    if run.reg_video is not None:
+        run.reg_video.close()
+        print("Registered video: %d frames in %s" % (run.reg_video.frames, args.registered))
+
+
+def stage_smooth(run, args):
+    sm = run.sm
+    if sm is None:
+        return
+    if len(sm) > 0:
+        xs, var = sm.run()
+        run.extra.update(Xs=xs, Xs_std=np.sqrt(var))
+    else:
+        run.extra.update(Xs=np.zeros((0, 4 * run.kf.N)), Xs_std=np.zeros((0, 4 * run.kf.N)))
+    sm.close()
+    print("Smoothed track: Xs, Xs_std (%d frames)" % len(run.states))
+
+
+def stage_cells_video(run, args):
+    if args.cells_video is None or not len(run.states):
+        return
+    use = args.cells_video_states or ("smoothed" if args.smooth else "filtered")
+    if run.cv_cells is not None and int(run.cv_cells[0].max()) < 0:
+        run.cv_cells = run.cv_levels = None
+    n_cv = cellview.write_video(run.kf, run.extra["Xs"] if use == "smoothed" else run.states, run.tracked_frames, args.cells_video,
+                                cells=run.cv_cells, levels=run.cv_levels, points=run.pts if run.cv_points is None else run.cv_points, **run.vkw)
+    print("Cells video: %d frames (%s states) in %s" % (n_cv, use, args.cells_video))
+
+
+def stage_strain(run, args):
+    extra = run.extra
+    if not ((args.strain or args.strain_video is not None) and len(run.states)):
+        return
+    st_states = extra["Xs"] if args.smooth else np.array(run.states)
+    if args.strain:
+        d = strain.triangles(run.kf, st_states)
+        extra.update(strain_J=d["J"], strain_l1=d["l1"], strain_l2=d["l2"], strain_axis=d["axis"], strain_rotation=d["rotation"],
+                     strain_body_area=d["body_area"])
+        print("Strain: %d triangles, body area %.4f .. %.4f of the rest area" % (d["J"].shape[1], np.nanmin(d["body_area"]), np.nanmax(d["body_area"])))
+        if "net_ens_traces" in extra:
+            extra.update(net_strain_r=network.strain_coupling(extra["net_ens_traces"], d["J"]))
+        st_cells = run.st_cells                                # the cells' labels; without cells the discs of the points
+        if st_cells is None and run.pts is not None:
+            st_cells = {"points": run.pts, "point_radius": args.point_radius}
+        if st_cells is not None and (len(st_cells["points"]) if "points" in st_cells else st_cells["L"]):
+            c = strain.labels(run.kf, st_states, **st_cells)
+            extra.update(strain_cell_J=c["J"], strain_cell_l1=c["l1"], strain_cell_l2=c["l2"])
+            if run.st_dff is not None:
+                extra.update(strain_artifact_r=strain.artifact_score(c["J"], run.st_dff))
+    if args.strain_video is not None:
+        n_sv = strain.write_video(run.kf, st_states, run.tracked_frames, args.strain_video, which=args.strain_which,
+                                  gain=args.strain_gain, alpha=args.strain_alpha, **run.vkw)
+        print("Strain video: %d frames (%s) in %s" % (n_sv, args.strain_which, args.strain_video))
+
+
+def stage_save(run, args):
+    if args.deep_traces and "deep_offset" not in run.extra:
         print("Full-depth traces: nothing read: no frame was tracked, no point lies inside the mesh, or the registered video "
               "did not fit and the points were found, not given")
-    np.savez(args.fn_out, X=np.array(states), err=np.array(errors), p=distmesh.p, t=kf.state.tri, **extra)
-    print("Finished: %d frames, states in %s" % (len(states), args.fn_out))
+    np.savez(args.fn_out, X=np.array(run.states), err=np.array(run.errors), p=run.distmesh.p, t=run.kf.state.tri, **run.extra)
+    print("Finished: %d frames, states in %s" % (len(run.states), args.fn_out))
+
+
+# The order is a contract: every stage says what it must come after, and why.  A new flag's stage goes where its inputs are
+# ready and before whatever rewrites or frees them (DESIGN.md §26).
+STAGES = (
+    stage_results,          # after tracking: what was summed while it ran, first into the states file (beside depth_*)
+    stage_stabilize,        # before every reader of the kept record: they see the stabilised frames; what was summed while tracking did not
+    stage_deform_correct,   # after the stabiliser (it moves pixels across seams: the gain stays the home triangle's), before every other reader
+    stage_pca,              # after both rewrites of the record, before anything else reads it
+    stage_search,           # the record is final; ends the statistics (body_stats_end) once it has searched them
+    stage_cells,            # after the search: it needs the points, and reuses the cells of --find-more
+    stage_events,           # after the cells: their dF/F; before the network (ev_*, net_r_events, then net_*)
+    stage_network,          # after the cells and the events
+    stage_record_end,       # after the last reader of the kept record: body_rec_end frees it; the readout is done with its writer
+    stage_smooth,           # after the record is freed: the smoother's device memory; before what draws at Xs
+    stage_cells_video,      # after the smoother: drawn at Xs with --smooth
+    stage_strain,           # after the smoother (of Xs with --smooth) and the network (net_strain_r)
+    stage_save,             # last: the --deep-traces notice when nothing was read, np.savez, the last line
+)
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    run = Run(parser, args, **check_args(parser, args))
+    if len(sys.argv) == 1 and argv is None:
+        print("No command line arguments provided, using defaults")
+    open_input(run, args)
+    (track_from_flow_files if run.flow_ready else track_in_process)(run, args)
+    for stage in STAGES:
+        stage(run, args)
     return 0
 
 

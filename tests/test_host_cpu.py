@@ -459,7 +459,7 @@ def test_videostream_and_shared_gray_conversion(hm, tmp_path):
     import optical_flow_ext
     import run_kalmanfilter
     assert "pipeline.load_video" in inspect.getsource(optical_flow_ext.main)
-    assert "VideoStream(args.fn_in" in inspect.getsource(run_kalmanfilter.main)
+    assert "VideoStream(args.fn_in" in inspect.getsource(run_kalmanfilter.open_input)
     vs = pipeline.VideoStream(fn, 100)
     assert (vs.nx, vs.ny) == (12, 10) and vs.isOpened()
     mask, ctrs, fd = vs.backsub()
