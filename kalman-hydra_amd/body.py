@@ -26,7 +26,7 @@ import ctypes
 
 import numpy as np
 
-from .pipeline import SlotRing
+from .taps import SlotRing
 
 SUB = 256          # the render's sub-pixel grid (csrc/ekf_kernels.h EKF_SUB)
 

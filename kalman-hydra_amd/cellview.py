@@ -10,6 +10,7 @@ image at a tracked state, the body pixel under it and blends the colours of the 
 import numpy as np
 
 from . import body as _body
+from .taps import write_painted_video
 
 #: twelve B G R colours far apart in hue, none of them gray (the frame under them is)
 _PALETTE = np.array([[0, 0, 255], [0, 255, 0], [255, 0, 0], [0, 255, 255], [255, 0, 255], [255, 255, 0],
@@ -90,8 +91,7 @@ def write_video(kf_or_renderer, states, source, path, cells=None, levels=None, p
     cells: (labels, weights) as layers_from_* give them, or a label image (H, W); None: markers only.  levels: (F, L)
     uint8 (None: 255).  points: (P, 2) body coordinates, followed through the mesh (body.locate / body.track); each
     gets its palette colour.  The frames are uploaded one by one, the views queued on the tracker's stream into a ring of
-    device slots and written by the writer thread of a pipeline.VideoTap: the disk is not waited for.  -> frames written."""
-    from .pipeline import write_painted_video
+    device slots and written by the writer thread of a taps.VideoTap: the disk is not waited for.  -> frames written."""
     r = _body.renderer_of(kf_or_renderer)
     F = len(states)
     if cells is None and points is None:

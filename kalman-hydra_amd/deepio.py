@@ -7,7 +7,7 @@ pixel, one window [lo, hi] for the whole recording from two shares in parts per 
 gamma) gives, and the frames through the table with what the window clipped, frame by frame.  With ``device=None`` each
 runs in NumPy and gives the same bytes: that is the path a machine without a GPU takes.  ``DeepSource`` feeds the
 pipeline's frame ring with the 16-bit pixels, 2 bytes a pixel over the bus, and the device writes the ring's three planes.
-``load_deep`` is what ``pipeline.load_video`` and the command-line tools call; ``depth_option`` turns the tools' flags
+``load_deep`` is what ``sources.load_video`` and the command-line tools call; ``depth_option`` turns the tools' flags
 into the ``depth`` they pass.
 """
 import ctypes
@@ -19,6 +19,7 @@ import struct
 import numpy as np
 
 from . import _lib
+from .devbuf import DeviceBuffer
 
 VALUES = 65536
 #: the window's shares, parts per million: policy, not measurements
@@ -439,7 +440,6 @@ def map_video(stack_or_array, lut, lo, hi, device=0, run=8):
             out[f] = lut[np.clip(a, lo, hi)]
             clipped[f] = np.count_nonzero(a < lo), np.count_nonzero(a > hi)
         return out, clipped
-    from .pipeline import DeviceBuffer
     n = fr.H * fr.W
     words = (run * n + 3) & ~3                                    # the clip words, 4-byte aligned behind the frames
     h = _Handle(fr.W, fr.H, run, device)

@@ -12,6 +12,7 @@ ratio J, the principal stretches l1 >= l2, the axis of l1 in the body frame and 
 import numpy as np
 
 from . import body as _body
+from .taps import write_painted_video
 
 WHICH = ("J", "l1", "l2")
 DEFAULT_GAIN = 256.0        # levels per unit of (value - 1): 0.5 .. 1.5 fills the table
@@ -114,9 +115,8 @@ def write_video(kf_or_renderer, states, source, path, which="J", gain=DEFAULT_GA
                 wire=False, fps=20, video_opts=None):
     """The strain video of a finished track: frame k of `source` (``frame_at(k)`` -> raw frame, ...; or an array
     (frames, H, W) uint8) with `which` (J, l1, l2) of the mesh at states[k] painted on (Renderer.view_strain), written
-    to the AVI `path` (uncompressed; video_opts: AviWriter's codec options) by the writer thread of a pipeline.VideoTap, as cellview.write_video does: the disk is
+    to the AVI `path` (uncompressed; video_opts: AviWriter's codec options) by the writer thread of a taps.VideoTap, as cellview.write_video does: the disk is
     not waited for.  Pass the smoothed states of a run that has them.  -> frames written."""
-    from .pipeline import write_painted_video
     r = _body.renderer_of(kf_or_renderer)
     if which not in WHICH:
         raise ValueError("write_video: which %r (one of %s)" % (which, ", ".join(WHICH)))

@@ -6,7 +6,7 @@ hm_avi_write_chunk around the device's JPEG encoder (hm_mjpeg_*); ``read_avi`` g
 to bottom, as every view of ``Renderer.view`` is.
 
 Reading: ``AviReader`` maps an AVI of any writer (Motion-JPEG or uncompressed 24-bit), ``MjpegDecoder`` wraps hm_mjpeg_dec_*
-(the baseline JPEG decoder on the device, bit-equal to libjpeg), ``decode_avi`` is what ``pipeline.load_video`` calls for an
+(the baseline JPEG decoder on the device, bit-equal to libjpeg), ``decode_avi`` is what ``sources.load_video`` calls for an
 MJPG file and ``AviSource`` feeds the pipeline's frame ring with JPEG bytes that the device decodes in place.
 """
 import ctypes
@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .devbuf import DeviceBuffer
 
 #: view names of Renderer.view -> the view ids of hm_view (include/hydra_mi.h)
 VIEWS = {"raw": 0, "overlay": 1, "texture": 2, "mask": 3, "flowx": 4, "flowy": 5}
@@ -220,7 +221,6 @@ class AviWriter:
         if self._h is None:
             raise ValueError("write to a closed AviWriter")
         if self._dev is None:
-            from .pipeline import DeviceBuffer
             self._slots = MjpegSlots(self.encoder, 1, self.device)
             self._dev = DeviceBuffer(self._slots.cap, self.device)
         self.encoder.encode_dev(d_frame, self._dev.ptr, self._slots.cap, self._slots.size_word(0), stream)
@@ -318,7 +318,7 @@ def decode_jpeg(data):
 
 
 def write_png(path, bgr):
-    """A (H, W, 3) B G R or (H, W) gray uint8 image as PNG (PIL, which pipeline.load_video uses for TIFF)."""
+    """A (H, W, 3) B G R or (H, W) gray uint8 image as PNG (PIL, which sources.load_video uses for TIFF)."""
     from PIL import Image
     a = np.ascontiguousarray(bgr, np.uint8)
     img = Image.fromarray(a[:, :, ::-1].copy() if a.ndim == 3 else a)
@@ -619,7 +619,6 @@ class AviReader:
 
 def decode_avi(reader, device=0, run=8, entropy="auto"):
     """Every frame of a Motion-JPEG AviReader through the device decoder, `run` frames a call -> (frames, H, W) uint8."""
-    from .pipeline import DeviceBuffer
     H, W = reader.shape
     F = len(reader)
     out = np.empty((F, H, W), np.uint8)

@@ -144,7 +144,7 @@ def test_two_series_in_flight_at_the_edges(hm):
                 assert all(same(pipe, k) for k in range(frames - 1)), (B, frames)
     with FlowEKFPipeline(new_filter(), video, masks, flow_batch=3) as pipe:
         pipe.run(0, 2)                                  # a first phase: calibrates, measures a frame of the filter
-        assert pipe._series_s and pipe._frame_s is not None
+        assert pipe.plan.series_s and pipe.plan.frame_s is not None
         pipe.run(2, 5)                                  # the second one sizes its series from that (_next_concurrent)
         assert same(pipe, 7) and same(pipe, 1)          # random access, backwards too
         pipe.run(5, F - 1)
@@ -206,7 +206,7 @@ def test_streaming_frame_ring_equals_resident_video(hm):
     p3.split_start = True                                     # (off by default: measured slower, pipeline.py)
     got3 = []
     p3.run(0, 2, on_frame=lambda k, e: got3.append((kf3.state.X.copy(), e[:4], kf3.niter)))
-    assert len(p3.bfs) == 1 and p3._series_s and p3._frame_s is not None
+    assert len(p3.bfs) == 1 and p3.plan.series_s and p3.plan.frame_s is not None
     p3.run(2, F - 1, on_frame=lambda k, e: got3.append((kf3.state.X.copy(), e[:4], kf3.niter)))
     assert len(p3.bfs) == 2                                   # the second handle was needed
     assert len(got3) == F - 1

@@ -697,78 +697,61 @@ def test_newton_worker_equals_synchronous_call(hm):
 
 
 def test_flow_series_are_sized_from_the_measured_model(hm):
-    """FlowEKFPipeline._first_series / _next_series (host logic, no GPU): with the calibrated times of a series of 2 and of B
+    """flowplan.SeriesPlanner.first / next (host logic, no GPU): with the calibrated times of a series of 2 and of B
     pairs and the filter's frame time, a phase starts with the smallest series the ramp can follow and every next series
     is the largest one that is done (beside the filter: 1.3 x) when the filter is through with the last, at least one
     pair more, never more than B; without measurements the fixed ramp 2, 3, 5, 8."""
-    from hydra_mi.pipeline import FlowEKFPipeline
-    p = object.__new__(FlowEKFPipeline)
-    p.B, p.concurrent_series, p.first_series, p.adaptive_first, p.model_ramp = 8, False, 0, True, True
-    p._series_s, p._frame_s = {}, None
-    assert p._first_series() == 2 and [p._next_series(n) for n in (2, 3, 5, 8)] == [3, 5, 8, 8]
+    from hydra_mi.flowplan import SeriesPlanner
+    p, B = SeriesPlanner(), 8
+    assert (p.first_series, p.adaptive_first, p.model_ramp, p.series_s, p.frame_s) == (0, True, True, {}, None)
+    assert p.first(B, False) == 2 and [p.next(n, B) for n in (2, 3, 5, 8)] == [3, 5, 8, 8]
     # a series of n pairs alone: 3.9 + 1.46 n ms (1024^2 on an MI355X), a frame of the filter 3.2 ms
-    p._series_s = {2: 6.82e-3, 8: 15.58e-3}
-    p._frame_s = 3.2e-3
-    n1 = p._first_series()
+    p.series_s = {2: 6.82e-3, 8: 15.58e-3}
+    p.frame_s = 3.2e-3
+    n1 = p.first(B, False)
     assert n1 == 4                                           # 1.3 x T(4) = 12.7 ms <= 4 x 3.2 ms, 1.3 x T(3) = 10.8 > 9.6
     sizes = [n1]
-    while sizes[-1] < p.B:
-        sizes.append(p._next_series(sizes[-1]))
+    while sizes[-1] < B:
+        sizes.append(p.next(sizes[-1], B))
     assert sizes == [4, 5, 6, 7, 8]
-    assert p._next_series(8) == 8
-    p._frame_s = 10e-3                                       # a slow filter: the flow is never waited for, series double
-    assert p._first_series() == 2 and p._next_series(2) == 4 and p._next_series(4) == 8
-    p.B = 16
-    p._frame_s = 3.2e-3
-    assert [p._next_series(n) for n in (8, 10, 14)] == [10, 14, 16]
+    assert p.next(8, B) == 8
+    p.frame_s = 10e-3                                        # a slow filter: the flow is never waited for, series double
+    assert p.first(B, False) == 2 and p.next(2, B) == 4 and p.next(4, B) == 8
+    B = 16
+    p.frame_s = 3.2e-3
+    assert [p.next(n, B) for n in (8, 10, 14)] == [10, 14, 16]
     p.model_ramp = False                                     # the fixed rule again
-    assert p._next_series(4) == 6
+    assert p.next(4, B) == 6
 
 
 def test_concurrent_series_are_sized_from_what_is_queued_in_front_of_them(hm):
-    """FlowEKFPipeline._next_concurrent (host logic, no GPU): with two handles the next series is the largest one that is done
+    """flowplan.SeriesPlanner.next_concurrent (host logic, no GPU): with two handles the next series is the largest one that is done
     (1.6 x its time alone and what the series in flight still have to do: they share the chip) when the filter has used up
     the pairs that are ready and the series in flight; never smaller
     than the series in front of it, larger when that one is overdue, None without measurements."""
-    import time
-    from hydra_mi.pipeline import FlowEKFPipeline
-    p = object.__new__(FlowEKFPipeline)
-    p.B, p.concurrent_series, p.first_series, p.adaptive_first, p.model_ramp, p.trace = 8, True, 0, True, True, None
-    p._series_s, p._frame_s, p._flying, p._ready, p._cursor, p._flow_late = {}, None, [], (0, 0), 0, False
-    assert p._next_concurrent() is None and p._first_series() == 1
-    p._series_s, p._frame_s = {2: 6.82e-3, 8: 15.58e-3}, 3.7e-3          # a series of n pairs alone: 6.82 + 1.46 (n - 2) ms
-    now = time.perf_counter()
+    from hydra_mi.flowplan import SeriesPlanner
+    p, B, now = SeriesPlanner(), 8, 1000.0
+    assert p.next_concurrent(now, (0, 0), 0, [], B) is None and p.first(B, True) == 1
+    p.series_s, p.frame_s = {2: 6.82e-3, 8: 15.58e-3}, 3.7e-3            # a series of n pairs alone: 6.82 + 1.46 (n - 2) ms
     # the start of a phase: one pair in flight since just now -- needed in 1.6 x 5.36 + 3.7 = 12.3 ms: 1.6 x T(2) = 10.9 fits
-    p._flying = [{"lo": 0, "hi": 1, "t0": now}]
-    assert p._next_concurrent() == 2
+    assert p.next_concurrent(now, (0, 0), 0, [(0, 1, now)], B) == 2
     # two pairs ready and unused, a series of two launched 7 ms ago (2.4 ms of its work left): needed in 14.8 ms, and the
     # chip is shared with what that series still has to do: 1.6 x (2.4 + T(2)) = 14.8 does not quite fit -- as large as the last
-    p._ready, p._cursor = (1, 3), 1
-    p._flying = [{"lo": 3, "hi": 5, "t0": now - 7e-3}]
-    assert p._next_concurrent() == 2
-    p._flying = [{"lo": 3, "hi": 5, "t0": now - 11e-3}]      # ... launched 11 ms ago it is done: 1.6 x T(3) = 13.2 fits
-    assert p._next_concurrent() == 3
+    assert p.next_concurrent(now, (1, 3), 1, [(3, 5, now - 7e-3)], B) == 2
+    assert p.next_concurrent(now, (1, 3), 1, [(3, 5, now - 11e-3)], B) == 3      # ... launched 11 ms ago it is done: 1.6 x T(3) = 13.2 fits
     # full series: 8 ready, 8 in flight: a series of 8 fits many times over
-    p._ready, p._cursor = (10, 18), 10
-    p._flying = [{"lo": 18, "hi": 26, "t0": now - 5e-3}]
-    assert p._next_concurrent() == 8
+    assert p.next_concurrent(now, (10, 18), 10, [(18, 26, now - 5e-3)], B) == 8
     # nothing ready, and the series in flight (3 pairs) should have been done long ago: the flow is late -- a larger series
-    p._ready, p._cursor = (5, 5), 5
-    p._flying = [{"lo": 5, "hi": 8, "t0": now - 1.0}]
-    assert p._next_concurrent() == 5
-    p._flying = [{"lo": 5, "hi": 6, "t0": now - 1.0}]
-    assert p._next_concurrent() == 2
+    assert p.next_concurrent(now, (5, 5), 5, [(5, 8, now - 1.0)], B) == 5
+    assert p.next_concurrent(now, (5, 5), 5, [(5, 6, now - 1.0)], B) == 2
     # never a series of one pair behind the opening one, whatever fits (a slow calibration, a fast filter)
-    p._ready, p._cursor, p._flying, p._frame_s = (5, 6), 5, [{"lo": 6, "hi": 7, "t0": now}], 0.5e-3
-    assert p._next_concurrent() == 2
-    p._frame_s = 3.7e-3
+    p.frame_s = 0.5e-3
+    assert p.next_concurrent(now, (5, 6), 5, [(6, 7, now)], B) == 2
     # a filter that converges in an iteration per frame (0.9 ms): nothing "fits", the series stay as large as the last one,
     # also when both handles are free (nothing in flight: the series the filter works through counts) ...
-    p._frame_s = 0.9e-3
-    p._ready, p._cursor, p._flying = (40, 48), 47, []
-    assert p._next_concurrent() == 8
-    p._ready, p._cursor, p._flying = (40, 43), 42, []
-    assert p._next_concurrent() == 3
+    p.frame_s = 0.9e-3
+    assert p.next_concurrent(now, (40, 48), 47, [], B) == 8
+    assert p.next_concurrent(now, (40, 43), 42, [], B) == 3
     # ... and grow when the filter has just waited for the flow
-    p._flow_late = True
-    assert p._next_concurrent() == 5
+    p.flow_late = True
+    assert p.next_concurrent(now, (40, 43), 42, [], B) == 5
