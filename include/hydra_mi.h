@@ -926,6 +926,75 @@ int hm_body_rec_residual_planes(hm_ctx_t h, int k0, int n_frames, int n_layers, 
 int hm_body_rec_residual_stats_add(hm_ctx_t h, int n_layers, const int32_t *labels, const uint16_t *weights, int L,
                                    const int32_t *traces, const uint8_t *blank, int offset, uint64_t *clipped);
 
+/* Activity waves: per event a latency map of the kept video, its sums over the events, and the sums of a local plane fit
+ * (hydra_mi/waves.py; csrc/waves_kernels.h; tests/waves_ref.py restates the rule in NumPy and Python
+ * integers).  Exact integers throughout.
+ *   Notation    F is the number of recorded frames.  y_k(p) is the byte of the plane of kind `what` (0 raw, 1 baseline,
+ *               2 excess, 3 dF/F) of frame k at box pixel p, exactly as hm_body_rec_planes defines it.  half, q, floor,
+ *               gain are the same arguments with the same ranges.
+ *   Binning     b is 0..8.  For a map pixel p:
+ *               Y_k(p) = sum of y_k(q) over the q of the (2b+1)^2 window round p that are on the frame, in the box and
+ *               in the map.  n(p) = the number of such q.  It is >= 1.  Y <= 255 * 289 < 2^17.
+ *   Windows     pre is 1..64, lead is 0..64, post is 1..256.  Event e has trigger frame t_e (int32).  E is 1..65536.
+ *               Baseline frames: t_e - lead - pre .. t_e - lead - 1.
+ *               Search frames: k_b = t_e - lead .. k_c = t_e + post.
+ *               A trigger with t_e - lead - pre < 0 or t_e + post > F - 1 is HM_ERR_ARG.  The error names the event, the
+ *               trigger and F.  Nothing has run at that point.
+ *   Per (e, p)  Every product below stays under 2^33: pre * M and S <= 64 * 73695 < 2^23; 2 * pre * Y and theta < 2^24;
+ *               256 * d0 <= 256 * theta < 2^32; Lat^2 <= (256 * 257)^2 < 2^33.
+ *               S = sum of Y over the baseline frames.
+ *               M = max of Y over the search frames.
+ *               k_M = the first frame that attains M.
+ *               R = pre * M - S (int32; may be <= 0).
+ *               theta = S + pre * M.
+ *               k_x = the first search frame with 2 * pre * Y_k >= theta.
+ *   Sub-frame step, when k_x > k_b:
+ *               d0 = theta - 2 * pre * Y_{k_x - 1}.
+ *               d1 = 2 * pre * (Y_{k_x} - Y_{k_x - 1}).  Then d1 >= d0 > 0.
+ *               frac = floor(256 * d0 / d1), in 0..256.
+ *               Latency Lat = 256 * (k_x - 1 - t_e) + frac, int32, in 1/256 frame relative to the trigger.
+ *   Code `why`, uint8.  The first rule that applies wins:
+ *               255   p off the map                                              off the map
+ *               2     R < pre * n(p) * min_rise (min_rise 1..255 grey levels)    rise too small
+ *               3     k_x == k_b                                                 already at half height when the search starts
+ *               1     k_M == k_c                                                 valid, still rising at the window's end
+ *               0     otherwise                                                  valid
+ *               Lat = INT32_MIN wherever why >= 2.  (R < 0 leaves no crossing: it is code 2.)  `rise` is R on the map
+ *               whatever the code, and 0 off it.
+ *   Across the events of one call.  Per pixel, over the events with why <= 1:
+ *               cnt (uint32).  sum_lat = sum of Lat (int64).  sum_lat2 = sum of Lat^2 (int64).  This is exact:
+ *               Lat^2 < 2^33, E <= 2^16.
+ *   Local fit per event.  step is 1..64, Rf is 1..16.
+ *               Node (i, j) sits at box column c0 + i * step, row r0 + j * step.  i < ceil(bw / step), j < ceil(bh / step).
+ *               Nodes are row-major.  The sums run over the pixels q = node + (dx, dy) with |dx|, |dy| <= Rf that are on
+ *               the frame, in the map and valid in this event.  Nine int64 sums per node: n, sum dx, sum dy, sum dx^2,
+ *               sum dx * dy, sum dy^2, sum Lat, sum dx * Lat, sum dy * Lat.  A node off the map is only a position; it
+ *               still sums its valid neighbours.  No validity test is made on the node itself.
+ *   waves       One call, any output may be NULL.  n_bin: W*H, n(p), 0 off the map.  lat, rise, why: E planes of W*H
+ *               each; outside the box as off the map (why 255, Lat INT32_MIN, rise 0).  cnt, sum_lat, sum_lat2: W*H, 0
+ *               off the map.  fit: E x nodes x 9.
+ *   wave_nodes  The grid of `step`: nx = ceil(bw / step), ny = ceil(bh / step), and the box's corner c0, r0 (any may be
+ *               NULL).  It needs the record begun (HM_ERR_STATE otherwise), not a frame in it.
+ *   Waiting, state errors and the empty-map case are those of hm_body_rec_seed_sums.  A map without a pixel gives why 255
+ *   everywhere (so Lat INT32_MIN) and zeros elsewhere.  It is not an error.  Every argument out of range is HM_ERR_ARG
+ *   with the numbers in hm_last_error: the detrend parameters that hm_body_rec_planes refuses, E, NULL triggers, b, pre,
+ *   lead, post, min_rise, step and Rf before the handle is looked at, the triggers against F after it.  The record, the
+ *   map, the statistics and the tracker do not change by a bit.  A refusal leaves the record usable.
+ *   One launch of the latency kernel takes hm_ctx_tune "rec_wv_frames" events (1..65535, default 16), and no more than
+ *   keep its planes of lat, rise and why and, where `fit` is asked for, its sums of the fit (72 bytes per node and event)
+ *   below 1 GiB together (one event at least); of kinds 1..3 a launch takes consecutive
+ *   events only as long as their windows together span no more than pre + lead + post + 1 frames, whose planes
+ *   (k_rec_running) go into a work buffer of the call's own in the record's layout.  That buffer, the launch's planes and
+ *   the call's sums are one allocation that is freed on every return including errors; it does not count against
+ *   "rec_scratch_bytes".  The bytes of every output are the same for every value of both keys. */
+int hm_body_rec_waves(hm_ctx_t h, int E, const int32_t *triggers, int what, int half, int q, int floor, int gain,
+                      int b, int pre, int lead, int post, int min_rise, int step, int Rf,
+                      uint16_t *n_bin,            /* W*H, n(p), 0 off the map */
+                      int32_t *lat, int32_t *rise, uint8_t *why,   /* E planes of W*H each; outside the box as off the map */
+                      uint32_t *cnt, int64_t *sum_lat, int64_t *sum_lat2,   /* W*H */
+                      int64_t *fit);              /* E x nodes x 9 */
+int hm_body_rec_wave_nodes(hm_ctx_t h, int step, int *nx, int *ny, int *c0, int *r0);
+
 /* The flow tool's preview (reference src/optical_flow_ext.cpp:172-281 colour code, :336-389 the
  * blend into <prefix>.avi): n frames (channels 1: gray, 3: B G R) and their flow planes fx, fy
  * (n x H x W f32 each) -> out n x H x W x 3, round((2 frame + 3 wheel) / 5) per channel.  wheel: the

@@ -181,6 +181,8 @@ SIGNATURES = {
                                                    ctypes.c_double, ctypes.c_double]),
     "hm_body_rec_event_sums": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_vp]),
+    "hm_body_rec_waves": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp] + [ctypes.c_int] * 12 + [c_vp] * 8),
+    "hm_body_rec_wave_nodes": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "hm_body_rec_residual_planes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp,
                                                    c_vp, ctypes.c_int, c_vp, c_vp]),
     "hm_body_rec_residual_stats_add": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int,

@@ -171,6 +171,7 @@ struct RecState {
     int null_frames = 256;           // hm_ctx_tune "rec_null_frames": frames per run of k_rec_trace_null (hm_body_rec_trace_null)
     int tm_frames = 64;              // hm_ctx_tune "rec_tm_frames": frames per run of k_rec_tri_maps (hm_body_rec_tri_maps)
     int gram_bytes = 16384;          // hm_ctx_tune "rec_gram_bytes": bytes per run of k_rec_gram (hm_body_rec_gram)
+    int wv_frames = 16;              // hm_ctx_tune "rec_wv_frames": events per launch of k_rec_wv_lat (hm_body_rec_waves)
     unsigned long long max = 0;      // the budget in bytes
     RecBox box = {0, 0, 0, 0, 0, 0, 0};
     std::vector<uint8_t *> chunks;
@@ -187,6 +188,9 @@ struct RecState {
     // there while the call runs and freed when it returns.
     size_t ev_bytes = (size_t)16 << 30;
     uint8_t *ev = nullptr, *ev_out = nullptr;
+    // hm_body_rec_waves: the map cut to the box, a launch's planes and results, the call's sums and, for kinds 1..3, a
+    // window's planes; there while the call runs, freed when it returns
+    uint8_t *wv = nullptr;
 };
 
 // ---- the filter's state, grouped as the readout's is.  Each struct says who writes it. ----------------------------------------

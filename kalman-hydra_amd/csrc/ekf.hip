@@ -287,6 +287,7 @@ static const struct TuneKey {
     {"rec_map_frames", 1, REC_MAP_MAX, 1, TUNE_SET(rec.map_frames), nullptr},
     {"rec_null_frames", 1, REC_NULL_MAX, 1, TUNE_SET(rec.null_frames), nullptr},
     {"rec_tm_frames", 1, REC_TM_MAX, 1, TUNE_SET(rec.tm_frames), nullptr},      // likewise: the maps against the pixel's own triangle
+    {"rec_wv_frames", 1, REC_WV_MAX, 1, TUNE_SET(rec.wv_frames), nullptr},      // events per launch of hm_body_rec_waves (same bytes for every value)
     // bytes per run of k_rec_gram (same results for every value)
     {"rec_gram_bytes", 64, REC_GRAM_BYTES_MAX, 64, TUNE_SET(rec.gram_bytes), "must be a multiple of 64 in 64..131008"},
     {"rec_scratch_bytes", 1, 1 << 30, 1, TUNE_SET(rec.scr_bytes), nullptr},    // tests only: the most scratch of a hm_body_rec_* call (same results for every value)

@@ -384,6 +384,7 @@ struct RecBox {
 #define REC_RES_MAX (1 << 24)          // the most frames of a run of k_rec_residual (hm_ctx_tune "rec_res_frames"; REC_MAX_FRAMES)
 #define REC_MAP_MAX 256                // the most frames of a run of k_rec_trace_maps (hm_ctx_tune "rec_map_frames"): 32-bit sums hold
 #define REC_NULL_MAX 256               // the most frames of a run of k_rec_trace_null (hm_ctx_tune "rec_null_frames"): 255 x 32767 x 256 < 2^31
+#define REC_WV_MAX 65535               // the most events of a launch of k_rec_wv_lat (hm_ctx_tune "rec_wv_frames"): its blockIdx.y
 #define REC_TM_MAX 256                 // the most frames of a run of k_rec_tri_maps (hm_ctx_tune "rec_tm_frames"): 255 x 32767 x 256 < 2^31
 // hm_body_rec_gram: the most frames of one Gram matrix (G is 8192^2 x 8 bytes = 512 MiB there), and the most bytes of a run of
 // k_rec_gram (hm_ctx_tune "rec_gram_bytes", multiples of 64).  The run's 32-bit sums hold products of signed bytes x = v - 128,

@@ -1,7 +1,7 @@
 // The registered video kept on the device (hm_body_rec_*): the record itself, the reductions over it, its residual motion
-// (match, shift, field, warp), the running baseline, the events per pixel and the residual of the cells' model.  Host orchestration and C-ABI
+// (match, shift, field, warp), the running baseline, the events per pixel, the residual of the cells' model and the activity waves.  Host orchestration and C-ABI
 // (include/hydra_mi.h); the kernels are in roi_kernels.h, stab_kernels.h, detrend_kernels.h, events_kernels.h, residual_kernels.h and
-// network_kernels.h, network_null_kernels.h, deform_kernels.h and gram_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses
+// network_kernels.h, network_null_kernels.h, deform_kernels.h, gram_kernels.h and waves_kernels.h, which this translation unit alone compiles.  Of the handle (ctx.h) it uses
 // rec, the body map (body.tri, body.h_tri), the
 // registered plane (body.reg) and the statistics' counters, and reads W, H, device, own and stream.  readout.hip queues the
 // warp: it reserves a frame's slot and queues the copy into it through body_rec_slot and body_rec_queue_copy, and this file
@@ -16,6 +16,7 @@
 #include "network_null_kernels.h"
 #include "deform_kernels.h"
 #include "gram_kernels.h"
+#include "waves_kernels.h"
 #include <cmath>
 #include <algorithm>
 #include <cstring>
@@ -1311,4 +1312,153 @@ extern "C" int hm_body_rec_residual_stats_add(hm_ctx_t h, int n_layers, const in
         HM_HIP(hipStreamSynchronize(h->stream));
         return res_clipped(h, g, clipped);
     });
+}
+
+// ---- activity waves: latency maps per event, their sums over the events, the local fits' sums (waves_kernels.h) --------
+static int wv_step_ok(const char *who, int step)
+{
+    HM_ARG(step >= 1 && step <= REC_WV_STEP_MAX, "%s: node step %d outside 1..%d", who, step, REC_WV_STEP_MAX);
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_wave_nodes(hm_ctx_t h, int step, int *nx, int *ny, int *c0, int *r0)
+{
+    HM_TRY(wv_step_ok("hm_body_rec_wave_nodes", step));
+    HM_ARG(h != nullptr, "hm_body_rec_wave_nodes: NULL handle");
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_begun(h, "hm_body_rec_wave_nodes"));
+    const RecBox &b = h->rec.box;
+    if (nx) *nx = hm_cdiv(b.bw, step);
+    if (ny) *ny = hm_cdiv(b.bh, step);
+    if (c0) *c0 = b.c0;
+    if (r0) *r0 = b.r0;
+    return HM_OK;
+}
+
+// a plane of the box on the device -> a full W x H plane of the caller's, `fill` outside the box
+template <typename T>
+static int wv_expand(const hm_ctx *h, const T *d_src, T fill, T *out)
+{
+    const RecBox &b = h->rec.box;
+    const size_t es = sizeof(T);
+    std::fill(out, out + (size_t)h->W * h->H, fill);
+    HM_HIP(hipMemcpy2D(out + (size_t)b.r0 * h->W + b.c0, (size_t)h->W * es, d_src, (size_t)b.pitch * es, (size_t)b.bw * es, (size_t)b.bh,
+                       hipMemcpyDeviceToHost));
+    return HM_OK;
+}
+
+extern "C" int hm_body_rec_waves(hm_ctx_t h, int E, const int32_t *triggers, int what, int half, int q, int floor, int gain, int bin,
+                                 int pre, int lead, int post, int min_rise, int step, int Rf, uint16_t *n_bin, int32_t *lat,
+                                 int32_t *rise, uint8_t *why, uint32_t *cnt, int64_t *sum_lat, int64_t *sum_lat2, int64_t *fit)
+{
+    const char *who = "hm_body_rec_waves";
+    HM_TRY(det_args_ok(who, what, half, q, floor, gain));
+    HM_ARG(E >= 1 && E <= REC_WV_EMAX, "%s: %d events outside 1..%d", who, E, REC_WV_EMAX);
+    HM_ARG(triggers != nullptr, "%s: NULL triggers", who);
+    HM_ARG(bin >= 0 && bin <= REC_WV_BMAX, "%s: bin radius %d outside 0..%d", who, bin, REC_WV_BMAX);
+    HM_ARG(pre >= 1 && pre <= REC_WV_PRE_MAX, "%s: pre %d outside 1..%d", who, pre, REC_WV_PRE_MAX);
+    HM_ARG(lead >= 0 && lead <= REC_WV_LEAD_MAX, "%s: lead %d outside 0..%d", who, lead, REC_WV_LEAD_MAX);
+    HM_ARG(post >= 1 && post <= REC_WV_POST_MAX, "%s: post %d outside 1..%d", who, post, REC_WV_POST_MAX);
+    HM_ARG(min_rise >= 1 && min_rise <= 255, "%s: min_rise %d outside 1..255", who, min_rise);
+    HM_TRY(wv_step_ok(who, step));
+    HM_ARG(Rf >= 1 && Rf <= REC_WV_RF_MAX, "%s: fit radius %d outside 1..%d", who, Rf, REC_WV_RF_MAX);
+    HM_ARG(h != nullptr, "%s: NULL handle", who);
+    HM_JOIN_LAZY(h);
+    HM_TRY(body_rec_ready(h, who));
+    const int F = h->rec.frames;
+    for (int e = 0; e < E; e++) {
+        const long long t = triggers[e];
+        HM_ARG(t - lead - pre >= 0 && t + post <= F - 1, "%s: event %d: trigger %lld needs the frames %lld .. %lld (pre %d, lead %d, "
+               "post %d) of a record of F = %d frames", who, e, t, t - lead - pre, t + post, pre, lead, post, F);
+    }
+    const bool want_sums = cnt || sum_lat || sum_lat2, want_lat = lat || rise || why || want_sums || fit;
+    if (!(n_bin || want_lat)) {
+        HM_HIP(hipStreamSynchronize(h->stream));
+        return HM_OK;
+    }
+    const RecBox &b = h->rec.box;
+    const size_t nb = (size_t)b.pitch * b.bh, px = (size_t)h->W * h->H;
+    const int nx = hm_cdiv(b.bw, step), ny = hm_cdiv(b.bh, step), nodes = nx * ny, frames = pre + lead + post + 1;
+    // the events of a launch: rec.wv_frames at most, and no more than keep their planes and the fit's sums below 1 GiB (one at least)
+    const size_t per_event = 9 * nb + (fit ? (size_t)nodes * 9 * sizeof(long long) : 0);
+    const int per = !want_lat ? 0 : (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(E, h->rec.wv_frames), ((size_t)1 << 30) / per_event));
+    RecWaves g;
+    uint8_t *d_mask = nullptr, *d_planes = nullptr;
+    uint16_t *d_nbin = nullptr;
+    int *d_trig = nullptr;
+    unsigned *d_cnt = nullptr;
+    long long *d_s1 = nullptr, *d_s2 = nullptr, *d_fit = nullptr;
+    auto lay = [&](RecCarve &cv) {
+        d_mask = cv.take<uint8_t>(nb);
+        d_nbin = cv.take<uint16_t>(nb);
+        d_trig = cv.take<int>((size_t)per);
+        g.lat = cv.take<int>((size_t)per * nb);
+        g.rise = cv.take<int>((size_t)per * nb);
+        g.why = cv.take<uint8_t>((size_t)per * nb);
+        d_cnt = cv.take<unsigned>(want_sums ? nb : 0);
+        d_s1 = cv.take<long long>(want_sums ? nb : 0);
+        d_s2 = cv.take<long long>(want_sums ? nb : 0);
+        d_fit = cv.take<long long>(fit ? (size_t)per * nodes * 9 : 0);
+        d_planes = cv.take<uint8_t>(what != 0 && want_lat ? (size_t)frames * b.fs : 0);
+    };
+    const DetPlanes d = {what, half, q, floor, gain};
+    const int rc = [&]() -> int {
+        RecCarve cv = {nullptr, 0};
+        lay(cv);
+        HM_HIP(h->own.grow(&h->rec.wv, cv.off));
+        cv = {h->rec.wv, 0};
+        lay(cv);
+        hipLaunchKernelGGL(k_rec_wv_mask, dim3(hm_cdiv((int)nb, 256)), dim3(256), 0, h->stream, h->W, b, (const int *)h->body.tri, d_mask);
+        hipLaunchKernelGGL(k_rec_wv_nbin, dim3(hm_cdiv((int)nb, 256)), dim3(256), 0, h->stream, b, bin, (const uint8_t *)d_mask, d_nbin);
+        HM_HIP(hipGetLastError());
+        if (want_sums) {
+            HM_HIP(hipMemsetAsync(d_cnt, 0, nb * sizeof(unsigned), h->stream));
+            HM_HIP(hipMemsetAsync(d_s1, 0, nb * 8, h->stream));
+            HM_HIP(hipMemsetAsync(d_s2, 0, nb * 8, h->stream));
+        }
+        HM_HIP(hipStreamSynchronize(h->stream));
+        if (n_bin) HM_TRY(wv_expand<uint16_t>(h, d_nbin, 0, n_bin));
+        g.b = b; g.chunks = (const uint8_t *const *)h->rec.tab; g.src = nullptr; g.ks = 0;
+        g.bin = bin; g.pre = pre; g.lead = lead; g.post = post; g.min_rise = min_rise; g.trig = d_trig; g.mask = d_mask; g.nbin = d_nbin;
+        const int tiles = hm_cdiv(b.bw, WV_TW) * hm_cdiv(b.bh, WV_TH);
+        for (int e0 = 0; want_lat && e0 < E;) {
+            // the launch's events: as many as `per`; of kinds 1..3, as long as their windows together span no more frames than one
+            // window's planes take (events of one trigger, then)
+            int m = 1, lo = triggers[e0] - lead - pre, hi = triggers[e0] + post;
+            for (; e0 + m < E && m < per; m++) {
+                const int l1 = std::min(lo, triggers[e0 + m] - lead - pre), h1 = std::max(hi, triggers[e0 + m] + post);
+                if (what != 0 && h1 - l1 + 1 > frames) break;
+                lo = l1; hi = h1;
+            }
+            HM_HIP(hipMemcpyAsync(d_trig, triggers + e0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            if (what != 0) {
+                HM_TRY(det_queue(h, d, lo, hi - lo + 1, d_planes));
+                g.src = d_planes; g.ks = lo;
+            }
+            hipLaunchKernelGGL(k_rec_wv_lat, dim3(tiles, m), dim3(256), 0, h->stream, g);
+            if (want_sums)
+                hipLaunchKernelGGL(k_rec_wv_sums, dim3(hm_cdiv((int)nb, 256)), dim3(256), 0, h->stream, b, m, (const int *)g.lat, d_cnt,
+                                   d_s1, d_s2);
+            if (fit)
+                hipLaunchKernelGGL(k_rec_wv_fit, dim3(nodes, m), dim3(64), 0, h->stream, b, step, Rf, nx, (const int *)g.lat, d_fit);
+            HM_HIP(hipGetLastError());
+            HM_HIP(hipStreamSynchronize(h->stream));
+            for (int e = 0; e < m; e++) {
+                if (lat) HM_TRY(wv_expand<int32_t>(h, g.lat + (size_t)e * nb, REC_WV_NONE, lat + (size_t)(e0 + e) * px));
+                if (rise) HM_TRY(wv_expand<int32_t>(h, g.rise + (size_t)e * nb, 0, rise + (size_t)(e0 + e) * px));
+                if (why) HM_TRY(wv_expand<uint8_t>(h, g.why + (size_t)e * nb, 255, why + (size_t)(e0 + e) * px));
+            }
+            if (fit) HM_HIP(hipMemcpy(fit + (size_t)e0 * nodes * 9, d_fit, (size_t)m * nodes * 9 * 8, hipMemcpyDeviceToHost));
+            e0 += m;
+        }
+        if (cnt) HM_TRY(rec_expand_planes(h, d_cnt, 1, cnt));
+        if (sum_lat) HM_TRY(rec_expand_planes(h, d_s1, 1, sum_lat));
+        if (sum_lat2) HM_TRY(rec_expand_planes(h, d_s2, 1, sum_lat2));
+        return HM_OK;
+    }();
+    if (rc) (void)hipStreamSynchronize(h->stream);
+    const hipError_t fe = h->own.free(&h->rec.wv);
+    if (rc) return rc;
+    HM_HIP(fe);
+    return HM_OK;
 }

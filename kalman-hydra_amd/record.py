@@ -331,6 +331,37 @@ class Record:
                                                      float(s_min), _lib.ptr(count), _lib.ptr(total)), "hm_body_rec_event_sums")
         return count, total
 
+    # -- activity waves: latency per event and pixel, its sums, the local fits' sums (hm_body_rec_waves; hydra_mi.waves) -----
+    WAVE_OUTPUTS = ("n_bin", "lat", "rise", "why", "cnt", "sum_lat", "sum_lat2", "fit")
+
+    def body_rec_wave_nodes(self, step):
+        """hm_body_rec_wave_nodes: -> (nx, ny, c0, r0): the grid of fit nodes of body_rec_waves, node (i, j) at column
+        c0 + i step, row r0 + j step of the frame, row-major."""
+        v = [ctypes.c_int(0) for _ in range(4)]
+        _lib.check(_lib.lib().hm_body_rec_wave_nodes(self._h, int(step), *[ctypes.byref(x) for x in v]), "hm_body_rec_wave_nodes")
+        return tuple(int(x.value) for x in v)
+
+    def body_rec_waves(self, triggers, what, half, q, floor=1, gain=1, b=2, pre=8, lead=8, post=24, min_rise=8, step=8, Rf=6,
+                       want=WAVE_OUTPUTS):
+        """hm_body_rec_waves: per trigger frame (int32, E of them) and pixel the latency at which the binned plane of kind
+        `what` (as body_rec_planes) crosses half of its rise, in 1/256 frame relative to the trigger -> a dict of the
+        outputs named in `want`: n_bin (H, W) uint16; lat, rise (E, H, W) int32 and why (E, H, W) uint8 (lat is INT32_MIN
+        where why >= 2); cnt (H, W) uint32, sum_lat, sum_lat2 (H, W) int64 over the events with why <= 1; fit
+        (E, nodes, 9) int64: n, sum dx, dy, dx^2, dx dy, dy^2, Lat, dx Lat, dy Lat over the valid pixels within Rf of a node."""
+        what = self._kind(what)
+        t = np.ascontiguousarray(triggers, np.int32).reshape(-1)
+        E, H, W = int(t.size), self.ny, self.nx
+        shapes = dict(n_bin=((H, W), np.uint16), lat=((E, H, W), np.int32), rise=((E, H, W), np.int32), why=((E, H, W), np.uint8),
+                      cnt=((H, W), np.uint32), sum_lat=((H, W), np.int64), sum_lat2=((H, W), np.int64))
+        if "fit" in want and E:
+            nx, ny = self.body_rec_wave_nodes(step)[:2]
+            shapes["fit"] = ((E, nx * ny, 9), np.int64)
+        out = self._wanted(want, **shapes)
+        _lib.check(_lib.lib().hm_body_rec_waves(self._h, E, _lib.ptr(t), what, int(half), int(q), int(floor), int(gain), int(b),
+                                                int(pre), int(lead), int(post), int(min_rise), int(step), int(Rf),
+                                                *[_lib.ptr(out.get(k)) for k in self.WAVE_OUTPUTS]), "hm_body_rec_waves")
+        return out
+
     # -- the residual of the record under a model of the cells (hm_body_rec_residual_*; hydra_mi.residual) -----
     def _residual_args(self, who, labels, weights, traces, blank):
         lab = np.ascontiguousarray(labels, np.int32)

@@ -156,6 +156,26 @@ Same arguments as the reference CLI (reference run_kalmanfilter.py:38-53):
                      uint32: frames with an event >= s_min), ev_sum_image (H x W: the events summed, rounded to float32 here);
                      ev_params: g, lambda, s_min of the pixels, then half, q, floor, gain of their dF/F bytes.  With
                      --network also net_r_events: network.coactivity of ev_s, as net_r is of the traces.
+    --waves          with a kept record (--rois, --demix, --detrend, --dff-video) and --network or --waves-frames: where every
+                     ensemble's events start and how they travel (hydra_mi.waves).  The triggers are the onsets of the
+                     ensembles' traces (waves.triggers) whose windows lie inside the record; around each, every map pixel's
+                     dF/F bytes, summed over bins of (2 --waves-bin + 1)^2 pixels (default 2), are followed on the device from a
+                     baseline of --waves-pre frames (8) that ends --waves-lead frames (8) before the trigger to their maximum
+                     within --waves-post frames (24) after it; the latency is the sub-frame time of half that rise, kept where
+                     the rise is at least --waves-min-rise grey levels (8).  wave_triggers, wave_trigger_ens (events);
+                     wave_lat_mean, wave_lat_sd (ensembles x H x W, frames after the trigger, float32), wave_count (uint32: the
+                     events a pixel is valid in); wave_nodes (nodes x 2: column, row of a grid every --waves-step pixels, 8),
+                     wave_velocity (ensembles x nodes x 2, pixels per frame: per node the median over the events of the plane
+                     fit within --waves-fit pixels, 6), wave_speed (ensembles: its median length over the nodes),
+                     wave_origin (ensembles x 2: column, row of the least mean latency; -1 none), wave_params: pre, lead,
+                     post, bin, min_rise, step, fit, then half, q, floor, gain of the dF/F bytes.
+    --waves-frames FILE   with --waves: the trigger frames of one ensemble from a text file of whole numbers (frames of the
+                     record, 0 the first tracked frame) instead of the ensembles of --network.
+    --waves-keep     with --waves: also wave_lat, wave_rise (events x H x W, int32), wave_why (uint8: 0 valid, 1 still rising at
+                     the window's end, 2 rise too small, 3 at half height when the search starts, 255 off the map) and
+                     wave_fit (events x nodes x 9, int64: the fit's sums).
+    --waves-map OUT.png   with --waves: the mean latency of the ensemble with the most valid pixels, early blue to late red,
+                     over the mean registered frame.
     --events-video OUT.avi   with --events: the event bytes min(255, floor(s + 0.5)) of every pixel and frame in the body
                      frame, grey (hydra_mi.events.event_video), through the writer of --dff-video.
     --pca K          with --rois or --demix: the K dominant modes of the kept registered video with nobody naming a cell
@@ -196,7 +216,7 @@ import numpy as np
 
 import hydra_mi  # noqa: F401
 from hydra_mi import (cellview, deepio, deeptrace, deform, demix, detrend, events, kalman, network, pca, residual, roi,
-                      stabilize, strain)
+                      stabilize, strain, waves)
 from hydra_mi.body import (BodyReadout, read_out, read_out_recorded, read_points_csv, record_bytes, write_points_csv,
                            write_points_txt)
 from hydra_mi.distmesh_dyn import DistMesh
@@ -304,6 +324,17 @@ def build_parser():
     parser.add_argument("--pca", default=None, type=int, metavar="K",
                         help="with --rois or --demix: the K dominant modes of the kept registered video (pca_* arrays)")
     parser.add_argument("--pca-frames", action="store_true", help="with --pca: also pca_frame_r, Pearson's r of every two frames")
+    parser.add_argument("--waves", action="store_true", help="with a kept record and --network or --waves-frames: latency maps, velocity and origin of every ensemble's events (wave_* arrays)")
+    parser.add_argument("--waves-frames", default=None, metavar="FILE", help="with --waves: the trigger frames of one ensemble, a text file of whole numbers")
+    parser.add_argument("--waves-pre", default=None, type=int, help="with --waves: frames of the baseline (default %d)" % waves.DEFAULT_PRE)
+    parser.add_argument("--waves-lead", default=None, type=int, help="with --waves: frames before the trigger at which the search starts (default %d)" % waves.DEFAULT_LEAD)
+    parser.add_argument("--waves-post", default=None, type=int, help="with --waves: frames after the trigger at which the search ends (default %d)" % waves.DEFAULT_POST)
+    parser.add_argument("--waves-bin", default=None, type=int, help="with --waves: bins of (2 N + 1)^2 pixels (default %d)" % waves.DEFAULT_BIN)
+    parser.add_argument("--waves-min-rise", default=None, type=int, help="with --waves: the least rise in grey levels (default %d)" % waves.DEFAULT_MIN_RISE)
+    parser.add_argument("--waves-step", default=None, type=int, help="with --waves: a fit node every N pixels (default %d)" % waves.DEFAULT_STEP)
+    parser.add_argument("--waves-fit", default=None, type=int, help="with --waves: the fit takes the pixels within N of a node (default %d)" % waves.DEFAULT_FIT)
+    parser.add_argument("--waves-keep", action="store_true", help="with --waves: also the planes per event (wave_lat, wave_rise, wave_why, wave_fit)")
+    parser.add_argument("--waves-map", default=None, metavar="OUT.png", help="with --waves: write the mean latency map here (.png)")
     parser.add_argument("--network-seed", default=0, type=int, help="with --network-null: the seed the shifts are drawn with")
     parser.add_argument("--events", action="store_true", help="with --rois or --demix: events behind the dF/F traces and per pixel (ev_* arrays)")
     parser.add_argument("--events-g", default=None, type=float, help="the decay per frame, 0 < g < 1 (default: estimated per cell)")
@@ -388,7 +419,8 @@ def check_args(parser, args):
     if args.resummarize and (not args.stabilize or args.detrend):
         parser.error("--resummarize sums the stabilised record up: it needs --stabilize, and not --detrend")
     keep_record = args.detrend or args.resummarize or args.dff_video is not None
-    if (keep_record or args.events) and not (0 <= args.detrend_half <= 1024 and 0 <= args.detrend_q <= 100 and 1 <= args.dff_floor <= 255
+    check_waves_args(parser, args, keep_record)
+    if (keep_record or args.events or args.waves) and not (0 <= args.detrend_half <= 1024 and 0 <= args.detrend_q <= 100 and 1 <= args.dff_floor <= 255
                             and 1 <= args.dff_gain <= 65535):
         parser.error("the running baseline needs a --detrend-half in 0..1024, a --detrend-q in 0..100, a --dff-floor in 1..255 "
                      "and a --dff-gain in 1..65535")
@@ -422,6 +454,58 @@ def check_args(parser, args):
     elif args.deep_offset != 0.0:
         parser.error("--deep-offset goes with --deep-traces")
     return dict(depth=depth, vopts=vopts, vkw=vkw, gopts=gopts, keep_record=keep_record)
+
+
+WAVES_OPTIONS = (("waves_pre", "pre", waves.DEFAULT_PRE, 1, waves.PRE_MAX), ("waves_lead", "lead", waves.DEFAULT_LEAD, 0, waves.LEAD_MAX),
+                 ("waves_post", "post", waves.DEFAULT_POST, 1, waves.POST_MAX), ("waves_bin", "b", waves.DEFAULT_BIN, 0, waves.B_MAX),
+                 ("waves_min_rise", "min_rise", waves.DEFAULT_MIN_RISE, 1, 255), ("waves_step", "step", waves.DEFAULT_STEP, 1, waves.STEP_MAX),
+                 ("waves_fit", "Rf", waves.DEFAULT_FIT, 1, waves.RF_MAX))
+
+
+def read_trigger_frames(path):
+    """The file of --waves-frames: whole numbers separated by white space -> int64 array; ValueError says what is wrong"""
+    try:
+        with open(path) as f:
+            words = f.read().split()
+    except OSError as exc:
+        raise ValueError("--waves-frames %s cannot be read: %s" % (path, exc.strerror))
+    try:
+        return np.array([int(w) for w in words], np.int64)
+    except ValueError:
+        raise ValueError("--waves-frames %s holds something that is no whole number" % path)
+
+
+def check_waves_args(parser, args, keep_record):
+    """The refusals of --waves and its options, in check_args' style and order: an option without --waves, --waves without a
+    kept record, --waves without triggers, a number out of range, a file of trigger frames that cannot be read (it is read
+    here, into args.waves_trigger_frames, before anything is tracked).  Then the defaults are filled in."""
+    flag = lambda name: "--" + name.replace("_", "-")
+    given = [flag(n) for n in ("waves_frames", "waves_map") + tuple(o[0] for o in WAVES_OPTIONS) if getattr(args, n) is not None]
+    given += ["--waves-keep"] if args.waves_keep else []
+    message = None
+    if given and not args.waves:
+        message = "%s goes with --waves" % given[0]
+    elif args.waves and not (args.rois or keep_record):
+        message = "--waves works on the kept record: it needs --rois or --demix"
+    elif args.waves and not (args.network or args.waves_frames is not None):
+        message = "--waves needs trigger frames: the ensembles of --network or a file of them (--waves-frames)"
+    elif args.waves:
+        for name, _, _, lo, hi in WAVES_OPTIONS:
+            v = getattr(args, name)
+            if v is not None and not lo <= v <= hi:
+                message = "%s %d outside %d..%d" % (flag(name), v, lo, hi)
+                break
+        args.waves_trigger_frames = None
+        if message is None and args.waves_frames is not None:
+            try:
+                args.waves_trigger_frames = read_trigger_frames(args.waves_frames)
+            except ValueError as exc:
+                message = str(exc)
+    if message is not None:
+        parser.error(message)
+    for name, _, default, _, _ in WAVES_OPTIONS:
+        if getattr(args, name) is None:
+            setattr(args, name, default)
 
 
 class Run:
@@ -805,6 +889,44 @@ def stage_network(run, args):
         print("Ensemble map: %s" % args.network_map)
 
 
+def stage_waves(run, args):
+    if not args.waves:
+        return
+    if not run.record_ready:
+        print("Waves: nothing read: the registered video was not kept, or no frame was tracked")
+        return
+    par = {key: getattr(args, name) for name, key, _, _, _ in WAVES_OPTIONS}
+    win = {k: par[k] for k in ("pre", "lead", "post")}
+    F = run.body.r.body_rec_count()
+    if args.waves_frames is not None:
+        t = args.waves_trigger_frames
+        ok = waves.admissible(t, F=F, **win)
+        if not ok.all():
+            print("Waves: %d of %d trigger frames dropped: their windows leave the record of %d frames" % ((~ok).sum(), len(t), F))
+        trig = [t[ok].astype(np.int32)]
+    elif "net_ens_traces" in run.extra:
+        trig = waves.triggers(run.extra["net_ens_traces"], F=F, **win)
+    else:
+        print("Waves: nothing read: there are no cells, so no ensembles")
+        return
+    px = dict(what="dff", half=args.detrend_half, q=args.detrend_q, floor=args.dff_floor, gain=args.dff_gain)
+    w = waves.extract(run.body, trig=trig, keep=args.waves_keep, **px, **par)
+    run.extra.update(wave_triggers=w["triggers"], wave_trigger_ens=w["trigger_ens"], wave_lat_mean=w["lat_mean"], wave_lat_sd=w["lat_sd"],
+                     wave_count=w["count"], wave_nodes=w["nodes"], wave_velocity=w["velocity"], wave_speed=w["speed"],
+                     wave_origin=w["origin"],
+                     wave_params=np.array([par[k] for k in ("pre", "lead", "post", "b", "min_rise", "step", "Rf")]
+                                          + [px[k] for k in ("half", "q", "floor", "gain")], np.float64))
+    if args.waves_keep:
+        run.extra.update(wave_lat=w["lat"], wave_rise=w["rise"], wave_why=w["why"], wave_fit=w["fit"])
+    for k, t in enumerate(trig):
+        print("Waves: ensemble %d: %d events, %.1f%% of their map pixels valid, origin (%d, %d), median speed %.3g px/frame" % (
+            k, len(t), 100.0 * w["valid"][k], w["origin"][k, 0], w["origin"][k, 1], w["speed"][k]))
+    if args.waves_map is not None:
+        best = int(np.argmax((w["count"] > 0).sum((1, 2)))) if len(trig) else -1
+        waves.colour_map(w["lat_mean"][best] if best >= 0 else np.full(w["gray"].shape, np.nan), w["gray"], args.waves_map)
+        print("Wave map: %s" % args.waves_map)
+
+
 def stage_record_end(run, args):
     """What --strain and --cells-video are handed of the cells; then the kept record is freed and the registered video closed."""
     e, n = run.e, len(run.inside)
@@ -898,6 +1020,7 @@ STAGES = (
     stage_cells,            # after the search: it needs the points, and reuses the cells of --find-more
     stage_events,           # after the cells: their dF/F; before the network (ev_*, net_r_events, then net_*)
     stage_network,          # after the cells and the events
+    stage_waves,            # after the network: the ensembles' traces give the triggers; the last reader of the kept record
     stage_record_end,       # after the last reader of the kept record: body_rec_end frees it; the readout is done with its writer
     stage_smooth,           # after the record is freed: the smoother's device memory; before what draws at Xs
     stage_cells_video,      # after the smoother: drawn at Xs with --smooth
